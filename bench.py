@@ -11,7 +11,7 @@ the build's seeded "live" generator (tests/weights.py: every parameter and buffe
 golden vectors of tests/golden/model_vitl1024.npz were captured with).  N > 1: one process per GPU, the batch is
 sharded (weak scaling: 2 images per rank, nothing shared on the data path) and every step ends with the pipeline's ONE
 exchange: an RCCL all-gather of the per-rank logits.  The step is the same at every N (at N=1 the gather is
-the identity), so per-N values are comparable.  `--no-head` times the encoder forward alone; the default run also
+the identity), so per-N values are comparable.  `--no-head` times the encoder forward alone; a `--full` run also
 reports it as `encoder_only`.
 
 `--gpus N` with no WORLD_SIZE in the environment: this process starts the N ranks itself (one child per GPU, RANK /
@@ -19,14 +19,23 @@ LOCAL_RANK / WORLD_SIZE / MASTER_* set, reference launch pattern segmentation/di
 call and relays rank 0's JSON line.  Under an existing WORLD_SIZE (torch.distributed.run) it is one of the ranks.
 
 Rank 0 prints ONE JSON line; `value` is the whole-job images/s (max-over-ranks time, barrier + synchronize on both
-sides of exactly K steps).
+sides of exactly K steps), `ms_per_step` the milliseconds of one of those K steps.
 
-What is timed is what is verified (`verified` object, checked OUTSIDE the timed region on every rank):
+A plain run does only what `value` needs: set-up (weights, first forward, graph capture, the chain probe, the attention logit guard's
+re-routing), W warm-up steps, the K timed steps, the result line.  `--full` adds every object listed below (the verification, the extra timed
+legs, the roofline and counter figures, the CPU baseline); the objects a run did not compute are null.
+
+`--dump-outputs DIR` writes, after the timed steps, what the timed path returned in its LAST step as DIR/<name>.npy (float32): `logits` (rank 0:
+the all-gathered logits at N > 1), or with `--no-head` the four maps `f1`..`f4`.  An array whose share of the 64 MB budget is too small is written as
+`<name>_sample.npy`: the values at a fixed seeded set of flat indices (tests/configs.probe_index, seed 7 + its position).  Weights and inputs are
+seeded, so the same arguments give the same inputs on every run.
+
+What is timed is what is verified (`--full`: `verified` object, checked OUTSIDE the timed region on every rank):
   * the HIP-graph replay of the step returns, bit for bit, what the eager launch sequence returns;
   * with the golden input of tests/golden/model_vitl1024.npz copied into image 0 of the graph's input buffer, the
     REPLAYED graph's f1..f4 match the reference's golden probes within the 1e-3 gate.
 
-Extra objects:
+Extra objects (`--full`):
   roofline     -- the dominant kernel family (the split3 GEMM: gemm_v2_kernel / gemm_split3_kernel): algorithmic FLOPs
                   (2*M*N*K per launch, NOT counting the 3x split products) / HIP-event time of those launches,
                   measured live in a single-stream profiled pass of one step right after the timed region (events on
@@ -88,14 +97,44 @@ def parse():
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--set", action="append", default=[], metavar="ATTR=VALUE",
                     help="set an attribute of the backbone before its first forward (A/B runs: --set fold_adapter_ln=False --set 'h8_sites=(\"vit\",)'); the value is a Python literal")
-    ap.add_argument("--no-extras", action="store_true", help="skip the eager_plugin_api / config4_frame / vith1024 lines of the default single-GPU run")
+    ap.add_argument("--no-extras", action="store_true", help="skip the eager_plugin_api / config4_frame / vith1024 lines of the --full single-GPU run")
     ap.add_argument("--no-verify", action="store_true", help="skip the untimed graph-vs-eager / golden-probe checks")
     ap.add_argument("--default-init", action="store_true", help="A/B aid: default-init weights instead of the seeded live generator")
     ap.add_argument("--no-head", action="store_true", help="time the encoder forward only (no decode head, no all-gather)")
     ap.add_argument("--chains", type=int, default=int(os.environ.get("MMSA_CHAINS", "2")),
                     help="the step's batch as this many independent sub-batch chains on concurrent HIP streams (mmsa.Chains); 1 = one chain")
     ap.add_argument("--force-chains", action="store_true", help="skip the untimed probe that falls back to one chain when the chains are slower on this machine")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: verification, encoder-only / worst-case / eager / frame / ViT-H legs, replay statistics, "
+                         "attention guard report, roofline and counter figures, CPU baseline (the --no-* switches above select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path returned in its last step as DIR/<name>.npy (float32, <= 64 MB in all)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not a.full:
+        a.no_verify = a.no_roofline = a.no_cpu_baseline = a.no_extras = True
+    return a
+
+
+DUMP_BYTES = 64 * 10**6
+
+
+def dump_outputs(d, outs):
+    """`outs`: name -> tensor, what a caller of the timed path receives.  Written as d/<name>.npy in float32 (float64 stays float64); an array larger than
+    its share of DUMP_BYTES is written as d/<name>_sample.npy, its values at probe_index(numel, share, seed=7 + position) of the flattened array."""
+    import numpy as np
+    import torch
+    from tests.configs import probe_index
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_BYTES // max(len(outs), 1)
+    for i, (name, t) in enumerate(outs.items()):
+        t = t.detach()
+        t = t if t.dtype == torch.float64 else t.float()
+        if t.numel() * t.element_size() <= share:
+            np.save(os.path.join(d, f"{name}.npy"), t.cpu().numpy())
+        else:
+            pi = probe_index(t.numel(), share // t.element_size(), seed=7 + i).to(t.device)
+            np.save(os.path.join(d, f"{name}_sample.npy"), t.flatten()[pi].cpu().numpy())
 
 
 def spawn_ranks(n):
@@ -400,6 +439,7 @@ def main():
     # collected (host-side) one step later, the last one by `drain` inside the timed region
     gather = LogitsGather() if (head is not None or STUB) and use_dist else None
     pending = [None]
+    last = [None]                           # what replay() returned in the latest step: a fresh tensor when eager (graphs and chains write local_out / their maps)
     overlap = {"next_step_enqueued_before_previous_gather_was_collected": 0, "collected": 0}
 
     def collect():
@@ -410,6 +450,7 @@ def main():
 
     def run():
         out_ = replay()                     # chains: both sub-batch chains of the step, joined into this stream (a step ends before the next starts)
+        last[0] = out_
         if gather is not None:
             if pending[0] is not None:      # step k is enqueued (or, in the stub, has run): only now is step k - 1's gather waited for
                 overlap["next_step_enqueued_before_previous_gather_was_collected"] += 1
@@ -430,8 +471,17 @@ def main():
     dt = timed(run, collect)
     imgs = (stub_global if stub_global is not None else a.batch * world) * a.steps
     value = imgs / dt
+    if a.dump_outputs and rank == 0:
+        if gather is not None:
+            outs = {"logits": gathered[0]}        # collected by the drain inside the timed region
+        elif head is not None or STUB:
+            outs = {"logits": last[0] if torch.is_tensor(last[0]) else local_out}
+        else:
+            maps = feats[0] if not graphed else graph_feats if chains is None else [torch.cat([chains.feats[c][k] for c in range(nch)], 0) for k in range(4)]
+            outs = {f"f{k + 1}": maps[k] for k in range(4)}
+        dump_outputs(a.dump_outputs, outs)
     replay_ms = None
-    if not STUB:   # median of >= 20 iterations, each between its own events (untimed by the contract's clock)
+    if a.full and not STUB:   # median of >= 20 iterations, each between its own events (untimed by the contract's clock)
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(max(20, a.steps))]
         for e0, e1 in evs:
             e0.record()
@@ -444,7 +494,7 @@ def main():
                      "images_per_s_at_median": round(a.batch * world / (statistics.median(ts) * 1e-3), 3),
                      "note": "this rank's step (+ the all-gather at N > 1) replayed after the timed region, one event pair per replay"}
     guard = None
-    if model is not None:
+    if a.full and model is not None:
         still = model.check_attention_guard(reroute=False)
         ml = [lg for _, lg in model.attention_modes()]
         guard = {"threshold_fp16": model.ATTN_F16_MAX_LOGIT, "max_abs_logit": round(max(ml), 3) if ml else None,
@@ -538,7 +588,7 @@ def main():
                 torch.cuda.synchronize()
 
     encoder_only = None
-    if head is not None and world == 1:
+    if a.full and head is not None and world == 1:
         if chains is not None:
             ereplay = mmsa.Chains(model, None, n=nch).capture(x).replay
         else:

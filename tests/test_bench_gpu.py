@@ -11,9 +11,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 
 
-def _bench(*args):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "vitb512", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-roofline", *args], capture_output=True, text=True, timeout=600)
+def _bench(*args, full=True):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "vitb512", "--steps", "2", "--warmup", "1"]
+                       + (["--full", "--no-cpu-baseline", "--no-roofline"] if full else []) + list(args), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
     return json.loads(line)
@@ -40,7 +40,8 @@ def test_bench_roofline_families_and_pipelined_gather_fields():
     """Round 6: the GEMM roofline is reported in two families -- launches that can be matrix-bound (`roofline.frac`) and launches below 100 FLOP per compulsory
     byte scored against HBM (`roofline.hbm_gemms`) -- and `roofline.all_gemm_launches` keeps the definition of rounds 1-5; their launch counts, FLOPs and kernel
     times add up.  Single rank: no collective, no overlap record."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "vitb512", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "vitb512", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
+                        "--no-extras"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -52,6 +53,22 @@ def test_bench_roofline_families_and_pipelined_gather_fields():
     assert abs(rf["kernel_ms_per_step"] + rf["hbm_gemms"]["kernel_ms_per_step"] - al["kernel_ms_per_step"]) <= 0.01
     assert rf["frac"] >= al["frac"] and 0.0 < rf["hbm_gemms"]["frac"] < 1.0
     assert d["config"]["collective_overlap"] is None and d["config"]["host_threads_per_rank"] is None
+
+
+def test_bench_plain_run_dumps_the_logits_of_its_last_timed_step(tmp_path):
+    """Without --full the benchmark times the step and computes nothing else; --dump-outputs writes the logits the last timed step returned.  The
+    replayed graph and the eager launch sequence write the same logits bit for bit."""
+    import numpy as np
+    runs = {"graph": _bench("--dump-outputs", str(tmp_path / "graph"), full=False),
+            "eager": _bench("--no-graph", "--chains", "1", "--dump-outputs", str(tmp_path / "eager"), full=False)}
+    for d in runs.values():
+        assert d["steps"] == 2 and d["ms_per_step"] > 0 and abs(d["value"] - 2 / (d["ms_per_step"] * 1e-3)) < 1e-2 * d["value"]
+        assert all(d[k] is None for k in ("verified", "encoder_only", "replay_ms", "attention_guard", "roofline", "hbm_kernels", "cpu_baseline",
+                                          "worst_case_precision", "eager_plugin_api", "config4_frame", "vith1024"))
+    assert runs["graph"]["config"]["hip_graph"] is True and runs["eager"]["config"]["hip_graph"] is False
+    g, e = np.load(tmp_path / "graph" / "logits.npy"), np.load(tmp_path / "eager" / "logits.npy")
+    assert g.shape == (2, 25, 128, 128) and g.dtype == np.float32 and np.isfinite(g).all() and g.std() > 0
+    assert np.array_equal(g, e)
 
 
 def _gather_cuda_worker(rk, ws, port, q):

@@ -337,6 +337,23 @@ def test_bench_rank_body_gloo_world8_with_ragged_shards():
     assert line["config"]["host_threads_per_rank"] == max(1, (os.cpu_count() or 1) // 8)
 
 
+def test_bench_stub_dumps_the_logits_of_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: rank 0 writes the logits the timed path returned in its last step -- one rank's own, and at N > 1 the all-gathered
+    logits of every rank in rank order -- as DIR/logits.npy in float32; a plain run (no --full) computes none of the extra objects."""
+    import json
+    import numpy as np
+    for n in (1, 2):
+        d = tmp_path / f"world{n}"
+        r = _run_bench_stub({}, args=("--gpus", str(n), "--steps", "2", "--warmup", "1", "--dump-outputs", str(d)))
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["replay_ms"] is None and line["encoder_only"] is None
+        got = np.load(d / "logits.npy")
+        assert got.dtype == np.float32 and got.shape == (2 * n, 25, 8, 8)
+        assert got[:, 0, 0, 0].tolist() == [float(r_) for r_ in range(n) for _ in range(2)]
+        assert os.listdir(d) == ["logits.npy"]
+
+
 def test_bench_parent_stops_the_job_when_a_rank_dies():
     """A rank that exits at start-up must not leave the parent waiting for rank 0's rendezvous timeout."""
     import time

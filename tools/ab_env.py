@@ -29,7 +29,7 @@ for a in args:
 best = {}
 for rnd in range(rounds):
     for name, env, extra in variants:
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "3", "--no-cpu-baseline", "--no-roofline", "--no-extras"] + extra
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "3", "--full", "--no-cpu-baseline", "--no-roofline", "--no-extras"] + extra
         if not verify:
             cmd.append("--no-verify")
         r = subprocess.run(cmd, capture_output=True, text=True, env=dict(os.environ, **env))

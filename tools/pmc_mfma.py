@@ -9,7 +9,7 @@ tag = sys.argv[1]
 
 
 def load(sub, names):
-    d = f"gpurun_out/pmc_{tag}_mfma_{sub}"
+    d = _os.path.join(_os.environ.get("MMSA_OUT_DIR", "results"), f"pmc_{tag}_mfma_{sub}")   # where tools/pmc_mfma.sh wrote the passes
     dur = {}
     for f in glob.glob(f"{d}/**/*kernel_trace.csv", recursive=True):
         for r in csv.DictReader(open(f)):

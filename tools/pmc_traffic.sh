@@ -4,8 +4,9 @@
 # profiles/<tag>_hbm_kernels.json).  Run on the GPU box:  bash tools/pmc_traffic.sh <tag>
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 TAG=${1:-r01}
+O=${MMSA_OUT_DIR:-results}
 for C in FETCH_SIZE WRITE_SIZE; do
-  timeout 500 rocprofv3 --pmc $C --kernel-trace --output-format csv -d gpurun_out/pmc_${TAG}_$C -- python bench.py --steps 1 --warmup 1 --no-graph --no-verify --no-cpu-baseline --no-roofline --no-head > /dev/null 2>&1
+  timeout 500 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/pmc_${TAG}_$C -- python bench.py --steps 1 --warmup 1 --full --no-graph --no-verify --no-cpu-baseline --no-roofline --no-head > /dev/null 2>&1
   echo "pass $C rc=$?"
 done
 python tools/pmc_traffic.py $TAG
