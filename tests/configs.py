@@ -57,6 +57,12 @@ CONFIGS = {
     "tiny256_wide": dict(kwargs=dict(_TINY, img_size=256), batch=1, seed=2, in_seed=6, large_mag=dict(ln2=(1, 5), ln1=(2, 9), gelu=(3, 17))),
     "vitl1024_wide": dict(kwargs=_VITL, batch=1, seed=5, in_seed=9, large_mag=dict(ln2=(7, 100), ln1=(12, 333), gelu=(20, 1234))),
     "vith1024": dict(kwargs=_VITH, batch=1, seed=17, in_seed=18),
+    # a padded head width at test size: embed 320 / 4 heads -> head_dim 80, run zero-padded to 96 per head like ViT-H; MSDA heads of 40
+    # channels (deform_num_heads 4, deform_ratio 0.5).  Probes-only goldens (no `tiny` prefix); the second entry has the q / k rows of
+    # every qkv projection x 3 (tests/weights.py peaky_attention): the guard moves its blocks to fp16 hi/lo pairs
+    "hd80_256": dict(kwargs=dict(_TINY, img_size=256, embed_dim=320, num_heads=4, deform_num_heads=4), batch=1, seed=25, in_seed=26),
+    "hd80_256_peaky": dict(kwargs=dict(_TINY, img_size=256, embed_dim=320, num_heads=4, deform_num_heads=4), batch=1, seed=25, in_seed=26,
+                           qk_scale=3.0),
     "vitl800": dict(kwargs=_VITL800, batch=1, seed=19, in_seed=20, type="SAMAdapterbimodalMixModNewInTwinConvNEWwithcp"),
 }
 
