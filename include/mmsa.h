@@ -39,6 +39,11 @@
  *                   (the factor 1.09375 makes up for q(hi) being the TRUNCATED top byte of hi in this format: csrc/common.h MMSA_H8C_LO_COMP).
  *                   Every `ld*` of h8c planes is the row-PAIR stride; activations and weights share the layout.  1.5 cache lines per row and
  *                   64 k-values where MMSA_FMT_H8 has 2: the GEMM's L2 -> LDS stream is what bounds its k loop (csrc/gemm_h8c.hip).
+ *      MMSA_FMT_W8  fp8 WEIGHTS (the opt-in fp8 weights of the ViT-block GEMMs): W[n, k] = 2^e_n * e4m3(code[n, k]) with OCP e4m3fn codes and one exponent
+ *                   e_n in [-15, 7] per row (every such value is exact in fp16).  A [N, K] weight (K % 128 == 0) is N rows of K code bytes -- one 128-byte
+ *                   line per 128 k, a line's 64-k half c = 4 groups g of 16 bytes = the codes of k = 64c + 8g .. +7, then of k = 64c + 32 + 8g .. +7 (the
+ *                   order of the h8c lo bytes) -- followed by the N exponents as signed bytes, zero padded to a multiple of 128.  A W operand only: the
+ *                   A operand of such a GEMM is MMSA_FMT_H8C planes (mmsa_gemm_split3 with fmt = MMSA_FMT_W8; csrc/gemm_h8c_w8.hip).
  *    `mmsa_split_planes` converts fp32; producer kernels emit the format of their `*_fmt` argument (h8c: mmsa_gemm_split3, mmsa_layernorm_rows,
  *    the three attention entries, mmsa_msda_fused, mmsa_split_planes).
  *  - Clamp watch (round 5).  The fp16-based formats clamp what they cannot hold (h8 / h8c: |x| > 57344, f3: |x| > 65504; bf16 hi/lo planes have fp32's
@@ -88,7 +93,7 @@ enum { MMSA_ACT_NONE = 0, MMSA_ACT_GELU = 1, MMSA_ACT_RELU = 2, MMSA_ACT_RELU6 =
 enum { MMSA_DT_F32 = 0, MMSA_DT_F16 = 1, MMSA_DT_F64 = 2 };
 
 /* operand-plane formats (see Conventions) */
-enum { MMSA_FMT_B3 = 0, MMSA_FMT_H8 = 1, MMSA_FMT_H8C = 2, MMSA_FMT_F3 = 3 };
+enum { MMSA_FMT_B3 = 0, MMSA_FMT_H8 = 1, MMSA_FMT_H8C = 2, MMSA_FMT_F3 = 3, MMSA_FMT_W8 = 4 /* weights only: see Conventions */ };
 
 /* --- reference native ops -----------------------------------------------------------------------------------
  * ms_deform_attn_forward (vision.cpp:14 -> ms_deform_attn.h:20-39 -> cuda/ms_deform_attn_cuda.cu:20-80).
@@ -144,7 +149,7 @@ int mmsa_msda_fused_planes(const uint16_t* value_planes, long ldvp, int lo_bytes
  * producing kernel; lda/strideA then count uint16 elements, lda >= 2K).  W: interleaved planes, row stride 2K.
  * The result goes to fp32 `C`, to planes `Cp` (row stride ldcp >= 2*N rounded up to 64), or both.
  * fmt = format of the A and W planes (MMSA_FMT_H8 / MMSA_FMT_H8C: A must come as planes, K % 64 == 0, any M -- rows beyond M are clamped on the way in and masked on the way out; lda / ldcp of h8c planes =
- * row-pair strides >= 3 K / 3 pad64(N)); cp_fmt = format written to `Cp`:
+ * row-pair strides >= 3 K / 3 pad64(N); MMSA_FMT_W8: A as MMSA_FMT_H8C planes, W = a W8 weight, K % 128 == 0, batch 1); cp_fmt = format written to `Cp`:
  * bits 0..7 MMSA_FMT_*, bits 8.. = split / 32 -- columns >= split (a multiple of 32; 0 = none) are written as MMSA_FMT_H8 planes
  * whatever the base format (the qkv projection: q and k as f3 planes, v with an fp16 hi part for the attention kernels' v_fmt = 1).
  * max_grid > 0 caps the number of persistent workgroups (a caller running independent chains on concurrent streams gives each

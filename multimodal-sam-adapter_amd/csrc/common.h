@@ -347,6 +347,14 @@ __device__ __forceinline__ void store_planes4_any(unsigned short* base, long ld,
 }
 #define MMSA_PAD64(x_) (((x_) + 63) & ~63)
 
+// ---- "W8" weights (the opt-in fp8 weights of the ViT-block GEMMs, csrc/gemm_h8c_w8.hip): W[n, k] = 2^e_n * e4m3(code[n, k]), OCP e4m3fn codes, one exponent
+// e_n in [MMSA_W8_EMIN, MMSA_W8_EMAX] per row: every such value is exact in fp16 (smallest 2^-9 * 2^-15 = 2^-24 = fp16's granularity, largest 448 * 2^7 = 57344),
+// so the GEMM converts a code to the fp16 hi operand of the h8 product exactly and its lo part is zero.  Row n of a [N, K] weight (K % 128 == 0) is K bytes:
+// k = 64c + 32t + 8g + e at byte 64c + 16g + 8t + e (the h8c lo-byte order: a lane's 16 bytes of a 64-k chunk are contiguous); the N exponents follow the N rows
+// as signed bytes, zero padded to a multiple of 128 (a workgroup reads the 128 of its output tile).  (enum MMSA_FMT_W8 = 4: include/mmsa.h)
+#define MMSA_W8_EMIN (-15)
+#define MMSA_W8_EMAX 7
+
 // ---- clamp watch (round 5, VERDICT r04 "the h8 / h8c clamp is silent").  The fp16-based operand formats clamp on the way in (h8 / h8c: +-57344, f3:
 // +-65504; bf16 hi/lo planes have fp32's range and never clamp).  The kernels that CONVERT unbounded fp32 values to those formats -- the GEMM epilogues,
 // LayerNorm, split_planes, the deformable-attention gather, the depthwise convs -- take an optional device float `clamp_max` (NULL = none): a lane keeps

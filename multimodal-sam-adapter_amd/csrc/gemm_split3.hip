@@ -353,11 +353,12 @@ extern "C" int mmsa_gemm_split3(const float* A, const unsigned short* Ap, long l
   MMSA_CHECK_ARG(!(rs_out && rn_mr), "gemm_split3: a GEMM either writes row statistics or normalises by them");
   const bool extras = rs_out || rn_mr;
   MMSA_CHECK_ARG(!extras || (ap && M >= 128), "gemm_split3: row statistics / row normalisation need activation planes and M >= 128");
-  MMSA_CHECK_ARG(fmt >= MMSA_FMT_B3 && fmt <= MMSA_FMT_F3 && cp_fmt >= 0 && MMSA_CP_BASE(cp_fmt) >= MMSA_FMT_B3 && MMSA_CP_BASE(cp_fmt) <= MMSA_FMT_F3, "gemm_split3: bad plane format %d / %d", fmt, cp_fmt);
+  MMSA_CHECK_ARG(fmt >= MMSA_FMT_B3 && fmt <= MMSA_FMT_W8 && cp_fmt >= 0 && MMSA_CP_BASE(cp_fmt) >= MMSA_FMT_B3 && MMSA_CP_BASE(cp_fmt) <= MMSA_FMT_F3, "gemm_split3: bad plane format %d / %d", fmt, cp_fmt);
   MMSA_CHECK_ARG(MMSA_CP_SPLIT(cp_fmt) == 0 || (out_mode == 0 && MMSA_CP_SPLIT(cp_fmt) < N && MMSA_CP_BASE(cp_fmt) != MMSA_FMT_H8C), "gemm_split3: the output-format split %d needs a plain [M, N] bf16 hi/lo planes output with N=%d beyond it", MMSA_CP_SPLIT(cp_fmt), N);
   MMSA_CHECK_ARG(fmt == MMSA_FMT_B3 || fmt == MMSA_FMT_F3 || (ap && K % 64 == 0), "gemm_split3: h8 / h8c operands need A planes and K %% 64 == 0 (K=%d)", K);
   MMSA_CHECK_ARG(fmt != MMSA_FMT_F3 || ap || !Cp, "gemm_split3: f3 weights with an fp32 A write fp32 outputs only");
-  const bool h8c = fmt == MMSA_FMT_H8C, cp_h8c = MMSA_CP_BASE(cp_fmt) == MMSA_FMT_H8C;
+  MMSA_CHECK_ARG(fmt != MMSA_FMT_W8 || (K % 128 == 0 && batch == 1), "gemm_split3: W8 weights need h8c A planes, K %% 128 == 0 and one batch (K=%d, batch=%d)", K, batch);
+  const bool h8c = fmt == MMSA_FMT_H8C || fmt == MMSA_FMT_W8, cp_h8c = MMSA_CP_BASE(cp_fmt) == MMSA_FMT_H8C;   // (W8: the A side is h8c planes)
   MMSA_CHECK_ARG((A || Ap) && Wp && (C || Cp), "gemm_split3: null pointer");
   MMSA_CHECK_ARG(!(A && Ap), "gemm_split3: pass either fp32 A or A planes, not both");
   MMSA_CHECK_ARG(M > 0 && N > 0 && K > 0 && batch > 0, "gemm_split3: bad shape M=%d N=%d K=%d batch=%d", M, N, K, batch);

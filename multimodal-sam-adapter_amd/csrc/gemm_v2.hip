@@ -538,6 +538,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_v2_kernel(GemmV
 }
 
 int mmsa_gemm_h8c_dispatch(const GemmV2Args& a, int grid, bool gen, int act, hipStream_t stream);   // gemm_h8c.hip
+int mmsa_gemm_h8c_w8_dispatch(const GemmV2Args& a, int grid, bool gen, int act, hipStream_t stream);   // gemm_h8c_w8.hip (h8c A x W8 fp8 weights)
 int mmsa_gemm_stream_try(const unsigned short* Ap, long lda, const unsigned short* Wp, const float* bias, const float* colscale, const float* resid, long ldr, float beta,
                          float* C, long ldc, unsigned short* Cp, long ldcp, int M, int N, int K, int batch, int act, float alpha, int out_mode, int resid_mod,
                          int fmt, int cp_fmt, int max_grid, const float* rs_out, const float* rn_mr, int flavour, float* clamp_max, hipStream_t stream);   // gemm_stream.hip
@@ -574,8 +575,10 @@ int mmsa_gemm_v2_launch(const unsigned short* Ap, long lda, long strideA,
   a.rs_out = rs_out; a.rs_strips = N >> 6; a.rn_mr = rn_mr; a.rn_cs = rn_cs;
   a.Ap = Ap; a.lda = lda; a.strideA = strideA;
   a.Wp = Wp; a.strideW = strideW;
-  const bool h8c = fmt == MMSA_FMT_H8C;
-  a.ldw = h8c ? 3L * K : 2L * K;   // dense packed weights (h8c: row-PAIR stride)
+  const bool w8 = fmt == MMSA_FMT_W8;             // h8c activation planes x W8 weights (gemm_h8c_w8.hip)
+  const bool h8c = fmt == MMSA_FMT_H8C || w8;     // (the A side: h8c planes either way)
+  MMSA_CHECK_ARG(!w8 || ((K & 127) == 0 && batch == 1), "gemm(v2): W8 weights need K %% 128 == 0 and one batch (K=%d, batch=%d)", K, batch);
+  a.ldw = w8 ? K / 2 : h8c ? 3L * K : 2L * K;   // dense packed weights (h8c: row-PAIR stride; W8: K code bytes per row)
   a.bias = bias; a.strideBias = strideBias; a.colscale = colscale;
   a.resid = resid; a.ldr = ldr; a.strideR = strideR; a.resid_mod = resid_mod; a.beta = beta;
   a.C = C; a.ldc = C ? ldc : 0; a.strideC = strideC;
@@ -621,7 +624,7 @@ int mmsa_gemm_v2_launch(const unsigned short* Ap, long lda, long strideA,
                               // So: only when forced (`flavour` = 4: the bit-identity test)
 #endif
   bool h8c4 = false;
-  if (h8c && out_mode == 0 && resid_mod <= 0 && act == ACT_NONE && flavour != 8 && M >= 128) {
+  if (h8c && !w8 && out_mode == 0 && resid_mod <= 0 && act == ACT_NONE && flavour != 8 && M >= 128) {
     const long t256 = (long)cdiv(M, 256) * cdiv(N, V2_BN) * batch;
     h8c4 = flavour == 4 || (t256 <= (long)cus && K <= MMSA_KNOB("MMSA_GEMM_H8C4_MAXK", 1024) && MMSA_KNOB("MMSA_GEMM_H8C4", MMSA_H8C4_DEFAULT) != 0);
   }
@@ -682,6 +685,7 @@ int mmsa_gemm_v2_launch(const unsigned short* Ap, long lda, long strideA,
     a.stagger = h8c ? (K >> 6) * 3800 + 16000 : (K >> 5) * (fmt == MMSA_FMT_H8 ? 1700 : 1900) + 16000;
   }
   const bool gen = out_mode != 0 || resid_mod > 0;
+  if (w8) return mmsa_gemm_h8c_w8_dispatch(a, grid, gen, act, stream);
   if (h8c4) return mmsa_gemm_h8c4_dispatch(a, grid, stream);
   if (h8c) return mmsa_gemm_h8c_dispatch(a, grid, gen, act, stream);
   const bool pp = MMSA_KNOB("MMSA_GEMM_PP", 1) != 0;   // 0 (debug-knob builds): every wave in phase (A/B timing)

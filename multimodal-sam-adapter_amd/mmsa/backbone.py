@@ -235,6 +235,16 @@ class SAMAdapterbimodalMixModNewInTwinConvNEW(nn.Module):
     # interaction indices, sticky like the blocks' modes, stored with the packed file).  `inter_follow_blocks = False`: the behaviour of rounds 3-5.
     inter_follow_blocks = True
 
+    # fp8 weights (opt-in; BASELINE.json configs[4]'s "fp8 MFMA weights"): the four GEMMs of every ViT block (qkv, proj, lin1, lin2) multiply by
+    # W_eff = 2^e_n * e4m3(code) of the weight the kernel sees (after the head padding and the LayerNorm fold): per output row n the smallest exponent in
+    # [-15, 7] that holds the row, OCP e4m3fn codes rounded to nearest even (ops.fp8_quantize), packed as W8 weights -- 1 byte per element where h8c
+    # planes take 3 -- against the usual h8c activation planes (csrc/gemm_h8c_w8.hip).  Everything derived from the weights (the folded bias, the fold's
+    # column sums, the pair repacks of the attention guard and of the wide-range state) is computed from W_eff: the model computes with the same weights in
+    # every state, and `effective_state_dict()` returns them in the reference's parameterisation.  Needs the blocks on h8c planes ("vit" among `h8_sites`,
+    # `h8c` on, every contraction >= 512 and a multiple of 128): otherwise the pack raises ValueError.  Interaction, up-conv, ConvNeXt, neck and head
+    # weights keep their formats.
+    fp8_weights = False
+
     def _inter_pair_set(self):
         return set(getattr(self, "_inter_pairs", ()) or ())
 
@@ -287,22 +297,74 @@ class SAMAdapterbimodalMixModNewInTwinConvNEW(nn.Module):
             out[:, :, :hd_true] = v
             return out.reshape(groups * heads_ * hd_, *w.shape[1:]).contiguous()
 
+        fp8 = self._fp8_wanted()   # (fmt = FMT_W8, or a pair format in the guard's / wide-range state's repacks: the same effective weights)
+
         def planes(w2d):
+            if fmt == ops.FMT_W8:
+                return ops.w8_planes(w2d.contiguous())
             return ops.split_planes(w2d.contiguous(), None, fmt=fmt, weight=fmt == ops.FMT_H8)
 
         def folded(w, bias, lnw, lnb):
-            """(planes of W o lnw, column sums of those planes as the kernel will read them, W lnb + bias)"""
-            pl = planes(w * lnw[None, :])
+            """(planes of W o lnw, column sums of those planes as the kernel will read them, W lnb + bias); fp8 weights: of the effective weights"""
+            wk, w = self._fp8_effective(w, lnw) if fp8 else (w * lnw[None, :], w)
+            pl = planes(wk)
             cs = ops.planes_to_float(pl, cols=w.shape[1])[: w.shape[0]].double().sum(1).float().contiguous()
             return pl, cs, (w.double() @ lnb.double()).float().add_(bias).contiguous()
+
+        def plain(w):
+            return planes(self._fp8_effective(w)[0] if fp8 else w)
         b = f"blocks.{i}."
         g = lambda k: sd[b + k].detach().to(dev, torch.float32)   # noqa: E731
         qkv_w, qkv_bias = pad_head_rows(g("attn.qkv.weight"), 3), pad_head_rows(g("attn.qkv.bias"), 3)
         proj_w = pad_head_rows(g("attn.proj.weight").t(), 1).t().contiguous()    # zero COLUMNS for the pad channels
-        out = dict(qkv=planes(qkv_w), proj=planes(proj_w), lin1=planes(g("mlp.lin1.weight")), lin2=planes(g("mlp.lin2.weight")))
+        skip = fp8 and fold   # (fp8: the unfolded qkv / lin1 would be quantized only to be replaced)
+        out = dict(qkv=None if skip else plain(qkv_w), proj=plain(proj_w), lin1=None if skip else plain(g("mlp.lin1.weight")), lin2=plain(g("mlp.lin2.weight")))
         if fold:   # the consumers' weights carry their LayerNorm (the unfolded planes are not kept: the fold is all or nothing per model)
             out["qkv"], out["qkv_cs"], out["qkv_bf"] = folded(qkv_w, qkv_bias, g("norm1.weight"), g("norm1.bias"))
             out["lin1"], out["lin1_cs"], out["lin1_bf"] = folded(g("mlp.lin1.weight"), g("mlp.lin1.bias"), g("norm2.weight"), g("norm2.bias"))
+        return out
+
+    def _fp8_wanted(self):
+        return bool(getattr(self, "fp8_weights", False))
+
+    def _fp8_check(self, D, Da, hidden):
+        """fp8_weights needs the ViT-block GEMMs on h8c planes: raise ValueError (at pack time) where they would not run there."""
+        sites = tuple(getattr(self, "h8_sites", self.H8_DEFAULT))   # (the configured sites: the wide-range state keeps the fp8 values on bf16 pairs)
+        why = ("'vit' is not among h8_sites" if "vit" not in sites else "h8c is off" if not self._h8c_wanted()
+               else f"a contraction is shorter than 512 (embed {D}, attention width {Da}, MLP hidden {hidden})" if min(D, Da, hidden) < 512
+               else f"a contraction is not a multiple of 128 (embed {D}, attention width {Da}, MLP hidden {hidden})" if (D % 128 or Da % 128 or hidden % 128)
+               else None)
+        if why:
+            raise ValueError(f"mmsa: fp8_weights needs the ViT-block GEMMs on h8c planes, but {why}")
+
+    @staticmethod
+    def _fp8_effective(w, lnw=None):
+        """fp8 weights: (what the kernel multiplies by -- 2^e e4m3(W o lnw), exact in fp32 --, the same in the reference's parameterisation: that / lnw,
+        and W itself in a column whose LayerNorm weight is 0, which then contributes through the LayerNorm bias alone -- consistently in the folded bias)."""
+        if lnw is None:
+            q = ops.fp8_dequantize(*ops.fp8_quantize(w))
+            return q, q
+        q = ops.fp8_dequantize(*ops.fp8_quantize(w * lnw[None, :]))
+        nz = lnw[None, :] != 0
+        return q, torch.where(nz, q / torch.where(nz, lnw[None, :], torch.ones_like(lnw[None, :])), w)
+
+    @torch.no_grad()
+    def effective_state_dict(self):
+        """state_dict() with the weights this model actually multiplies by, in the reference's parameterisation: same keys, shapes and order; with
+        `fp8_weights` the four Linear weights of every ViT block hold their effective fp8 weights (deq(W o w) / w where the LayerNorm is folded), every
+        other tensor -- and state_dict() itself -- is untouched.  Loaded into the reference (or the oracle) it computes what this model computes."""
+        sd = self.state_dict()
+        out = type(sd)((k, v.detach().clone()) for k, v in sd.items())
+        if not self._fp8_wanted():
+            return out
+        fold = self._fold_ln_wanted()
+        dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        for i in range(self.cfg["depth"]):
+            b = f"blocks.{i}."
+            for key, ln in (("attn.qkv.weight", "norm1.weight"), ("attn.proj.weight", None), ("mlp.lin1.weight", "norm2.weight"), ("mlp.lin2.weight", None)):
+                w = sd[b + key].detach().to(dev, torch.float32)
+                lnw = sd[b + ln].detach().to(dev, torch.float32) if (fold and ln) else None
+                out[b + key] = self._fp8_effective(w, lnw)[1].to(sd[b + key].device, sd[b + key].dtype)
         return out
 
     def _pack_state_dict(self, dev):
@@ -430,6 +492,11 @@ class SAMAdapterbimodalMixModNewInTwinConvNEW(nn.Module):
         vfmt = self._pair_fmt()   # the hi/lo pair format of the ViT blocks (h8 off, or a block moved off fp16 attention): fp16 hi/lo pairs, like the attention kernels' own (bf16 pairs in the wide-range state)
         if "vit" in h8_sites and D % 64 == 0 and Da % 64 == 0 and hidden_ % 64 == 0:
             vfmt = ops.FMT_H8C if (min(D, Da, hidden_) >= 512 and self._h8c_wanted()) else ops.FMT_H8
+        pk["fp8_weights"] = self._fp8_wanted()
+        if pk["fp8_weights"]:
+            self._fp8_check(D, Da, hidden_)
+            if vfmt == ops.FMT_H8C:
+                vfmt = ops.FMT_W8   # (the wide-range state keeps its bf16 pairs, with the same effective weights)
         pk["vit_fmt"] = vfmt
         # LayerNorm fold (IE:396-421; LAB_NOTES.md 4.2): norm1 / norm2 of the ViT blocks live in their consumer GEMMs.  The producer of the
         # residual stream (proj, lin2, the injector's output projection) also writes the stream as planes and per-row strip sums; qkv / lin1
@@ -771,7 +838,8 @@ class SAMAdapterbimodalMixModNewInTwinConvNEW(nn.Module):
         x = x.contiguous().float()
         if (self._packed is None or self._packed.get("dev") != dev or tuple(self._packed.get("h8_sites", ())) != self._h8_sites()
                 or self._packed.get("h8c") != self._h8c_wanted() or self._packed.get("cnx_f16") != self._cnx_f16_wanted()
-                or bool(self._packed.get("wide", False)) != self._wide() or list(self._packed.get("inter_pairs", [])) != sorted(self._inter_pair_set())):
+                or bool(self._packed.get("wide", False)) != self._wide() or list(self._packed.get("inter_pairs", [])) != sorted(self._inter_pair_set())
+                or bool(self._packed.get("fp8_weights", False)) != self._fp8_wanted()):
             self._packed = self._pack(dev)
             self._packed["dev"] = dev
         if self._ws is None or self._ws.device != dev:
@@ -901,7 +969,7 @@ class SAMAdapterbimodalMixModNewInTwinConvNEW(nn.Module):
             self._injector(it["inj"], xs[i], xs[i + 1], cbuf, geo, B, T, Nc)   # (with the LayerNorm fold: also the producer of block idx[0]'s stream planes)
             for bi in range(idx[0], idx[-1] + 1):
                 self._block(pk["blocks"][bi], geo["rel"][bi], xs[i + 1], B, Hp, Wp, geo["relg"][bi],
-                            next_fmt=pk["blocks"][bi + 1]["qkv"].fmt if bi < idx[-1] else None)
+                            next_fmt=pk["blocks"][bi + 1]["qkv"].afmt if bi < idx[-1] else None)
             for j, ex in enumerate(it["ext"]):
                 self._extractor(ex, cbuf, xs[i + 1], geo, B, T, Nc, H, W, last=(i == n_inter - 1 and j == len(it["ext"]) - 1))
             if taps is not None:
@@ -967,7 +1035,7 @@ class SAMAdapterbimodalMixModNewInTwinConvNEW(nn.Module):
         # fp16 operands inside the attention kernels ("attnv" site) only where this block's logits are small enough: _attn_mode (on the
         # first forward it may also move this block's qkv GEMM to bf16 hi/lo operands)
         f16 = bp["qkv_bp16"] is not None and self._attn_mode(bp) == "f16"
-        vf = bp["qkv"].fmt   # operand format of this block's qkv GEMM: its producer wrote the stream planes / LayerNorm writes them in it
+        vf = bp["qkv"].afmt   # operand format of this block's qkv GEMM: its producer wrote the stream planes / LayerNorm writes them in it
         gw = self._packed["attn_guard"][bp["index"]:bp["index"] + 1]   # this block's logit guard word
         if fold:
             xp, rs = self._stream_planes(B * T, vf)
@@ -994,7 +1062,7 @@ class SAMAdapterbimodalMixModNewInTwinConvNEW(nn.Module):
         else:
             ops.gemm(n, bp["qkv"], bias=bp["qkv_bf"] if folded_w else bp["qkv_b"], out_planes=qkv)
         wsz = bp["ws"]
-        ao = ws.planes("blk_ao", B * T, Da, fmt=bp["proj"].fmt)
+        ao = ws.planes("blk_ao", B * T, Da, fmt=bp["proj"].afmt)
         if bp.get("relp") is not None:   # windowed block, head_dim 64: K/V-resident kernel with the rel-pos terms fused
             ops.window_attention(qkv, bias_p, bp["relp16"] if all16 else bp["relp"], ao, B, Hp, Wp, heads, hd, wsz, scale, max_logit=gw)
         elif relg is not None:           # global block on a 64-wide grid: flash kernel with the rel-pos terms fused
@@ -1004,7 +1072,7 @@ class SAMAdapterbimodalMixModNewInTwinConvNEW(nn.Module):
             rp = ws.get("blk_rp", B * heads * T, kk)
             ops.relpos_bias(qkv, rel[0], rel[1], rp, B, Hp, Wp, heads, hd, wsz)
             ops.attention(qkv, bias_p, rp, ao, B, Hp, Wp, heads, hd, wsz, scale, max_logit=gw)
-        vf = bp["lin1"].fmt              # the MLP's operand format (the qkv GEMM of a block with large logits runs on bf16 hi/lo: _attn_mode)
+        vf = bp["lin1"].afmt             # the MLP's operand format (the qkv GEMM of a block with large logits runs on bf16 hi/lo: _attn_mode)
         h = ws.planes("blk_h", B * T, bp["lin1"].n, fmt=vf)
         if fold:
             xp, rs = self._stream_planes(B * T, vf)
@@ -1202,7 +1270,7 @@ class SAMAdapterbimodalMixModNewInTwinConvNEW(nn.Module):
             else:
                 ops.layernorm(c, ip["fnw"], ip["fnb"], 1e-6, out_planes=fn)
         self._msda(ip["attn"], qn, fn, x_in, x_out, geo["ss1"], geo["lsi1"], geo["ref1"], B, T, Nc, 3, colscale=ip["gamma"],
-                   stream_out=(self._stream_planes(B * T, self._packed["blocks"][ip["first_block"]]["qkv"].fmt)
+                   stream_out=(self._stream_planes(B * T, self._packed["blocks"][ip["first_block"]]["qkv"].afmt)
                                if self._packed["fold_ln"] and B * T >= 128 else None), f_rn=f_rn)
 
     def _extractor(self, ep, c, x, geo, B, T, Nc, H, W, last=False):  # AM:490-511, ConvFFN AM:446-471

@@ -178,12 +178,14 @@ def save_packed(model, path, device="cuda"):
         torch.cuda.synchronize(dev)
     sd = {k: v.detach().cpu() for k, v in model.state_dict().items()}
     enc = _enc(pk)
+    settings = {"h8_sites": list(model._h8_sites()), "h8c": bool(pk.get("h8c", False)), "share_c_norm": bool(pk.get("share_c_norm", True)), "fold_ln": bool(pk.get("fold_ln", False)),
+                "fold_cnx_ln": bool(pk.get("fold_cnx_ln", False)), "cnx_f16": bool(pk.get("cnx_f16", False)),
+                "fold_adapter_ln": bool(pk.get("fold_adapter_ln", False)), "wide": bool(pk.get("wide", False)),
+                "inter_pairs": list(pk.get("inter_pairs", []))}
+    if pk.get("fp8_weights"):   # (fp8 packs only: the ViT-block weights are W8 codes + exponents; a file without the key was packed without the switch)
+        settings["fp8_weights"] = True
     torch.save({"format": PACK_FORMAT, "cfg": model.cfg, "state_dict": sd, "packed": enc, "fingerprint": _fingerprint(sd),
-                "packed_checksum": _packed_checksum(enc),
-                "settings": {"h8_sites": list(model._h8_sites()), "h8c": bool(pk.get("h8c", False)), "share_c_norm": bool(pk.get("share_c_norm", True)), "fold_ln": bool(pk.get("fold_ln", False)),
-                             "fold_cnx_ln": bool(pk.get("fold_cnx_ln", False)), "cnx_f16": bool(pk.get("cnx_f16", False)),
-                             "fold_adapter_ln": bool(pk.get("fold_adapter_ln", False)), "wide": bool(pk.get("wide", False)),
-                             "inter_pairs": list(pk.get("inter_pairs", []))}}, path)
+                "packed_checksum": _packed_checksum(enc), "settings": settings}, path)
 
 
 def load_packed(model, path, device="cuda"):
@@ -210,6 +212,8 @@ def load_packed(model, path, device="cuda"):
     want["wide"] = wide
     want["inter_pairs"] = sorted(inter_pairs)
     want["fold_adapter_ln"] = bool(model._fold_adapter_ln_wanted())   # (a pack-time setting that drives the run-time path: ADVICE r05)
+    if model._fp8_wanted():
+        want["fp8_weights"] = True   # (fp8 weights: a file packed without them is refused, and an fp8 file by a model without them)
     if blob.get("settings") != want:
         raise RuntimeError(f"{path}: packed with settings {blob.get('settings')}, the model runs {want}: repack")
     if blob["fingerprint"] != _fingerprint(blob["state_dict"]):
@@ -225,8 +229,11 @@ def load_packed(model, path, device="cuda"):
         raise RuntimeError(f"{path}: the packed guard words have shape {tuple(pk['attn_guard'].shape)}, expected ({model.cfg['depth'] + 1},): repack")
     # spot check on the device: planes -> float must give back the weights they claim to be the split of
     sd = blob["state_dict"]
+    lin2 = sd[f"blocks.{model.cfg['depth'] - 1}.mlp.lin2.weight"]
+    if want.get("fp8_weights"):   # the planes hold the effective fp8 weights
+        lin2 = ops.fp8_dequantize(*ops.fp8_quantize(lin2.float()))
     for planes, w in ((pk["pe_w"], sd["patch_embed.proj.weight"].reshape(model.cfg["embed_dim"], -1)),
-                      (pk["blocks"][-1]["lin2"], sd[f"blocks.{model.cfg['depth'] - 1}.mlp.lin2.weight"])):
+                      (pk["blocks"][-1]["lin2"], lin2)):
         back = ops.planes_to_float(planes, cols=w.shape[1])[: w.shape[0]].cpu()
         if not torch.allclose(back, w.float(), rtol=2e-3, atol=1e-6):
             raise RuntimeError(f"{path}: state dict and packed planes do not belong together (planes decode to other weights)")

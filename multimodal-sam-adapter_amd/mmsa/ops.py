@@ -93,6 +93,72 @@ def _mat(t, name, dtype=torch.float32):
 
 
 FMT_B3, FMT_H8, FMT_H8C, FMT_F3 = 0, 1, 2, 3   # MMSA_FMT_* (include/mmsa.h); F3 = the B3 layout with fp16 halves (22 significant bits)
+FMT_W8 = 4   # MMSA_FMT_W8: fp8 (OCP e4m3) weight codes + one power-of-two scale per row, a W operand against h8c activation planes (backbone.fp8_weights)
+W8_EMIN, W8_EMAX = -15, 7   # every 2^e * e4m3 value is exact in fp16 in this range (granularity 2^-24, largest 448 * 2^7 = 57344): csrc/common.h
+E4M3_MAX = 448.0
+
+
+def _binade(a, lo):
+    """floor(log2(a)) for a > 0, at least `lo` (float64; exact: log2 rounding next to a power of two is corrected)."""
+    b = torch.floor(torch.log2(a.clamp_min(2.0 ** (lo - 1)))).clamp_min(lo)
+    b = torch.where(a >= torch.exp2(b + 1), b + 1, b)
+    return torch.where((b > lo) & (a < torch.exp2(b)), b - 1, b)
+
+
+def fp8_quantize(w2d):
+    """[N, K] float weight -> (codes uint8 [N, K], exponents int8 [N]) with W_eff[n, k] = 2^e_n * e4m3(codes[n, k]): e_n = the smallest exponent in
+    [W8_EMIN, W8_EMAX] with max_k |w[n, k]| <= 448 * 2^e_n, codes = OCP e4m3fn (not fnuz) of w / 2^e_n rounded to nearest even.  A row beyond
+    448 * 2^7 = 57344 raises ValueError: nothing saturates silently.  Pack-time preprocessing (float64 torch ops on the weight's device)."""
+    w = w2d.detach().to(torch.float64)
+    if w.dim() != 2 or not bool(torch.isfinite(w).all()):
+        raise ValueError("mmsa.fp8_quantize: a finite 2-D weight is expected")
+    amax = w.abs().amax(1) if w.shape[1] else w.new_zeros(w.shape[0])
+    lim = E4M3_MAX * 2.0 ** W8_EMAX
+    if bool((amax > lim).any()):
+        n = int(torch.argmax(amax))
+        raise ValueError(f"mmsa.fp8_quantize: row {n} has max |w| = {float(amax[n]):.6g} > {lim:g} = 448 * 2^{W8_EMAX}: not representable as fp8 weights")
+    e = torch.ceil(torch.log2(amax.clamp_min(1e-300) / E4M3_MAX)).clamp(W8_EMIN, W8_EMAX)
+    e = torch.where(amax > E4M3_MAX * torch.exp2(e), e + 1, e)                                  # (log2 rounding at exact powers of two)
+    e = torch.where((e > W8_EMIN) & (amax <= E4M3_MAX * torch.exp2(e - 1)), e - 1, e)
+    v = w / torch.exp2(e)[:, None]                                                             # exact: a power-of-two scale, |v| <= 448
+    a = v.abs()
+    step = torch.exp2(_binade(a, -6) - 3)                                                      # e4m3: 3 mantissa bits; subnormals share 2^-6's spacing 2^-9
+    q = torch.round(a / step) * step                                                           # round half to even (exact in float64); q <= 448
+    b = _binade(q, -6)
+    normal = q >= 2.0 ** -6
+    code = torch.where(normal, (b + 7) * 8 + (q / torch.exp2(b) * 8 - 8), q * 512.0).to(torch.int32)
+    code = code | torch.where((v < 0) & (q > 0), 128, 0)
+    return code.to(torch.uint8), e.to(torch.int8)
+
+
+def fp8_dequantize(codes, exps):
+    """(codes uint8 [N, K] e4m3fn, exponents int8 [N]) -> float32 2^e_n * e4m3(code) (exact)."""
+    c = codes.to(torch.int32)
+    ex, m = (c >> 3) & 15, (c & 7).double()
+    mag = torch.where(ex == 0, m * 2.0 ** -9, (8.0 + m) * torch.exp2(ex.double() - 10.0))
+    return (torch.where(c >= 128, -mag, mag) * torch.exp2(exps.double())[:, None]).float()
+
+
+def w8_planes(w2d):
+    """[N, K] float weight (K % 128 == 0) -> W8 weight Planes (include/mmsa.h MMSA_FMT_W8): fp8_quantize's codes, row n = K bytes in the h8c lo-byte
+    order (k = 64c + 32t + 8g + e at byte 64c + 16g + 8t + e), then the N exponents as bytes, zero padded to a multiple of 128 (one int16 tensor of
+    N + ceil(pad128(N) / K) rows of K / 2)."""
+    n, k = w2d.shape
+    if k % 128:
+        raise ValueError(f"mmsa.w8_planes: K={k} must be a multiple of 128")
+    codes, exps = fp8_quantize(w2d)
+    rows = n + -(-((n + 127) // 128 * 128) // k)
+    buf = torch.zeros(rows * k, dtype=torch.uint8, device=w2d.device)
+    buf[:n * k] = codes.reshape(n, k // 64, 2, 4, 8).permute(0, 1, 3, 2, 4).reshape(-1)
+    buf[n * k:n * k + n] = exps.view(torch.uint8)
+    return Planes(buf.view(torch.int16).view(rows, k // 2), n, k, k, FMT_W8, True)
+
+
+def w8_codes(pl):
+    """(codes uint8 [N, K] in k order, exponents int8 [N]) of W8 weight Planes."""
+    n, k = pl.n, pl.kpad
+    by = pl.p.contiguous().view(torch.uint8).view(-1)
+    return by[:n * k].view(n, k // 64, 4, 2, 8).permute(0, 1, 3, 2, 4).reshape(n, k), by[n * k:n * k + n].view(torch.int8)
 
 
 class Planes:
@@ -115,6 +181,11 @@ class Planes:
         self.fmt = fmt
         self.weight = weight
         self.gen = None   # (cell, value): set by a producer whose buffer is reused; live() tells whether it still holds this data
+
+    @property
+    def afmt(self):
+        """Format of the ACTIVATION planes a GEMM with this weight reads (W8 weights run against h8c planes, every other format against its own)."""
+        return FMT_H8C if self.fmt == FMT_W8 else self.fmt
 
     def stamp(self, cell):
         """Mark these planes as valid while `cell[0]` keeps its current value (the producer bumps it when it reuses the buffer)."""
@@ -195,6 +266,8 @@ def planes_to_float(pl, cols=None):
         lo_part = planes_to_float(Planes(pl.p[:, :2 * pl.split], pl.n, pl.split, pl.split, pl.fmt))
         hi_part = planes_to_float(Planes(pl.p[:, 2 * pl.split:], pl.n, pl.kpad - pl.split, pl.kpad - pl.split, FMT_H8))
         return torch.cat([lo_part, hi_part], 1)[:, :(pl.k if cols is None else cols)]
+    if pl.fmt == FMT_W8:
+        return fp8_dequantize(*w8_codes(pl))[:, :(pl.k if cols is None else cols)]
     if pl.fmt == FMT_H8C:
         kp = pl.kpad
         by = pl.p[:, :3 * kp].contiguous().view(torch.uint8).view(r, 6 * kp)
@@ -253,7 +326,7 @@ def gemm(a, w, out=None, bias=None, act="none", alpha=1.0, colscale=None, resid=
         pa = None
         if ka < w.kpad:
             raise RuntimeError(f"mmsa.gemm: A planes have {ka} columns but the packed weight expects K={w.kpad}")
-        if a.fmt != w.fmt or a.weight or (w.fmt == FMT_H8 and not w.weight) or (w.fmt == FMT_H8C and w.weight):
+        if a.fmt != w.afmt or a.weight or (w.fmt == FMT_H8 and not w.weight) or (w.fmt == FMT_H8C and w.weight):
             raise RuntimeError(f"mmsa.gemm: operand formats differ (A fmt {a.fmt}, W fmt {w.fmt} weight={w.weight})")
     elif fmt not in (FMT_B3, FMT_F3):
         raise RuntimeError("mmsa.gemm: h8 weights need A as h8 planes")
@@ -284,10 +357,11 @@ def gemm(a, w, out=None, bias=None, act="none", alpha=1.0, colscale=None, resid=
              _chk(rowstats_out), _chk(row_norm[0]) if row_norm else None, _chk(row_norm[1]) if row_norm else None, GEMM_FLAVOUR, _clamp_ptr(), _stream())
     if prof is not None:
         lib.call("mmsa_event_record", e1, _stream())
-        ob = 3.0 if fmt == FMT_H8C else 4.0          # bytes per operand element (h8c planes: 3)
+        ob = 3.0 if fmt in (FMT_H8C, FMT_W8) else 4.0          # bytes per operand element (h8c planes: 3)
+        wb = 1.0 if fmt == FMT_W8 else ob                      # (W8 weights: 1)
         pb = 0.0 if out_planes is None else (3.0 if out_planes.fmt == FMT_H8C else 4.0)
         prof.append((2.0 * m * w.n * w.k * batch, e0, e1,
-                     batch * (ob * (m * w.kpad + w.n * w.kpad) + m * w.n * (pb + 4.0 * ((1 if out is not None else 0) + (1 if resid is not None else 0))))))
+                     batch * (ob * m * w.kpad + wb * w.n * w.kpad + m * w.n * (pb + 4.0 * ((1 if out is not None else 0) + (1 if resid is not None else 0))))))
         if GEMM_SHAPES is not None:
             GEMM_SHAPES.append((m, w.n, w.k, batch, act, resid is not None, ("C" if out is not None else "") + ("P" if out_planes is not None else ""),
                                 "planes" if pap is not None else "fp32"))

@@ -29,7 +29,7 @@ def census(src, extra=()):
             m = re.match(r"^(_Z\S+):", line)
             if m:
                 name = demangle_template(m.group(1))
-                res[name] = dict(scratch=0, vgprs=0, scratch_bytes=0, vmcnt0=0, readlane=0, lines=0)
+                res[name] = dict(scratch=0, vgprs=0, scratch_bytes=0, vmcnt0=0, readlane=0, lines=0, mfma_f16=0, mfma_scale_f8=0)
             if name is None:
                 continue
             r = res[name]
@@ -40,6 +40,10 @@ def census(src, extra=()):
                 r["vmcnt0"] += 1
             if "v_readlane_b32" in line:
                 r["readlane"] += 1
+            if "v_mfma_f32_16x16x32_f16" in line:
+                r["mfma_f16"] += 1
+            if "v_mfma_scale_f32_16x16x128_f8f6f4" in line:
+                r["mfma_scale_f8"] += 1
             m2 = re.search(r"; NumVgprs: (\d+)", line)
             if m2:
                 r["vgprs"] = int(m2.group(1))
