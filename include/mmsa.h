@@ -340,6 +340,24 @@ int mmsa_crop_batch_nchw(const float* src, int B, int C, int H, int W, const int
 int mmsa_slide_argmax(const float* logits, int n, int C, int hs, int ws, const int* windows, unsigned char* out, int B, int H, int W,
                       int hc, int wc, int* uncovered, mmsa_stream_t stream);
 
+/* --- the input side of the test pipelines (segmentation/mmseg_custom/datasets/pipelines/transform.py): Pad_multimodal (2934-3010, impad bottom /
+ *     right) -> Normalize_multimodal / Normalize_multimodal_Muses (2601-2825: `/ 255` when norm_by_max, mmcv.imnormalize = channel reversal when
+ *     to_rgb, subtract mean, multiply by 1 / float64(std)) -> ImageToTensor (HWC -> CHW) -> Collectmod, from the loaders' frames in one pass.
+ *     src0 / src1 = the two modalities, each [B, Hs, Ws, 3] HWC contiguous, uint8 or float32 (dtype0 / dtype1 below).  HOST arrays (copied into
+ *     the launch arguments): mean[6], sinv[6] per OUTPUT channel, sinv = float32(1 / float64(float32(std))); div255[2], swap[2], pad_val[2] per
+ *     modality.  out[c] = (a - mean[c]) * sinv[c] with a = x / 255.0f where div255 (a correctly rounded division), x = the modality's channel
+ *     2 - c where swap; float32, one rounding per step, no fused multiply-add.  Pixels outside the source (H >= Hs, W >= Ws: padded bottom /
+ *     right) are pad_val BEFORE normalisation, as in the FMB pipelines (pad first, normalise after).
+ *     preprocess_nhwc: dst [B, 6, H, W].  preprocess_crops: dst[k] = window (image, y0, x0) of size hc x wc of that canvas (ED:205-212),
+ *     `windows` as in mmsa_crop_batch_nchw, checked against the PADDED H x W canvas; the full-size normalised frame is never written. --- */
+enum { MMSA_PRE_U8 = 0, MMSA_PRE_F32 = 1 };
+int mmsa_preprocess_nhwc(const void* src0, int dtype0, const void* src1, int dtype1, int B, int Hs, int Ws, const float* mean,
+                         const float* sinv, const int* div255, const int* swap, const float* pad_val, float* dst, int H, int W,
+                         mmsa_stream_t stream);
+int mmsa_preprocess_crops(const void* src0, int dtype0, const void* src1, int dtype1, int B, int Hs, int Ws, const float* mean,
+                          const float* sinv, const int* div255, const int* swap, const float* pad_val, int H, int W, const int* windows,
+                          int n, float* dst, int hc, int wc, mmsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,8 @@ from . import inference  # noqa: F401  (encode_decode / slide_inference / argmax
 from .backbone import OperandRangeError, SAMAdapterbimodalMixModNewInTwinConvNEW, SAMAdapterbimodalMixModNewInTwinConvNEWwithcp
 from .head import SegformerHead
 from .chains import AttentionRangeError, Chains, Replay
+from . import preprocess  # noqa: F401  (raw frames -> normalised NCHW, whole or as windows; FrameFeeder)
+from .preprocess import FrameFeeder, Preprocess
 from .registry import BACKBONES, HEADS, build_backbone, build_head
 
 for _cls in (SAMAdapterbimodalMixModNewInTwinConvNEW, SAMAdapterbimodalMixModNewInTwinConvNEWwithcp):
@@ -29,4 +31,5 @@ if not _HAVE_MMSEG:     # local registry (no mmseg in the process): nothing to o
     register_head()
 
 __all__ = ["SegformerHead", "HEADS", "build_head", "register_head", "SAMAdapterbimodalMixModNewInTwinConvNEW", "SAMAdapterbimodalMixModNewInTwinConvNEWwithcp",
-           "BACKBONES", "build_backbone", "ops", "lib", "inference", "Chains", "Replay", "AttentionRangeError", "OperandRangeError"]
+           "BACKBONES", "build_backbone", "ops", "lib", "inference", "Chains", "Replay", "AttentionRangeError", "OperandRangeError",
+           "preprocess", "Preprocess", "FrameFeeder"]

@@ -17,6 +17,8 @@ def _on_device(fn):
     @functools.wraps(fn)
     def wrapped(*args, **kw):
         t = next((a for a in args if isinstance(a, torch.Tensor)), None)
+        if t is None:                                           # raw frames (preprocess=): the first argument that is a pair of tensors
+            t = next((a[0] for a in args if isinstance(a, (tuple, list)) and len(a) == 2 and isinstance(a[0], torch.Tensor)), None)
         if t is None or not t.is_cuda:
             return fn(*args, **kw)     # _check raises the "no CPU path" error
         with torch.cuda.device(t.device):
@@ -35,6 +37,15 @@ def _pair(backbone, head):
     from .head import SegformerHead
     if isinstance(head, SegformerHead) and hasattr(backbone, "_vit"):
         backbone.emit_planes = True
+
+
+def _raw(preprocess, img, what):
+    """With `preprocess=`: img is the pair (rgb, aux) of raw [B, Hs, Ws, 3] frames -> (rgb, aux, B, H, W) of the normalised canvas."""
+    if not isinstance(img, (tuple, list)) or len(img) != 2:
+        raise RuntimeError(f"mmsa.{what}: with preprocess=, the image is the pair (rgb, aux) of raw [B, H, W, 3] GPU tensors")
+    rgb, aux = preprocess.check(*img)
+    H, W = preprocess.canvas(rgb.shape[1], rgb.shape[2])
+    return rgb, aux, rgb.shape[0], H, W
 
 
 def _check(img):
@@ -73,11 +84,19 @@ def crop_boxes(h_img, w_img, crop_size, stride):
 
 @_on_device
 @torch.no_grad()
-def slide_inference(backbone, head, img, crop_size, stride, max_batch=8):
+def slide_inference(backbone, head, img, crop_size, stride, max_batch=8, preprocess=None):
     """ED:191-234 without the optional rescale: averaged logits [B, classes, H, W] of overlapping windows.  All windows have
-    the crop size here (the backbone needs H = W = img_size), i.e. the image must be at least as large as the crop."""
-    _check(img)
-    B, _, H, W = img.shape
+    the crop size here (the backbone needs H = W = img_size), i.e. the image must be at least as large as the crop.
+    `preprocess=` (mmsa.preprocess.Preprocess): img is the pair (rgb, aux) of raw frames; the windows are cut AND normalised by one launch."""
+    if preprocess is not None:
+        rgb, aux, B, H, W = _raw(preprocess, img, "slide_inference")
+        device = rgb.device
+        cut = lambda chunk: preprocess.crops(rgb, aux, chunk, crop_size)
+    else:
+        _check(img)
+        B, _, H, W = img.shape
+        device = img.device
+        cut = lambda chunk: _crops(img, chunk, crop_size)
     if H < crop_size[0] or W < crop_size[1]:
         raise RuntimeError("mmsa.slide_inference: the image must be at least as large as the crop")
     boxes = crop_boxes(H, W, crop_size, stride)
@@ -86,12 +105,12 @@ def slide_inference(backbone, head, img, crop_size, stride, max_batch=8):
     jobs = [(b, box) for box in boxes for b in range(B)]
     for s in range(0, len(jobs), max_batch):
         chunk = jobs[s:s + max_batch]
-        crops = _crops(img, chunk, crop_size)
+        crops = cut(chunk)
         feats, _ = backbone(crops)
         lg = head(feats)                                   # [n, classes, hc/4, wc/4]
         if preds is None:
-            preds = torch.zeros(B, lg.shape[1], H, W, device=img.device)
-            count = torch.zeros(B, H, W, device=img.device)
+            preds = torch.zeros(B, lg.shape[1], H, W, device=device)
+            count = torch.zeros(B, H, W, device=device)
         for k, (b, (y1, x1, y2, x2)) in enumerate(chunk):   # preds[b] += pad(resize(logits_k)); count[b, window] += 1
             _resize_into(lg[k:k + 1], preds[b:b + 1], y1, x1, y2 - y1, x2 - x1, count=count[b:b + 1], accumulate=True)
     if bool((count == 0).any()):
@@ -136,16 +155,24 @@ def _check_overlap(boxes, what):
 
 @_on_device
 @torch.no_grad()
-def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8):
+def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preprocess=None):
     """`simple_test` of a sliding-window frame (ED:191-234 + ED:449,477) -> uint8 class map [B, H, W], without the
     [B, classes, H, W] logits canvas: every window's logits stay at head resolution and ONE kernel (mmsa_slide_argmax) resizes,
     sums the overlapping windows in window order, divides by the count and takes the argmax -- the same additions in the same order
     as slide_inference + argmax_map, so the same class map bit for bit.  All windows of the frame go through the encoder in
-    batches of `max_batch`; with static shapes the whole function is HIP-graph capturable (no host sync inside)."""
+    batches of `max_batch`; with static shapes the whole function is HIP-graph capturable (no host sync inside).
+    `preprocess=` (mmsa.preprocess.Preprocess): img is the pair (rgb, aux) of raw frames; the windows are cut AND normalised by one launch."""
     import ctypes
-    _check(img)
-    img = img.contiguous()
-    B, _, H, W = img.shape
+    if preprocess is not None:
+        rgb, aux, B, H, W = _raw(preprocess, img, "slide_class_map")
+        device = rgb.device
+        cut = lambda chunk: preprocess.crops(rgb, aux, chunk, crop_size)
+    else:
+        _check(img)
+        img = img.contiguous()
+        B, _, H, W = img.shape
+        device = img.device
+        cut = lambda chunk: _crops(img, chunk, crop_size)
     if H < crop_size[0] or W < crop_size[1]:
         raise RuntimeError("mmsa.slide_class_map: the image must be at least as large as the crop")
     boxes = crop_boxes(H, W, crop_size, stride)
@@ -157,13 +184,13 @@ def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8):
     lgs = []
     for s in range(0, len(jobs), max_batch):
         chunk = jobs[s:s + max_batch]
-        feats, _ = backbone(_crops(img, chunk, crop_size))
+        feats, _ = backbone(cut(chunk))
         lgs.append(head(feats))
     lg = lgs[0] if len(lgs) == 1 else torch.cat(lgs, 0)
     n = len(jobs)
     tab = (ctypes.c_int * (3 * n))(*[v for b, (y1, x1, _, _) in jobs for v in (b, y1, x1)])
-    out = torch.empty(B, H, W, dtype=torch.uint8, device=img.device)
-    unc = torch.zeros(1, dtype=torch.int32, device=img.device)
+    out = torch.empty(B, H, W, dtype=torch.uint8, device=device)
+    unc = torch.zeros(1, dtype=torch.int32, device=device)
     lib.call("mmsa_slide_argmax", lg.data_ptr(), n, lg.shape[1], lg.shape[2], lg.shape[3], tab, out.data_ptr(), B, H, W,
              crop_size[0], crop_size[1], unc.data_ptr(), ops._stream())
     return out, unc          # unc[0] != 0 <=> some pixel is not covered (ED:220); checked by the caller outside a capture
@@ -171,9 +198,12 @@ def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8):
 
 @_on_device
 @torch.no_grad()
-def whole_class_map(backbone, head, img):
-    """Whole-image `simple_test`: resize x4 (bilinear, align_corners=False) + argmax fused (ED:90-94,449,477) -> uint8 [B, H, W]."""
+def whole_class_map(backbone, head, img, preprocess=None):
+    """Whole-image `simple_test`: resize x4 (bilinear, align_corners=False) + argmax fused (ED:90-94,449,477) -> uint8 [B, H, W].
+    `preprocess=` (mmsa.preprocess.Preprocess): img is the pair (rgb, aux) of raw frames, normalised (and padded) by one launch."""
     import ctypes
+    if preprocess is not None:
+        img = preprocess(*_raw(preprocess, img, "whole_class_map")[:2])
     _check(img)
     _pair(backbone, head)
     feats, _ = backbone(img)
@@ -226,13 +256,17 @@ def whole_inference_dim_cut(backbone, head, img, dim, cut_dim, rescale=True):
 
 @_on_device
 @torch.no_grad()
-def inference(backbone, head, img, test_cfg, rescale=True):
+def inference(backbone, head, img, test_cfg, rescale=True, preprocess=None):
     """ED:417-447 dispatch on `test_cfg['mode']` -- 'slide', 'whole', 'whole_dim', 'whole_dim_cut' ('slide_mod_sel' runs the segmentor's
     modality-selection variant, ED:236-308, which needs a backbone with a selection head: not this backbone) -- returning the logits the
-    reference softmaxes (ED:448-470; flips are the caller's, as in the reference's test pipeline)."""
+    reference softmaxes (ED:448-470; flips are the caller's, as in the reference's test pipeline).
+    `preprocess=` (mmsa.preprocess.Preprocess): img is the pair (rgb, aux) of raw frames -- 'slide' cuts its windows from them, the whole modes
+    normalise the frame first."""
     mode = test_cfg["mode"]
     if mode == "slide":
-        return slide_inference(backbone, head, img, tuple(test_cfg["crop_size"]), tuple(test_cfg["stride"]))
+        return slide_inference(backbone, head, img, tuple(test_cfg["crop_size"]), tuple(test_cfg["stride"]), preprocess=preprocess)
+    if preprocess is not None and mode in ("whole", "whole_dim", "whole_dim_cut"):
+        img = preprocess(*_raw(preprocess, img, "inference")[:2])
     if mode == "whole":
         return whole_inference(backbone, head, img)
     if mode == "whole_dim":
@@ -275,15 +309,24 @@ class SlideRunner:
     """Throughput form of slide_class_map for a fixed frame geometry: the frame's windows are cut by one kernel, go through the
     encoder + head as `chains` concurrent sub-batches (mmsa.Chains: one HIP graph per chain, shared packed weights) and one kernel
     (mmsa_slide_argmax) turns the head-resolution logits into the class map.  Same class map as slide_inference + argmax_map, bit
-    for bit.  `frame` is the static [B, 6, H, W] buffer the runner reads on every run()."""
+    for bit.  `frame` is the static [B, 6, H, W] buffer the runner reads on every run().
+    With `preprocess=` (mmsa.preprocess.Preprocess) `frame` is the pair (rgb, aux) of raw [B, Hs, Ws, 3] buffers -- the runner's static inputs -- and the
+    windows are cut AND normalised from them by one launch; run(frame=pair) reads another pair of the same geometry instead (mmsa.preprocess.FrameFeeder's slots)."""
 
-    def __init__(self, backbone, head, frame, crop_size, stride, chains=2, check_every=1):
+    def __init__(self, backbone, head, frame, crop_size, stride, chains=2, check_every=1, preprocess=None):
         import ctypes
         from .chains import Chains
-        _check(frame)
+        self.preprocess = preprocess
+        if preprocess is not None:
+            rgb, aux, B, H, W = _raw(preprocess, frame, "SlideRunner")
+            self.frame = (rgb, aux)
+            self.device = rgb.device
+        else:
+            _check(frame)
+            self.frame = frame.contiguous()
+            B, _, H, W = self.frame.shape
+            self.device = self.frame.device
         _pair(backbone, head)
-        self.frame = frame.contiguous()
-        B, _, H, W = self.frame.shape
         self.crop_size = tuple(crop_size)
         boxes = crop_boxes(H, W, crop_size, stride)
         _check_overlap(boxes, "SlideRunner")
@@ -293,21 +336,34 @@ class SlideRunner:
             raise RuntimeError("mmsa.SlideRunner: at most 64 windows per frame batch")
         if n % chains:
             chains = 1
-        with torch.cuda.device(self.frame.device):
-            self.crops = _crops(self.frame, self.jobs, self.crop_size)          # also the static input buffer of the chains
+        with torch.cuda.device(self.device):
+            self.crops = self._cut(self.frame)          # also the static input buffer of the chains
             self.chains = Chains(backbone, head, n=chains, check_every=check_every).capture(self.crops)
             self.tab = (ctypes.c_int * (3 * n))(*[v for b, (y1, x1, _, _) in self.jobs for v in (b, y1, x1)])
-            self.out = torch.empty(B, H, W, dtype=torch.uint8, device=self.frame.device)
-            self.unc = torch.zeros(1, dtype=torch.int32, device=self.frame.device)
+            self.out = torch.empty(B, H, W, dtype=torch.uint8, device=self.device)
+            self.unc = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def _cut(self, frame, out=None):
+        if self.preprocess is not None:
+            return self.preprocess.crops(frame[0], frame[1], self.jobs, self.crop_size, out=out)
+        return _crops(frame, self.jobs, self.crop_size, out=out)
 
     @torch.no_grad()
-    def run(self):
+    def run(self, frame=None):
         """Enqueue one frame on the current stream (asynchronous) -> FrameResult; `.outputs()` = (class map uint8 [B, H, W], uncovered-pixel flag) once the
         attention logit guard of this pass has been inspected.  The inspection costs one 4 * depth-byte copy per `check_every` frames and an event wait,
         no device sync; a frame that scored logits beyond the fp16 range raises mmsa.chains.AttentionRangeError from outputs() -- or from the next run(),
         whichever comes first -- after the blocks concerned have been moved to fp16 hi/lo pairs and the graphs captured again: run that frame again."""
-        with torch.cuda.device(self.frame.device):
-            _crops(self.frame, self.jobs, self.crop_size, out=self.crops)
+        if frame is None:
+            frame = self.frame
+        else:
+            if self.preprocess is None:
+                raise RuntimeError("mmsa.SlideRunner.run(frame=...): only with preprocess= (without it the runner reads its static frame buffer)")
+            frame = self.preprocess.check(*frame)
+            if any(f.shape != s.shape or f.dtype != s.dtype or f.device != s.device for f, s in zip(frame, self.frame)):
+                raise RuntimeError("mmsa.SlideRunner.run(frame=...): the pair must have the shape, dtypes and device of the runner's own buffers")
+        with torch.cuda.device(self.device):
+            self._cut(frame, out=self.crops)
             rp = self.chains.replay()
             lg = rp.unverified          # the argmax kernel below is enqueued behind the pass; nothing is read on the host before outputs() verifies it
             B, H, W = self.out.shape
