@@ -357,6 +357,23 @@ int mmsa_preprocess_nhwc(const void* src0, int dtype0, const void* src1, int dty
 int mmsa_preprocess_crops(const void* src0, int dtype0, const void* src1, int dtype1, int B, int Hs, int Ws, const float* mean,
                           const float* sinv, const int* div255, const int* swap, const float* pad_val, int H, int W, const int* windows,
                           int n, float* dst, int hc, int wc, mmsa_stream_t stream);
+/* The same two outputs from sources of another size: `Resize_multimodal` FIRST (transform.py:1136-1167: mmcv.imrescale / mmcv.imresize per
+ * modality = cv2.resize(..., INTER_LINEAR)), then the steps above.  The Hs x Ws sources are resized to Hr x Wr inside the H x W canvas (H >= Hr,
+ * W >= Wr; the rest is padding).  DEVICE tables, one entry per resized row / column: yofs[Hr] / xofs[Wr] = first source row / column of the two
+ * taps (the second is + 1, clamped to the source), ycoef / xcoef = the coefficient pair: int16[.][2] scaled by 2048 when fixed_point (OpenCV's
+ * 8-bit path: D = S0 * a0 + S1 * a1 in int32, dst = (((b0 * (D0 >> 4)) >> 16) + ((b1 * (D1 >> 4)) >> 16) + 2) >> 2; both sources must be uint8),
+ * float32[.][2] otherwise (D = S0 * a0 + S1 * a1, dst = D0 * b0 + D1 * b1, one float32 rounding per product and sum; a uint8 source is
+ * converted exactly first, as numpy's concatenation of a uint8 and a float32 modality does, loading.py:225).  The tables are the caller's
+ * (mmsa/preprocess.py builds them as OpenCV's resize.cpp states them); taps are clamped into the source whatever they hold.  The resized frame
+ * is never written. */
+int mmsa_preprocess_resize_nhwc(const void* src0, int dtype0, const void* src1, int dtype1, int B, int Hs, int Ws, const float* mean,
+                                const float* sinv, const int* div255, const int* swap, const float* pad_val, float* dst, int H, int W,
+                                int Hr, int Wr, const int* xofs, const void* xcoef, const int* yofs, const void* ycoef, int fixed_point,
+                                mmsa_stream_t stream);
+int mmsa_preprocess_resize_crops(const void* src0, int dtype0, const void* src1, int dtype1, int B, int Hs, int Ws, const float* mean,
+                                 const float* sinv, const int* div255, const int* swap, const float* pad_val, int H, int W, const int* windows,
+                                 int n, float* dst, int hc, int wc, int Hr, int Wr, const int* xofs, const void* xcoef, const int* yofs,
+                                 const void* ycoef, int fixed_point, mmsa_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -3,8 +3,9 @@
  * mmsa_convnext_mlp_fused and the attention entries and removed mmsa_gemm_next_extras / mmsa_debug_*_flavour / mmsa_dwconv7_ln without bumping it.
  * 102 (round 6): mmsa_convnext_mlp_fused takes clamp_max; new entry mmsa_msda_fused_planes.
  * 103: mmsa_gemm_split3's `fmt` accepts MMSA_FMT_W8 (fp8 weights against h8c activation planes).
- * 104: new entries mmsa_preprocess_nhwc / mmsa_preprocess_crops (raw HWC frames -> normalised NCHW, whole or as windows). */
+ * 104: new entries mmsa_preprocess_nhwc / mmsa_preprocess_crops (raw HWC frames -> normalised NCHW, whole or as windows).
+ * 105: new entries mmsa_preprocess_resize_nhwc / mmsa_preprocess_resize_crops (the same from sources of another size: bilinear resize first). */
 #ifndef MMSA_VERSION_H
 #define MMSA_VERSION_H
-#define MMSA_ABI_VERSION 104
+#define MMSA_ABI_VERSION 105
 #endif

@@ -1,5 +1,5 @@
 """The input side of the reference's test pipelines on device (segmentation/mmseg_custom/datasets/pipelines/transform.py):
-`Pad_multimodal` (2934-3010) -> `Normalize_multimodal` / `Normalize_multimodal_Muses` (2601-2825) -> `ImageToTensor` -> `Collectmod`,
+[`Resize_multimodal` (1136-1167), opt-in] -> `Pad_multimodal` (2934-3010) -> `Normalize_multimodal` / `Normalize_multimodal_Muses` (2601-2825) -> `ImageToTensor` -> `Collectmod`,
 from the frames the loaders return -- one HWC tensor [B, Hs, Ws, 3] per modality, uint8 or float32 -- to the float32 NCHW tensor the
 network reads, in ONE launch (csrc/preprocess.hip): whole (`pp(rgb, aux)` -> [B, 6, H, W]) or directly as the windows of slide inference
 (`pp.crops(...)` -> [n, 6, hc, wc]; the full-size normalised frame is never written).  `FrameFeeder` brings host frames to the device
@@ -32,15 +32,37 @@ def rescale_size(h, w, scale):
     return int(h * float(f) + 0.5), int(w * float(f) + 0.5)
 
 
+def resize_axis_table(n_src, n_dst, fixed_point):
+    """One axis of cv2.resize(INTER_LINEAR) as OpenCV's resize.cpp states it -> (first tap int32 [n_dst], coefficient pairs [n_dst, 2]).
+    inv = double(n_dst) / n_src, scale = 1.0 / inv (not n_src / n_dst); f = float32((d + 0.5) * scale - 0.5), evaluated in double and rounded
+    once; s = floor(f), f -= s; s < 0 -> (0, 0); s >= n_src - 1 -> (n_src - 1, 0): the second tap is then the same pixel.  Coefficients:
+    int16 round-half-even of (1 - f) * 2048 and f * 2048 (the 8-bit fixed-point path), or float32 (1 - f, f)."""
+    scale = 1.0 / (np.float64(n_dst) / np.float64(n_src))
+    f = ((np.arange(n_dst, dtype=np.float64) + 0.5) * scale - 0.5).astype(np.float32)
+    s = np.floor(f).astype(np.int32)
+    f = f - s.astype(np.float32)
+    low, high = s < 0, s >= n_src - 1
+    s[low], f[low] = 0, 0
+    s[high], f[high] = n_src - 1, 0
+    pair = np.stack([np.float32(1) - f, f], 1)
+    if fixed_point:
+        pair = np.rint(pair * np.float32(2048)).astype(np.int16)       # cvRound: half to even; the products are exact in float32
+    return s, np.ascontiguousarray(pair)
+
+
 class Preprocess:
     """Normalisation (+ padding) of a bimodal frame with the keyword names of the reference's `Normalize_multimodal*` / `Pad_multimodal`.
 
     variant "multimodal": every modality is divided by 255 when `norm_by_max` (transform.py:2801-2804);
     variant "muses": only the modality named 'rgb' is (transform.py:2685-2694).
     `pad_size` = (H, W) of `Pad_multimodal(size=...)` applied BEFORE the normalisation (the FMB test pipelines): pixels below / right of the
-    source are `pad_val`, then normalised."""
+    source are `pad_val`, then normalised.
+    `resize` = dict(img_scale=(w, h), keep_ratio=True) of a `Resize_multimodal` step that comes FIRST (transform.py:1136-1167).  By default it is
+    accepted only where it is the identity for the frames given; with `device_resize=True` the launch resizes (cv2.resize INTER_LINEAR as
+    OpenCV's resize.cpp states it: 8-bit fixed point when both sources are uint8, float32 otherwise), then pads and normalises."""
 
-    def __init__(self, mean, std, to_rgb, modalities_name, modalities_ch, norm_by_max=False, variant="multimodal", pad_size=None, pad_val=0):
+    def __init__(self, mean, std, to_rgb, modalities_name, modalities_ch, norm_by_max=False, variant="multimodal", pad_size=None, pad_val=0,
+                 resize=None, device_resize=False):
         if variant not in VARIANTS:
             raise ValueError(f"mmsa.Preprocess: variant '{variant}' is not one of {VARIANTS}")
         if list(modalities_ch) != [3, 3] or len(modalities_name) != 2:
@@ -67,7 +89,14 @@ class Preprocess:
         if len(pv) != 2 or not np.isfinite(np.array(pv, dtype=np.float32)).all():
             raise ValueError("mmsa.Preprocess: pad_val is one finite number, or one per modality")
         self.pad_val = [float(v) for v in pv]
-        self.resize = None          # from_pipeline: a Resize_multimodal step that must be the identity for the frames given
+        if resize is not None:
+            sc = resize.get("img_scale")
+            if sc is None or len(sc) != 2 or isinstance(sc[0], (list, tuple)) or resize.get("ratio_range") is not None:
+                raise NotImplementedError("mmsa.Preprocess: resize needs one img_scale=(w, h); a ratio range or several scales are not built")
+            resize = dict(img_scale=(int(sc[0]), int(sc[1])), keep_ratio=bool(resize.get("keep_ratio", True)))
+        self.resize = resize        # a Resize_multimodal step before the padding: the identity for the frames given unless device_resize
+        self.device_resize = bool(device_resize)
+        self._tables = {}           # (Hs, Ws, Hr, Wr, fixed_point, device) -> device tables, uploaded once
         self._c_mean = (ctypes.c_float * 6)(*self.mean.tolist())
         self._c_sinv = (ctypes.c_float * 6)(*self.sinv.tolist())
         self._c_div = (ctypes.c_int * 2)(*[int(v) for v in self.div255])
@@ -75,12 +104,16 @@ class Preprocess:
         self._c_pad = (ctypes.c_float * 2)(*self.pad_val)
 
     @classmethod
-    def from_pipeline(cls, test_pipeline):
+    def from_pipeline(cls, test_pipeline, resize=None):
         """Build from a reference config's `test_pipeline` (the list of dicts).  Recognised: the `LoadImageandModalities*` loaders (the caller's
         job: they produce what this object takes), `MultiScaleFlipAug` with one scale and flip=False, `Normalize_multimodal(_Muses)`,
-        `Pad_multimodal(size=...)` before the normalisation, `ImageToTensor`, `Collectmod`, and `Resize_multimodal` where it is the identity for the
-        frames given (checked per call against the source size).  Any other step raises NotImplementedError naming it."""
-        norm = pad = resize = None
+        `Pad_multimodal(size=...)` before the normalisation, `ImageToTensor`, `Collectmod`, and `Resize_multimodal` as the first of them: where it
+        is the identity for the frames given (checked per call against the source size), or, with resize="device", carried out by the launch.
+        Any other step raises NotImplementedError naming it."""
+        if resize not in (None, "device"):
+            raise ValueError(f"mmsa.Preprocess.from_pipeline: resize={resize!r}; None (identity only) or 'device'")
+        device_resize, resize = resize == "device", None
+        norm = pad = None
 
         def walk(steps):
             nonlocal norm, pad, resize
@@ -111,7 +144,7 @@ class Preprocess:
                     pad = st
                 elif t == "Resize_multimodal":
                     if st.get("ratio_range") is not None or st.get("img_scale") is None or isinstance(st["img_scale"][0], (list, tuple)):
-                        raise NotImplementedError("Resize_multimodal with a ratio range or several scales (the OpenCV bilinear resize is not built)")
+                        raise NotImplementedError("Resize_multimodal with a ratio range or several scales (only one fixed img_scale has a device form)")
                     if norm is not None or pad is not None or resize is not None:
                         raise NotImplementedError("Resize_multimodal after Pad_multimodal / the normalisation, or twice")
                     resize = dict(img_scale=tuple(st["img_scale"]), keep_ratio=bool(st.get("keep_ratio", True)))
@@ -124,25 +157,57 @@ class Preprocess:
         if norm is None:
             raise NotImplementedError("the pipeline has no Normalize_multimodal / Normalize_multimodal_Muses step")
         pp = cls(norm["mean"], norm["std"], norm["to_rgb"], norm["modalities_name"], norm["modalities_ch"], norm_by_max=norm.get("norm_by_max", False),
-                 variant=_NORMALIZE[norm["type"]], pad_size=None if pad is None else pad["size"], pad_val=0 if pad is None else pad.get("pad_val", 0))
-        pp.resize = resize
+                 variant=_NORMALIZE[norm["type"]], pad_size=None if pad is None else pad["size"], pad_val=0 if pad is None else pad.get("pad_val", 0),
+                 resize=resize, device_resize=device_resize)
         return pp
 
     # ---- geometry / checks ----
-    def canvas(self, Hs, Ws):
-        """(H, W) of the normalised frame for an Hs x Ws source: the pad size, or the source size."""
-        if self.resize is not None:
-            sc = self.resize["img_scale"]
-            new = rescale_size(Hs, Ws, sc) if self.resize["keep_ratio"] else (sc[1], sc[0])       # img_scale is (w, h)
-            if new != (Hs, Ws):
-                raise NotImplementedError(f"Resize_multimodal(img_scale={sc}, keep_ratio={self.resize['keep_ratio']}) turns a {Hs} x {Ws} frame into {new[0]} x {new[1]}: "
-                                          "only the identity is supported (the OpenCV bilinear resize is not built)")
-        if self.pad_size is None:
+    def resized(self, Hs, Ws):
+        """(Hr, Wr) of an Hs x Ws source after the Resize_multimodal step (the source size without one)."""
+        if self.resize is None:
             return Hs, Ws
+        sc = self.resize["img_scale"]
+        new = rescale_size(Hs, Ws, sc) if self.resize["keep_ratio"] else (sc[1], sc[0])       # img_scale is (w, h)
+        if new != (Hs, Ws):
+            if not self.device_resize:
+                raise NotImplementedError(f"Resize_multimodal(img_scale={sc}, keep_ratio={self.resize['keep_ratio']}) turns a {Hs} x {Ws} frame into {new[0]} x {new[1]}: "
+                                          "only the identity is supported (the OpenCV bilinear resize is not built) unless the object is made with "
+                                          "from_pipeline(..., resize='device') / device_resize=True")
+            if Hs == 2 * new[0] and Ws == 2 * new[1]:
+                raise NotImplementedError(f"Resize_multimodal from {Hs} x {Ws} to {new[0]} x {new[1]}: with both scale factors exactly 2, cv2.resize replaces "
+                                          "INTER_LINEAR by its 2 x 2 area average (INTER_AREA), which is not built")
+        return new
+
+    def canvas(self, Hs, Ws):
+        """(H, W) of the normalised frame for an Hs x Ws source: the pad size, or the (resized) source size."""
+        Hr, Wr = self.resized(Hs, Ws)
+        if self.pad_size is None:
+            return Hr, Wr
         H, W = self.pad_size
-        if H < Hs or W < Ws:
-            raise RuntimeError(f"mmsa.Preprocess: pad size {H} x {W} is smaller than the {Hs} x {Ws} source (padding only grows a frame)")
+        if H < Hr or W < Wr:
+            raise RuntimeError(f"mmsa.Preprocess: pad size {H} x {W} is smaller than the {Hr} x {Wr} {'source' if (Hr, Wr) == (Hs, Ws) else 'resized frame'} "
+                               "(padding only grows a frame)")
         return H, W
+
+    def resize_tables(self, Hs, Ws, Hr, Wr, fixed_point, device):
+        """The four device tables of the resizing launch (x taps, x coefficients, y taps, y coefficients), built in numpy, uploaded once per
+        geometry and kept: a later call with the same geometry launches without any copy or allocation (and can be captured in a HIP graph)."""
+        key = (Hs, Ws, Hr, Wr, bool(fixed_point), torch.device(device))
+        tabs = self._tables.get(key)
+        if tabs is None:
+            if _capturing(key[-1]):
+                raise RuntimeError(f"mmsa.Preprocess: the resize tables for {Hs} x {Ws} -> {Hr} x {Wr} are not on the device yet and cannot be uploaded "
+                                   "during a graph capture: run one call with this geometry before capturing")
+            xs, xc = resize_axis_table(Ws, Wr, fixed_point)
+            ys, yc = resize_axis_table(Hs, Hr, fixed_point)
+            tabs = tuple(torch.from_numpy(t).to(key[-1]) for t in (xs, xc, ys, yc))
+            self._tables[key] = tabs
+        return tabs
+
+    def _resize_args(self, rgb, aux, Hr, Wr):
+        fixed = rgb.dtype == torch.uint8 and aux.dtype == torch.uint8     # a pair with a float32 modality is float32 as a whole (loading.py:225)
+        xs, xc, ys, yc = self.resize_tables(rgb.shape[1], rgb.shape[2], Hr, Wr, fixed, rgb.device)
+        return (Hr, Wr, xs.data_ptr(), xc.data_ptr(), ys.data_ptr(), yc.data_ptr(), int(fixed))
 
     def check(self, rgb, aux):
         """The two sources as the kernels need them, or a RuntimeError: [B, Hs, Ws, 3], HWC contiguous, uint8 or float32, on one GPU."""
@@ -174,7 +239,11 @@ class Preprocess:
             if out is None:
                 out = torch.empty(B, 6, H, W, device=rgb.device)
             _check_out(out, (B, 6, H, W), rgb.device)
-            lib.call("mmsa_preprocess_nhwc", *self._args(rgb, aux), out.data_ptr(), H, W, ops._stream())
+            Hr, Wr = self.resized(Hs, Ws)
+            if (Hr, Wr) == (Hs, Ws):
+                lib.call("mmsa_preprocess_nhwc", *self._args(rgb, aux), out.data_ptr(), H, W, ops._stream())
+            else:
+                lib.call("mmsa_preprocess_resize_nhwc", *self._args(rgb, aux), out.data_ptr(), H, W, *self._resize_args(rgb, aux, Hr, Wr), ops._stream())
         return out
 
     @torch.no_grad()
@@ -193,8 +262,17 @@ class Preprocess:
             if out is None:
                 out = torch.empty(n, 6, hc, wc, device=rgb.device)
             _check_out(out, (n, 6, hc, wc), rgb.device)
-            lib.call("mmsa_preprocess_crops", *self._args(rgb, aux), H, W, tab, n, out.data_ptr(), hc, wc, ops._stream())
+            Hr, Wr = self.resized(Hs, Ws)
+            if (Hr, Wr) == (Hs, Ws):
+                lib.call("mmsa_preprocess_crops", *self._args(rgb, aux), H, W, tab, n, out.data_ptr(), hc, wc, ops._stream())
+            else:
+                lib.call("mmsa_preprocess_resize_crops", *self._args(rgb, aux), H, W, tab, n, out.data_ptr(), hc, wc, *self._resize_args(rgb, aux, Hr, Wr),
+                         ops._stream())
         return out
+
+
+def _capturing(device):
+    return device.type == "cuda" and torch.cuda.is_current_stream_capturing()
 
 
 def _check_out(out, shape, device):
