@@ -99,7 +99,6 @@
 #pragma unroll
                 for (int ni = 0; ni < 4; ++ni) rra[mi][ni] = *reinterpret_cast<const float4*>(rbase + (long)mi * 16 * a.ldr + ni * 16);
             }
-            EPI_DRAIN();   // (gemm_h8c: the next tile's first operand pieces are still in flight -- waited for together with the vectors requested above)
             EPI_STAMP(1) EPI_STAMP_WAIT() EPI_STAMP(2)
             float* cbase = nullptr;
             if constexpr (kC) cbase = C + (long)row0 * a.ldc + col0;
@@ -246,7 +245,6 @@
 #pragma unroll
               for (int i = 0; i < 4; ++i) rq[0][i] = *reinterpret_cast<const float4*>(rb_ + (long)(4 * i) * a.ldr);
             }
-            EPI_DRAIN();
             EPI_STAMP(1) EPI_STAMP_WAIT() EPI_STAMP(2)
             float* cb_ = C + (long)rowb * a.ldc + col;
 #pragma unroll

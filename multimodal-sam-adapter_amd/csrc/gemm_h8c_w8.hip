@@ -1,6 +1,7 @@
 // h8c activations x W8 (fp8 e4m3) weights: the opt-in fp8 weight path of the ViT-block GEMMs (`model.fp8_weights`, mmsa/backbone.py).
 // Same tiles (256 x 128, 8 waves, wave tile 64 x 64), persistent workgroups, tile order, A operand stream (h8c planes through LDS-DMA)
-// and epilogue (gemm_v2_epilogue.inc -> gemm_epilogue_regs.inc) as gemm_h8c.hip -- read that file first; only the differences are noted here.
+// and epilogue (gemm_v2_epilogue.inc -> gemm_epilogue_regs.inc) as gemm_h8c.hip -- read that file first; what the two share is the text of gemm_h8c_shared.h,
+// so only the differences are written (and noted) here.
 //
 // Weights.  W_eff[n, k] = 2^e_n * e4m3(code[n, k]) (common.h "W8"): every value is exact in fp16, so its h8 lo part is zero and of the two
 // cross terms of the h8 product only q(hi_W) . lo_A is left:
@@ -24,9 +25,8 @@
 // (free LO unit + gap) is the epilogue's staging area, as in gemm_h8c.hip.
 // Column scales: the wave's 64 exponent bytes of the output tile come with scalar LOADS (lgkmcnt: the k loop's DMA stream -- vmcnt -- is not
 // touched) at the top of every output tile; a lane selects the four bytes of its columns.
-#include "gemm_v2_shared.h"
+#include "gemm_h8c_shared.h"
 
-typedef __attribute__((ext_vector_type(4))) unsigned hw_u4;
 typedef __attribute__((ext_vector_type(2))) _Float16 hw_h2;
 
 #define HW_H_UNIT 40960   // A hi 32 KiB + W codes 8 KiB
@@ -34,10 +34,6 @@ typedef __attribute__((ext_vector_type(2))) _Float16 hw_h2;
 #define HW_LDS_H(i_) ((i_) * HW_H_UNIT)
 #define HW_LDS_L(i_) (2 * HW_H_UNIT + (i_) * (HW_L_UNIT + 16384))
 #define HW_LDS_TOTAL (2 * HW_H_UNIT + 2 * HW_L_UNIT + 16384)   // 160 KiB
-
-#ifndef HW_EPI_UNROLL
-#define HW_EPI_UNROLL 1
-#endif
 
 // 4 e4m3 codes (one dword) -> 4 fp16 (two dwords), scaled by 2^e: exact for codes x 2^e inside fp16 (e in [-15, 7], common.h W8)
 __device__ __forceinline__ uint2 w8_cvt4(unsigned c, float s) {
@@ -49,7 +45,7 @@ __device__ __forceinline__ uint2 w8_cvt4(unsigned c, float s) {
 template <bool GEN, int ACT>
 __global__ __launch_bounds__(512, 1) void gemm_h8c_w8_kernel(GemmV2Args a) {
   constexpr bool PP = true;
-  constexpr bool EPI_UNROLL = ACT >= 0 && HW_EPI_UNROLL;
+  constexpr bool EPI_UNROLL = ACT >= 0;
   constexpr int V2_BM = 256;
   constexpr int V2_NST = 3;   // (epilogue include: unused on the PP path)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -63,7 +59,7 @@ __global__ __launch_bounds__(512, 1) void gemm_h8c_w8_kernel(GemmV2Args a) {
   const int swid = 64;
   const int G = gridDim.x;
   int rb = blockIdx.x;
-  { const int xcd = rb & 7, q = G >> 3, r = G & 7; rb = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (rb >> 3); }
+  V2_XCD_REMAP(rb, G)
   const int my_tiles = (a.ntiles - rb + G - 1) / G;
   if (my_tiles <= 0) return;
   V2_SLACK_STAGGER(a, rb, G)
@@ -72,34 +68,29 @@ __global__ __launch_bounds__(512, 1) void gemm_h8c_w8_kernel(GemmV2Args a) {
 
   // ---- DMA lane mapping.  A: as gemm_h8c.hip.  W: one instruction = 16 columns x 64 B of one chunk, lane -> (column wcol = lane >> 2,
   // LDS slot = lane & 3), the piece fetched into slot s of column c is s ^ ((c >> 2) & 3) (= s ^ ((lane >> 4) & 3): wave * 16 is a multiple of 16)
-  const int drow = lane >> 3;
-  const int dpiece = ((lane & 7) ^ (drow >> 1)) * 16;
-  const int lq = ((lane & 7) ^ ((-(drow >> 1)) & 3)) * 16;
+  H8C_DMA_LANE();
   const int lds_ha = wave * 32 * 128, lds_hw = 32768 + wave * 1024;
   const int lds_la = wave * 2048;
   const unsigned ldaB = (unsigned)(a.lda * 2);           // A row-PAIR stride in bytes
   const unsigned ldwB = (unsigned)(a.ldw * 2);           // W row stride in bytes (= K)
   const unsigned K2 = (unsigned)K * 2u, K4 = (unsigned)K * 4u;
-  const unsigned LA_E = (unsigned)(drow >> 1) * ldaB + (unsigned)(drow & 1) * K2 + dpiece, LA_O = LA_E ^ 64u;
+  H8C_A_LANE_HI();
   const int wcol = lane >> 2;
   const unsigned wpiece = (unsigned)(((lane & 3) ^ ((lane >> 4) & 3)) * 16);
   const unsigned LW = (unsigned)wcol * ldwB + wpiece;
-  const unsigned LLA = (unsigned)drow * ldaB + K4 + lq;
+  H8C_A_LANE_LO();
 
   const unsigned char *hA, *hW, *lA;
   int h_m0 = 0, h_n0 = 0, l_m0 = 0, l_n0 = 0;
   bool h_edge = false, l_edge = false;
   int hp_tile = rb, hp_p = 0, hp_j = 0, lp_tile = rb, lp_p = 0, lp_j = 0;
-#define HW_TILE(t_, bz_, m0_, n0_)                                                                          \
-  { const int per_b_ = a.nbm * a.nbn; bz_ = (t_) / per_b_; const int r_ = (t_) - bz_ * per_b_; int tmi_, tni_;  \
-    V2_TILE_MN(r_, tmi_, tni_); m0_ = tmi_ * 256; n0_ = tni_ * 128; }
 #define HW_SET_H(t_)                                                                                        \
-  { int bz_; HW_TILE(t_, bz_, h_m0, h_n0)                                                                   \
+  { int bz_; H8C_TILE(t_, 256, bz_, h_m0, h_n0)                                                                   \
     hA = reinterpret_cast<const unsigned char*>(a.Ap + (long)bz_ * a.strideA + (long)(h_m0 >> 1) * a.lda);  \
     hW = reinterpret_cast<const unsigned char*>(a.Wp + (long)bz_ * a.strideW) + (long)h_n0 * ldwB;          \
     h_edge = h_m0 + 256 > a.M || h_n0 + 128 > a.N; }
 #define HW_SET_L(t_)                                                                                        \
-  { int bz_; HW_TILE(t_, bz_, l_m0, l_n0)                                                                   \
+  { int bz_; H8C_TILE(t_, 256, bz_, l_m0, l_n0)                                                                   \
     lA = reinterpret_cast<const unsigned char*>(a.Ap + (long)bz_ * a.strideA + (long)(l_m0 >> 1) * a.lda);  \
     l_edge = l_m0 + 256 > a.M; }
   HW_SET_H(hp_tile) HW_SET_L(lp_tile)
@@ -107,56 +98,45 @@ __global__ __launch_bounds__(512, 1) void gemm_h8c_w8_kernel(GemmV2Args a) {
   { unsigned char* d_ = smem + HW_LDS_H(hp_j & 1);                                                          \
     const unsigned char* sa_ = hA + (long)hp_p * 128 + (unsigned long)((unsigned)(wave * 16) * ldaB);       \
     const unsigned char* sw_ = hW + (long)hp_p * 64 + (unsigned long)((unsigned)(wave * 16) * ldwB);        \
-    GLDS16(sa_ + LA_E, d_ + lds_ha); GLDS16(sa_ + 4u * ldaB + LA_O, d_ + lds_ha + 1024);                     \
-    GLDS16(sa_ + 8u * ldaB + LA_E, d_ + lds_ha + 2048); GLDS16(sa_ + 12u * ldaB + LA_O, d_ + lds_ha + 3072); \
+    H8C_A_HI_FAST(sa_, d_)                                                                                  \
     GLDS16(sw_ + LW, d_ + lds_hw); }
 #define HW_L_ISSUE_FAST()                                                                                   \
   { unsigned char* d_ = smem + HW_LDS_L(lp_j & 1);                                                          \
     const unsigned char* sa_ = lA + (long)lp_p * 256 + (unsigned long)((unsigned)(wave * 16) * ldaB);       \
-    GLDS16(sa_ + LLA, d_ + lds_la); GLDS16(sa_ + 8u * ldaB + LLA, d_ + lds_la + 1024);                       \
-    GLDS16(sa_ + 128 + LLA, d_ + 16384 + lds_la); GLDS16(sa_ + 128 + 8u * ldaB + LLA, d_ + 16384 + lds_la + 1024); }
-#define HW_HOFF(row_, m0_, ld_) (((unsigned)((row_) - (m0_)) >> 1) * (ld_) + ((unsigned)((row_) - (m0_)) & 1u) * K2)
+    H8C_A_LO_FAST(sa_, d_) H8C_A_LO_FAST(sa_ + 128, d_ + 16384) }
 #define HW_H_ISSUE()                                                                                        \
   if (!h_edge) HW_H_ISSUE_FAST() else {                                                                     \
     unsigned char* d_ = smem + HW_LDS_H(hp_j & 1); const long ko_ = (long)hp_p * 128;                       \
     const int ab_ = h_m0 + wave * 32 + drow, wb_ = h_n0 + wave * 16 + wcol;                                  \
-    GLDS16(hA + ko_ + (unsigned long)(HW_HOFF(min(ab_, a.M - 1), h_m0, ldaB) + dpiece), d_ + lds_ha);        \
-    GLDS16(hA + ko_ + (unsigned long)(HW_HOFF(min(ab_ + 8, a.M - 1), h_m0, ldaB) + (dpiece ^ 64)), d_ + lds_ha + 1024); \
-    GLDS16(hA + ko_ + (unsigned long)(HW_HOFF(min(ab_ + 16, a.M - 1), h_m0, ldaB) + dpiece), d_ + lds_ha + 2048);       \
-    GLDS16(hA + ko_ + (unsigned long)(HW_HOFF(min(ab_ + 24, a.M - 1), h_m0, ldaB) + (dpiece ^ 64)), d_ + lds_ha + 3072); \
+    H8C_A_HI_EDGE(hA + ko_, ab_, h_m0, d_)                                                                  \
     GLDS16(hW + (long)hp_p * 64 + (unsigned long)((unsigned)(min(wb_, a.N - 1) - h_n0) * ldwB + wpiece), d_ + lds_hw); }
 #define HW_H_ADVANCE() { ++hp_j; if (++hp_p == np) { hp_p = 0; hp_tile += G; if (hp_j < total) HW_SET_H(hp_tile) } }
 #define HW_L_ISSUE()                                                                                        \
   if (!l_edge) HW_L_ISSUE_FAST() else {                                                                     \
     unsigned char* d_ = smem + HW_LDS_L(lp_j & 1); const long ko_ = (long)lp_p * 256;                       \
     const int aj_ = (l_m0 >> 1) + wave * 16 + drow;                                                          \
-    const unsigned o0_ = (unsigned)(min(aj_, (a.M - 1) >> 1) - (l_m0 >> 1)) * ldaB + K4 + lq;               \
-    const unsigned o1_ = (unsigned)(min(aj_ + 8, (a.M - 1) >> 1) - (l_m0 >> 1)) * ldaB + K4 + lq;           \
+    const unsigned o0_ = H8C_A_LO_OFF(aj_, l_m0), o1_ = H8C_A_LO_OFF(aj_ + 8, l_m0);                         \
     GLDS16(lA + ko_ + o0_, d_ + lds_la); GLDS16(lA + ko_ + o1_, d_ + lds_la + 1024);                         \
     GLDS16(lA + ko_ + 128 + o0_, d_ + 16384 + lds_la); GLDS16(lA + ko_ + 128 + o1_, d_ + 16384 + lds_la + 1024); }
 #define HW_L_ADVANCE() { ++lp_j; if (++lp_p == nsteps) { lp_p = 0; lp_tile += G; if (lp_j < total_s) HW_SET_L(lp_tile) } }
 
   // ---- fragment offsets: A as gemm_h8c.hip; W codes of column cw = wn * 64 + ni * 16 + l15 (ni: + 1024 bytes per step), group g
-  const int fslot = g ^ ((l15 >> 1) & 7);
-  const int frag0 = l15 * 128 + fslot * 16, frag1 = l15 * 128 + (fslot ^ 4) * 16;
+  H8C_FRAG_HI();
   const int fha = (wm * 64) * 128;
   const int fcw = 32768 + (wn * 64 + l15) * 64 + ((g ^ ((l15 >> 2) & 3)) * 16);
-  const int lo_off = 128 * (l15 >> 1) + 16 * ((((l15 & 1) << 2) | g) ^ ((-(l15 >> 2)) & 3));
+  H8C_FRAG_LO();
   const int fla = (wm * 4) * 1024 + lo_off;
 
   f32x4 acc[4][4];   // [ni][mi]
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j_ = 0; j_ < 4; ++j_) acc[i][j_] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  hw_u4 ah0[4], ah1[4];
-  hw_u4 cW[4];            // q(w) of the even chunk, completed into the fp8 tuples by the odd chunk
+  H8C_ZERO_ACC()
+  h8c_u4 ah0[4], ah1[4];
+  h8c_u4 cW[4];            // q(w) of the even chunk, completed into the fp8 tuples by the odd chunk
   float wsc[4];           // 2^e of the lane's four columns in the output tile being computed
 
   // column scales of output tile t_: the wave's 64 exponent bytes by scalar loads, lane l15 of group ni takes byte l15 of dwords 4 ni .. 4 ni + 3
   const signed char* wexp = reinterpret_cast<const signed char*>(a.Wp) + (long)a.N * ldwB;   // (batch 1: mmsa_gemm_v2_launch)
 #define HW_SCALES(t_)                                                                                       \
-  { int bz_, m0_, n0_; HW_TILE(t_, bz_, m0_, n0_) (void)bz_; (void)m0_;                                     \
+  { int bz_, m0_, n0_; H8C_TILE(t_, 256, bz_, m0_, n0_) (void)bz_; (void)m0_;                                     \
     const __attribute__((address_space(4))) unsigned* e4_ =                                                 \
         (const __attribute__((address_space(4))) unsigned*)(wexp + n0_ + wn * 64);                          \
     int lane_s_ = lane; asm volatile("" : "+v"(lane_s_));                                                   \
@@ -172,15 +152,10 @@ __global__ __launch_bounds__(512, 1) void gemm_h8c_w8_kernel(GemmV2Args a) {
   HW_H_ISSUE() HW_H_ADVANCE()
   if (total > 1) { HW_H_ISSUE() HW_H_ADVANCE() }
   HW_L_ISSUE() HW_L_ADVANCE()
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  H8C_WAIT(0);
   __builtin_amdgcn_s_barrier();
 
   int j = 0, tile = rb, nowait = 0;
-  const unsigned psel = 0x07050301u;
-#define HW_SB() __builtin_amdgcn_sched_barrier(0)
-#define HW_BAR() { HW_SB(); __builtin_amdgcn_s_barrier(); HW_SB(); }
-#define HW_PERM(d_, hi_, lo_) asm volatile("v_perm_b32 %0, %1, %2, %3" : "=v"(d_) : "v"(hi_), "v"(lo_), "s"(psel))
-#define HW_WAIT(n_) asm volatile("s_waitcnt vmcnt(" #n_ ")" ::: "memory")
 // One pair (one 64-k chunk); barriers as gemm_h8c.hip.  ODD_ (literal): 0 = the even chunk of a 128-k step (phase X requests LO(step + 1), phase Y
 // keeps q(w), no fp8 MFMA), 1 = the odd chunk (phase Y reads LO(step) and issues the 16 fp8 MFMAs of both chunks).  Stream order of one wave's DMA
 // instructions: ... H(2s+1) [Y of 2s-1] | L(s+1) [X of 2s, 4] | H(2s+2) [Y of 2s, 5] | H(2s+3) [Y of 2s+1, 5] ...  Visibility (group 0 / 1 one barrier apart,
@@ -195,77 +170,77 @@ __global__ __launch_bounds__(512, 1) void gemm_h8c_w8_kernel(GemmV2Args a) {
     const bool skipw = !(FAST_) && nowait > 0;                                                                        \
     /* ======== phase X, read part: A hi fragments, W codes */                                                                                   \
     _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                                   \
-      ah0[i] = *reinterpret_cast<const hw_u4*>(hb + fha + i * 2048 + frag0);                                          \
-      ah1[i] = *reinterpret_cast<const hw_u4*>(hb + fha + i * 2048 + frag1);                                          \
+      ah0[i] = *reinterpret_cast<const h8c_u4*>(hb + fha + i * 2048 + frag0);                                         \
+      ah1[i] = *reinterpret_cast<const h8c_u4*>(hb + fha + i * 2048 + frag1);                                         \
     }                                                                                                                 \
-    hw_u4 wc_[4];                                                                                                     \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i) wc_[i] = *reinterpret_cast<const hw_u4*>(hb + fcw + i * 1024);     \
-    HW_SB();                                                                                                          \
+    h8c_u4 wc_[4];                                                                                                    \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i) wc_[i] = *reinterpret_cast<const h8c_u4*>(hb + fcw + i * 1024);    \
+    H8C_SB();                                                                                                         \
     const bool do_l = !(ODD_) && ((FAST_) || lp_j < total_s);                                                         \
     if (!(ODD_)) { if (FAST_) { HW_L_ISSUE_FAST() } else if (do_l) { HW_L_ISSUE() } }                                 \
-    HW_SB();                                                                                                          \
+    H8C_SB();                                                                                                         \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                                \
-    if (tail) HW_WAIT(0); else if ((ODD_) && ((FAST_) || !skipw)) HW_WAIT(19);                                        \
-    HW_BAR()                                                                                                          \
+    if (tail) H8C_WAIT(0); else if ((ODD_) && ((FAST_) || !skipw)) H8C_WAIT(19);                                      \
+    H8C_BAR()                                                                                                         \
     /* ======== phase X, matrix part: per k-tile, codes -> fp16 (column scale), 16 fp16 MFMAs, q(w) = top bytes; the conversions sit here, */ \
     /* not in the read part: there the fp16 image of both k-tiles beside the codes spilled (first build) */           \
-    hw_u4 q_[4];                                                                                                      \
+    h8c_u4 q_[4];                                                                                                     \
     _Pragma("unroll") for (int t = 0; t < 2; ++t) {                                                                   \
-      hw_u4 wt_[4];                                                                                                   \
+      h8c_u4 wt_[4];                                                                                                  \
       _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                                 \
         const uint2 x0_ = w8_cvt4(wc_[i][2 * t], wsc[i]), x1_ = w8_cvt4(wc_[i][2 * t + 1], wsc[i]);                   \
-        wt_[i] = (hw_u4){x0_.x, x0_.y, x1_.x, x1_.y};                                                                 \
+        wt_[i] = (h8c_u4){x0_.x, x0_.y, x1_.x, x1_.y};                                                                \
       }                                                                                                               \
       _Pragma("unroll") for (int ni = 0; ni < 4; ++ni)                                                                \
         _Pragma("unroll") for (int mi = 0; mi < 4; ++mi)                                                              \
           acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(mx_h8, wt_[ni]), __builtin_bit_cast(mx_h8, t ? ah1[mi] : ah0[mi]), acc[ni][mi], 0, 0, 0); \
       _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                                 \
         unsigned u0_, u1_;                                                                                            \
-        HW_PERM(u0_, wt_[i][1], wt_[i][0]); HW_PERM(u1_, wt_[i][3], wt_[i][2]);                                       \
+        H8C_PERM(u0_, wt_[i][1], wt_[i][0]); H8C_PERM(u1_, wt_[i][3], wt_[i][2]);                                     \
         q_[i][2 * t] = u0_; q_[i][2 * t + 1] = u1_;                                                                   \
       }                                                                                                               \
-      HW_SB();                                                                                                        \
+      H8C_SB();                                                                                                       \
     }                                                                                                                 \
-    if (tail) HW_WAIT(0); else if ((ODD_) && ((FAST_) || !skipw)) HW_WAIT(19);                                        \
-    HW_BAR()                                                                                                          \
+    if (tail) H8C_WAIT(0); else if ((ODD_) && ((FAST_) || !skipw)) H8C_WAIT(19);                                      \
+    H8C_BAR()                                                                                                         \
     /* ======== phase Y, read part (odd chunk): lo of A of both chunks (16 bytes each: k = 8g .. +7 and 32 + 8g .. +7 of a chunk) */ \
     mx_v8i opA[4], opW[4];                                                                                            \
     _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                                   \
       if (ODD_) {                                                                                                     \
-        const hw_u4 l0_ = *reinterpret_cast<const hw_u4*>(lb + fla + i * 1024);                                      \
-        const hw_u4 l1_ = *reinterpret_cast<const hw_u4*>(lb + 16384 + fla + i * 1024);                               \
+        const h8c_u4 l0_ = *reinterpret_cast<const h8c_u4*>(lb + fla + i * 1024);                                    \
+        const h8c_u4 l1_ = *reinterpret_cast<const h8c_u4*>(lb + 16384 + fla + i * 1024);                             \
         opA[i] = (mx_v8i){(int)l0_[0], (int)l0_[1], (int)l0_[2], (int)l0_[3], (int)l1_[0], (int)l1_[1], (int)l1_[2], (int)l1_[3]}; \
         opW[i] = (mx_v8i){(int)cW[i][0], (int)cW[i][1], (int)cW[i][2], (int)cW[i][3], (int)q_[i][0], (int)q_[i][1], (int)q_[i][2], (int)q_[i][3]}; \
       } else {                                                                                                        \
         cW[i] = q_[i];                                                                                                \
       }                                                                                                               \
     }                                                                                                                 \
-    HW_SB();                                                                                                          \
+    H8C_SB();                                                                                                         \
     const bool do_h = (FAST_) || hp_j < total;                                                                        \
     if (FAST_) { HW_H_ISSUE_FAST() } else if (do_h) { HW_H_ISSUE() }                                                   \
-    HW_SB();                                                                                                          \
+    H8C_SB();                                                                                                         \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                                \
-    if (tail) HW_WAIT(0); else if ((FAST_) || !skipw) { if (ODD_) HW_WAIT(5); else HW_WAIT(9); }                     \
-    HW_BAR()                                                                                                          \
+    if (tail) H8C_WAIT(0); else if ((FAST_) || !skipw) { if (ODD_) H8C_WAIT(5); else H8C_WAIT(9); }                  \
+    H8C_BAR()                                                                                                         \
     /* ======== phase Y, matrix part (odd chunk): 16 block-scaled fp8 MFMAs, K = 128 = the lo terms of both chunks */  \
     if (ODD_) {                                                                                                       \
       _Pragma("unroll") for (int ni = 0; ni < 4; ++ni)                                                                \
         _Pragma("unroll") for (int mi = 0; mi < 4; ++mi)                                                              \
           acc[ni][mi] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(opW[ni], opA[mi], acc[ni][mi], 1, 1, 0, 0x7f7f7f7f, 0, MMSA_H8_MFMA_SCALE); \
     }                                                                                                                 \
-    HW_SB();                                                                                                          \
+    H8C_SB();                                                                                                         \
     if (FAST_) { if (!(ODD_)) { ++lp_j; ++lp_p; } ++hp_j; ++hp_p; } else { if (do_l) HW_L_ADVANCE() if (do_h) HW_H_ADVANCE() } \
-    HW_SB();                                                                                                          \
-    if (tail || last) HW_WAIT(0); else if ((FAST_) || !skipw) { if (ODD_) HW_WAIT(5); else HW_WAIT(9); }             \
-    HW_BAR()                                                                                                          \
+    H8C_SB();                                                                                                         \
+    if (tail || last) H8C_WAIT(0); else if ((FAST_) || !skipw) { if (ODD_) H8C_WAIT(5); else H8C_WAIT(9); }          \
+    H8C_BAR()                                                                                                         \
     if (!(FAST_)) nowait = 0;                                                                                         \
     ++j;                                                                                                              \
   }
 
   for (int tdone = 0; tdone < my_tiles; ++tdone) {
-    if (grp) HW_BAR()
+    if (grp) H8C_BAR()
     bool interior;
-    { int bz_, m0_, n0_; HW_TILE(tile, bz_, m0_, n0_) interior = m0_ + 256 <= a.M && n0_ + 128 <= a.N; }
+    { int bz_, m0_, n0_; H8C_TILE(tile, 256, bz_, m0_, n0_) interior = m0_ + 256 <= a.M && n0_ + 128 <= a.N; }
     HW_SCALES(tile)
     int p = 0;
     HW_PAIR(0, 0)
@@ -285,26 +260,14 @@ __global__ __launch_bounds__(512, 1) void gemm_h8c_w8_kernel(GemmV2Args a) {
       HW_PAIR(0, 1)
       ++p;
     }
-    if (!grp) HW_BAR()
+    if (!grp) H8C_BAR()
     // ---- tile boundary (every DMA issued so far has landed: the last pair drained)
-    if (V2_DBG(a) == 2) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j_ = 0; j_ < 4; ++j_) { asm volatile("" :: "v"(acc[i][j_])); acc[i][j_] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-      nowait = 1;
-    } else {
-      int lane_o_ = lane;
-      asm volatile("" : "+v"(lane_o_));
-      const int lane = lane_o_, l15 = lane_o_ & 15, g = lane_o_ >> 4;
+    if (V2_DBG(a) == 2) H8C_NO_EPILOGUE() else {
 #define EPI_STAGING_BASE (smem + ((((j - 1) >> 1) & 1) ? HW_LDS_L(1) - 16384 : HW_LDS_L(0)))   // the last step's LO unit + the gap
-#define EPI_LATE_DRAIN 0
 #include "gemm_v2_epilogue.inc"
-#undef EPI_LATE_DRAIN
-#undef EPI_STAGING_BASE
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    HW_BAR()   // the staging area is free again
+    H8C_BAR()   // the staging area is free again
     tile += G;
   }
 }
@@ -314,21 +277,11 @@ int mmsa_gemm_h8c_w8_dispatch(const GemmV2Args& a, int grid, bool gen, int act, 
   static MmsaPerDevice per_dev_ = {};
   (void)mmsa_per_device(per_dev_, [] {
 #define HW_ATTR(GEN_, ACT_) (void)hipFuncSetAttribute((const void*)gemm_h8c_w8_kernel<GEN_, ACT_>, hipFuncAttributeMaxDynamicSharedMemorySize, HW_LDS_TOTAL);
-    HW_ATTR(false, ACT_NONE) HW_ATTR(false, ACT_GELU) HW_ATTR(false, ACT_RELU) HW_ATTR(false, -1) HW_ATTR(true, -1) HW_ATTR(true, ACT_NONE)
+    V2_EPI_TABLE(HW_ATTR)
 #undef HW_ATTR
   });
-#define HW_LAUNCH(GEN_, ACT_) hipLaunchKernelGGL((gemm_h8c_w8_kernel<GEN_, ACT_>), dim3(grid), dim3(512), HW_LDS_TOTAL, stream, a)
-  if (gen) {
-    if (act == ACT_NONE) HW_LAUNCH(true, ACT_NONE);
-    else HW_LAUNCH(true, -1);
-  } else {
-    switch (act) {
-      case ACT_NONE: HW_LAUNCH(false, ACT_NONE); break;
-      case ACT_GELU: HW_LAUNCH(false, ACT_GELU); break;
-      case ACT_RELU: HW_LAUNCH(false, ACT_RELU); break;
-      default: HW_LAUNCH(false, -1); break;
-    }
-  }
+#define HW_LAUNCH(GEN_, ACT_) if (v2_epi_serves(gen, act, GEN_, ACT_)) hipLaunchKernelGGL((gemm_h8c_w8_kernel<GEN_, ACT_>), dim3(grid), dim3(512), HW_LDS_TOTAL, stream, a);
+  V2_EPI_TABLE(HW_LAUNCH)
 #undef HW_LAUNCH
   MMSA_CHECK_LAUNCH("gemm_split3(h8c x w8)");
   return MMSA_OK;

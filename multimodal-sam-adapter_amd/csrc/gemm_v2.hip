@@ -51,14 +51,9 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_v2_kernel(GemmV
   const int K = a.K;
   const int nk = K / V2_BK;
 
-  // XCD-aware logical id: blocks with equal blockIdx % 8 (same XCD under round-robin placement) get
-  // consecutive logical ids, hence neighbouring tiles.  Bijective for any grid size.
   const int G = gridDim.x;
   int rb = blockIdx.x;
-  {
-    const int xcd = rb & 7, q = G >> 3, r = G & 7;
-    rb = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (rb >> 3);
-  }
+  V2_XCD_REMAP(rb, G)   // XCD-aware logical id
   const int my_tiles = (a.ntiles - rb + G - 1) / G;   // tiles rb, rb+G, ...
   if (my_tiles <= 0) return;
   V2_SLACK_STAGGER(a, rb, G)
@@ -198,7 +193,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_v2_kernel(GemmV
       if (MXPAR && !V2_FP8_FIRST && !V2_EXP_NO_FP8) acc[ni][mi] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(opW[ni], opA[mi], acc[ni][mi], 1, 1, 0, MMSA_H8_MFMA_SCALE, 0, 0x7f7f7f7f); \
     }                                                                                                       \
   } else {                                                                                                  \
-    if (V2_SETPRIO) __builtin_amdgcn_s_setprio(1);                                                          \
     _Pragma("unroll") for (int mi = 0; mi < 4; ++mi) {                                                      \
       if constexpr (FMT == MMSA_FMT_F3) {   /* fp16 hi/lo pairs: the same three products on the fp16 MFMA */                 \
         acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(mx_h8, wl[ni]), __builtin_bit_cast(mx_h8, ah[mi]), acc[ni][mi], 0, 0, 0); \
@@ -210,7 +204,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_v2_kernel(GemmV
       acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[ni], ah[mi], acc[ni][mi], 0, 0, 0);          \
       }                                                                                                     \
     }                                                                                                       \
-    if (V2_SETPRIO) __builtin_amdgcn_s_setprio(0);                                                          \
   }
 #define K_STEP()                                                                                            \
   {                                                                                                         \
@@ -509,18 +502,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_v2_kernel(GemmV
     const int st_cur = st == 0 ? V2_NST - 1 : st - 1;   // ring slot of the k-tile just consumed: free until the next DMA into it (issued after the next barrier)
 
     if (V2_DBG(a) == 2 || V2_DBG(a) == 5 || V2_DBG(a) >= 64) { tile += G; continue; }
-    {
-      // the epilogue sees the lane id through an opaque copy (as in gemm_h8c.hip): what it derives from it -- row / column indices, 64-bit
-      // addresses -- is then computed per tile instead of being hoisted above the tile loop, where those values were live across the k loops
-      // and pushed loop invariants into scratch (round 4 ISA: 143-184 scratch instructions in the h8-line flavours; a scratch reload in
-      // front of an LDS-DMA instruction is an s_waitcnt vmcnt(0), i.e. a drain of the prefetch stream)
-      int lane_o_ = lane;
-      asm volatile("" : "+v"(lane_o_));
-      const int lane = lane_o_, l15 = lane_o_ & 15, g = lane_o_ >> 4;
 #define EPI_STAGING_BASE (smem + st_cur * V2_STAGE)
 #include "gemm_v2_epilogue.inc"
-#undef EPI_STAGING_BASE
-    }
     if constexpr (PP) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();   // slot st_cur (epilogue staging of every wave) is free again: group 0 DMAs into it next
@@ -606,28 +589,17 @@ int mmsa_gemm_v2_launch(const unsigned short* Ap, long lda, long strideA,
   (void)hipFuncSetAttribute((const void*)gemm_v2_kernel<GEN_, ACT_, true, 8, MMSA_FMT_H8>, hipFuncAttributeMaxDynamicSharedMemorySize, V2_LDS_BYTES(8));  \
   (void)hipFuncSetAttribute((const void*)gemm_v2_kernel<GEN_, ACT_, true, 8, MMSA_FMT_F3>, hipFuncAttributeMaxDynamicSharedMemorySize, V2_LDS_BYTES(8));  \
   (void)hipFuncSetAttribute((const void*)gemm_v2_kernel<GEN_, ACT_, false, 4, MMSA_FMT_B3>, hipFuncAttributeMaxDynamicSharedMemorySize, V2_LDS_BYTES(4));
-    V2_ATTR(false, ACT_NONE) V2_ATTR(false, ACT_GELU) V2_ATTR(false, ACT_RELU) V2_ATTR(false, -1) V2_ATTR(true, -1) V2_ATTR(true, ACT_NONE)
+    V2_EPI_TABLE(V2_ATTR)
 #undef V2_ATTR
   });
   // max_grid > 0: at most that many persistent workgroups -- a caller that runs independent chains on concurrent streams gives each
   // GEMM its share of the CUs, so that the kernels of two chains are resident together (one 144 KiB workgroup fits a CU).  The tile
   // shape below is chosen for THAT many CUs (the value of an output element does not depend on the shape of its tile).
   const int cus = (max_grid > 0 && max_grid < num_cus) ? max_grid : num_cus;
-  // h8c operands, 4-wave flavour (gemm_h8c4.hip; round 6; OFF by default, see MMSA_H8C4_DEFAULT below): 128 x 128 tiles, two workgroups per CU -- meant for launches whose 256-row tiling is at most ONE round of
-  // the CUs it may use (one tile per CU: fill -> k loop -> epilogue with nothing to overlap; proj 8192 x 1024 x 1024 is exactly that) and whose contraction is
-  // short enough that the tile is not its k loop (K <= 1024; lin2, K = 4096, measured slower in this form: profiles/r05_h8c_2wg_microbench.txt).  Plain epilogue
-  // family only (no activation, no pixel-shuffle / broadcast residual).  `flavour` 4 / 8 force either form (tests, A/B); results are bit-identical.
-#ifndef MMSA_H8C4_DEFAULT
-#define MMSA_H8C4_DEFAULT 0   // 1 (A/B builds: tools/build_variant.sh ... gemm_v2.hip -DMMSA_H8C4_DEFAULT=1): dispatch the 4-wave flavour by shape.  Measured step-neutral
-                              // (profiles/r06_h8c_4wave.txt: proj 58.2 vs 56.8 us, step 32.10 / 32.21 vs 32.29 / 32.17 ms) -- the -18 % of round 5's microbenchmark was its lighter
-                              // epilogue; with the site's real one (fp32 rows + planes + strip sums + residual) two resident workgroups pay for it twice on the same issue ports.
-                              // So: only when forced (`flavour` = 4: the bit-identity test)
-#endif
-  bool h8c4 = false;
-  if (h8c && !w8 && out_mode == 0 && resid_mod <= 0 && act == ACT_NONE && flavour != 8 && M >= 128) {
-    const long t256 = (long)cdiv(M, 256) * cdiv(N, V2_BN) * batch;
-    h8c4 = flavour == 4 || (t256 <= (long)cus && K <= MMSA_KNOB("MMSA_GEMM_H8C4_MAXK", 1024) && MMSA_KNOB("MMSA_GEMM_H8C4", MMSA_H8C4_DEFAULT) != 0);
-  }
+  // h8c operands, 4-wave flavour (gemm_h8c4.hip; round 6): 128 x 128 tiles, two workgroups per CU.  Only when forced (`flavour` = 4: the bit-identity test, A/B runs):
+  // dispatching it by shape -- launches of at most one round of 256-row tiles with K <= 1024 -- measured step-neutral (profiles/r06_h8c_4wave.txt).  Plain epilogue
+  // family only (no activation, no pixel-shuffle / broadcast residual); results are bit-identical to the 8-wave kernel's.
+  const bool h8c4 = flavour == 4 && h8c && !w8 && out_mode == 0 && resid_mod <= 0 && act == ACT_NONE && M >= 128;
   const int nw = h8c4 ? 4 : (h8 || rs_out || rn_mr || fmt == MMSA_FMT_F3) ? 8 : flavour ? flavour : (K <= MMSA_KNOB("MMSA_GEMM_NW4_MAXK", 256) && max_grid <= 0 ? 4 : 8);
   const int bm = nw * 32, wg_per_cu = nw == 4 ? 2 : 1;
   a.nbm = cdiv(M, bm);
@@ -690,24 +662,14 @@ int mmsa_gemm_v2_launch(const unsigned short* Ap, long lda, long strideA,
   if (h8c) return mmsa_gemm_h8c_dispatch(a, grid, gen, act, stream);
   const bool pp = MMSA_KNOB("MMSA_GEMM_PP", 1) != 0;   // 0 (debug-knob builds): every wave in phase (A/B timing)
 #define V2_LAUNCH(GEN_, ACT_)                                                                                              \
-  do {                                                                                                                     \
+  if (v2_epi_serves(gen, act, GEN_, ACT_)) {                                                                               \
     if (fmt == MMSA_FMT_H8) hipLaunchKernelGGL((gemm_v2_kernel<GEN_, ACT_, true, 8, MMSA_FMT_H8>), dim3(grid), dim3(512), V2_LDS_BYTES(8), stream, a);          \
     else if (fmt == MMSA_FMT_F3) hipLaunchKernelGGL((gemm_v2_kernel<GEN_, ACT_, true, 8, MMSA_FMT_F3>), dim3(grid), dim3(512), V2_LDS_BYTES(8), stream, a);     \
     else if (nw == 4) hipLaunchKernelGGL((gemm_v2_kernel<GEN_, ACT_, false, 4, MMSA_FMT_B3>), dim3(grid), dim3(256), V2_LDS_BYTES(4), stream, a);     \
     else if (pp) hipLaunchKernelGGL((gemm_v2_kernel<GEN_, ACT_, true, 8, MMSA_FMT_B3>), dim3(grid), dim3(512), V2_LDS_BYTES(8), stream, a);     \
     else hipLaunchKernelGGL((gemm_v2_kernel<GEN_, ACT_, false, 8, MMSA_FMT_B3>), dim3(grid), dim3(512), V2_LDS_BYTES(8), stream, a);            \
-  } while (0)
-  if (gen) {
-    if (act == ACT_NONE) V2_LAUNCH(true, ACT_NONE);   // the up-conv / pos-embed GEMMs: unrolled epilogue
-    else V2_LAUNCH(true, -1);
-  } else {
-    switch (act) {
-      case ACT_NONE: V2_LAUNCH(false, ACT_NONE); break;
-      case ACT_GELU: V2_LAUNCH(false, ACT_GELU); break;
-      case ACT_RELU: V2_LAUNCH(false, ACT_RELU); break;
-      default: V2_LAUNCH(false, -1); break;
-    }
   }
+  V2_EPI_TABLE(V2_LAUNCH)   // (gen: the up-conv / pos-embed GEMMs; with no activation they run the unrolled epilogue)
 #undef V2_LAUNCH
   MMSA_CHECK_LAUNCH("gemm_split3(v2)");
   return MMSA_OK;

@@ -1,7 +1,17 @@
 // Tile-boundary epilogue of the LDS-DMA GEMM kernels, included textually into the kernel body (gemm_v2.hip, gemm_h8c.hip).  Expects in scope:
 // GemmV2Args a; template parameters GEN, ACT, PP (+ constexpr EPI_UNROLL, V2_BM, V2_NST); acc[4][4] (accumulators, zeroed on the way out);
-// tile (output tile index), wave / lane / wm / wn / l15 / g, ni4 / swid, nowait; smem; and EPI_STAGING_BASE = byte address of >= 34816 B of
-// LDS that no DMA in flight targets (8 waves x 16 rows x 68 floats).
+// tile (output tile index), wave / lane / wm / wn, ni4 / swid, nowait; smem; and EPI_STAGING_BASE = byte address of >= 34816 B of
+// LDS that no DMA in flight targets (8 waves x 16 rows x 68 floats), #defined by the kernel in front of the #include and #undef'd here.
+    {
+      // The epilogue sees the lane id through an opaque copy: everything it derives from it (row / column indices, 64-bit addresses) is
+      // computed HERE, per tile.  Hoisted above the tile loop -- what LICM does with them otherwise -- those values are live across the k
+      // loops, whose steady state needs 192 registers for accumulators, hi fragments and fp8 tuples alone: ~200 spilled registers in
+      // gemm_h8c.hip, 143-184 scratch instructions in gemm_v2.hip's h8-line flavours (round 4 ISA), reloaded (scratch loads, one exposed
+      // round trip per group) in every epilogue -- and a scratch reload in front of an LDS-DMA instruction is an s_waitcnt vmcnt(0), i.e.
+      // a drain of the prefetch stream.
+      int lane_o_ = lane;
+      asm volatile("" : "+v"(lane_o_));
+      const int lane = lane_o_, l15 = lane_o_ & 15, g = lane_o_ >> 4;
     // ---- tile boundary.  MFMA layout: lane holds C[m = ..+l15][n = ..+4g .. +3].  Each wave transposes 16 x 64
     // sub-tiles through the ring slot it has just finished computing from, so that residual loads and output stores
     // are FULL 256-byte row segments (4 rows per wave-instruction).  After the transpose a lane owns the SAME 4
@@ -19,13 +29,6 @@
       float* C = a.C ? a.C + (long)bz * a.strideC : nullptr;
       unsigned short* Cp = a.Cp ? a.Cp + (long)bz * a.strideCp : nullptr;
       const bool vec_ok = ((a.ldc & 3) == 0) && (!resid || (a.ldr & 3) == 0) && ((a.N & 3) == 0) && ((a.ldcp & 3) == 0);
-#ifndef EPI_LATE_DRAIN
-#define EPI_LATE_DRAIN 0   // 1 (gemm_h8c.hip built with -DHC_LATE_DRAIN=1, an A/B option): operand pieces of the NEXT tile are still in flight when the epilogue starts.  Whichever epilogue path runs executes EPI_DRAIN()
-                           // once, after it has requested its own vectors (bias, column sums, row statistics, first residual rows) and before its first store: one wait
-                           // covers both, and the barrier behind the epilogue makes the pieces visible to every wave
-#define EPI_LATE_DRAIN_DEFAULTED_ 1
-#endif
-#define EPI_DRAIN() do { if (EPI_LATE_DRAIN) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); } while (0)
       if constexpr (PP) {
         nowait = 1;   // both groups drained before the last barrier of the k loop: k-tile j (and j+1) are visible
       } else {
@@ -44,7 +47,7 @@
       const bool cp_h8c = cp_base == MMSA_FMT_H8C;
       const int cp_kpad = MMSA_PAD64((GEN && a.out_mode == 1) ? a.ps_C : a.N);   // h8c: fp16 values per row of the output planes
 #include "gemm_epilogue_regs.inc"
-      if (!regs_done) { EPI_DRAIN();   // ---- the LDS-staged epilogue: ragged tiles, 96-column tiles, pixel-shuffle stores, split plane formats, other activations
+      if (!regs_done) {   // ---- the LDS-staged epilogue: ragged tiles, 96-column tiles, pixel-shuffle stores, split plane formats, other activations
       // clamp watch of this path (common.h): checked per stored group, nothing carried (a running maximum kept across this path's unrolled sub-tiles cost the
       // kernel ~200 bytes of scratch and the extractor output projection 35 %: profiles/r05_clamp_watch.txt); a split output (f3 | h8 columns) is held to
       // the h8 limit throughout
@@ -361,13 +364,10 @@
       }
       }
     }
-#undef EPI_DRAIN
+    }
+#undef EPI_STAGING_BASE
 #ifdef EPI_STAMP_DEFAULTED_
 #undef EPI_STAMP_DEFAULTED_
 #undef EPI_STAMP
 #undef EPI_STAMP_WAIT
-#endif
-#ifdef EPI_LATE_DRAIN_DEFAULTED_
-#undef EPI_LATE_DRAIN_DEFAULTED_
-#undef EPI_LATE_DRAIN
 #endif

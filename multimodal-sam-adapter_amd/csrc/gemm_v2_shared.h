@@ -1,5 +1,5 @@
-// Shared by the LDS-DMA GEMM kernels (gemm_v2.hip: bf16 hi/lo and h8 line planes; gemm_h8c.hip: h8c planes): argument block, tile
-// geometry, tile order.  See gemm_v2.hip for the design notes.
+// Shared by the LDS-DMA GEMM kernels (gemm_v2.hip: bf16 hi/lo and h8 line planes; gemm_h8c*.hip through gemm_h8c_shared.h: h8c planes): argument block,
+// tile geometry, tile order, XCD block remap, the list of epilogue instantiations.  See gemm_v2.hip for the design notes.
 #pragma once
 #include "common.h"
 #include <type_traits>
@@ -58,9 +58,6 @@ struct GemmV2Args {
 #ifndef V2_FAST_STEPS
 #define V2_FAST_STEPS 1   // 0: every k-tile runs the general step (A/B timing; the ablation build -DV2_KABL needs it)
 #endif
-#ifndef V2_SETPRIO
-#define V2_SETPRIO 0   // s_setprio(1) around the MFMA chunks: measured no effect on this kernel (same-box A/B)
-#endif
 
 // Slack stagger (round 5).  When the tiles do not divide evenly among the persistent workgroups, most workgroups walk one tile fewer than the longest ones and
 // have one tile period of slack.  Started together, all workgroups reach their epilogues together, and the epilogues of the adapter-token GEMMs (read-modify-write
@@ -101,6 +98,22 @@ extern "C" int mmsa_debug_stamps(unsigned long long* host_out) {
 #define CLK_SAMPLE(o_)
 #define STAMP(i_)
 #endif
+
+// XCD-aware logical workgroup id: blocks with equal blockIdx % 8 (same XCD under round-robin placement) get consecutive logical ids, hence
+// neighbouring tiles.  Bijective for any grid size.  rb_ = an int variable holding blockIdx.x, remapped in place.  (A macro: as a __forceinline__ function it
+// changed the register allocation of gemm_h8c4_kernel and of four gemm_v2_kernel instantiations.)
+#define V2_XCD_REMAP(rb_, G_) { const int xcd = rb_ & 7, q = (G_) >> 3, r = (G_) & 7; rb_ = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (rb_ >> 3); }
+
+// The epilogue instantiations (GEN, ACT) every dispatcher compiles, stated once: X_(GEN, ACT) per pair.  v2_epi_serves(gen, act, GEN, ACT): the pair
+// that runs a launch with (gen, act) -- the listed pair itself, else the runtime-activation one (ACT = -1) of its GEN.  Exactly one pair serves a launch.
+#define V2_EPI_TABLE(X_) X_(false, ACT_NONE) X_(false, ACT_GELU) X_(false, ACT_RELU) X_(false, -1) X_(true, -1) X_(true, ACT_NONE)
+inline bool v2_epi_serves(bool gen, int act, bool GEN, int ACT) {
+  bool listed = false;
+#define V2_EPI_LISTED_(GEN_, ACT_) listed = listed || (gen == (GEN_) && act == (ACT_));
+  V2_EPI_TABLE(V2_EPI_LISTED_)
+#undef V2_EPI_LISTED_
+  return gen == GEN && (listed ? act == ACT : ACT == -1);
+}
 
 // Tile index inside a batch -> (m-tile, n-tile).  The 32 workgroups that share an XCD (consecutive logical ids) hold 32 consecutive
 // tile indices at any time; row-major order made those one row of up to 32 n-tiles, i.e. every XCD streamed the WHOLE weight

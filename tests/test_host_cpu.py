@@ -634,6 +634,14 @@ def test_gemm_kernels_do_not_spill_into_their_k_loops():
     assert len(res4) >= 1
     for k, v in res4.items():
         assert v["scratch"] == 0 and v["vgprs"] <= 256, f"{k}: {v['scratch']} scratch instructions, {v['vgprs']} VGPRs"
+    res_w8 = mod.census(os.path.join(ROOT, "multimodal-sam-adapter_amd", "csrc", "gemm_h8c_w8.hip"))   # the fp8-weight kernel: gemm_h8c's bound
+    assert len(res_w8) >= 6
+    for k, v in res_w8.items():
+        assert v["scratch"] <= 10, f"{k}: {v['scratch']} scratch instructions"
+    res_v2 = mod.census(os.path.join(ROOT, "multimodal-sam-adapter_amd", "csrc", "gemm_v2.hip"))
+    assert len(res_v2) >= 30
+    for k, v in res_v2.items():
+        assert v["scratch"] == 0, f"{k}: {v['scratch']} scratch instructions"
 
 
 def test_kernel_gelu_coefficients_hold_their_error_bound():
