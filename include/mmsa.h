@@ -375,6 +375,30 @@ int mmsa_preprocess_resize_crops(const void* src0, int dtype0, const void* src1,
                                  int n, float* dst, int hc, int wc, int Hr, int Wr, const int* xofs, const void* xcoef, const int* yofs,
                                  const void* ycoef, int fixed_point, mmsa_stream_t stream);
 
+/* --- evaluation (segmentation/mmseg_custom/datasets/DELIVER.py:219-259 `pre_eval` -> apis/evaluation/metrics_micro.py:26-86 `intersect_and_union`): the
+ *     confusion counts of a uint8 class map against a uint8 label map.  counts = int64 [n_slots, C + 1, C + 1], counts[s][l][p] = pixels of the images
+ *     routed to slot s with transformed label class l and predicted class p; index C = a value outside [0, C) that is not ignored (what
+ *     torch.histc(min=0, max=C-1) drops from one of its histograms only); pixels whose label is ignored are counted nowhere.  The reference's four
+ *     histograms: area_intersect = diag[:C]; area_pred_label[p] = sum over all C + 1 rows of column p < C; area_label[l] = sum over all C + 1 columns
+ *     of row l < C; area_union = area_pred_label + area_label - area_intersect.  The call ADDS into counts (the caller zeroes it): integer sums, the
+ *     same bytes whatever the order of arrival.
+ *     lut: 256 DEVICE bytes, raw label byte -> class 0 .. C - 1, C (kept, out of range; any other code counts as C too) or 255 (ignored): the whole of
+ *       label_map / reduce_zero_label / ignore_index (metrics_micro.py:66-74; mmsa/evaluate.py builds it).
+ *     ymap [H], xmap [W]: optional DEVICE int32 source-index tables, both or neither: the label is read at label[b, ymap[y], xmap[x]] -- the
+ *       nearest-neighbour resize of Resize_multimodal._resize_seg (datasets/pipelines/transform.py:1169-1188) -- clamped into the label map whatever
+ *       they hold.  Without them Hl == H and Wl == W is required.
+ *     slots: HOST int [B] (copied into the launch arguments, B <= 64), each in [0, n_slots): the count slot of image b.  0 .. B - 1 = per-image counts
+ *       as pre_eval returns them; several images on one slot = a per-case total.
+ *     2 <= C <= 126 (the (C + 1)^2 uint32 histogram a workgroup keeps in LDS must fit 64 KiB).
+ *   eval_confusion_u8: pred [B, H, W], label [B, Hl, Wl].
+ *   slide_argmax_eval: mmsa_slide_argmax and the counts of its class map in ONE launch; out == NULL writes no map.  Uncovered pixels (class 255)
+ *     count under predicted index C, as a 255 in a map given to eval_confusion_u8 does. --- */
+int mmsa_eval_confusion_u8(const unsigned char* pred, const unsigned char* label, int B, int H, int W, int Hl, int Wl, const unsigned char* lut,
+                           int C, const int* ymap, const int* xmap, const int* slots, int n_slots, int64_t* counts, mmsa_stream_t stream);
+int mmsa_slide_argmax_eval(const float* logits, int n, int C, int hs, int ws, const int* windows, unsigned char* out, int B, int H, int W,
+                           int hc, int wc, int* uncovered, const unsigned char* label, int Hl, int Wl, const unsigned char* lut, const int* ymap,
+                           const int* xmap, const int* slots, int n_slots, int64_t* counts, mmsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

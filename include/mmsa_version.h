@@ -4,8 +4,9 @@
  * 102 (round 6): mmsa_convnext_mlp_fused takes clamp_max; new entry mmsa_msda_fused_planes.
  * 103: mmsa_gemm_split3's `fmt` accepts MMSA_FMT_W8 (fp8 weights against h8c activation planes).
  * 104: new entries mmsa_preprocess_nhwc / mmsa_preprocess_crops (raw HWC frames -> normalised NCHW, whole or as windows).
- * 105: new entries mmsa_preprocess_resize_nhwc / mmsa_preprocess_resize_crops (the same from sources of another size: bilinear resize first). */
+ * 105: new entries mmsa_preprocess_resize_nhwc / mmsa_preprocess_resize_crops (the same from sources of another size: bilinear resize first).
+ * 106: new entries mmsa_eval_confusion_u8 / mmsa_slide_argmax_eval (confusion counts of a class map against a label map, alone or fused into the class-map kernel). */
 #ifndef MMSA_VERSION_H
 #define MMSA_VERSION_H
-#define MMSA_ABI_VERSION 105
+#define MMSA_ABI_VERSION 106
 #endif

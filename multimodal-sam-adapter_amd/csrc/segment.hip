@@ -7,6 +7,7 @@
 //   argmax_nchw         : seg_logit.argmax(dim=1) (ED:477; the softmax of ED:449 is monotonic) -> uint8 class map.
 // All are one pass over the canvas, HBM-bound.
 #include "common.h"
+#include "eval_hist.h"
 
 // No fused multiply-add contraction in this file: the canvas path (bilinear_accum + div_count + argmax) and the one-pass class map
 // (slide_argmax) must round the SAME interpolation formula identically, or an exact tie between two classes in one of them is not a
@@ -128,54 +129,40 @@ extern "C" int mmsa_crop_batch_nchw(const float* src, int B, int C, int H, int W
 // the whole-image `resize x4 + argmax` of ED:90-94,477.  Pixels no window covers make the call fail (ED:220 asserts the same).
 __global__ __launch_bounds__(256) void slide_argmax_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
                                                            int H, int W, int hc, int wc, float rh, float rw, WindowTable wt, int* __restrict__ uncovered) {
-  const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, b = blockIdx.z;
-  if (x >= W) return;
-  // covering windows (at most 8 per pixel) and their 4-tap coordinates (PyTorch upsample_bilinear2d: src = (dst + 0.5) * in/out - 0.5,
-  // clamped at 0).  The slot arrays are only ever indexed by unrolled constants (predicated inserts), so they live in registers.
-  int nk = 0, kk[8], o00[8], o01[8], o10[8], o11[8];
-  float lhs[8], lws[8];
-#pragma unroll
-  for (int q = 0; q < 8; ++q) { kk[q] = 0; o00[q] = o01[q] = o10[q] = o11[q] = 0; lhs[q] = lws[q] = 0.f; }
-  for (int k = 0; k < wt.n; ++k) {
-    if (wt.b[k] != b) continue;
-    const int i = y - wt.y0[k], j = x - wt.x0[k];
-    if (i < 0 || i >= hc || j < 0 || j >= wc) continue;
-    float sh = ((float)i + 0.5f) * rh - 0.5f, sw = ((float)j + 0.5f) * rw - 0.5f;
-    sh = sh < 0.f ? 0.f : sh;
-    sw = sw < 0.f ? 0.f : sw;
-    const int h0 = min((int)sh, hs - 1), w0 = min((int)sw, ws - 1);
-    const int h1 = h0 + (h0 < hs - 1 ? 1 : 0), w1 = w0 + (w0 < ws - 1 ? 1 : 0);
-#pragma unroll
-    for (int q = 0; q < 8; ++q)
-      if (q == nk) {
-        kk[q] = k; lhs[q] = sh - (float)h0; lws[q] = sw - (float)w0;
-        o00[q] = h0 * ws + w0; o01[q] = h0 * ws + w1; o10[q] = h1 * ws + w0; o11[q] = h1 * ws + w1;
-      }
-    ++nk;
+#define SLIDE_EVAL 0
+#define SLIDE_Y blockIdx.y
+#define SLIDE_EXIT return
+#include "slide_pixel.inc"
+#undef SLIDE_EVAL
+#undef SLIDE_Y
+#undef SLIDE_EXIT
+}
+
+// slide_argmax_kernel + the confusion counts of its class map in the same pass (csrc/evaluate.hip does the same from a stored map): the workgroup's
+// 256-pixel segments of SLIDE_EVAL_ROWS rows go into a private LDS histogram, whose non-zero bins are added to the int64 counts of the image's slot.
+// One row = one flush per 256-pixel segment is the measured choice (profiles/evaluate.txt): eight rows per workgroup cost + 28 / + 194 us over the
+// plain kernel where one row costs + 19 / + 18 us (the rows of a workgroup run one after the other, with an eighth of the workgroups in flight).
+// out == NULL: no map is written.
+#define SLIDE_EVAL_ROWS 1
+__global__ __launch_bounds__(256) void slide_argmax_eval_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
+                                                                int H, int W, int hc, int wc, float rh, float rw, WindowTable wt, int* __restrict__ uncovered,
+                                                                EvalLabel ev, EvalSlots es) {
+  extern __shared__ unsigned eval_lds[];
+  const int nbins = (C + 1) * (C + 1);
+  unsigned char* lut_s = (unsigned char*)(eval_lds + nbins);
+  eval_hist_init(eval_lds, lut_s, ev.lut, nbins);
+  unsigned* hist = eval_lds;
+  const int row1 = min(H, ((int)blockIdx.y + 1) * SLIDE_EVAL_ROWS);
+  for (int row = (int)blockIdx.y * SLIDE_EVAL_ROWS; row < row1; ++row) {
+#define SLIDE_EVAL 1
+#define SLIDE_Y row
+#define SLIDE_EXIT continue
+#include "slide_pixel.inc"
+#undef SLIDE_EVAL
+#undef SLIDE_Y
+#undef SLIDE_EXIT
   }
-  if (nk == 0 || nk > 8) {   // no window, or more than 8 overlapping windows per pixel: not supported -- counted, and the pixel gets 255, never an unwritten byte
-    atomicAdd(uncovered, 1);
-    out[((long)b * H + y) * W + x] = 255;
-    return;
-  }
-  const float cnt = (float)nk;
-  float best = -INFINITY;
-  int bi = 0;
-  for (int c = 0; c < C; ++c) {
-    float acc = 0.f;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      if (q < nk) {
-        const float* sp = logits + ((long)kk[q] * C + c) * hs * ws;
-        const float lh = lhs[q], lw = lws[q];
-        const float v = (1.f - lh) * ((1.f - lw) * sp[o00[q]] + lw * sp[o01[q]]) + lh * ((1.f - lw) * sp[o10[q]] + lw * sp[o11[q]]);
-        acc = q == 0 ? v : acc + v;     // window order: the first window WRITES (0 + v == v), later ones add
-      }
-    }
-    const float p = acc / cnt;
-    if (c == 0 || p > best) { best = p; bi = c; }
-  }
-  out[((long)b * H + y) * W + x] = (unsigned char)bi;
+  eval_hist_flush(eval_lds, ev.counts + (long)es.s[blockIdx.z] * nbins, nbins);
 }
 
 extern "C" int mmsa_slide_argmax(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out,
@@ -187,5 +174,23 @@ extern "C" int mmsa_slide_argmax(const float* logits, int n, int C, int hs, int 
   hipLaunchKernelGGL(slide_argmax_kernel, dim3(cdiv(W, 256), H, B), dim3(256), 0, stream, logits, C, hs, ws, out, H, W, hc, wc,
                      (float)hs / (float)hc, (float)ws / (float)wc, wt, uncovered);
   MMSA_CHECK_LAUNCH("slide_argmax");
+  return MMSA_OK;
+}
+
+extern "C" int mmsa_slide_argmax_eval(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out /* or NULL */,
+                                      int B, int H, int W, int hc, int wc, int* uncovered, const unsigned char* label, int Hl, int Wl,
+                                      const unsigned char* lut, const int* ymap, const int* xmap, const int* slots /* HOST [B] */, int n_slots,
+                                      int64_t* counts, hipStream_t stream) {
+  MMSA_CHECK_ARG(logits && uncovered && hs > 0 && ws > 0 && hc > 0 && wc > 0 && B > 0 && H <= 65535 && B <= 65535, "slide_argmax_eval: bad args");
+  EvalSlots es;
+  int rc = eval_check("slide_argmax_eval", label, B, H, W, Hl, Wl, lut, C, ymap, xmap, slots, n_slots, counts, es);
+  if (rc) return rc;
+  WindowTable wt;
+  rc = fill_windows(wt, windows, n, B, H, W, hc, wc, "slide_argmax_eval");
+  if (rc) return rc;
+  const EvalLabel ev = {label, lut, ymap, xmap, (unsigned long long*)counts, Hl, Wl, C};
+  hipLaunchKernelGGL(slide_argmax_eval_kernel, dim3(cdiv(W, 256), cdiv(H, SLIDE_EVAL_ROWS), B), dim3(256), (size_t)(C + 1) * (C + 1) * 4 + 256, stream, logits, C, hs, ws, out,
+                     H, W, hc, wc, (float)hs / (float)hc, (float)ws / (float)wc, wt, uncovered, ev, es);
+  MMSA_CHECK_LAUNCH("slide_argmax_eval");
   return MMSA_OK;
 }

@@ -1,0 +1,74 @@
+// The pixel body of the two class-map kernels of csrc/segment.hip, included once per kernel (like the GEMM epilogues' .inc files):
+//   SLIDE_EVAL 0: slide_argmax_kernel, statement for statement what it always was;
+//   SLIDE_EVAL 1: slide_argmax_eval_kernel -- the pixel's (label class, predicted class) pair also goes into the workgroup's LDS histogram
+//                 `hist` (csrc/eval_hist.h; `ev` = the label side, `lut_s` = its LUT in LDS) and the map is written only when `out` is given.
+// SLIDE_Y is the pixel's row: blockIdx.y in the first kernel, the row variable of the second kernel's loop over its workgroup's rows.
+// SLIDE_EXIT leaves the body: `return` in the first kernel, `continue` with the next row in the second, which still has its histogram to flush.
+// SLIDE_EXIT MUST NOT be used inside a loop of this body: there `continue` would go on with that loop in the second kernel only, where `return`
+// leaves the first (every use below is at the body's top level).  In scope: logits, C, hs, ws, out, H, W, hc, wc, rh, rw, wt, uncovered.
+  const int x = blockIdx.x * 256 + threadIdx.x, y = SLIDE_Y, b = blockIdx.z;
+  if (x >= W) SLIDE_EXIT;
+#if SLIDE_EVAL
+  int ebin = -1;                                // row offset of the pixel's label class in the histogram, -1 = ignored
+  {
+    const int ys = ev.ymap ? min(max(ev.ymap[y], 0), ev.Hl - 1) : y, xs = ev.xmap ? min(max(ev.xmap[x], 0), ev.Wl - 1) : x;
+    const int l = lut_s[ev.label[((long)b * ev.Hl + ys) * ev.Wl + xs]];
+    if (l != MMSA_EVAL_IGNORE) ebin = min(l, C) * (C + 1);
+  }
+#endif
+  // covering windows (at most 8 per pixel) and their 4-tap coordinates (PyTorch upsample_bilinear2d: src = (dst + 0.5) * in/out - 0.5,
+  // clamped at 0).  The slot arrays are only ever indexed by unrolled constants (predicated inserts), so they live in registers.
+  int nk = 0, kk[8], o00[8], o01[8], o10[8], o11[8];
+  float lhs[8], lws[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) { kk[q] = 0; o00[q] = o01[q] = o10[q] = o11[q] = 0; lhs[q] = lws[q] = 0.f; }
+  for (int k = 0; k < wt.n; ++k) {
+    if (wt.b[k] != b) continue;
+    const int i = y - wt.y0[k], j = x - wt.x0[k];
+    if (i < 0 || i >= hc || j < 0 || j >= wc) continue;
+    float sh = ((float)i + 0.5f) * rh - 0.5f, sw = ((float)j + 0.5f) * rw - 0.5f;
+    sh = sh < 0.f ? 0.f : sh;
+    sw = sw < 0.f ? 0.f : sw;
+    const int h0 = min((int)sh, hs - 1), w0 = min((int)sw, ws - 1);
+    const int h1 = h0 + (h0 < hs - 1 ? 1 : 0), w1 = w0 + (w0 < ws - 1 ? 1 : 0);
+#pragma unroll
+    for (int q = 0; q < 8; ++q)
+      if (q == nk) {
+        kk[q] = k; lhs[q] = sh - (float)h0; lws[q] = sw - (float)w0;
+        o00[q] = h0 * ws + w0; o01[q] = h0 * ws + w1; o10[q] = h1 * ws + w0; o11[q] = h1 * ws + w1;
+      }
+    ++nk;
+  }
+  if (nk == 0 || nk > 8) {   // no window, or more than 8 overlapping windows per pixel: not supported -- counted, and the pixel gets 255, never an unwritten byte
+    atomicAdd(uncovered, 1);
+#if SLIDE_EVAL
+    if (out) out[((long)b * H + y) * W + x] = 255;
+    eval_hist_add(hist, ebin < 0 ? -1 : ebin + C, 1u);     // class 255 counts under pred index C
+#else
+    out[((long)b * H + y) * W + x] = 255;
+#endif
+    SLIDE_EXIT;
+  }
+  const float cnt = (float)nk;
+  float best = -INFINITY;
+  int bi = 0;
+  for (int c = 0; c < C; ++c) {
+    float acc = 0.f;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      if (q < nk) {
+        const float* sp = logits + ((long)kk[q] * C + c) * hs * ws;
+        const float lh = lhs[q], lw = lws[q];
+        const float v = (1.f - lh) * ((1.f - lw) * sp[o00[q]] + lw * sp[o01[q]]) + lh * ((1.f - lw) * sp[o10[q]] + lw * sp[o11[q]]);
+        acc = q == 0 ? v : acc + v;     // window order: the first window WRITES (0 + v == v), later ones add
+      }
+    }
+    const float p = acc / cnt;
+    if (c == 0 || p > best) { best = p; bi = c; }
+  }
+#if SLIDE_EVAL
+  if (out) out[((long)b * H + y) * W + x] = (unsigned char)bi;
+  eval_hist_add(hist, ebin < 0 ? -1 : ebin + bi, 1u);
+#else
+  out[((long)b * H + y) * W + x] = (unsigned char)bi;
+#endif

@@ -10,6 +10,8 @@ from .head import SegformerHead
 from .chains import AttentionRangeError, Chains, Replay
 from . import preprocess  # noqa: F401  (raw frames -> normalised NCHW, whole or as windows; FrameFeeder)
 from .preprocess import FrameFeeder, Preprocess
+from . import evaluate  # noqa: F401  (confusion counts and mIoU on device: LabelPrep, confusion, Evaluator)
+from .evaluate import Evaluator, LabelPrep, confusion
 from .registry import BACKBONES, HEADS, build_backbone, build_head
 
 for _cls in (SAMAdapterbimodalMixModNewInTwinConvNEW, SAMAdapterbimodalMixModNewInTwinConvNEWwithcp):
@@ -32,4 +34,4 @@ if not _HAVE_MMSEG:     # local registry (no mmseg in the process): nothing to o
 
 __all__ = ["SegformerHead", "HEADS", "build_head", "register_head", "SAMAdapterbimodalMixModNewInTwinConvNEW", "SAMAdapterbimodalMixModNewInTwinConvNEWwithcp",
            "BACKBONES", "build_backbone", "ops", "lib", "inference", "Chains", "Replay", "AttentionRangeError", "OperandRangeError",
-           "preprocess", "Preprocess", "FrameFeeder"]
+           "preprocess", "Preprocess", "FrameFeeder", "evaluate", "Evaluator", "LabelPrep", "confusion"]

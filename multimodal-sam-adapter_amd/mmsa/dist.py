@@ -60,6 +60,17 @@ def allgather_logits(local, global_batch=None):
     return torch.cat([out[r * cap:r * cap + (hi - lo)] for r, (lo, hi) in enumerate(sizes)], 0)
 
 
+def allreduce_counts(counts):
+    """Evaluation across ranks: ONE all_reduce(SUM) of the int64 confusion counts (mmsa.evaluate; [n_slots, C + 1, C + 1], about 5 KB per slot at 25
+    classes), in place, where a host evaluation gathers every rank's class maps or logits (13 MB per rank and step).  Integer sums: the same bytes on
+    every rank whatever the reduction order.  The slots must mean the same on every rank (cases, or a per-rank image range in a shared buffer)."""
+    if counts.dtype != torch.int64:
+        raise ValueError(f"allreduce_counts: int64 counts expected, got {counts.dtype}")
+    if world() > 1:
+        dist.all_reduce(counts, op=dist.ReduceOp.SUM)
+    return counts
+
+
 class LogitsGather:
     """The step's all-gather, pipelined behind the NEXT step (round 6).
 

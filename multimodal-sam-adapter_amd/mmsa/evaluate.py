@@ -1,0 +1,356 @@
+"""The output side of the reference's `tools/test.py` loop on device: what `dataset.pre_eval` -> `intersect_and_union` -> `pre_eval_to_metrics` /
+`total_area_to_metrics` do with a class map (segmentation/mmseg_custom/datasets/DELIVER.py:194-259, apis/evaluation/metrics_micro.py:26-86, 451-526).
+
+The device keeps ONE integer matrix per count slot, int64 [C + 1, C + 1], counts[label class, predicted class]; index C = "a value outside [0, C) that is
+not ignored" (what torch.histc(min=0, max=C-1) drops from one of its histograms only), ignored pixels are counted nowhere.  The reference's four
+histograms follow from it (`areas_of`).  `label_map`, `reduce_zero_label` and `ignore_index` are one 256-byte LUT applied to the raw label byte; the
+nearest-neighbour label resize of `Resize_multimodal._resize_seg` (datasets/pipelines/transform.py:1169-1188) is a pair of per-axis index tables.
+Counting is either a pass of its own over a stored map (`confusion`, mmsa_eval_confusion_u8) or part of the class-map kernel (`labels=` / `evaluator=`
+of mmsa.inference's class-map calls, mmsa_slide_argmax_eval).  Only `Evaluator.areas()` copies anything to the host: (C + 1)^2 integers per slot.
+
+Deviation from the reference, on purpose: it sums per-image float32 histograms in float32 (metrics_micro.py:416-419), exact only below 2^24 pixels per
+class and case; the int64 counts here are exact at any size, and the metrics are formed in float64.  There is no CPU path for the counting."""
+import ctypes
+from collections import OrderedDict
+
+import numpy as np
+import torch
+
+from . import lib
+from . import ops
+from .preprocess import _capturing, rescale_size
+
+IGNORE = 255            # LUT code of an ignored label byte (csrc/eval_hist.h MMSA_EVAL_IGNORE)
+MAX_IMAGES = 64         # images per launch (the slot table travels in the launch arguments)
+FUSED_DEFAULT = False   # measured (profiles/evaluate.txt): the class map followed by the standalone pass is 4-9 us faster than the fused launch, beyond
+                        # the yardstick's spread: two launches by default; the fused entry is reached with fused=True / return_map=False
+
+_METRICS = ("mIoU", "mDice", "mFscore", "microIoU")
+
+
+# ---- host-side restatements (numpy) ----
+def label_bytes(ignore_index=255, label_map=None, reduce_zero_label=False):
+    """What the reference's sequence (metrics_micro.py:66-74) makes of each of the 256 label byte values -> (transformed uint8 [256], kept bool [256]):
+    the `label_map` entries one after the other in dict order (a later entry sees what an earlier one wrote), then `reduce_zero_label` in uint8
+    arithmetic (0 -> 255, minus 1 with wrap-around, 254 -> 255), then the compare with `ignore_index`."""
+    t = np.arange(256, dtype=np.uint8)
+    for old, new in (label_map or {}).items():
+        if not 0 <= int(new) <= 255:
+            raise ValueError(f"mmsa.evaluate: label_map maps {old} to {new}, which a uint8 label cannot hold")
+        t[t == old] = new
+    if reduce_zero_label:
+        t[t == 0] = 255
+        t = t - np.uint8(1)
+        t[t == 254] = 255
+    return t, t != ignore_index
+
+
+def label_lut(num_classes, ignore_index=255, label_map=None, reduce_zero_label=False):
+    """The device LUT uint8 [256]: class 0 .. C - 1, C = kept but outside [0, C), IGNORE = dropped by the ignore mask."""
+    C = int(num_classes)
+    if not 2 <= C <= 254:
+        raise ValueError(f"mmsa.evaluate: num_classes {num_classes}; a uint8 class map has 2..254 classes")
+    t, keep = label_bytes(ignore_index, label_map, reduce_zero_label)
+    return np.where(keep, np.minimum(t, C), IGNORE).astype(np.uint8)
+
+
+def nearest_axis_table(n_src, n_dst):
+    """One axis of cv2.resize(INTER_NEAREST) as OpenCV's resize.cpp states it: src = min(floor(d * (1.0 / (double(n_dst) / n_src))), n_src - 1), int32 [n_dst]."""
+    ifx = 1.0 / (np.float64(n_dst) / np.float64(n_src))
+    return np.minimum(np.floor(np.arange(n_dst, dtype=np.float64) * ifx).astype(np.int64), n_src - 1).astype(np.int32)
+
+
+def areas_of(counts):
+    """int64 [..., C + 1, C + 1] counts -> (area_intersect, area_union, area_pred_label, area_label), each int64 [..., C] (metrics_micro.py:78-86)."""
+    counts = np.asarray(counts, dtype=np.int64)
+    C = counts.shape[-1] - 1
+    inter = np.diagonal(counts, axis1=-2, axis2=-1)[..., :C].copy()
+    pred = counts.sum(-2)[..., :C]
+    label = counts.sum(-1)[..., :C]
+    return inter, pred + label - inter, pred, label
+
+
+def area_metrics(area_intersect, area_union, area_pred_label, area_label, metric=("mIoU",), nan_to_num=None, beta=1):
+    """`total_area_to_metrics` (metrics_micro.py:451-526) in float64 on integer areas [C]: 'aAcc' and, per metric, 'IoU' / 'Acc', 'Dice' / 'Acc',
+    'Fscore' / 'Precision' / 'Recall' per class.  0 / 0 is NaN as in the reference; `nan_to_num` replaces it afterwards (np.nan_to_num)."""
+    metric = [metric] if isinstance(metric, str) else list(metric)
+    if not set(metric).issubset(_METRICS):
+        raise KeyError(f"metrics {metric} is not supported")
+    i, u, p, l = (np.asarray(a, dtype=np.float64) for a in (area_intersect, area_union, area_pred_label, area_label))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out = OrderedDict(aAcc=np.float64(i.sum()) / np.float64(l.sum()))
+        for m in metric:
+            if m in ("mIoU", "microIoU"):
+                out["IoU"], out["Acc"] = i / u, i / l
+            elif m == "mDice":
+                out["Dice"], out["Acc"] = 2 * i / (p + l), i / l
+            elif m == "mFscore":
+                prec, rec = i / p, i / l
+                out["Fscore"] = (1 + beta ** 2) * (prec * rec) / ((beta ** 2 * prec) + rec)
+                out["Precision"], out["Recall"] = prec, rec
+    if nan_to_num is not None:
+        out = OrderedDict((k, np.nan_to_num(v, nan=nan_to_num)) for k, v in out.items())
+    return out
+
+
+def summary_of(metrics):
+    """The summary `evaluate` forms from such a dict (DELIVER.py:327-367): nanmean per entry, x 100 rounded to two places, / 100; every key but
+    'aAcc' gets the 'm' prefix."""
+    return OrderedDict((k if k == "aAcc" else "m" + k, np.round(np.nanmean(v) * 100, 2) / 100.0) for k, v in metrics.items())
+
+
+# ---- the label side of a launch ----
+class LabelPrep:
+    """How a raw uint8 label map [B, Hl, Wl] is read against a prediction: the LUT of `label_map` / `reduce_zero_label` / `ignore_index`, and `resize` =
+    dict(seg_scale=(w, h) or img_scale=(w, h), keep_ratio=True) of a `Resize_multimodal` step the ground truth goes through (transform.py:1169-1188:
+    `seg_scale` where given, else the image scale; mmcv.imrescale / imresize with interpolation='nearest').  LUT and index tables are built in numpy,
+    uploaded once per device / geometry and kept on the object: a later call with the same geometry allocates and copies nothing and can be captured."""
+
+    def __init__(self, num_classes, ignore_index=255, label_map=None, reduce_zero_label=False, resize=None):
+        self.num_classes = int(num_classes)
+        self.ignore_index, self.label_map, self.reduce_zero_label = ignore_index, dict(label_map or {}), bool(reduce_zero_label)
+        self.lut = label_lut(num_classes, ignore_index, label_map, reduce_zero_label)
+        if resize is not None:
+            sc = resize.get("seg_scale")
+            if sc is None or list(sc) == [None]:
+                sc = resize.get("img_scale")
+            if isinstance(sc, list) and len(sc) == 1:
+                sc = sc[0]
+            if sc is None or len(sc) != 2 or isinstance(sc[0], (list, tuple)) or resize.get("ratio_range") is not None:
+                raise NotImplementedError("mmsa.LabelPrep: resize needs one seg_scale=(w, h) or img_scale=(w, h); a ratio range or several scales are not built")
+            resize = dict(scale=(int(sc[0]), int(sc[1])), keep_ratio=bool(resize.get("keep_ratio", True)))
+        self.resize = resize
+        self._lut_dev = {}      # device -> LUT
+        self._tables = {}       # (Hl, Wl, H, W, device) -> (ymap, xmap)
+
+    @classmethod
+    def from_pipeline(cls, test_pipeline, num_classes, ignore_index=255, label_map=None, reduce_zero_label=False):
+        """From a reference config's `test_pipeline`.  The ground truth goes through `transforms[1 : index of MultiScaleFlipAug]` behind LoadAnnotations
+        (DELIVER.py:199-203): a `Resize_multimodal` there resizes it (seg_scale / img_scale / keep_ratio are read); a `Pad_multimodal` there leaves it
+        as it is (without an image in `results` its `_pad_img` raises before 'pad_shape' exists, `_pad_seg` then raises too, and both are swallowed:
+        transform.py:2968-3011).  Any other step there raises NotImplementedError naming it."""
+        idx = next((k for k, st in enumerate(test_pipeline) if st.get("type") == "MultiScaleFlipAug"), None)
+        if idx is None:
+            raise NotImplementedError("mmsa.LabelPrep.from_pipeline: the pipeline has no MultiScaleFlipAug step (the ground-truth steps are the ones in front of it)")
+        resize = None
+        for st in test_pipeline[1:idx]:
+            t = st.get("type")
+            if t == "Resize_multimodal":
+                if resize is not None:
+                    raise NotImplementedError("a second Resize_multimodal step in front of MultiScaleFlipAug")
+                if st.get("ratio_range") is not None or st.get("img_scale") is None or isinstance(st["img_scale"][0], (list, tuple)):
+                    raise NotImplementedError("Resize_multimodal with a ratio range or several scales (only one fixed scale has a device form)")
+                resize = dict(img_scale=tuple(st["img_scale"]), seg_scale=st.get("seg_scale"), keep_ratio=bool(st.get("keep_ratio", True)))
+            elif t == "Pad_multimodal":
+                continue
+            else:
+                raise NotImplementedError(f"pipeline step '{t}' in front of MultiScaleFlipAug has no device form in mmsa.LabelPrep")
+        return cls(num_classes, ignore_index=ignore_index, label_map=label_map, reduce_zero_label=reduce_zero_label, resize=resize)
+
+    def resized(self, Hl, Wl):
+        """(H, W) of an Hl x Wl label map after the resize step (its own size without one)."""
+        if self.resize is None:
+            return Hl, Wl
+        sc = self.resize["scale"]
+        return rescale_size(Hl, Wl, sc) if self.resize["keep_ratio"] else (sc[1], sc[0])
+
+    def check(self, labels, device=None):
+        if not isinstance(labels, torch.Tensor) or not labels.is_cuda:
+            raise RuntimeError("mmsa.evaluate: labels must be a GPU tensor (there is no CPU path)")
+        if labels.dtype != torch.uint8:
+            raise RuntimeError(f"mmsa.evaluate: labels are {labels.dtype}; raw uint8 label maps are expected")
+        if labels.dim() != 3 or not labels.is_contiguous():
+            raise RuntimeError(f"mmsa.evaluate: labels must be a contiguous [B, H, W] tensor, got {tuple(labels.shape)}")
+        if device is not None and labels.device != device:
+            raise RuntimeError(f"mmsa.evaluate: labels are on {labels.device}, the prediction on {device}")
+        return labels
+
+    def tables(self, Hl, Wl, H, W, device):
+        """(ymap, xmap) int32 device tables of the nearest-neighbour resize Hl x Wl -> H x W, or (None, None) where the sizes are equal."""
+        if (Hl, Wl) == (H, W):
+            return None, None
+        key = (Hl, Wl, H, W, torch.device(device))
+        tabs = self._tables.get(key)
+        if tabs is None:
+            if _capturing(key[-1]):
+                raise RuntimeError(f"mmsa.LabelPrep: the label tables for {Hl} x {Wl} -> {H} x {W} are not on the device yet and cannot be uploaded during a "
+                                   "graph capture: run one call with this geometry before capturing")
+            tabs = tuple(torch.from_numpy(nearest_axis_table(s, d)).to(key[-1]) for s, d in ((Hl, H), (Wl, W)))
+            self._tables[key] = tabs
+        return tabs
+
+    def lut_on(self, device):
+        device = torch.device(device)
+        t = self._lut_dev.get(device)
+        if t is None:
+            if _capturing(device):
+                raise RuntimeError("mmsa.LabelPrep: the label LUT is not on the device yet and cannot be uploaded during a graph capture: run one call before capturing")
+            t = self._lut_dev[device] = torch.from_numpy(self.lut).to(device)
+        return t
+
+    def launch_args(self, labels, B, H, W, device):
+        """The label-side arguments of both entries for a [B, H, W] prediction: (label, Hl, Wl, lut, ymap, xmap)."""
+        labels = self.check(labels, device)
+        Hl, Wl = int(labels.shape[1]), int(labels.shape[2])
+        if labels.shape[0] != B:
+            raise RuntimeError(f"mmsa.evaluate: {labels.shape[0]} label maps for {B} predictions")
+        if self.resized(Hl, Wl) != (H, W):
+            how = "" if self.resize is None else f" (resized to {self.resized(Hl, Wl)[0]} x {self.resized(Hl, Wl)[1]} by scale={self.resize['scale']}, keep_ratio={self.resize['keep_ratio']})"
+            raise RuntimeError(f"mmsa.evaluate: size mismatch: the label maps are {Hl} x {Wl}{how}, the prediction is {H} x {W}")
+        ymap, xmap = self.tables(Hl, Wl, H, W, device)
+        return (labels.data_ptr(), Hl, Wl, self.lut_on(device).data_ptr(), None if ymap is None else ymap.data_ptr(), None if xmap is None else xmap.data_ptr())
+
+
+def _slot_args(slots, B, n_slots):
+    slots = list(range(B)) if slots is None else [int(s) for s in slots]
+    if len(slots) != B:
+        raise RuntimeError(f"mmsa.evaluate: {len(slots)} slots for {B} images")
+    if B > MAX_IMAGES:
+        raise RuntimeError(f"mmsa.evaluate: at most {MAX_IMAGES} images per call, got {B}")
+    if any(not 0 <= s < n_slots for s in slots):
+        raise RuntimeError(f"mmsa.evaluate: slots {slots} outside the {n_slots} count slots")
+    return (ctypes.c_int * B)(*slots)
+
+
+def _check_counts(counts, C, device):
+    if (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int64 or counts.dim() != 3 or tuple(counts.shape[1:]) != (C + 1, C + 1)
+            or counts.device != device or not counts.is_contiguous()):
+        raise RuntimeError(f"mmsa.evaluate: counts must be a contiguous int64 [n_slots, {C + 1}, {C + 1}] tensor on {device}")
+    return counts
+
+
+def _check_pred(pred):
+    if not isinstance(pred, torch.Tensor) or not pred.is_cuda:
+        raise RuntimeError("mmsa.evaluate: pred must be a GPU tensor (there is no CPU path)")
+    if pred.dtype != torch.uint8:
+        raise RuntimeError(f"mmsa.evaluate: pred is {pred.dtype}; a uint8 class map is expected")
+    if pred.dim() != 3 or not pred.is_contiguous():
+        raise RuntimeError(f"mmsa.evaluate: pred must be a contiguous [B, H, W] tensor, got {tuple(pred.shape)}")
+    return pred
+
+
+@torch.no_grad()
+def confusion(pred, labels, prep, counts=None, slots=None):
+    """ADD the confusion counts of the uint8 class maps pred [B, H, W] against the raw labels [B, Hl, Wl] into counts[slots[b]] (one launch,
+    mmsa_eval_confusion_u8) -> counts, int64 [n_slots, C + 1, C + 1] on the device.  `slots` defaults to 0 .. B - 1 (per-image counts, as `pre_eval`
+    returns them); `counts` defaults to a zeroed buffer of max(slots) + 1 slots."""
+    pred = _check_pred(pred)
+    B, H, W = (int(v) for v in pred.shape)
+    C = prep.num_classes
+    with torch.cuda.device(pred.device):
+        largs = prep.launch_args(labels, B, H, W, pred.device)
+        if counts is None:
+            n_slots = B if slots is None else max(int(s) for s in slots) + 1
+            counts = torch.zeros(n_slots, C + 1, C + 1, dtype=torch.int64, device=pred.device)
+        _check_counts(counts, C, pred.device)
+        tab = _slot_args(slots, B, counts.shape[0])
+        lib.call("mmsa_eval_confusion_u8", pred.data_ptr(), largs[0], B, H, W, largs[1], largs[2], largs[3], C, largs[4], largs[5], tab, counts.shape[0],
+                 counts.data_ptr(), ops._stream())
+    return counts
+
+
+@torch.no_grad()
+def slide_argmax_eval(lg, n, windows, out, B, H, W, hc, wc, unc, labels, prep, counts, slots=None):
+    """mmsa_slide_argmax on the head-resolution logits lg [n, C, hs, ws] AND the counts of its class map in one launch; `out` = None writes no map."""
+    C = int(lg.shape[1])
+    if C != prep.num_classes:
+        raise RuntimeError(f"mmsa.evaluate: the head has {C} classes, the LabelPrep {prep.num_classes}")
+    largs = prep.launch_args(labels, B, H, W, lg.device)
+    _check_counts(counts, C, lg.device)
+    tab = _slot_args(slots, B, counts.shape[0])
+    lib.call("mmsa_slide_argmax_eval", lg.data_ptr(), n, C, lg.shape[2], lg.shape[3], windows, None if out is None else out.data_ptr(), B, H, W, hc, wc,
+             unc.data_ptr(), largs[0], largs[1], largs[2], largs[3], largs[4], largs[5], tab, counts.shape[0], counts.data_ptr(), ops._stream())
+
+
+class Evaluator:
+    """Owns the count buffer of an evaluation run.  `cases` = None: one slot per IMAGE, in the order the images are added (what `pre_eval` returns per
+    image), `images` slots in all; `cases` = a list of names: one slot per case, every image of an add(..., case=name) goes into that case's slot (the
+    `case=[...]` breakdown of the DELIVER configs) with no extra launch.  Pass `device` to have the buffer before the first add (graph capture).
+    Per-image mode holds `images` images (64 unless told otherwise): read areas() and reset() before it is full, or size it for the dataset."""
+
+    def __init__(self, prep, cases=None, images=MAX_IMAGES, device=None):
+        self.prep = prep
+        self.cases = None if cases is None else list(cases)
+        self.n_slots = int(images) if self.cases is None else len(self.cases)
+        if self.n_slots < 1:
+            raise ValueError("mmsa.Evaluator: at least one slot")
+        self.counts = None
+        self.used = 0           # per-image mode: slots taken so far
+        if device is not None:
+            self._buffer(torch.device(device))
+
+    def _buffer(self, device):
+        if self.counts is None:
+            if _capturing(device):
+                raise RuntimeError("mmsa.Evaluator: the count buffer cannot be allocated during a graph capture: construct the Evaluator with device=")
+            C = self.prep.num_classes
+            self.counts = torch.zeros(self.n_slots, C + 1, C + 1, dtype=torch.int64, device=device)
+        elif self.counts.device != device:
+            raise RuntimeError(f"mmsa.Evaluator: the counts live on {self.counts.device}, this batch on {device}")
+        return self.counts
+
+    def slots_for(self, B, case=None, slots=None):
+        """The count slots the NEXT batch of B images gets (nothing is taken yet: add / add_fused take them once their launch has gone through).
+        `slots=` names them outright (a captured call that must hit the same slots on every replay)."""
+        if slots is not None:
+            return [int(s) for s in slots]
+        if self.cases is not None:
+            if case not in self.cases:
+                raise KeyError(f"mmsa.Evaluator: case {case!r} is not one of {self.cases}")
+            return [self.cases.index(case)] * B
+        if case is not None:
+            raise KeyError("mmsa.Evaluator: case= needs an Evaluator made with cases=[...]")
+        if self.used + B > self.n_slots:
+            raise RuntimeError(f"mmsa.Evaluator: {self.used} + {B} images but {self.n_slots} per-image slots (read areas(), reset(), or make it with images=)")
+        return list(range(self.used, self.used + B))
+
+    def _taken(self, B, case, slots):
+        """A launch went through: in per-image mode its images now own their slots (a call that raised has consumed none)."""
+        if slots is None and self.cases is None and case is None:
+            self.used += B
+
+    def add(self, pred, labels, case=None, slots=None):
+        """Count a batch of stored class maps (one launch)."""
+        pred = _check_pred(pred)
+        with torch.cuda.device(pred.device):
+            counts = self._buffer(pred.device)
+        confusion(pred, labels, self.prep, counts=counts, slots=self.slots_for(pred.shape[0], case, slots))
+        self._taken(pred.shape[0], case, slots)
+        return self
+
+    def add_fused(self, lg, n, windows, out, B, H, W, hc, wc, unc, labels, case=None, slots=None):
+        """Class map + counts in one launch (mmsa.inference's class-map calls with labels= / evaluator=)."""
+        counts = self._buffer(lg.device)
+        slide_argmax_eval(lg, n, windows, out, B, H, W, hc, wc, unc, labels, self.prep, counts, slots=self.slots_for(B, case, slots))
+        self._taken(B, case, slots)
+        return self
+
+    def reset(self):
+        if self.counts is not None:
+            self.counts.zero_()
+        self.used = 0
+
+    def host_counts(self):
+        """The counts on the host (the ONE device-to-host copy of an evaluation): int64 numpy [n, C + 1, C + 1], n = images added so far / cases."""
+        C = self.prep.num_classes
+        if self.counts is None:
+            return np.zeros((0 if self.cases is None else self.n_slots, C + 1, C + 1), dtype=np.int64)
+        c = self.counts.cpu().numpy()
+        return c[:self.used] if self.cases is None else c
+
+    def areas(self):
+        """(area_intersect, area_union, area_pred_label, area_label): int64 numpy [n, C] each, row per image (per case with cases=)."""
+        return areas_of(self.host_counts())
+
+    def _slot_index(self, slot):
+        return self.cases.index(slot) if self.cases is not None and not isinstance(slot, int) else int(slot)
+
+    def metrics(self, metric=("mIoU",), nan_to_num=None, beta=1, slot=None):
+        """`total_area_to_metrics` of the totals over every slot (the reference's 'global' entry) or of one slot (index or case name), in float64."""
+        a = self.areas()
+        a = [x.sum(0) for x in a] if slot is None else [x[self._slot_index(slot)] for x in a]
+        return area_metrics(*a, metric=metric, nan_to_num=nan_to_num, beta=beta)
+
+    def summary(self, metric=("mIoU",), nan_to_num=None, beta=1, slot=None):
+        """aAcc / mIoU / mAcc / ... as `evaluate` forms them from the per-class values: nanmean, rounded to two places of a percent."""
+        return summary_of(self.metrics(metric, nan_to_num, beta, slot))

@@ -153,15 +153,42 @@ def _check_overlap(boxes, what):
                            "(use slide_inference + argmax_map, or a larger stride)")
 
 
+def _class_map(lg, n, tab, out, B, H, W, hc, wc, unc, labels, evaluator, case, fused, return_map):
+    """The class-map launch of the three class-map calls.  Without `labels`: mmsa_slide_argmax.  With `labels` (raw uint8 label maps [B, Hl, Wl]) and
+    `evaluator` (mmsa.evaluate.Evaluator): the confusion counts of the map are ADDED to the evaluator's buffer as well -- by the same launch
+    (mmsa_slide_argmax_eval: `fused=True`) or by a second one over the stored map (mmsa_eval_confusion_u8); `fused=None` takes mmsa.evaluate.FUSED_DEFAULT.
+    The map is the same either way; `return_map=False` with the fused launch writes none.  No host sync, no allocation."""
+    if labels is None and evaluator is None:
+        if not return_map:
+            raise RuntimeError("mmsa.inference: return_map=False only makes sense with labels= and evaluator=")
+        lib.call("mmsa_slide_argmax", lg.data_ptr(), n, lg.shape[1], lg.shape[2], lg.shape[3], tab, out.data_ptr(), B, H, W, hc, wc, unc.data_ptr(),
+                 ops._stream())
+        return
+    if labels is None or evaluator is None:
+        raise RuntimeError("mmsa.inference: labels= and evaluator= come together")
+    if fused is False and not return_map:
+        raise RuntimeError("mmsa.inference: return_map=False needs the fused launch (two launches go through the stored map); drop fused=False")
+    from . import evaluate
+    if (evaluate.FUSED_DEFAULT or not return_map) if fused is None else fused:      # no map wanted: only the fused launch can leave it unwritten
+        evaluator.add_fused(lg, n, tab, out if return_map else None, B, H, W, hc, wc, unc, labels, case=case)
+    else:
+        lib.call("mmsa_slide_argmax", lg.data_ptr(), n, lg.shape[1], lg.shape[2], lg.shape[3], tab, out.data_ptr(), B, H, W, hc, wc, unc.data_ptr(),
+                 ops._stream())
+        evaluator.add(out, labels, case=case)
+
+
 @_on_device
 @torch.no_grad()
-def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preprocess=None):
+def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preprocess=None, labels=None, evaluator=None, case=None, fused=None,
+                    return_map=True):
     """`simple_test` of a sliding-window frame (ED:191-234 + ED:449,477) -> uint8 class map [B, H, W], without the
     [B, classes, H, W] logits canvas: every window's logits stay at head resolution and ONE kernel (mmsa_slide_argmax) resizes,
     sums the overlapping windows in window order, divides by the count and takes the argmax -- the same additions in the same order
     as slide_inference + argmax_map, so the same class map bit for bit.  All windows of the frame go through the encoder in
     batches of `max_batch`; with static shapes the whole function is HIP-graph capturable (no host sync inside).
-    `preprocess=` (mmsa.preprocess.Preprocess): img is the pair (rgb, aux) of raw frames; the windows are cut AND normalised by one launch."""
+    `preprocess=` (mmsa.preprocess.Preprocess): img is the pair (rgb, aux) of raw frames; the windows are cut AND normalised by one launch.
+    `labels=` + `evaluator=` (mmsa.evaluate.Evaluator; `case=` with a per-case one): the map's confusion counts are added to the evaluator on device
+    (see _class_map); the returned map is unchanged, `return_map=False` returns None in its place."""
     import ctypes
     if preprocess is not None:
         rgb, aux, B, H, W = _raw(preprocess, img, "slide_class_map")
@@ -191,16 +218,16 @@ def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preproc
     tab = (ctypes.c_int * (3 * n))(*[v for b, (y1, x1, _, _) in jobs for v in (b, y1, x1)])
     out = torch.empty(B, H, W, dtype=torch.uint8, device=device)
     unc = torch.zeros(1, dtype=torch.int32, device=device)
-    lib.call("mmsa_slide_argmax", lg.data_ptr(), n, lg.shape[1], lg.shape[2], lg.shape[3], tab, out.data_ptr(), B, H, W,
-             crop_size[0], crop_size[1], unc.data_ptr(), ops._stream())
-    return out, unc          # unc[0] != 0 <=> some pixel is not covered (ED:220); checked by the caller outside a capture
+    _class_map(lg, n, tab, out, B, H, W, crop_size[0], crop_size[1], unc, labels, evaluator, case, fused, return_map)
+    return (out if return_map else None), unc          # unc[0] != 0 <=> some pixel is not covered (ED:220); checked by the caller outside a capture
 
 
 @_on_device
 @torch.no_grad()
-def whole_class_map(backbone, head, img, preprocess=None):
+def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator=None, case=None, fused=None, return_map=True):
     """Whole-image `simple_test`: resize x4 (bilinear, align_corners=False) + argmax fused (ED:90-94,449,477) -> uint8 [B, H, W].
-    `preprocess=` (mmsa.preprocess.Preprocess): img is the pair (rgb, aux) of raw frames, normalised (and padded) by one launch."""
+    `preprocess=` (mmsa.preprocess.Preprocess): img is the pair (rgb, aux) of raw frames, normalised (and padded) by one launch.
+    `labels=` + `evaluator=` (+ `case=`): as in slide_class_map."""
     import ctypes
     if preprocess is not None:
         img = preprocess(*_raw(preprocess, img, "whole_class_map")[:2])
@@ -212,9 +239,8 @@ def whole_class_map(backbone, head, img, preprocess=None):
     tab = (ctypes.c_int * (3 * B))(*[v for b in range(B) for v in (b, 0, 0)])
     out = torch.empty(B, H, W, dtype=torch.uint8, device=img.device)
     unc = torch.zeros(1, dtype=torch.int32, device=img.device)
-    lib.call("mmsa_slide_argmax", lg.data_ptr(), B, lg.shape[1], lg.shape[2], lg.shape[3], tab, out.data_ptr(), B, H, W, H, W,
-             unc.data_ptr(), ops._stream())
-    return out
+    _class_map(lg, B, tab, out, B, H, W, H, W, unc, labels, evaluator, case, fused, return_map)
+    return out if return_map else None
 
 
 @_on_device
@@ -292,17 +318,18 @@ class FrameResult:
     """What SlideRunner.run() returns: the class map of ONE frame, readable once the attention logit guard of its pass has been inspected
     (mmsa.chains.Replay; a pass that ran fp16 attention out of range raises mmsa.chains.AttentionRangeError instead)."""
 
-    def __init__(self, runner, replay):
-        self._runner, self._replay = runner, replay
+    def __init__(self, runner, replay, has_map=True):
+        self._runner, self._replay, self._has_map = runner, replay, has_map
 
     def outputs(self):
-        """(class map uint8 [B, H, W], uncovered-pixel flag) -- verified.  Both are the runner's static buffers: read them before the next run()."""
+        """(class map uint8 [B, H, W], uncovered-pixel flag) -- verified.  Both are the runner's static buffers: read them before the next run().
+        The map is None for a run(return_map=False): that frame wrote none, the buffer still holds an earlier frame's."""
         self._replay._owner._verify(self._replay.seq)
-        return self._runner.out, self._runner.unc
+        return (self._runner.out if self._has_map else None), self._runner.unc
 
     @property
     def unverified(self):
-        return self._runner.out, self._runner.unc
+        return (self._runner.out if self._has_map else None), self._runner.unc
 
 
 class SlideRunner:
@@ -349,11 +376,14 @@ class SlideRunner:
         return _crops(frame, self.jobs, self.crop_size, out=out)
 
     @torch.no_grad()
-    def run(self, frame=None):
+    def run(self, frame=None, labels=None, evaluator=None, case=None, fused=None, return_map=True):
         """Enqueue one frame on the current stream (asynchronous) -> FrameResult; `.outputs()` = (class map uint8 [B, H, W], uncovered-pixel flag) once the
         attention logit guard of this pass has been inspected.  The inspection costs one 4 * depth-byte copy per `check_every` frames and an event wait,
         no device sync; a frame that scored logits beyond the fp16 range raises mmsa.chains.AttentionRangeError from outputs() -- or from the next run(),
-        whichever comes first -- after the blocks concerned have been moved to fp16 hi/lo pairs and the graphs captured again: run that frame again."""
+        whichever comes first -- after the blocks concerned have been moved to fp16 hi/lo pairs and the graphs captured again: run that frame again.
+        `labels=` + `evaluator=` (mmsa.evaluate.Evaluator, best one made with cases=[...] and device=; `case=`): the frame's confusion counts are ADDED to the
+        evaluator on device (see _class_map); a frame that has to be run again has been counted, so reset the evaluator or subtract what it added.
+        `return_map=False` (always the fused launch) leaves the runner's map buffer untouched; the FrameResult's map is then None."""
         if frame is None:
             frame = self.frame
         else:
@@ -368,9 +398,9 @@ class SlideRunner:
             lg = rp.unverified          # the argmax kernel below is enqueued behind the pass; nothing is read on the host before outputs() verifies it
             B, H, W = self.out.shape
             self.unc.zero_()
-            lib.call("mmsa_slide_argmax", lg.data_ptr(), len(self.jobs), lg.shape[1], lg.shape[2], lg.shape[3], self.tab, self.out.data_ptr(),
-                     B, H, W, self.crop_size[0], self.crop_size[1], self.unc.data_ptr(), ops._stream())
-        return FrameResult(self, rp)
+            _class_map(lg, len(self.jobs), self.tab, self.out, B, H, W, self.crop_size[0], self.crop_size[1], self.unc, labels, evaluator, case, fused,
+                       return_map)
+        return FrameResult(self, rp, has_map=return_map)
 
     def check_guard(self):
         """Chains.check_guard for the runner's chains (host sync): [] = the frames since the last check ran inside the attention kernels' operand range;

@@ -295,10 +295,53 @@ def gen_sam_ckpt():
     np.savez_compressed(os.path.join(OUT, "sam_ckpt.npz"), **out)
 
 
+def gen_eval():
+    """The reference's own `intersect_and_union` and `total_area_to_metrics` (apis/evaluation/metrics_micro.py:26-86, 451-526, imported UNMODIFIED; its
+    `import mmcv` is served by the stub harness) on seeded class maps (tests/golden/eval_counts.npz): three 97 x 131 images of 25 classes whose labels
+    hold 255, an out-of-range value (30) and class 0, whose predictions hold 255, and where class 24 occurs nowhere (0 / 0 in the metrics).  Per
+    variant -- plain, reduce_zero_label, a chained label_map -- the four per-image histograms, the metrics of their float32 sums with and without
+    nan_to_num, and what the label sequence makes of each of the 256 byte values (read off one-pixel images through a 256-bin area_label; -1 =
+    ignored)."""
+    import importlib.util
+    from tests import eval_ref as ER
+    ref_import.install()
+    spec = importlib.util.spec_from_file_location("ref_metrics_micro", os.path.join(ref_import.SEG, "mmseg_custom", "apis", "evaluation", "metrics_micro.py"))
+    mm = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mm)
+    C = 25
+    pred, label = ER.make_case(61, 97, 131, C, B=3)
+    pred[pred == 24] = 23
+    label[label == 24] = 23
+    assert (label == 255).any() and (label == 30).any() and (label == 0).any() and (pred == 255).any()
+    out = dict(pred=pred, label=label, num_classes=np.int64(C), ignore_index=np.int64(255))
+    variants = dict(plain=dict(label_map=dict(), reduce_zero_label=False), rzl=dict(label_map=dict(), reduce_zero_label=True),
+                    map=dict(label_map={30: 3, 3: 7, 0: 255}, reduce_zero_label=False))
+    for tag, kw in variants.items():
+        per = [mm.intersect_and_union(pred[b].copy(), label[b].copy(), C, 255, dict(kw["label_map"]), kw["reduce_zero_label"]) for b in range(3)]
+        out[f"{tag}_areas"] = np.stack([np.stack([t.numpy() for t in img]) for img in per])           # [3, 4, C] float32: intersect, union, pred, label
+        tot = [sum(img[k] for img in per) for k in range(4)]                                          # float32 sums, as pre_eval_to_metrics forms them
+        assert all(float(t.sum()) < 2 ** 24 for t in tot)
+        for nan in (None, 0):
+            m = mm.total_area_to_metrics(*tot, ["mIoU", "mDice", "mFscore"], nan, 1)
+            for k, v in m.items():
+                out[f"{tag}_metrics_{'nan' if nan is None else 'num'}_{k}"] = np.asarray(v)
+        lut = np.full(256, -1, dtype=np.int16)
+        for v in range(256):
+            al = mm.intersect_and_union(np.zeros((1, 1), np.uint8), np.full((1, 1), v, np.uint8), 256, 255, dict(kw["label_map"]), kw["reduce_zero_label"])[3].numpy()
+            if al.sum() == 1:
+                lut[v] = int(al.argmax())
+        out[f"{tag}_bytes"] = lut
+        out[f"{tag}_label_map"] = np.array([[a, b] for a, b in kw["label_map"].items()], dtype=np.int64).reshape(-1, 2)
+        out[f"{tag}_reduce_zero_label"] = np.int64(kw["reduce_zero_label"])
+    path = os.path.join(OUT, "eval_counts.npz")
+    np.savez_compressed(path, **out)
+    print("eval_counts", os.path.getsize(path), "bytes", {k: v.shape for k, v in out.items() if k.endswith("_areas")}, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--big", action="store_true", help="also ViT-B@512 and ViT-L@1024 (minutes, GBs of RAM)")
-    ap.add_argument("--only", default=None, help="run one generator: msda_bwd | sam_ckpt | model:<config name>")
+    ap.add_argument("--only", default=None, help="run one generator: msda_bwd | sam_ckpt | eval | model:<config name>")
     a = ap.parse_args()
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
@@ -317,6 +360,7 @@ def main():
     gen_slide()
     gen_whole_dim()
     gen_ckpt()
+    gen_eval()
     gen_head("head_vitl", full=False)
     gen_head("head_odd", full=True)
     gen_head("head_tiny", full=True)
