@@ -259,6 +259,12 @@ int mmsa_dwconv_nhwc(const float* x, long ldx, long xstrideB, const float* w, co
                      float* clamp_max /* optional clamp watch word, see Conventions */, mmsa_stream_t stream);
 int mmsa_gconv_nhwc(const float* x, long ldx, const float* w, const float* bias, float* y, long ldy, int B, int H,
                     int W, int G, int cin_g, int cout_g, int k, int act, mmsa_stream_t stream);
+/* GFE qkv (AM:87-92): qkv2(qkv1(x)), a bias-free grouped 1x1 conv (cin_g -> cout_g) followed by a bias-free grouped 3x3 conv (cout_g -> cout_g) over
+ * the same G groups, as ONE grouped 3x3 conv with the folded weights w[g][tap][ci][co] = sum_m q1[g][ci][m] * q2[g][tap][m][co] (csrc/gfe_qkv.hip; fp32
+ * operands and accumulation).  Covered: cout_g = 3 cin_g, cin_g = 3 / 6 / 12 / 24, G * cin_g a multiple of 24.  *covered = 1: y is written;
+ * *covered = 0: nothing was launched and the caller runs the two mmsa_gconv_nhwc launches. */
+int mmsa_gfe_qkv_conv(const float* x, long ldx, const float* w, float* y, long ldy, int B, int H, int W, int G, int cin_g, int cout_g,
+                      int* covered, mmsa_stream_t stream);
 /* gated pair stage of the neck Mlp (AM:127-132): y = gelu(dw3x3(x)[:, :C]) * dw3x3(x)[:, C:], x token-major [B*H*W, 2C], the
  * depthwise conv has 2 channels per group (C groups), weights TAP-major [9][C][ci=2][co=2]; fp32 and/or interleaved-planes output */
 int mmsa_dwpair_gate(const float* x, long ldx, const float* w, float* y, long ldy, uint16_t* y_planes, long ldp, int B, int H,

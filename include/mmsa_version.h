@@ -5,8 +5,9 @@
  * 103: mmsa_gemm_split3's `fmt` accepts MMSA_FMT_W8 (fp8 weights against h8c activation planes).
  * 104: new entries mmsa_preprocess_nhwc / mmsa_preprocess_crops (raw HWC frames -> normalised NCHW, whole or as windows).
  * 105: new entries mmsa_preprocess_resize_nhwc / mmsa_preprocess_resize_crops (the same from sources of another size: bilinear resize first).
- * 106: new entries mmsa_eval_confusion_u8 / mmsa_slide_argmax_eval (confusion counts of a class map against a label map, alone or fused into the class-map kernel). */
+ * 106: new entries mmsa_eval_confusion_u8 / mmsa_slide_argmax_eval (confusion counts of a class map against a label map, alone or fused into the class-map kernel).
+ * 107: new entry mmsa_gfe_qkv_conv (the GFE's 1x1 and 3x3 qkv convs as one grouped 3x3 conv with folded weights). */
 #ifndef MMSA_VERSION_H
 #define MMSA_VERSION_H
-#define MMSA_ABI_VERSION 106
+#define MMSA_ABI_VERSION 107
 #endif

@@ -91,6 +91,21 @@ class _Tagged:
         return self.ws.nbytes()
 
 
+def fold_gfe_qkv(q1, q2, q1_bias=None, groups=32):
+    """The GFE's qkv2(qkv1(x)) (AM:87-92: grouped 1x1 conv c -> 3c, then grouped 3x3 conv 3c -> 3c, the same groups, no bias, nothing in between) is
+    itself a grouped 3x3 conv c -> 3c: group g of qkv2 reads exactly the channels group g of qkv1 wrote, and zero padding commutes with a bias-free
+    1x1 conv, so the border pixels are exact too.  From the module weights q1 [3c, c/G, 1, 1] and q2 [3c, 3c/G, 3, 3] returns
+    W_eff[g][tap][ci][co] = sum_m q1[g][ci][m] q2[g][tap][m][co], summed in float64 and rounded once to fp32 -- the layout of the packed `q2`
+    (ops.gfe_qkv).  With a qkv1 bias the padded border of qkv2 would see zeros where the composition sees the bias: no fold, returns None."""
+    if q1_bias is not None:
+        return None
+    G = groups
+    co, ci = q1.shape[0] // G, q1.shape[1]
+    a = q1.detach().double().reshape(G, 1, co, ci).transpose(2, 3)            # [G][1][ci][m]
+    b = q2.detach().double().reshape(G, co, co, 9).permute(0, 3, 2, 1)        # [G][tap][m][co]
+    return torch.matmul(a, b).float().contiguous()                             # [G][tap][ci][co]
+
+
 class SAMAdapterbimodalMixModNewInTwinConvNEW(nn.Module):
     def __init__(self, pretrain_size=1024, num_heads=12, conv_inplane=64, n_points=4,
                  modalities_name=['rgb', 'depth', 'lidar', 'event'], modalities_ch=[3, 3, 3, 1],
@@ -209,7 +224,7 @@ class SAMAdapterbimodalMixModNewInTwinConvNEW(nn.Module):
     # projections, ConvFFN); "up" = the 2x2 transposed conv of the tail.  The TwinConvNeXt / neck GEMMs stay on bf16 hi/lo (the most
     # error-sensitive part of the path: SURVEY appendix F).  `model.h8_sites = ()` keeps every site on 16-bit hi/lo pairs.
     # Every switch of this class that changes numerics is an ATTRIBUTE (h8_sites, h8c, cnx_f16, fold_ln, fold_adapter_ln, fold_convnext_ln, share_c_norm,
-    # fuse_convnext_mlp, attention_precision, attention_guard, range_fallback, inter_follow_blocks, msda_value): set it before the first forward, or call invalidate() after changing it; the A/B tools pass
+    # fuse_convnext_mlp, fuse_gfe_qkv, attention_precision, attention_guard, range_fallback, inter_follow_blocks, msda_value): set it before the first forward, or call invalidate() after changing it; the A/B tools pass
     # them through `bench.py --set attr=value`.  No environment variable changes what this module computes.
     # "attnv" = the attention kernels run P V on the fp16 MFMA: the v third of the qkv planes (GEMM output and bias rows) is h8-encoded
     # and P is rounded to fp16 (csrc/attention.hip VF; 2.9e-5 on the ViT-B oracle study, LAB_NOTES.md 4.1); the kernels with the rel-pos terms
@@ -244,6 +259,11 @@ class SAMAdapterbimodalMixModNewInTwinConvNEW(nn.Module):
     # `h8c` on, every contraction >= 512 and a multiple of 128): otherwise the pack raises ValueError.  Interaction, up-conv, ConvNeXt, neck and head
     # weights keep their formats.
     fp8_weights = False
+
+    # The GFE's qkv1 (grouped 1x1) and qkv2 (grouped 3x3) run as ONE grouped 3x3 conv with weights folded at pack time (fold_gfe_qkv, csrc/gfe_qkv.hip)
+    # where the kernel covers the width (c / 32 = 3 / 6 / 12 / 24: every shipped config; the tiny test models keep the two launches).  A run-time
+    # switch: both weight sets are packed.  `fuse_gfe_qkv = False`: the two launches everywhere.
+    fuse_gfe_qkv = True
 
     def _inter_pair_set(self):
         return set(getattr(self, "_inter_pairs", ()) or ())
@@ -630,6 +650,9 @@ class SAMAdapterbimodalMixModNewInTwinConvNEW(nn.Module):
                     q2=q2.reshape(G, co2, ci2, 9).permute(0, 3, 2, 1).contiguous(),
                     temp=sd[b + "attn.scale"].reshape(8).contiguous(), scale2=scalar(b + "attn.scale2"),
                     proj=sd[b + "attn.proj.weight"].reshape(c, c).contiguous()))
+                q12 = fold_gfe_qkv(q1, q2, sd.get(b + "attn.qkv1.bias"), G)   # (q1 / q2 stay: shapes the fused kernel does not cover, fuse_gfe_qkv = False)
+                if q12 is not None:
+                    lv["gfe"][-1]["q12"] = q12
                 b = f + f"local_feature_encoder_{m}.{i}."
                 dw = sd[b + "bottleneckBlock.2.weight"]
                 lv["loc"].append(dict(
@@ -1492,10 +1515,11 @@ class SAMAdapterbimodalMixModNewInTwinConvNEW(nn.Module):
             y = ws.get("nk_y", P, c)
             s = ws.get("nk_s", P, c)
             ops.layernorm(X, gp["nw"], gp["nb"], 1e-5, y, out2=s)
-            q1 = ws.get("nk_q1", P, 3 * c)
             q2 = ws.get("nk_q2", P, 3 * c)
-            ops.gconv(y, gp["q1"], None, q1, B, h, w, 32, c // 32, 3 * c // 32, 1)
-            ops.gconv(q1, gp["q2"], None, q2, B, h, w, 32, 3 * c // 32, 3 * c // 32, 3)
+            if not ("q12" in gp and getattr(self, "fuse_gfe_qkv", True) and ops.gfe_qkv(y, gp["q12"], q2, B, h, w, 32, c // 32, 3 * c // 32)):
+                q1 = ws.get("nk_q1", P, 3 * c)
+                ops.gconv(y, gp["q1"], None, q1, B, h, w, 32, c // 32, 3 * c // 32, 1)
+                ops.gconv(q1, gp["q2"], None, q2, B, h, w, 32, 3 * c // 32, 3 * c // 32, 3)
             st = acc_buf(B * 3, 3 * c)
             ops.colstats(q2, HW * 3 * c, B, HW, st, out_is_zero=True)
             g = acc_buf(B * c, c, gram=True)

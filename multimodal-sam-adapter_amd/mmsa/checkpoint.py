@@ -19,7 +19,7 @@ import torch
 
 from . import ops
 
-PACK_FORMAT = 11   # 11 (round 6): extractor dicts carry `first`, fc1 of every shared-norm extractor the folded ffn_norm, attn_guard has depth + 1 words (the clamp watch), the offsets / attention-weights projection is padded to 128 columns, settings carry fold_adapter_ln and the wide-range state, the pack its `weights_clamped` flag; 10: the attention path's hi/lo planes (bias rows, rel-pos tables, fallback block weights) are fp16 pairs; 9: the ConvNeXt planes' format (fp16 hi/lo pairs) among the settings; 8: byte-exact digests (sha1) instead of floating-point sums; the blocks' attention modes / largest logits travel with the planes; 7: ConvNeXt LayerNorm fold (pw1f / pw1_cs / pw1_bf, setting fold_cnx_ln); 6: plane checksum + pack-time settings in the header, both attention table formats (relp / relp16, qkv_bp_b3); 3: planes carry their operand format (bf16 hi/lo or h8); 4: LayerNorm affine parts folded into the adapter projections (share_c_norm); 5: planes carry `split` (qkv bias rows: v columns as h8 planes)
+PACK_FORMAT = 12   # 12: the neck's GFE dicts carry `q12`, the qkv1 and qkv2 weights folded into one grouped 3x3 conv (backbone.fold_gfe_qkv); 11 (round 6): extractor dicts carry `first`, fc1 of every shared-norm extractor the folded ffn_norm, attn_guard has depth + 1 words (the clamp watch), the offsets / attention-weights projection is padded to 128 columns, settings carry fold_adapter_ln and the wide-range state, the pack its `weights_clamped` flag; 10: the attention path's hi/lo planes (bias rows, rel-pos tables, fallback block weights) are fp16 pairs; 9: the ConvNeXt planes' format (fp16 hi/lo pairs) among the settings; 8: byte-exact digests (sha1) instead of floating-point sums; the blocks' attention modes / largest logits travel with the planes; 7: ConvNeXt LayerNorm fold (pw1f / pw1_cs / pw1_bf, setting fold_cnx_ln); 6: plane checksum + pack-time settings in the header, both attention table formats (relp / relp16, qkv_bp_b3); 3: planes carry their operand format (bf16 hi/lo or h8); 4: LayerNorm affine parts folded into the adapter projections (share_c_norm); 5: planes carry `split` (qkv bias rows: v columns as h8 planes)
 
 
 def unwrap_state_dict(ck):

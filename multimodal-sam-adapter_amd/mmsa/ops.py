@@ -667,6 +667,16 @@ def gconv(x, w, bias, out, b, h, wd, groups, cin_g, cout_g, k, act="none"):
     px, _, _, ldx = _mat(x, "x")
     po, _, _, ldo = _mat(out, "y")
     lib.call("mmsa_gconv_nhwc", px, ldx, _chk(w), _chk(bias), po, ldo, b, h, wd, groups, cin_g, cout_g, k, ACT[act], _stream())
+
+
+def gfe_qkv(x, w12, out, b, h, wd, groups, cin_g, cout_g):
+    """GFE qkv2(qkv1(x)) as one grouped 3x3 conv with the folded weights `w12` [G][9][cin_g][cout_g] (backbone.fold_gfe_qkv).  Returns False -- and
+    launches nothing -- for a shape the kernel does not cover: the caller then runs the two gconv launches."""
+    px, _, _, ldx = _mat(x, "x")
+    po, _, _, ldo = _mat(out, "y")
+    covered = ctypes.c_int(0)
+    lib.call("mmsa_gfe_qkv_conv", px, ldx, _chk(w12), po, ldo, b, h, wd, groups, cin_g, cout_g, ctypes.byref(covered), _stream())
+    return bool(covered.value)
     return out
 
 
