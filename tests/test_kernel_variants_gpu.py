@@ -1,0 +1,460 @@
+"""Every `__global__` of conv.hip, conv_pair.hip, gconv_mfma.hip, gfe_qkv.hip, norm.hip (colstats / ffrm / lnhw), neck.hip, tail.hip and head.hip that a
+shape can select, reached through its launcher at the smallest shape that selects it and held ELEMENT BY ELEMENT to the float64 bound of
+tests/variant_ref.py.  Every call runs twice into NaN-filled outputs and must give identical bits; wherever a launch writes fp32 and operand planes
+together, the planes must be ops.split_planes of that launch's own fp32 output, bit for bit over the whole zero-initialised buffer (pad columns stay zero).
+None of these launchers writes the row-pair (h8c) format, so there is no unused half of a last row pair to watch here.
+
+The table: case id -> operation, launcher, the kernel the shape selects and why.  The ids carry the shape; B = 2 throughout (the batch stride is part of
+what can go wrong).  profiles/README.md says how the kernel trace of one run of this file is recorded.
+
+  dw3-strip-*     mmsa_dwconv_nhwc   dwconv3_strip_kernel      k = 3, W % 4 == 0, 16-byte aligned pointers
+  dw3-nhwc-*      mmsa_dwconv_nhwc   dwconv3_nhwc_kernel       k = 3, W = 7 (W % 4 != 0), aligned
+  dw3-gen-*       mmsa_dwconv_nhwc   dwconv_nhwc_kernel        k = 3, x starts one float past a 16-byte boundary: the alignment test fails
+  dw3-stride      mmsa_dwconv_nhwc   dwconv3_strip_kernel      xstride_b / ystride_b larger than dense (the gap must stay untouched)
+  dw3-pl-*        mmsa_dwconv_nhwc   strip / nhwc / generic    fp32 + planes (b3, h8, f3) at C = 36 (pad columns) and C = 64; -only: planes alone
+  dw5-*           mmsa_dwconv_nhwc   dwconv_nhwc_kernel        k = 5 has no kernel of its own
+  dw7-gelu        mmsa_dwconv_nhwc   dwconv_nhwc_kernel        k = 7 with an activation: the 7 x 7 kernels take act == none only
+  dw7-tiled-*     mmsa_dwconv_nhwc   dwconv7_tiled_kernel      k = 7, act none, aligned, H or W not a multiple of 16 (8x8, ragged 9x15, 1x1; C = 96: a 32-channel last chunk)
+  dw7-blk-*       mmsa_dwconv_nhwc   dwconv7_blk_kernel        k = 7, act none, fp32 only, C % 32 == 0, H % 16 == 0, W % 16 == 0
+  dw7-*-ipg       mmsa_dwconv_nhwc   blk / tiled               imgs_per_group = 1: each image its own weights and bias
+  dw7-pl-*        mmsa_dwconv_nhwc   dwconv7_tiled_kernel      planes need C % 64 == 0, H % 8 == 0, W % 8 == 0 (lane-pair stores)
+  dw7-pl-gen      mmsa_dwconv_nhwc   dwconv_nhwc_kernel        k = 7 planes at C = 32: not a full 64-channel chunk, the generic kernel writes them
+  gc1-t*          mmsa_gconv_nhwc    gconv_tiled_kernel<N,1>   k = 1, no bias / act, cout_g = N in the template list
+  gc3-t*          mmsa_gconv_nhwc    gconv_tiled_kernel<N,3>   k = 3, cout_g = N <= 16: mmsa_gconv3_mfma_launch declines one n-tile.  (<18,3> <24,3> <36,3> <72,3> are
+                                                               reachable through the MMSA_GCONV_VALU knob only: the matrix-pipe kernel takes cout_g 17..48 and 65..80.)
+  gc3-mfma*       mmsa_gconv_nhwc    gconv3_mfma_kernel<2|3|5> k = 3, cout_g = 18 / 40 / 72 (2, 3, 5 n-tiles)
+  gc3-gen50/81    mmsa_gconv_nhwc    gconv_nhwc_kernel         k = 3, cout_g = 50 (4 n-tiles: declined) / 81 (> 5 n-tiles: declined), not in the template list
+  gc1-gen5, gc3-gen5  mmsa_gconv_nhwc gconv_nhwc_kernel        cout_g = 5: outside the template list (k = 3: one n-tile, declined too)
+  gc3-gen-bias-*  mmsa_gconv_nhwc    gconv_nhwc_kernel         bias / activation: the generic kernel alone takes them
+  gc5-gen         mmsa_gconv_nhwc    gconv_nhwc_kernel         k = 5
+  gc3-pair-w*     mmsa_gconv_nhwc    dwpair_nhwc_kernel        k = 3, cin_g = cout_g = 2, even G, aligned: handed to mmsa_dwpair_nhwc_launch
+  gc3-pair-oddG   mmsa_gconv_nhwc    gconv_nhwc_kernel         the same with G = 7: the pair kernel works on two groups per lane
+  gfe-*           mmsa_gfe_qkv_conv  gfe_qkv_kernel<3|6|12|24> cout_g = 3 cin_g, G cin_g % 24 == 0; -declined: returns False and leaves the NaN-filled output alone
+  gate-*          mmsa_dwpair_gate   dwpair_gate4_kernel (W % 4 == 0) / dwpair_gate_kernel; fp32 + b3 planes
+  ca-*            mmsa_ca_apply      ca_apply_kernel           fp32 + b3 planes
+  gg-*            mmsa_gelu_gate     gelu_gate_kernel
+  pool-*          mmsa_pool_hw       pool_hw_kernel<true>; pool-c6: C % 4 != 0 -> pool_hw_kernel<false>
+  cs-*            mmsa_colstats      colstats_kernel           HW = 4097: nine 512-row blocks; wrow on / off; out_is_zero on / off.  The blocks meet in a double
+                                                               atomicAdd whose order is free, yet two calls must agree in every bit: every term is an fp32
+                                                               partial of eight rows (24 bits; it ends at 2^-36 or above for the seeded inputs here, whose
+                                                               totals stay below 2^17), so each double addition is exact and the order cannot show.  Data
+                                                               with a far wider range of magnitudes could differ in the last bit without a fault in the kernel.
+  ffrm-*          mmsa_ffrm_finalize ffrm_stats / ffrm_matvec / ffrm_gate kernels
+  lnhw-*          mmsa_lnhw_apply    lnhw_apply_kernel
+  gram-*          mmsa_gram_tn       gram_part_kernel + gram_sum_kernel; P around the 256-row slice, c = 768: 8 x 8 blocks; nblk = 8: diagonal head blocks only
+  chan-*, gffm-*  mmsa_chanattn_build / mmsa_gffm_build        c = 80: cpad = 96, pad columns must stay zero
+  tail-*          mmsa_tail_fuse     tail_fuse64_kernel; tail-c6: C % 4 != 0 -> tail_fuse_kernel; -pl: b3 planes (C % 32 == 0); -noxtok: xtok = None;
+                                     tail-pl-narrow: cmap one float past a 16-byte boundary -> tail_fuse_kernel with planes
+  n2p-*           mmsa_nchw_to_planes  nchw_to_planes_kernel<true>: HW % 4 == 0 and image stride % 4 == 0 (n2p-c36-hw4096 dense, n2p-c64-hw4096 stride + 4);
+                                       every other case <false> (HW = 1, 35, or n2p-c8-hw4096 with stride + 3)
+  t2n-*           mmsa_tokens_to_nchw  tokens_to_nchw_kernel
+  head-*          mmsa_head_fuse     head_fuse_kernel          four unequal, non-square levels, fp32 + planes
+"""
+import pytest
+import torch
+
+from tests import variant_ref as V
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+NAN = float("nan")
+B = 2
+
+CASES = []     # (id, op, params)
+RAISES = []    # (id, op, params): the launcher must refuse
+
+
+def _c(cid, op, **p):
+    p.setdefault("B", B)
+    CASES.append((cid, op, p))
+
+
+_AB = [(a, b) for b in (False, True) for a in V.ACTS]     # the twelve (activation, bias) pairs
+n = 0
+for W in (4, 8, 12):
+    for H in (1, 5):
+        for C in (4, 36, 64):
+            a, b = _AB[n % 12]
+            n += 1
+            _c(f"dw3-strip-{H}x{W}-c{C}-{a}-b{int(b)}", "dwconv", C=C, H=H, W=W, k=3, act=a, bias=b)
+for n, (a, b) in enumerate(_AB):
+    C, H = ((36, 5), (4, 1), (64, 5), (4, 5), (36, 1), (64, 1))[n % 6]
+    _c(f"dw3-nhwc-{H}x7-c{C}-{a}-b{int(b)}", "dwconv", C=C, H=H, W=7, k=3, act=a, bias=b)
+for n, a in enumerate(V.ACTS):
+    _c(f"dw3-gen-5x8-c36-{a}-b{n % 2}", "dwconv", C=36, H=5, W=8, k=3, act=a, bias=bool(n % 2), misalign=True)
+_c("dw3-stride", "dwconv", C=36, H=5, W=8, k=3, act="relu6", bias=True, xpad=8, ypad=12)
+for fmt in ("b3", "h8", "f3"):
+    for C in (36, 64):
+        _c(f"dw3-pl-strip-{fmt}-c{C}", "dwconv", C=C, H=5, W=8, k=3, act="gelu", bias=True, planes=fmt)
+        _c(f"dw3-pl-nhwc-{fmt}-c{C}", "dwconv", C=C, H=5, W=7, k=3, act="relu6", bias=False, planes=fmt)
+        _c(f"dw3-pl-gen-{fmt}-c{C}", "dwconv", C=C, H=5, W=8, k=3, act="none", bias=True, planes=fmt, misalign=True)
+    _c(f"dw3-pl-only-{fmt}", "dwconv", C=36, H=5, W=8, k=3, act="gelu", bias=True, planes=fmt, no_y=True)
+_c("dw5-none", "dwconv", C=36, H=5, W=7, k=5, act="none", bias=True)
+_c("dw5-gelu", "dwconv", C=36, H=5, W=7, k=5, act="gelu", bias=False)
+_c("dw7-gelu", "dwconv", C=32, H=9, W=15, k=7, act="gelu", bias=True)
+for H, W, C in ((8, 8, 32), (9, 15, 32), (1, 1, 32), (9, 15, 96)):
+    _c(f"dw7-tiled-{H}x{W}-c{C}", "dwconv", C=C, H=H, W=W, k=7, act="none", bias=True)
+for H, W in ((16, 16), (32, 16)):
+    for C in (32, 96):
+        _c(f"dw7-blk-{H}x{W}-c{C}", "dwconv", C=C, H=H, W=W, k=7, act="none", bias=C == 32)
+_c("dw7-blk-ipg", "dwconv", C=32, H=16, W=16, k=7, act="none", bias=True, ipg=1)
+_c("dw7-tiled-ipg", "dwconv", C=64, H=8, W=8, k=7, act="none", bias=True, ipg=1)
+for fmt in ("b3", "h8", "f3"):
+    _c(f"dw7-pl-{fmt}", "dwconv", C=64, H=8, W=16, k=7, act="none", bias=True, planes=fmt)
+_c("dw7-pl-gen", "dwconv", C=32, H=8, W=8, k=7, act="none", bias=True, planes="b3")
+RAISES.append(("dw3-ipg-refused", "dwconv", dict(B=B, C=36, H=5, W=8, k=3, act="none", bias=True, ipg=1)))
+
+for co in (3, 6, 9, 12, 18, 24, 36, 72):
+    _c(f"gc1-t{co}", "gconv", G=4, cin_g=co // 3, cout_g=co, H=5, W=7, k=1, act="none")
+for co in (3, 6, 9, 12):
+    _c(f"gc3-t{co}", "gconv", G=4, cin_g=co, cout_g=co, H=5, W=7, k=3, act="none")
+_c("gc3-t9-17x18", "gconv", G=3, cin_g=9, cout_g=9, H=17, W=18, k=3, act="none")
+for co in (18, 40, 72):
+    _c(f"gc3-mfma{co}", "gconv", G=2, cin_g=co, cout_g=co, H=5, W=7, k=3, act="none")
+_c("gc3-mfma18-17x18", "gconv", G=3, cin_g=10, cout_g=18, H=17, W=18, k=3, act="none")
+_c("gc3-gen50", "gconv", G=2, cin_g=5, cout_g=50, H=5, W=7, k=3, act="none")
+_c("gc3-gen81", "gconv", G=2, cin_g=3, cout_g=81, H=5, W=7, k=3, act="none")
+_c("gc1-gen5", "gconv", G=4, cin_g=3, cout_g=5, H=5, W=7, k=1, act="none")
+_c("gc3-gen5", "gconv", G=4, cin_g=3, cout_g=5, H=5, W=7, k=3, act="none")
+for a in ("gelu", "sigmoid", "hswish", "relu"):
+    _c(f"gc3-gen-bias-{a}", "gconv", G=4, cin_g=9, cout_g=9, H=5, W=7, k=3, act=a, bias=True)
+_c("gc5-gen", "gconv", G=4, cin_g=3, cout_g=6, H=5, W=7, k=5, act="none")
+for W in (3, 4, 9):
+    _c(f"gc3-pair-w{W}", "gconv", G=8, cin_g=2, cout_g=2, H=5, W=W, k=3, act="none")
+_c("gc3-pair-oddG", "gconv", G=7, cin_g=2, cout_g=2, H=5, W=4, k=3, act="none")
+
+for ci, G in ((3, 8), (6, 4), (12, 2), (24, 1), (3, 16)):
+    _c(f"gfe-ci{ci}-g{G}-5x7", "gfe_qkv", G=G, cin_g=ci, cout_g=3 * ci, H=5, W=7, covered=True)
+_c("gfe-ci6-g4-17x18", "gfe_qkv", G=4, cin_g=6, cout_g=18, H=17, W=18, covered=True)
+_c("gfe-ci9-declined", "gfe_qkv", G=8, cin_g=9, cout_g=27, H=5, W=7, covered=False)
+_c("gfe-c36-declined", "gfe_qkv", G=12, cin_g=3, cout_g=9, H=5, W=7, covered=False)
+
+_HW = ((1, 1), (1, 9), (7, 1), (10, 14))
+for C in (4, 36, 64, 100):
+    for H, W in _HW + ((5, 8),):
+        _c(f"gate-{H}x{W}-c{C}", "dwpair_gate", C=C, H=H, W=W)
+    for H, W in _HW:
+        _c(f"ca-{H}x{W}-c{C}", "ca_apply", C=C, H=H, W=W)
+        _c(f"gg-{H}x{W}-c{C}", "gelu_gate", C=C, H=H, W=W)
+        _c(f"pool-{H}x{W}-c{C}", "pool_hw", C=C, H=H, W=W)
+_c("pool-c6", "pool_hw", C=6, H=10, W=14)
+
+for C in (32, 96):
+    for HW in (1, 63, 480, 4097):
+        for wr in (False, True):
+            for z in (False, True):
+                _c(f"cs-c{C}-hw{HW}-w{int(wr)}-z{int(z)}", "colstats", C=C, HW=HW, wrow=wr, out_is_zero=z)
+        _c(f"lnhw-c{C}-hw{HW}", "lnhw", C=C, HW=HW)
+    for HW in (1, 63, 480, 4097):        # HW = 1: the variance is exactly 0, rstd = 1 / sqrt(1e-5), avg collapses to mean_b
+        _c(f"ffrm-c{C}-hw{HW}", "ffrm", C=C, HW=HW)
+
+for P in (1, 255, 256, 257, 1500):
+    for c in (8, 12, 80, 768):
+        for nblk in (1, 8):
+            if c % nblk:
+                if P == 1:
+                    RAISES.append((f"gram-p{P}-c{c}-n{nblk}-refused", "gram", dict(B=B, P=P, c=c, nblk=nblk)))
+                continue
+            _c(f"gram-p{P}-c{c}-n{nblk}", "gram", P=P, c=c, nblk=nblk)
+for c in (32, 80, 96):
+    _c(f"chan-c{c}", "chanattn", c=c, heads=8)
+    _c(f"gffm-c{c}", "gffm", c=c)
+
+for sc, (hx, wx) in ((4, (3, 5)), (2, (4, 6)), (1, (5, 7)), (0.5, (6, 10))):
+    _c(f"tail-x{sc}", "tail", C=96, Hx=hx, Wx=wx, Hc=int(hx * sc), Wc=int(wx * sc), xtok=True)
+_c("tail-noxtok", "tail", C=96, Hx=4, Wx=6, Hc=8, Wc=12, xtok=False)
+_c("tail-c6", "tail", C=6, Hx=4, Wx=6, Hc=8, Wc=12, xtok=True)
+for C in (32, 96):
+    _c(f"tail-pl-c{C}", "tail", C=C, Hx=4, Wx=6, Hc=8, Wc=12, xtok=True, planes=True)
+_c("tail-pl-narrow-c32", "tail", C=32, Hx=4, Wx=6, Hc=8, Wc=12, xtok=True, planes=True, misalign=True)
+for n, C in enumerate((8, 36, 64)):
+    for m, HW in enumerate((1, 35, 4096)):        # image / row stride: dense, + 4, + 3 floats; HW = 4096 meets all three (C = 36, 64, 8)
+        _c(f"n2p-c{C}-hw{HW}", "nchw_to_planes", C=C, HW=HW, pad=(0, 4, 3)[(n + m) % 3])
+        _c(f"t2n-c{C}-hw{HW}", "tokens_to_nchw", C=C, HW=HW, pad=(0, 4, 3)[(n + m) % 3])
+for C in (8, 40):
+    _c(f"head-c{C}", "head_fuse", C=C, sizes=((8, 12), (4, 6), (2, 3), (16, 24)))
+del n
+
+assert len({c[0] for c in CASES}) == len(CASES)
+
+
+@pytest.fixture(scope="module")
+def ops():
+    import mmsa
+    return mmsa.ops
+
+
+def dev(t):
+    return t.contiguous().to(DEV)
+
+
+def nanbuf(*shape, dtype=torch.float32):
+    return torch.full(shape, NAN, dtype=dtype, device=DEV)
+
+
+def bits(t):
+    t = t.contiguous()
+    return t.view({2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
+
+
+def fmt_of(ops, name):
+    return {"b3": ops.FMT_B3, "h8": ops.FMT_H8, "f3": ops.FMT_F3}[name]
+
+
+def planes_equal_split(ops, pl, y, fmt):
+    """The planes a launch wrote next to its fp32 output are split_planes of that output, bit for bit over the whole buffer (pad columns: zero)."""
+    want = ops.split_planes(y.contiguous(), out=ops.alloc_planes(y.shape[0], y.shape[1], DEV, zero=True, fmt=fmt))
+    torch.cuda.synchronize()
+    assert pl.p.shape == want.p.shape
+    assert torch.equal(pl.p, want.p), "planes differ from split_planes of the same launch's fp32 output"
+    assert pads_zero(ops, pl)
+
+
+def pads_zero(ops, pl):
+    """Every 16-bit word / byte that belongs to a column >= k of the planes is zero."""
+    k, kp = pl.k, pl.kpad
+    if k == kp:
+        return True
+    by = pl.p.contiguous().view(torch.uint8).view(pl.p.shape[0], kp // 32, 128)
+    cols = torch.arange(32 * (k // 32), kp)
+    blk, c = cols // 32, cols % 32
+    if pl.fmt == ops.FMT_H8:
+        lo = 64 + (c // 8) * 16 + c % 8
+        offs = [2 * c, 2 * c + 1, lo, lo + 8]
+    else:
+        offs = [2 * c, 2 * c + 1, 64 + 2 * c, 64 + 2 * c + 1]
+    keep = cols >= k
+    return all(bool((by[:, blk[keep], o[keep]] == 0).all()) for o in offs)
+
+
+# ------------------------------------------------------------------------------------------------ runners: one launch into fresh NaN-filled outputs
+# each returns dict(y = fp32 result in the reference's layout or None, raw = every buffer the launch wrote (compared bit for bit between two runs),
+# planes = (Planes, format) written next to y, or decoded = fp32 decode of a planes-only output)
+def run_dwconv(ops, i, p):
+    Bn, C, H, W, k = p["B"], p["C"], p["H"], p["W"], p["k"]
+    hwc = H * W * C
+    xs, ys = hwc + p.get("xpad", 0), hwc + p.get("ypad", 0)
+    off = 1 if p.get("misalign") else 0
+    xbuf = nanbuf(off + Bn * xs + 3)
+    xbuf[off:off + Bn * xs].view(Bn, xs)[:, :hwc] = dev(V.nhwc(i["x"]).view(Bn, hwc))
+    w = dev(i["w"].reshape(-1, C, k * k).transpose(1, 2))          # [groups][tap][C]
+    b = dev(i["b"]) if "b" in i else None
+    ybuf = None if p.get("no_y") else nanbuf(Bn * ys)
+    pl = ops.alloc_planes(Bn * H * W, C, DEV, zero=True, fmt=fmt_of(ops, p["planes"])) if p.get("planes") else None
+    ops.dwconv(xbuf[off:off + hwc].view(H * W, C), w, b, None if ybuf is None else ybuf[:hwc].view(H * W, C), Bn, H, W, k, act=p["act"],
+               xstride_b=xs, ystride_b=ys, out_planes=pl, imgs_per_group=p.get("ipg", 0))
+    out = dict(raw=[t for t in (ybuf, pl.p if pl else None) if t is not None])
+    if ybuf is not None:
+        out["y"] = ybuf.view(Bn, ys)[:, :hwc].reshape(Bn * H * W, C)
+        assert bool(torch.isnan(ybuf.view(Bn, ys)[:, hwc:]).all()), "the gap between two images was written"
+        if pl:
+            out["planes"] = (pl, pl.fmt)
+    else:
+        out["decoded"] = (ops.planes_to_float(pl), V.FMT_REL[p["planes"]])
+        assert pads_zero(ops, pl)
+    return out
+
+
+def run_gconv(ops, i, p):
+    Bn, G, ci, co, H, W, k = p["B"], p["G"], p["cin_g"], p["cout_g"], p["H"], p["W"], p["k"]
+    w = dev(i["w"].reshape(G, co, ci, k * k).permute(0, 3, 2, 1))   # [g][tap][ci][co]
+    y = nanbuf(Bn * H * W, G * co)
+    ops.gconv(dev(V.nhwc(i["x"])), w, dev(i["b"]) if "b" in i else None, y, Bn, H, W, G, ci, co, k, act=p["act"])
+    return dict(y=y, raw=[y])
+
+
+def run_gfe_qkv(ops, i, p):
+    from mmsa.backbone import fold_gfe_qkv
+    Bn, G, ci, co, H, W = p["B"], p["G"], p["cin_g"], p["cout_g"], p["H"], p["W"]
+    if co == 3 * ci:
+        w12 = dev(fold_gfe_qkv(i["q1"], i["q2"], groups=G))
+    else:
+        w12 = torch.zeros(G, 9, ci, co, device=DEV)
+    y = nanbuf(Bn * H * W, G * co)
+    covered = ops.gfe_qkv(dev(V.nhwc(i["x"])), w12, y, Bn, H, W, G, ci, co)
+    torch.cuda.synchronize()
+    assert covered == p["covered"]
+    if not covered:
+        assert bool(torch.isnan(y).all()), "a declined call wrote to its output"
+        return dict(y=None, raw=[y])
+    return dict(y=y, raw=[y])
+
+
+def run_dwpair_gate(ops, i, p):
+    Bn, C, H, W = p["B"], p["C"], p["H"], p["W"]
+    w = dev(i["w"].reshape(C, 2, 2, 9).permute(3, 0, 2, 1))          # [tap][group][ci][co]
+    y = nanbuf(Bn * H * W, C)
+    pl = ops.alloc_planes(Bn * H * W, C, DEV, zero=True)
+    ops.dwpair_gate(dev(V.nhwc(i["x"])), w, y, Bn, H, W, C, out_planes=pl)
+    return dict(y=y, raw=[y, pl.p], planes=(pl, ops.FMT_B3))
+
+
+def run_ca_apply(ops, i, p):
+    Bn, C, H, W = p["B"], p["C"], p["H"], p["W"]
+    y = nanbuf(Bn * H * W, C)
+    pl = ops.alloc_planes(Bn * H * W, C, DEV, zero=True)
+    ops.ca_apply(dev(i["z"]), dev(i["att"]), y, Bn, H, W, out_planes=pl)
+    return dict(y=y, raw=[y, pl.p], planes=(pl, ops.FMT_B3))
+
+
+def run_gelu_gate(ops, i, p):
+    y = nanbuf(i["x"].shape[0], p["C"])
+    ops.gelu_gate(dev(i["x"]), y, p["C"])
+    return dict(y=y, raw=[y])
+
+
+def run_pool_hw(ops, i, p):
+    y = nanbuf(p["B"] * (p["H"] + p["W"]), p["C"])
+    ops.pool_hw(dev(i["z"]), y, p["B"], p["H"], p["W"])
+    return dict(y=y, raw=[y])
+
+
+def run_colstats(ops, i, p):
+    Bn, C, HW = p["B"], p["C"], p["HW"]
+    st = torch.zeros(Bn * 3, C, dtype=torch.float64, device=DEV) if p["out_is_zero"] else nanbuf(Bn * 3, C, dtype=torch.float64)
+    ops.colstats(dev(i["x"]), HW * C, Bn, HW, st, wrow=dev(i["wrow"]) if "wrow" in i else None, out_is_zero=p["out_is_zero"])
+    return dict(y=st, raw=[st])
+
+
+def run_ffrm(ops, i, p):
+    Bn, C, HW = p["B"], p["C"], p["HW"]
+    o = nanbuf(3 * Bn, C)
+    ops.ffrm_finalize(dev(i["stats"]), Bn, HW, C, i["mean_w"], i["mean_b"], dev(i["wc"]), dev(i["gn_w"]), dev(i["gn_b"]),
+                      o[:Bn], o[Bn:2 * Bn], o[2 * Bn:], nanbuf(2 * Bn, C))
+    return dict(y=o, raw=[o])
+
+
+def run_lnhw(ops, i, p):
+    y = nanbuf(p["B"] * p["HW"], p["C"])
+    ops.lnhw_apply(dev(i["x"]), dev(i["mean"]), dev(i["rstd"]), dev(i["mult"]), dev(i["w"]), dev(i["b"]), y, p["B"], p["HW"])
+    return dict(y=y, raw=[y])
+
+
+def run_gram(ops, i, p):
+    Bn, P, c, nblk = p["B"], p["P"], p["c"], p["nblk"]
+    xy = dev(i["xy"])
+    g = nanbuf(Bn * c, c, dtype=torch.float64)
+    need = ops.gram_tn_scratch_bytes(Bn, P, c)
+    assert need % 4 == 0
+    ops.gram_tn(xy[:, :c], xy[:, c:], P * 2 * c, g, Bn, P, nblk=nblk, scratch=nanbuf(need // 4))    # exactly the bytes asked for
+    return dict(y=g, raw=[g], mask=V.gram_mask(c, nblk).repeat(Bn, 1))
+
+
+def run_chanattn(ops, i, p):
+    Bn, c, heads = p["B"], p["c"], p["heads"]
+    cpad = ops.pad32(c)
+    pl = ops.Planes(torch.zeros(Bn * c, 2 * cpad, dtype=torch.int16, device=DEV), Bn * c, c, cpad)
+    sq, sk = dev(i["sq"]), dev(i["sk"])
+    ops.chanattn_build(dev(i["G"]), sq.data_ptr(), c, sk.data_ptr(), c, dev(i["temp"]), dev(i["wp"]), pl, Bn, c, heads)
+    torch.cuda.synchronize()
+    assert pads_zero(ops, pl)
+    return dict(y=None, raw=[pl.p], decoded=(ops.planes_to_float(pl), None))
+
+
+def run_gffm(ops, i, p):
+    Bn, c = p["B"], p["c"]
+    cpad = ops.pad32(c)
+    px, py = (ops.Planes(torch.zeros(Bn * c, 2 * cpad, dtype=torch.int16, device=DEV), Bn * c, c, cpad) for _ in range(2))
+    ops.gffm_build(dev(i["E"]), px, py, Bn, c)
+    torch.cuda.synchronize()
+    assert pads_zero(ops, px) and pads_zero(ops, py)
+    return dict(y=None, raw=[px.p, py.p], decoded=(torch.cat([ops.planes_to_float(px), ops.planes_to_float(py)]), None))
+
+
+def run_tail(ops, i, p):
+    Bn, C, Hc, Wc = p["B"], p["C"], p["Hc"], p["Wc"]
+    y = nanbuf(Bn, C, Hc, Wc)
+    pl = ops.alloc_planes(Bn * Hc * Wc, C, DEV, zero=True) if p.get("planes") else None
+    cm = dev(V.nhwc(i["cm"]))
+    if p.get("misalign"):                         # the map starts one float past a 16-byte boundary
+        buf = nanbuf(1 + cm.numel() + 3)
+        buf[1:1 + cm.numel()] = cm.flatten()
+        cm = buf[1:1 + cm.numel()].view(cm.shape)
+    ops.tail_fuse(cm, Hc * Wc * C, dev(V.nhwc(i["xt"])) if "xt" in i else None, dev(i["scale"]), dev(i["shift"]), y,
+                  Bn, Hc, Wc, p["Hx"], p["Wx"], out_planes=pl)
+    out = dict(y=y, raw=[y] + ([pl.p] if pl else []))
+    if pl:
+        out["planes"] = (pl, ops.FMT_B3)
+        out["planes_src"] = V.nhwc(y)
+    return out
+
+
+def run_nchw_to_planes(ops, i, p):
+    from mmsa import lib
+    Bn, C, HW = p["B"], p["C"], p["HW"]
+    sb = C * HW + p["pad"]
+    src = nanbuf(Bn, sb)
+    src[:, :C * HW] = dev(i["x"].reshape(Bn, C * HW))
+    pl = ops.alloc_planes(Bn * HW, C, DEV, zero=True)
+    lib.call("mmsa_nchw_to_planes", src.data_ptr(), sb, pl.p.data_ptr(), 2 * pl.kpad, Bn, C, HW, ops._stream())
+    torch.cuda.synchronize()
+    planes_equal_split(ops, pl, dev(i["x"].permute(0, 2, 1).reshape(Bn * HW, C)), ops.FMT_B3)     # a pure layout change: the planes of the token matrix
+    return dict(y=None, raw=[pl.p], decoded=(ops.planes_to_float(pl), None))
+
+
+def run_tokens_to_nchw(ops, i, p):
+    from mmsa import lib
+    Bn, C, HW = p["B"], p["C"], p["HW"]
+    ld = C + p["pad"]
+    src = nanbuf(Bn * HW, ld)
+    src[:, :C] = dev(i["x"])
+    y = nanbuf(Bn, C, HW)
+    lib.call("mmsa_tokens_to_nchw", src.data_ptr(), ld, y.data_ptr(), Bn, HW, C, ops._stream())
+    return dict(y=y, raw=[y])
+
+
+def run_head_fuse(ops, i, p):
+    from mmsa import lib
+    Bn, C, sizes = p["B"], p["C"], p["sizes"]
+    ld = C + 4
+    zs = []
+    for l, (h, w) in enumerate(sizes):
+        z = nanbuf(Bn * h * w, ld)
+        z[:, :C] = dev(V.nhwc(i[f"z{l}"]))
+        zs.append(z)
+    (H, W) = sizes[0]
+    y = nanbuf(Bn * H * W, C)
+    pl = ops.alloc_planes(Bn * H * W, C, DEV, zero=True)
+    sc, sh = dev(i["scale"]), dev(i["shift"])
+    lib.call("mmsa_head_fuse", zs[0].data_ptr(), zs[1].data_ptr(), sizes[1][0], sizes[1][1], zs[2].data_ptr(), sizes[2][0], sizes[2][1],
+             zs[3].data_ptr(), sizes[3][0], sizes[3][1], ld, sc.data_ptr(), sh.data_ptr(), pl.p.data_ptr(), 2 * pl.kpad, y.data_ptr(), C,
+             Bn, H, W, C, ops.ACT["relu"], ops._stream())
+    return dict(y=y, raw=[y, pl.p], planes=(pl, ops.FMT_B3))
+
+
+RUN = {"dwconv": run_dwconv, "gconv": run_gconv, "gfe_qkv": run_gfe_qkv, "dwpair_gate": run_dwpair_gate, "ca_apply": run_ca_apply,
+       "gelu_gate": run_gelu_gate, "pool_hw": run_pool_hw, "colstats": run_colstats, "ffrm": run_ffrm, "lnhw": run_lnhw, "gram": run_gram,
+       "chanattn": run_chanattn, "gffm": run_gffm, "tail": run_tail, "nchw_to_planes": run_nchw_to_planes, "tokens_to_nchw": run_tokens_to_nchw,
+       "head_fuse": run_head_fuse}
+
+
+@pytest.mark.parametrize("cid,op,p", CASES, ids=[c[0] for c in CASES])
+def test_variant(ops, cid, op, p):
+    i, r, bnd = V.case_data(cid, op, p)
+    first = RUN[op](ops, i, p)
+    again = RUN[op](ops, i, p)
+    torch.cuda.synchronize()
+    for a, b in zip(first["raw"], again["raw"]):
+        assert torch.equal(bits(a), bits(b)), f"{cid}: two identical calls differ in their bits"
+    y = first.get("y")
+    if y is not None:
+        if "mask" in first:                      # only part of the output is defined (gram_tn's diagonal head blocks)
+            m = first["mask"]
+            y, r, bnd = torch.where(m, y.cpu(), 0.0), torch.where(m, r, 0.0), torch.where(m, bnd, 0.0)
+        ratio = V.assert_inside(y, r, bnd, cid)
+        print(f"{cid}: worst |y - r| / bound = {ratio:.3f}")
+        if "planes" in first:
+            pl, fmt = first["planes"]
+            planes_equal_split(ops, pl, first.get("planes_src", y).to(DEV), fmt)
+    if "decoded" in first:                        # planes only: the bound plus the format's own rounding
+        d, rel = first["decoded"]
+        ratio = V.assert_inside(d, r, bnd + (rel * r.abs() if rel else 0.0), cid + " (planes)")
+        print(f"{cid}: worst |planes - r| / bound = {ratio:.3f}")
+
+
+@pytest.mark.parametrize("cid,op,p", RAISES, ids=[c[0] for c in RAISES])
+def test_variant_refused(ops, cid, op, p):
+    """Shapes a launcher must refuse: image groups outside the 7 x 7 kernels; head blocks that do not divide the channels."""
+    i, _, _ = V.case_data(cid, op, p)
+    with pytest.raises(RuntimeError):
+        RUN[op](ops, i, p)
