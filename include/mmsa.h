@@ -405,6 +405,27 @@ int mmsa_slide_argmax_eval(const float* logits, int n, int C, int hs, int ws, co
                            int hc, int wc, int* uncovered, const unsigned char* label, int Hl, int Wl, const unsigned char* lut, const int* ymap,
                            const int* xmap, const int* slots, int n_slots, int64_t* counts, mmsa_stream_t stream);
 
+/* --- the picture of a prediction (segmentation/mmseg_custom/apis/test_bs.py:257-349, the `--show` / `--show-dir` output): `tensor2imgs` (test_bs.py:18-63) on
+ *     planes 0..2 of the input tensor -> the crop `img[:h, :w]` (test_bs.py:275-276) -> `show_result` (tools/color_gt_according_palette.py:23-81:
+ *     color_seg[seg == label] = color, channels reversed, img * (1 - opacity) + color_seg * opacity, .astype(uint8)), in one pass.
+ *     pred: uint8 class map, pixel (b, y, x) at pred[b * pred_image_stride + y * pred_row_stride + x] (a crop of a larger map needs no copy).
+ *     palette: DEVICE uint32 [npal], 1 <= npal <= 256, entry = c0 | c1 << 8 | c2 << 16 (bits 24..31 ignored); palette_reverse swaps c0 and c2 (what
+ *       show_result does).  A class without an entry -- 255, the "uncovered" value of mmsa_slide_argmax, included -- has colour 0 (the zero-initialised color_seg).
+ *     opacity in (0, 1] and one_minus_opacity = the double 1 - opacity, formed by the CALLER.  out[c] = uint8(double(img[c]) * one_minus_opacity +
+ *       double(colour[c]) * opacity): two float64 products and one float64 sum, each rounded, no fused multiply-add, then truncation.
+ *     out: uint8 [B, h, w, 3] contiguous (HWC, what mmcv.imwrite takes).
+ *   render_u8: src = NULL (a black image: out = uint8(colour * opacity)) or the raw uint8 frames [B, Hs, Ws, 3], Hs >= h, Ws >= w, of which the top-left
+ *     h x w is used; src_reverse swaps the frame's channels 0 and 2 first.
+ *   render_denorm_f32: src = the normalised float32 tensor [B, Cs >= 3, Hs >= h, Ws >= w] the backbone read; HOST mean[3], std[3] per PLANE.  Per pixel, in
+ *     float32 with one rounding per step: d[p] = n[p] * std[p] + mean[p]; img[c] = d[2 - c] when to_rgb, else d[c]; * 255.0f when mul255 (norm_by_max);
+ *     truncation to uint8.  Values below 0 / from 255 up saturate to 0 / 255 and NaN gives 0 (the reference's C cast is undefined there). --- */
+int mmsa_render_u8(const unsigned char* pred, long pred_image_stride, long pred_row_stride, int B, int h, int w, const unsigned* palette, int npal,
+                   int palette_reverse, const unsigned char* src, int Hs, int Ws, int src_reverse, double opacity, double one_minus_opacity,
+                   unsigned char* out, mmsa_stream_t stream);
+int mmsa_render_denorm_f32(const unsigned char* pred, long pred_image_stride, long pred_row_stride, int B, int h, int w, const unsigned* palette, int npal,
+                           int palette_reverse, const float* src, int Cs, int Hs, int Ws, const float* mean, const float* std, int to_rgb, int mul255,
+                           double opacity, double one_minus_opacity, unsigned char* out, mmsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,8 @@ from . import preprocess  # noqa: F401  (raw frames -> normalised NCHW, whole or
 from .preprocess import FrameFeeder, Preprocess
 from . import evaluate  # noqa: F401  (confusion counts and mIoU on device: LabelPrep, confusion, Evaluator)
 from .evaluate import Evaluator, LabelPrep, confusion
+from . import render  # noqa: F401  (the picture of a prediction on device: palette map over the frame, show_result)
+from .render import Renderer
 from .registry import BACKBONES, HEADS, build_backbone, build_head
 
 for _cls in (SAMAdapterbimodalMixModNewInTwinConvNEW, SAMAdapterbimodalMixModNewInTwinConvNEWwithcp):
@@ -34,4 +36,4 @@ if not _HAVE_MMSEG:     # local registry (no mmseg in the process): nothing to o
 
 __all__ = ["SegformerHead", "HEADS", "build_head", "register_head", "SAMAdapterbimodalMixModNewInTwinConvNEW", "SAMAdapterbimodalMixModNewInTwinConvNEWwithcp",
            "BACKBONES", "build_backbone", "ops", "lib", "inference", "Chains", "Replay", "AttentionRangeError", "OperandRangeError",
-           "preprocess", "Preprocess", "FrameFeeder", "evaluate", "Evaluator", "LabelPrep", "confusion"]
+           "preprocess", "Preprocess", "FrameFeeder", "evaluate", "Evaluator", "LabelPrep", "confusion", "render", "Renderer"]

@@ -153,6 +153,16 @@ def _check_overlap(boxes, what):
                            "(use slide_inference + argmax_map, or a larger stride)")
 
 
+def _picture_source(render, preprocess, frame, H, W, return_map, what):
+    """The source `render=` paints over in the slide modes (None without `render=`); refusals come before any launch."""
+    if render is None:
+        return None
+    if not return_map:
+        raise RuntimeError(f"mmsa.{what}: render= paints the stored map; drop return_map=False")
+    from .render import slide_source
+    return slide_source(render, preprocess, frame, H, W, what)
+
+
 def _class_map(lg, n, tab, out, B, H, W, hc, wc, unc, labels, evaluator, case, fused, return_map):
     """The class-map launch of the three class-map calls.  Without `labels`: mmsa_slide_argmax.  With `labels` (raw uint8 label maps [B, Hl, Wl]) and
     `evaluator` (mmsa.evaluate.Evaluator): the confusion counts of the map are ADDED to the evaluator's buffer as well -- by the same launch
@@ -180,7 +190,7 @@ def _class_map(lg, n, tab, out, B, H, W, hc, wc, unc, labels, evaluator, case, f
 @_on_device
 @torch.no_grad()
 def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preprocess=None, labels=None, evaluator=None, case=None, fused=None,
-                    return_map=True):
+                    return_map=True, render=None):
     """`simple_test` of a sliding-window frame (ED:191-234 + ED:449,477) -> uint8 class map [B, H, W], without the
     [B, classes, H, W] logits canvas: every window's logits stay at head resolution and ONE kernel (mmsa_slide_argmax) resizes,
     sums the overlapping windows in window order, divides by the count and takes the argmax -- the same additions in the same order
@@ -188,7 +198,9 @@ def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preproc
     batches of `max_batch`; with static shapes the whole function is HIP-graph capturable (no host sync inside).
     `preprocess=` (mmsa.preprocess.Preprocess): img is the pair (rgb, aux) of raw frames; the windows are cut AND normalised by one launch.
     `labels=` + `evaluator=` (mmsa.evaluate.Evaluator; `case=` with a per-case one): the map's confusion counts are added to the evaluator on device
-    (see _class_map); the returned map is unchanged, `return_map=False` returns None in its place."""
+    (see _class_map); the returned map is unchanged, `return_map=False` returns None in its place.
+    `render=` (mmsa.render.Renderer): a second launch paints the frame's picture (test_bs.py:257-349, `show_result`) -> (map, unc, picture uint8
+    [B, H, W, 3]); over the raw uint8 RGB frames with `preprocess=` (they must have the map's size), else over the de-normalised `img`."""
     import ctypes
     if preprocess is not None:
         rgb, aux, B, H, W = _raw(preprocess, img, "slide_class_map")
@@ -202,6 +214,7 @@ def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preproc
         cut = lambda chunk: _crops(img, chunk, crop_size)
     if H < crop_size[0] or W < crop_size[1]:
         raise RuntimeError("mmsa.slide_class_map: the image must be at least as large as the crop")
+    src = _picture_source(render, preprocess, img, H, W, return_map, "slide_class_map")
     boxes = crop_boxes(H, W, crop_size, stride)
     _check_overlap(boxes, "slide_class_map")
     _pair(backbone, head)
@@ -219,19 +232,36 @@ def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preproc
     out = torch.empty(B, H, W, dtype=torch.uint8, device=device)
     unc = torch.zeros(1, dtype=torch.int32, device=device)
     _class_map(lg, n, tab, out, B, H, W, crop_size[0], crop_size[1], unc, labels, evaluator, case, fused, return_map)
+    if render is not None:
+        return out, unc, render(out, src)
     return (out if return_map else None), unc          # unc[0] != 0 <=> some pixel is not covered (ED:220); checked by the caller outside a capture
 
 
 @_on_device
 @torch.no_grad()
-def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator=None, case=None, fused=None, return_map=True):
+def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator=None, case=None, fused=None, return_map=True, render=None):
     """Whole-image `simple_test`: resize x4 (bilinear, align_corners=False) + argmax fused (ED:90-94,449,477) -> uint8 [B, H, W].
     `preprocess=` (mmsa.preprocess.Preprocess): img is the pair (rgb, aux) of raw frames, normalised (and padded) by one launch.
-    `labels=` + `evaluator=` (+ `case=`): as in slide_class_map."""
+    `labels=` + `evaluator=` (+ `case=`): as in slide_class_map.
+    `render=` (mmsa.render.Renderer): a second launch paints the frame's picture -> (map, picture uint8 [B, H, W, 3]); over the raw uint8 RGB frames where
+    `preprocess=` got frames of the map's size, else over the de-normalised input tensor (a padded or device-resized frame, a float32 RGB modality, no
+    `preprocess=`)."""
     import ctypes
+    src = None
     if preprocess is not None:
-        img = preprocess(*_raw(preprocess, img, "whole_class_map")[:2])
+        rgb, aux = _raw(preprocess, img, "whole_class_map")[:2]
+        img = preprocess(rgb, aux)
+        if render is not None:
+            from .render import raw_source
+            src = raw_source(rgb, img.shape[2], img.shape[3])
     _check(img)
+    if render is not None:
+        if not return_map:
+            raise RuntimeError("mmsa.whole_class_map: render= paints the stored map; drop return_map=False")
+        if src is None:
+            if render.preprocess is None:
+                raise RuntimeError("mmsa.whole_class_map: render= on the normalised tensor needs the Renderer made with preprocess= (mean, std, to_rgb, norm_by_max)")
+            src = img = img.contiguous()
     _pair(backbone, head)
     feats, _ = backbone(img)
     lg = head(feats)
@@ -240,6 +270,8 @@ def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator
     out = torch.empty(B, H, W, dtype=torch.uint8, device=img.device)
     unc = torch.zeros(1, dtype=torch.int32, device=img.device)
     _class_map(lg, B, tab, out, B, H, W, H, W, unc, labels, evaluator, case, fused, return_map)
+    if render is not None:
+        return out, render(out, src)
     return out if return_map else None
 
 
@@ -327,6 +359,14 @@ class FrameResult:
         self._replay._owner._verify(self._replay.seq)
         return (self._runner.out if self._has_map else None), self._runner.unc
 
+    def picture(self):
+        """The frame's picture uint8 [B, H, W, 3] of a runner made with render= -- verified, exactly as outputs() is.  The runner's static buffer: read it
+        before the next run()."""
+        if self._runner.render is None:
+            raise RuntimeError("mmsa.FrameResult.picture: the SlideRunner was made without render=")
+        self._replay._owner._verify(self._replay.seq)
+        return self._runner.pic
+
     @property
     def unverified(self):
         return (self._runner.out if self._has_map else None), self._runner.unc
@@ -338,9 +378,10 @@ class SlideRunner:
     (mmsa_slide_argmax) turns the head-resolution logits into the class map.  Same class map as slide_inference + argmax_map, bit
     for bit.  `frame` is the static [B, 6, H, W] buffer the runner reads on every run().
     With `preprocess=` (mmsa.preprocess.Preprocess) `frame` is the pair (rgb, aux) of raw [B, Hs, Ws, 3] buffers -- the runner's static inputs -- and the
-    windows are cut AND normalised from them by one launch; run(frame=pair) reads another pair of the same geometry instead (mmsa.preprocess.FrameFeeder's slots)."""
+    windows are cut AND normalised from them by one launch; run(frame=pair) reads another pair of the same geometry instead (mmsa.preprocess.FrameFeeder's slots).
+    With `render=` (mmsa.render.Renderer) every run() also paints the frame's picture into a static buffer (one more launch): FrameResult.picture()."""
 
-    def __init__(self, backbone, head, frame, crop_size, stride, chains=2, check_every=1, preprocess=None):
+    def __init__(self, backbone, head, frame, crop_size, stride, chains=2, check_every=1, preprocess=None, render=None):
         import ctypes
         from .chains import Chains
         self.preprocess = preprocess
@@ -353,6 +394,8 @@ class SlideRunner:
             self.frame = frame.contiguous()
             B, _, H, W = self.frame.shape
             self.device = self.frame.device
+        self.render = render
+        _picture_source(render, preprocess, self.frame, H, W, True, "SlideRunner")      # refuses a frame the picture has no source for
         _pair(backbone, head)
         self.crop_size = tuple(crop_size)
         boxes = crop_boxes(H, W, crop_size, stride)
@@ -369,6 +412,10 @@ class SlideRunner:
             self.tab = (ctypes.c_int * (3 * n))(*[v for b, (y1, x1, _, _) in self.jobs for v in (b, y1, x1)])
             self.out = torch.empty(B, H, W, dtype=torch.uint8, device=self.device)
             self.unc = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self.pic = None
+            if render is not None:
+                render.palette_on(self.device)
+                self.pic = torch.empty(B, H, W, 3, dtype=torch.uint8, device=self.device)
 
     def _cut(self, frame, out=None):
         if self.preprocess is not None:
@@ -392,6 +439,7 @@ class SlideRunner:
             frame = self.preprocess.check(*frame)
             if any(f.shape != s.shape or f.dtype != s.dtype or f.device != s.device for f, s in zip(frame, self.frame)):
                 raise RuntimeError("mmsa.SlideRunner.run(frame=...): the pair must have the shape, dtypes and device of the runner's own buffers")
+        src = _picture_source(self.render, self.preprocess, frame, self.out.shape[1], self.out.shape[2], return_map, "SlideRunner.run")
         with torch.cuda.device(self.device):
             self._cut(frame, out=self.crops)
             rp = self.chains.replay()
@@ -400,6 +448,8 @@ class SlideRunner:
             self.unc.zero_()
             _class_map(lg, len(self.jobs), self.tab, self.out, B, H, W, self.crop_size[0], self.crop_size[1], self.unc, labels, evaluator, case, fused,
                        return_map)
+            if self.render is not None:
+                self.render(self.out, src, out=self.pic)
         return FrameResult(self, rp, has_map=return_map)
 
     def check_guard(self):
