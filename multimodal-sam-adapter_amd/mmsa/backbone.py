@@ -9,14 +9,15 @@ All arithmetic is done by hand-written HIP kernels through the C ABI (mmsa.ops);
 and provides the stream.  Activations are fp32, token-major (NHWC) end to end; only the four outputs are written
 NCHW by the fused tail kernel.  There is no CPU / PyTorch fallback."""
 import contextlib
+import functools
 import math
-
 import os
 
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, pack
+from .pack import PackPlan, _linear_resize_rows, fold_gfe_qkv   # noqa: F401  (fold_gfe_qkv: its importers' name for it)
 from .params import CONVNEXT_ARCH, build_tree
 
 _VIT_DEFAULTS = dict(img_size=1024, patch_size=16, in_chans=3, embed_dim=1024, depth=24, mlp_ratio=4.0,
@@ -89,21 +90,6 @@ class _Tagged:
 
     def nbytes(self):
         return self.ws.nbytes()
-
-
-def fold_gfe_qkv(q1, q2, q1_bias=None, groups=32):
-    """The GFE's qkv2(qkv1(x)) (AM:87-92: grouped 1x1 conv c -> 3c, then grouped 3x3 conv 3c -> 3c, the same groups, no bias, nothing in between) is
-    itself a grouped 3x3 conv c -> 3c: group g of qkv2 reads exactly the channels group g of qkv1 wrote, and zero padding commutes with a bias-free
-    1x1 conv, so the border pixels are exact too.  From the module weights q1 [3c, c/G, 1, 1] and q2 [3c, 3c/G, 3, 3] returns
-    W_eff[g][tap][ci][co] = sum_m q1[g][ci][m] q2[g][tap][m][co], summed in float64 and rounded once to fp32 -- the layout of the packed `q2`
-    (ops.gfe_qkv).  With a qkv1 bias the padded border of qkv2 would see zeros where the composition sees the bias: no fold, returns None."""
-    if q1_bias is not None:
-        return None
-    G = groups
-    co, ci = q1.shape[0] // G, q1.shape[1]
-    a = q1.detach().double().reshape(G, 1, co, ci).transpose(2, 3)            # [G][1][ci][m]
-    b = q2.detach().double().reshape(G, co, co, 9).permute(0, 3, 2, 1)        # [G][tap][m][co]
-    return torch.matmul(a, b).float().contiguous()                             # [G][tap][ci][co]
 
 
 class SAMAdapterbimodalMixModNewInTwinConvNEW(nn.Module):
@@ -224,7 +210,7 @@ class SAMAdapterbimodalMixModNewInTwinConvNEW(nn.Module):
     # projections, ConvFFN); "up" = the 2x2 transposed conv of the tail.  The TwinConvNeXt / neck GEMMs stay on bf16 hi/lo (the most
     # error-sensitive part of the path: SURVEY appendix F).  `model.h8_sites = ()` keeps every site on 16-bit hi/lo pairs.
     # Every switch of this class that changes numerics is an ATTRIBUTE (h8_sites, h8c, cnx_f16, fold_ln, fold_adapter_ln, fold_convnext_ln, share_c_norm,
-    # fuse_convnext_mlp, fuse_gfe_qkv, attention_precision, attention_guard, range_fallback, inter_follow_blocks, msda_value): set it before the first forward, or call invalidate() after changing it; the A/B tools pass
+    # fuse_convnext_mlp, fuse_gfe_qkv, attention_precision, attention_guard, range_fallback, inter_follow_blocks, msda_value): set it before the first forward; the pack-time ones among them (PackPlan.settings()) are compared with the pack by every forward, which packs again when one has changed, the others need invalidate(); the A/B tools pass
     # them through `bench.py --set attr=value`.  No environment variable changes what this module computes.
     # "attnv" = the attention kernels run P V on the fp16 MFMA: the v third of the qkv planes (GEMM output and bias rows) is h8-encoded
     # and P is rounded to fp16 (csrc/attention.hip VF; 2.9e-5 on the ViT-B oracle study, LAB_NOTES.md 4.1); the kernels with the rel-pos terms
@@ -277,16 +263,8 @@ class SAMAdapterbimodalMixModNewInTwinConvNEW(nn.Module):
     def _wide(self):
         return bool(getattr(self, "_wide_range", False))
 
-    def _pair_fmt(self):
-        """The hi/lo PAIR format of the ViT-block GEMMs (h8 off, or a block moved off single fp16 operands by the logit guard): fp16 pairs (f3: 22
-        significant bits, +-65504), or bf16 pairs (16 bits, fp32's range) in the wide-range state."""
-        return ops.FMT_B3 if self._wide() else ops.FMT_F3
-
     def _h8_sites(self):
-        sites = tuple(getattr(self, "h8_sites", self.H8_DEFAULT))
-        if self._wide():   # wide-range state: no GEMM site on fp16-based planes ("attnv", the attention kernels' own operands, stays)
-            sites = tuple(s_ for s_ in sites if s_ not in ("vit", "inter", "up", "cnx", "cnx2"))
-        return sites
+        return PackPlan.of(self).h8_sites
 
     @contextlib.contextmanager
     def chain(self, index):
@@ -302,72 +280,7 @@ class SAMAdapterbimodalMixModNewInTwinConvNEW(nn.Module):
         finally:
             self._ws = base
 
-    # ------------------------------------------------------------------ packing (one-time weight preprocessing)
-    @torch.no_grad()
-    def _block_gemm_planes(self, sd, i, fmt, fold, dev):
-        """The four GEMM weights of ViT block i as operand planes of format `fmt` (+ the LayerNorm-folded forms of qkv / lin1 when
-        `fold`): head widths that are not a multiple of 32 zero-padded per head (ViT-H), see _pack."""
-        heads_, hd_true, hd_ = self.cfg["num_heads"], self._hd_true, self._hd_pad
-
-        def pad_head_rows(w, groups):
-            if hd_ == hd_true:
-                return w.contiguous()
-            v = w.reshape(groups, heads_, hd_true, *w.shape[1:])
-            out = v.new_zeros(groups, heads_, hd_, *w.shape[1:])
-            out[:, :, :hd_true] = v
-            return out.reshape(groups * heads_ * hd_, *w.shape[1:]).contiguous()
-
-        fp8 = self._fp8_wanted()   # (fmt = FMT_W8, or a pair format in the guard's / wide-range state's repacks: the same effective weights)
-
-        def planes(w2d):
-            if fmt == ops.FMT_W8:
-                return ops.w8_planes(w2d.contiguous())
-            return ops.split_planes(w2d.contiguous(), None, fmt=fmt, weight=fmt == ops.FMT_H8)
-
-        def folded(w, bias, lnw, lnb):
-            """(planes of W o lnw, column sums of those planes as the kernel will read them, W lnb + bias); fp8 weights: of the effective weights"""
-            wk, w = self._fp8_effective(w, lnw) if fp8 else (w * lnw[None, :], w)
-            pl = planes(wk)
-            cs = ops.planes_to_float(pl, cols=w.shape[1])[: w.shape[0]].double().sum(1).float().contiguous()
-            return pl, cs, (w.double() @ lnb.double()).float().add_(bias).contiguous()
-
-        def plain(w):
-            return planes(self._fp8_effective(w)[0] if fp8 else w)
-        b = f"blocks.{i}."
-        g = lambda k: sd[b + k].detach().to(dev, torch.float32)   # noqa: E731
-        qkv_w, qkv_bias = pad_head_rows(g("attn.qkv.weight"), 3), pad_head_rows(g("attn.qkv.bias"), 3)
-        proj_w = pad_head_rows(g("attn.proj.weight").t(), 1).t().contiguous()    # zero COLUMNS for the pad channels
-        skip = fp8 and fold   # (fp8: the unfolded qkv / lin1 would be quantized only to be replaced)
-        out = dict(qkv=None if skip else plain(qkv_w), proj=plain(proj_w), lin1=None if skip else plain(g("mlp.lin1.weight")), lin2=plain(g("mlp.lin2.weight")))
-        if fold:   # the consumers' weights carry their LayerNorm (the unfolded planes are not kept: the fold is all or nothing per model)
-            out["qkv"], out["qkv_cs"], out["qkv_bf"] = folded(qkv_w, qkv_bias, g("norm1.weight"), g("norm1.bias"))
-            out["lin1"], out["lin1_cs"], out["lin1_bf"] = folded(g("mlp.lin1.weight"), g("mlp.lin1.bias"), g("norm2.weight"), g("norm2.bias"))
-        return out
-
-    def _fp8_wanted(self):
-        return bool(getattr(self, "fp8_weights", False))
-
-    def _fp8_check(self, D, Da, hidden):
-        """fp8_weights needs the ViT-block GEMMs on h8c planes: raise ValueError (at pack time) where they would not run there."""
-        sites = tuple(getattr(self, "h8_sites", self.H8_DEFAULT))   # (the configured sites: the wide-range state keeps the fp8 values on bf16 pairs)
-        why = ("'vit' is not among h8_sites" if "vit" not in sites else "h8c is off" if not self._h8c_wanted()
-               else f"a contraction is shorter than 512 (embed {D}, attention width {Da}, MLP hidden {hidden})" if min(D, Da, hidden) < 512
-               else f"a contraction is not a multiple of 128 (embed {D}, attention width {Da}, MLP hidden {hidden})" if (D % 128 or Da % 128 or hidden % 128)
-               else None)
-        if why:
-            raise ValueError(f"mmsa: fp8_weights needs the ViT-block GEMMs on h8c planes, but {why}")
-
-    @staticmethod
-    def _fp8_effective(w, lnw=None):
-        """fp8 weights: (what the kernel multiplies by -- 2^e e4m3(W o lnw), exact in fp32 --, the same in the reference's parameterisation: that / lnw,
-        and W itself in a column whose LayerNorm weight is 0, which then contributes through the LayerNorm bias alone -- consistently in the folded bias)."""
-        if lnw is None:
-            q = ops.fp8_dequantize(*ops.fp8_quantize(w))
-            return q, q
-        q = ops.fp8_dequantize(*ops.fp8_quantize(w * lnw[None, :]))
-        nz = lnw[None, :] != 0
-        return q, torch.where(nz, q / torch.where(nz, lnw[None, :], torch.ones_like(lnw[None, :])), w)
-
+    # ------------------------------------------------------------------ packing (one-time weight preprocessing: mmsa/pack.py)
     @torch.no_grad()
     def effective_state_dict(self):
         """state_dict() with the weights this model actually multiplies by, in the reference's parameterisation: same keys, shapes and order; with
@@ -375,433 +288,28 @@ class SAMAdapterbimodalMixModNewInTwinConvNEW(nn.Module):
         other tensor -- and state_dict() itself -- is untouched.  Loaded into the reference (or the oracle) it computes what this model computes."""
         sd = self.state_dict()
         out = type(sd)((k, v.detach().clone()) for k, v in sd.items())
-        if not self._fp8_wanted():
+        plan = PackPlan.of(self)
+        if not plan.fp8_weights:
             return out
-        fold = self._fold_ln_wanted()
+        fold = plan.fold_ln
         dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
         for i in range(self.cfg["depth"]):
             b = f"blocks.{i}."
             for key, ln in (("attn.qkv.weight", "norm1.weight"), ("attn.proj.weight", None), ("mlp.lin1.weight", "norm2.weight"), ("mlp.lin2.weight", None)):
                 w = sd[b + key].detach().to(dev, torch.float32)
                 lnw = sd[b + ln].detach().to(dev, torch.float32) if (fold and ln) else None
-                out[b + key] = self._fp8_effective(w, lnw)[1].to(sd[b + key].device, sd[b + key].dtype)
+                out[b + key] = pack.fp8_effective(w, lnw)[1].to(sd[b + key].device, sd[b + key].dtype)
         return out
 
-    def _pack_state_dict(self, dev):
-        """The float parameters on `dev`, plus ZERO stand-ins for the tensors a ViT built with qkv_bias=False / use_rel_pos=False does not
-        have (IE:317,320-327): a zero qkv bias and zero rel-pos tables make the kernels compute exactly what the reference computes
-        without them (the pad tokens' k / v = bias = 0; rel_pos . q = 0 added to the logits)."""
-        sd = {k: v.detach().to(dev, torch.float32) for k, v in self.state_dict().items() if v.dtype.is_floating_point}
-        cfg = self.cfg
-        D, hd = cfg["embed_dim"], cfg["embed_dim"] // cfg["num_heads"]
-        grid = cfg["pretrained_size"] // cfg["patch_size"]
-        for i in range(cfg["depth"]):
-            b = f"blocks.{i}.attn."
-            if not cfg["qkv_bias"]:
-                sd[b + "qkv.bias"] = torch.zeros(3 * D, device=dev)
-            if not cfg["use_rel_pos"]:
-                L = 2 * (grid if i in cfg["global_attn_indexes"] else cfg["window_size"]) - 1
-                sd[b + "rel_pos_h"] = torch.zeros(L, hd, device=dev)
-                sd[b + "rel_pos_w"] = torch.zeros(L, hd, device=dev)
-        return sd
+    def _fold_ln_wanted(self):
+        """Whether the pack folds the ViT blocks' LayerNorms into their consumer GEMMs (PackPlan.fold_ln)."""
+        return PackPlan.of(self).fold_ln
 
-    def _h8c_wanted(self):
-        """h8 sites with deep contractions travel as h8c planes (default); `model.h8c = False` keeps them on h8 line planes (A/B)."""
-        return bool(getattr(self, "h8c", True))
+    def _pack(self, dev):   # pre-pack the weights for `dev` (mmsa/pack.py): the single entry point of every pack and repack
+        return pack.pack(self, dev)
 
-    def _cnx_f16_wanted(self):
-        """TwinConvNeXt GEMMs on fp16 hi/lo pairs (default) instead of bf16 hi/lo; `model.cnx_f16 = False` for the A/B.  Not with
-        the opt-in ConvNeXt LayerNorm fold (its depthwise kernel writes bf16 hi/lo planes)."""
-        fold = bool(getattr(self, "fold_convnext_ln", False))
-        return bool(getattr(self, "cnx_f16", True)) and not fold and not self._wide()
-
-    def _fold_ln_wanted(self, hidden=None):
-        """Whether _pack folds the ViT blocks' LayerNorms into their consumer GEMMs (a pack-time setting: checkpoint.load_packed compares it)."""
-        D, heads = self.cfg["embed_dim"], self.cfg["num_heads"]
-        Da = heads * ops.pad32(D // heads)
-        hidden = int(D * self.cfg["mlp_ratio"]) if hidden is None else hidden
-        return (bool(getattr(self, "fold_ln", True)) and D % 64 == 0
-                and (3 * Da) % 128 == 0 and hidden % 128 == 0)
-
-    def _fold_adapter_ln_wanted(self):
-        """Whether _pack folds the adapter tokens' LayerNorms into their consumer GEMMs (opt-in `fold_adapter_ln`; a pack-time setting that drives the
-        run-time path: checkpoint.load_packed compares it)."""
-        cfg = self.cfg
-        D = cfg["embed_dim"]
-        hid_c = int(D * cfg["cffn_ratio"]) if cfg["with_cffn"] else 128
-        return bool(getattr(self, "share_c_norm", True) and getattr(self, "fold_adapter_ln", False) and "inter" in self._h8_sites() and D % 64 == 0
-                    and int(D * cfg["deform_ratio"]) % 128 == 0 and hid_c % 128 == 0
-                    and not self._inter_pair_set())   # (the fold hands c's planes from one interaction's producer to the next one's consumers: one format for all)
-
-    @torch.no_grad()
-    def _pack(self, dev):
-        """Pre-pack the weights for `dev`.  The guard words of the model live here too: one logit word per ViT block (check_attention_guard) and, last, the
-        clamp watch word (include/mmsa.h "Clamp watch") -- weight planes that had to clamp a value report into it like every forward's activations do."""
-        depth = self.cfg["depth"]
-        guard = torch.zeros(depth + 1, device=dev)
-        carry, self._carry_modes = getattr(self, "_carry_modes", None), None
-        with ops.clamp_watch(guard[depth:]):
-            pk = self._pack_impl(dev)
-            if carry is not None and len(carry) == len(pk["blocks"]):
-                # a pack was dropped whose blocks had settled their attention precision (the switch to the wide-range state; interactions following their
-                # blocks): the decisions carry over, and a block on pair attention runs its four GEMMs on pairs too (check_attention_guard)
-                sd_dev = None
-                for bp, (amode, ml) in zip(pk["blocks"], carry):
-                    bp["max_logit"] = ml
-                    if amode is not None:
-                        bp["amode"] = amode
-                    if amode == "b3" and bp["qkv"].fmt != self._pair_fmt():
-                        if sd_dev is None:
-                            sd_dev = self._pack_state_dict(dev)
-                        bp.update(self._block_gemm_planes(sd_dev, bp["index"], self._pair_fmt(), pk["fold_ln"], dev))
-        pk["attn_guard"] = guard
-        # a WEIGHT that had to be clamped stays clamped in its planes: kept as a host-side flag of this pack (the device word is zeroed with every
-        # refusal, the planes are not repacked by that: ADVICE r05) -- check_attention_guard() goes wide / refuses on it until the pack is dropped
-        pk["weights_clamped"] = float(guard[depth].item())
-        guard[depth:].zero_()
-        pk["wide"] = self._wide()
-        pk["inter_pairs"] = sorted(self._inter_pair_set())
-        return pk
-
-    def _pack_impl(self, dev):
-        cfg = self.cfg
-        h8_sites = self._h8_sites()
-        sd = self._pack_state_dict(dev)
-        pk = {"h8_sites": h8_sites, "h8c": self._h8c_wanted()}
-        D = cfg["embed_dim"]
-
-        def planes(w2d, kpad=None, fmt=ops.FMT_B3):
-            return ops.split_planes(w2d.contiguous(), kpad, fmt=fmt, weight=fmt == ops.FMT_H8)
-
-        def scalar(k):
-            return float(sd[k].item())
-
-        # --- ViT
-        pk["pe_w"] = planes(sd["patch_embed.proj.weight"].reshape(D, -1))  # K order (c,kh,kw)
-        pk["pe_b"] = sd["patch_embed.proj.bias"].contiguous()
-        pk["blocks"] = []
-        # Head widths that are not a multiple of the 32-wide MFMA k-block (ViT-H: 1280 / 16 = 80) run ZERO-PADDED per head
-        # (80 -> 96): the qkv projection gets zero rows (and zero bias) for the pad channels, the output projection zero
-        # columns, the rel-pos tables zero columns.  q.k, the rel-pos terms and the proj output are unchanged -- every added
-        # term is an exact zero -- and the softmax scale stays head_dim^-0.5 of the true width.
-        heads_ = cfg["num_heads"]
-        hd_true = D // heads_
-        hd_ = ops.pad32(hd_true)
-        Da = heads_ * hd_            # attention width (= D unless padded)
-        self._hd_true, self._hd_pad = hd_true, hd_
-
-        def pad_head_rows(w, groups):   # [groups*heads*hd_true, ...] -> [groups*heads*hd_, ...]
-            if hd_ == hd_true:
-                return w.contiguous()
-            v = w.reshape(groups, heads_, hd_true, *w.shape[1:])
-            out = v.new_zeros(groups, heads_, hd_, *w.shape[1:])
-            out[:, :, :hd_true] = v
-            return out.reshape(groups * heads_ * hd_, *w.shape[1:]).contiguous()
-
-        def pad_cols(t):                # [L, hd_true] -> [L, hd_]
-            if hd_ == hd_true:
-                return t
-            out = t.new_zeros(t.shape[0], hd_)
-            out[:, :hd_true] = t
-            return out
-
-        # operand format of the ViT-block GEMMs: h8 needs every contraction length (D, attention width, MLP hidden) % 64 == 0
-        hidden_ = sd["blocks.0.mlp.lin1.weight"].shape[0]
-        # ... as h8c planes (3 bytes per element, csrc/gemm_h8c.hip: a shorter operand stream and balanced matrix phases) where every contraction of
-        # the block is at least 512 deep (few k-tile pairs per output tile leave that kernel's straight-line loop nothing to run), h8 line planes otherwise
-        vfmt = self._pair_fmt()   # the hi/lo pair format of the ViT blocks (h8 off, or a block moved off fp16 attention): fp16 hi/lo pairs, like the attention kernels' own (bf16 pairs in the wide-range state)
-        if "vit" in h8_sites and D % 64 == 0 and Da % 64 == 0 and hidden_ % 64 == 0:
-            vfmt = ops.FMT_H8C if (min(D, Da, hidden_) >= 512 and self._h8c_wanted()) else ops.FMT_H8
-        pk["fp8_weights"] = self._fp8_wanted()
-        if pk["fp8_weights"]:
-            self._fp8_check(D, Da, hidden_)
-            if vfmt == ops.FMT_H8C:
-                vfmt = ops.FMT_W8   # (the wide-range state keeps its bf16 pairs, with the same effective weights)
-        pk["vit_fmt"] = vfmt
-        # LayerNorm fold (IE:396-421; LAB_NOTES.md 4.2): norm1 / norm2 of the ViT blocks live in their consumer GEMMs.  The producer of the
-        # residual stream (proj, lin2, the injector's output projection) also writes the stream as planes and per-row strip sums; qkv / lin1
-        # run on W o w and compute rstd * (x W'^T - mean * colsum(W')) + (W b + bias) in their epilogue.  tools/lnfold_study.py: same error as
-        # LayerNorm + GEMM on the seeded weights, + 1.5e-5 at |mean| = 4.5 std.  Needs whole 128-column tiles and 64-column strips.
-        fold = self._fold_ln_wanted(hidden_)
-        pk["fold_ln"] = fold
-
-        for i in range(cfg["depth"]):
-            b = f"blocks.{i}."
-            qkv_bias = pad_head_rows(sd[b + "attn.qkv.bias"], 3)
-            pk["blocks"].append(dict(
-                n1w=sd[b + "norm1.weight"], n1b=sd[b + "norm1.bias"], n2w=sd[b + "norm2.weight"], n2b=sd[b + "norm2.bias"],
-                qkv_b=qkv_bias,
-                # k = v of pad tokens; with the fp16 P V of the attention kernels (the "attnv" site, a default; `h8_sites` without it: fp16 hi/lo pairs) the v third
-                # of the qkv planes -- these bias rows and the qkv GEMM's output -- is h8-encoded (ops.Planes.split)
-                qkv_bp=(ops.split_planes_qkv(qkv_bias.reshape(1, -1).contiguous(), Da) if ("attnv" in h8_sites and Da % 32 == 0)
-                        else ops.split_planes(qkv_bias.reshape(1, -1).contiguous(), kpad=3 * Da, fmt=ops.FMT_F3)),
-                # ... and for the kernels with the rel-pos terms fused (head_dim 64) the whole row, the qkv GEMM's whole output and the
-                # rel-pos tables are h8 planes: every contraction of those kernels runs on the fp16 hi parts (v_fmt = 2)
-                qkv_bp16=(ops.split_planes(qkv_bias.reshape(1, -1).contiguous(), kpad=3 * Da, fmt=ops.FMT_H8) if "attnv" in h8_sites else None),
-                # ... and plain bf16 hi/lo planes for a block whose logit range rules fp16 operands out (attention_precision, _attn_mode)
-                qkv_bp_b3=ops.split_planes(qkv_bias.reshape(1, -1).contiguous(), kpad=3 * Da, fmt=ops.FMT_F3),
-                proj_b=sd[b + "attn.proj.bias"], lin1_b=sd[b + "mlp.lin1.bias"], lin2_b=sd[b + "mlp.lin2.bias"],
-                rph=pad_cols(sd[b + "attn.rel_pos_h"]), rpw=pad_cols(sd[b + "attn.rel_pos_w"]),
-                ws=0 if i in cfg["global_attn_indexes"] else cfg["window_size"], index=i))
-            pk["blocks"][-1].update(self._block_gemm_planes(sd, i, vfmt, fold, dev))
-        for blk in pk["blocks"]:   # windowed blocks with head_dim 64: rel-pos tables packed for the fused window kernel
-            wsz = blk["ws"]
-            if wsz and wsz <= 14 and hd_ == 64:
-                L = 2 * wsz - 1
-                th = blk["rph"] if blk["rph"].shape[0] == L else _linear_resize_rows(blk["rph"], L)
-                tw = blk["rpw"] if blk["rpw"].shape[0] == L else _linear_resize_rows(blk["rpw"], L)
-                blk["relp"] = ops.window_relpos_planes(th, tw, wsz, fmt=ops.FMT_F3)
-                blk["relp16"] = ops.window_relpos_planes(th, tw, wsz, fmt=ops.FMT_H8) if blk["qkv_bp16"] is not None else None
-        # --- TwinConvNeXt
-        cnx_f16 = self._cnx_f16_wanted()
-
-        def cfmt(w2d, pw=0):   # "cnx" in h8_sites (NOT a default: the 36-block chain is the error-sensitive part of the path, LAB_NOTES.md section 2):
-            # h8 operands for the pointwise convs whose two contraction lengths (C and 4C) are multiples of 64 and that do not run on the fused stage-0 kernel
-            # ("cnx2": stage 2 alone -- the selective variant of tools/cnx_h8_study.py, measured and left off: LAB_NOTES.md section 4.2)
-            c_ = min(w2d.shape)
-            on = "cnx" in h8_sites or ("cnx2" in h8_sites and c_ == self.channels[2])
-            if on and c_ % 64 == 0 and not ops.convnext_mlp_fused_supported(c_):
-                return ops.FMT_H8
-            # "cnx2p2" (round 6, VERDICT r05 item 5; NOT a default): pointwise_conv2 of stage 2 alone (K = 4C = 1536: 12 k-tile pairs, the h8c kernel's regime) on
-            # h8c planes -- two matrix units per product instead of three; pointwise_conv1 stays on f3 and writes its GELU output as h8c planes.
-            # tools/cnx_precision_trade.py + profiles/r06_cnx_precision_trade.txt: f3 / f4 error x 2 / x 3.5 at ViT-B on the oracle for the step time measured there
-            if "cnx2p2" in h8_sites and pw == 2 and c_ == self.channels[2] and (4 * c_) % 64 == 0 and 4 * c_ >= 512 and self._h8c_wanted():
-                return ops.FMT_H8C
-            # default (round 4): fp16 hi/lo pairs ("f3": 22 significant bits, the same three MFMAs per product as bf16 hi/lo) for the whole
-            # chain (stem, downsample and pointwise convs) -- its operand rounding is what GFFM amplifies (LAB_NOTES.md section 2, tools/f3_study.py)
-            return ops.FMT_F3 if cnx_f16 else ops.FMT_B3
-        # ConvNeXt LayerNorm fold (round 3): OPT-IN (`model.fold_convnext_ln = True`).  Built, tested, and measured at
-        # ViT-L 1024^2: step -0.17 ms, golden probes 2.9e-4 -> 4.6e-4 (the chain's error is amplified ~15 x by GFFM, LAB_NOTES.md sections 2 and 4.2):
-        # not worth the margin.  Applies to the stages that run pointwise_conv1 as a GEMM (not the fused stage-0 pair), 64-channel chunks.
-        want_cnx = bool(getattr(self, "fold_convnext_ln", False))
-        pk["cnx_f16"] = cnx_f16
-
-        def fold_cnx(c_):
-            return want_cnx and c_ % 64 == 0 and (4 * c_) % 128 == 0 and not ops.convnext_mlp_fused_supported(c_)
-        pk["fold_cnx_ln"] = want_cnx
-        t = "spm.twin_conv."
-        pk["twin"] = {}
-        for s in ("x", "y"):
-            d = t + f"downsample_layers_{s}."
-            st = dict(stem=planes(sd[d + "0.0.weight"].reshape(self.channels[0], -1), fmt=ops.FMT_F3 if cnx_f16 else ops.FMT_B3), stem_b=sd[d + "0.0.bias"],
-                      stem_nw=sd[d + "0.1.weight"], stem_nb=sd[d + "0.1.bias"], ds=[], stages=[], out_norm=[])
-            for i in range(1, 4):
-                w = sd[d + f"{i}.1.weight"]  # [Cout, Cin, 2, 2] -> K order (kh, kw, cin)
-                st["ds"].append(dict(nw=sd[d + f"{i}.0.weight"], nb=sd[d + f"{i}.0.bias"],
-                                     w=planes(w.permute(0, 2, 3, 1).reshape(w.shape[0], -1), fmt=ops.FMT_F3 if cnx_f16 else ops.FMT_B3),
-                                     b=sd[d + f"{i}.1.bias"]))
-            for i in range(4):
-                blks = []
-                for j in range(self.depths[i]):
-                    b = t + f"stages_{s}.{i}.{j}."
-                    dw = sd[b + "depthwise_conv.weight"]  # [C,1,7,7] -> tap-major [49, C]
-                    blk = dict(dw=dw.reshape(dw.shape[0], 49).t().contiguous(), dw_b=sd[b + "depthwise_conv.bias"],
-                               nw=sd[b + "norm.weight"], nb=sd[b + "norm.bias"],
-                               pw1=planes(sd[b + "pointwise_conv1.weight"], fmt=cfmt(sd[b + "pointwise_conv1.weight"])), pw1_b=sd[b + "pointwise_conv1.bias"],
-                               pw2=planes(sd[b + "pointwise_conv2.weight"], fmt=cfmt(sd[b + "pointwise_conv2.weight"], 2)), pw2_b=sd[b + "pointwise_conv2.bias"],
-                               gamma=sd[b + "gamma"])
-                    if fold_cnx(self.channels[i]):
-                        # the block's LayerNorm (TC:103-106) folded into pointwise_conv1: W o w as planes, their column sums as the kernel
-                        # reads them, W b + bias (the depthwise conv writes the RAW planes + strip sums, _spm)
-                        w1 = sd[b + "pointwise_conv1.weight"]
-                        pl = planes(w1 * sd[b + "norm.weight"][None, :], fmt=cfmt(w1))
-                        blk["pw1f"] = pl
-                        blk["pw1_cs"] = ops.planes_to_float(pl, cols=w1.shape[1])[: w1.shape[0]].double().sum(1).float().contiguous()
-                        blk["pw1_bf"] = (w1.double() @ sd[b + "norm.bias"].double()).float().add_(sd[b + "pointwise_conv1.bias"]).contiguous()
-                    blks.append(blk)
-                st["stages"].append(blks)
-                st["out_norm"].append((sd[t + f"norm_{s}{i}.weight"], sd[t + f"norm_{s}{i}.bias"]))
-            pk["twin"][s] = st
-        # both streams stacked along a leading batch dimension: the two ConvNeXt chains run as ONE chain of batched kernels
-        # (per-batch weights), see _twin_batched
-        def stack2(fx, fy):
-            if isinstance(fx, ops.Planes):
-                buf = torch.cat([fx.p, fy.p], 0).contiguous()
-                pl = ops.Planes(buf[:fx.p.shape[0]], fx.n, fx.k, fx.kpad, fx.fmt, fx.weight)    # (h8c planes hold row PAIRS: n / 2 tensor rows)
-                pl.full = buf           # keeps the second batch alive; batch stride = Planes.batch_stride(n)
-                return pl
-            return torch.stack([fx, fy], 0).contiguous()
-
-        def merge(ax, ay):
-            if isinstance(ax, dict):
-                return {k: merge(ax[k], ay[k]) for k in ax}
-            if isinstance(ax, (list, tuple)):
-                return [merge(u, v) for u, v in zip(ax, ay)]
-            return stack2(ax, ay)
-        pk["twin2"] = merge(pk["twin"]["x"], pk["twin"]["y"])
-        del pk["twin"]     # only the stacked form is used by the forward (and written by checkpoint.save_packed)
-        # --- fusion neck
-        f = "spm.smart_fusion."
-        pk["neck"] = []
-        for i in range(4):
-            C = 2 * self.channels[i]
-            c = self.channels[i]
-            lv = dict(gfe=[], loc=[])
-            for m in ("rgb", "sne"):
-                b = f + f"global_feature_encoder_{m}.{i}."
-                q1 = sd[b + "attn.qkv1.weight"]  # [3c, c/32, 1, 1], groups 32 -> [G][tap][ci][co]
-                q2 = sd[b + "attn.qkv2.weight"]  # [3c, 3c/32, 3, 3]
-                G = 32
-                co1, ci1 = 3 * c // G, c // G
-                co2, ci2 = 3 * c // G, 3 * c // G
-                lv["gfe"].append(dict(
-                    nw=sd[b + "norm1.body.weight"], nb=sd[b + "norm1.body.bias"],
-                    q1=q1.reshape(G, co1, ci1, 1).permute(0, 3, 2, 1).contiguous(),
-                    q2=q2.reshape(G, co2, ci2, 9).permute(0, 3, 2, 1).contiguous(),
-                    temp=sd[b + "attn.scale"].reshape(8).contiguous(), scale2=scalar(b + "attn.scale2"),
-                    proj=sd[b + "attn.proj.weight"].reshape(c, c).contiguous()))
-                q12 = fold_gfe_qkv(q1, q2, sd.get(b + "attn.qkv1.bias"), G)   # (q1 / q2 stay: shapes the fused kernel does not cover, fuse_gfe_qkv = False)
-                if q12 is not None:
-                    lv["gfe"][-1]["q12"] = q12
-                b = f + f"local_feature_encoder_{m}.{i}."
-                dw = sd[b + "bottleneckBlock.2.weight"]
-                lv["loc"].append(dict(
-                    w1=planes(sd[b + "bottleneckBlock.0.weight"].reshape(2 * c, c)),
-                    dw=dw.reshape(2 * c, 9).t().contiguous(),
-                    w3=planes(sd[b + "bottleneckBlock.4.weight"].reshape(c, 2 * c)), scale=scalar(b + "scale")))
-            b = f + f"fuse_blocks.{i}."
-            lv["gx"], lv["gy"] = scalar(b + "gammax.scale"), scalar(b + "gammay.scale")
-            lv["lnw"], lv["lnb"] = sd[b + "norm.weight"].contiguous(), sd[b + "norm.bias"].contiguous()
-            lv["lnw_mean"], lv["lnb_mean"] = float(lv["lnw"].double().mean().item()), float(lv["lnb"].double().mean().item())
-            b = f + f"enhance_blocks.{i}.conv_atten."
-            lv["ffrm_w"] = sd[b + "conv.weight"].reshape(C, C).contiguous()
-            lv["gn_w"], lv["gn_b"] = sd[b + "gn.weight"], sd[b + "gn.bias"]
-            b = f + f"detail_feature_extractions.{i}."
-            dw = sd[b + "dwconv.weight"]  # [2C, 2, 3, 3], groups=C -> [G=C][tap][ci=2][co=2]
-            lv["mlp_in"] = planes(sd[b + "project_in.weight"].reshape(2 * C, C))
-            lv["mlp_dw"] = dw.reshape(C, 2, 2, 9).permute(3, 0, 2, 1).contiguous()   # tap-major [9][g][ci][co]
-            lv["mlp_out"] = planes(sd[b + "project_out.weight"].reshape(C, C))
-            lv["s1"], lv["s2"] = scalar(f + f"scale_layers.{i}.scale1"), scalar(f + f"scale_layers.{i}.scale2")
-            b = f + f"ca_blocks.{i}.coord_atten."
-            mip = max(8, C // 32)
-            inv = sd[b + "bn1.weight"] / torch.sqrt(sd[b + "bn1.running_var"] + 1e-5)  # BN(eval) folded into conv1
-            w1 = sd[b + "conv1.weight"].reshape(mip, C) * inv[:, None]
-            b1 = (sd[b + "conv1.bias"] - sd[b + "bn1.running_mean"]) * inv + sd[b + "bn1.bias"]
-            lv["mip"], lv["mip_pad"] = mip, ops.pad32(mip)
-            lv["ca1"], lv["ca1_b"] = planes(w1), b1.contiguous()
-            lv["cah"], lv["cah_b"] = planes(sd[b + "conv_h.weight"].reshape(C, mip)), sd[b + "conv_h.bias"]
-            lv["caw"], lv["caw_b"] = planes(sd[b + "conv_w.weight"].reshape(C, mip)), sd[b + "conv_w.bias"]
-            lv["fc"] = planes(sd[f"spm.fc{i+1}.weight"].reshape(D, C))
-            fb = sd[f"spm.fc{i+1}.bias"]
-            lv["fc_b"] = (fb + sd["level_embed"][i - 1]).contiguous() if i >= 1 else fb.contiguous()  # BK:149-156 folded
-            pk["neck"].append(lv)
-        # --- interactions
-        M, Pn = cfg["deform_num_heads"], cfg["n_points"]
-
-        inter_pairs = self._inter_pair_set()
-        cur_inter = [None]      # index of the interaction being packed (pack_msda / pack_extractor are called inside the loop below)
-
-        def ifmt(w2d, site="inter", h8c_ok=True):   # operand format of one GEMM of a site group: h8c / h8 when selected and the contraction length allows it
-            kk = ops.pad32(w2d.shape[1])
-            if site == "inter" and cur_inter[0] in inter_pairs and site in h8_sites:
-                return self._pair_fmt()             # this interaction follows its blocks onto hi/lo pairs (inter_follow_blocks)
-            if site not in h8_sites or kk % 64:
-                return ops.FMT_B3
-            return ops.FMT_H8C if (h8c_ok and kk >= 512 and self._h8c_wanted()) else ops.FMT_H8
-
-        def iplanes(w2d, site="inter", h8c_ok=True):
-            return planes(w2d, fmt=ifmt(w2d, site, h8c_ok))
-
-        # Injector i normalises the adapter tokens c with its feat_norm, extractor i normalises the SAME c (the injector only
-        # updates x) with its query_norm: two LayerNorm passes over the largest token matrix of the path (Nc = 21504 rows per
-        # image).  LN(c; w, b) W^T + bias = chat (W * w)^T + (W b + bias) with chat = (c - mean) * rstd, so the affine parts are folded
-        # into the two projections' weights here and ONE pass computes chat for both (`share_c_norm = False` keeps two).
-        share_c = bool(getattr(self, "share_c_norm", True))
-        pk["share_c_norm"] = share_c
-        pk["ln_one"], pk["ln_zero"] = torch.ones(D, device=dev), torch.zeros(D, device=dev)
-
-        def fold_ln(w2d, bias, lnw, lnb):      # -> weight and bias of the projection applied to the un-affine normalised tokens
-            return (w2d * lnw[None, :]).contiguous(), (bias + w2d @ lnb).contiguous()
-
-        # Round 5: the adapter tokens' LayerNorms inside their consumer GEMMs (`fold_adapter_ln`; the ViT blocks' fold of round 3 applied to AM:490-511,525-542).
-        # Every LayerNorm over c -- the shared injector feat_norm / extractor query_norm, the extra extractors' query_norm, every ffn_norm -- follows a GEMM that
-        # has just written c (ConvFFN fc2, the extractor's output projection).  That producer also writes c's RAW operand planes and per-row strip sums;
-        # mmsa_rowstats_finalize turns them into (mean, rstd); the consumers (value / offsets projections, fc1) run on W o w with the row-normalising epilogue.
-        # Twelve passes over the largest token matrix of the path (21504 x 1024 per image: 88 MB read + 66 MB planes written each) go away.  Needs the affine
-        # parts folded into the weights (share_c_norm) and whole 128-column tiles at every consumer; tools/lnfold_adapter_study.py: no measurable error.
-        def colsum(pl):   # column sums of packed planes as the kernel reads them (what every x_k is actually multiplied with)
-            return ops.planes_to_float(pl, cols=pl.k)[: pl.n].double().sum(1).float().contiguous()
-        hid_c = int(D * cfg["cffn_ratio"]) if cfg["with_cffn"] else 128
-        # OPT-IN (`model.fold_adapter_ln = True`): built, pinned against the oracle (tests/test_backbone_gpu.py::test_adapter_layernorm_fold_against_the_oracle), and
-        # measured step-NEUTRAL at ViT-L 1024^2 (profiles/r05_adapter_ln_fold.txt: 31.12 / 31.39 ms without, 31.41 / 31.34 ms with; golden probes 0.94e-4 ->
-        # 1.15e-4): the eleven passes it deletes cost what the producers' extra plane + strip-sum stores and the consumers' row loads cost -- by bytes the fold
-        # saves only the read of c (176 MB per pass at batch 2), 0.3 ms at best.
-        fold_rn = self._fold_adapter_ln_wanted()
-        pk["fold_adapter_ln"] = fold_rn
-
-        def pack_msda(b, fold_val=None, fold_oa=None):
-            w = torch.cat([sd[b + "sampling_offsets.weight"], sd[b + "attention_weights.weight"]], 0)
-            bb = torch.cat([sd[b + "sampling_offsets.bias"], sd[b + "attention_weights.bias"]], 0)
-            wv, bv_ = sd[b + "value_proj.weight"], sd[b + "value_proj.bias"]
-            if fold_oa is not None:
-                w, bb = fold_ln(w, bb, *fold_oa)
-            if fold_val is not None:
-                wv, bv_ = fold_ln(wv, bv_, *fold_val)
-            # the offsets + attention-weights projection has 3 * heads * levels * points output columns (192 / 576 at ViT-L): padded with zero rows to whole
-            # 128-column GEMM tiles -- the same number of tiles, none of them ragged, so that every tile of the launch takes the register-resident epilogue
-            # (a launch that runs both epilogues no longer fits the instruction cache: profiles/r05_epilogue_regs.txt).  The deformable-attention kernel
-            # reads the first 3 * heads * levels * points columns of a row (ldraw = the padded width).
-            n_oa = w.shape[0]
-            if n_oa % 128:
-                npad = 128 - n_oa % 128
-                w = torch.cat([w, w.new_zeros(npad, w.shape[1])], 0)
-                bb = torch.cat([bb, bb.new_zeros(npad)], 0)
-            mp = dict(oa=iplanes(w), oa_b=bb.contiguous(), val=iplanes(wv), val_b=bv_,
-                      out=iplanes(sd[b + "output_proj.weight"]), out_b=sd[b + "output_proj.bias"])
-            if fold_rn:
-                if fold_oa is not None:
-                    mp["oa_cs"] = colsum(mp["oa"])
-                if fold_val is not None:
-                    mp["val_cs"] = colsum(mp["val"])
-            return mp
-
-        def pack_extractor(b, fold_c=False):
-            ep = dict(qnw=sd[b + "query_norm.weight"], qnb=sd[b + "query_norm.bias"], fnw=sd[b + "feat_norm.weight"],
-                      fnb=sd[b + "feat_norm.bias"], fold_c=fold_c, first=False, cffn=self.cfg["with_cffn"],
-                      attn=pack_msda(b + "attn.", fold_oa=(sd[b + "query_norm.weight"], sd[b + "query_norm.bias"]) if fold_c else None))
-            if self.cfg["with_cffn"]:   # AM:485-488, 499-500
-                dw = sd[b + "ffn.dwconv.dwconv.weight"]
-                fc1_w, fc1_bias = sd[b + "ffn.fc1.weight"], sd[b + "ffn.fc1.bias"]
-                if fold_c:   # ffn_norm folded into fc1 (its input is then the un-affine normalised c, or raw c + the row-normalising epilogue)
-                    fc1_w, fc1_bias = fold_ln(fc1_w, fc1_bias, sd[b + "ffn_norm.weight"], sd[b + "ffn_norm.bias"])
-                ep.update(fc1=iplanes(fc1_w), fc1_b=fc1_bias,
-                          dw=dw.reshape(dw.shape[0], 9).t().contiguous(), dw_b=sd[b + "ffn.dwconv.dwconv.bias"],
-                          # fc2's A operand is written by the 3 x 3 depthwise conv (mmsa_dwconv_nhwc), which emits bf16 hi/lo and h8 LINE planes only:
-                          # a hidden width >= 512 (cffn_ratio 0.5 at embed_dim 1024; the reference's configs stay <= 320) must not pick h8c here (ADVICE r04)
-                          fc2=iplanes(sd[b + "ffn.fc2.weight"], h8c_ok=False), fc2_b=sd[b + "ffn.fc2.bias"],
-                          ffw=sd[b + "ffn_norm.weight"], ffb=sd[b + "ffn_norm.bias"])
-                if fold_rn and fold_c:
-                    ep["fc1_cs"] = colsum(ep["fc1"])
-            return ep
-
-        pk["inter"] = []
-        n_int = len(self.interaction_indexes)
-        for i in range(n_int):
-            b = f"interactions.{i}."
-            cur_inter[0] = i
-            it = dict(inj=dict(gamma=sd[b + "injector.gamma"], qnw=sd[b + "injector.query_norm.weight"],
-                               qnb=sd[b + "injector.query_norm.bias"], fnw=sd[b + "injector.feat_norm.weight"],
-                               fnb=sd[b + "injector.feat_norm.bias"], fold_c=share_c,
-                               attn=pack_msda(b + "injector.attn.", fold_val=(sd[b + "injector.feat_norm.weight"], sd[b + "injector.feat_norm.bias"]) if share_c else None)),
-                      ext=[pack_extractor(b + "extractor.", fold_c=share_c)])
-            it["ext"][0]["first"] = True     # the extractor that shares the injector's un-affine normalised c (share_c_norm) when nothing is folded further
-            if i == n_int - 1 and self.cfg["use_extra_extractor"]:   # BK:91-92
-                it["ext"] += [pack_extractor(b + "extra_extractors.0.", fold_c=share_c), pack_extractor(b + "extra_extractors.1.", fold_c=share_c)]
-            it["inj"]["first_block"] = self.interaction_indexes[i][0]   # whose qkv GEMM reads the stream planes the injector writes (LayerNorm fold)
-            pk["inter"].append(it)
-        cur_inter[0] = None
-        # --- tail: ConvTranspose2d(D,D,2,2) weight [Cin, Cout, 2, 2] -> rows (i,j,co), K = ci  (BK:55,324)
-        up = sd["up.weight"]
-        pk["up"] = iplanes(up.permute(2, 3, 1, 0).reshape(4 * D, D), "up")
-        pk["up_b"] = sd["up.bias"].repeat(4).contiguous()
-        pk["bn"] = []
-        for i in range(1, 5):
-            inv = sd[f"norm{i}.weight"] / torch.sqrt(sd[f"norm{i}.running_var"] + 1e-5)
-            pk["bn"].append((inv.contiguous(), (sd[f"norm{i}.bias"] - sd[f"norm{i}.running_mean"] * inv).contiguous()))
-        pk["pos_src"] = sd["pos_embed"]
-        pk["geom"] = {}
-        torch.cuda.synchronize(dev)
-        return pk
+    _hd_true = property(lambda self: self.cfg["embed_dim"] // self.cfg["num_heads"])
+    _hd_pad = property(lambda self: ops.pad32(self._hd_true))   # head width the kernels see: zero-padded to a multiple of 32 (pack.pack_vit)
 
     # geometry-dependent, input-independent tables (cached per (H, W))
     @torch.no_grad()
@@ -859,10 +367,8 @@ class SAMAdapterbimodalMixModNewInTwinConvNEW(nn.Module):
             raise RuntimeError("mmsa: img_size must be a multiple of 32")
         dev = x.device
         x = x.contiguous().float()
-        if (self._packed is None or self._packed.get("dev") != dev or tuple(self._packed.get("h8_sites", ())) != self._h8_sites()
-                or self._packed.get("h8c") != self._h8c_wanted() or self._packed.get("cnx_f16") != self._cnx_f16_wanted()
-                or bool(self._packed.get("wide", False)) != self._wide() or list(self._packed.get("inter_pairs", [])) != sorted(self._inter_pair_set())
-                or bool(self._packed.get("fp8_weights", False)) != self._fp8_wanted()):
+        if self._packed is None or self._packed.get("dev") != dev or pack.packed_settings(self._packed) != PackPlan.of(self).settings():
+            # (no pack yet, another device, or a pack-time setting / sticky state that is no longer the one the pack was made with)
             self._packed = self._pack(dev)
             self._packed["dev"] = dev
         if self._ws is None or self._ws.device != dev:
@@ -1186,7 +692,8 @@ class SAMAdapterbimodalMixModNewInTwinConvNEW(nn.Module):
                                        "entry beyond +-65504)." if self._wide() else "`range_fallback = True` (the default) re-routes instead of refusing."))
         auto = self._attn_policy() == "auto"
         moved = []
-        sd_dev = None     # the float parameters on the device, built once for all the blocks that move in this call
+        dev, plan = pk["attn_guard"].device, PackPlan.of(self)
+        sd_dev = functools.lru_cache(None)(lambda: pack.float_state_dict(self, dev))   # the float parameters on the device, built once for all the blocks that move in this call
         for bp, v in zip(pk["blocks"], vals):
             bp["max_logit"] = max(float(v), bp.get("max_logit", 0.0))
             if not auto or bp["qkv_bp16"] is None:
@@ -1194,21 +701,17 @@ class SAMAdapterbimodalMixModNewInTwinConvNEW(nn.Module):
             if bp.get("amode") != "b3" and bp["max_logit"] > self.ATTN_F16_MAX_LOGIT:
                 moved.append(bp["index"])
                 if reroute:
+                    # the projections around those logits must not lose them either: q and k from 2^-15.6 products turn a logit of 48 into
+                    # an error of ~1e-3 before the exponential, and what proj / lin1 / lin2 lose reaches the NEXT block's q and k.  The
+                    # whole block moves to hi/lo PAIR operands -- fp16 pairs since round 4 (f3 planes, 2^-22 per product; bf16 pairs before:
+                    # 2^-17, a floor of 2^-17 x the logit) --, repacked here from the state dict.
                     bp["amode"] = "b3"
-                    if bp["qkv"].fmt != self._pair_fmt():
-                        # the projections around those logits must not lose them either: q and k from 2^-15.6 products turn a logit of 48 into
-                        # an error of ~1e-3 before the exponential, and what proj / lin1 / lin2 lose reaches the NEXT block's q and k.  The
-                        # whole block moves to hi/lo PAIR operands -- fp16 pairs since round 4 (f3 planes, 2^-22 per product; bf16 pairs before:
-                        # 2^-17, a floor of 2^-17 x the logit) --, repacked here from the state dict.
-                        dev = pk["attn_guard"].device
-                        if sd_dev is None:
-                            sd_dev = self._pack_state_dict(dev)
-                        bp.update(self._block_gemm_planes(sd_dev, bp["index"], self._pair_fmt(), pk["fold_ln"], dev))
+                    pack.repack_block_on_pairs(pk, bp, sd_dev, plan, dev)
             elif bp.get("amode") is None:
                 bp["amode"] = "f16"
         if moved and reroute and auto and self.inter_follow_blocks and "inter" in self._h8_sites():
-            # the interactions of the moved blocks follow them onto pairs: their GEMM planes are packed inside _pack_impl's closures, so the pack is
-            # dropped (the blocks' settled modes carry over) and the next forward -- forward() runs it at once, a graph owner's capture does -- packs again
+            # the interactions of the moved blocks follow them onto pairs: the pack is dropped (the blocks' settled modes carry over) and the next forward --
+            # forward() runs it at once, a graph owner's capture does -- packs again, the interactions' planes included
             want = self._inter_pair_set() | {i for i in (self._interaction_of_block(b) for b in moved) if i is not None}
             if want != self._inter_pair_set():
                 self._inter_pairs = want
@@ -1621,18 +1124,6 @@ def rel_pos_index(q_size, k_size):
     q = torch.arange(q_size)[:, None] * max(k_size / q_size, 1.0)
     k = torch.arange(k_size)[None, :] * max(q_size / k_size, 1.0)
     return ((q - k) + (k_size - 1) * max(q_size / k_size, 1.0)).long()
-
-
-def _linear_resize_rows(tab, L):
-    """F.interpolate(mode='linear', align_corners=False) along dim 0 of a [Lin, C] table (IE:568-575)."""
-    Lin = tab.shape[0]
-    scale = Lin / L
-    pos = (torch.arange(L, dtype=torch.float32, device=tab.device) + 0.5) * scale - 0.5
-    pos = pos.clamp(min=0)
-    i0 = pos.floor().long().clamp(max=Lin - 1)
-    i1 = (i0 + 1).clamp(max=Lin - 1)
-    lam = (pos - i0.float()).unsqueeze(1)
-    return tab[i0] * (1 - lam) + tab[i1] * lam
 
 
 def _rel_table(size, rel_pos):

@@ -11,15 +11,16 @@
 
 Pinned by tests/test_host_cpu.py against tests/golden/sam_ckpt.npz, which the reference's own loader and converter produced on
 seeded checkpoints (tools/oracle/make_golden.py::gen_sam_ckpt)."""
+import functools
 import hashlib
 import os
 import warnings
 
 import torch
 
-from . import ops
+from . import ops, pack
 
-PACK_FORMAT = 12   # 12: the neck's GFE dicts carry `q12`, the qkv1 and qkv2 weights folded into one grouped 3x3 conv (backbone.fold_gfe_qkv); 11 (round 6): extractor dicts carry `first`, fc1 of every shared-norm extractor the folded ffn_norm, attn_guard has depth + 1 words (the clamp watch), the offsets / attention-weights projection is padded to 128 columns, settings carry fold_adapter_ln and the wide-range state, the pack its `weights_clamped` flag; 10: the attention path's hi/lo planes (bias rows, rel-pos tables, fallback block weights) are fp16 pairs; 9: the ConvNeXt planes' format (fp16 hi/lo pairs) among the settings; 8: byte-exact digests (sha1) instead of floating-point sums; the blocks' attention modes / largest logits travel with the planes; 7: ConvNeXt LayerNorm fold (pw1f / pw1_cs / pw1_bf, setting fold_cnx_ln); 6: plane checksum + pack-time settings in the header, both attention table formats (relp / relp16, qkv_bp_b3); 3: planes carry their operand format (bf16 hi/lo or h8); 4: LayerNorm affine parts folded into the adapter projections (share_c_norm); 5: planes carry `split` (qkv bias rows: v columns as h8 planes)
+PACK_FORMAT = 12   # 12: the neck's GFE dicts carry `q12`, the qkv1 and qkv2 weights folded into one grouped 3x3 conv (pack.fold_gfe_qkv); 11 (round 6): extractor dicts carry `first`, fc1 of every shared-norm extractor the folded ffn_norm, attn_guard has depth + 1 words (the clamp watch), the offsets / attention-weights projection is padded to 128 columns, settings carry fold_adapter_ln and the wide-range state, the pack its `weights_clamped` flag; 10: the attention path's hi/lo planes (bias rows, rel-pos tables, fallback block weights) are fp16 pairs; 9: the ConvNeXt planes' format (fp16 hi/lo pairs) among the settings; 8: byte-exact digests (sha1) instead of floating-point sums; the blocks' attention modes / largest logits travel with the planes; 7: ConvNeXt LayerNorm fold (pw1f / pw1_cs / pw1_bf, setting fold_cnx_ln); 6: plane checksum + pack-time settings in the header, both attention table formats (relp / relp16, qkv_bp_b3); 3: planes carry their operand format (bf16 hi/lo or h8); 4: LayerNorm affine parts folded into the adapter projections (share_c_norm); 5: planes carry `split` (qkv bias rows: v columns as h8 planes)
 
 
 def unwrap_state_dict(ck):
@@ -163,29 +164,19 @@ def save_packed(model, path, device="cuda"):
     checksum of the packed planes, the pack-time settings the planes depend on}."""
     dev = torch.device(device)
     with torch.cuda.device(dev):
+        plan = pack.PackPlan.of(model)
         pk = model._pack(dev)
         # the per-block attention precision the model has settled on (backbone.check_attention_guard) travels with the planes: a block
         # that was moved to bf16 hi/lo operands is packed that way, and every block keeps the largest logit it has seen
         old = getattr(model, "_packed", None)
         if old is not None:
-            sd_dev = model._pack_state_dict(dev)
-            for bp, bo in zip(pk["blocks"], old["blocks"]):
-                for k in ("amode", "max_logit"):
-                    if k in bo:
-                        bp[k] = bo[k]
-                if bo.get("amode") == "b3" and bp["qkv"].fmt != model._pair_fmt():
-                    bp.update(model._block_gemm_planes(sd_dev, bp["index"], model._pair_fmt(), pk["fold_ln"], dev))
+            modes = [{k: bo[k] for k in ("amode", "max_logit") if k in bo} for bo in old["blocks"]]
+            pack.carry_block_modes(pk, modes, functools.lru_cache(None)(lambda: pack.float_state_dict(model, dev)), plan, dev)
         torch.cuda.synchronize(dev)
     sd = {k: v.detach().cpu() for k, v in model.state_dict().items()}
     enc = _enc(pk)
-    settings = {"h8_sites": list(model._h8_sites()), "h8c": bool(pk.get("h8c", False)), "share_c_norm": bool(pk.get("share_c_norm", True)), "fold_ln": bool(pk.get("fold_ln", False)),
-                "fold_cnx_ln": bool(pk.get("fold_cnx_ln", False)), "cnx_f16": bool(pk.get("cnx_f16", False)),
-                "fold_adapter_ln": bool(pk.get("fold_adapter_ln", False)), "wide": bool(pk.get("wide", False)),
-                "inter_pairs": list(pk.get("inter_pairs", []))}
-    if pk.get("fp8_weights"):   # (fp8 packs only: the ViT-block weights are W8 codes + exponents; a file without the key was packed without the switch)
-        settings["fp8_weights"] = True
     torch.save({"format": PACK_FORMAT, "cfg": model.cfg, "state_dict": sd, "packed": enc, "fingerprint": _fingerprint(sd),
-                "packed_checksum": _packed_checksum(enc), "settings": settings}, path)
+                "packed_checksum": _packed_checksum(enc), "settings": plan.settings()}, path)
 
 
 def load_packed(model, path, device="cuda"):
@@ -204,16 +195,7 @@ def load_packed(model, path, device="cuda"):
     inter_pairs = set((blob.get("settings") or {}).get("inter_pairs", []))   # interactions that followed their blocks onto pairs (backbone.inter_follow_blocks): settled state, like the blocks' modes
     model._wide_range = wide
     model._inter_pairs = inter_pairs
-    want = {"h8_sites": list(model._h8_sites()), "h8c": bool(model._h8c_wanted()),
-            "share_c_norm": bool(getattr(model, "share_c_norm", True))}
-    want["fold_ln"] = bool(model._fold_ln_wanted())
-    want["fold_cnx_ln"] = bool(getattr(model, "fold_convnext_ln", False))
-    want["cnx_f16"] = bool(model._cnx_f16_wanted())
-    want["wide"] = wide
-    want["inter_pairs"] = sorted(inter_pairs)
-    want["fold_adapter_ln"] = bool(model._fold_adapter_ln_wanted())   # (a pack-time setting that drives the run-time path: ADVICE r05)
-    if model._fp8_wanted():
-        want["fp8_weights"] = True   # (fp8 weights: a file packed without them is refused, and an fp8 file by a model without them)
+    want = pack.PackPlan.of(model).settings()   # (fp8 weights among them: a file packed without them is refused, and an fp8 file by a model without them)
     if blob.get("settings") != want:
         raise RuntimeError(f"{path}: packed with settings {blob.get('settings')}, the model runs {want}: repack")
     if blob["fingerprint"] != _fingerprint(blob["state_dict"]):
@@ -240,6 +222,4 @@ def load_packed(model, path, device="cuda"):
     pk["geom"] = {}
     pk["dev"] = dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
     model._packed = pk
-    hd = model.cfg["embed_dim"] // model.cfg["num_heads"]
-    model._hd_true, model._hd_pad = hd, ops.pad32(hd)
     return model
