@@ -345,6 +345,13 @@ int mmsa_crop_batch_nchw(const float* src, int B, int C, int H, int W, const int
  * `uncovered` (device int, zeroed by the caller) counts pixels that no window covers (ED:220). */
 int mmsa_slide_argmax(const float* logits, int n, int C, int hs, int ws, const int* windows, unsigned char* out, int B, int H, int W,
                       int hc, int wc, int* uncovered, mmsa_stream_t stream);
+/* the same class map at a RESCALED size (`rescale=True`: ED:227-233, 314-325, 349-360, 393-414): the averaged logits of the H x W frame are resized once
+ * more (bilinear, align_corners=False) to Hd x Wd -- larger or smaller, any ratio per axis, no antialiasing -- and cropped to [:Hcut, :Wcut] (Hcut <= Hd,
+ * Wcut <= Wd; ED:414) before the argmax; out [B, Hcut, Wcut].  Bit for bit the map of bilinear_accum (accumulate) + div_count + bilinear_accum (write, into
+ * [B,C,Hd,Wd]) + argmax + crop, with neither canvas in memory.  Each of an output pixel's four canvas taps divides by its own window count; a pixel with a
+ * tap that no window covers (or more than 8 do) gets 255 and is counted once in `uncovered`. */
+int mmsa_slide_argmax_resized(const float* logits, int n, int C, int hs, int ws, const int* windows, unsigned char* out, int B, int H, int W,
+                              int hc, int wc, int Hd, int Wd, int Hcut, int Wcut, int* uncovered, mmsa_stream_t stream);
 
 /* --- the input side of the test pipelines (segmentation/mmseg_custom/datasets/pipelines/transform.py): Pad_multimodal (2934-3010, impad bottom /
  *     right) -> Normalize_multimodal / Normalize_multimodal_Muses (2601-2825: `/ 255` when norm_by_max, mmcv.imnormalize = channel reversal when

@@ -7,8 +7,9 @@
  * 105: new entries mmsa_preprocess_resize_nhwc / mmsa_preprocess_resize_crops (the same from sources of another size: bilinear resize first).
  * 106: new entries mmsa_eval_confusion_u8 / mmsa_slide_argmax_eval (confusion counts of a class map against a label map, alone or fused into the class-map kernel).
  * 107: new entry mmsa_gfe_qkv_conv (the GFE's 1x1 and 3x3 qkv convs as one grouped 3x3 conv with folded weights).
- * 108: new entries mmsa_render_u8 / mmsa_render_denorm_f32 (the picture of a prediction: palette map blended over nothing, the raw frame or the de-normalised input tensor). */
+ * 108: new entries mmsa_render_u8 / mmsa_render_denorm_f32 (the picture of a prediction: palette map blended over nothing, the raw frame or the de-normalised input tensor).
+ * 109: new entry mmsa_slide_argmax_resized (the class map at a rescaled size: second bilinear resize + crop + argmax in the class-map pass). */
 #ifndef MMSA_VERSION_H
 #define MMSA_VERSION_H
-#define MMSA_ABI_VERSION 108
+#define MMSA_ABI_VERSION 109
 #endif

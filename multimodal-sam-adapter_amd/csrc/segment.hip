@@ -194,3 +194,148 @@ extern "C" int mmsa_slide_argmax_eval(const float* logits, int n, int C, int hs,
   MMSA_CHECK_LAUNCH("slide_argmax_eval");
   return MMSA_OK;
 }
+
+// ---- class map of a frame at a RESCALED size in one pass (ED:227-233, 314-325, 349-360, 393-414 + ED:449,477): what `rescale=True` adds to the
+// canvas above -- a second bilinear resize (align_corners=False) of the averaged logits to Hd x Wd, then the crop [:Hcut, :Wcut] -- before the argmax:
+//   canvas[c, y, x]  = (sum over covering windows, in window order, of bilinear(logits_k -> hc x wc)[c]) / count       (slide_pixel.inc)
+//   resized[c, Y, X] = bilinear_{align_corners=False}(canvas -> Hd x Wd)                                                (bilinear_accum_kernel, write mode)
+//   out[Y, X]        = first argmax_c resized[c, Y, X]
+// with neither the [B, C, H, W] canvas nor the [B, C, Hd, Wd] one in memory.  An output pixel reads a 2 x 2 block of canvas pixels (its four taps; on a
+// downscale the blocks of neighbouring output pixels skip canvas pixels, PyTorch's bilinear has no antialiasing); each tap is a canvas pixel of its own,
+// with its own covering windows and its own count.  Both stages are the file's formula in the file's operation order (no contraction, see the top), so
+// the map equals bilinear_accum + div_count + bilinear_accum + argmax + crop bit for bit.  A pixel with a tap that no window covers, or more than 8
+// windows, gets 255 and is counted in `uncovered`.
+// Registers: four taps with the eight slots of slide_pixel.inc would need 4 x 56 (the first form did: 372 registers, one wave per SIMD).  Here a tap
+// keeps RESIZED_SLOTS = 4 windows, each packed to four registers (offset of the top-left logit, window index | "has a row below" << 8 | "has a column
+// to the right" << 9, the two weights); a pixel with a tap under 5 .. 8 windows (strides below half the crop) takes the scanning form instead, which walks
+// the window table again for every class and keeps nothing.  Same terms, same order, same bits either way.
+#define RESIZED_SLOTS 4
+struct TapSlots { int nk; int o[RESIZED_SLOTS], kf[RESIZED_SLOTS]; float lh[RESIZED_SLOTS], lw[RESIZED_SLOTS]; };
+
+// window k of image b over canvas pixel (ty, tx)?  -> its 4-tap coordinates in the window's logits, as slide_pixel.inc computes them
+__device__ __forceinline__ bool tap_coords(const WindowTable& wt, int k, int b, int ty, int tx, int hc, int wc, int hs, int ws, float rh, float rw,
+                                           int& o, int& kf, float& lh, float& lw) {
+  if (wt.b[k] != b) return false;
+  const int i = ty - wt.y0[k], j = tx - wt.x0[k];
+  if (i < 0 || i >= hc || j < 0 || j >= wc) return false;
+  float sh = ((float)i + 0.5f) * rh - 0.5f, sw = ((float)j + 0.5f) * rw - 0.5f;
+  sh = sh < 0.f ? 0.f : sh;
+  sw = sw < 0.f ? 0.f : sw;
+  const int h0 = min((int)sh, hs - 1), w0 = min((int)sw, ws - 1);
+  o = h0 * ws + w0;
+  kf = k | (h0 < hs - 1 ? 256 : 0) | (w0 < ws - 1 ? 512 : 0);
+  lh = sh - (float)h0;
+  lw = sw - (float)w0;
+  return true;
+}
+
+// one window's term of a canvas pixel: the interpolation of bilinear_accum_kernel / slide_pixel.inc
+__device__ __forceinline__ float tap_term(const float* __restrict__ logits, int C, int c, int hs, int ws, int o, int kf, float lh, float lw) {
+  const int dh = (kf >> 8) & 1 ? ws : 0, dw = (kf >> 9) & 1;
+  const float* sp = logits + ((long)(kf & 255) * C + c) * hs * ws + o;
+  return (1.f - lh) * ((1.f - lw) * sp[0] + lw * sp[dw]) + lh * ((1.f - lw) * sp[dh] + lw * sp[dh + dw]);
+}
+
+__device__ __forceinline__ float tap_value(const TapSlots& t, const float* __restrict__ logits, int C, int c, int hs, int ws) {
+  float acc = 0.f;
+#pragma unroll
+  for (int q = 0; q < RESIZED_SLOTS; ++q) {
+    if (q < t.nk) {
+      const float v = tap_term(logits, C, c, hs, ws, t.o[q], t.kf[q], t.lh[q], t.lw[q]);
+      acc = q == 0 ? v : acc + v;     // window order: the first window WRITES (0 + v == v), later ones add
+    }
+  }
+  return acc / (float)t.nk;
+}
+
+__device__ __forceinline__ float tap_value_scan(const WindowTable& wt, int b, int ty, int tx, int nk, const float* __restrict__ logits, int C, int c,
+                                                int hs, int ws, int hc, int wc, float rh, float rw) {
+  float acc = 0.f;
+  bool first = true;
+  for (int k = 0; k < wt.n; ++k) {
+    int o, kf;
+    float lh, lw;
+    if (!tap_coords(wt, k, b, ty, tx, hc, wc, hs, ws, rh, rw, o, kf, lh, lw)) continue;
+    const float v = tap_term(logits, C, c, hs, ws, o, kf, lh, lw);
+    acc = first ? v : acc + v;
+    first = false;
+  }
+  return acc / (float)nk;
+}
+
+__global__ __launch_bounds__(256) void slide_argmax_resized_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
+                                                                   int H, int W, int hc, int wc, float rh, float rw, int Hcut, int Wcut, float rh2, float rw2,
+                                                                   WindowTable wt, int* __restrict__ uncovered) {
+  const int X = blockIdx.x * 256 + threadIdx.x, Y = blockIdx.y, b = blockIdx.z;
+  if (X >= Wcut) return;
+  // second stage: the taps of output pixel (Y, X) in the H x W canvas (bilinear_accum_kernel with src = the canvas)
+  float sh2 = ((float)Y + 0.5f) * rh2 - 0.5f, sw2 = ((float)X + 0.5f) * rw2 - 0.5f;
+  sh2 = sh2 < 0.f ? 0.f : sh2;
+  sw2 = sw2 < 0.f ? 0.f : sw2;
+  const int y0 = min((int)sh2, H - 1), x0 = min((int)sw2, W - 1);
+  const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
+  const float lh2 = sh2 - (float)y0, lw2 = sw2 - (float)x0;
+  // first stage: the covering windows of each tap (tap t: row y0 / y1 = t >> 1, column x0 / x1 = t & 1).  Slot arrays only ever indexed by unrolled constants.
+  TapSlots tp[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    tp[t].nk = 0;
+#pragma unroll
+    for (int q = 0; q < RESIZED_SLOTS; ++q) { tp[t].o[q] = tp[t].kf[q] = 0; tp[t].lh[q] = tp[t].lw[q] = 0.f; }
+  }
+  for (int k = 0; k < wt.n; ++k) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      int o, kf;
+      float lh, lw;
+      if (!tap_coords(wt, k, b, t >> 1 ? y1 : y0, t & 1 ? x1 : x0, hc, wc, hs, ws, rh, rw, o, kf, lh, lw)) continue;
+#pragma unroll
+      for (int q = 0; q < RESIZED_SLOTS; ++q)
+        if (q == tp[t].nk) { tp[t].o[q] = o; tp[t].kf[q] = kf; tp[t].lh[q] = lh; tp[t].lw[q] = lw; }
+      ++tp[t].nk;
+    }
+  }
+  const int nmin = min(min(tp[0].nk, tp[1].nk), min(tp[2].nk, tp[3].nk)), nmax = max(max(tp[0].nk, tp[1].nk), max(tp[2].nk, tp[3].nk));
+  const long op = ((long)b * Hcut + Y) * Wcut + X;
+  if (nmin == 0 || nmax > 8) {      // a tap without a window, or with more than 8: counted once per output pixel, and the pixel gets 255
+    atomicAdd(uncovered, 1);
+    out[op] = 255;
+    return;
+  }
+  float best = -INFINITY;
+  int bi = 0;
+  if (nmax <= RESIZED_SLOTS) {
+    for (int c = 0; c < C; ++c) {
+      const float p00 = tap_value(tp[0], logits, C, c, hs, ws), p01 = tap_value(tp[1], logits, C, c, hs, ws);
+      const float p10 = tap_value(tp[2], logits, C, c, hs, ws), p11 = tap_value(tp[3], logits, C, c, hs, ws);
+      const float p = (1.f - lh2) * ((1.f - lw2) * p00 + lw2 * p01) + lh2 * ((1.f - lw2) * p10 + lw2 * p11);
+      if (c == 0 || p > best) { best = p; bi = c; }
+    }
+  } else {
+    for (int c = 0; c < C; ++c) {
+      const float p00 = tap_value_scan(wt, b, y0, x0, tp[0].nk, logits, C, c, hs, ws, hc, wc, rh, rw);
+      const float p01 = tap_value_scan(wt, b, y0, x1, tp[1].nk, logits, C, c, hs, ws, hc, wc, rh, rw);
+      const float p10 = tap_value_scan(wt, b, y1, x0, tp[2].nk, logits, C, c, hs, ws, hc, wc, rh, rw);
+      const float p11 = tap_value_scan(wt, b, y1, x1, tp[3].nk, logits, C, c, hs, ws, hc, wc, rh, rw);
+      const float p = (1.f - lh2) * ((1.f - lw2) * p00 + lw2 * p01) + lh2 * ((1.f - lw2) * p10 + lw2 * p11);
+      if (c == 0 || p > best) { best = p; bi = c; }
+    }
+  }
+  out[op] = (unsigned char)bi;
+}
+
+extern "C" int mmsa_slide_argmax_resized(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out,
+                                         int B, int H, int W, int hc, int wc, int Hd, int Wd, int Hcut, int Wcut,
+                                         int* uncovered /* device int, zeroed by the caller */, hipStream_t stream) {
+  MMSA_CHECK_ARG(logits && out && uncovered && C > 0 && C <= 255 && hs > 0 && ws > 0 && hc > 0 && wc > 0 && B > 0 && H > 0 && W > 0 && B <= 65535,
+                 "slide_argmax_resized: bad args");
+  MMSA_CHECK_ARG(Hd > 0 && Wd > 0 && Hcut > 0 && Wcut > 0 && Hcut <= Hd && Wcut <= Wd && Hcut <= 65535,
+                 "slide_argmax_resized: the cut %dx%d must lie inside the target %dx%d (and have at most 65535 rows)", Hcut, Wcut, Hd, Wd);
+  WindowTable wt;
+  int rc = fill_windows(wt, windows, n, B, H, W, hc, wc, "slide_argmax_resized");
+  if (rc) return rc;
+  hipLaunchKernelGGL(slide_argmax_resized_kernel, dim3(cdiv(Wcut, 256), Hcut, B), dim3(256), 0, stream, logits, C, hs, ws, out, H, W, hc, wc,
+                     (float)hs / (float)hc, (float)ws / (float)wc, Hcut, Wcut, (float)H / (float)Hd, (float)W / (float)Wd, wt, uncovered);
+  MMSA_CHECK_LAUNCH("slide_argmax_resized");
+  return MMSA_OK;
+}

@@ -1,6 +1,8 @@
 """Inference glue of the reference's EncoderDecoder on device (segmentation/mmseg_custom/models/segmentors/encoder_decoder.py):
 `encode_decode` (ED:85-95), `slide_inference` (ED:191-234), `whole_inference`, `whole_inference_dim` (ED:329-362),
-`whole_inference_dim_cut` (ED:364-413), the mode dispatch of `inference` (ED:417-447) and the class map of `simple_test` (ED:449,477).
+`whole_inference_dim_cut` (ED:364-413), the mode dispatch of `inference` (ED:417-447) and the class map of `simple_test` (ED:449,477) -- with
+`rescale=True` (test_bs.py:241-244) at the size the reference rescales to: `ori_shape` in the slide and whole modes (ED:227-233, 314-325), `dim` in the
+`whole_dim*` modes, as logits (a second resize of the canvas) or as the class map of ONE launch that writes neither canvas (mmsa_slide_argmax_resized).
 
 The crops of a sliding-window frame are batched through ONE backbone + head call (the reference runs them one by one,
 ED:205-214), and the resize / pad / accumulate / count of every crop is one kernel launch on the logits canvas."""
@@ -84,8 +86,9 @@ def crop_boxes(h_img, w_img, crop_size, stride):
 
 @_on_device
 @torch.no_grad()
-def slide_inference(backbone, head, img, crop_size, stride, max_batch=8, preprocess=None):
-    """ED:191-234 without the optional rescale: averaged logits [B, classes, H, W] of overlapping windows.  All windows have
+def slide_inference(backbone, head, img, crop_size, stride, max_batch=8, preprocess=None, rescale=True, ori_shape=None):
+    """ED:191-234: averaged logits [B, classes, H, W] of overlapping windows; with `rescale` and an `ori_shape` (h, w[, 3]) other than the frame's they
+    are resized once more (bilinear, align_corners=False) to [B, classes, h, w] (ED:227-233).  All windows have
     the crop size here (the backbone needs H = W = img_size), i.e. the image must be at least as large as the crop.
     `preprocess=` (mmsa.preprocess.Preprocess): img is the pair (rgb, aux) of raw frames; the windows are cut AND normalised by one launch."""
     if preprocess is not None:
@@ -116,7 +119,27 @@ def slide_inference(backbone, head, img, crop_size, stride, max_batch=8, preproc
     if bool((count == 0).any()):
         raise RuntimeError("mmsa.slide_inference: windows do not cover the image")   # ED:220
     lib.call("mmsa_div_count_nchw", preds.data_ptr(), count.data_ptr(), B, preds.shape[1], H * W, ops._stream())
-    return preds
+    return _rescaled_logits(preds, _target(ori_shape, H, W, "slide_inference") if rescale else None)
+
+
+def _target(shape, H, W, what):
+    """The size a prediction of an H x W frame is rescaled to: (h, w) of `ori_shape` / `dim`, or None where that is the frame's own size (a same-size
+    align_corners=False resize is the identity) or no shape is given."""
+    if shape is None:
+        return None
+    if len(shape) < 2 or int(shape[0]) < 1 or int(shape[1]) < 1:
+        raise RuntimeError(f"mmsa.{what}: the rescale target must be (h, w[, channels]) with h, w >= 1, got {tuple(shape)}")
+    t = (int(shape[0]), int(shape[1]))
+    return None if t == (H, W) else t
+
+
+def _rescaled_logits(y, target):
+    """The second resize of ED:227-233 / 314-325 / 349-360 on the logits canvas."""
+    if target is None:
+        return y
+    out = torch.empty(y.shape[0], y.shape[1], target[0], target[1], device=y.device)
+    _resize_into(y, out, 0, 0, target[0], target[1])
+    return out
 
 
 def _crops(img, chunk, crop_size, out=None):
@@ -153,21 +176,67 @@ def _check_overlap(boxes, what):
                            "(use slide_inference + argmax_map, or a larger stride)")
 
 
-def _picture_source(render, preprocess, frame, H, W, return_map, what):
-    """The source `render=` paints over in the slide modes (None without `render=`); refusals come before any launch."""
+def _picture_source(render, preprocess, frame, H, W, return_map, what, rescaled=False):
+    """The source `render=` paints over in the slide modes (None without `render=`); refusals come before any launch.  H x W is the MAP's size; a
+    normalised frame is no source for a map rescaled to another size."""
     if render is None:
         return None
     if not return_map:
         raise RuntimeError(f"mmsa.{what}: render= paints the stored map; drop return_map=False")
     from .render import slide_source
+    if rescaled and preprocess is None:
+        raise RuntimeError(f"mmsa.{what}: render= has no source for the picture: the class map is rescaled to {H} x {W}, the normalised frame has another size "
+                           "(raw uint8 frames of the map's size, with preprocess=, are needed)")
     return slide_source(render, preprocess, frame, H, W, what)
 
 
-def _class_map(lg, n, tab, out, B, H, W, hc, wc, unc, labels, evaluator, case, fused, return_map):
+# Which launch makes a RESCALED class map by default: True = the one-pass kernel (mmsa_slide_argmax_resized), False = the canvas path
+# (_rescaled_map_canvas: the launches of slide_inference + the second resize + argmax_map, from the same head-resolution logits; the same map bit for bit).
+# Per direction of the second resize ("up": the target has more pixels than the frame).  `one_pass=` of the class-map calls overrides it.
+ONE_PASS_RESCALE_DEFAULT = dict(up=True, down=True)   # not measured yet (tools/exp/rescale_class_map_bench.py)
+
+
+def _rescaled_map_canvas(lg, n, tab, out, B, H, W, hc, wc, unc, rs):
+    """The rescaled class map the long way round, from the head-resolution logits lg [n, C, hs, ws] and the window table: canvas (accumulate, count,
+    divide), second canvas, argmax, crop -- the launches slide_inference / encode_decode + argmax_map make.  `unc` gets the number of CANVAS pixels that no
+    window covers (non-zero exactly when the one-pass kernel's count of output pixels may be)."""
+    Hd, Wd, Hcut, Wcut = rs
+    C = lg.shape[1]
+    canvas = torch.zeros(B, C, H, W, device=lg.device)
+    count = torch.zeros(B, H, W, device=lg.device)
+    for k in range(n):
+        b, y0, x0 = tab[3 * k], tab[3 * k + 1], tab[3 * k + 2]
+        _resize_into(lg[k:k + 1], canvas[b:b + 1], y0, x0, hc, wc, count=count[b:b + 1], accumulate=True)
+    unc.add_((count == 0).sum().to(torch.int32))
+    lib.call("mmsa_div_count_nchw", canvas.data_ptr(), count.data_ptr(), B, C, H * W, ops._stream())
+    full = argmax_map(_rescaled_logits(canvas, None if (Hd, Wd) == (H, W) else (Hd, Wd)))
+    out.copy_(full[:, :Hcut, :Wcut])
+
+
+def _class_map(lg, n, tab, out, B, H, W, hc, wc, unc, labels, evaluator, case, fused, return_map, rs=None, one_pass=None):
     """The class-map launch of the three class-map calls.  Without `labels`: mmsa_slide_argmax.  With `labels` (raw uint8 label maps [B, Hl, Wl]) and
     `evaluator` (mmsa.evaluate.Evaluator): the confusion counts of the map are ADDED to the evaluator's buffer as well -- by the same launch
     (mmsa_slide_argmax_eval: `fused=True`) or by a second one over the stored map (mmsa_eval_confusion_u8); `fused=None` takes mmsa.evaluate.FUSED_DEFAULT.
-    The map is the same either way; `return_map=False` with the fused launch writes none.  No host sync, no allocation."""
+    The map is the same either way; `return_map=False` with the fused launch writes none.  No host sync, no allocation.
+    `rs` = (Hd, Wd, Hcut, Wcut): the map at a rescaled size, out [B, Hcut, Wcut] -- mmsa_slide_argmax_resized, or the canvas path where
+    ONE_PASS_RESCALE_DEFAULT / `one_pass=False` say so; the counts then always go through the stored map (no fused variant at the rescaled size)."""
+    if rs is not None:
+        if (labels is None) != (evaluator is None):
+            raise RuntimeError("mmsa.inference: labels= and evaluator= come together")
+        if fused or not return_map:
+            raise RuntimeError("mmsa.inference: fused=True / return_map=False need the fused class-map + evaluation launch, and that launch has no variant at "
+                               "a rescaled or cut size: the counts of a rescaled map go through the stored map (drop fused= / return_map=)")
+        Hd, Wd, Hcut, Wcut = rs
+        if ONE_PASS_RESCALE_DEFAULT["up" if Hd * Wd > H * W else "down"] if one_pass is None else one_pass:
+            lib.call("mmsa_slide_argmax_resized", lg.data_ptr(), n, lg.shape[1], lg.shape[2], lg.shape[3], tab, out.data_ptr(), B, H, W, hc, wc,
+                     Hd, Wd, Hcut, Wcut, unc.data_ptr(), ops._stream())
+        else:
+            _rescaled_map_canvas(lg, n, tab, out, B, H, W, hc, wc, unc, rs)
+        if evaluator is not None:
+            evaluator.add(out, labels, case=case)
+        return
+    if one_pass is not None:
+        raise RuntimeError("mmsa.inference: one_pass= chooses the launch of a RESCALED class map; this map has the frame's size")
     if labels is None and evaluator is None:
         if not return_map:
             raise RuntimeError("mmsa.inference: return_map=False only makes sense with labels= and evaluator=")
@@ -190,7 +259,7 @@ def _class_map(lg, n, tab, out, B, H, W, hc, wc, unc, labels, evaluator, case, f
 @_on_device
 @torch.no_grad()
 def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preprocess=None, labels=None, evaluator=None, case=None, fused=None,
-                    return_map=True, render=None):
+                    return_map=True, render=None, ori_shape=None, one_pass=None):
     """`simple_test` of a sliding-window frame (ED:191-234 + ED:449,477) -> uint8 class map [B, H, W], without the
     [B, classes, H, W] logits canvas: every window's logits stay at head resolution and ONE kernel (mmsa_slide_argmax) resizes,
     sums the overlapping windows in window order, divides by the count and takes the argmax -- the same additions in the same order
@@ -200,7 +269,11 @@ def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preproc
     `labels=` + `evaluator=` (mmsa.evaluate.Evaluator; `case=` with a per-case one): the map's confusion counts are added to the evaluator on device
     (see _class_map); the returned map is unchanged, `return_map=False` returns None in its place.
     `render=` (mmsa.render.Renderer): a second launch paints the frame's picture (test_bs.py:257-349, `show_result`) -> (map, unc, picture uint8
-    [B, H, W, 3]); over the raw uint8 RGB frames with `preprocess=` (they must have the map's size), else over the de-normalised `img`."""
+    [B, H, W, 3]); over the raw uint8 RGB frames with `preprocess=` (they must have the map's size), else over the de-normalised `img`.
+    `ori_shape=` (h, w[, 3]): the map of `rescale=True` (ED:227-233), uint8 [B, h, w] -- the averaged logits resized once more before the argmax, by the
+    same single launch (mmsa_slide_argmax_resized; `one_pass=False`: by the canvas path), bit for bit argmax_map(slide_inference(..., ori_shape=)).  None or
+    the frame's own size: the launch above.  A LabelPrep for `labels=` must be built for [h, w]; `fused=True` / `return_map=False` are refused; `render=`
+    needs raw uint8 frames of [h, w]."""
     import ctypes
     if preprocess is not None:
         rgb, aux, B, H, W = _raw(preprocess, img, "slide_class_map")
@@ -214,7 +287,9 @@ def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preproc
         cut = lambda chunk: _crops(img, chunk, crop_size)
     if H < crop_size[0] or W < crop_size[1]:
         raise RuntimeError("mmsa.slide_class_map: the image must be at least as large as the crop")
-    src = _picture_source(render, preprocess, img, H, W, return_map, "slide_class_map")
+    tgt = _target(ori_shape, H, W, "slide_class_map")
+    Ho, Wo = tgt or (H, W)
+    src = _picture_source(render, preprocess, img, Ho, Wo, return_map, "slide_class_map", rescaled=tgt is not None)
     boxes = crop_boxes(H, W, crop_size, stride)
     _check_overlap(boxes, "slide_class_map")
     _pair(backbone, head)
@@ -229,9 +304,10 @@ def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preproc
     lg = lgs[0] if len(lgs) == 1 else torch.cat(lgs, 0)
     n = len(jobs)
     tab = (ctypes.c_int * (3 * n))(*[v for b, (y1, x1, _, _) in jobs for v in (b, y1, x1)])
-    out = torch.empty(B, H, W, dtype=torch.uint8, device=device)
+    out = torch.empty(B, Ho, Wo, dtype=torch.uint8, device=device)
     unc = torch.zeros(1, dtype=torch.int32, device=device)
-    _class_map(lg, n, tab, out, B, H, W, crop_size[0], crop_size[1], unc, labels, evaluator, case, fused, return_map)
+    _class_map(lg, n, tab, out, B, H, W, crop_size[0], crop_size[1], unc, labels, evaluator, case, fused, return_map,
+               rs=None if tgt is None else (Ho, Wo, Ho, Wo), one_pass=one_pass)
     if render is not None:
         return out, unc, render(out, src)
     return (out if return_map else None), unc          # unc[0] != 0 <=> some pixel is not covered (ED:220); checked by the caller outside a capture
@@ -239,22 +315,47 @@ def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preproc
 
 @_on_device
 @torch.no_grad()
-def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator=None, case=None, fused=None, return_map=True, render=None):
+def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator=None, case=None, fused=None, return_map=True, render=None,
+                    ori_shape=None, dim=None, cut_dim=None, rescale=True, one_pass=None):
     """Whole-image `simple_test`: resize x4 (bilinear, align_corners=False) + argmax fused (ED:90-94,449,477) -> uint8 [B, H, W].
     `preprocess=` (mmsa.preprocess.Preprocess): img is the pair (rgb, aux) of raw frames, normalised (and padded) by one launch.
     `labels=` + `evaluator=` (+ `case=`): as in slide_class_map.
     `render=` (mmsa.render.Renderer): a second launch paints the frame's picture -> (map, picture uint8 [B, H, W, 3]); over the raw uint8 RGB frames where
     `preprocess=` got frames of the map's size, else over the de-normalised input tensor (a padded or device-resized frame, a float32 RGB modality, no
-    `preprocess=`)."""
+    `preprocess=`).
+    The map at another size, by ONE launch (mmsa_slide_argmax_resized; `one_pass=False`: the canvas path), bit for bit the argmax_map of the logits call named:
+      `ori_shape=` (h, w[, 3])  'whole' with rescale (ED:314-325): whole_inference(..., ori_shape=) -> uint8 [B, h, w];
+      `dim=` (h, w)             'whole_dim' (ED:349-360): whole_inference_dim(..., dim) -> [B, h, w]; `rescale=False` is refused as it is there;
+      `dim=` + `cut_dim=` (w, h) 'whole_dim_cut' (ED:393-414): whole_inference_dim_cut(..., dim, cut_dim, rescale) -> [B, min(cut h, .), min(cut w, .)], the
+                                crop [:cut_dim[1], :cut_dim[0]] of the map at `dim` (rescale) or at the input size (`rescale=False`, the FMB configs).
+    A LabelPrep for `labels=` must be built for that size; `fused=True` / `return_map=False` are refused; `render=` needs a source of the map's size: raw
+    uint8 frames of the size before the cut, or -- for a cut alone -- the input tensor."""
     import ctypes
-    src = None
+    if cut_dim is not None and dim is None:
+        raise RuntimeError("mmsa.whole_class_map: cut_dim= comes with dim= (test_cfg of 'whole_dim_cut')")
+    if dim is not None and ori_shape is not None:
+        raise RuntimeError("mmsa.whole_class_map: the whole_dim modes rescale to dim=, not to ori_shape=; give one of them")
+    if dim is not None and cut_dim is None and not rescale:
+        raise RuntimeError("mmsa.whole_class_map: 'whole_dim' with rescale=False has no defined result in the reference (encoder_decoder.py:334-346 "
+                           "returns None); use ori_shape= / no target, or dim= with cut_dim=")
+    src = rgb = None
     if preprocess is not None:
         rgb, aux = _raw(preprocess, img, "whole_class_map")[:2]
         img = preprocess(rgb, aux)
-        if render is not None:
-            from .render import raw_source
-            src = raw_source(rgb, img.shape[2], img.shape[3])
     _check(img)
+    H, W = int(img.shape[2]), int(img.shape[3])
+    tgt = _target((dim if dim is not None else ori_shape) if rescale else None, H, W, "whole_class_map")
+    Hd, Wd = tgt or (H, W)
+    Ho, Wo = (min(int(cut_dim[1]), Hd), min(int(cut_dim[0]), Wd)) if cut_dim is not None else (Hd, Wd)
+    if Ho < 1 or Wo < 1:
+        raise RuntimeError(f"mmsa.whole_class_map: cut_dim {tuple(cut_dim)} leaves nothing of the map")
+    rs = None if (Ho, Wo) == (H, W) and tgt is None else (Hd, Wd, Ho, Wo)
+    if render is not None and rgb is not None:
+        from .render import raw_source
+        src = raw_source(rgb, Hd, Wd)
+    if render is not None and src is None and tgt is not None:
+        raise RuntimeError(f"mmsa.whole_class_map: render= has no source for the picture: the class map is rescaled to {Hd} x {Wd}, the input tensor is "
+                           f"{H} x {W} (raw uint8 frames of the map's size, with preprocess=, are needed)")
     if render is not None:
         if not return_map:
             raise RuntimeError("mmsa.whole_class_map: render= paints the stored map; drop return_map=False")
@@ -265,11 +366,11 @@ def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator
     _pair(backbone, head)
     feats, _ = backbone(img)
     lg = head(feats)
-    B, _, H, W = img.shape
+    B = img.shape[0]
     tab = (ctypes.c_int * (3 * B))(*[v for b in range(B) for v in (b, 0, 0)])
-    out = torch.empty(B, H, W, dtype=torch.uint8, device=img.device)
+    out = torch.empty(B, Ho, Wo, dtype=torch.uint8, device=img.device)
     unc = torch.zeros(1, dtype=torch.int32, device=img.device)
-    _class_map(lg, B, tab, out, B, H, W, H, W, unc, labels, evaluator, case, fused, return_map)
+    _class_map(lg, B, tab, out, B, H, W, H, W, unc, labels, evaluator, case, fused, return_map, rs=rs, one_pass=one_pass)
     if render is not None:
         return out, render(out, src)
     return out if return_map else None
@@ -277,9 +378,11 @@ def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator
 
 @_on_device
 @torch.no_grad()
-def whole_inference(backbone, head, img):
-    """ED: whole-image mode = encode_decode on the full input."""
-    return encode_decode(backbone, head, img)
+def whole_inference(backbone, head, img, rescale=True, ori_shape=None):
+    """ED:310-327: whole-image mode = encode_decode on the full input; with `rescale` and an `ori_shape` (h, w[, 3]) other than the input's, resized once
+    more to [B, classes, h, w] (ED:314-325)."""
+    y = encode_decode(backbone, head, img)
+    return _rescaled_logits(y, _target(ori_shape, y.shape[2], y.shape[3], "whole_inference") if rescale else None)
 
 
 @_on_device
@@ -314,24 +417,52 @@ def whole_inference_dim_cut(backbone, head, img, dim, cut_dim, rescale=True):
 
 @_on_device
 @torch.no_grad()
-def inference(backbone, head, img, test_cfg, rescale=True, preprocess=None):
+def inference(backbone, head, img, test_cfg, rescale=True, preprocess=None, ori_shape=None):
     """ED:417-447 dispatch on `test_cfg['mode']` -- 'slide', 'whole', 'whole_dim', 'whole_dim_cut' ('slide_mod_sel' runs the segmentor's
     modality-selection variant, ED:236-308, which needs a backbone with a selection head: not this backbone) -- returning the logits the
     reference softmaxes (ED:448-470; flips are the caller's, as in the reference's test pipeline).
     `preprocess=` (mmsa.preprocess.Preprocess): img is the pair (rgb, aux) of raw frames -- 'slide' cuts its windows from them, the whole modes
-    normalise the frame first."""
+    normalise the frame first.
+    `ori_shape=` (h, w[, 3]) of the frame's meta: with `rescale`, 'slide' and 'whole' resize their logits to it (ED:227-233, 314-325); the `whole_dim*`
+    modes rescale to `test_cfg['dim']` and ignore it, as the reference does."""
     mode = test_cfg["mode"]
     if mode == "slide":
-        return slide_inference(backbone, head, img, tuple(test_cfg["crop_size"]), tuple(test_cfg["stride"]), preprocess=preprocess)
+        return slide_inference(backbone, head, img, tuple(test_cfg["crop_size"]), tuple(test_cfg["stride"]), preprocess=preprocess, rescale=rescale,
+                               ori_shape=ori_shape)
     if preprocess is not None and mode in ("whole", "whole_dim", "whole_dim_cut"):
         img = preprocess(*_raw(preprocess, img, "inference")[:2])
     if mode == "whole":
-        return whole_inference(backbone, head, img)
+        return whole_inference(backbone, head, img, rescale=rescale, ori_shape=ori_shape)
     if mode == "whole_dim":
         return whole_inference_dim(backbone, head, img, tuple(test_cfg["dim"]), rescale)
     if mode == "whole_dim_cut":
         return whole_inference_dim_cut(backbone, head, img, tuple(test_cfg["dim"]), tuple(test_cfg["cut_dim"]), rescale)
     raise RuntimeError(f"mmsa.inference: test_cfg.mode '{mode}' is not one of slide / whole / whole_dim / whole_dim_cut")
+
+
+@_on_device
+@torch.no_grad()
+def class_map(backbone, head, img, test_cfg, rescale=True, ori_shape=None, preprocess=None, labels=None, evaluator=None, case=None, render=None, one_pass=None):
+    """`simple_test` (ED:471-477) by mode: the dispatch of `inference` (ED:417-447) onto the class-map calls -> uint8 map, bit for bit
+    argmax_map(inference(...)) of the same arguments, without a logits canvas: [B, H, W], or at the size `rescale` gives ('slide' / 'whole': `ori_shape`;
+    'whole_dim': test_cfg['dim']; 'whole_dim_cut': the crop of the map at `dim`, or at the input size without `rescale`).  What `inference` refuses is
+    refused here ('slide_mod_sel'; 'whole_dim' with rescale=False).  'slide' reads the kernel's uncovered-pixel word back (one host sync, as
+    slide_inference's coverage check is) and raises on a window grid that does not cover the frame (ED:220).
+    `preprocess=`, `labels=` + `evaluator=` (+ `case=`; through the stored map), `render=` (-> (map, picture)), `one_pass=`: as in the calls it goes to."""
+    mode = test_cfg["mode"]
+    kw = dict(preprocess=preprocess, labels=labels, evaluator=evaluator, case=case, render=render, one_pass=one_pass)
+    if mode == "slide":
+        r = slide_class_map(backbone, head, img, tuple(test_cfg["crop_size"]), tuple(test_cfg["stride"]), ori_shape=ori_shape if rescale else None, **kw)
+        if int(r[1].item()) != 0:
+            raise RuntimeError("mmsa.class_map: windows do not cover the image")   # ED:220
+        return r[0] if render is None else (r[0], r[2])
+    if mode == "whole":
+        return whole_class_map(backbone, head, img, ori_shape=ori_shape if rescale else None, **kw)
+    if mode == "whole_dim":
+        return whole_class_map(backbone, head, img, dim=tuple(test_cfg["dim"]), rescale=rescale, **kw)
+    if mode == "whole_dim_cut":
+        return whole_class_map(backbone, head, img, dim=tuple(test_cfg["dim"]), cut_dim=tuple(test_cfg["cut_dim"]), rescale=rescale, **kw)
+    raise RuntimeError(f"mmsa.class_map: test_cfg.mode '{mode}' is not one of slide / whole / whole_dim / whole_dim_cut")
 
 
 @_on_device
@@ -379,9 +510,11 @@ class SlideRunner:
     for bit.  `frame` is the static [B, 6, H, W] buffer the runner reads on every run().
     With `preprocess=` (mmsa.preprocess.Preprocess) `frame` is the pair (rgb, aux) of raw [B, Hs, Ws, 3] buffers -- the runner's static inputs -- and the
     windows are cut AND normalised from them by one launch; run(frame=pair) reads another pair of the same geometry instead (mmsa.preprocess.FrameFeeder's slots).
-    With `render=` (mmsa.render.Renderer) every run() also paints the frame's picture into a static buffer (one more launch): FrameResult.picture()."""
+    With `render=` (mmsa.render.Renderer) every run() also paints the frame's picture into a static buffer (one more launch): FrameResult.picture().
+    With `ori_shape=` (h, w[, 3]) the class map -- and the static `out` buffer -- is the one of `rescale=True` at [B, h, w] (slide_class_map's `ori_shape=`:
+    mmsa_slide_argmax_resized in place of mmsa_slide_argmax, or the canvas path with `one_pass=False`)."""
 
-    def __init__(self, backbone, head, frame, crop_size, stride, chains=2, check_every=1, preprocess=None, render=None):
+    def __init__(self, backbone, head, frame, crop_size, stride, chains=2, check_every=1, preprocess=None, render=None, ori_shape=None, one_pass=None):
         import ctypes
         from .chains import Chains
         self.preprocess = preprocess
@@ -395,7 +528,12 @@ class SlideRunner:
             B, _, H, W = self.frame.shape
             self.device = self.frame.device
         self.render = render
-        _picture_source(render, preprocess, self.frame, H, W, True, "SlideRunner")      # refuses a frame the picture has no source for
+        self.size = (H, W)
+        self.one_pass = one_pass
+        tgt = _target(ori_shape, H, W, "SlideRunner")
+        self.rs = None if tgt is None else (tgt[0], tgt[1], tgt[0], tgt[1])
+        Ho, Wo = tgt or (H, W)
+        _picture_source(render, preprocess, self.frame, Ho, Wo, True, "SlideRunner", rescaled=tgt is not None)      # refuses a frame the picture has no source for
         _pair(backbone, head)
         self.crop_size = tuple(crop_size)
         boxes = crop_boxes(H, W, crop_size, stride)
@@ -410,12 +548,12 @@ class SlideRunner:
             self.crops = self._cut(self.frame)          # also the static input buffer of the chains
             self.chains = Chains(backbone, head, n=chains, check_every=check_every).capture(self.crops)
             self.tab = (ctypes.c_int * (3 * n))(*[v for b, (y1, x1, _, _) in self.jobs for v in (b, y1, x1)])
-            self.out = torch.empty(B, H, W, dtype=torch.uint8, device=self.device)
+            self.out = torch.empty(B, Ho, Wo, dtype=torch.uint8, device=self.device)
             self.unc = torch.zeros(1, dtype=torch.int32, device=self.device)
             self.pic = None
             if render is not None:
                 render.palette_on(self.device)
-                self.pic = torch.empty(B, H, W, 3, dtype=torch.uint8, device=self.device)
+                self.pic = torch.empty(B, Ho, Wo, 3, dtype=torch.uint8, device=self.device)
 
     def _cut(self, frame, out=None):
         if self.preprocess is not None:
@@ -439,15 +577,15 @@ class SlideRunner:
             frame = self.preprocess.check(*frame)
             if any(f.shape != s.shape or f.dtype != s.dtype or f.device != s.device for f, s in zip(frame, self.frame)):
                 raise RuntimeError("mmsa.SlideRunner.run(frame=...): the pair must have the shape, dtypes and device of the runner's own buffers")
-        src = _picture_source(self.render, self.preprocess, frame, self.out.shape[1], self.out.shape[2], return_map, "SlideRunner.run")
+        src = _picture_source(self.render, self.preprocess, frame, self.out.shape[1], self.out.shape[2], return_map, "SlideRunner.run", rescaled=self.rs is not None)
         with torch.cuda.device(self.device):
             self._cut(frame, out=self.crops)
             rp = self.chains.replay()
             lg = rp.unverified          # the argmax kernel below is enqueued behind the pass; nothing is read on the host before outputs() verifies it
-            B, H, W = self.out.shape
+            B, (H, W) = self.out.shape[0], self.size
             self.unc.zero_()
             _class_map(lg, len(self.jobs), self.tab, self.out, B, H, W, self.crop_size[0], self.crop_size[1], self.unc, labels, evaluator, case, fused,
-                       return_map)
+                       return_map, rs=self.rs, one_pass=self.one_pass)
             if self.render is not None:
                 self.render(self.out, src, out=self.pic)
         return FrameResult(self, rp, has_map=return_map)

@@ -211,6 +211,43 @@ def gen_whole_dim():
     print("whole_dim", {k: v.shape for k, v in out.items() if k.endswith("_out")}, flush=True)
 
 
+RESCALE_CASES = dict(          # tag -> (frame (h, w), crop, stride, ori_shape); crop None = whole_inference
+    a=((90, 150), (64, 64), (40, 40), (77, 131)),       # 2 x 4 windows, shifted last row / column, overlap up to 4; down, no integer ratio
+    c=((70, 70), (64, 64), (64, 64), (105, 84)),        # 2 x 2 windows shifted by 6; up, another ratio per axis
+    w=((90, 150), None, None, (45, 75)))                # whole frame; exactly half
+
+
+def rescale_frame(hw, seed=35):
+    """The seeded frame of gen_rescale (tests/rescale_ref.py restates it): white noise plus one offset per channel, as a normalised real frame has.  White
+    noise alone leaves 1.3 - 1.9 % of the pixels with a top-two margin inside the class-map test's exclusion band whatever the seed (measured on 21 seeds
+    of the toy weights): five zero-mean classes tie too often for the 1 % cap."""
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(1, 6, hw[0], hw[1], generator=g) + torch.randn(1, 6, 1, 1, generator=g)
+
+
+def gen_rescale():
+    """The reference's own EncoderDecoder.slide_inference(rescale=True) / whole_inference(rescale=True) with `ori_shape` set, on seeded one-image frames
+    with the fixed toy encode_decode of gen_slide (tests/golden/rescale.npz).  Also checked here: the share of pixels whose top-two margin is within
+    twice tests.util.REL_TOL of the fixture's largest magnitude -- the pixels the class-map test may exclude -- stays under 1 % (else: another seed)."""
+    from tests.configs import toy_encode_decode
+    from tests.util import REL_TOL
+    out = {}
+    for tag, (hw, crop, stride, ori) in RESCALE_CASES.items():
+        img = rescale_frame(hw)
+        fn = toy_encode_decode(5, seed=79)
+        y = ref_import.reference_rescale(fn, img, ori, crop, stride, 5)
+        assert tuple(y.shape) == (1, 5) + tuple(ori)
+        top = y.topk(2, dim=1).values
+        close = ((top[:, 0] - top[:, 1]) <= 2 * REL_TOL * y.abs().max()).float().mean().item()
+        assert close <= 0.01, f"rescale case {tag}: {close:.4f} of the pixels have a top-two margin inside the tolerance; choose another seed"
+        out[f"{tag}_cfg"] = np.array(list(hw) + (list(crop) + list(stride) if crop else [0, 0, 0, 0]) + list(ori))
+        out[f"{tag}_out"] = y.numpy()
+        print("rescale", tag, tuple(y.shape), f"near-ties {close:.4%}", flush=True)
+    path = os.path.join(OUT, "rescale.npz")
+    np.savez_compressed(path, **out)
+    print("rescale", os.path.getsize(path), "bytes", flush=True)
+
+
 def gen_ckpt():
     """TwinConvNeXt.init_weights (TC:403-443) of the reference on a seeded single-stream ConvNeXt checkpoint: which twin keys
     end up loaded, and their checksums (tests/golden/convnext_ckpt.npz)."""
@@ -341,7 +378,7 @@ def gen_eval():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--big", action="store_true", help="also ViT-B@512 and ViT-L@1024 (minutes, GBs of RAM)")
-    ap.add_argument("--only", default=None, help="run one generator: msda_bwd | sam_ckpt | eval | model:<config name>")
+    ap.add_argument("--only", default=None, help="run one generator: msda_bwd | sam_ckpt | eval | rescale | model:<config name>")
     a = ap.parse_args()
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
@@ -359,6 +396,7 @@ def main():
         gen_model(n, full=True)
     gen_slide()
     gen_whole_dim()
+    gen_rescale()
     gen_ckpt()
     gen_eval()
     gen_head("head_vitl", full=False)

@@ -331,3 +331,33 @@ def reference_whole_dim(encode_decode_fn, img, dim, cut_dim=None, rescale=True):
     if cut_dim is None:
         return mod.EncoderDecoder.whole_inference_dim(fake, img, meta, rescale, dim)
     return mod.EncoderDecoder.whole_inference_dim_cut(fake, img, meta, rescale, dim, cut_dim)
+
+
+def reference_rescale(encode_decode_fn, img, ori_shape, crop_size=None, stride=None, num_classes=None):
+    """Run the reference's own `EncoderDecoder.slide_inference` (segmentors/encoder_decoder.py:191-234; with `crop_size`) or `whole_inference`
+    (:310-327), UNMODIFIED, with rescale=True and `ori_shape` (h, w) in the frame's meta: the second resize of ED:227-233 / 314-325.  Stand-in `self` as
+    in reference_slide_inference; `resize` is the `F.interpolate` wrapper it is upstream (mmseg.ops.resize)."""
+    import torch.nn as nn
+    import torch.nn.functional as F
+    install()
+    if "mmseg_custom.models.segmentors" not in sys.modules:
+        m = types.ModuleType("mmseg_custom.models.segmentors")
+        m.__path__ = [os.path.join(SEG, "mmseg_custom/models/segmentors")]
+        sys.modules["mmseg_custom.models.segmentors"] = m
+    import mmseg.models.segmentors.base as sb
+    import mmseg.ops as mo
+
+    class BaseSegmentor(nn.Module):
+        def __init__(self, init_cfg=None):
+            super().__init__()
+    sb.BaseSegmentor = BaseSegmentor
+    mo.resize = lambda input, size=None, scale_factor=None, mode="nearest", align_corners=None, warning=True: F.interpolate(input, size, scale_factor, mode, align_corners)
+    mod = importlib.import_module("mmseg_custom.models.segmentors.encoder_decoder")
+    mod.resize = mo.resize
+    meta = [dict(ori_shape=tuple(ori_shape) + (3,))]
+    if crop_size is None:
+        fake = types.SimpleNamespace(align_corners=False, encode_decode=lambda im, meta: encode_decode_fn(im))
+        return mod.EncoderDecoder.whole_inference(fake, img, meta, True)
+    fake = types.SimpleNamespace(test_cfg=types.SimpleNamespace(stride=stride, crop_size=crop_size), num_classes=num_classes,
+                                 align_corners=False, encode_decode=lambda im, meta: encode_decode_fn(im))
+    return mod.EncoderDecoder.slide_inference(fake, img, meta, True)
