@@ -318,11 +318,12 @@ class Evaluator:
         self._taken(pred.shape[0], case, slots)
         return self
 
-    def add_fused(self, lg, n, windows, out, B, H, W, hc, wc, unc, labels, case=None, slots=None):
-        """Class map + counts in one launch (mmsa.inference's class-map calls with labels= / evaluator=)."""
+    def add_fused(self, lg, plan, out, unc, labels, case=None, slots=None):
+        """Class map + counts in one launch (mmsa.inference's class-map calls with labels= / evaluator=); `plan`: the frame's mmsa.inference.MapPlan."""
         counts = self._buffer(lg.device)
-        slide_argmax_eval(lg, n, windows, out, B, H, W, hc, wc, unc, labels, self.prep, counts, slots=self.slots_for(B, case, slots))
-        self._taken(B, case, slots)
+        slide_argmax_eval(lg, plan.n, plan.tab, out, plan.B, plan.H, plan.W, plan.hc, plan.wc, unc, labels, self.prep, counts,
+                          slots=self.slots_for(plan.B, case, slots))
+        self._taken(plan.B, case, slots)
         return self
 
     def reset(self):

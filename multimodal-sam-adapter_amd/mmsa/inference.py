@@ -5,17 +5,23 @@
 `whole_dim*` modes, as logits (a second resize of the canvas) or as the class map of ONE launch that writes neither canvas (mmsa_slide_argmax_resized).
 
 The crops of a sliding-window frame are batched through ONE backbone + head call (the reference runs them one by one,
-ED:205-214), and the resize / pad / accumulate / count of every crop is one kernel launch on the logits canvas."""
+ED:205-214), and the resize / pad / accumulate / count of every crop is one kernel launch on the logits canvas.
+
+What a frame's output looks like -- its windows, the size after the second resize and after the cut, which class-map kernel that takes -- is decided once,
+in `MapPlan`, a record without device state; the entries read the frame (`_intake`), make the plan, and launch from it."""
+import ctypes
+import dataclasses
+import functools
+
 import torch
 
 from . import lib
 from . import ops
+from .render import slide_source, whole_source
 
 
 def _on_device(fn):
     """Run an entry point with its first tensor argument's device current (launches go to that device's current stream)."""
-    import functools
-
     @functools.wraps(fn)
     def wrapped(*args, **kw):
         t = next((a for a in args if isinstance(a, torch.Tensor)), None)
@@ -55,6 +61,26 @@ def _check(img):
         raise RuntimeError("mmsa.inference: img must be a float32 [B, C, H, W] GPU tensor (there is no CPU path)")
 
 
+def _intake(img, preprocess, what, contiguous=True):
+    """The frame of a slide entry -> (B, H, W, device, frame, cut): H x W is the canvas the windows cover; `frame` is the checked pair (rgb, aux) of raw frames
+    (`preprocess=`) or the normalised tensor; `cut(windows, out=None, frame=frame)` is the one launch that cuts (and, from raw frames, normalises) the
+    windows (image, (y1, x1, y2, x2)), all of the first one's size.  `contiguous=False` hands a strided tensor on as it came: what slide_inference does."""
+    if preprocess is not None:
+        rgb, aux, B, H, W = _raw(preprocess, img, what)
+        frame, device = (rgb, aux), rgb.device
+        crops = lambda f, windows, size, out: preprocess.crops(f[0], f[1], windows, size, out=out)
+    else:
+        _check(img)
+        frame = img.contiguous() if contiguous else img
+        (B, _, H, W), device = frame.shape, frame.device
+        crops = _crops
+
+    def cut(windows, out=None, frame=frame):
+        y1, x1, y2, x2 = windows[0][1]
+        return crops(frame, windows, (y2 - y1, x2 - x1), out)
+    return B, H, W, device, frame, cut
+
+
 @_on_device
 @torch.no_grad()
 def encode_decode(backbone, head, img):
@@ -91,23 +117,12 @@ def slide_inference(backbone, head, img, crop_size, stride, max_batch=8, preproc
     are resized once more (bilinear, align_corners=False) to [B, classes, h, w] (ED:227-233).  All windows have
     the crop size here (the backbone needs H = W = img_size), i.e. the image must be at least as large as the crop.
     `preprocess=` (mmsa.preprocess.Preprocess): img is the pair (rgb, aux) of raw frames; the windows are cut AND normalised by one launch."""
-    if preprocess is not None:
-        rgb, aux, B, H, W = _raw(preprocess, img, "slide_inference")
-        device = rgb.device
-        cut = lambda chunk: preprocess.crops(rgb, aux, chunk, crop_size)
-    else:
-        _check(img)
-        B, _, H, W = img.shape
-        device = img.device
-        cut = lambda chunk: _crops(img, chunk, crop_size)
-    if H < crop_size[0] or W < crop_size[1]:
-        raise RuntimeError("mmsa.slide_inference: the image must be at least as large as the crop")
-    boxes = crop_boxes(H, W, crop_size, stride)
+    B, H, W, device, _, cut = _intake(img, preprocess, "slide_inference", contiguous=False)
+    plan = MapPlan.slide(B, H, W, crop_size, stride, ori_shape if rescale else None, what="slide_inference")     # any overlap, any number of windows
     _pair(backbone, head)
     preds = count = None
-    jobs = [(b, box) for box in boxes for b in range(B)]
-    for s in range(0, len(jobs), max_batch):
-        chunk = jobs[s:s + max_batch]
+    for s in range(0, plan.n, max_batch):
+        chunk = plan.windows[s:s + max_batch]
         crops = cut(chunk)
         feats, _ = backbone(crops)
         lg = head(feats)                                   # [n, classes, hc/4, wc/4]
@@ -119,7 +134,7 @@ def slide_inference(backbone, head, img, crop_size, stride, max_batch=8, preproc
     if bool((count == 0).any()):
         raise RuntimeError("mmsa.slide_inference: windows do not cover the image")   # ED:220
     lib.call("mmsa_div_count_nchw", preds.data_ptr(), count.data_ptr(), B, preds.shape[1], H * W, ops._stream())
-    return _rescaled_logits(preds, _target(ori_shape, H, W, "slide_inference") if rescale else None)
+    return _rescaled_logits(preds, (plan.Hd, plan.Wd) if plan.rescaled else None)
 
 
 def _target(shape, H, W, what):
@@ -144,7 +159,6 @@ def _rescaled_logits(y, target):
 
 def _crops(img, chunk, crop_size, out=None):
     """ED:205-212 for a batch of windows: one HIP launch (mmsa_crop_batch_nchw), no ATen slicing / stacking."""
-    import ctypes
     n = len(chunk)
     if out is None:
         out = torch.empty(n, img.shape[1], crop_size[0], crop_size[1], device=img.device)
@@ -176,84 +190,148 @@ def _check_overlap(boxes, what):
                            "(use slide_inference + argmax_map, or a larger stride)")
 
 
-def _picture_source(render, preprocess, frame, H, W, return_map, what, rescaled=False):
-    """The source `render=` paints over in the slide modes (None without `render=`); refusals come before any launch.  H x W is the MAP's size; a
-    normalised frame is no source for a map rescaled to another size."""
-    if render is None:
-        return None
-    if not return_map:
-        raise RuntimeError(f"mmsa.{what}: render= paints the stored map; drop return_map=False")
-    from .render import slide_source
-    if rescaled and preprocess is None:
-        raise RuntimeError(f"mmsa.{what}: render= has no source for the picture: the class map is rescaled to {H} x {W}, the normalised frame has another size "
-                           "(raw uint8 frames of the map's size, with preprocess=, are needed)")
-    return slide_source(render, preprocess, frame, H, W, what)
-
-
 # Which launch makes a RESCALED class map by default: True = the one-pass kernel (mmsa_slide_argmax_resized), False = the canvas path
 # (_rescaled_map_canvas: the launches of slide_inference + the second resize + argmax_map, from the same head-resolution logits; the same map bit for bit).
 # Per direction of the second resize ("up": the target has more pixels than the frame).  `one_pass=` of the class-map calls overrides it.
 ONE_PASS_RESCALE_DEFAULT = dict(up=True, down=True)   # not measured yet (tools/exp/rescale_class_map_bench.py)
 
 
-def _rescaled_map_canvas(lg, n, tab, out, B, H, W, hc, wc, unc, rs):
-    """The rescaled class map the long way round, from the head-resolution logits lg [n, C, hs, ws] and the window table: canvas (accumulate, count,
+@dataclasses.dataclass(frozen=True)
+class MapPlan:
+    """The output geometry of one frame batch, decided on the host before anything is launched: B x (H x W) is the canvas the windows cover, hc x wc the
+    window size, `jobs` the windows (image, y0, x0) in the accumulation order of slide_inference, Hd x Wd the size after the second resize of
+    `rescale=True` (H x W when there is none) and Ho x Wo the size after the cut of 'whole_dim_cut' (Hd x Wd without one): the class map is
+    uint8 [B, Ho, Wo].  Made by `slide` (a window grid; target `ori_shape`) or `whole` (one full-size window per image; target `ori_shape` or `dim`, cut
+    `cut_dim`), which own the refusals of a geometry; `class_map` is the launch."""
+    B: int
+    H: int
+    W: int
+    hc: int
+    wc: int
+    jobs: tuple
+    Hd: int
+    Wd: int
+    Ho: int
+    Wo: int
+
+    @classmethod
+    def slide(cls, B, H, W, crop_size, stride, ori_shape=None, what="slide_class_map"):
+        """The window grid of ED:198-212 on a B x H x W frame batch; `ori_shape` (h, w[, 3]): the target of ED:227-233 (None: no second resize)."""
+        hc, wc = crop_size
+        if H < hc or W < wc:
+            raise RuntimeError(f"mmsa.{what}: the image must be at least as large as the crop")
+        Hd, Wd = _target(ori_shape, H, W, what) or (H, W)
+        jobs = tuple((b, y1, x1) for y1, x1, _, _ in crop_boxes(H, W, crop_size, stride) for b in range(B))
+        return cls(B, H, W, hc, wc, jobs, Hd, Wd, Hd, Wd)
+
+    @classmethod
+    def whole(cls, B, H, W, ori_shape=None, dim=None, cut_dim=None, rescale=True, what="whole_class_map"):
+        """One window per image, the image itself.  `ori_shape`: 'whole' (ED:314-325); `dim` (h, w): 'whole_dim' (ED:349-360); `dim` + `cut_dim` (w, h):
+        'whole_dim_cut' (ED:393-414), the top-left [:cut_dim[1], :cut_dim[0]] of the map at `dim` (`rescale`) or at the input size, clamped to it."""
+        if cut_dim is not None and dim is None:
+            raise RuntimeError(f"mmsa.{what}: cut_dim= comes with dim= (test_cfg of 'whole_dim_cut')")
+        if dim is not None and ori_shape is not None:
+            raise RuntimeError(f"mmsa.{what}: the whole_dim modes rescale to dim=, not to ori_shape=; give one of them")
+        if dim is not None and cut_dim is None and not rescale:
+            raise RuntimeError(f"mmsa.{what}: 'whole_dim' with rescale=False has no defined result in the reference (encoder_decoder.py:334-346 "
+                               "returns None); use ori_shape= / no target, or dim= with cut_dim=")
+        Hd, Wd = _target((dim if dim is not None else ori_shape) if rescale else None, H, W, what) or (H, W)
+        Ho, Wo = (min(int(cut_dim[1]), Hd), min(int(cut_dim[0]), Wd)) if cut_dim is not None else (Hd, Wd)
+        if Ho < 1 or Wo < 1:
+            raise RuntimeError(f"mmsa.{what}: cut_dim {tuple(cut_dim)} leaves nothing of the map")
+        return cls(B, H, W, H, W, tuple((b, 0, 0) for b in range(B)), Hd, Wd, Ho, Wo)
+
+    def check_windows(self, what, per="call"):
+        """What the one-pass class-map kernels ask of the windows (slide_inference asks neither): overlap up to MAX_OVERLAP, at most 64 windows."""
+        _check_overlap({(y0, x0, y0 + self.hc, x0 + self.wc) for _, y0, x0 in self.jobs}, what)
+        if self.n > 64:
+            raise RuntimeError(f"mmsa.{what}: at most 64 windows per {per}")
+
+    @property
+    def n(self):
+        return len(self.jobs)
+
+    @property
+    def resized(self):
+        """A second resize applies (_target gave a size: one other than the canvas's own)."""
+        return (self.Hd, self.Wd) != (self.H, self.W)
+
+    @property
+    def rescaled(self):
+        """A second resize or a cut applies: the map comes from mmsa_slide_argmax_resized (or the canvas path), not from mmsa_slide_argmax."""
+        return self.resized or (self.Ho, self.Wo) != (self.H, self.W)
+
+    @property
+    def rs(self):
+        return (self.Hd, self.Wd, self.Ho, self.Wo) if self.rescaled else None
+
+    @functools.cached_property
+    def windows(self):
+        """`jobs` in the form the crop launches take: (image, (y1, x1, y2, x2))."""
+        return [(b, (y0, x0, y0 + self.hc, x0 + self.wc)) for b, y0, x0 in self.jobs]
+
+    @functools.cached_property
+    def tab(self):
+        """`jobs` as the int [n, 3] window table of the kernels."""
+        return (ctypes.c_int * (3 * self.n))(*[v for job in self.jobs for v in job])
+
+    def _args(self, lg, out):
+        """The leading arguments the three class-map entries share."""
+        return lg.data_ptr(), self.n, lg.shape[1], lg.shape[2], lg.shape[3], self.tab, out.data_ptr(), self.B, self.H, self.W, self.hc, self.wc
+
+    def class_map(self, lg, out, unc, labels=None, evaluator=None, case=None, fused=None, return_map=True, one_pass=None):
+        """The class-map launch of the three class-map calls, from the head-resolution logits lg [n, C, hs, ws] into out uint8 [B, Ho, Wo] and the
+        uncovered-pixel word `unc`.  Without `labels`: mmsa_slide_argmax.  With `labels` (raw uint8 label maps [B, Hl, Wl]) and `evaluator`
+        (mmsa.evaluate.Evaluator): the confusion counts of the map are ADDED to the evaluator's buffer as well -- by the same launch
+        (mmsa_slide_argmax_eval: `fused=True`) or by a second one over the stored map (mmsa_eval_confusion_u8); `fused=None` takes mmsa.evaluate.FUSED_DEFAULT.
+        The map is the same either way; `return_map=False` with the fused launch writes none.  No host sync, no allocation.
+        A `rescaled` plan: mmsa_slide_argmax_resized, or the canvas path where ONE_PASS_RESCALE_DEFAULT / `one_pass=False` say so; the counts then always go
+        through the stored map (no fused variant at the rescaled size)."""
+        if self.rescaled:
+            if (labels is None) != (evaluator is None):
+                raise RuntimeError("mmsa.inference: labels= and evaluator= come together")
+            if fused or not return_map:
+                raise RuntimeError("mmsa.inference: fused=True / return_map=False need the fused class-map + evaluation launch, and that launch has no variant at "
+                                   "a rescaled or cut size: the counts of a rescaled map go through the stored map (drop fused= / return_map=)")
+            if ONE_PASS_RESCALE_DEFAULT["up" if self.Hd * self.Wd > self.H * self.W else "down"] if one_pass is None else one_pass:
+                lib.call("mmsa_slide_argmax_resized", *self._args(lg, out), *self.rs, unc.data_ptr(), ops._stream())
+            else:
+                _rescaled_map_canvas(self, lg, out, unc)
+            if evaluator is not None:
+                evaluator.add(out, labels, case=case)
+            return
+        if one_pass is not None:
+            raise RuntimeError("mmsa.inference: one_pass= chooses the launch of a RESCALED class map; this map has the frame's size")
+        if labels is None and evaluator is None:
+            if not return_map:
+                raise RuntimeError("mmsa.inference: return_map=False only makes sense with labels= and evaluator=")
+            lib.call("mmsa_slide_argmax", *self._args(lg, out), unc.data_ptr(), ops._stream())
+            return
+        if labels is None or evaluator is None:
+            raise RuntimeError("mmsa.inference: labels= and evaluator= come together")
+        if fused is False and not return_map:
+            raise RuntimeError("mmsa.inference: return_map=False needs the fused launch (two launches go through the stored map); drop fused=False")
+        from . import evaluate
+        if (evaluate.FUSED_DEFAULT or not return_map) if fused is None else fused:      # no map wanted: only the fused launch can leave it unwritten
+            evaluator.add_fused(lg, self, out if return_map else None, unc, labels, case=case)
+        else:
+            lib.call("mmsa_slide_argmax", *self._args(lg, out), unc.data_ptr(), ops._stream())
+            evaluator.add(out, labels, case=case)
+
+
+def _rescaled_map_canvas(plan, lg, out, unc):
+    """The rescaled class map the long way round, from the head-resolution logits lg [n, C, hs, ws] and the plan's windows: canvas (accumulate, count,
     divide), second canvas, argmax, crop -- the launches slide_inference / encode_decode + argmax_map make.  `unc` gets the number of CANVAS pixels that no
     window covers (non-zero exactly when the one-pass kernel's count of output pixels may be)."""
-    Hd, Wd, Hcut, Wcut = rs
-    C = lg.shape[1]
+    B, H, W, C = plan.B, plan.H, plan.W, lg.shape[1]
     canvas = torch.zeros(B, C, H, W, device=lg.device)
     count = torch.zeros(B, H, W, device=lg.device)
-    for k in range(n):
-        b, y0, x0 = tab[3 * k], tab[3 * k + 1], tab[3 * k + 2]
-        _resize_into(lg[k:k + 1], canvas[b:b + 1], y0, x0, hc, wc, count=count[b:b + 1], accumulate=True)
+    for k, (b, y0, x0) in enumerate(plan.jobs):
+        _resize_into(lg[k:k + 1], canvas[b:b + 1], y0, x0, plan.hc, plan.wc, count=count[b:b + 1], accumulate=True)
     unc.add_((count == 0).sum().to(torch.int32))
     lib.call("mmsa_div_count_nchw", canvas.data_ptr(), count.data_ptr(), B, C, H * W, ops._stream())
-    full = argmax_map(_rescaled_logits(canvas, None if (Hd, Wd) == (H, W) else (Hd, Wd)))
-    out.copy_(full[:, :Hcut, :Wcut])
-
-
-def _class_map(lg, n, tab, out, B, H, W, hc, wc, unc, labels, evaluator, case, fused, return_map, rs=None, one_pass=None):
-    """The class-map launch of the three class-map calls.  Without `labels`: mmsa_slide_argmax.  With `labels` (raw uint8 label maps [B, Hl, Wl]) and
-    `evaluator` (mmsa.evaluate.Evaluator): the confusion counts of the map are ADDED to the evaluator's buffer as well -- by the same launch
-    (mmsa_slide_argmax_eval: `fused=True`) or by a second one over the stored map (mmsa_eval_confusion_u8); `fused=None` takes mmsa.evaluate.FUSED_DEFAULT.
-    The map is the same either way; `return_map=False` with the fused launch writes none.  No host sync, no allocation.
-    `rs` = (Hd, Wd, Hcut, Wcut): the map at a rescaled size, out [B, Hcut, Wcut] -- mmsa_slide_argmax_resized, or the canvas path where
-    ONE_PASS_RESCALE_DEFAULT / `one_pass=False` say so; the counts then always go through the stored map (no fused variant at the rescaled size)."""
-    if rs is not None:
-        if (labels is None) != (evaluator is None):
-            raise RuntimeError("mmsa.inference: labels= and evaluator= come together")
-        if fused or not return_map:
-            raise RuntimeError("mmsa.inference: fused=True / return_map=False need the fused class-map + evaluation launch, and that launch has no variant at "
-                               "a rescaled or cut size: the counts of a rescaled map go through the stored map (drop fused= / return_map=)")
-        Hd, Wd, Hcut, Wcut = rs
-        if ONE_PASS_RESCALE_DEFAULT["up" if Hd * Wd > H * W else "down"] if one_pass is None else one_pass:
-            lib.call("mmsa_slide_argmax_resized", lg.data_ptr(), n, lg.shape[1], lg.shape[2], lg.shape[3], tab, out.data_ptr(), B, H, W, hc, wc,
-                     Hd, Wd, Hcut, Wcut, unc.data_ptr(), ops._stream())
-        else:
-            _rescaled_map_canvas(lg, n, tab, out, B, H, W, hc, wc, unc, rs)
-        if evaluator is not None:
-            evaluator.add(out, labels, case=case)
-        return
-    if one_pass is not None:
-        raise RuntimeError("mmsa.inference: one_pass= chooses the launch of a RESCALED class map; this map has the frame's size")
-    if labels is None and evaluator is None:
-        if not return_map:
-            raise RuntimeError("mmsa.inference: return_map=False only makes sense with labels= and evaluator=")
-        lib.call("mmsa_slide_argmax", lg.data_ptr(), n, lg.shape[1], lg.shape[2], lg.shape[3], tab, out.data_ptr(), B, H, W, hc, wc, unc.data_ptr(),
-                 ops._stream())
-        return
-    if labels is None or evaluator is None:
-        raise RuntimeError("mmsa.inference: labels= and evaluator= come together")
-    if fused is False and not return_map:
-        raise RuntimeError("mmsa.inference: return_map=False needs the fused launch (two launches go through the stored map); drop fused=False")
-    from . import evaluate
-    if (evaluate.FUSED_DEFAULT or not return_map) if fused is None else fused:      # no map wanted: only the fused launch can leave it unwritten
-        evaluator.add_fused(lg, n, tab, out if return_map else None, B, H, W, hc, wc, unc, labels, case=case)
-    else:
-        lib.call("mmsa_slide_argmax", lg.data_ptr(), n, lg.shape[1], lg.shape[2], lg.shape[3], tab, out.data_ptr(), B, H, W, hc, wc, unc.data_ptr(),
-                 ops._stream())
-        evaluator.add(out, labels, case=case)
+    full = argmax_map(_rescaled_logits(canvas, (plan.Hd, plan.Wd) if plan.resized else None))
+    out.copy_(full[:, :plan.Ho, :plan.Wo])
 
 
 @_on_device
@@ -267,47 +345,26 @@ def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preproc
     batches of `max_batch`; with static shapes the whole function is HIP-graph capturable (no host sync inside).
     `preprocess=` (mmsa.preprocess.Preprocess): img is the pair (rgb, aux) of raw frames; the windows are cut AND normalised by one launch.
     `labels=` + `evaluator=` (mmsa.evaluate.Evaluator; `case=` with a per-case one): the map's confusion counts are added to the evaluator on device
-    (see _class_map); the returned map is unchanged, `return_map=False` returns None in its place.
+    (see MapPlan.class_map); the returned map is unchanged, `return_map=False` returns None in its place.
     `render=` (mmsa.render.Renderer): a second launch paints the frame's picture (test_bs.py:257-349, `show_result`) -> (map, unc, picture uint8
     [B, H, W, 3]); over the raw uint8 RGB frames with `preprocess=` (they must have the map's size), else over the de-normalised `img`.
     `ori_shape=` (h, w[, 3]): the map of `rescale=True` (ED:227-233), uint8 [B, h, w] -- the averaged logits resized once more before the argmax, by the
     same single launch (mmsa_slide_argmax_resized; `one_pass=False`: by the canvas path), bit for bit argmax_map(slide_inference(..., ori_shape=)).  None or
     the frame's own size: the launch above.  A LabelPrep for `labels=` must be built for [h, w]; `fused=True` / `return_map=False` are refused; `render=`
     needs raw uint8 frames of [h, w]."""
-    import ctypes
-    if preprocess is not None:
-        rgb, aux, B, H, W = _raw(preprocess, img, "slide_class_map")
-        device = rgb.device
-        cut = lambda chunk: preprocess.crops(rgb, aux, chunk, crop_size)
-    else:
-        _check(img)
-        img = img.contiguous()
-        B, _, H, W = img.shape
-        device = img.device
-        cut = lambda chunk: _crops(img, chunk, crop_size)
-    if H < crop_size[0] or W < crop_size[1]:
-        raise RuntimeError("mmsa.slide_class_map: the image must be at least as large as the crop")
-    tgt = _target(ori_shape, H, W, "slide_class_map")
-    Ho, Wo = tgt or (H, W)
-    src = _picture_source(render, preprocess, img, Ho, Wo, return_map, "slide_class_map", rescaled=tgt is not None)
-    boxes = crop_boxes(H, W, crop_size, stride)
-    _check_overlap(boxes, "slide_class_map")
+    B, H, W, device, frame, cut = _intake(img, preprocess, "slide_class_map")
+    plan = MapPlan.slide(B, H, W, crop_size, stride, ori_shape)
+    src = None if render is None else slide_source(render, preprocess, frame, plan, return_map, "slide_class_map")
+    plan.check_windows("slide_class_map")
     _pair(backbone, head)
-    jobs = [(b, box) for box in boxes for b in range(B)]      # the accumulation order of slide_inference
-    if len(jobs) > 64:
-        raise RuntimeError("mmsa.slide_class_map: at most 64 windows per call")
     lgs = []
-    for s in range(0, len(jobs), max_batch):
-        chunk = jobs[s:s + max_batch]
-        feats, _ = backbone(cut(chunk))
+    for s in range(0, plan.n, max_batch):
+        feats, _ = backbone(cut(plan.windows[s:s + max_batch]))
         lgs.append(head(feats))
     lg = lgs[0] if len(lgs) == 1 else torch.cat(lgs, 0)
-    n = len(jobs)
-    tab = (ctypes.c_int * (3 * n))(*[v for b, (y1, x1, _, _) in jobs for v in (b, y1, x1)])
-    out = torch.empty(B, Ho, Wo, dtype=torch.uint8, device=device)
+    out = torch.empty(B, plan.Ho, plan.Wo, dtype=torch.uint8, device=device)
     unc = torch.zeros(1, dtype=torch.int32, device=device)
-    _class_map(lg, n, tab, out, B, H, W, crop_size[0], crop_size[1], unc, labels, evaluator, case, fused, return_map,
-               rs=None if tgt is None else (Ho, Wo, Ho, Wo), one_pass=one_pass)
+    plan.class_map(lg, out, unc, labels, evaluator, case, fused, return_map, one_pass)
     if render is not None:
         return out, unc, render(out, src)
     return (out if return_map else None), unc          # unc[0] != 0 <=> some pixel is not covered (ED:220); checked by the caller outside a capture
@@ -330,47 +387,24 @@ def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator
                                 crop [:cut_dim[1], :cut_dim[0]] of the map at `dim` (rescale) or at the input size (`rescale=False`, the FMB configs).
     A LabelPrep for `labels=` must be built for that size; `fused=True` / `return_map=False` are refused; `render=` needs a source of the map's size: raw
     uint8 frames of the size before the cut, or -- for a cut alone -- the input tensor."""
-    import ctypes
-    if cut_dim is not None and dim is None:
-        raise RuntimeError("mmsa.whole_class_map: cut_dim= comes with dim= (test_cfg of 'whole_dim_cut')")
-    if dim is not None and ori_shape is not None:
-        raise RuntimeError("mmsa.whole_class_map: the whole_dim modes rescale to dim=, not to ori_shape=; give one of them")
-    if dim is not None and cut_dim is None and not rescale:
-        raise RuntimeError("mmsa.whole_class_map: 'whole_dim' with rescale=False has no defined result in the reference (encoder_decoder.py:334-346 "
-                           "returns None); use ori_shape= / no target, or dim= with cut_dim=")
-    src = rgb = None
+    rgb = None
     if preprocess is not None:
-        rgb, aux = _raw(preprocess, img, "whole_class_map")[:2]
+        rgb, aux, B, H, W = _raw(preprocess, img, "whole_class_map")
+    else:
+        _check(img)
+        B, _, H, W = (int(v) for v in img.shape)
+    plan = MapPlan.whole(B, H, W, ori_shape, dim, cut_dim, rescale)
+    src = None if render is None else whole_source(render, rgb, plan, return_map, "whole_class_map")      # the raw frames, or None: the tensor below
+    if preprocess is not None:
         img = preprocess(rgb, aux)
-    _check(img)
-    H, W = int(img.shape[2]), int(img.shape[3])
-    tgt = _target((dim if dim is not None else ori_shape) if rescale else None, H, W, "whole_class_map")
-    Hd, Wd = tgt or (H, W)
-    Ho, Wo = (min(int(cut_dim[1]), Hd), min(int(cut_dim[0]), Wd)) if cut_dim is not None else (Hd, Wd)
-    if Ho < 1 or Wo < 1:
-        raise RuntimeError(f"mmsa.whole_class_map: cut_dim {tuple(cut_dim)} leaves nothing of the map")
-    rs = None if (Ho, Wo) == (H, W) and tgt is None else (Hd, Wd, Ho, Wo)
-    if render is not None and rgb is not None:
-        from .render import raw_source
-        src = raw_source(rgb, Hd, Wd)
-    if render is not None and src is None and tgt is not None:
-        raise RuntimeError(f"mmsa.whole_class_map: render= has no source for the picture: the class map is rescaled to {Hd} x {Wd}, the input tensor is "
-                           f"{H} x {W} (raw uint8 frames of the map's size, with preprocess=, are needed)")
-    if render is not None:
-        if not return_map:
-            raise RuntimeError("mmsa.whole_class_map: render= paints the stored map; drop return_map=False")
-        if src is None:
-            if render.preprocess is None:
-                raise RuntimeError("mmsa.whole_class_map: render= on the normalised tensor needs the Renderer made with preprocess= (mean, std, to_rgb, norm_by_max)")
-            src = img = img.contiguous()
+    if render is not None and src is None:
+        src = img = img.contiguous()
     _pair(backbone, head)
     feats, _ = backbone(img)
     lg = head(feats)
-    B = img.shape[0]
-    tab = (ctypes.c_int * (3 * B))(*[v for b in range(B) for v in (b, 0, 0)])
-    out = torch.empty(B, Ho, Wo, dtype=torch.uint8, device=img.device)
+    out = torch.empty(B, plan.Ho, plan.Wo, dtype=torch.uint8, device=img.device)
     unc = torch.zeros(1, dtype=torch.int32, device=img.device)
-    _class_map(lg, B, tab, out, B, H, W, H, W, unc, labels, evaluator, case, fused, return_map, rs=rs, one_pass=one_pass)
+    plan.class_map(lg, out, unc, labels, evaluator, case, fused, return_map, one_pass)
     if render is not None:
         return out, render(out, src)
     return out if return_map else None
@@ -395,11 +429,7 @@ def whole_inference_dim(backbone, head, img, dim, rescale=True):
         raise RuntimeError("mmsa.whole_inference_dim: rescale=False has no defined result in the reference (encoder_decoder.py:334-346 "
                            "returns None); use whole_inference or whole_inference_dim_cut")
     y = encode_decode(backbone, head, img)
-    if tuple(dim) == tuple(y.shape[2:]):
-        return y                      # the second resize is the identity (align_corners=False, same size)
-    out = torch.empty(y.shape[0], y.shape[1], dim[0], dim[1], device=y.device)
-    _resize_into(y, out, 0, 0, dim[0], dim[1])
-    return out
+    return _rescaled_logits(y, _target(dim, y.shape[2], y.shape[3], "whole_inference_dim"))      # `dim` = the input size: y itself, no copy
 
 
 @_on_device
@@ -408,10 +438,7 @@ def whole_inference_dim_cut(backbone, head, img, dim, cut_dim, rescale=True):
     """ED:364-413 -- `test_cfg.mode = 'whole_dim_cut'`, the test mode of every FMB config (rescale=False, dim=(600,800), cut_dim=(800,600)):
     the logits at input size, resized to `dim` when `rescale`, cropped to [:, :, :cut_dim[1], :cut_dim[0]] (a contiguous copy)."""
     y = encode_decode(backbone, head, img)
-    if rescale and tuple(dim) != tuple(y.shape[2:]):
-        out = torch.empty(y.shape[0], y.shape[1], dim[0], dim[1], device=y.device)
-        _resize_into(y, out, 0, 0, dim[0], dim[1])
-        y = out
+    y = _rescaled_logits(y, _target(dim, y.shape[2], y.shape[3], "whole_inference_dim_cut") if rescale else None)
     return y[:, :, :cut_dim[1], :cut_dim[0]].contiguous()
 
 
@@ -515,50 +542,25 @@ class SlideRunner:
     mmsa_slide_argmax_resized in place of mmsa_slide_argmax, or the canvas path with `one_pass=False`)."""
 
     def __init__(self, backbone, head, frame, crop_size, stride, chains=2, check_every=1, preprocess=None, render=None, ori_shape=None, one_pass=None):
-        import ctypes
         from .chains import Chains
-        self.preprocess = preprocess
-        if preprocess is not None:
-            rgb, aux, B, H, W = _raw(preprocess, frame, "SlideRunner")
-            self.frame = (rgb, aux)
-            self.device = rgb.device
-        else:
-            _check(frame)
-            self.frame = frame.contiguous()
-            B, _, H, W = self.frame.shape
-            self.device = self.frame.device
-        self.render = render
-        self.size = (H, W)
-        self.one_pass = one_pass
-        tgt = _target(ori_shape, H, W, "SlideRunner")
-        self.rs = None if tgt is None else (tgt[0], tgt[1], tgt[0], tgt[1])
-        Ho, Wo = tgt or (H, W)
-        _picture_source(render, preprocess, self.frame, Ho, Wo, True, "SlideRunner", rescaled=tgt is not None)      # refuses a frame the picture has no source for
+        self.preprocess, self.render, self.one_pass = preprocess, render, one_pass
+        B, H, W, self.device, self.frame, self._cut = _intake(frame, preprocess, "SlideRunner")
+        self.plan = plan = MapPlan.slide(B, H, W, tuple(crop_size), stride, ori_shape, what="SlideRunner")
+        if render is not None:
+            slide_source(render, preprocess, self.frame, plan, True, "SlideRunner")      # refuses a frame the picture has no source for
         _pair(backbone, head)
-        self.crop_size = tuple(crop_size)
-        boxes = crop_boxes(H, W, crop_size, stride)
-        _check_overlap(boxes, "SlideRunner")
-        self.jobs = [(b, box) for box in boxes for b in range(B)]      # the accumulation order of slide_inference
-        n = len(self.jobs)
-        if n > 64:
-            raise RuntimeError("mmsa.SlideRunner: at most 64 windows per frame batch")
-        if n % chains:
+        plan.check_windows("SlideRunner", per="frame batch")
+        if plan.n % chains:
             chains = 1
         with torch.cuda.device(self.device):
-            self.crops = self._cut(self.frame)          # also the static input buffer of the chains
+            self.crops = self._cut(plan.windows)          # also the static input buffer of the chains
             self.chains = Chains(backbone, head, n=chains, check_every=check_every).capture(self.crops)
-            self.tab = (ctypes.c_int * (3 * n))(*[v for b, (y1, x1, _, _) in self.jobs for v in (b, y1, x1)])
-            self.out = torch.empty(B, Ho, Wo, dtype=torch.uint8, device=self.device)
+            self.out = torch.empty(B, plan.Ho, plan.Wo, dtype=torch.uint8, device=self.device)
             self.unc = torch.zeros(1, dtype=torch.int32, device=self.device)
             self.pic = None
             if render is not None:
                 render.palette_on(self.device)
-                self.pic = torch.empty(B, Ho, Wo, 3, dtype=torch.uint8, device=self.device)
-
-    def _cut(self, frame, out=None):
-        if self.preprocess is not None:
-            return self.preprocess.crops(frame[0], frame[1], self.jobs, self.crop_size, out=out)
-        return _crops(frame, self.jobs, self.crop_size, out=out)
+                self.pic = torch.empty(B, plan.Ho, plan.Wo, 3, dtype=torch.uint8, device=self.device)
 
     @torch.no_grad()
     def run(self, frame=None, labels=None, evaluator=None, case=None, fused=None, return_map=True):
@@ -567,7 +569,7 @@ class SlideRunner:
         no device sync; a frame that scored logits beyond the fp16 range raises mmsa.chains.AttentionRangeError from outputs() -- or from the next run(),
         whichever comes first -- after the blocks concerned have been moved to fp16 hi/lo pairs and the graphs captured again: run that frame again.
         `labels=` + `evaluator=` (mmsa.evaluate.Evaluator, best one made with cases=[...] and device=; `case=`): the frame's confusion counts are ADDED to the
-        evaluator on device (see _class_map); a frame that has to be run again has been counted, so reset the evaluator or subtract what it added.
+        evaluator on device (see MapPlan.class_map); a frame that has to be run again has been counted, so reset the evaluator or subtract what it added.
         `return_map=False` (always the fused launch) leaves the runner's map buffer untouched; the FrameResult's map is then None."""
         if frame is None:
             frame = self.frame
@@ -577,15 +579,13 @@ class SlideRunner:
             frame = self.preprocess.check(*frame)
             if any(f.shape != s.shape or f.dtype != s.dtype or f.device != s.device for f, s in zip(frame, self.frame)):
                 raise RuntimeError("mmsa.SlideRunner.run(frame=...): the pair must have the shape, dtypes and device of the runner's own buffers")
-        src = _picture_source(self.render, self.preprocess, frame, self.out.shape[1], self.out.shape[2], return_map, "SlideRunner.run", rescaled=self.rs is not None)
+        src = None if self.render is None else slide_source(self.render, self.preprocess, frame, self.plan, return_map, "SlideRunner.run")
         with torch.cuda.device(self.device):
-            self._cut(frame, out=self.crops)
+            self._cut(self.plan.windows, out=self.crops, frame=frame)
             rp = self.chains.replay()
             lg = rp.unverified          # the argmax kernel below is enqueued behind the pass; nothing is read on the host before outputs() verifies it
-            B, (H, W) = self.out.shape[0], self.size
             self.unc.zero_()
-            _class_map(lg, len(self.jobs), self.tab, self.out, B, H, W, self.crop_size[0], self.crop_size[1], self.unc, labels, evaluator, case, fused,
-                       return_map, rs=self.rs, one_pass=self.one_pass)
+            self.plan.class_map(lg, self.out, self.unc, labels, evaluator, case, fused, return_map, self.one_pass)
             if self.render is not None:
                 self.render(self.out, src, out=self.pic)
         return FrameResult(self, rp, has_map=return_map)

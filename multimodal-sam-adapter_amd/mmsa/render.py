@@ -132,10 +132,17 @@ def raw_source(rgb, H, W):
     return None
 
 
-def slide_source(render, preprocess, frame, H, W, what):
-    """The source of the picture in the slide modes, where no full-size normalised tensor exists with raw frames: the raw uint8 frame of the map's size, or the
-    normalised frame itself.  A raw frame of another size (padded, or resized on device) or dtype is refused by name."""
+def slide_source(render, preprocess, frame, plan, return_map, what):
+    """The source `render=` paints over in the slide modes, where no full-size normalised tensor exists with raw frames: the raw uint8 frame of the map's
+    size, or the normalised frame itself.  `plan`: the frame's mmsa.inference.MapPlan.  A raw frame of another size (padded, or resized on device) or
+    dtype, and a normalised frame under a map rescaled to another size, are refused by name; every refusal comes before any launch."""
+    H, W = plan.Ho, plan.Wo
+    if not return_map:
+        raise RuntimeError(f"mmsa.{what}: render= paints the stored map; drop return_map=False")
     if preprocess is None:
+        if plan.rescaled:
+            raise RuntimeError(f"mmsa.{what}: render= has no source for the picture: the class map is rescaled to {H} x {W}, the normalised frame has another size "
+                               "(raw uint8 frames of the map's size, with preprocess=, are needed)")
         if render.preprocess is None:
             raise RuntimeError(f"mmsa.{what}: render= on a normalised frame needs the Renderer made with preprocess= (mean, std, to_rgb, norm_by_max)")
         return frame
@@ -144,4 +151,19 @@ def slide_source(render, preprocess, frame, H, W, what):
         raise RuntimeError(f"mmsa.{what}: render= has no source for the picture: the raw frame is {frame[0].dtype} {int(frame[0].shape[1])} x {int(frame[0].shape[2])}, "
                            f"the class map {H} x {W}, and slide mode never writes the full-size normalised frame (uint8 frames of the map's size are needed; "
                            "Resize_multimodal on device / Pad_multimodal / a float32 RGB modality are not)")
+    return src
+
+
+def whole_source(render, rgb, plan, return_map, what):
+    """The source in the whole modes -> the raw uint8 frames `rgb` (None without `preprocess=`) where they have the size of the map before its cut, else
+    None: the caller paints over the normalised tensor the backbone reads, which exists here -- a padded or device-resized frame, a float32 RGB
+    modality, no `preprocess=`.  That tensor is no source for a map resized to another size (a cut alone is fine: its top-left is used)."""
+    src = None if rgb is None else raw_source(rgb, plan.Hd, plan.Wd)
+    if src is None and plan.resized:
+        raise RuntimeError(f"mmsa.{what}: render= has no source for the picture: the class map is rescaled to {plan.Hd} x {plan.Wd}, the input tensor is "
+                           f"{plan.H} x {plan.W} (raw uint8 frames of the map's size, with preprocess=, are needed)")
+    if not return_map:
+        raise RuntimeError(f"mmsa.{what}: render= paints the stored map; drop return_map=False")
+    if src is None and render.preprocess is None:
+        raise RuntimeError(f"mmsa.{what}: render= on the normalised tensor needs the Renderer made with preprocess= (mean, std, to_rgb, norm_by_max)")
     return src

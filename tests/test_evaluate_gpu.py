@@ -316,14 +316,14 @@ def test_class_map_launch_without_a_map_writes_none():
     lg = torch.randn(2, C, 16, 16, generator=g).to(DEV)
     _, label = ER.make_case(44, 64, 64, C, B=2)
     lab = torch.from_numpy(label).to(DEV)
-    tab = _windows([(0, 0, 0), (1, 0, 0)])
+    plan = inf.MapPlan.whole(2, 64, 64)
     unc = torch.zeros(1, dtype=torch.int32, device=DEV)
     out = torch.full((2, 64, 64), 77, dtype=torch.uint8, device=DEV)
     ev = Evaluator(LabelPrep(C))
-    inf._class_map(lg, 2, tab, out, 2, 64, 64, 64, 64, unc, lab, ev, None, None, False)
+    plan.class_map(lg, out, unc, lab, ev, return_map=False)
     torch.cuda.synchronize()
     assert bool((out == 77).all())
     ev2 = Evaluator(LabelPrep(C))
-    inf._class_map(lg, 2, tab, out, 2, 64, 64, 64, 64, unc, lab, ev2, None, True, True)
+    plan.class_map(lg, out, unc, lab, ev2, fused=True, return_map=True)
     assert not bool((out == 77).all()) and np.array_equal(ev.host_counts(), ev2.host_counts())
     assert np.array_equal(ev.host_counts(), _ref_counts(out.cpu().numpy(), label, C))

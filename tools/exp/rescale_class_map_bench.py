@@ -7,7 +7,6 @@ rotated), `--inner` calls per timing between two events on the launch stream, fr
 Shapes: the six-window 1080 x 1920 frame at 25 classes rescaled up to (1200, 2133) and down to (810, 1440); two 1024 x 1024 whole frames to (1042, 1042).
 Every (o) map is checked against (c) bit for bit first."""
 import argparse
-import ctypes
 import os
 import sys
 
@@ -38,21 +37,18 @@ def main():
         lines.append(s)
 
     say(f"device {torch.cuda.get_device_name(0)}; reps {a.reps}, {a.inner} calls per timing; times in microseconds per call")
-    cases = [("slide 1080 x 1920, six 1024 x 1024 windows", 1, 1080, 1920, inf.crop_boxes(1080, 1920, (1024, 1024), (640, 640)), (1200, 2133)),
-             ("slide 1080 x 1920, six 1024 x 1024 windows", 1, 1080, 1920, inf.crop_boxes(1080, 1920, (1024, 1024), (640, 640)), (810, 1440)),
-             ("whole 2 x 1024 x 1024", 2, 1024, 1024, [(0, 0, 1024, 1024)], (1042, 1042))]
-    for name, B, H, W, boxes, (Hd, Wd) in cases:
-        wins = [(b, y1, x1) for (y1, x1, _, _) in boxes for b in range(B)]
-        n = len(wins)
-        tab = (ctypes.c_int * (3 * n))(*[v for w in wins for v in w])
+    slide = lambda ori: inf.MapPlan.slide(1, 1080, 1920, (1024, 1024), (640, 640), ori_shape=ori)
+    cases = [("slide 1080 x 1920, six 1024 x 1024 windows", slide((1200, 2133))), ("slide 1080 x 1920, six 1024 x 1024 windows", slide((810, 1440))),
+             ("whole 2 x 1024 x 1024", inf.MapPlan.whole(2, 1024, 1024, ori_shape=(1042, 1042)))]
+    for name, plan in cases:
+        B, H, W, Hd, Wd, n, tab = plan.B, plan.H, plan.W, plan.Hd, plan.Wd, plan.n, plan.tab
         g = torch.Generator().manual_seed(7)
         coarse = torch.randn(n, C, 32, 32, generator=g)
         lg = (torch.nn.functional.interpolate(coarse, size=(256, 256), mode="bilinear") + 0.05 * torch.randn(n, C, 256, 256, generator=g)).to(dev)
-        rs = (Hd, Wd, Hd, Wd)
         out = {k: torch.empty(B, Hd, Wd, dtype=torch.uint8, device=dev) for k in "co"}
         same = torch.empty(B, H, W, dtype=torch.uint8, device=dev)
         unc = torch.zeros(1, dtype=torch.int32, device=dev)
-        legs = dict(c=lambda: inf._rescaled_map_canvas(lg, n, tab, out["c"], B, H, W, 1024, 1024, unc, rs),
+        legs = dict(c=lambda: inf._rescaled_map_canvas(plan, lg, out["c"], unc),
                     o=lambda: lib.call("mmsa_slide_argmax_resized", lg.data_ptr(), n, C, 256, 256, tab, out["o"].data_ptr(), B, H, W, 1024, 1024, Hd, Wd, Hd, Wd,
                                        unc.data_ptr(), ops._stream()),
                     y=lambda: lib.call("mmsa_slide_argmax", lg.data_ptr(), n, C, 256, 256, tab, same.data_ptr(), B, H, W, 1024, 1024, unc.data_ptr(), ops._stream()))
