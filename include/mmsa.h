@@ -353,6 +353,23 @@ int mmsa_slide_argmax(const float* logits, int n, int C, int hs, int ws, const i
 int mmsa_slide_argmax_resized(const float* logits, int n, int C, int hs, int ws, const int* windows, unsigned char* out, int B, int H, int W,
                               int hc, int wc, int Hd, int Wd, int Hcut, int Wcut, int* uncovered, mmsa_stream_t stream);
 
+/* --- test-time augmentation (EncoderDecoder.aug_test, ED:509-546): several views of a frame -- flipped, at several scales -- whose PROBABILITIES are
+ *     averaged before the argmax.
+ * the canvas-path step: p = softmax over C of logits [B, C, H, W] (F.softmax(seg_logit, dim=1), ED:449,460: m = max, e = expf(x - m), s = sum in class
+ * order, p = e / s), flipped back (flip 1 = 'horizontal': x' = W - 1 - x, ED:454-455,465-466; 2 = 'vertical': y' = H - 1 - y, ED:456-457,467-468; 0: not
+ * flipped) and written (accumulate = 0) or added (seg_logit += cur_seg_logit, ED:540) to acc [B, C, H, W]; finish_div > 0: the stored value is also
+ * divided by it (seg_logit /= len(imgs), ED:541).  acc must not alias logits. */
+int mmsa_softmax_flip_accum_nchw(const float* logits, float* acc, int B, int C, int H, int W, int flip, int accumulate, int finish_div, mmsa_stream_t stream);
+/* the whole of aug_test after the head in ONE launch (ED:517, 538-542): out uint8 [B, Ho, Wo] = first argmax_c of the mean over the A views (1..12), in
+ * view order, of the softmax of view a's logits at the pixel's mirror image (that view's flip) -- the logits mmsa_slide_argmax_resized computes there from
+ * the view's head-resolution logits.  logits: HOST array of A device pointers, view a's being [n_a, C, hs_a, ws_a]; views: HOST int [A, 11] rows
+ * (w0, n, hs, ws, H, W, hc, wc, Hd, Wd, flip): view a's windows are rows w0 .. w0 + n - 1 (n <= 64) of `windows`, a DEVICE int [total, 3] array of
+ * (image, y0, x0) owned by the caller, with `windows_host` its HOST copy (validated here); H x W the view's canvas, hc x wc its window size, Hd x Wd its
+ * rescale target (H x W: none), of which [:Ho, :Wo] is kept.  Bit for bit mmsa_argmax_nchw of the mmsa_softmax_flip_accum_nchw canvas path.  C <= 128 (two
+ * columns of C floats per pixel in LDS).  A pixel where any view has a tap that no window covers (or more than 8 do) gets 255 and is counted once in `uncovered`. */
+int mmsa_aug_argmax(const float* const* logits, const int* views, int A, int C, const int* windows, const int* windows_host, int total,
+                    unsigned char* out, int B, int Ho, int Wo, int* uncovered, mmsa_stream_t stream);
+
 /* --- the input side of the test pipelines (segmentation/mmseg_custom/datasets/pipelines/transform.py): Pad_multimodal (2934-3010, impad bottom /
  *     right) -> Normalize_multimodal / Normalize_multimodal_Muses (2601-2825: `/ 255` when norm_by_max, mmcv.imnormalize = channel reversal when
  *     to_rgb, subtract mean, multiply by 1 / float64(std)) -> ImageToTensor (HWC -> CHW) -> Collectmod, from the loaders' frames in one pass.

@@ -13,6 +13,7 @@
 // (slide_argmax) must round the SAME interpolation formula identically, or an exact tie between two classes in one of them is not a
 // tie in the other (seen once in 2 073 600 pixels of a 1080 x 1920 frame, where the compiler had contracted the two differently).
 #pragma clang fp contract(off)
+#include "slide_taps.h"   // WindowTable and the tap arithmetic of the rescaled class map (shared with augment.hip)
 
 __global__ __launch_bounds__(256) void bilinear_accum_kernel(const float* __restrict__ src, int C, int hs, int ws, long sstrideB,
                                                              float* __restrict__ dst, int Hd, int Wd, int y0, int x0, int hc, int wc,
@@ -88,9 +89,6 @@ extern "C" int mmsa_argmax_nchw(const float* x, unsigned char* out, int B, int C
 
 // ---- crop extraction of slide inference (ED:205-212: crop_img = img[:, :, y1:y2, x1:x2]) as one launch for a batch of windows:
 // dst[k] = src[b_k, :, y0_k : y0_k + hc, x0_k : x0_k + wc].  The window table travels by value in the launch arguments.
-#define MMSA_MAX_WINDOWS 64
-struct WindowTable { int n; int b[MMSA_MAX_WINDOWS], y0[MMSA_MAX_WINDOWS], x0[MMSA_MAX_WINDOWS]; };
-
 __global__ __launch_bounds__(256) void crop_batch_kernel(const float* __restrict__ src, int C, int H, int W, float* __restrict__ dst,
                                                          int hc, int wc, WindowTable wt) {
   const int k = blockIdx.z, c = blockIdx.y / hc, i = blockIdx.y - c * hc;
@@ -205,64 +203,7 @@ extern "C" int mmsa_slide_argmax_eval(const float* logits, int n, int C, int hs,
 // with its own covering windows and its own count.  Both stages are the file's formula in the file's operation order (no contraction, see the top), so
 // the map equals bilinear_accum + div_count + bilinear_accum + argmax + crop bit for bit.  A pixel with a tap that no window covers, or more than 8
 // windows, gets 255 and is counted in `uncovered`.
-// Registers: four taps with the eight slots of slide_pixel.inc would need 4 x 56 (the first form did: 372 registers, one wave per SIMD).  Here a tap
-// keeps RESIZED_SLOTS = 4 windows, each packed to four registers (offset of the top-left logit, window index | "has a row below" << 8 | "has a column
-// to the right" << 9, the two weights); a pixel with a tap under 5 .. 8 windows (strides below half the crop) takes the scanning form instead, which walks
-// the window table again for every class and keeps nothing.  Same terms, same order, same bits either way.
-#define RESIZED_SLOTS 4
-struct TapSlots { int nk; int o[RESIZED_SLOTS], kf[RESIZED_SLOTS]; float lh[RESIZED_SLOTS], lw[RESIZED_SLOTS]; };
-
-// window k of image b over canvas pixel (ty, tx)?  -> its 4-tap coordinates in the window's logits, as slide_pixel.inc computes them
-__device__ __forceinline__ bool tap_coords(const WindowTable& wt, int k, int b, int ty, int tx, int hc, int wc, int hs, int ws, float rh, float rw,
-                                           int& o, int& kf, float& lh, float& lw) {
-  if (wt.b[k] != b) return false;
-  const int i = ty - wt.y0[k], j = tx - wt.x0[k];
-  if (i < 0 || i >= hc || j < 0 || j >= wc) return false;
-  float sh = ((float)i + 0.5f) * rh - 0.5f, sw = ((float)j + 0.5f) * rw - 0.5f;
-  sh = sh < 0.f ? 0.f : sh;
-  sw = sw < 0.f ? 0.f : sw;
-  const int h0 = min((int)sh, hs - 1), w0 = min((int)sw, ws - 1);
-  o = h0 * ws + w0;
-  kf = k | (h0 < hs - 1 ? 256 : 0) | (w0 < ws - 1 ? 512 : 0);
-  lh = sh - (float)h0;
-  lw = sw - (float)w0;
-  return true;
-}
-
-// one window's term of a canvas pixel: the interpolation of bilinear_accum_kernel / slide_pixel.inc
-__device__ __forceinline__ float tap_term(const float* __restrict__ logits, int C, int c, int hs, int ws, int o, int kf, float lh, float lw) {
-  const int dh = (kf >> 8) & 1 ? ws : 0, dw = (kf >> 9) & 1;
-  const float* sp = logits + ((long)(kf & 255) * C + c) * hs * ws + o;
-  return (1.f - lh) * ((1.f - lw) * sp[0] + lw * sp[dw]) + lh * ((1.f - lw) * sp[dh] + lw * sp[dh + dw]);
-}
-
-__device__ __forceinline__ float tap_value(const TapSlots& t, const float* __restrict__ logits, int C, int c, int hs, int ws) {
-  float acc = 0.f;
-#pragma unroll
-  for (int q = 0; q < RESIZED_SLOTS; ++q) {
-    if (q < t.nk) {
-      const float v = tap_term(logits, C, c, hs, ws, t.o[q], t.kf[q], t.lh[q], t.lw[q]);
-      acc = q == 0 ? v : acc + v;     // window order: the first window WRITES (0 + v == v), later ones add
-    }
-  }
-  return acc / (float)t.nk;
-}
-
-__device__ __forceinline__ float tap_value_scan(const WindowTable& wt, int b, int ty, int tx, int nk, const float* __restrict__ logits, int C, int c,
-                                                int hs, int ws, int hc, int wc, float rh, float rw) {
-  float acc = 0.f;
-  bool first = true;
-  for (int k = 0; k < wt.n; ++k) {
-    int o, kf;
-    float lh, lw;
-    if (!tap_coords(wt, k, b, ty, tx, hc, wc, hs, ws, rh, rw, o, kf, lh, lw)) continue;
-    const float v = tap_term(logits, C, c, hs, ws, o, kf, lh, lw);
-    acc = first ? v : acc + v;
-    first = false;
-  }
-  return acc / (float)nk;
-}
-
+// The taps (TapSlots, tap_coords, tap_term, tap_value, tap_value_scan; why a tap keeps four windows in registers): csrc/slide_taps.h.
 __global__ __launch_bounds__(256) void slide_argmax_resized_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
                                                                    int H, int W, int hc, int wc, float rh, float rw, int Hcut, int Wcut, float rh2, float rw2,
                                                                    WindowTable wt, int* __restrict__ uncovered) {

@@ -7,6 +7,9 @@
 The crops of a sliding-window frame are batched through ONE backbone + head call (the reference runs them one by one,
 ED:205-214), and the resize / pad / accumulate / count of every crop is one kernel launch on the logits canvas.
 
+Test-time augmentation (`aug_test`, ED:509-546): `probabilities` (the softmax and un-flip of ED:448-469), `aug_inference` (the mean over the views, on
+canvases), `aug_class_map` (its argmax, from the canvas path or from ONE launch after the head, mmsa_aug_argmax) and `AugPlan`, the MapPlan of several views.
+
 What a frame's output looks like -- its windows, the size after the second resize and after the cut, which class-map kernel that takes -- is decided once,
 in `MapPlan`, a record without device state; the entries read the frame (`_intake`), make the plan, and launch from it."""
 import ctypes
@@ -319,10 +322,10 @@ class MapPlan:
             evaluator.add(out, labels, case=case)
 
 
-def _rescaled_map_canvas(plan, lg, out, unc):
-    """The rescaled class map the long way round, from the head-resolution logits lg [n, C, hs, ws] and the plan's windows: canvas (accumulate, count,
-    divide), second canvas, argmax, crop -- the launches slide_inference / encode_decode + argmax_map make.  `unc` gets the number of CANVAS pixels that no
-    window covers (non-zero exactly when the one-pass kernel's count of output pixels may be)."""
+def _canvas_logits(plan, lg, unc):
+    """The logits of a plan at its target size the long way round, from the head-resolution logits lg [n, C, hs, ws] and the plan's windows: canvas
+    (accumulate, count, divide), second canvas -> [B, C, Hd, Wd] -- the launches slide_inference / encode_decode make.  `unc` gets the number of CANVAS
+    pixels that no window covers (non-zero exactly when the one-pass kernels' count of output pixels may be)."""
     B, H, W, C = plan.B, plan.H, plan.W, lg.shape[1]
     canvas = torch.zeros(B, C, H, W, device=lg.device)
     count = torch.zeros(B, H, W, device=lg.device)
@@ -330,7 +333,12 @@ def _rescaled_map_canvas(plan, lg, out, unc):
         _resize_into(lg[k:k + 1], canvas[b:b + 1], y0, x0, plan.hc, plan.wc, count=count[b:b + 1], accumulate=True)
     unc.add_((count == 0).sum().to(torch.int32))
     lib.call("mmsa_div_count_nchw", canvas.data_ptr(), count.data_ptr(), B, C, H * W, ops._stream())
-    full = argmax_map(_rescaled_logits(canvas, (plan.Hd, plan.Wd) if plan.resized else None))
+    return _rescaled_logits(canvas, (plan.Hd, plan.Wd) if plan.resized else None)
+
+
+def _rescaled_map_canvas(plan, lg, out, unc):
+    """The rescaled class map the long way round: _canvas_logits, argmax, crop -- the launches slide_inference / encode_decode + argmax_map make."""
+    full = argmax_map(_canvas_logits(plan, lg, unc))
     out.copy_(full[:, :plan.Ho, :plan.Wo])
 
 
@@ -444,18 +452,19 @@ def whole_inference_dim_cut(backbone, head, img, dim, cut_dim, rescale=True):
 
 @_on_device
 @torch.no_grad()
-def inference(backbone, head, img, test_cfg, rescale=True, preprocess=None, ori_shape=None):
+def inference(backbone, head, img, test_cfg, rescale=True, preprocess=None, ori_shape=None, max_batch=8):
     """ED:417-447 dispatch on `test_cfg['mode']` -- 'slide', 'whole', 'whole_dim', 'whole_dim_cut' ('slide_mod_sel' runs the segmentor's
     modality-selection variant, ED:236-308, which needs a backbone with a selection head: not this backbone) -- returning the logits the
-    reference softmaxes (ED:448-470; flips are the caller's, as in the reference's test pipeline).
+    reference softmaxes (ED:448-470; `probabilities` is that softmax and the un-flip; the views come flipped from the caller, as from the reference's test
+    pipeline).  `max_batch`: the windows of 'slide' per backbone call.
     `preprocess=` (mmsa.preprocess.Preprocess): img is the pair (rgb, aux) of raw frames -- 'slide' cuts its windows from them, the whole modes
     normalise the frame first.
     `ori_shape=` (h, w[, 3]) of the frame's meta: with `rescale`, 'slide' and 'whole' resize their logits to it (ED:227-233, 314-325); the `whole_dim*`
     modes rescale to `test_cfg['dim']` and ignore it, as the reference does."""
     mode = test_cfg["mode"]
     if mode == "slide":
-        return slide_inference(backbone, head, img, tuple(test_cfg["crop_size"]), tuple(test_cfg["stride"]), preprocess=preprocess, rescale=rescale,
-                               ori_shape=ori_shape)
+        return slide_inference(backbone, head, img, tuple(test_cfg["crop_size"]), tuple(test_cfg["stride"]), max_batch=max_batch, preprocess=preprocess,
+                               rescale=rescale, ori_shape=ori_shape)
     if preprocess is not None and mode in ("whole", "whole_dim", "whole_dim_cut"):
         img = preprocess(*_raw(preprocess, img, "inference")[:2])
     if mode == "whole":
@@ -502,6 +511,269 @@ def argmax_map(seg_logit):
     out = torch.empty(B, H, W, dtype=torch.uint8, device=seg_logit.device)
     lib.call("mmsa_argmax_nchw", seg_logit.data_ptr(), out.data_ptr(), B, C, H * W, ops._stream())
     return out
+
+
+# ---- test-time augmentation: EncoderDecoder.aug_test (ED:509-546) -- several views of a frame (flipped, at several scales), whose probabilities are averaged
+
+MAX_AUGS = 12          # views per call: MMSA_MAX_AUGS of csrc/augment.hip (their descriptors travel in the launch arguments)
+MAX_AUG_CLASSES = 128  # classes mmsa_aug_argmax keeps per pixel in LDS; more take the canvas path
+FLIPS = {None: 0, "horizontal": 1, "vertical": 2}      # img_meta's flip / flip_direction (ED:450-457) -> the kernels' code
+
+# Which launch makes an AUGMENTED class map by default: True = the one-pass kernel (mmsa_aug_argmax), False = the canvas path (per view: canvas, second
+# resize, mmsa_softmax_flip_accum_nchw; then argmax_map -- the same map bit for bit).  `one_pass=` of aug_class_map overrides it.
+# Measured (profiles/aug_class_map.txt; 1080 x 1920, six 1024 x 1024 windows, 25 classes): the canvas path wins, 1.9 ms against 7.1 ms for two views and
+# 4.9 ms against 8.4 ms for four, far outside its 0.02 - 0.04 ms spread -- the canvases stay in the 256 MB last-level cache, while the one-pass kernel runs
+# two waves per SIMD and its pixels under 5 .. 8 windows walk the window table once per class.  One pass remains the choice where memory is: it allocates
+# nothing, the canvas path three [B, C, h, w] float32 arrays per view (207 MB each at that size).
+ONE_PASS_AUG_DEFAULT = False
+
+
+def _flip_code(flip, what):
+    if flip not in FLIPS:
+        raise RuntimeError(f"mmsa.{what}: flip must be None, 'horizontal' or 'vertical' (img_meta's flip_direction, encoder_decoder.py:453), got {flip!r}")
+    return FLIPS[flip]
+
+
+def _softmax_accum(logits, acc, flip=0, accumulate=False, finish_div=0):
+    """ED:448-469 + ED:540-541 on a logits canvas: acc (=|+=) flip(softmax(logits)) [/ finish_div]."""
+    B, C, H, W = logits.shape
+    lib.call("mmsa_softmax_flip_accum_nchw", logits.data_ptr(), acc.data_ptr(), B, C, H, W, flip, 1 if accumulate else 0, finish_div, ops._stream())
+
+
+def _plan_of(test_cfg, B, H, W, rescale, ori_shape, what):
+    """The MapPlan of one frame batch by `test_cfg['mode']`: the dispatch of `class_map` / `inference` (ED:417-447)."""
+    mode = test_cfg["mode"]
+    if mode == "slide":
+        return MapPlan.slide(B, H, W, tuple(test_cfg["crop_size"]), tuple(test_cfg["stride"]), ori_shape if rescale else None, what=what)
+    if mode == "whole":
+        return MapPlan.whole(B, H, W, ori_shape=ori_shape if rescale else None, what=what)
+    if mode == "whole_dim":
+        return MapPlan.whole(B, H, W, dim=tuple(test_cfg["dim"]), rescale=rescale, what=what)
+    if mode == "whole_dim_cut":
+        return MapPlan.whole(B, H, W, dim=tuple(test_cfg["dim"]), cut_dim=tuple(test_cfg["cut_dim"]), rescale=rescale, what=what)
+    raise RuntimeError(f"mmsa.{what}: test_cfg.mode '{mode}' is not one of slide / whole / whole_dim / whole_dim_cut")
+
+
+@_on_device
+@torch.no_grad()
+def probabilities(backbone, head, img, test_cfg, rescale=True, ori_shape=None, flip=None, preprocess=None, max_batch=8):
+    """What the reference's `inference` returns (ED:417-469): F.softmax(seg_logit, dim=1) of `inference(...)`'s logits, flipped back when the view `img`
+    was flipped (`flip` = None, 'horizontal' or 'vertical': img_meta's flip_direction) -> float32 [B, classes, Ho, Wo].  One more launch
+    (mmsa_softmax_flip_accum_nchw) on the logits; `inference` itself keeps returning logits."""
+    code = _flip_code(flip, "probabilities")
+    y = inference(backbone, head, img, test_cfg, rescale=rescale, preprocess=preprocess, ori_shape=ori_shape, max_batch=max_batch).contiguous()
+    out = torch.empty_like(y)
+    _softmax_accum(y, out, code)
+    return out
+
+
+@dataclasses.dataclass(frozen=True)
+class AugPlan:
+    """The MapPlan of several views of one frame batch (`aug_test`, ED:509-546), decided on the host: one MapPlan per view, made by the mode dispatch of
+    `class_map`, and the views' flips as the kernels' codes.  All views end at the same [B, Ho, Wo]: the probabilities are added pixel by pixel.
+    `table` is the window tables of all views one after the other (view a's rows: offsets[a] .. offsets[a] + plans[a].n - 1), built once; `table_on(device)`
+    uploads it on first use and keeps it, so a second call allocates and copies nothing.  `make` / `of` own the refusals of a set of views;
+    `class_map` is the launch."""
+    plans: tuple
+    flips: tuple
+
+    @staticmethod
+    def views(imgs, flips=None, preprocess=None, what="aug_class_map"):
+        """The three per-view lists of the entries, checked for their lengths -> (imgs, flips, preprocess objects), each a list of len(imgs); `preprocess`
+        may be one object for all views."""
+        if not isinstance(imgs, (list, tuple)):
+            raise RuntimeError(f"mmsa.{what}: imgs is the LIST of views (already flipped and resized by the caller), one tensor or (rgb, aux) pair each")
+        n = len(imgs)
+        flips = [None] * n if flips is None else list(flips)
+        pre = list(preprocess) if isinstance(preprocess, (list, tuple)) else [preprocess] * n
+        if len(flips) != n or len(pre) != n:
+            raise RuntimeError(f"mmsa.{what}: {n} imgs, {len(flips)} flips and {len(pre)} preprocess objects: the lists must have the same length")
+        return list(imgs), flips, pre
+
+    @classmethod
+    def make(cls, test_cfg, shapes, flips=None, ori_shape=None, rescale=True, what="aug_class_map"):
+        """`shapes`: (B, H, W) of every view's canvas; `flips`: None / 'horizontal' / 'vertical' per view (None: no view is flipped)."""
+        if not rescale:
+            raise RuntimeError(f"mmsa.{what}: only rescale=True is supported, as in the reference (encoder_decoder.py:515 asserts it): the views are added at one size")
+        shapes = [tuple(int(v) for v in s) for s in shapes]
+        if not 1 <= len(shapes) <= MAX_AUGS:
+            raise RuntimeError(f"mmsa.{what}: {len(shapes)} views; 1 .. {MAX_AUGS} per call")
+        flips = [None] * len(shapes) if flips is None else list(flips)
+        if len(flips) != len(shapes):
+            raise RuntimeError(f"mmsa.{what}: {len(shapes)} imgs and {len(flips)} flips: the lists must have the same length")
+        codes = tuple(_flip_code(f, what) for f in flips)
+        plans = tuple(_plan_of(test_cfg, B, H, W, True, ori_shape, what) for B, H, W in shapes)
+        sizes = [(p.B, p.Ho, p.Wo) for p in plans]
+        if any(s != sizes[0] for s in sizes):
+            raise RuntimeError(f"mmsa.{what}: the views end at different sizes (B, h, w) = {sizes}; their probabilities are added pixel by pixel -- "
+                               "give ori_shape= (the frame's size before the pipeline resized it), which every view is rescaled to")
+        for p in plans:
+            p.check_windows(what, per="view")
+        return cls(plans, codes)
+
+    @classmethod
+    def of(cls, test_cfg, shapes, flips=None, ori_shape=None, rescale=True, what="aug_class_map"):
+        """`make`, remembered per geometry: the same views give the same plan object, whose window table is already on the device."""
+        freeze = lambda v: tuple(freeze(x) for x in v) if isinstance(v, (list, tuple)) else v
+        key = (tuple(sorted((k, freeze(v)) for k, v in dict(test_cfg).items() if k in ("mode", "crop_size", "stride", "dim", "cut_dim"))),
+               freeze(shapes), None if flips is None else tuple(flips), None if ori_shape is None else freeze(ori_shape), bool(rescale))
+        try:
+            hash(key)
+        except TypeError:
+            return cls.make(test_cfg, shapes, flips, ori_shape, rescale, what)
+        plan = _AUG_PLANS.get(key)
+        if plan is None:
+            if len(_AUG_PLANS) >= 32:
+                _AUG_PLANS.clear()
+            plan = _AUG_PLANS[key] = cls.make(test_cfg, shapes, flips, ori_shape, rescale, what)
+        return plan
+
+    @property
+    def A(self):
+        return len(self.plans)
+
+    @property
+    def size(self):
+        """(B, Ho, Wo) of the class map, the same for every view."""
+        return self.plans[0].B, self.plans[0].Ho, self.plans[0].Wo
+
+    @functools.cached_property
+    def offsets(self):
+        """First row of every view's windows in `table`."""
+        out, at = [], 0
+        for p in self.plans:
+            out.append(at)
+            at += p.n
+        return tuple(out)
+
+    @property
+    def total(self):
+        return sum(p.n for p in self.plans)
+
+    @functools.cached_property
+    def table(self):
+        """The window tables (image, y0, x0) of all views, concatenated: host int [total, 3]."""
+        return (ctypes.c_int * (3 * self.total))(*[v for p in self.plans for job in p.jobs for v in job])
+
+    @functools.cached_property
+    def _on(self):
+        return {}
+
+    def table_on(self, device):
+        """`table` on `device`, uploaded by the first call (not inside a graph capture: run the entry once before capturing it)."""
+        key = str(torch.device(device))
+        if key not in self._on:
+            self._on[key] = torch.tensor(list(self.table), dtype=torch.int32).view(-1, 3).to(device)
+        return self._on[key]
+
+    def rows(self, lgs):
+        """The [A, 11] view rows of mmsa_aug_argmax (w0, n, hs, ws, H, W, hc, wc, Hd, Wd, flip) for the head-resolution logits `lgs` (shapes only)."""
+        return [(w0, p.n, int(lg.shape[2]), int(lg.shape[3]), p.H, p.W, p.hc, p.wc, p.Hd, p.Wd, f) for p, f, w0, lg in zip(self.plans, self.flips, self.offsets, lgs)]
+
+    def mean_probabilities(self, lgs, unc):
+        """The canvas path from the views' head-resolution logits: per view the logits at [B, C, Ho, Wo] (_canvas_logits + cut), softmax, un-flip and
+        add (mmsa_softmax_flip_accum_nchw), the last with the division by A -> float32 [B, C, Ho, Wo]."""
+        acc = None
+        for a, (p, f, lg) in enumerate(zip(self.plans, self.flips, lgs)):
+            y = _canvas_logits(p, lg, unc)[:, :, :p.Ho, :p.Wo].contiguous()
+            if acc is None:
+                acc = torch.empty_like(y)
+            _softmax_accum(y, acc, f, accumulate=a > 0, finish_div=self.A if a == self.A - 1 else 0)
+        return acc
+
+    def class_map(self, lgs, out, unc, one_pass=None):
+        """The class map of the views' head-resolution logits `lgs` (one [n_a, C, hs_a, ws_a] per view) into out uint8 [B, Ho, Wo] and the uncovered-pixel
+        word `unc`: ONE launch (mmsa_aug_argmax; no host sync, no allocation once the table is on the device) where `one_pass=True` / ONE_PASS_AUG_DEFAULT
+        say so and the classes fit the kernel (at most MAX_AUG_CLASSES), else the canvas path + argmax_map.  The same map bit for bit."""
+        if len(lgs) != self.A or any(lg.shape[0] != p.n for lg, p in zip(lgs, self.plans)):
+            raise RuntimeError("mmsa.inference: AugPlan.class_map takes one logits tensor per view, one row per window of that view")
+        C = int(lgs[0].shape[1])
+        if (ONE_PASS_AUG_DEFAULT and C <= MAX_AUG_CLASSES) if one_pass is None else one_pass:
+            lgs = [lg.contiguous() for lg in lgs]
+            ptrs = (ctypes.c_void_p * self.A)(*[lg.data_ptr() for lg in lgs])
+            rows = (ctypes.c_int * (11 * self.A))(*[v for r in self.rows(lgs) for v in r])
+            B, Ho, Wo = self.size
+            lib.call("mmsa_aug_argmax", ptrs, rows, self.A, C, self.table_on(out.device).data_ptr(), self.table, self.total, out.data_ptr(), B, Ho, Wo,
+                     unc.data_ptr(), ops._stream())
+        else:
+            out.copy_(argmax_map(self.mean_probabilities(lgs, unc)))
+
+
+_AUG_PLANS = {}
+
+
+def _aug_first_tensor(imgs):
+    v = imgs[0] if isinstance(imgs, (list, tuple)) and len(imgs) else None
+    return v[0] if isinstance(v, (list, tuple)) and len(v) else v
+
+
+def _on_views_device(fn):
+    """_on_device for the entries whose frames come as a list of views."""
+    @functools.wraps(fn)
+    def wrapped(backbone, head, imgs, *args, **kw):
+        t = _aug_first_tensor(imgs)
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            return fn(backbone, head, imgs, *args, **kw)
+        with torch.cuda.device(t.device):
+            return fn(backbone, head, imgs, *args, **kw)
+    return wrapped
+
+
+@_on_views_device
+@torch.no_grad()
+def aug_inference(backbone, head, imgs, test_cfg, ori_shape=None, flips=None, preprocess=None, max_batch=8):
+    """`aug_test` up to its argmax (ED:517, 538-541) on logits canvases: the mean over the views of `probabilities(view)` -> float32 [B, classes, Ho, Wo].
+    `imgs`: the views, normalised [B, 6, H_a, W_a] tensors -- or (rgb, aux) pairs of raw frames with `preprocess=` (one object, or one per view) -- ALREADY
+    flipped and resized by the caller, as the reference's test pipeline hands them over; `flips`: None / 'horizontal' / 'vertical' per view.
+    Per view: `inference`, then mmsa_softmax_flip_accum_nchw (write, then add; the last view's launch also divides by the number of views)."""
+    imgs, flips, pre = AugPlan.views(imgs, flips, preprocess, "aug_inference")
+    if not 1 <= len(imgs) <= MAX_AUGS:
+        raise RuntimeError(f"mmsa.aug_inference: {len(imgs)} views; 1 .. {MAX_AUGS} per call")
+    codes = [_flip_code(f, "aug_inference") for f in flips]
+    acc = None
+    for a, (img, f, p) in enumerate(zip(imgs, codes, pre)):
+        y = inference(backbone, head, img, test_cfg, rescale=True, preprocess=p, ori_shape=ori_shape, max_batch=max_batch).contiguous()
+        if acc is None:
+            acc = torch.empty_like(y)
+        elif y.shape != acc.shape:
+            raise RuntimeError(f"mmsa.aug_inference: view {a} ends at {tuple(y.shape)}, the first at {tuple(acc.shape)}; give ori_shape= (the frame's size "
+                               "before the pipeline resized it), which every view is rescaled to")
+        _softmax_accum(y, acc, f, accumulate=a > 0, finish_div=len(imgs) if a == len(imgs) - 1 else 0)
+    return acc
+
+
+@_on_views_device
+@torch.no_grad()
+def aug_class_map(backbone, head, imgs, test_cfg, ori_shape=None, flips=None, preprocess=None, max_batch=8, labels=None, evaluator=None, case=None,
+                  one_pass=None):
+    """`aug_test` (ED:509-546) -> (uint8 class map [B, Ho, Wo], uncovered-pixel word), bit for bit argmax_map(aug_inference(...)) of the same arguments.
+    Every view goes through backbone and head (`max_batch` windows per call, per view); then ONE launch (mmsa_aug_argmax) resizes every view's
+    head-resolution logits as `class_map` would, takes the softmax, un-flips, averages over the views and takes the argmax, with no logits or probability
+    canvas in memory (`one_pass=True`), or the canvas path runs from the same logits (`one_pass=False`, more than 128 classes, and -- being the faster of
+    the two where measured -- the default: ONE_PASS_AUG_DEFAULT).  No host sync either way; the one-pass launch is HIP-graph capturable once a first call
+    has put the plan's window table on the device.  unc[0] != 0 <=> some view's windows do not cover its frame (ED:220): checked by the caller.
+    `labels=` + `evaluator=` (+ `case=`): the map's confusion counts are added to the evaluator through the stored map, as at any rescaled size."""
+    if (labels is None) != (evaluator is None):
+        raise RuntimeError("mmsa.inference: labels= and evaluator= come together")
+    imgs, flips, pre = AugPlan.views(imgs, flips, preprocess, "aug_class_map")
+    frames = [_intake(img, p, "aug_class_map") for img, p in zip(imgs, pre)]
+    plan = AugPlan.of(test_cfg, [f[:3] for f in frames], flips, ori_shape)
+    _pair(backbone, head)
+    lgs = []
+    for mp, p, (_, _, _, _, frame, cut) in zip(plan.plans, pre, frames):
+        if test_cfg["mode"] == "slide":
+            part = [head(backbone(cut(mp.windows[s:s + max_batch]))[0]) for s in range(0, mp.n, max_batch)]
+            lgs.append(part[0] if len(part) == 1 else torch.cat(part, 0))
+        else:
+            lgs.append(head(backbone(p(*frame) if p is not None else frame)[0]))
+    device = frames[0][3]
+    B, Ho, Wo = plan.size
+    out = torch.empty(B, Ho, Wo, dtype=torch.uint8, device=device)
+    unc = torch.zeros(1, dtype=torch.int32, device=device)
+    plan.class_map(lgs, out, unc, one_pass)
+    if evaluator is not None:
+        evaluator.add(out, labels, case=case)
+    return out, unc
 
 
 class FrameResult:

@@ -248,6 +248,35 @@ def gen_rescale():
     print("rescale", os.path.getsize(path), "bytes", flush=True)
 
 
+def gen_aug():
+    """The reference's own EncoderDecoder.aug_test on top of its own inference (softmax, un-flip) with the fixed toy encode_decode of gen_rescale, on the
+    views tests/aug_ref.py lists (tests/golden/aug.npz: per case the config row, the averaged probabilities and the class map).  Also checked here: the
+    near-tie share the class-map tests may exclude stays under 1 %, and on the slide cases the augmented map differs from the single-view one (a fixture
+    that ignoring the views would satisfy pins nothing)."""
+    from tests import aug_ref as AR
+    from tests.configs import toy_encode_decode
+    from tests.util import REL_TOL
+    out = {}
+    for tag, case in AR.CASES.items():
+        hw, crop, stride, ori, _ = case
+        imgs, flips = AR.views_of(case)
+        fn = toy_encode_decode(5, seed=79)
+        p, pred = ref_import.reference_aug_test(fn, imgs, flips, ori, crop, stride, 5)
+        assert tuple(p.shape) == (1, 5) + tuple(ori) and tuple(pred.shape) == tuple(ori) and torch.equal(p.argmax(1)[0], pred)
+        close = AR.near_ties(p, REL_TOL).float().mean().item()
+        single = ref_import.reference_aug_test(fn, imgs[:1], flips[:1], ori, crop, stride, 5)[1]
+        moved = (single != pred).float().mean().item()
+        assert close <= 0.01, f"aug case {tag}: {close:.4f} of the pixels have a top-two margin inside the tolerance; choose another seed"
+        assert crop is None or moved > 0.01, f"aug case {tag}: the views change only {moved:.4f} of the map"
+        out[f"{tag}_cfg"] = np.array(AR.cfg_row(case))
+        out[f"{tag}_prob"] = p.numpy()
+        out[f"{tag}_map"] = pred.numpy().astype(np.uint8)
+        print("aug", tag, tuple(p.shape), f"near-ties {close:.4%}, {moved:.2%} of the map differs from the single view's", flush=True)
+    path = os.path.join(OUT, "aug.npz")
+    np.savez_compressed(path, **out)
+    print("aug", os.path.getsize(path), "bytes", flush=True)
+
+
 def gen_ckpt():
     """TwinConvNeXt.init_weights (TC:403-443) of the reference on a seeded single-stream ConvNeXt checkpoint: which twin keys
     end up loaded, and their checksums (tests/golden/convnext_ckpt.npz)."""
@@ -378,7 +407,7 @@ def gen_eval():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--big", action="store_true", help="also ViT-B@512 and ViT-L@1024 (minutes, GBs of RAM)")
-    ap.add_argument("--only", default=None, help="run one generator: msda_bwd | sam_ckpt | eval | rescale | model:<config name>")
+    ap.add_argument("--only", default=None, help="run one generator: msda_bwd | sam_ckpt | eval | rescale | aug | model:<config name>")
     a = ap.parse_args()
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
@@ -397,6 +426,7 @@ def main():
     gen_slide()
     gen_whole_dim()
     gen_rescale()
+    gen_aug()
     gen_ckpt()
     gen_eval()
     gen_head("head_vitl", full=False)

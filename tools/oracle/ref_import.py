@@ -361,3 +361,45 @@ def reference_rescale(encode_decode_fn, img, ori_shape, crop_size=None, stride=N
     fake = types.SimpleNamespace(test_cfg=types.SimpleNamespace(stride=stride, crop_size=crop_size), num_classes=num_classes,
                                  align_corners=False, encode_decode=lambda im, meta: encode_decode_fn(im))
     return mod.EncoderDecoder.slide_inference(fake, img, meta, True)
+
+
+def reference_aug_test(encode_decode_fn, imgs, flips, ori_shape, crop_size=None, stride=None, num_classes=None):
+    """Run the reference's own `EncoderDecoder.aug_test` (segmentors/encoder_decoder.py:509-546) on top of its own `inference` (:417-469: mode dispatch,
+    softmax, un-flip), `slide_inference` / `whole_inference`, all UNMODIFIED, with a stand-in `self` as in reference_rescale.  `imgs`: the views (already
+    flipped); `flips`: None / 'horizontal' / 'vertical' per view, handed over as img_meta's flip / flip_direction.  -> (averaged probabilities
+    [1, classes, h, w], class map int64 [h, w]).  aug_test returns the class map only, but it accumulates IN PLACE into the tensor its first `inference`
+    call returned (:517, 540-541): the stand-in's `inference` is the reference's, wrapped to keep a handle on that tensor -- nothing is edited."""
+    import torch.nn as nn
+    import torch.nn.functional as F
+    install()
+    if "mmseg_custom.models.segmentors" not in sys.modules:
+        m = types.ModuleType("mmseg_custom.models.segmentors")
+        m.__path__ = [os.path.join(SEG, "mmseg_custom/models/segmentors")]
+        sys.modules["mmseg_custom.models.segmentors"] = m
+    import mmseg.models.segmentors.base as sb
+    import mmseg.ops as mo
+
+    class BaseSegmentor(nn.Module):
+        def __init__(self, init_cfg=None):
+            super().__init__()
+    sb.BaseSegmentor = BaseSegmentor
+    mo.resize = lambda input, size=None, scale_factor=None, mode="nearest", align_corners=None, warning=True: F.interpolate(input, size, scale_factor, mode, align_corners)
+    mod = importlib.import_module("mmseg_custom.models.segmentors.encoder_decoder")
+    mod.resize = mo.resize
+    ED = mod.EncoderDecoder
+    cfg = types.SimpleNamespace(mode="whole") if crop_size is None else types.SimpleNamespace(mode="slide", stride=stride, crop_size=crop_size)
+    fake = types.SimpleNamespace(test_cfg=cfg, num_classes=num_classes, align_corners=False, encode_decode=lambda im, meta: encode_decode_fn(im))
+    fake.slide_inference = lambda img, meta, rescale: ED.slide_inference(fake, img, meta, rescale)
+    fake.whole_inference = lambda img, meta, rescale: ED.whole_inference(fake, img, meta, rescale)
+    seen = []
+
+    def inference(img, meta, rescale):
+        seen.append(ED.inference(fake, img, meta, rescale))
+        return seen[-1]
+    fake.inference = inference
+    metas = [[dict(ori_shape=tuple(ori_shape) + (3,), flip=f is not None, flip_direction=f or "horizontal")] for f in flips]
+    pred = ED.aug_test(fake, list(imgs), metas, True)
+    assert len(seen) == len(imgs) and len(pred) == 1
+    import numpy as np
+    import torch
+    return seen[0], torch.from_numpy(np.asarray(pred[0]))
