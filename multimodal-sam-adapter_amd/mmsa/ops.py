@@ -490,7 +490,10 @@ def msda_fused(value2d, spatial_shapes, level_start_index, raw, ref_points, out,
                  _chk(ref_points), po, ldo, pp, ldp, out_planes.fmt if out_planes is not None else FMT_B3,
                  batch, spatial, heads, d, levels, lq, points, _clamp_ptr(), _stream())
         return out if out is not None else out_planes
-    pv, _, _, _ = _mat(value2d, "value")
+    pv, vrows, vcols, ldv = _mat(value2d, "value")
+    if vrows != batch * spatial or vcols != heads * d or (vrows > 1 and ldv != heads * d):   # the entry takes no row stride: rows of heads * d floats
+        raise RuntimeError(f"mmsa.msda_fused: value must be a dense [batch * spatial, heads * d] = [{batch * spatial}, {heads * d}] matrix, "
+                           f"got shape {tuple(value2d.shape)} with row stride {ldv}")
     po, ldo = None, 0
     if out is not None:
         po, _, _, ldo = _mat(out, "out")

@@ -1,8 +1,9 @@
-"""Every `__global__` of conv.hip, conv_pair.hip, gconv_mfma.hip, gfe_qkv.hip, norm.hip (colstats / ffrm / lnhw), neck.hip, tail.hip and head.hip that a
-shape can select, reached through its launcher at the smallest shape that selects it and held ELEMENT BY ELEMENT to the float64 bound of
-tests/variant_ref.py.  Every call runs twice into NaN-filled outputs and must give identical bits; wherever a launch writes fp32 and operand planes
-together, the planes must be ops.split_planes of that launch's own fp32 output, bit for bit over the whole zero-initialised buffer (pad columns stay zero).
-None of these launchers writes the row-pair (h8c) format, so there is no unused half of a last row pair to watch here.
+"""Every `__global__` of conv.hip, conv_pair.hip, gconv_mfma.hip, gfe_qkv.hip, norm.hip (layernorm_rows / rowstats_finalize / colstats / ffrm / lnhw), neck.hip,
+tail.hip, head.hip and the forward kernels of msda.hip that a shape can select, reached through its launcher at the smallest shape that selects it and held
+ELEMENT BY ELEMENT to the float64 bound of tests/variant_ref.py.  Every call runs twice into NaN-filled outputs and must give identical bits; wherever a
+launch writes fp32 and operand planes together, the planes must be ops.split_planes of that launch's own fp32 output, bit for bit over the whole
+zero-initialised buffer (pad columns stay zero).  layernorm_rows and the fused MSDA entries also write the row-pair (h8c) format (csrc/common.h h8c_row /
+h8c_lo_off): there the pad columns, whatever lies behind a pair, and the unused half of a last odd row pair must stay as initialised (h8c_untouched_zero).
 
 The table: case id -> operation, launcher, the kernel the shape selects and why.  The ids carry the shape; B = 2 throughout (the batch stride is part of
 what can go wrong).  profiles/README.md says how the kernel trace of one run of this file is recorded.
@@ -49,6 +50,39 @@ what can go wrong).  profiles/README.md says how the kernel trace of one run of 
                                        every other case <false> (HW = 1, 35, or n2p-c8-hw4096 with stride + 3)
   t2n-*           mmsa_tokens_to_nchw  tokens_to_nchw_kernel
   head-*          mmsa_head_fuse     head_fuse_kernel          four unequal, non-square levels, fp32 + planes
+  ln-c*-r*        mmsa_layernorm_rows  layernorm_rows_kernel<NV, RPW>: C = 4, 8, 36, 96, 128 -> <1,2>; 132, 256 -> <1,1>; 260, 384, 512 -> <2,1>; 516, 1024 -> <4,1>;
+                                       1028, 2048 -> <8,1>; 2052, 4096 -> <16,1>: each side of each dispatch boundary; rows = 1, 7, 9: less than one workgroup's rows
+                                       (4, or 8 at <1,2>) and a ragged last workgroup; eps alternates 1e-6 / 1e-5; every seventh row has a variance near eps
+  ln-stream-*     mmsa_layernorm_rows  the streamed walk: rows = 4099 (two rows per slot) / 8197 (four): a slot handles several rows with the next row's loads in flight
+  ln-out-*        mmsa_layernorm_rows  y + y2; y + planes and planes alone in b3, h8, f3, h8c at C = 36, 100 (C % 8 != 0: store_planes4 / h8c_store4), 96 (pad
+                                       columns up to 128) and 64 (the lane-pair stores); rows = 7: an odd last row pair of the h8c planes
+  ln-stride-*     mmsa_layernorm_rows  x a column slice of a wider NaN-filled matrix, y and y2 with ld > C (the gap stays NaN)
+  ln-patch-*      mmsa_layernorm_rows  the 2 x 2 patchify map, (H, W) = (2, 2) and (4, 6), two images; planes need C % 32 == 0
+  ln-grp*         mmsa_layernorm_rows  row groups with their own weights: group_rows = 5 at C = 96 (<1,2>: the two halves of a wave in different groups); 300 with
+                                       wrap and y_gcol = C, and plain; 2050 with rows = 4100 (a slot crosses the group boundary in mid-walk: the `grp != cur_grp`
+                                       weight reload); ln-grp-patch-*: grouping with patchify, one image per group
+  ln-cw-*         mmsa_layernorm_rows  the clamp watch: h8 planes with |y| > 57344 leave the largest |y| of the fp32 output in the word, bit for bit; ordinary
+                                       magnitudes and bf16 hi/lo planes leave 0
+  ln-*-refused    mmsa_layernorm_rows  odd patchify H; y2 with patchify; patchified planes with C % 32 != 0; h8c with patchify / groups / a pair stride below
+                                       3 * pad64(C); C = 6; C = 4100; rows not a multiple of group_rows
+  rs-*            mmsa_rowstats_finalize  rowstats_finalize_kernel: rows = 1, 255, 257 (one 256-thread block and one row more), strips = 1, 2, 16; row 3 constant
+                                       (the variance clamps to 0); rs-d100-refused: D != 64 * strips
+  msda-d*-q*      mmsa_ms_deform_attn_forward  msda_kernel<false>: D = 4, 8, 12, 32, 40, 64.  Workgroups = ceil(B Lq M (D / 4) / block), block = (256 / (D / 4)) (D / 4);
+                                       mmsa_xcd_order permutes the first 8 * (grid / 8) of them:
+                                           D = 32, M = 4 (block 256): Lq = 4 / 27 / 32 / 33 / 67 -> 1 / 7 / 8 / 9 / 17 workgroups
+                                           D = 40, M = 4 (block 250): Lq = 3 / 26 -> 1 / 9
+                                           D = 4 / 8 / 64, M = 4, Lq = 33 -> 2 / 3 / 17;  D = 12, M = 3 (block 255), Lq = 33 -> 3
+  msda-scalar-*   mmsa_ms_deform_attn_forward  msda_scalar_kernel<float>: D = 2, D = 6 (D % 4 != 0) and D = 32 with `value` one float past a 16-byte boundary;
+                                       <__half> and <double>: D = 2 and 32
+  msda-dyadic-*   both entries         levels (4, 8), (2, 4) and dyadic locations: every pixel coordinate exact in fp32; h_im / w_im hit -1 (excluded), -0.5, 0,
+                                       size - 1 (upper taps zero) and size (excluded)
+  msdaf-*         mmsa_msda_fused      msda_kernel<true> on fp32 values: fp32 alone, fp32 + planes (b3, h8, f3, h8c), planes alone; D = 4, 12 (store_planes4_any),
+                                       8, 32, 40 (the pair store); M D = 96 with h8c (pad to 128); msdaf-stride: ldraw and ldo larger than dense, NaN gaps;
+                                       msdaf-cw-*: the clamp watch with h8c planes
+  msdap-*         mmsa_msda_fused_planes  msda_planes_kernel<false|true> (lo0 / lo1) on H8 value planes that hold the case's values exactly: (M, D) = (4, 8),
+                                       (2, 32), (3, 64), (1, 32); outputs as msdaf-*
+  msda*-refused   the MSDA entries     D = 6 fused; M D = 48 with value planes; ldraw too small; b3 planes as value; batch 3 with im2col_step 2; an fp32 value
+                                       matrix with a row stride, or with the wrong row count (ops.msda_fused: the entry takes no stride)
 """
 import pytest
 import torch
@@ -175,6 +209,101 @@ for C in (8, 40):
     _c(f"head-c{C}", "head_fuse", C=C, sizes=((8, 12), (4, 6), (2, 3), (16, 24)))
 del n
 
+# ---- layernorm_rows: each C with the instantiation it selects (variant_ref.ln_variant), rows below one workgroup's and with a ragged last workgroup
+_LN_C = (4, 8, 36, 96, 128, 132, 256, 260, 384, 512, 516, 1024, 1028, 2048, 2052, 4096)
+for n, (C, rows) in enumerate((C, rows) for C in _LN_C for rows in (1, 7, 9)):
+    _c(f"ln-c{C}-r{rows}", "layernorm_rows", C=C, rows=rows, eps=(1e-6, 1e-5)[n % 2])
+for n, (C, rows) in enumerate([(C, rows) for rows in (4099, 8197) for C in (8, 96, 132, 260, 516)] + [(4096, 4099)]):      # the streamed walk: 2 / 4 rows per slot
+    _c(f"ln-stream-c{C}-r{rows}", "layernorm_rows", C=C, rows=rows, eps=(1e-6, 1e-5)[n % 2])
+_FMTS = ("b3", "h8", "f3", "h8c")
+for C in (36, 100, 96, 64):            # 36, 100: C % 8 != 0 (store_planes4 / h8c_store4); 96: pad columns up to 128; rows = 7: an odd last row pair
+    _c(f"ln-out-y2-c{C}", "layernorm_rows", C=C, rows=7, eps=1e-6, y2=True)
+    for fmt in _FMTS:
+        _c(f"ln-out-y-{fmt}-c{C}", "layernorm_rows", C=C, rows=7, eps=1e-6, planes=fmt)
+        _c(f"ln-out-only-{fmt}-c{C}", "layernorm_rows", C=C, rows=7, eps=1e-5, planes=fmt, no_y=True)
+_c("ln-out-y-h8c-c64-r8", "layernorm_rows", C=64, rows=8, eps=1e-6, planes="h8c")
+for C in (36, 260):
+    _c(f"ln-stride-c{C}", "layernorm_rows", C=C, rows=9, eps=1e-6, y2=True, xpad=8, ypad=12)
+for H, W in ((2, 2), (4, 6)):
+    _c(f"ln-patch-{H}x{W}-c36", "layernorm_rows", C=36, rows=B * H * W, eps=1e-6, patchify=(H, W))
+    _c(f"ln-patch-{H}x{W}-c32-b3", "layernorm_rows", C=32, rows=B * H * W, eps=1e-6, patchify=(H, W), planes="b3")
+    _c(f"ln-patch-{H}x{W}-c64-h8", "layernorm_rows", C=64, rows=B * H * W, eps=1e-5, patchify=(H, W), planes="h8")
+_c("ln-grp5-c96", "layernorm_rows", C=96, rows=10, eps=1e-6, group_rows=5)                       # the two halves of one wave in different groups
+_c("ln-grp5-wrap-c96", "layernorm_rows", C=96, rows=10, eps=1e-6, group_rows=5, wrap=True, gcol=96)
+for C in (96, 132):
+    _c(f"ln-grp300-wrap-c{C}", "layernorm_rows", C=C, rows=600, eps=1e-6, group_rows=300, wrap=True, gcol=C)
+    _c(f"ln-grp300-c{C}", "layernorm_rows", C=C, rows=600, eps=1e-5, group_rows=300)
+_c("ln-grp300-wrap-c96-b3", "layernorm_rows", C=96, rows=600, eps=1e-6, group_rows=300, wrap=True, gcol=96, planes="b3")
+for C in (96, 260):                                                                              # a slot crosses the group boundary in mid-walk: the weight reload
+    _c(f"ln-grp2050-c{C}", "layernorm_rows", C=C, rows=4100, eps=1e-6, group_rows=2050)
+_c("ln-grp-patch-4x6-c36", "layernorm_rows", C=36, rows=B * 24, eps=1e-6, group_rows=24, patchify=(4, 6))
+_c("ln-grp-patch-4x6-c32-b3", "layernorm_rows", C=32, rows=B * 24, eps=1e-6, group_rows=24, patchify=(4, 6), planes="b3")
+# the clamp watch: |y| beyond 57344 with h8 planes leaves the largest |y| in the word; ordinary magnitudes, or bf16 hi/lo planes, leave 0
+_c("ln-cw-h8-big", "layernorm_rows", C=96, rows=9, eps=1e-6, planes="h8", wscale=1e5, cw=True)
+_c("ln-cw-h8", "layernorm_rows", C=96, rows=9, eps=1e-6, planes="h8", cw=True)
+_c("ln-cw-b3-big", "layernorm_rows", C=96, rows=9, eps=1e-6, planes="b3", wscale=1e5, cw=True)
+_c("ln-cw-b3", "layernorm_rows", C=96, rows=9, eps=1e-6, planes="b3", cw=True)
+for cid, kw in (("ln-oddH-refused", dict(C=36, rows=B * 18, patchify=(3, 6))), ("ln-y2-patch-refused", dict(C=36, rows=B * 4, patchify=(2, 2), y2=True)),
+                ("ln-patch-c36-planes-refused", dict(C=36, rows=B * 4, patchify=(2, 2), planes="b3")),
+                ("ln-h8c-patch-refused", dict(C=64, rows=B * 4, patchify=(2, 2), planes="h8c")),
+                ("ln-h8c-grp-refused", dict(C=64, rows=10, group_rows=5, planes="h8c")),
+                ("ln-h8c-ldp-refused", dict(C=64, rows=8, planes="h8c", short_ldp=True)),
+                ("ln-c6-refused", dict(C=6, rows=9)), ("ln-c4100-refused", dict(C=4100, rows=9)),
+                ("ln-grp-rows-refused", dict(C=96, rows=11, group_rows=5))):
+    RAISES.append((cid, "layernorm_rows", dict(B=B, eps=1e-6, **kw)))
+
+for rows in (1, 255, 257):
+    for strips in (1, 2, 16):
+        _c(f"rs-r{rows}-s{strips}", "rowstats", rows=rows, strips=strips, eps=(1e-6, 1e-5)[strips % 2])
+RAISES.append(("rs-d100-refused", "rowstats", dict(B=B, rows=9, strips=1, eps=1e-6, D=100)))
+
+# ---- MSDA: non-square levels throughout.  Workgroups of the fp32 vector kernel = ceil(B Lq M (D / 4) / block), block = (256 / (D / 4)) (D / 4):
+#        D = 32, M = 4 (block 256): Lq = 4 / 27 / 32 / 33 / 67 -> 1 / 7 / 8 / 9 / 17 workgroups (mmsa_xcd_order permutes the first 8 * (grid / 8))
+#        D = 40, M = 4 (block 250): Lq = 3 / 26 -> 1 / 9          D = 4 / 8 / 64, M = 4, Lq = 33 -> 2 / 3 / 17          D = 12, M = 3, Lq = 33 -> 3
+_LV2, _LV3 = ((5, 7), (3, 2)), ((9, 7), (5, 4), (2, 3))
+for n, Lq in enumerate((4, 27, 32, 33, 67)):
+    _c(f"msda-d32-q{Lq}", "msda", levels=(_LV2, _LV3)[n % 2], P=(3, 4)[n % 2], M=4, D=32, Lq=Lq)
+for n, (D, M, Lq) in enumerate(((4, 4, 33), (8, 4, 33), (12, 3, 33), (64, 4, 33), (40, 4, 3), (40, 4, 26))):
+    _c(f"msda-d{D}-q{Lq}", "msda", levels=(_LV3, _LV2)[n % 2], P=(4, 3)[n % 2], M=M, D=D, Lq=Lq)
+_c("msda-scalar-d2", "msda", levels=_LV2, P=4, M=3, D=2, Lq=33)
+_c("msda-scalar-d6", "msda", levels=_LV3, P=3, M=3, D=6, Lq=33)
+_c("msda-scalar-d32-misaligned", "msda", levels=_LV2, P=4, M=4, D=32, Lq=33, misalign=True)
+for dtn in ("f16", "f64"):
+    _c(f"msda-scalar-{dtn}-d2", "msda", levels=_LV3, P=4, M=3, D=2, Lq=33, dtype=dtn)
+    _c(f"msda-scalar-{dtn}-d32", "msda", levels=_LV2, P=3, M=4, D=32, Lq=33, dtype=dtn)
+_DY = ((4, 8), (2, 4))
+_c("msda-dyadic-fwd", "msda", levels=_DY, P=4, M=2, D=8, Lq=33, dyadic=True)
+_c("msda-dyadic-fwd-scalar", "msda", levels=_DY, P=4, M=2, D=2, Lq=33, dyadic=True)
+_c("msda-dyadic-fused", "msda_fused", levels=_DY, P=4, M=2, D=8, Lq=33, dyadic=True)
+_c("msda-dyadic-fused-h8", "msda_fused", levels=_DY, P=4, M=4, D=8, Lq=33, dyadic=True, value="h8", lo_bytes=True)
+for n, (M, D) in enumerate(((4, 4), (3, 12), (4, 8), (4, 32), (4, 40), (3, 32))):      # D = 4, 12: store_planes4_any; 8, 32, 40: the pair store; M D = 96: h8c pads to 128
+    kw = dict(levels=(_LV2, _LV3)[n % 2], P=(3, 4)[n % 2], M=M, D=D, Lq=(33, 26)[n % 2])
+    _c(f"msdaf-m{M}d{D}", "msda_fused", **kw)
+    for fmt in _FMTS:
+        _c(f"msdaf-m{M}d{D}-{fmt}", "msda_fused", planes=fmt, **kw)
+    _c(f"msdaf-m{M}d{D}-only-{_FMTS[n % 4]}", "msda_fused", planes=_FMTS[n % 4], no_y=True, **kw)
+_c("msdaf-m3d32-only-h8c", "msda_fused", levels=_LV2, P=3, M=3, D=32, Lq=33, planes="h8c", no_y=True)
+_c("msdaf-stride", "msda_fused", levels=_LV3, P=4, M=4, D=8, Lq=33, rawpad=5, opad=12)
+for n, (M, D) in enumerate(((4, 8), (2, 32), (3, 64), (1, 32))):                          # the gather on H8 value planes, both lo_bytes settings
+    for lo in (False, True):
+        kw = dict(levels=(_LV3, _LV2)[n % 2], P=(4, 3)[n % 2], M=M, D=D, Lq=33, value="h8", lo_bytes=lo)
+        _c(f"msdap-m{M}d{D}-lo{int(lo)}", "msda_fused", **kw)
+        for fmt in _FMTS:
+            _c(f"msdap-m{M}d{D}-lo{int(lo)}-{fmt}", "msda_fused", planes=fmt, **kw)
+        _c(f"msdap-m{M}d{D}-lo{int(lo)}-only-{_FMTS[(n + lo) % 4]}", "msda_fused", planes=_FMTS[(n + lo) % 4], no_y=True, **kw)
+_c("msdap-stride", "msda_fused", levels=_LV3, P=4, M=4, D=8, Lq=33, value="h8", lo_bytes=True, rawpad=5, opad=12)
+_c("msdaf-cw-h8c-big", "msda_fused", levels=_LV2, P=3, M=3, D=32, Lq=33, planes="h8c", vscale=1e5, cw=True)
+_c("msdaf-cw-h8c", "msda_fused", levels=_LV2, P=3, M=3, D=32, Lq=33, planes="h8c", cw=True)
+_c("msdaf-cw-b3-big", "msda_fused", levels=_LV2, P=3, M=3, D=32, Lq=33, planes="b3", vscale=1e5, cw=True)
+_c("msdaf-cw-b3", "msda_fused", levels=_LV2, P=3, M=3, D=32, Lq=33, planes="b3", cw=True)
+_KW = dict(B=B, levels=_LV2, P=3, Lq=9)
+RAISES += [("msdaf-d6-refused", "msda_fused", dict(M=4, D=6, **_KW)), ("msdap-md48-refused", "msda_fused", dict(M=2, D=24, value="h8", lo_bytes=False, **_KW)),
+           ("msdaf-ldraw-refused", "msda_fused", dict(M=4, D=8, short_raw=True, **_KW)), ("msdaf-b3-value-refused", "msda_fused", dict(M=4, D=8, value="b3", **_KW)),
+           ("msda-batch3-step2-refused", "msda", dict(M=4, D=8, batch=3, im2col_step=2, **_KW)),
+           ("msdaf-value-strided-refused", "msda_fused", dict(M=4, D=8, value_slice=True, **_KW)),
+           ("msdaf-value-rows-refused", "msda_fused", dict(M=4, D=8, value_short=True, **_KW))]
+del n, kw, _KW
+
 assert len({c[0] for c in CASES}) == len(CASES)
 
 
@@ -198,7 +327,7 @@ def bits(t):
 
 
 def fmt_of(ops, name):
-    return {"b3": ops.FMT_B3, "h8": ops.FMT_H8, "f3": ops.FMT_F3}[name]
+    return {"b3": ops.FMT_B3, "h8": ops.FMT_H8, "f3": ops.FMT_F3, "h8c": ops.FMT_H8C}[name]
 
 
 def planes_equal_split(ops, pl, y, fmt):
@@ -213,6 +342,8 @@ def planes_equal_split(ops, pl, y, fmt):
 def pads_zero(ops, pl):
     """Every 16-bit word / byte that belongs to a column >= k of the planes is zero."""
     k, kp = pl.k, pl.kpad
+    if pl.fmt == ops.FMT_H8C:
+        return h8c_untouched_zero(pl)
     if k == kp:
         return True
     by = pl.p.contiguous().view(torch.uint8).view(pl.p.shape[0], kp // 32, 128)
@@ -225,6 +356,25 @@ def pads_zero(ops, pl):
         offs = [2 * c, 2 * c + 1, 64 + 2 * c, 64 + 2 * c + 1]
     keep = cols >= k
     return all(bool((by[:, blk[keep], o[keep]] == 0).all()) for o in offs)
+
+
+def h8c_untouched_zero(pl):
+    """Row-pair planes (csrc/common.h h8c_row / h8c_lo_off): pair j = [row 2j: kpad fp16 hi][row 2j+1: kpad fp16 hi][kpad / 64 lines of 128 lo bytes: row 2j's
+    64 | row 2j+1's 64], the lo byte of column c of a chunk at ((c & 31) >> 3) * 16 + ((c >> 5) & 1) * 8 + (c & 7).  Everything that belongs to a column
+    >= k, whatever lies beyond 3 * kpad in a pair, and the unused half of a last odd row pair must be as initialised: zero."""
+    k, kp, n = pl.k, pl.kpad, pl.n
+    pairs = pl.p.shape[0]
+    ok = bool((pl.p[:, 3 * kp:] == 0).all())
+    by = pl.p[:, :3 * kp].contiguous().view(torch.uint8).view(pairs, 6 * kp)
+    hi = by[:, :4 * kp].contiguous().view(torch.int16).view(pairs, 2, kp)
+    lo = by[:, 4 * kp:].view(pairs, kp // 64, 2, 64)
+    if k < kp:
+        cols = torch.arange(k, kp)
+        c = cols % 64
+        ok = ok and bool((hi[:, :, k:] == 0).all()) and bool((lo[:, cols // 64, :, ((c & 31) >> 3) * 16 + ((c >> 5) & 1) * 8 + (c & 7)] == 0).all())
+    if n % 2:
+        ok = ok and bool((hi[-1, 1] == 0).all()) and bool((lo[-1, :, 1] == 0).all())
+    return ok
 
 
 # ------------------------------------------------------------------------------------------------ runners: one launch into fresh NaN-filled outputs
@@ -422,7 +572,129 @@ def run_head_fuse(ops, i, p):
     return dict(y=y, raw=[y, pl.p], planes=(pl, ops.FMT_B3))
 
 
-RUN = {"dwconv": run_dwconv, "gconv": run_gconv, "gfe_qkv": run_gfe_qkv, "dwpair_gate": run_dwpair_gate, "ca_apply": run_ca_apply,
+def watch_word(ops, p):
+    """(context, word): the clamp watch of a `cw` case -- a zeroed device word handed to the launch."""
+    import contextlib
+    if not p.get("cw"):
+        return contextlib.nullcontext(), None
+    word = torch.zeros(1, device=DEV)
+    return ops.clamp_watch(word), word
+
+
+def check_watch(p, word, y):
+    """The word holds the largest |y| of the launch's fp32 output, bit for bit, when a format of fp16 range had to clamp (the `big` cases); 0 otherwise."""
+    if word is None:
+        return
+    torch.cuda.synchronize()
+    big = y.abs().max().reshape(1)
+    clamps = p["planes"] in ("h8", "h8c") and float(big) > 57344.0
+    assert clamps == (p["planes"] in ("h8", "h8c") and (p.get("wscale", 1) > 1 or p.get("vscale", 1) > 1)), "the case does not do what its id says"
+    want = big if clamps else torch.zeros_like(big)
+    assert torch.equal(bits(word), bits(want)), f"clamp watch word {float(word)!r}, expected {float(want)!r}"
+
+
+def out_buffers(ops, p, rows, cols):
+    """NaN-filled fp32 output (row stride cols + opad) and zero-initialised planes, as the case asks."""
+    ybuf = None if p.get("no_y") else nanbuf(rows, cols + p.get("opad", p.get("ypad", 0)))
+    pl = ops.alloc_planes(rows, cols, DEV, zero=True, fmt=fmt_of(ops, p["planes"])) if p.get("planes") else None
+    return ybuf, pl
+
+
+def finish(ops, p, ybuf, pl, cols, extra_raw=(), y_extra=None):
+    out = dict(raw=[t for t in (ybuf, pl.p if pl else None) + tuple(extra_raw) if t is not None])
+    if ybuf is not None:
+        assert bool(torch.isnan(ybuf[:, cols:]).all()), "the gap behind an output row was written"
+        y = ybuf[:, :cols]
+        out["y"] = y if y_extra is None else torch.cat([y, y_extra], 1)
+        if pl:
+            out["planes"], out["planes_src"] = (pl, pl.fmt), y
+    else:
+        torch.cuda.synchronize()
+        out["decoded"] = (ops.planes_to_float(pl), V.FMT_REL[p["planes"]])
+        assert pads_zero(ops, pl)
+    return out
+
+
+def run_layernorm_rows(ops, i, p):
+    rows, C, gr = p["rows"], p["C"], p.get("group_rows", 0)
+    xoff, xpad = (4, p["xpad"]) if p.get("xpad") else (0, 0)
+    xbuf = nanbuf(rows, C + xpad)                                    # x: a column slice of a wider NaN-filled matrix
+    xbuf[:, xoff:xoff + C] = dev(i["x"])
+    orows, ocols = V.ln_out_shape(p)
+    ybuf, pl = out_buffers(ops, p, orows, ocols)
+    if p.get("short_ldp"):                                           # a pair stride below 3 * pad64(C)
+        pl = ops.Planes(torch.zeros((rows + 1) // 2, 3 * pl.kpad - 64, dtype=torch.int16, device=DEV), rows, C, pl.kpad, ops.FMT_H8C)
+    y2buf = nanbuf(rows, C + p.get("ypad", 0)) if p.get("y2") else None
+    ctx, word = watch_word(ops, p)
+    with ctx:
+        ops.layernorm(xbuf[:, xoff:xoff + C], dev(i["w"]), dev(i["b"]), p["eps"], out=None if ybuf is None else ybuf[:, :ocols],
+                      out2=None if y2buf is None else y2buf[:, :C], patchify=p.get("patchify"), out_planes=pl, group_rows=gr,
+                      w_gstride=C if gr else 0, y_gcol=p.get("gcol", 0), y_wrap=bool(p.get("wrap")))
+    if y2buf is not None:
+        assert bool(torch.isnan(y2buf[:, C:]).all()), "the gap behind a y2 row was written"
+    out = finish(ops, p, ybuf, pl, ocols, extra_raw=(y2buf,), y_extra=None if y2buf is None else y2buf[:, :C])
+    check_watch(p, word, ybuf[:, :ocols] if ybuf is not None else None)
+    return out
+
+
+def run_rowstats(ops, i, p):
+    rows = p["rows"]
+    o = nanbuf(rows, 2)
+    ops.rowstats_finalize(dev(i["rs"].float()), rows, p.get("D", 64 * p["strips"]), p["eps"], o)
+    return dict(y=o, raw=[o])
+
+
+def msda_tables(p):
+    levels, starts, S = V.msda_geometry(p)
+    return torch.tensor(levels, dtype=torch.long, device=DEV), torch.tensor(starts, dtype=torch.long, device=DEV), S
+
+
+def run_msda(ops, i, p):
+    ss, lsi, S = msda_tables(p)
+    dt = {"f16": torch.float16, "f64": torch.float64}.get(p.get("dtype"), torch.float32)
+    nb = p.get("batch", p["B"])
+    value, loc, aw = (dev(torch.cat([t] * 2)[:nb].to(dt)) for t in (i["value"], i["loc"], i["aw"]))
+    if p.get("misalign"):                                            # value starts one float past a 16-byte boundary: the scalar kernel takes it
+        buf = nanbuf(1 + value.numel() + 3)
+        buf[1:1 + value.numel()] = value.flatten()
+        value = buf[1:1 + value.numel()].view(value.shape)
+        assert value.data_ptr() % 16 == 4
+    y = ops.msda_forward(value, ss, lsi, loc, aw, im2col_step=p.get("im2col_step", 64))
+    y = y.view(nb * p["Lq"], p["M"] * p["D"])
+    return dict(y=y, raw=[y])
+
+
+def run_msda_fused(ops, i, p):
+    ss, lsi, S = msda_tables(p)
+    Bn, M, D, Lq, P, L = p["B"], p["M"], p["D"], p["Lq"], p["P"], len(p["levels"])
+    n3 = M * L * P * 3
+    if p.get("value") == "h8":                                       # the planes hold the case's values exactly (variant_ref.h8_exact)
+        v = dev(i["value"])
+        value = ops.split_planes(v, fmt=ops.FMT_H8)
+        torch.cuda.synchronize()
+        assert torch.equal(bits(ops.planes_to_float(value)), bits(v)), "split_planes / planes_to_float do not return the H8-exact values"
+    elif p.get("value") == "b3":
+        value = ops.split_planes(dev(i["value"]), fmt=ops.FMT_B3)
+    elif p.get("value_slice"):                                       # a column slice of a wider matrix: the entry has no row stride for it
+        value = nanbuf(Bn * S, M * D + 4)[:, :M * D]
+    elif p.get("value_short"):
+        value = dev(i["value"])[:Bn * S - 1]
+    else:
+        value = dev(i["value"])
+    rawbuf = nanbuf(Bn * Lq, n3 + p.get("rawpad", 0))
+    rawbuf[:, :n3] = dev(i["raw"])
+    raw = rawbuf[:, :n3 - 4].contiguous() if p.get("short_raw") else rawbuf[:, :n3]
+    ybuf, pl = out_buffers(ops, p, Bn * Lq, M * D)
+    ctx, word = watch_word(ops, p)
+    with ctx:
+        ops.msda_fused(value, ss, lsi, raw, dev(i["ref"]), None if ybuf is None else ybuf[:, :M * D], Bn, S, M, D, L, Lq, P, out_planes=pl,
+                       lo_bytes=bool(p.get("lo_bytes")))
+    out = finish(ops, p, ybuf, pl, M * D)
+    check_watch(p, word, ybuf[:, :M * D] if ybuf is not None else None)
+    return out
+
+
+RUN = {"layernorm_rows": run_layernorm_rows, "rowstats": run_rowstats, "msda": run_msda, "msda_fused": run_msda_fused, "dwconv": run_dwconv, "gconv": run_gconv, "gfe_qkv": run_gfe_qkv, "dwpair_gate": run_dwpair_gate, "ca_apply": run_ca_apply,
        "gelu_gate": run_gelu_gate, "pool_hw": run_pool_hw, "colstats": run_colstats, "ffrm": run_ffrm, "lnhw": run_lnhw, "gram": run_gram,
        "chanattn": run_chanattn, "gffm": run_gffm, "tail": run_tail, "nchw_to_planes": run_nchw_to_planes, "tokens_to_nchw": run_tokens_to_nchw,
        "head_fuse": run_head_fuse}
@@ -454,7 +726,8 @@ def test_variant(ops, cid, op, p):
 
 @pytest.mark.parametrize("cid,op,p", RAISES, ids=[c[0] for c in RAISES])
 def test_variant_refused(ops, cid, op, p):
-    """Shapes a launcher must refuse: image groups outside the 7 x 7 kernels; head blocks that do not divide the channels."""
-    i, _, _ = V.case_data(cid, op, p)
+    """Shapes a launcher must refuse: image groups outside the 7 x 7 kernels; head blocks that do not divide the channels; the ln-*, rs-* and msda*
+    refusals of the table.  (Only the inputs are drawn: a refused shape need not have a reference.)"""
+    i = V.OPS[op][0](p, V.gen_for(cid))
     with pytest.raises(RuntimeError):
         RUN[op](ops, i, p)

@@ -1,4 +1,4 @@
-"""Float64 restatements of the conv / norm / neck / tail / head operations and the per-element bound the kernel-variant tests hold the
+"""Float64 restatements of the conv / norm / neck / tail / head, LayerNorm-rows, row-statistics and deformable-attention operations and the per-element bound the kernel-variant tests hold the
 device to (tests/test_kernel_variants_gpu.py; tests/test_kernel_variants_cpu.py keeps the bound itself honest).
 
 Every `ref_<op>(i, p)` takes the case's inputs `i` (a dict of CPU tensors, all of ONE floating dtype) and its parameters `p` and returns
@@ -8,7 +8,43 @@ it is torch's own fp32 evaluation of the same operation (bnd is then ignored).
 The bound.  A result formed as a sum of n products with magnitude sum s = sum |x_i| |w_i| + |bias| passes when, element by element,
     |y - r| <= (n + 4) * 2^-24 * s + a
 -- the standard fp32 accumulation bound (n + 4 roundings of relative size 2^-24 on every path through the sum) plus the activation's own absolute
-error a, scaled by whatever multiplies the activation.  Nothing measured goes into the first term."""
+error a, scaled by whatever multiplies the activation.  Nothing measured goes into the first term.
+
+The LayerNorm-rows, row-statistics and deformable-attention (MSDA) operations have bounds of their own, derived here; u = 2^-24.
+
+layernorm_rows (csrc/norm.hip).  Reference, per row: mu and the biased variance over C, rho = 1 / sqrt(var + eps), y = (x - mu) rho w_g + b_g, y2 = y + x;
+eps is the fp32 value the launcher receives.  Let Dp be the longest chain of additions behind the row sum: two inside a float4, NV - 1 across a lane's
+float4s, six (one row per wave) or five (two rows per wave) butterfly steps; a = mean_c |x_c|, d_c = x_c - mu.
+    mean        the sum carries Dp roundings on every path, the division one more:                 delta_mu = (Dp + 1) u a
+    difference  the device's d_c is off by the mean's error plus its own rounding:                 e_c = delta_mu + u (|d_c| + delta_mu)
+    variance    squares, the same sum, the division: (Dp + 3) u var; d^2 moves by 2 |d_c| e_c:     delta_sigma2 = (Dp + 3) u var + 2 mean_c(|d_c| e_c)
+    rstd        relative: the variance's error through 1 / sqrt, and three correctly rounded operations (eps add, sqrt, divide -- the build uses neither
+                fast-math nor approximate division):                                               E_rho = delta_sigma2 / (2 (var + eps)) + 3 u
+    y           d rho w + b, three roundings on the product, two on the sum:
+                                                                   bnd_y = |w| rho (e_c + |d_c| (E_rho + 3 u)) + 2 u (|w rho d_c| + |b|)
+    y2          one more addition:                                                                 bnd_y2 = bnd_y + u |y2|
+
+rowstats (rowstats_finalize_kernel).  From the given fp32 strip sums, in float64 on the device as here: mean = s1 / D, var = max(s2 / D - mean^2, 0), rstd =
+1 / sqrt(var + eps).  The device's double arithmetic adds `strips` terms and a handful of operations (2^-53 each, amplified by the cancellation
+(s2 / D) / (var + eps)) and rounds once to fp32:        mean: u |mean|;       rstd: rstd (u + 2^-53 (strips + 4) (s2 / D) / (var + eps)).
+
+msda / msda_fused (csrc/msda.hip).  Reference: a direct gather.  pixel = loc * (W, H) - 0.5; a sample counts iff -1 < h < H and -1 < w < W; four taps, a
+tap outside the map is zero; out = sum over l, p of weight * bilinear.  The fused form first computes loc = ref + off / (W_l, H_l) and weights = softmax
+over L * P of the logits.  Per sample s: A_s the weight, c_k the float64 bilinear weights, v_k the tap values.
+    S1 = sum_s |A_s| sum_k c_k |v_k|,  T_s = sum over the existing taps of |v_k|
+    eps_h = 2 u (|ly H| + 0.5), eps_w = 2 u (|lx W| + 0.5): the product and the subtraction behind a pixel coordinate (the fused form has the division
+    and the addition in front of them: 4 u (|r H| + |off| + 0.5)); a coordinate's error moves the bilinear value by at most that times T_s
+    bnd = (n + 12) u S1 + sum_s |A_s| (eps_h + eps_w) T_s
+    n = the terms accumulated per element: L P (msda_kernel, msda_scalar_kernel), 4 L P (msda_planes_kernel<false>), 8 L P (<true>); the 12 covers the
+    roundings of lh, hh, the tap weight products and the multiplication by the sample weight.
+The position term holds only while both evaluations take the same four taps, so make_msda* moves every drawn sample whose float64 pixel coordinate lies
+within 2^-12 of an integer (-1, H and W are integers) a quarter pixel away from it, to the side it lay on; the exact coordinates are the business of the
+dyadic cases, whose every coordinate is exact in fp32 and whose position term is therefore zero.
+Fused weights: exp(logit - max) / sum: the subtraction (u |logit - max| on the exponent), the exponential, L P additions, the division, the
+product with the reciprocal: relative (L P + 6 + max |logit - max|) u, times S1 -- plus what the runtime's expf adds, which the source cannot tell:
+EXPF_EXCESS below, handled like SIGMOID_EXCESS (measured against float64 on an MI355X, twice the measured value allowed, relative to S1).
+Scalar kernels: f16 computes in fp32 on the fp16 inputs as given and rounds once: the fp32 bound + 2^-11 |r| + 2^-24; f64: the formula with u = 2^-53.
+Planes-only outputs: bnd + FMT_REL |r|."""
 import zlib
 
 import torch
@@ -21,9 +57,14 @@ GELU_ABS = 3.3e-7          # csrc/common.h: the fp32 evaluation of the degree-7 
 SIGMOID_EXCESS = 2.0e-8    # measured 1.99977671e-08 (dw3-nhwc-1x7-c64-sigmoid-b0); every other sigmoid case stays below the accumulation term
 HSWISH_EXCESS = 0.0        # measured: no excess, the closest case stays 6.04e-09 BELOW the accumulation term (dw3-nhwc-1x7-c36-hswish-b0)
 ACT_ABS = {"none": 0.0, "relu": 0.0, "relu6": 0.0, "gelu": GELU_ABS, "sigmoid": 2 * SIGMOID_EXCESS, "hswish": 2 * HSWISH_EXCESS}
-assert max(ACT_ABS.values()) <= 1e-6   # a larger allowance would be a finding about the kernel, not a tolerance
-# rounding of the operand formats themselves (relative to |r|), where only planes can be compared: bf16 hi/lo, fp16 hi/lo, fp16 hi + e5m2 lo
-FMT_REL = {"b3": 2.0 ** -16, "f3": 2.0 ** -22, "h8": 2.0 ** -14}
+# msda_kernel<true> / msda_planes_kernel form their softmax weights with the runtime's expf.  The figure is the largest excess of |y - r| over the derived
+# part of the bound, relative to S1 (the magnitude sum the weight errors scale with; O(1) at the magnitudes of the table), against float64 on an MI355X
+# over every msda_fused case (fp32 outputs); twice it is allowed.
+EXPF_EXCESS = 0.0          # measured: no excess, the closest case stays 2.07e-06 S1 BELOW the derived part (msda-dyadic-fused; ref_msda_fused(parts=True))
+assert max(max(ACT_ABS.values()), 2 * EXPF_EXCESS) <= 1e-6   # a larger allowance would be a finding about the kernel, not a tolerance
+# rounding of the operand formats themselves (relative to |r|), where only planes can be compared: bf16 hi/lo, fp16 hi/lo, fp16 hi + e5m2 lo (h8c: the
+# same arithmetic as h8 on 3 bytes per element)
+FMT_REL = {"b3": 2.0 ** -16, "f3": 2.0 ** -22, "h8": 2.0 ** -14, "h8c": 2.0 ** -14}
 ACTS = ("none", "gelu", "relu", "relu6", "hswish", "sigmoid")
 
 
@@ -381,7 +422,291 @@ def ref_head_fuse(i, p):
     return nhwc(F.relu(tot * sc + sh)), nhwc(bound(4 * nl, s * sc.abs() + sh.abs()))
 
 
+# ------------------------------------------------------------------------------------------------ layernorm_rows
+def ln_variant(C):
+    """(NV, RPW) of the layernorm_rows_kernel instantiation the launcher selects for C channels."""
+    return (1, 2) if C <= 128 else (1, 1) if C <= 256 else (2, 1) if C <= 512 else (4, 1) if C <= 1024 else (8, 1) if C <= 2048 else (16, 1)
+
+
+def ln_out_shape(p):
+    rows, C, gr = p["rows"], p["C"], p.get("group_rows", 0)
+    if p.get("patchify"):
+        return rows // 4, 4 * C
+    return (gr if gr and p.get("wrap") else rows), C + ((rows // gr - 1) * p.get("gcol", 0) if gr else 0)
+
+
+def ln_place(t, p):
+    """Where row `row` of the [rows, C] result goes: patchify sends token (b, h, w) to row (b, h/2, w/2), column block (h&1)*2 + (w&1); group
+    g = row / group_rows writes at column g * y_gcol, and at row % group_rows when wrapping."""
+    rows, C = t.shape
+    r = torch.arange(rows)
+    gr = p.get("group_rows", 0)
+    g = r // gr if gr else torch.zeros_like(r)
+    orow = r - g * gr if gr and p.get("wrap") else r
+    ocol = g * p.get("gcol", 0)
+    if p.get("patchify"):
+        H, W = p["patchify"]
+        w_, h_, b_ = r % W, (r // W) % H, r // (W * H)
+        orow = (b_ * (H // 2) + h_ // 2) * (W // 2) + w_ // 2
+        ocol = ocol + ((h_ & 1) * 2 + (w_ & 1)) * C
+    out = t.new_zeros(ln_out_shape(p))
+    out[orow[:, None], ocol[:, None] + torch.arange(C)[None, :]] = t
+    return out
+
+
+def make_layernorm_rows(p, g):
+    rows, C = p["rows"], p["C"]
+    G = rows // p["group_rows"] if p.get("group_rows") else 1
+    x = torch.randn(rows, C, generator=g) * 3 + 1
+    x[4::5] *= 100                                                                      # every fifth row: large magnitudes
+    x[6::7] = 1.5 + 1e-3 * torch.randn(x[6::7].shape, generator=g)                      # every seventh: variance near eps, eps matters
+    s = p.get("wscale", 1.0)                                                            # (clamp-watch cases: |y| beyond the fp16 formats' range)
+    return dict(x=x, w=(torch.randn(G, C, generator=g) * 0.5 + 1) * s, b=torch.randn(G, C, generator=g) * 0.5 * s)
+
+
+def ref_layernorm_rows(i, p, mut=None):
+    """(y | y2) in the launch's output layout ([.., C] or [.., 2 C] with y2 next to y).  `mut`: a deliberately wrong restatement (the CPU companion)."""
+    x, w, b = i["x"], i["w"], i["b"]
+    rows, C = x.shape
+    eps = float(torch.tensor(p["eps"], dtype=torch.float32))        # the launcher receives eps as fp32
+    if mut == "eps":
+        eps = 1e-5 if p["eps"] < 5e-6 else 1e-6
+    gr = p.get("group_rows", 0)
+    grp = torch.arange(rows) // gr if gr and mut != "group0" else torch.zeros(rows, dtype=torch.long)
+    wg, bg = w[grp], b[grp]
+    mu = x[:, :C - 4].sum(1, keepdim=True) / C if mut == "mean_drop4" else x.mean(1, keepdim=True)
+    d = x - mu
+    var = (d * d).sum(1, keepdim=True) / (C - 1 if mut == "var_cm1" else C)
+    rho = 1 / torch.sqrt(var + eps)
+    y = d * rho * wg + bg
+    out = [ln_place(y, p)] + ([y + x] if p.get("y2") else [])
+    if x.dtype != torch.float64 or mut:
+        return torch.cat(out, 1), None
+    nv, rpw = ln_variant(C)
+    dp = 2 + (nv - 1) + (6 if rpw == 1 else 5)
+    a = x.abs().mean(1, keepdim=True)
+    dmu = (dp + 1) * U * a
+    e = dmu + U * (d.abs() + dmu)
+    dsig = (dp + 3) * U * var + 2 * (d.abs() * e).mean(1, keepdim=True)
+    erho = dsig / (2 * (var + eps)) + 3 * U
+    by = wg.abs() * rho * (e + d.abs() * (erho + 3 * U)) + 2 * U * ((wg * rho * d).abs() + bg.abs())
+    bnd = [ln_place(by, p)] + ([by + U * (y + x).abs()] if p.get("y2") else [])
+    return torch.cat(out, 1), torch.cat(bnd, 1)
+
+
+# ------------------------------------------------------------------------------------------------ rowstats_finalize
+def make_rowstats(p, g):
+    """Strip sums (sum x, sum x^2 per 64-column strip): the float64 sums of drawn rows, rounded to fp32 -- kept as float64 tensors that hold fp32 values,
+    because the device, like the reference, continues in double from them."""
+    rows, strips = p["rows"], p["strips"]
+    x = (torch.randn(rows, strips, 64, generator=g) * 2 + 0.5).double()
+    if rows > 3:
+        x[3] = 1.25                                                  # a constant row: the variance clamps to 0, rstd = 1 / sqrt(eps)
+    return dict(rs=torch.stack([x.sum(2), (x * x).sum(2)], 2).float().double())
+
+
+def ref_rowstats(i, p):
+    """(mean, rstd) per row, [rows, 2]; double arithmetic on either side, one rounding to the working type."""
+    rs, D = i["rs"].double(), 64 * p["strips"]
+    eps = float(torch.tensor(p["eps"], dtype=torch.float32))
+    s1, s2 = rs[..., 0].sum(1), rs[..., 1].sum(1)
+    mean = s1 / D
+    var = (s2 / D - mean * mean).clamp_min(0)
+    rstd = 1 / torch.sqrt(var + eps)
+    bnd = torch.stack([U * mean.abs(), rstd * (U + 2.0 ** -53 * (p["strips"] + 4) * (s2 / D) / (var + eps))], 1)
+    return torch.stack([mean, rstd], 1).to(i["_dt"]), bnd
+
+
+# ------------------------------------------------------------------------------------------------ deformable attention
+NEAR = 2.0 ** -12
+
+
+def msda_geometry(p):
+    levels = p["levels"]
+    starts = [sum(h * w for h, w in levels[:l]) for l in range(len(levels))]
+    return levels, starts, sum(h * w for h, w in levels)
+
+
+def _size(levels, dt=torch.float64):
+    return torch.tensor([[w, h] for h, w in levels], dtype=dt).view(1, 1, 1, len(levels), 1, 2)     # (W, H): locations are (x, y)
+
+
+def _off_integers(pix):
+    """Pixel coordinates within 2^-12 of an integer (-1, H and W among them) move a quarter pixel away from it, to the side they lay on."""
+    k = torch.round(pix)
+    near = (pix - k).abs() < NEAR
+    return torch.where(near, k + torch.where(pix >= k, 0.25, -0.25), pix), near
+
+
+def _dyadic_pixels(levels, shape, g):
+    """Exact pixel coordinates (x, y) per level that hit -1 (excluded), -0.5, 0, size - 1 (the upper taps are zero) and size (excluded), and a few
+    dyadic interior points.  shape = [B, Lq, M, L, P]."""
+    pix = torch.empty(*shape, 2, dtype=torch.float64)
+    for l, (H, W) in enumerate(levels):
+        for ax, n in ((0, W), (1, H)):
+            cand = torch.tensor([-1.0, -0.5, 0.0, 0.25, 0.5, n - 1.5, n - 1.0, n - 0.5, float(n)], dtype=torch.float64)
+            pix[:, :, :, l, :, ax] = cand[torch.randint(0, len(cand), pix[:, :, :, l, :, ax].shape, generator=g)]
+    return pix
+
+
+def _value(p, g, S):
+    return torch.randn(p["B"], S, p["M"], p["D"], generator=g) * p.get("vscale", 1.0)
+
+
+def make_msda(p, g):
+    levels, _, S = msda_geometry(p)
+    Bn, M, Lq, P, L = p["B"], p["M"], p["Lq"], p["P"], len(levels)
+    rnd = (lambda t: t.half().float()) if p.get("dtype") == "f16" else (lambda t: t.float())       # f16: the inputs are fp16 numbers as given
+    size = _size(levels)
+    if p.get("dyadic"):
+        loc = rnd((_dyadic_pixels(levels, (Bn, Lq, M, L, P), g) + 0.5) / size)                    # power-of-two sizes: exact
+        assert bool((loc.double() * size - 0.5 == (loc * size.float() - 0.5).double()).all())
+    else:
+        loc = rnd(torch.rand(Bn, Lq, M, L, P, 2, generator=g) * 1.2 - 0.1)                         # roughly a quarter of the samples leave the map
+        for _ in range(8):
+            pix, near = _off_integers(loc.double() * size - 0.5)
+            if not bool(near.any()):
+                break
+            loc = rnd((pix + 0.5) / size)
+        assert not bool(near.any())
+    aw = torch.softmax(torch.randn(Bn, Lq, M, L * P, generator=g), -1).view(Bn, Lq, M, L, P)
+    return dict(value=rnd(_value(p, g, S)), loc=loc, aw=rnd(aw))
+
+
+def _gather(value, levels, starts, loc, wgt, mut=None):
+    """out[b, q, m, :] = sum_{l, p} wgt * bilinear(value_l at loc) as [B, Lq, M, D], with S1 and the per-sample tap sums T [B, Lq, M, L, P, D]."""
+    Bn, S, M, D = value.shape
+    Lq, L, P = loc.shape[1], loc.shape[3], loc.shape[4]
+    if mut == "start":                                       # the second level's start index one row too late
+        starts = [s + (levels[1][1] if l >= 1 else 0) for l, s in enumerate(starts)]
+        value = torch.cat([value, value.new_zeros(Bn, levels[1][1], M, D)], 1)
+    out = value.new_zeros(Bn, Lq, M, D)
+    s1 = value.new_zeros(Bn, Lq, M, D)
+    T = value.new_zeros(Bn, Lq, M, L, P, D)
+    for l, (H, W) in enumerate(levels):
+        vl = value[:, starts[l]:starts[l] + H * W].permute(0, 2, 1, 3)                             # [B, M, HW, D]
+        sx, sy = (H, W) if mut == "swap" else (W, H)
+        half = 0.0 if mut == "nohalf" else 0.5
+        x, y = loc[:, :, :, l, :, 0] * sx - half, loc[:, :, :, l, :, 1] * sy - half                 # [B, Lq, M, P]
+        inside = (y > -1) & (x > -1) & (y < H) & (x < W)
+        y0, x0 = torch.floor(y), torch.floor(x)
+        ly, lx = y - y0, x - x0
+        a = wgt[:, :, :, l, :]
+        for dy, dx, cw in ((0, 0, (1 - ly) * (1 - lx)), (0, 1, (1 - ly) * lx), (1, 0, ly * (1 - lx)), (1, 1, ly * lx)):
+            yy, xx = y0 + dy, x0 + dx
+            ok = inside & (yy >= 0) & (yy <= H - 1) & (xx >= 0) & (xx <= W - 1)
+            idx = (yy.clamp(0, H - 1) * W + xx.clamp(0, W - 1)).long().permute(0, 2, 1, 3).reshape(Bn, M, Lq * P, 1)
+            v = torch.gather(vl, 2, idx.expand(Bn, M, Lq * P, D)).view(Bn, M, Lq, P, D).permute(0, 2, 1, 3, 4) * ok[..., None]
+            out = out + ((a * cw)[..., None] * v).sum(3)
+            s1 = s1 + ((a.abs() * cw.abs())[..., None] * v.abs()).sum(3)
+            T[:, :, :, l] += v.abs()
+    return out, s1, T
+
+
+def _msda_u(p):
+    return 2.0 ** -53 if p.get("dtype") == "f64" else U
+
+
+def ref_msda(i, p, mut=None):
+    levels, starts, _ = msda_geometry(p)
+    value, loc, aw = i["value"], i["loc"], i["aw"]
+    if p.get("dtype") == "f64":                              # the device computes this case in double: so does its plain torch statement
+        value, loc, aw = value.double(), loc.double(), aw.double()
+    Bn, Lq, M, D = p["B"], p["Lq"], p["M"], p["D"]
+    out, s1, T = _gather(value, levels, starts, loc, aw, mut)
+    r = out.reshape(Bn * Lq, M * D)
+    if i["_dt"] != torch.float64 or mut:
+        return r, None
+    u = _msda_u(p)
+    pos = 0.0
+    if not p.get("dyadic"):
+        e = (2 * u * ((loc * _size(levels)).abs() + 0.5)).sum(-1)                                   # eps_w + eps_h, [B, Lq, M, L, P]
+        pos = ((aw.abs() * e)[..., None] * T).sum((3, 4))
+    bnd = ((len(levels) * p["P"] + 12) * u * s1 + pos).reshape(Bn * Lq, M * D)
+    if p.get("dtype") == "f16":
+        bnd = bnd + 2.0 ** -11 * r.abs() + 2.0 ** -24
+    return r, bnd
+
+
+def h8_exact(t, g):
+    """(h, h + l / 2048): values the h8 planes hold exactly.  h is an fp16 number (|h| >= 2^-4), l an e5m2 number of h's sign with |l| < 2^e (2^e <= |h|):
+    |l / 2048| stays below half an ulp of h, so fp16 rounding returns h and the remainder is l / 2048 exactly; the sum spans 15 bits: exact in fp32."""
+    h = t.half().float()
+    h = torch.where(h.abs() < 2.0 ** -4, torch.where(h < 0, -(2.0 ** -4), 2.0 ** -4), h)
+    e = torch.floor(torch.log2(h.abs().double())).float()
+    k = torch.randint(0, 5, h.shape, generator=g).float()
+    l = torch.where(k == 0, torch.zeros_like(h), torch.sign(h) * (1 + (k - 1) / 4) * torch.exp2(e - 1))
+    v = h + l / 2048
+    assert bool((v.double() == h.double() + l.double() / 2048).all()) and bool((v.half().float() == h).all())
+    return h, v
+
+
+def make_msda_fused(p, g):
+    levels, _, S = msda_geometry(p)
+    Bn, M, D, Lq, P, L = p["B"], p["M"], p["D"], p["Lq"], p["P"], len(levels)
+    size = _size(levels)
+    if p.get("dyadic"):
+        ref = torch.randint(0, 9, (Lq, 2), generator=g).double() / 8
+        off = _dyadic_pixels(levels, (Bn, Lq, M, L, P), g) + 0.5 - ref.view(1, Lq, 1, 1, 1, 2) * size   # exact: power-of-two sizes, ref in eighths
+        assert bool((off.float().double() == off).all())
+        off = off.float()
+    else:
+        ref = torch.rand(Lq, 2, generator=g).double()
+        rr = ref.view(1, Lq, 1, 1, 1, 2)
+        off = (((torch.rand(Bn, Lq, M, L, P, 2, generator=g) * 1.2 - 0.1).double() - rr) * size).float()   # loc uniform over [-0.1, 1.1]
+        for _ in range(8):
+            pix, near = _off_integers((ref.float().double().view(1, Lq, 1, 1, 1, 2) + off.double() / size) * size - 0.5)
+            if not bool(near.any()):
+                break
+            off = (pix + 0.5 - ref.float().double().view(1, Lq, 1, 1, 1, 2) * size).float()
+        assert not bool(near.any())
+    logit = torch.randn(Bn, Lq, M, L * P, generator=g) * 2
+    raw = torch.cat([off.reshape(Bn * Lq, M * L * P * 2), logit.reshape(Bn * Lq, M * L * P)], 1)
+    i = dict(raw=raw, ref=ref.float())
+    v = _value(p, g, S) * 3
+    if p.get("value") == "h8":
+        i["vhi"], i["value"] = (t.reshape(Bn * S, M * D) for t in h8_exact(v, g))
+    else:
+        i["value"] = v.reshape(Bn * S, M * D)
+    return i
+
+
+def ref_msda_fused(i, p, mut=None, parts=False):
+    """parts: (r, the derived part of the bound, S1) -- what EXPF_EXCESS (top of the module) is measured with: max over the elements of
+    (|y - r| - derived) / S1."""
+    levels, starts, S = msda_geometry(p)
+    Bn, M, D, Lq, P, L = p["B"], p["M"], p["D"], p["Lq"], p["P"], len(levels)
+    LP = L * P
+    raw, ref = i["raw"], i["ref"]
+    dt = raw.dtype
+    off = raw[:, :M * LP * 2].reshape(Bn, Lq, M, L, P, 2)
+    logit = raw[:, M * LP * 2:].reshape(Bn, Lq, M, LP)
+    wgt = (torch.softmax(logit.view(Bn, Lq, M, L, P), -1) if mut == "softmaxP" else torch.softmax(logit, -1).view(Bn, Lq, M, L, P))
+    size = _size(levels, dt)
+    rr = ref.view(1, Lq, 1, 1, 1, 2)
+    loc = rr + off / size
+    planes = p.get("value") == "h8"
+    value = (i["vhi"] if planes and not p.get("lo_bytes") else i["value"]).view(Bn, S, M, D)
+    out, s1, T = _gather(value, levels, starts, loc, wgt, mut)
+    r = out.reshape(Bn * Lq, M * D)
+    if dt != torch.float64 or mut:
+        return r, None
+    pos = 0.0
+    if not p.get("dyadic"):
+        e = (4 * U * ((rr * size).abs() + off.abs() + 0.5)).sum(-1)
+        pos = ((wgt * e)[..., None] * T).sum((3, 4))
+    n = LP * ((8 if p.get("lo_bytes") else 4) if planes else 1)
+    wrel = (LP + 6 + (logit - logit.amax(-1, keepdim=True)).abs().amax(-1)) * U                      # [B, Lq, M]
+    derived = ((n + 12) * U * s1 + wrel[..., None] * s1 + pos).reshape(Bn * Lq, M * D)
+    s1 = s1.reshape(Bn * Lq, M * D)
+    if parts:
+        return r, derived, s1
+    return r, derived + 2 * EXPF_EXCESS * s1
+
+
 OPS = {
+    "layernorm_rows": (make_layernorm_rows, ref_layernorm_rows), "rowstats": (make_rowstats, ref_rowstats), "msda": (make_msda, ref_msda),
+    "msda_fused": (make_msda_fused, ref_msda_fused),
     "dwconv": (make_dwconv, ref_dwconv), "gconv": (make_gconv, ref_gconv), "gfe_qkv": (make_gfe_qkv, ref_gfe_qkv),
     "dwpair_gate": (make_dwpair_gate, ref_dwpair_gate), "ca_apply": (make_ca_apply, ref_ca_apply), "gelu_gate": (make_gelu_gate, ref_gelu_gate),
     "pool_hw": (make_pool_hw, ref_pool_hw), "colstats": (make_colstats, ref_colstats), "ffrm": (make_ffrm, ref_ffrm), "lnhw": (make_lnhw, ref_lnhw),
