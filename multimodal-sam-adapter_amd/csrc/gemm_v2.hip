@@ -610,8 +610,9 @@ int mmsa_gemm_v2_launch(const unsigned short* Ap, long lda, long strideA,
   a.debug = MMSA_KNOB("MMSA_GEMM_DEBUG", 0);
 #endif
   // 96-column tiles when they occupy the CUs better: rounds(tiles) x relative tile cost (0.75) against rounds of 128-column tiles.
-  // fp32 output only (the planes epilogue writes whole 64-column strips) and no pixel-shuffle / broadcast-residual store.
-  if (!Cp && out_mode == 0 && resid_mod <= 0 && N >= 96 && N % 96 == 0 && !rs_out && !h8c) {   // (a ragged last 96-column tile would run the element-wise
+  // fp32 output only (the planes epilogue writes whole 64-column strips) and no pixel-shuffle / broadcast-residual store.  Not for a row-normalising launch either: on an
+  // fp32 output only the register-resident "rows" epilogue has that form, and it declines 96-column tiles -- the staged epilogue would store acc + bias, un-normalised.
+  if (!Cp && out_mode == 0 && resid_mod <= 0 && N >= 96 && N % 96 == 0 && !rs_out && !rn_mr && !h8c) {   // (a ragged last 96-column tile would run the element-wise
     // epilogue: N = 256 -- the ConvFFN fc1 of the extractors -- was routed here and spent 40 of its 92 us in it, profiles/r03_v3_vs_v2.txt)
     const bool no96 = MMSA_KNOB("MMSA_GEMM_NO96", 0) != 0;   // A/B aid (debug-knob builds)
     const int nbn96 = cdiv(N, 96);

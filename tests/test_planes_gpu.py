@@ -7,6 +7,7 @@ import torch.nn.functional as F
 from oracle import ref_encoder as R
 from tests.weights import seeded_state_dict
 from tests.util import assert_close
+from tests.gemm_ref import _h8_emulated_product, _h8c_emulated_product
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -652,15 +653,6 @@ def test_gemm_stream_kernel(ops, M, N, K, fmt_name, mode):
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # "h8" operand planes (fp16 hi + e5m2 cross-term bytes; csrc/common.h): format, the GEMM on them, and the producers that emit them
-def _h8_emulated_product(a, w):
-    """What the kernel computes, restated with torch casts: hi.hi exactly + the two cross terms with e5m2-rounded operands."""
-    ah = a.clamp(-57344, 57344).half().float()
-    wh = w.clamp(-57344, 57344).half().float()
-    al, wl = (a - ah) * 2048, (w - wh) * 2048
-    q = lambda t: t.to(torch.float8_e5m2).float()
-    return ah.double() @ wh.double().t() + (q(ah).double() @ q(wl).double().t() + q(al).double() @ q(wh).double().t()) / 2048
-
-
 def test_split_planes_h8_roundtrip_and_layout(ops):
     x = torch.randn(37, 50, generator=g(41)) * 3
     for weight in (False, True):
@@ -733,17 +725,6 @@ def test_gemm_h8_exact_on_integers_and_cross_terms(ops):
 # "h8c" operand planes (round 4; csrc/common.h, csrc/gemm_h8c.hip): the h8 arithmetic on 3 bytes per element, rows stored in pairs, q(hi) taken
 # in registers as the fp16 value's top byte (truncation)
 H8C_LO_COMP = 1.09375
-
-
-def _h8c_emulated_product(a, w):
-    """hi.hi exactly + the two cross terms with q(hi) = the fp16 hi value truncated to its top byte (an e5m2) and lo rounded to e5m2 after the
-    scaling by 2^11 x 1.09375 that makes up for the truncation's mean (csrc/common.h MMSA_H8C_LO_COMP; the MFMA's block scale undoes the 2^11)."""
-    ah = a.clamp(-57344, 57344).half()
-    wh = w.clamp(-57344, 57344).half()
-    al, wl = (a - ah.float()) * (2048 * H8C_LO_COMP), (w - wh.float()) * (2048 * H8C_LO_COMP)
-    q = lambda t: t.to(torch.float8_e5m2).float()
-    trunc = lambda h: (h.view(torch.int16) & -256).view(torch.float16).float()
-    return ah.double() @ wh.double().t() + (trunc(ah).double() @ q(wl).double().t() + q(al).double() @ trunc(wh).double().t()) / 2048
 
 
 def test_split_planes_h8c_roundtrip_and_layout(ops):
