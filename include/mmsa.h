@@ -370,6 +370,24 @@ int mmsa_softmax_flip_accum_nchw(const float* logits, float* acc, int B, int C, 
 int mmsa_aug_argmax(const float* const* logits, const int* views, int A, int C, const int* windows, const int* windows_host, int total,
                     unsigned char* out, int B, int Ho, int Wo, int* uncovered, mmsa_stream_t stream);
 
+/* --- confidence maps: next to every class map above, the probability of the class it names -- conf[b, y, x] = max_c P[b, c, y, x], float32 [B, Ho, Wo],
+ *     with P what EncoderDecoder.inference returns (F.softmax(seg_logit, dim=1), ED:449,460; for several views their mean, ED:538-541).  One view, with
+ *     x_c the pixel's logits after the resize stages: m = max_c x_c; s = e_0, s += e_c in class order, e_c = expf(x_c - m); conf = expf(m - m) / s, which
+ *     is P at the first maximum and so the largest P.  Several views: conf = max_c (sum over the views of P_a[c]) / A.  Bit for bit the maximum over C of
+ *     the mmsa_softmax_flip_accum_nchw canvas path.  A pixel the one-pass kernels mark 255 (a tap without a window, or more than 8) gets conf = 0.
+ *     Each entry is its sibling above with `conf` (not NULL) after `out`: same arguments, same checks, same class map. --- */
+/* mmsa_argmax_nchw that also writes the maximum, maxval float [B, HW]: on a canvas of probabilities, the class map and its confidence (ED:449,460,477). */
+int mmsa_argmax_max_nchw(const float* x, unsigned char* out, float* maxval, int B, int C, long HW, mmsa_stream_t stream);
+/* mmsa_slide_argmax + conf [B, H, W] (ED:449,460 on the averaged logits of ED:213-225). */
+int mmsa_slide_argmax_conf(const float* logits, int n, int C, int hs, int ws, const int* windows, unsigned char* out, float* conf, int B, int H, int W,
+                           int hc, int wc, int* uncovered, mmsa_stream_t stream);
+/* mmsa_slide_argmax_resized + conf [B, Hcut, Wcut] (ED:449,460 on the logits at the rescaled size). */
+int mmsa_slide_argmax_resized_conf(const float* logits, int n, int C, int hs, int ws, const int* windows, unsigned char* out, float* conf, int B, int H,
+                                   int W, int hc, int wc, int Hd, int Wd, int Hcut, int Wcut, int* uncovered, mmsa_stream_t stream);
+/* mmsa_aug_argmax + conf [B, Ho, Wo] (ED:449,460 per view, the mean of ED:538-541, its maximum over the classes). */
+int mmsa_aug_argmax_conf(const float* const* logits, const int* views, int A, int C, const int* windows, const int* windows_host, int total,
+                         unsigned char* out, float* conf, int B, int Ho, int Wo, int* uncovered, mmsa_stream_t stream);
+
 /* --- the input side of the test pipelines (segmentation/mmseg_custom/datasets/pipelines/transform.py): Pad_multimodal (2934-3010, impad bottom /
  *     right) -> Normalize_multimodal / Normalize_multimodal_Muses (2601-2825: `/ 255` when norm_by_max, mmcv.imnormalize = channel reversal when
  *     to_rgb, subtract mean, multiply by 1 / float64(std)) -> ImageToTensor (HWC -> CHW) -> Collectmod, from the loaders' frames in one pass.

@@ -107,8 +107,10 @@ __device__ __forceinline__ bool aug_view_logits(const AugView& v, const int* __r
 // One lane owns one output pixel and two columns of C floats in LDS, laid out [c][lane] (consecutive lanes, consecutive banks): this view's logits,
 // overwritten by their exponentials, and the probabilities summed over the views so far.  The columns are private to the lane: no barrier anywhere.
 // T = blockDim.x = 256 / 128 / 64 lanes for C <= 32 / 64 / 128 keeps the 2 C T floats within 64 KiB.
-__global__ __launch_bounds__(256) void aug_argmax_kernel(AugViews av, int C, const int* __restrict__ windows, unsigned char* __restrict__ out, int Ho, int Wo,
-                                                         int* __restrict__ uncovered) {
+// CONF: `best`, the mean probability of the predicted class, also goes to conf float [B, Ho, Wo] (0 for a 255 pixel).
+template <bool CONF>
+__device__ __forceinline__ void aug_pixel(const AugViews& av, int C, const int* __restrict__ windows, unsigned char* __restrict__ out, float* __restrict__ conf,
+                                          int Ho, int Wo, int* __restrict__ uncovered) {
   extern __shared__ float aug_lds[];
   const int T = blockDim.x;
   const int X = blockIdx.x * T + threadIdx.x, Y = blockIdx.y, b = blockIdx.z;
@@ -122,6 +124,7 @@ __global__ __launch_bounds__(256) void aug_argmax_kernel(AugViews av, int C, con
     if (!aug_view_logits(v, windows, C, b, v.flip == 2 ? Ho - 1 - Y : Y, v.flip == 1 ? Wo - 1 - X : X, xs, T)) {
       atomicAdd(uncovered, 1);      // a tap without a window, or with more than 8, in ANY view: counted once per output pixel, and the pixel gets 255
       out[op] = 255;
+      if constexpr (CONF) conf[op] = 0.f;
       return;
     }
     float m = xs[0];
@@ -141,18 +144,30 @@ __global__ __launch_bounds__(256) void aug_argmax_kernel(AugViews av, int C, con
     if (c == 0 || p > best) { best = p; bi = c; }      // first maximum wins, like torch.argmax on ties
   }
   out[op] = (unsigned char)bi;
+  if constexpr (CONF) conf[op] = best;      // max_c of the mean probabilities: what the argmax above compared
+}
+
+__global__ __launch_bounds__(256) void aug_argmax_kernel(AugViews av, int C, const int* __restrict__ windows, unsigned char* __restrict__ out, int Ho, int Wo,
+                                                         int* __restrict__ uncovered) {
+  aug_pixel<false>(av, C, windows, out, nullptr, Ho, Wo, uncovered);
+}
+
+// aug_argmax_kernel + the confidence map of the augmented frame: conf = max_c mean_a P_a[c] (ED:449,460 + ED:538-541).
+__global__ __launch_bounds__(256) void aug_argmax_conf_kernel(AugViews av, int C, const int* __restrict__ windows, unsigned char* __restrict__ out,
+                                                              float* __restrict__ conf, int Ho, int Wo, int* __restrict__ uncovered) {
+  aug_pixel<true>(av, C, windows, out, conf, Ho, Wo, uncovered);
 }
 
 #define AUG_VIEW_INTS 11      // one row of `views`: w0, n, hs, ws, H, W, hc, wc, Hd, Wd, flip
 
-extern "C" int mmsa_aug_argmax(const float* const* logits /* HOST [A] device pointers */, const int* views /* HOST [A, 11] */, int A, int C,
-                               const int* windows /* DEVICE [total, 3] */, const int* windows_host /* HOST copy of it */, int total, unsigned char* out,
-                               int B, int Ho, int Wo, int* uncovered /* device int, zeroed by the caller */, hipStream_t stream) {
-  MMSA_CHECK_ARG(A >= 1 && A <= MMSA_MAX_AUGS, "aug_argmax: %d views, 1..%d per call", A, MMSA_MAX_AUGS);
-  MMSA_CHECK_ARG(C >= 1 && C <= 128, "aug_argmax: %d classes; the per-pixel columns of more than 128 do not fit 64 KiB of LDS (use the canvas path: "
-                 "mmsa_softmax_flip_accum_nchw per view + mmsa_argmax_nchw)", C);
+// the checks and the launch of both entries; `conf` given: aug_argmax_conf_kernel
+static int aug_argmax_launch(const char* name, const float* const* logits, const int* views, int A, int C, const int* windows, const int* windows_host, int total,
+                             unsigned char* out, float* conf, int B, int Ho, int Wo, int* uncovered, hipStream_t stream) {
+  MMSA_CHECK_ARG(A >= 1 && A <= MMSA_MAX_AUGS, "%s: %d views, 1..%d per call", name, A, MMSA_MAX_AUGS);
+  MMSA_CHECK_ARG(C >= 1 && C <= 128, "%s: %d classes; the per-pixel columns of more than 128 do not fit 64 KiB of LDS (use the canvas path: "
+                 "mmsa_softmax_flip_accum_nchw per view + mmsa_argmax_nchw)", name, C);
   MMSA_CHECK_ARG(logits && views && windows && windows_host && out && uncovered && total > 0 && B > 0 && Ho > 0 && Wo > 0 && Ho <= 65535 && B <= 65535,
-                 "aug_argmax: bad args");
+                 "%s: bad args", name);
   AugViews av;
   av.A = A;
   for (int a = 0; a < A; ++a) {
@@ -162,20 +177,35 @@ extern "C" int mmsa_aug_argmax(const float* const* logits /* HOST [A] device poi
     v.w0 = r[0]; v.n = r[1]; v.hs = r[2]; v.ws = r[3]; v.H = r[4]; v.W = r[5]; v.hc = r[6]; v.wc = r[7]; v.flip = r[10];
     const int Hd = r[8], Wd = r[9];
     MMSA_CHECK_ARG(v.logits && v.hs > 0 && v.ws > 0 && v.H > 0 && v.W > 0 && v.hc > 0 && v.wc > 0 && v.flip >= 0 && v.flip <= 2,
-                   "aug_argmax: view %d: bad sizes or flip (0 none, 1 horizontal, 2 vertical)", a);
-    MMSA_CHECK_ARG(Hd > 0 && Wd > 0 && Ho <= Hd && Wo <= Wd, "aug_argmax: view %d: the cut %dx%d must lie inside the target %dx%d", a, Ho, Wo, Hd, Wd);
-    MMSA_CHECK_ARG(v.n > 0 && v.n <= MMSA_MAX_WINDOWS && v.w0 >= 0 && (long)v.w0 + v.n <= total, "aug_argmax: view %d: 1..%d windows per view, inside the table of %d rows",
-                   a, MMSA_MAX_WINDOWS, total);
+                   "%s: view %d: bad sizes or flip (0 none, 1 horizontal, 2 vertical)", name, a);
+    MMSA_CHECK_ARG(Hd > 0 && Wd > 0 && Ho <= Hd && Wo <= Wd, "%s: view %d: the cut %dx%d must lie inside the target %dx%d", name, a, Ho, Wo, Hd, Wd);
+    MMSA_CHECK_ARG(v.n > 0 && v.n <= MMSA_MAX_WINDOWS && v.w0 >= 0 && (long)v.w0 + v.n <= total, "%s: view %d: 1..%d windows per view, inside the table of %d rows",
+                   name, a, MMSA_MAX_WINDOWS, total);
     for (int k = 0; k < v.n; ++k) {      // as fill_windows of segment.hip
       const int* w = windows_host + 3 * (long)(v.w0 + k);
       MMSA_CHECK_ARG(w[0] >= 0 && w[0] < B && w[1] >= 0 && w[2] >= 0 && w[1] + v.hc <= v.H && w[2] + v.wc <= v.W,
-                     "aug_argmax: view %d window %d (image %d, y0 %d, x0 %d, %dx%d) outside the [%d, %d, %d] input", a, k, w[0], w[1], w[2], v.hc, v.wc, B, v.H, v.W);
+                     "%s: view %d window %d (image %d, y0 %d, x0 %d, %dx%d) outside the [%d, %d, %d] input", name, a, k, w[0], w[1], w[2], v.hc, v.wc, B, v.H, v.W);
     }
     v.rh = (float)v.hs / (float)v.hc; v.rw = (float)v.ws / (float)v.wc;
     v.rh2 = (float)v.H / (float)Hd; v.rw2 = (float)v.W / (float)Wd;
   }
   const int T = C <= 32 ? 256 : C <= 64 ? 128 : 64;
-  hipLaunchKernelGGL(aug_argmax_kernel, dim3(cdiv(Wo, T), Ho, B), dim3(T), (size_t)2 * C * T * sizeof(float), stream, av, C, windows, out, Ho, Wo, uncovered);
-  MMSA_CHECK_LAUNCH("aug_argmax");
+  const size_t lds = (size_t)2 * C * T * sizeof(float);
+  if (conf) hipLaunchKernelGGL(aug_argmax_conf_kernel, dim3(cdiv(Wo, T), Ho, B), dim3(T), lds, stream, av, C, windows, out, conf, Ho, Wo, uncovered);
+  else hipLaunchKernelGGL(aug_argmax_kernel, dim3(cdiv(Wo, T), Ho, B), dim3(T), lds, stream, av, C, windows, out, Ho, Wo, uncovered);
+  MMSA_CHECK_LAUNCH(name);
   return MMSA_OK;
+}
+
+extern "C" int mmsa_aug_argmax(const float* const* logits /* HOST [A] device pointers */, const int* views /* HOST [A, 11] */, int A, int C,
+                               const int* windows /* DEVICE [total, 3] */, const int* windows_host /* HOST copy of it */, int total, unsigned char* out,
+                               int B, int Ho, int Wo, int* uncovered /* device int, zeroed by the caller */, hipStream_t stream) {
+  return aug_argmax_launch("aug_argmax", logits, views, A, C, windows, windows_host, total, out, nullptr, B, Ho, Wo, uncovered, stream);
+}
+
+extern "C" int mmsa_aug_argmax_conf(const float* const* logits /* HOST [A] device pointers */, const int* views /* HOST [A, 11] */, int A, int C,
+                                    const int* windows /* DEVICE [total, 3] */, const int* windows_host /* HOST copy of it */, int total, unsigned char* out,
+                                    float* conf, int B, int Ho, int Wo, int* uncovered /* device int, zeroed by the caller */, hipStream_t stream) {
+  MMSA_CHECK_ARG(conf, "aug_argmax_conf: bad args (conf is NULL)");
+  return aug_argmax_launch("aug_argmax_conf", logits, views, A, C, windows, windows_host, total, out, conf, B, Ho, Wo, uncovered, stream);
 }

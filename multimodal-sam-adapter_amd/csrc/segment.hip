@@ -4,7 +4,8 @@
 //                         slide inference, ADDED (preds += F.pad(crop_seg_logit, ...), count_mat[...] += 1, ED:213-219) -- into a
 //                         window (y0, x0, hc, wc) of a [B, C, Hd, Wd] canvas;
 //   div_count_nchw      : preds / count_mat (ED:225);
-//   argmax_nchw         : seg_logit.argmax(dim=1) (ED:477; the softmax of ED:449 is monotonic) -> uint8 class map.
+//   argmax_nchw         : seg_logit.argmax(dim=1) (ED:477; the softmax of ED:449 is monotonic) -> uint8 class map;
+//   argmax_max_nchw     : the same, and the maximum itself -> float32 [B, H, W]: on probabilities, the confidence map.
 // All are one pass over the canvas, HBM-bound.
 #include "common.h"
 #include "eval_hist.h"
@@ -14,6 +15,7 @@
 // tie in the other (seen once in 2 073 600 pixels of a 1080 x 1920 frame, where the compiler had contracted the two differently).
 #pragma clang fp contract(off)
 #include "slide_taps.h"   // WindowTable and the tap arithmetic of the rescaled class map (shared with augment.hip)
+#include "softmax_px.h"   // the softmax of the confidence variants (shared with augment.hip)
 
 __global__ __launch_bounds__(256) void bilinear_accum_kernel(const float* __restrict__ src, int C, int hs, int ws, long sstrideB,
                                                              float* __restrict__ dst, int Hd, int Wd, int y0, int x0, int hc, int wc,
@@ -128,10 +130,12 @@ extern "C" int mmsa_crop_batch_nchw(const float* src, int B, int C, int H, int W
 __global__ __launch_bounds__(256) void slide_argmax_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
                                                            int H, int W, int hc, int wc, float rh, float rw, WindowTable wt, int* __restrict__ uncovered) {
 #define SLIDE_EVAL 0
+#define SLIDE_CONF 0
 #define SLIDE_Y blockIdx.y
 #define SLIDE_EXIT return
 #include "slide_pixel.inc"
 #undef SLIDE_EVAL
+#undef SLIDE_CONF
 #undef SLIDE_Y
 #undef SLIDE_EXIT
 }
@@ -153,10 +157,12 @@ __global__ __launch_bounds__(256) void slide_argmax_eval_kernel(const float* __r
   const int row1 = min(H, ((int)blockIdx.y + 1) * SLIDE_EVAL_ROWS);
   for (int row = (int)blockIdx.y * SLIDE_EVAL_ROWS; row < row1; ++row) {
 #define SLIDE_EVAL 1
+#define SLIDE_CONF 0
 #define SLIDE_Y row
 #define SLIDE_EXIT continue
 #include "slide_pixel.inc"
 #undef SLIDE_EVAL
+#undef SLIDE_CONF
 #undef SLIDE_Y
 #undef SLIDE_EXIT
   }
@@ -207,62 +213,9 @@ extern "C" int mmsa_slide_argmax_eval(const float* logits, int n, int C, int hs,
 __global__ __launch_bounds__(256) void slide_argmax_resized_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
                                                                    int H, int W, int hc, int wc, float rh, float rw, int Hcut, int Wcut, float rh2, float rw2,
                                                                    WindowTable wt, int* __restrict__ uncovered) {
-  const int X = blockIdx.x * 256 + threadIdx.x, Y = blockIdx.y, b = blockIdx.z;
-  if (X >= Wcut) return;
-  // second stage: the taps of output pixel (Y, X) in the H x W canvas (bilinear_accum_kernel with src = the canvas)
-  float sh2 = ((float)Y + 0.5f) * rh2 - 0.5f, sw2 = ((float)X + 0.5f) * rw2 - 0.5f;
-  sh2 = sh2 < 0.f ? 0.f : sh2;
-  sw2 = sw2 < 0.f ? 0.f : sw2;
-  const int y0 = min((int)sh2, H - 1), x0 = min((int)sw2, W - 1);
-  const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
-  const float lh2 = sh2 - (float)y0, lw2 = sw2 - (float)x0;
-  // first stage: the covering windows of each tap (tap t: row y0 / y1 = t >> 1, column x0 / x1 = t & 1).  Slot arrays only ever indexed by unrolled constants.
-  TapSlots tp[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    tp[t].nk = 0;
-#pragma unroll
-    for (int q = 0; q < RESIZED_SLOTS; ++q) { tp[t].o[q] = tp[t].kf[q] = 0; tp[t].lh[q] = tp[t].lw[q] = 0.f; }
-  }
-  for (int k = 0; k < wt.n; ++k) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      int o, kf;
-      float lh, lw;
-      if (!tap_coords(wt, k, b, t >> 1 ? y1 : y0, t & 1 ? x1 : x0, hc, wc, hs, ws, rh, rw, o, kf, lh, lw)) continue;
-#pragma unroll
-      for (int q = 0; q < RESIZED_SLOTS; ++q)
-        if (q == tp[t].nk) { tp[t].o[q] = o; tp[t].kf[q] = kf; tp[t].lh[q] = lh; tp[t].lw[q] = lw; }
-      ++tp[t].nk;
-    }
-  }
-  const int nmin = min(min(tp[0].nk, tp[1].nk), min(tp[2].nk, tp[3].nk)), nmax = max(max(tp[0].nk, tp[1].nk), max(tp[2].nk, tp[3].nk));
-  const long op = ((long)b * Hcut + Y) * Wcut + X;
-  if (nmin == 0 || nmax > 8) {      // a tap without a window, or with more than 8: counted once per output pixel, and the pixel gets 255
-    atomicAdd(uncovered, 1);
-    out[op] = 255;
-    return;
-  }
-  float best = -INFINITY;
-  int bi = 0;
-  if (nmax <= RESIZED_SLOTS) {
-    for (int c = 0; c < C; ++c) {
-      const float p00 = tap_value(tp[0], logits, C, c, hs, ws), p01 = tap_value(tp[1], logits, C, c, hs, ws);
-      const float p10 = tap_value(tp[2], logits, C, c, hs, ws), p11 = tap_value(tp[3], logits, C, c, hs, ws);
-      const float p = (1.f - lh2) * ((1.f - lw2) * p00 + lw2 * p01) + lh2 * ((1.f - lw2) * p10 + lw2 * p11);
-      if (c == 0 || p > best) { best = p; bi = c; }
-    }
-  } else {
-    for (int c = 0; c < C; ++c) {
-      const float p00 = tap_value_scan(wt, b, y0, x0, tp[0].nk, logits, C, c, hs, ws, hc, wc, rh, rw);
-      const float p01 = tap_value_scan(wt, b, y0, x1, tp[1].nk, logits, C, c, hs, ws, hc, wc, rh, rw);
-      const float p10 = tap_value_scan(wt, b, y1, x0, tp[2].nk, logits, C, c, hs, ws, hc, wc, rh, rw);
-      const float p11 = tap_value_scan(wt, b, y1, x1, tp[3].nk, logits, C, c, hs, ws, hc, wc, rh, rw);
-      const float p = (1.f - lh2) * ((1.f - lw2) * p00 + lw2 * p01) + lh2 * ((1.f - lw2) * p10 + lw2 * p11);
-      if (c == 0 || p > best) { best = p; bi = c; }
-    }
-  }
-  out[op] = (unsigned char)bi;
+#define RESIZED_CONF 0
+#include "slide_resized_pixel.inc"
+#undef RESIZED_CONF
 }
 
 extern "C" int mmsa_slide_argmax_resized(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out,
@@ -278,5 +231,124 @@ extern "C" int mmsa_slide_argmax_resized(const float* logits, int n, int C, int 
   hipLaunchKernelGGL(slide_argmax_resized_kernel, dim3(cdiv(Wcut, 256), Hcut, B), dim3(256), 0, stream, logits, C, hs, ws, out, H, W, hc, wc,
                      (float)hs / (float)hc, (float)ws / (float)wc, Hcut, Wcut, (float)H / (float)Hd, (float)W / (float)Wd, wt, uncovered);
   MMSA_CHECK_LAUNCH("slide_argmax_resized");
+  return MMSA_OK;
+}
+
+// ---- confidence maps: the probability of the predicted class next to every class map, conf[b, y, x] = max_c P[b, c, y, x] with P the probabilities of
+// EncoderDecoder.inference (F.softmax(seg_logit, dim=1), ED:449,460), written by the launch that writes the map.  The arithmetic is csrc/softmax_px.h:
+// m = max_c x_c; s = e_0, s += e_c in class order, e_c = expf(x_c - m); conf = expf(m - m) / s -- P at the first maximum, which is the largest P.  The
+// kernels stand BELOW the ones they extend so that those keep their place in the file and with it their instruction streams, label for label
+// (profiles/confidence_isa.txt).
+
+// argmax_nchw_kernel that also writes the maximum: on the probabilities of the canvas paths (mmsa_softmax_flip_accum_nchw), the confidence map
+// max_c P[b, c, y, x] of ED:449,460 next to the class map, from one read of the canvas.
+__global__ __launch_bounds__(256) void argmax_max_nchw_kernel(const float* __restrict__ x, unsigned char* __restrict__ out, float* __restrict__ maxval, int C,
+                                                              long HW, long total) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;   // b * HW + p
+  if (i >= total) return;
+  const long b = i / HW, p = i - b * HW;
+  const float* xp = x + b * C * HW + p;
+  float best = xp[0];
+  int bi = 0;
+  for (int c = 1; c < C; ++c) {
+    const float v = xp[(long)c * HW];
+    if (v > best) { best = v; bi = c; }
+  }
+  out[i] = (unsigned char)bi;
+  maxval[i] = best;
+}
+
+extern "C" int mmsa_argmax_max_nchw(const float* x, unsigned char* out, float* maxval, int B, int C, long HW, hipStream_t stream) {
+  MMSA_CHECK_ARG(x && out && maxval && B > 0 && C > 0 && C <= 256 && HW > 0, "argmax_max_nchw: bad args (C <= 256 for the uint8 map)");
+  const long total = (long)B * HW;
+  hipLaunchKernelGGL(argmax_max_nchw_kernel, dim3(cdiv(total, 256)), dim3(256), 0, stream, x, out, maxval, C, HW, total);
+  MMSA_CHECK_LAUNCH("argmax_max_nchw");
+  return MMSA_OK;
+}
+
+// slide_argmax_kernel + the confidence map: conf[b, y, x] = max_c softmax(preds / count)[c], the probability of the class the map names (ED:449,460).  The
+// sum of the exponentials needs the maximum first, so the pixel's C values are needed twice; two forms (slide_pixel.inc), chosen by measurement
+// (profiles/confidence.txt):
+//   slide_argmax_conf_lds_kernel : the first pass keeps them in a per-lane LDS column [c][lane], as aug_argmax_kernel does -- C * 256 floats of dynamic LDS,
+//                                  so C <= SLIDE_CONF_LDS_CLASSES = 64 (64 KiB); the faster form -- within the spread of the plain kernel (+ 7 / - 15 us) where the other
+//                                  costs + 97 / + 330 us (two 1024 x 1024 maps / the six-window 1080 x 1920 frame, 25 classes) -- and the one the entry
+//                                  takes wherever it fits;
+//   slide_argmax_conf_kernel     : a second pass recomputes them (the same operations on the same inputs, the same bits): no LDS, any C the map allows.
+// Both take 160 registers.  Bit for bit max over C of mmsa_softmax_flip_accum_nchw on the canvas path's logits, either way.
+#define SLIDE_CONF_LDS_CLASSES 64
+__global__ __launch_bounds__(256) void slide_argmax_conf_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
+                                                                float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, WindowTable wt,
+                                                                int* __restrict__ uncovered) {
+#define SLIDE_EVAL 0
+#define SLIDE_CONF 1
+#define SLIDE_Y blockIdx.y
+#define SLIDE_EXIT return
+#include "slide_pixel.inc"
+#undef SLIDE_EVAL
+#undef SLIDE_CONF
+#undef SLIDE_Y
+#undef SLIDE_EXIT
+}
+
+__global__ __launch_bounds__(256) void slide_argmax_conf_lds_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
+                                                                    float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, WindowTable wt,
+                                                                    int* __restrict__ uncovered) {
+  extern __shared__ float conf_lds[];
+  float* conf_col = conf_lds + threadIdx.x;      // private to the lane: no barrier
+#define SLIDE_EVAL 0
+#define SLIDE_CONF 2
+#define SLIDE_Y blockIdx.y
+#define SLIDE_EXIT return
+#include "slide_pixel.inc"
+#undef SLIDE_EVAL
+#undef SLIDE_CONF
+#undef SLIDE_Y
+#undef SLIDE_EXIT
+}
+
+extern "C" int mmsa_slide_argmax_conf(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out, float* conf,
+                                      int B, int H, int W, int hc, int wc, int* uncovered /* device int, zeroed by the caller */, hipStream_t stream) {
+  MMSA_CHECK_ARG(logits && out && conf && uncovered && C > 0 && C <= 255 && hs > 0 && ws > 0 && hc > 0 && wc > 0 && B > 0 && H <= 65535 && B <= 65535,
+                 "slide_argmax_conf: bad args");
+  WindowTable wt;
+  int rc = fill_windows(wt, windows, n, B, H, W, hc, wc, "slide_argmax_conf");
+  if (rc) return rc;
+#ifdef MMSA_CONF_SECOND_PASS      // measurement build only (tools/exp/confidence_bench.py): the second-pass form for every C
+  const bool lds = false;
+#else
+  const bool lds = C <= SLIDE_CONF_LDS_CLASSES;
+#endif
+  if (lds)
+    hipLaunchKernelGGL(slide_argmax_conf_lds_kernel, dim3(cdiv(W, 256), H, B), dim3(256), (size_t)C * 256 * sizeof(float), stream, logits, C, hs, ws, out, conf,
+                       H, W, hc, wc, (float)hs / (float)hc, (float)ws / (float)wc, wt, uncovered);
+  else
+    hipLaunchKernelGGL(slide_argmax_conf_kernel, dim3(cdiv(W, 256), H, B), dim3(256), 0, stream, logits, C, hs, ws, out, conf, H, W, hc, wc,
+                       (float)hs / (float)hc, (float)ws / (float)wc, wt, uncovered);
+  MMSA_CHECK_LAUNCH("slide_argmax_conf");
+  return MMSA_OK;
+}
+
+// slide_argmax_resized_kernel + the confidence map at the rescaled / cut size: conf = max_c softmax(resized)[c] (ED:449,460), slot form and scanning form.
+__global__ __launch_bounds__(256) void slide_argmax_resized_conf_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
+                                                                        float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, int Hcut,
+                                                                        int Wcut, float rh2, float rw2, WindowTable wt, int* __restrict__ uncovered) {
+#define RESIZED_CONF 1
+#include "slide_resized_pixel.inc"
+#undef RESIZED_CONF
+}
+
+extern "C" int mmsa_slide_argmax_resized_conf(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out,
+                                              float* conf, int B, int H, int W, int hc, int wc, int Hd, int Wd, int Hcut, int Wcut,
+                                              int* uncovered /* device int, zeroed by the caller */, hipStream_t stream) {
+  MMSA_CHECK_ARG(logits && out && conf && uncovered && C > 0 && C <= 255 && hs > 0 && ws > 0 && hc > 0 && wc > 0 && B > 0 && H > 0 && W > 0 && B <= 65535,
+                 "slide_argmax_resized_conf: bad args");
+  MMSA_CHECK_ARG(Hd > 0 && Wd > 0 && Hcut > 0 && Wcut > 0 && Hcut <= Hd && Wcut <= Wd && Hcut <= 65535,
+                 "slide_argmax_resized_conf: the cut %dx%d must lie inside the target %dx%d (and have at most 65535 rows)", Hcut, Wcut, Hd, Wd);
+  WindowTable wt;
+  int rc = fill_windows(wt, windows, n, B, H, W, hc, wc, "slide_argmax_resized_conf");
+  if (rc) return rc;
+  hipLaunchKernelGGL(slide_argmax_resized_conf_kernel, dim3(cdiv(Wcut, 256), Hcut, B), dim3(256), 0, stream, logits, C, hs, ws, out, conf, H, W, hc, wc,
+                     (float)hs / (float)hc, (float)ws / (float)wc, Hcut, Wcut, (float)H / (float)Hd, (float)W / (float)Wd, wt, uncovered);
+  MMSA_CHECK_LAUNCH("slide_argmax_resized_conf");
   return MMSA_OK;
 }

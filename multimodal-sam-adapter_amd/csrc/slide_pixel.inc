@@ -1,11 +1,17 @@
-// The pixel body of the two class-map kernels of csrc/segment.hip, included once per kernel (like the GEMM epilogues' .inc files):
+// The pixel body of the frame-size class-map kernels of csrc/segment.hip, included once per kernel (like the GEMM epilogues' .inc files):
 //   SLIDE_EVAL 0: slide_argmax_kernel, statement for statement what it always was;
 //   SLIDE_EVAL 1: slide_argmax_eval_kernel -- the pixel's (label class, predicted class) pair also goes into the workgroup's LDS histogram
 //                 `hist` (csrc/eval_hist.h; `ev` = the label side, `lut_s` = its LUT in LDS) and the map is written only when `out` is given.
+//   SLIDE_CONF 1: slide_argmax_conf_kernel (with SLIDE_EVAL 0) -- the probability of the predicted class also goes to `conf` float [B, H, W]: the softmax of
+//                 csrc/softmax_px.h over the pixel's averaged logits, whose maximum m is `best`, so that its numerator is expf(m - m).  The sum of the
+//                 exponentials needs m first, hence a SECOND pass over the classes that recomputes acc / cnt (the same operations on the same inputs, the
+//                 same bits): no LDS, no limit on C beyond the map's.  An uncovered pixel (map 255) gets 0.
+//   SLIDE_CONF 2: slide_argmax_conf_lds_kernel -- the same, but the first pass keeps the pixel's values in the per-lane LDS column conf_col[c * 256], as
+//                 aug_argmax_kernel does, and the second pass reads them back: the faster form (segment.hip has the figures), for C * 256 floats <= 64 KiB.
 // SLIDE_Y is the pixel's row: blockIdx.y in the first kernel, the row variable of the second kernel's loop over its workgroup's rows.
 // SLIDE_EXIT leaves the body: `return` in the first kernel, `continue` with the next row in the second, which still has its histogram to flush.
 // SLIDE_EXIT MUST NOT be used inside a loop of this body: there `continue` would go on with that loop in the second kernel only, where `return`
-// leaves the first (every use below is at the body's top level).  In scope: logits, C, hs, ws, out, H, W, hc, wc, rh, rw, wt, uncovered.
+// leaves the first (every use below is at the body's top level).  In scope: logits, C, hs, ws, out, H, W, hc, wc, rh, rw, wt, uncovered (and conf).
   const int x = blockIdx.x * 256 + threadIdx.x, y = SLIDE_Y, b = blockIdx.z;
   if (x >= W) SLIDE_EXIT;
 #if SLIDE_EVAL
@@ -47,6 +53,9 @@
 #else
     out[((long)b * H + y) * W + x] = 255;
 #endif
+#if SLIDE_CONF
+    conf[((long)b * H + y) * W + x] = 0.f;
+#endif
     SLIDE_EXIT;
   }
   const float cnt = (float)nk;
@@ -64,6 +73,9 @@
       }
     }
     const float p = acc / cnt;
+#if SLIDE_CONF == 2
+    conf_col[c * 256] = p;
+#endif
     if (c == 0 || p > best) { best = p; bi = c; }
   }
 #if SLIDE_EVAL
@@ -71,4 +83,25 @@
   eval_hist_add(hist, ebin < 0 ? -1 : ebin + bi, 1u);
 #else
   out[((long)b * H + y) * W + x] = (unsigned char)bi;
+#endif
+#if SLIDE_CONF == 2
+  float s = 0.f;
+  for (int c = 0; c < C; ++c) s = softmax_px_sum(s, softmax_px_exp(conf_col[c * 256], best), c == 0);
+  conf[((long)b * H + y) * W + x] = softmax_px_prob(softmax_px_exp(best, best), s);
+#elif SLIDE_CONF
+  float s = 0.f;
+  for (int c = 0; c < C; ++c) {
+    float acc = 0.f;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      if (q < nk) {
+        const float* sp = logits + ((long)kk[q] * C + c) * hs * ws;
+        const float lh = lhs[q], lw = lws[q];
+        const float v = (1.f - lh) * ((1.f - lw) * sp[o00[q]] + lw * sp[o01[q]]) + lh * ((1.f - lw) * sp[o10[q]] + lw * sp[o11[q]]);
+        acc = q == 0 ? v : acc + v;
+      }
+    }
+    s = softmax_px_sum(s, softmax_px_exp(acc / cnt, best), c == 0);
+  }
+  conf[((long)b * H + y) * W + x] = softmax_px_prob(softmax_px_exp(best, best), s);      // e_c / s at the first maximum: the largest probability
 #endif

@@ -10,6 +10,9 @@ ED:205-214), and the resize / pad / accumulate / count of every crop is one kern
 Test-time augmentation (`aug_test`, ED:509-546): `probabilities` (the softmax and un-flip of ED:448-469), `aug_inference` (the mean over the views, on
 canvases), `aug_class_map` (its argmax, from the canvas path or from ONE launch after the head, mmsa_aug_argmax) and `AugPlan`, the MapPlan of several views.
 
+Confidence maps (`confidence=` of the class-map entries, `conf=` of the plans, `argmax_max_map`): the probability of the predicted class, max over the
+classes of what `probabilities` / `aug_inference` return (ED:449,460), float32 [B, Ho, Wo], written by the launch that writes the class map.
+
 What a frame's output looks like -- its windows, the size after the second resize and after the cut, which class-map kernel that takes -- is decided once,
 in `MapPlan`, a record without device state; the entries read the frame (`_intake`), make the plan, and launch from it."""
 import ctypes
@@ -199,6 +202,37 @@ def _check_overlap(boxes, what):
 ONE_PASS_RESCALE_DEFAULT = dict(up=True, down=True)   # not measured yet (tools/exp/rescale_class_map_bench.py)
 
 
+_NO_CONF_FUSED = ("confidence with fused=True / return_map=False: the fused class-map + evaluation launch (mmsa_slide_argmax_eval) has no confidence variant; "
+                  "with labels= the counts of a map with confidence go through the stored map (drop fused= / return_map=)")
+
+
+def _check_conf(conf, size, device, what="inference"):
+    """A confidence buffer must be what the kernels write: a contiguous float32 [B, Ho, Wo] tensor on the map's device."""
+    if not isinstance(conf, torch.Tensor):
+        raise RuntimeError(f"mmsa.{what}: the confidence buffer must be a tensor, got {type(conf).__name__}")
+    if tuple(conf.shape) != tuple(size):
+        raise RuntimeError(f"mmsa.{what}: the confidence buffer has shape {tuple(conf.shape)}, the class map is [B, Ho, Wo] = {tuple(size)}")
+    if conf.dtype != torch.float32:
+        raise RuntimeError(f"mmsa.{what}: the confidence buffer must be float32, got {conf.dtype}")
+    if conf.device != torch.device(device):
+        raise RuntimeError(f"mmsa.{what}: the confidence buffer is on {conf.device}, the class map on {torch.device(device)}")
+    if not conf.is_contiguous():
+        raise RuntimeError(f"mmsa.{what}: the confidence buffer must be contiguous (its layout is the class map's)")
+    return conf
+
+
+def _confidence(confidence, size, device, what, fused=None, return_map=True):
+    """`confidence=` of an entry -> the buffer the launch writes, or None: False / None = no confidence map; True = a new float32 [B, Ho, Wo]; a tensor = the
+    output buffer itself (checked; nothing is allocated).  Refuses, before anything is launched, what has no confidence variant."""
+    if confidence is None or confidence is False:
+        return None
+    if fused or not return_map:
+        raise RuntimeError(f"mmsa.{what}: {_NO_CONF_FUSED}")
+    if confidence is True:
+        return torch.empty(size, dtype=torch.float32, device=device)
+    return _check_conf(confidence, size, device, what)
+
+
 @dataclasses.dataclass(frozen=True)
 class MapPlan:
     """The output geometry of one frame batch, decided on the host before anything is launched: B x (H x W) is the canvas the windows cover, hc x wc the
@@ -278,18 +312,31 @@ class MapPlan:
         """`jobs` as the int [n, 3] window table of the kernels."""
         return (ctypes.c_int * (3 * self.n))(*[v for job in self.jobs for v in job])
 
-    def _args(self, lg, out):
-        """The leading arguments the three class-map entries share."""
-        return lg.data_ptr(), self.n, lg.shape[1], lg.shape[2], lg.shape[3], self.tab, out.data_ptr(), self.B, self.H, self.W, self.hc, self.wc
+    def _args(self, lg, out, conf=None):
+        """The leading arguments the class-map entries share; the `_conf` entries take `conf` behind `out`."""
+        outs = (out.data_ptr(),) if conf is None else (out.data_ptr(), conf.data_ptr())
+        return (lg.data_ptr(), self.n, lg.shape[1], lg.shape[2], lg.shape[3], self.tab) + outs + (self.B, self.H, self.W, self.hc, self.wc)
 
-    def class_map(self, lg, out, unc, labels=None, evaluator=None, case=None, fused=None, return_map=True, one_pass=None):
+    def _plain(self, lg, out, unc, conf):
+        """mmsa_slide_argmax, or its sibling that also writes `conf`."""
+        lib.call("mmsa_slide_argmax" if conf is None else "mmsa_slide_argmax_conf", *self._args(lg, out, conf), unc.data_ptr(), ops._stream())
+
+    def class_map(self, lg, out, unc, labels=None, evaluator=None, case=None, fused=None, return_map=True, one_pass=None, conf=None):
         """The class-map launch of the three class-map calls, from the head-resolution logits lg [n, C, hs, ws] into out uint8 [B, Ho, Wo] and the
         uncovered-pixel word `unc`.  Without `labels`: mmsa_slide_argmax.  With `labels` (raw uint8 label maps [B, Hl, Wl]) and `evaluator`
         (mmsa.evaluate.Evaluator): the confusion counts of the map are ADDED to the evaluator's buffer as well -- by the same launch
         (mmsa_slide_argmax_eval: `fused=True`) or by a second one over the stored map (mmsa_eval_confusion_u8); `fused=None` takes mmsa.evaluate.FUSED_DEFAULT.
         The map is the same either way; `return_map=False` with the fused launch writes none.  No host sync, no allocation.
         A `rescaled` plan: mmsa_slide_argmax_resized, or the canvas path where ONE_PASS_RESCALE_DEFAULT / `one_pass=False` say so; the counts then always go
-        through the stored map (no fused variant at the rescaled size)."""
+        through the stored map (no fused variant at the rescaled size).
+        `conf` (a contiguous float32 [B, Ho, Wo] tensor on the map's device): the confidence map max_c softmax(logits)[c] (ED:449,460) is written too, by
+        the `_conf` sibling of the launch the plan takes (mmsa_slide_argmax_conf / mmsa_slide_argmax_resized_conf; on the canvas path
+        mmsa_softmax_flip_accum_nchw + mmsa_argmax_max_nchw): bit for bit probabilities(...).max(1), 0 where the map is 255.  The fused evaluation launch
+        has no such sibling: `fused=True` / `return_map=False` are refused, and counts go through the stored map."""
+        if conf is not None:
+            if fused or not return_map:
+                raise RuntimeError(f"mmsa.inference: {_NO_CONF_FUSED}")
+            _check_conf(conf, (self.B, self.Ho, self.Wo), out.device)
         if self.rescaled:
             if (labels is None) != (evaluator is None):
                 raise RuntimeError("mmsa.inference: labels= and evaluator= come together")
@@ -297,9 +344,12 @@ class MapPlan:
                 raise RuntimeError("mmsa.inference: fused=True / return_map=False need the fused class-map + evaluation launch, and that launch has no variant at "
                                    "a rescaled or cut size: the counts of a rescaled map go through the stored map (drop fused= / return_map=)")
             if ONE_PASS_RESCALE_DEFAULT["up" if self.Hd * self.Wd > self.H * self.W else "down"] if one_pass is None else one_pass:
-                lib.call("mmsa_slide_argmax_resized", *self._args(lg, out), *self.rs, unc.data_ptr(), ops._stream())
+                if conf is None:
+                    lib.call("mmsa_slide_argmax_resized", *self._args(lg, out), *self.rs, unc.data_ptr(), ops._stream())
+                else:
+                    lib.call("mmsa_slide_argmax_resized_conf", *self._args(lg, out, conf), *self.rs, unc.data_ptr(), ops._stream())
             else:
-                _rescaled_map_canvas(self, lg, out, unc)
+                _rescaled_map_canvas(self, lg, out, unc, conf)
             if evaluator is not None:
                 evaluator.add(out, labels, case=case)
             return
@@ -308,17 +358,17 @@ class MapPlan:
         if labels is None and evaluator is None:
             if not return_map:
                 raise RuntimeError("mmsa.inference: return_map=False only makes sense with labels= and evaluator=")
-            lib.call("mmsa_slide_argmax", *self._args(lg, out), unc.data_ptr(), ops._stream())
+            self._plain(lg, out, unc, conf)
             return
         if labels is None or evaluator is None:
             raise RuntimeError("mmsa.inference: labels= and evaluator= come together")
         if fused is False and not return_map:
             raise RuntimeError("mmsa.inference: return_map=False needs the fused launch (two launches go through the stored map); drop fused=False")
         from . import evaluate
-        if (evaluate.FUSED_DEFAULT or not return_map) if fused is None else fused:      # no map wanted: only the fused launch can leave it unwritten
+        if conf is None and ((evaluate.FUSED_DEFAULT or not return_map) if fused is None else fused):      # no map wanted: only the fused launch can leave it unwritten
             evaluator.add_fused(lg, self, out if return_map else None, unc, labels, case=case)
         else:
-            lib.call("mmsa_slide_argmax", *self._args(lg, out), unc.data_ptr(), ops._stream())
+            self._plain(lg, out, unc, conf)
             evaluator.add(out, labels, case=case)
 
 
@@ -336,16 +386,24 @@ def _canvas_logits(plan, lg, unc):
     return _rescaled_logits(canvas, (plan.Hd, plan.Wd) if plan.resized else None)
 
 
-def _rescaled_map_canvas(plan, lg, out, unc):
-    """The rescaled class map the long way round: _canvas_logits, argmax, crop -- the launches slide_inference / encode_decode + argmax_map make."""
-    full = argmax_map(_canvas_logits(plan, lg, unc))
-    out.copy_(full[:, :plan.Ho, :plan.Wo])
+def _rescaled_map_canvas(plan, lg, out, unc, conf=None):
+    """The rescaled class map the long way round: _canvas_logits, argmax, crop -- the launches slide_inference / encode_decode + argmax_map make.  With
+    `conf`: also the softmax of the cut logits (what `probabilities` launches) and mmsa_argmax_max_nchw for its maximum.  The MAP stays the argmax of the
+    logits, as without `conf` and as in the one-pass kernels: the softmax can round two distinct logits to one probability, and the first class would win."""
+    y = _canvas_logits(plan, lg, unc)
+    out.copy_(argmax_map(y)[:, :plan.Ho, :plan.Wo])
+    if conf is None:
+        return
+    y = y[:, :, :plan.Ho, :plan.Wo].contiguous()
+    prob = torch.empty_like(y)
+    _softmax_accum(y, prob)
+    _argmax_max_into(prob, torch.empty_like(out), conf)
 
 
 @_on_device
 @torch.no_grad()
 def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preprocess=None, labels=None, evaluator=None, case=None, fused=None,
-                    return_map=True, render=None, ori_shape=None, one_pass=None):
+                    return_map=True, render=None, ori_shape=None, one_pass=None, confidence=False):
     """`simple_test` of a sliding-window frame (ED:191-234 + ED:449,477) -> uint8 class map [B, H, W], without the
     [B, classes, H, W] logits canvas: every window's logits stay at head resolution and ONE kernel (mmsa_slide_argmax) resizes,
     sums the overlapping windows in window order, divides by the count and takes the argmax -- the same additions in the same order
@@ -359,11 +417,16 @@ def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preproc
     `ori_shape=` (h, w[, 3]): the map of `rescale=True` (ED:227-233), uint8 [B, h, w] -- the averaged logits resized once more before the argmax, by the
     same single launch (mmsa_slide_argmax_resized; `one_pass=False`: by the canvas path), bit for bit argmax_map(slide_inference(..., ori_shape=)).  None or
     the frame's own size: the launch above.  A LabelPrep for `labels=` must be built for [h, w]; `fused=True` / `return_map=False` are refused; `render=`
-    needs raw uint8 frames of [h, w]."""
+    needs raw uint8 frames of [h, w].
+    `confidence=` True, or a contiguous float32 [B, h, w] tensor on the device to write into (nothing is allocated for it, so the launch can be captured):
+    the confidence map -- the probability of the predicted class, bit for bit probabilities(...).max(1).values, 0 where the map is 255 -- is written by the
+    same launch and returned as the LAST element: (map, unc[, picture], conf).  Refused with `fused=True` / `return_map=False`; `labels=` count through the
+    stored map."""
     B, H, W, device, frame, cut = _intake(img, preprocess, "slide_class_map")
     plan = MapPlan.slide(B, H, W, crop_size, stride, ori_shape)
     src = None if render is None else slide_source(render, preprocess, frame, plan, return_map, "slide_class_map")
     plan.check_windows("slide_class_map")
+    conf = _confidence(confidence, (B, plan.Ho, plan.Wo), device, "slide_class_map", fused, return_map)
     _pair(backbone, head)
     lgs = []
     for s in range(0, plan.n, max_batch):
@@ -372,16 +435,15 @@ def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preproc
     lg = lgs[0] if len(lgs) == 1 else torch.cat(lgs, 0)
     out = torch.empty(B, plan.Ho, plan.Wo, dtype=torch.uint8, device=device)
     unc = torch.zeros(1, dtype=torch.int32, device=device)
-    plan.class_map(lg, out, unc, labels, evaluator, case, fused, return_map, one_pass)
-    if render is not None:
-        return out, unc, render(out, src)
-    return (out if return_map else None), unc          # unc[0] != 0 <=> some pixel is not covered (ED:220); checked by the caller outside a capture
+    plan.class_map(lg, out, unc, labels, evaluator, case, fused, return_map, one_pass, conf)
+    r = (out, unc, render(out, src)) if render is not None else ((out if return_map else None), unc)   # unc[0] != 0 <=> some pixel is not covered (ED:220); checked by the caller outside a capture
+    return r if conf is None else r + (conf,)
 
 
 @_on_device
 @torch.no_grad()
 def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator=None, case=None, fused=None, return_map=True, render=None,
-                    ori_shape=None, dim=None, cut_dim=None, rescale=True, one_pass=None):
+                    ori_shape=None, dim=None, cut_dim=None, rescale=True, one_pass=None, confidence=False):
     """Whole-image `simple_test`: resize x4 (bilinear, align_corners=False) + argmax fused (ED:90-94,449,477) -> uint8 [B, H, W].
     `preprocess=` (mmsa.preprocess.Preprocess): img is the pair (rgb, aux) of raw frames, normalised (and padded) by one launch.
     `labels=` + `evaluator=` (+ `case=`): as in slide_class_map.
@@ -394,7 +456,8 @@ def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator
       `dim=` + `cut_dim=` (w, h) 'whole_dim_cut' (ED:393-414): whole_inference_dim_cut(..., dim, cut_dim, rescale) -> [B, min(cut h, .), min(cut w, .)], the
                                 crop [:cut_dim[1], :cut_dim[0]] of the map at `dim` (rescale) or at the input size (`rescale=False`, the FMB configs).
     A LabelPrep for `labels=` must be built for that size; `fused=True` / `return_map=False` are refused; `render=` needs a source of the map's size: raw
-    uint8 frames of the size before the cut, or -- for a cut alone -- the input tensor."""
+    uint8 frames of the size before the cut, or -- for a cut alone -- the input tensor.
+    `confidence=`: as in slide_class_map; the confidence map float32 [B, Ho, Wo] comes as the last element, (map[, picture], conf)."""
     rgb = None
     if preprocess is not None:
         rgb, aux, B, H, W = _raw(preprocess, img, "whole_class_map")
@@ -403,6 +466,7 @@ def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator
         B, _, H, W = (int(v) for v in img.shape)
     plan = MapPlan.whole(B, H, W, ori_shape, dim, cut_dim, rescale)
     src = None if render is None else whole_source(render, rgb, plan, return_map, "whole_class_map")      # the raw frames, or None: the tensor below
+    conf = _confidence(confidence, (B, plan.Ho, plan.Wo), (rgb if rgb is not None else img).device, "whole_class_map", fused, return_map)
     if preprocess is not None:
         img = preprocess(rgb, aux)
     if render is not None and src is None:
@@ -412,9 +476,11 @@ def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator
     lg = head(feats)
     out = torch.empty(B, plan.Ho, plan.Wo, dtype=torch.uint8, device=img.device)
     unc = torch.zeros(1, dtype=torch.int32, device=img.device)
-    plan.class_map(lg, out, unc, labels, evaluator, case, fused, return_map, one_pass)
+    plan.class_map(lg, out, unc, labels, evaluator, case, fused, return_map, one_pass, conf)
     if render is not None:
-        return out, render(out, src)
+        return (out, render(out, src)) if conf is None else (out, render(out, src), conf)
+    if conf is not None:
+        return out, conf
     return out if return_map else None
 
 
@@ -478,20 +544,23 @@ def inference(backbone, head, img, test_cfg, rescale=True, preprocess=None, ori_
 
 @_on_device
 @torch.no_grad()
-def class_map(backbone, head, img, test_cfg, rescale=True, ori_shape=None, preprocess=None, labels=None, evaluator=None, case=None, render=None, one_pass=None):
+def class_map(backbone, head, img, test_cfg, rescale=True, ori_shape=None, preprocess=None, labels=None, evaluator=None, case=None, render=None, one_pass=None,
+              confidence=False):
     """`simple_test` (ED:471-477) by mode: the dispatch of `inference` (ED:417-447) onto the class-map calls -> uint8 map, bit for bit
     argmax_map(inference(...)) of the same arguments, without a logits canvas: [B, H, W], or at the size `rescale` gives ('slide' / 'whole': `ori_shape`;
     'whole_dim': test_cfg['dim']; 'whole_dim_cut': the crop of the map at `dim`, or at the input size without `rescale`).  What `inference` refuses is
     refused here ('slide_mod_sel'; 'whole_dim' with rescale=False).  'slide' reads the kernel's uncovered-pixel word back (one host sync, as
     slide_inference's coverage check is) and raises on a window grid that does not cover the frame (ED:220).
-    `preprocess=`, `labels=` + `evaluator=` (+ `case=`; through the stored map), `render=` (-> (map, picture)), `one_pass=`: as in the calls it goes to."""
+    `preprocess=`, `labels=` + `evaluator=` (+ `case=`; through the stored map), `render=` (-> (map, picture)), `one_pass=`: as in the calls it goes to.
+    `confidence=` (True or an output tensor): the confidence map, probabilities(...).max(1).values bit for bit, as the last element: (map[, picture], conf)."""
     mode = test_cfg["mode"]
-    kw = dict(preprocess=preprocess, labels=labels, evaluator=evaluator, case=case, render=render, one_pass=one_pass)
+    kw = dict(preprocess=preprocess, labels=labels, evaluator=evaluator, case=case, render=render, one_pass=one_pass, confidence=confidence)
     if mode == "slide":
         r = slide_class_map(backbone, head, img, tuple(test_cfg["crop_size"]), tuple(test_cfg["stride"]), ori_shape=ori_shape if rescale else None, **kw)
         if int(r[1].item()) != 0:
             raise RuntimeError("mmsa.class_map: windows do not cover the image")   # ED:220
-        return r[0] if render is None else (r[0], r[2])
+        r = (r[0],) + tuple(r[2:])           # without the uncovered-pixel word: (map[, picture][, conf])
+        return r[0] if len(r) == 1 else r
     if mode == "whole":
         return whole_class_map(backbone, head, img, ori_shape=ori_shape if rescale else None, **kw)
     if mode == "whole_dim":
@@ -511,6 +580,25 @@ def argmax_map(seg_logit):
     out = torch.empty(B, H, W, dtype=torch.uint8, device=seg_logit.device)
     lib.call("mmsa_argmax_nchw", seg_logit.data_ptr(), out.data_ptr(), B, C, H * W, ops._stream())
     return out
+
+
+def _argmax_max_into(prob, out, conf):
+    B, C, H, W = prob.shape
+    lib.call("mmsa_argmax_max_nchw", prob.data_ptr(), out.data_ptr(), conf.data_ptr(), B, C, H * W, ops._stream())
+
+
+@_on_device
+@torch.no_grad()
+def argmax_max_map(prob):
+    """argmax_map that also returns the maximum -> (uint8 [B, H, W], float32 [B, H, W]), one launch (mmsa_argmax_max_nchw).  On the probabilities of
+    `probabilities` / `aug_inference` (ED:449,460) the second is the confidence map: the probability of the predicted class."""
+    _check(prob)
+    prob = prob.contiguous()
+    B, C, H, W = prob.shape
+    out = torch.empty(B, H, W, dtype=torch.uint8, device=prob.device)
+    conf = torch.empty(B, H, W, dtype=torch.float32, device=prob.device)
+    _argmax_max_into(prob, out, conf)
+    return out, conf
 
 
 # ---- test-time augmentation: EncoderDecoder.aug_test (ED:509-546) -- several views of a frame (flipped, at several scales), whose probabilities are averaged
@@ -681,10 +769,14 @@ class AugPlan:
             _softmax_accum(y, acc, f, accumulate=a > 0, finish_div=self.A if a == self.A - 1 else 0)
         return acc
 
-    def class_map(self, lgs, out, unc, one_pass=None):
+    def class_map(self, lgs, out, unc, one_pass=None, conf=None):
         """The class map of the views' head-resolution logits `lgs` (one [n_a, C, hs_a, ws_a] per view) into out uint8 [B, Ho, Wo] and the uncovered-pixel
         word `unc`: ONE launch (mmsa_aug_argmax; no host sync, no allocation once the table is on the device) where `one_pass=True` / ONE_PASS_AUG_DEFAULT
-        say so and the classes fit the kernel (at most MAX_AUG_CLASSES), else the canvas path + argmax_map.  The same map bit for bit."""
+        say so and the classes fit the kernel (at most MAX_AUG_CLASSES), else the canvas path + argmax_map.  The same map bit for bit.
+        `conf` (a contiguous float32 [B, Ho, Wo] tensor on the map's device): the confidence map max_c of the mean probabilities is written too, by
+        mmsa_aug_argmax_conf or, on the canvas path, by mmsa_argmax_max_nchw in place of mmsa_argmax_nchw: bit for bit mean_probabilities(...).max(1)."""
+        if conf is not None:
+            _check_conf(conf, self.size, out.device)
         if len(lgs) != self.A or any(lg.shape[0] != p.n for lg, p in zip(lgs, self.plans)):
             raise RuntimeError("mmsa.inference: AugPlan.class_map takes one logits tensor per view, one row per window of that view")
         C = int(lgs[0].shape[1])
@@ -693,10 +785,13 @@ class AugPlan:
             ptrs = (ctypes.c_void_p * self.A)(*[lg.data_ptr() for lg in lgs])
             rows = (ctypes.c_int * (11 * self.A))(*[v for r in self.rows(lgs) for v in r])
             B, Ho, Wo = self.size
-            lib.call("mmsa_aug_argmax", ptrs, rows, self.A, C, self.table_on(out.device).data_ptr(), self.table, self.total, out.data_ptr(), B, Ho, Wo,
-                     unc.data_ptr(), ops._stream())
-        else:
+            outs = (out.data_ptr(),) if conf is None else (out.data_ptr(), conf.data_ptr())
+            lib.call("mmsa_aug_argmax" if conf is None else "mmsa_aug_argmax_conf", ptrs, rows, self.A, C, self.table_on(out.device).data_ptr(), self.table,
+                     self.total, *outs, B, Ho, Wo, unc.data_ptr(), ops._stream())
+        elif conf is None:
             out.copy_(argmax_map(self.mean_probabilities(lgs, unc)))
+        else:
+            _argmax_max_into(self.mean_probabilities(lgs, unc), out, conf)
 
 
 _AUG_PLANS = {}
@@ -745,19 +840,22 @@ def aug_inference(backbone, head, imgs, test_cfg, ori_shape=None, flips=None, pr
 @_on_views_device
 @torch.no_grad()
 def aug_class_map(backbone, head, imgs, test_cfg, ori_shape=None, flips=None, preprocess=None, max_batch=8, labels=None, evaluator=None, case=None,
-                  one_pass=None):
+                  one_pass=None, confidence=False):
     """`aug_test` (ED:509-546) -> (uint8 class map [B, Ho, Wo], uncovered-pixel word), bit for bit argmax_map(aug_inference(...)) of the same arguments.
     Every view goes through backbone and head (`max_batch` windows per call, per view); then ONE launch (mmsa_aug_argmax) resizes every view's
     head-resolution logits as `class_map` would, takes the softmax, un-flips, averages over the views and takes the argmax, with no logits or probability
     canvas in memory (`one_pass=True`), or the canvas path runs from the same logits (`one_pass=False`, more than 128 classes, and -- being the faster of
     the two where measured -- the default: ONE_PASS_AUG_DEFAULT).  No host sync either way; the one-pass launch is HIP-graph capturable once a first call
     has put the plan's window table on the device.  unc[0] != 0 <=> some view's windows do not cover its frame (ED:220): checked by the caller.
-    `labels=` + `evaluator=` (+ `case=`): the map's confusion counts are added to the evaluator through the stored map, as at any rescaled size."""
+    `labels=` + `evaluator=` (+ `case=`): the map's confusion counts are added to the evaluator through the stored map, as at any rescaled size.
+    `confidence=` (True or a contiguous float32 [B, Ho, Wo] output tensor): the confidence map -- the mean probability of the predicted class, bit for bit
+    aug_inference(...).max(1).values, 0 where the map is 255 -- from the same launch, as the last element: (map, unc, conf)."""
     if (labels is None) != (evaluator is None):
         raise RuntimeError("mmsa.inference: labels= and evaluator= come together")
     imgs, flips, pre = AugPlan.views(imgs, flips, preprocess, "aug_class_map")
     frames = [_intake(img, p, "aug_class_map") for img, p in zip(imgs, pre)]
     plan = AugPlan.of(test_cfg, [f[:3] for f in frames], flips, ori_shape)
+    conf = _confidence(confidence, plan.size, frames[0][3], "aug_class_map")
     _pair(backbone, head)
     lgs = []
     for mp, p, (_, _, _, _, frame, cut) in zip(plan.plans, pre, frames):
@@ -770,10 +868,10 @@ def aug_class_map(backbone, head, imgs, test_cfg, ori_shape=None, flips=None, pr
     B, Ho, Wo = plan.size
     out = torch.empty(B, Ho, Wo, dtype=torch.uint8, device=device)
     unc = torch.zeros(1, dtype=torch.int32, device=device)
-    plan.class_map(lgs, out, unc, one_pass)
+    plan.class_map(lgs, out, unc, one_pass, conf)
     if evaluator is not None:
         evaluator.add(out, labels, case=case)
-    return out, unc
+    return (out, unc) if conf is None else (out, unc, conf)
 
 
 class FrameResult:
@@ -797,6 +895,14 @@ class FrameResult:
         self._replay._owner._verify(self._replay.seq)
         return self._runner.pic
 
+    def confidence(self):
+        """The frame's confidence map float32 [B, H, W] of a runner made with confidence=True -- verified, exactly as outputs() is.  The runner's static
+        buffer: read it before the next run()."""
+        if self._runner.conf is None:
+            raise RuntimeError("mmsa.FrameResult.confidence: the SlideRunner was made without confidence=True")
+        self._replay._owner._verify(self._replay.seq)
+        return self._runner.conf
+
     @property
     def unverified(self):
         return (self._runner.out if self._has_map else None), self._runner.unc
@@ -811,9 +917,12 @@ class SlideRunner:
     windows are cut AND normalised from them by one launch; run(frame=pair) reads another pair of the same geometry instead (mmsa.preprocess.FrameFeeder's slots).
     With `render=` (mmsa.render.Renderer) every run() also paints the frame's picture into a static buffer (one more launch): FrameResult.picture().
     With `ori_shape=` (h, w[, 3]) the class map -- and the static `out` buffer -- is the one of `rescale=True` at [B, h, w] (slide_class_map's `ori_shape=`:
-    mmsa_slide_argmax_resized in place of mmsa_slide_argmax, or the canvas path with `one_pass=False`)."""
+    mmsa_slide_argmax_resized in place of mmsa_slide_argmax, or the canvas path with `one_pass=False`).
+    With `confidence=True` every run() also writes the frame's confidence map (slide_class_map's `confidence=`) into a static float32 [B, h, w] buffer, by the
+    `_conf` sibling of the class-map launch: FrameResult.confidence().  Such a runner refuses run(fused=True) and run(return_map=False)."""
 
-    def __init__(self, backbone, head, frame, crop_size, stride, chains=2, check_every=1, preprocess=None, render=None, ori_shape=None, one_pass=None):
+    def __init__(self, backbone, head, frame, crop_size, stride, chains=2, check_every=1, preprocess=None, render=None, ori_shape=None, one_pass=None,
+                 confidence=False):
         from .chains import Chains
         self.preprocess, self.render, self.one_pass = preprocess, render, one_pass
         B, H, W, self.device, self.frame, self._cut = _intake(frame, preprocess, "SlideRunner")
@@ -829,6 +938,7 @@ class SlideRunner:
             self.chains = Chains(backbone, head, n=chains, check_every=check_every).capture(self.crops)
             self.out = torch.empty(B, plan.Ho, plan.Wo, dtype=torch.uint8, device=self.device)
             self.unc = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self.conf = torch.empty(B, plan.Ho, plan.Wo, dtype=torch.float32, device=self.device) if confidence else None
             self.pic = None
             if render is not None:
                 render.palette_on(self.device)
@@ -843,6 +953,8 @@ class SlideRunner:
         `labels=` + `evaluator=` (mmsa.evaluate.Evaluator, best one made with cases=[...] and device=; `case=`): the frame's confusion counts are ADDED to the
         evaluator on device (see MapPlan.class_map); a frame that has to be run again has been counted, so reset the evaluator or subtract what it added.
         `return_map=False` (always the fused launch) leaves the runner's map buffer untouched; the FrameResult's map is then None."""
+        if self.conf is not None and (fused or not return_map):
+            raise RuntimeError(f"mmsa.SlideRunner.run: {_NO_CONF_FUSED}")
         if frame is None:
             frame = self.frame
         else:
@@ -857,7 +969,7 @@ class SlideRunner:
             rp = self.chains.replay()
             lg = rp.unverified          # the argmax kernel below is enqueued behind the pass; nothing is read on the host before outputs() verifies it
             self.unc.zero_()
-            self.plan.class_map(lg, self.out, self.unc, labels, evaluator, case, fused, return_map, self.one_pass)
+            self.plan.class_map(lg, self.out, self.unc, labels, evaluator, case, fused, return_map, self.one_pass, self.conf)
             if self.render is not None:
                 self.render(self.out, src, out=self.pic)
         return FrameResult(self, rp, has_map=return_map)

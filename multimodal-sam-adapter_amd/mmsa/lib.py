@@ -81,6 +81,10 @@ SIGNATURES = {
     "mmsa_slide_argmax_resized": [P, I, I, I, I, P, P, I, I, I, I, I, I, I, I, I, P, P],
     "mmsa_softmax_flip_accum_nchw": [P, P, I, I, I, I, I, I, I, P],
     "mmsa_aug_argmax": [P, P, I, I, P, P, I, P, I, I, I, P, P],
+    "mmsa_argmax_max_nchw": [P, P, P, I, I, L, P],
+    "mmsa_slide_argmax_conf": [P, I, I, I, I, P, P, P, I, I, I, I, I, P, P],
+    "mmsa_slide_argmax_resized_conf": [P, I, I, I, I, P, P, P, I, I, I, I, I, I, I, I, I, P, P],
+    "mmsa_aug_argmax_conf": [P, P, I, I, P, P, I, P, P, I, I, I, P, P],
     "mmsa_preprocess_nhwc": [P, I, P, I, I, I, I, P, P, P, P, P, P, I, I, P],
     "mmsa_preprocess_crops": [P, I, P, I, I, I, I, P, P, P, P, P, I, I, P, I, P, I, I, P],
     "mmsa_preprocess_resize_nhwc": [P, I, P, I, I, I, I, P, P, P, P, P, P, I, I, I, I, P, P, P, P, I, P],
@@ -100,7 +104,7 @@ for _name, _args in SIGNATURES.items():
 
 # The C ABI is not self-describing: a library built from another tree (MMSA_LIB variants, a stale in-tree .so) may export every symbol and still take
 # different argument lists.  include/mmsa.h MMSA_ABI_VERSION is bumped with every such change; this binding was written for:
-ABI_VERSION = 110
+ABI_VERSION = 111
 if _lib.mmsa_version() != ABI_VERSION:
     raise RuntimeError(f"{LIB_PATH}: ABI version {_lib.mmsa_version()} but mmsa/lib.py binds version {ABI_VERSION} (include/mmsa.h MMSA_ABI_VERSION): "
                        "rebuild with python multimodal-sam-adapter_amd/build.py")
