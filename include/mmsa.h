@@ -447,6 +447,20 @@ int mmsa_slide_argmax_eval(const float* logits, int n, int C, int hs, int ws, co
                            int hc, int wc, int* uncovered, const unsigned char* label, int Hl, int Wl, const unsigned char* lut, const int* ymap,
                            const int* xmap, const int* slots, int n_slots, int64_t* counts, mmsa_stream_t stream);
 
+/* --- calibration of the confidence map (the probability of the predicted class, float32, written next to every class map): reliability bins of a uint8
+ *     class map and its confidence map against a uint8 label map.  cal = int64 [n_slots, 3, bins], rows total / correct / conf_sum per confidence bin.
+ *     The label side -- lut, ymap / xmap (both or neither, clamped into the label map), slots (HOST int [B]) -- is mmsa_eval_confusion_u8's.  Per pixel:
+ *       it takes part iff its transformed label l = lut[label byte] is a class, l < C (ignored, 255, and kept-but-out-of-range labels take no part);
+ *       it is correct iff pred == l (a prediction of 255, uncovered, never is);
+ *       c = conf with NaN and negative values -> 0.0f and values above 1 -> 1.0f;
+ *       bin k = min(bins - 1, (int)(c * (float)bins)): one float32 product, truncated (conf == 1 falls into the last bin);
+ *       conf_sum gets floor(c * 2^24) (the scaling is exact): mean confidence = conf_sum / (2^24 * total), below the float64 mean by less than 2^-24.
+ *     The call ADDS into cal (the caller zeroes it): integer sums, the same bytes whatever the order of arrival; int64 holds 2^39 pixels per bin and slot.
+ *     pred and label may sit at any byte address, conf at any 4-byte aligned one.  2 <= C <= 254, 1 <= bins <= 64, 1 <= B <= 64. --- */
+int mmsa_eval_calibration(const unsigned char* pred, const float* conf, const unsigned char* label, int B, int H, int W, int Hl, int Wl,
+                          const unsigned char* lut, int C, const int* ymap, const int* xmap, const int* slots, int n_slots, int bins, int64_t* cal,
+                          mmsa_stream_t stream);
+
 /* --- the picture of a prediction (segmentation/mmseg_custom/apis/test_bs.py:257-349, the `--show` / `--show-dir` output): `tensor2imgs` (test_bs.py:18-63) on
  *     planes 0..2 of the input tensor -> the crop `img[:h, :w]` (test_bs.py:275-276) -> `show_result` (tools/color_gt_according_palette.py:23-81:
  *     color_seg[seg == label] = color, channels reversed, img * (1 - opacity) + color_seg * opacity, .astype(uint8)), in one pass.

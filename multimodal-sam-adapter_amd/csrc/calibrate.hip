@@ -1,0 +1,231 @@
+// Calibration on device: the reliability bins of a uint8 class map and its float32 confidence map against a uint8 label map.  Per count slot and
+// confidence bin k of K: total (pixels whose transformed label is a class), correct (of those, pred == label class) and conf_sum (the sum of
+// floor(conf * 2^24), the confidence in 24-bit fixed point) -- int64 [n_slots, 3, K].  ECE, MCE, the reliability diagram and accuracy against coverage
+// are formed from these integers in float64 on the host (mmsa/evaluate.py).  The label side (LUT, nearest-neighbour tables, clamping) is the one of
+// csrc/evaluate.hip.
+// One pass over 6 bytes per pixel, shaped like eval_confusion_kernel: a workgroup walks CAL_CHUNK pixels (whole rows where the tables apply, one flat
+// run per image otherwise); pred as dwords, conf as float4 where that span's address is 16-byte aligned (four dword loads otherwise), the label as
+// dwords where it shares pred's alignment and no table is in the way; an edge path, one pixel per lane, serves the unaligned head and tail.
+//
+// Bin updates.  Confidence is not patchy like a class map: there are few bins, most pixels of a trained model fall into the top one, and 64 lanes would
+// queue on a handful of LDS addresses.  So a lane first merges those of its four pixels that share a bin (neighbours usually do), and a wave then
+// reduces bin by bin: the lowest pending lane's bin is broadcast, the lanes that hold it retire, and their (total | correct << 16) and confidence sums
+// are two wave reductions in registers; the leading lane then makes TWO 64-bit LDS adds (total | correct << 32, and conf_sum).  A round costs the
+// same whatever the number of lanes it retires, so the usual frame (one to three bins per 256 pixels) pays one to three rounds and the worst case, K
+// bins spread evenly, pays 4 * min(K, 64) -- and no LDS address ever sees more than one add per wave and round.  Chosen over per-wave sub-histograms
+// with lane-by-lane adds: those still serialise the lanes of a wave on the top bin's address, which is the common case here; the rounds remove exactly
+// that queue.  (Timed, profiles/calibration.txt: one round per PIXEL of a lane, with ballot popcounts for the counts, took 25.6 us on two 1024 x 1024
+// maps where the confusion pass takes 14.1, the lane merge 23.8, and two workgroups per CU -- CAL_CHUNK below -- 16.2.)
+// Integer sums only, in LDS and in the int64 result: the same bytes whatever the order of arrival.
+#include "common.h"
+#include "eval_hist.h"
+
+// Pixels per workgroup.  Timed at 2048 / 4096 / 8192 (profiles/calibration.txt; -DCAL_CHUNK with tools/build_variant.sh): at 8192 (EVAL_CHUNK) a CU
+// holds one workgroup, one wave per SIMD, and nothing hides a round's dependent steps or the loads in front of them; at 2048 four times as many
+// workgroups queue their final 64-bit atomics on the same few addresses; 4096 is the fastest on the model's confidences at both sizes.
+#ifndef CAL_CHUNK
+#define CAL_CHUNK 4096           // at most 3 * K 64-bit atomics per workgroup at the end (usually under ten)
+#endif
+#define CAL_MAX_BINS 64
+#define CAL_MAX_CLASSES 254      // the LUT's limit (255 = ignored); there is no (C + 1)^2 histogram here
+#define CAL_NONE (-1)            // a lane without a participating pixel
+
+struct CalArgs {
+  const unsigned char* pred;     // [B, H, W]
+  const float* conf;             // [B, H, W]
+  const unsigned char* label;    // [B, Hl, Wl]
+  const unsigned char* lut;      // [256]
+  const int* ymap;               // [H] / [W], or both NULL
+  const int* xmap;
+  unsigned long long* cal;       // [n_slots, 3, K]
+  int H, W, Hl, Wl, C, K;
+};
+
+// one pixel -> its bin (CAL_NONE: takes no part), whether it is correct, and its confidence in 24-bit fixed point
+__device__ __forceinline__ int cal_pixel(const unsigned char* lut_s, unsigned label_byte, unsigned pred_byte, float c, int C, int K, float Kf, bool& ok,
+                                         unsigned& q) {
+  const int l = lut_s[label_byte & 255u];
+  c = c > 0.0f ? (c > 1.0f ? 1.0f : c) : 0.0f;                       // NaN, negatives and -0.0 -> 0; above 1 (and +inf) -> 1
+  ok = (int)pred_byte == l;
+  q = (unsigned)(c * 16777216.0f);                                   // exact scaling, truncated: 0 .. 2^24
+  const int k = min(K - 1, (int)(c * Kf));                           // ONE float32 product, truncated
+  return l < C ? k : CAL_NONE;
+}
+
+// Sum of v over the 64 lanes of a wave, the same in every lane; all lanes must be active.  Inside each row of 16 lanes by data-parallel-primitive moves
+// (no LDS crossbar: lane ^ 1, lane ^ 2, then the row rotated by 4 and by 8) in 32 bits -- a row's sum must fit them -- then the four row sums through
+// scalar registers, added in 64 bits.
+__device__ __forceinline__ unsigned long long cal_wave_sum(unsigned v) {
+  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, true);      // quad_perm:[1,0,3,2]
+  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, true);      // quad_perm:[2,3,0,1]: every lane holds its quad's sum
+  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x124, 0xf, 0xf, true);     // row_ror:4: two quads
+  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xf, 0xf, true);     // row_ror:8: the row
+  return (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)v, 0) + (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)v, 16) +
+         (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)v, 32) + (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)v, 48);
+}
+
+// Add one entry per lane to the workgroup's bins (see the header): `cnt` = pixels | correct pixels << 16 (up to 4 each), `q` their confidence sum (up to
+// 4 * 2^24, so a row of 16 lanes stays below 2^32).  Must be called by all lanes of a wave together (bin = CAL_NONE where a lane has none).
+__device__ __forceinline__ void cal_wave_add(unsigned long long* tc, unsigned long long* cs, int bin, unsigned cnt, unsigned q) {
+  bool pending = bin >= 0;
+  unsigned long long m = __ballot(pending);
+  while (m != 0ull) {
+    const int lead = __ffsll((long long)m) - 1;
+    const int lb = __builtin_amdgcn_readlane(bin, lead);
+    const bool same = pending && bin == lb;
+    const unsigned long long ms = __ballot(same);
+    const unsigned long long n = cal_wave_sum(same ? cnt : 0u);          // at most 256 in either half
+    const unsigned long long v = cal_wave_sum(same ? q : 0u);
+    if ((int)(threadIdx.x & 63u) == lead) {
+      atomicAdd(&tc[lb], (n & 0xffffull) | ((n >> 16) << 32));
+      atomicAdd(&cs[lb], v);
+    }
+    pending = pending && !same;
+    m &= ~ms;
+  }
+}
+
+template <bool TABLES>
+__device__ __forceinline__ unsigned cal_label_at(const unsigned char* __restrict__ l, const int* __restrict__ xmap, int Wl, int i) {
+  if (TABLES) return l[min(max(xmap[i], 0), Wl - 1)];
+  return l[i];
+}
+
+// n pixels: pred p[0..n) and conf c[0..n) against label l[0..n) (TABLES: l[xmap[0..n)], a label ROW)
+template <bool TABLES>
+__device__ __forceinline__ void cal_span(const unsigned char* __restrict__ p, const float* __restrict__ c, const unsigned char* __restrict__ l,
+                                         const int* __restrict__ xmap, int Wl, int n, unsigned long long* tc, unsigned long long* cs,
+                                         const unsigned char* lut_s, int C, int K) {
+  const float Kf = (float)K;
+  const int head = min(n, (int)((4u - (unsigned)((uintptr_t)p & 3u)) & 3u));     // bytes in front of the first aligned pred dword
+  const int ndw = (n - head) >> 2;
+  const int tail0 = head + (ndw << 2);
+  const int nedge = head + (n - tail0);                                          // edge path: at most 3 + 3 pixels, one lane each
+  if (nedge > 0 && threadIdx.x < 64u) {                                          // the first wave, all of its lanes
+    int bin = CAL_NONE;
+    bool ok = false;
+    unsigned q = 0u;
+    if ((int)threadIdx.x < nedge) {
+      const int i = (int)threadIdx.x < head ? (int)threadIdx.x : tail0 + ((int)threadIdx.x - head);
+      bin = cal_pixel(lut_s, cal_label_at<TABLES>(l, xmap, Wl, i), p[i], c[i], C, K, Kf, ok, q);
+    }
+    cal_wave_add(tc, cs, bin, 1u | ((unsigned)ok << 16), q);
+  }
+  const unsigned* __restrict__ pw = (const unsigned*)(p + head);
+  const float* __restrict__ cw = c + head;
+  const bool c16 = (((uintptr_t)cw) & 15u) == 0;                                 // this span's confidences start on a 16-byte boundary: float4 loads
+  const bool ldw = !TABLES && (((uintptr_t)(l + head)) & 3u) == 0;               // the label shares pred's alignment: dwords too
+  for (int i0 = 0; i0 < ndw; i0 += 256) {
+    const int i = i0 + (int)threadIdx.x;
+    int b[4] = {CAL_NONE, CAL_NONE, CAL_NONE, CAL_NONE};
+    bool ok[4] = {false, false, false, false};
+    unsigned q[4] = {0u, 0u, 0u, 0u};
+    if (i < ndw) {
+      const unsigned pv = pw[i];
+      const int base = head + 4 * i;
+      unsigned lv;
+      if (ldw)
+        lv = ((const unsigned*)(l + head))[i];
+      else
+        lv = cal_label_at<TABLES>(l, xmap, Wl, base) | (cal_label_at<TABLES>(l, xmap, Wl, base + 1) << 8) |
+             (cal_label_at<TABLES>(l, xmap, Wl, base + 2) << 16) | (cal_label_at<TABLES>(l, xmap, Wl, base + 3) << 24);
+      float4 cv;
+      if (c16) {
+        cv = ((const float4*)cw)[i];
+      } else {
+        cv.x = cw[4 * i];
+        cv.y = cw[4 * i + 1];
+        cv.z = cw[4 * i + 2];
+        cv.w = cw[4 * i + 3];
+      }
+      b[0] = cal_pixel(lut_s, lv, pv & 255u, cv.x, C, K, Kf, ok[0], q[0]);
+      b[1] = cal_pixel(lut_s, lv >> 8, (pv >> 8) & 255u, cv.y, C, K, Kf, ok[1], q[1]);
+      b[2] = cal_pixel(lut_s, lv >> 16, (pv >> 16) & 255u, cv.z, C, K, Kf, ok[2], q[2]);
+      b[3] = cal_pixel(lut_s, lv >> 24, pv >> 24, cv.w, C, K, Kf, ok[3], q[3]);
+    }
+    unsigned cn[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) cn[j] = 1u | ((unsigned)ok[j] << 16);
+#pragma unroll
+    for (int j = 1; j < 4; ++j) {                                                // a later pixel of an earlier one's bin joins it
+#pragma unroll
+      for (int i = 0; i < j; ++i) {
+        if (b[j] >= 0 && b[j] == b[i]) {
+          cn[i] += cn[j];
+          q[i] += q[j];
+          b[j] = CAL_NONE;
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) cal_wave_add(tc, cs, b[j], cn[j], q[j]);
+  }
+}
+
+template <bool TABLES>
+__global__ __launch_bounds__(256) void eval_calibration_kernel(CalArgs a, EvalSlots es, int rows) {
+  __shared__ unsigned long long tc[CAL_MAX_BINS];      // total | correct << 32: a workgroup sees at most CAL_CHUNK pixels, no carry between the halves
+  __shared__ unsigned long long cs[CAL_MAX_BINS];      // sum of floor(conf * 2^24): up to CAL_CHUNK * 2^24 = 2^37
+  __shared__ unsigned char lut_s[256];
+  const int K = a.K;
+  if ((int)threadIdx.x < CAL_MAX_BINS) {
+    tc[threadIdx.x] = 0ull;
+    cs[threadIdx.x] = 0ull;
+  }
+  lut_s[threadIdx.x] = a.lut[threadIdx.x];             // 256 threads, 256 bytes
+  __syncthreads();
+  const int b = blockIdx.y, H = a.H, W = a.W;
+  if (TABLES) {
+    const int y1 = min(H, ((int)blockIdx.x + 1) * rows);
+    for (int y = (int)blockIdx.x * rows; y < y1; ++y) {
+      const int ys = min(max(a.ymap[y], 0), a.Hl - 1);
+      const long at = ((long)b * H + y) * W;
+      cal_span<true>(a.pred + at, a.conf + at, a.label + ((long)b * a.Hl + ys) * a.Wl, a.xmap, a.Wl, W, tc, cs, lut_s, a.C, K);
+    }
+  } else {                                             // same size: image b is one run of H * W pixels
+    const long HW = (long)H * W, start = (long)blockIdx.x * CAL_CHUNK;
+    const int n = (int)min((long)CAL_CHUNK, HW - start);
+    const long at = b * HW + start;
+    cal_span<false>(a.pred + at, a.conf + at, a.label + at, nullptr, 0, n, tc, cs, lut_s, a.C, K);
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < K) {
+    unsigned long long* dst = a.cal + (long)es.s[b] * 3 * K;
+    const unsigned long long t = tc[threadIdx.x], s = cs[threadIdx.x];
+    if (t) {                                           // conf_sum and correct are zero wherever total is
+      atomicAdd(&dst[threadIdx.x], t & 0xffffffffull);
+      if (t >> 32) atomicAdd(&dst[K + threadIdx.x], t >> 32);
+      if (s) atomicAdd(&dst[2 * K + threadIdx.x], s);
+    }
+  }
+}
+
+extern "C" int mmsa_eval_calibration(const unsigned char* pred, const float* conf, const unsigned char* label, int B, int H, int W, int Hl, int Wl,
+                                     const unsigned char* lut, int C, const int* ymap, const int* xmap, const int* slots /* HOST [B] */, int n_slots,
+                                     int bins, int64_t* cal, hipStream_t stream) {
+  const char* name = "eval_calibration";
+  MMSA_CHECK_ARG(pred && conf && label && lut && slots && cal, "%s: pred, conf, label, lut, slots and cal are required", name);
+  MMSA_CHECK_ARG(((uintptr_t)conf & 3u) == 0, "%s: conf must be 4-byte aligned", name);
+  MMSA_CHECK_ARG(C >= 2 && C <= CAL_MAX_CLASSES, "%s: %d classes; 2..%d are supported (a uint8 label LUT; 255 means ignored)", name, C, CAL_MAX_CLASSES);
+  MMSA_CHECK_ARG(bins >= 1 && bins <= CAL_MAX_BINS, "%s: %d bins; 1..%d are supported", name, bins, CAL_MAX_BINS);
+  MMSA_CHECK_ARG(B > 0 && B <= MMSA_EVAL_MAX_IMAGES, "%s: 1..%d images per call, got %d", name, MMSA_EVAL_MAX_IMAGES, B);
+  MMSA_CHECK_ARG(H > 0 && W > 0 && Hl > 0 && Wl > 0 && (long)H * W < (1l << 31) && (long)Hl * Wl < (1l << 31), "%s: bad map size", name);
+  MMSA_CHECK_ARG((ymap != NULL) == (xmap != NULL), "%s: ymap and xmap come together", name);
+  MMSA_CHECK_ARG(ymap || (Hl == H && Wl == W), "%s: size mismatch: the label is %d x %d, the prediction %d x %d, and no ymap / xmap tables were given",
+                 name, Hl, Wl, H, W);
+  MMSA_CHECK_ARG(n_slots > 0, "%s: n_slots must be positive", name);
+  EvalSlots es;
+  for (int b = 0; b < B; ++b) {
+    MMSA_CHECK_ARG(slots[b] >= 0 && slots[b] < n_slots, "%s: slots[%d] = %d outside the %d count slots", name, b, slots[b], n_slots);
+    es.s[b] = slots[b];
+  }
+  const CalArgs a = {pred, conf, label, lut, ymap, xmap, (unsigned long long*)cal, H, W, Hl, Wl, C, bins};
+  if (ymap) {
+    const int rows = max(1, cdiv(CAL_CHUNK, W));
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(eval_calibration_kernel<true>), dim3(cdiv(H, rows), B), dim3(256), 0, stream, a, es, rows);
+  } else {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(eval_calibration_kernel<false>), dim3(cdiv((long)H * W, (long)CAL_CHUNK), B), dim3(256), 0, stream, a, es, 0);
+  }
+  MMSA_CHECK_LAUNCH("eval_calibration");
+  return MMSA_OK;
+}

@@ -14,6 +14,7 @@ from . import preprocess  # noqa: F401  (raw frames -> normalised NCHW, whole or
 from .preprocess import FrameFeeder, Preprocess
 from . import evaluate  # noqa: F401  (confusion counts and mIoU on device: LabelPrep, confusion, Evaluator)
 from .evaluate import Evaluator, LabelPrep, confusion
+from .evaluate import Calibration, calibration  # noqa: F401  (reliability bins, ECE and risk-coverage of the confidence map on device)
 from . import render  # noqa: F401  (the picture of a prediction on device: palette map over the frame, show_result)
 from .render import Renderer
 from .registry import BACKBONES, HEADS, build_backbone, build_head
@@ -38,5 +39,5 @@ if not _HAVE_MMSEG:     # local registry (no mmseg in the process): nothing to o
 
 __all__ = ["SegformerHead", "HEADS", "build_head", "register_head", "SAMAdapterbimodalMixModNewInTwinConvNEW", "SAMAdapterbimodalMixModNewInTwinConvNEWwithcp",
            "BACKBONES", "build_backbone", "ops", "lib", "inference", "Chains", "Replay", "AttentionRangeError", "OperandRangeError",
-           "preprocess", "Preprocess", "FrameFeeder", "evaluate", "Evaluator", "LabelPrep", "confusion", "render", "Renderer",
+           "preprocess", "Preprocess", "FrameFeeder", "evaluate", "Evaluator", "LabelPrep", "confusion", "Calibration", "calibration", "render", "Renderer",
            "probabilities", "aug_inference", "aug_class_map", "AugPlan", "argmax_max_map"]

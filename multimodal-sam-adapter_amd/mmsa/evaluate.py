@@ -9,7 +9,12 @@ Counting is either a pass of its own over a stored map (`confusion`, mmsa_eval_c
 of mmsa.inference's class-map calls, mmsa_slide_argmax_eval).  Only `Evaluator.areas()` copies anything to the host: (C + 1)^2 integers per slot.
 
 Deviation from the reference, on purpose: it sums per-image float32 histograms in float32 (metrics_micro.py:416-419), exact only below 2^24 pixels per
-class and case; the int64 counts here are exact at any size, and the metrics are formed in float64.  There is no CPU path for the counting."""
+class and case; the int64 counts here are exact at any size, and the metrics are formed in float64.  There is no CPU path for the counting.
+
+Calibration of the confidence map (the probability of the predicted class, `confidence=` of the class-map calls) is the second half: `calibration` /
+`Calibration` reduce (class map, confidence map, label map) to int64 [3, K] reliability bins per slot -- total, correct, and the confidence sum in 24-bit
+fixed point (mmsa_eval_calibration, csrc/calibrate.hip) -- from which `reliability_of`, `ece_of`, `mce_of` and `risk_coverage_of` form the reliability
+diagram, the expected / maximum calibration error and accuracy against coverage in float64 on the host.  The reference has no such step."""
 import ctypes
 from collections import OrderedDict
 
@@ -26,6 +31,11 @@ FUSED_DEFAULT = False   # measured (profiles/evaluate.txt): the class map follow
                         # the yardstick's spread: two launches by default; the fused entry is reached with fused=True / return_map=False
 
 _METRICS = ("mIoU", "mDice", "mFscore", "microIoU")
+
+MAX_BINS = 64           # confidence bins per launch (csrc/calibrate.hip CAL_MAX_BINS)
+DEFAULT_BINS = 15       # the usual reliability diagram
+CONF_ONE = 1 << 24      # the fixed-point unit of a bin's confidence sum: conf_sum = sum of floor(conf * 2^24)
+BIN_CAPACITY = 1 << 39  # participating pixels per bin and slot before the int64 confidence sum can overflow (2^39 * 2^24 = 2^63)
 
 
 # ---- host-side restatements (numpy) ----
@@ -97,6 +107,82 @@ def summary_of(metrics):
     """The summary `evaluate` forms from such a dict (DELIVER.py:327-367): nanmean per entry, x 100 rounded to two places, / 100; every key but
     'aAcc' gets the 'm' prefix."""
     return OrderedDict((k if k == "aAcc" else "m" + k, np.round(np.nanmean(v) * 100, 2) / 100.0) for k, v in metrics.items())
+
+
+# ---- calibration metrics from the integer bins (numpy, float64) ----
+def _bins3(bins):
+    """int64 [3, K] (rows total, correct, conf_sum) of one slot, checked; OverflowError where a bin has reached the capacity of its confidence sum."""
+    b = np.asarray(bins)
+    if b.ndim != 2 or b.shape[0] != 3 or b.shape[1] < 1 or b.dtype.kind not in "iu":
+        raise ValueError(f"mmsa.evaluate: calibration bins are an integer [3, K] array (total, correct, conf_sum), got {b.dtype} {b.shape}")
+    b = b.astype(np.int64, copy=False)
+    if (b[0] >= BIN_CAPACITY).any():
+        raise OverflowError(f"mmsa.evaluate: a calibration bin holds {int(b[0].max())} pixels; from 2^39 on its int64 confidence sum may have wrapped "
+                            "(read and reset() the Calibration more often, or split the run over slots)")
+    return b
+
+
+def reliability_of(bins):
+    """The reliability diagram of int64 [3, K] bins -> OrderedDict(edges float64 [K + 1] = k / K, count int64 [K], accuracy = correct / total and
+    confidence = conf_sum / (2^24 total), float64 [K], NaN in an empty bin).  The per-bin confidence lies below the float64 mean of the same
+    confidences by less than 2^-24 (every term is truncated to 24 fractional bits)."""
+    b = _bins3(bins)
+    K = b.shape[1]
+    t = b[0].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return OrderedDict(edges=np.arange(K + 1, dtype=np.float64) / K, count=b[0].copy(), accuracy=b[1].astype(np.float64) / t,
+                           confidence=b[2].astype(np.float64) / (np.float64(CONF_ONE) * t))
+
+
+def _gaps(bins):
+    """(weights total_k / N, |accuracy_k - confidence_k|) over the NON-EMPTY bins; two empty arrays when N == 0."""
+    r = reliability_of(bins)
+    full = r["count"] > 0
+    n = np.float64(max(int(r["count"].sum()), 1))
+    return r["count"][full].astype(np.float64) / n, np.abs(r["accuracy"][full] - r["confidence"][full])
+
+
+def ece_of(bins):
+    """Expected calibration error: sum over the non-empty bins of (total_k / N) |accuracy_k - confidence_k|, float64; NaN when N == 0.  Within 2^-24 of
+    the ECE formed in float64 from the unquantised confidences (the weights sum to 1, each gap moves by less than 2^-24)."""
+    w, g = _gaps(bins)
+    return np.float64(np.nan) if g.size == 0 else np.float64(np.sum(w * g))
+
+
+def mce_of(bins):
+    """Maximum calibration error: the largest |accuracy_k - confidence_k| over the non-empty bins; NaN when N == 0."""
+    _, g = _gaps(bins)
+    return np.float64(np.nan) if g.size == 0 else np.float64(g.max())
+
+
+def accuracy_of(bins):
+    """sum(correct) / sum(total): the reference's aAcc (labels outside [0, C) take no part); NaN when N == 0."""
+    b = _bins3(bins)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.float64(b[1].sum()) / np.float64(b[0].sum())
+
+
+def mean_confidence_of(bins):
+    """sum(conf_sum) / (2^24 sum(total)); NaN when N == 0.  Summed as Python integers: K bins below 2^63 each may pass 2^63 together."""
+    b = _bins3(bins)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.float64(sum(int(v) for v in b[2])) / (np.float64(CONF_ONE) * np.float64(b[0].sum()))
+
+
+def risk_coverage_of(bins):
+    """Accuracy against coverage -> (coverage float64 [K], selective_accuracy float64 [K]): entry k keeps the bins k .. K - 1 (confidence >= k / K),
+    coverage_k = kept / N, selective_accuracy_k = correct among the kept / kept (NaN where nothing is kept).  Entry 0 is (1, accuracy)."""
+    b = _bins3(bins)
+    kept = np.cumsum(b[0][::-1])[::-1].astype(np.float64)
+    good = np.cumsum(b[1][::-1])[::-1].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return kept / np.float64(b[0].sum()), good / kept
+
+
+def calibration_summary_of(bins):
+    """ECE, MCE, aAcc and the mean confidence in PERCENT, rounded to two places as `summary_of` rounds (np.round(v * 100, 2)); NaN when N == 0."""
+    vals = (("ECE", ece_of(bins)), ("MCE", mce_of(bins)), ("aAcc", accuracy_of(bins)), ("mConf", mean_confidence_of(bins)))
+    return OrderedDict((k, np.round(v * 100, 2)) for k, v in vals)
 
 
 # ---- the label side of a launch ----
@@ -249,6 +335,60 @@ def confusion(pred, labels, prep, counts=None, slots=None):
     return counts
 
 
+def _check_confmap(conf, pred):
+    """The confidence map of `pred`: a contiguous float32 [B, H, W] GPU tensor on pred's device with pred's shape (what `confidence=` returns)."""
+    if not isinstance(conf, torch.Tensor) or not conf.is_cuda:
+        raise RuntimeError("mmsa.evaluate: conf must be a GPU tensor (there is no CPU path)")
+    if conf.dtype != torch.float32:
+        raise RuntimeError(f"mmsa.evaluate: conf is {conf.dtype}; a float32 confidence map is expected")
+    if conf.device != pred.device:
+        raise RuntimeError(f"mmsa.evaluate: conf is on {conf.device}, pred on {pred.device}")
+    if tuple(conf.shape) != tuple(pred.shape):
+        raise RuntimeError(f"mmsa.evaluate: conf has shape {tuple(conf.shape)}, pred is [B, H, W] = {tuple(pred.shape)}")
+    if not conf.is_contiguous():
+        raise RuntimeError("mmsa.evaluate: conf must be contiguous (its layout is the class map's)")
+    return conf
+
+
+def _check_bins(bins):
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 1 <= int(bins) <= MAX_BINS:
+        raise ValueError(f"mmsa.evaluate: bins = {bins!r}; 1..{MAX_BINS} confidence bins are supported")
+    return int(bins)
+
+
+def _check_cal(cal, K, device):
+    if (not isinstance(cal, torch.Tensor) or cal.dtype != torch.int64 or cal.dim() != 3 or tuple(cal.shape[1:]) != (3, K) or cal.device != device
+            or not cal.is_contiguous()):
+        raise RuntimeError(f"mmsa.evaluate: cal must be a contiguous int64 [n_slots, 3, {K}] tensor on {device}")
+    return cal
+
+
+@torch.no_grad()
+def calibration(pred, conf, labels, prep, bins=None, cal=None, slots=None):
+    """ADD the reliability bins of the uint8 class maps pred [B, H, W] and their float32 confidence maps conf [B, H, W] against the raw labels
+    [B, Hl, Wl] into cal[slots[b]] (one launch, mmsa_eval_calibration) -> cal, int64 [n_slots, 3, K] on the device, rows total / correct / conf_sum.
+    A pixel takes part iff its transformed label is a class (< C); it is correct iff pred equals it; its bin is min(K - 1, int(float32(c) * float32(K)))
+    of its confidence c clamped to [0, 1] (NaN -> 0); conf_sum adds floor(c * 2^24).  `bins` = K defaults to cal's, or to 15; `slots` defaults to
+    0 .. B - 1 (per-image bins); `cal` defaults to a zeroed buffer of max(slots) + 1 slots."""
+    pred = _check_pred(pred)
+    conf = _check_confmap(conf, pred)
+    B, H, W = (int(v) for v in pred.shape)
+    C = prep.num_classes
+    if bins is None:
+        bins = int(cal.shape[-1]) if isinstance(cal, torch.Tensor) and cal.dim() == 3 else DEFAULT_BINS
+    K = _check_bins(bins)
+    with torch.cuda.device(pred.device):
+        largs = prep.launch_args(labels, B, H, W, pred.device)
+        if cal is None:
+            n_slots = B if slots is None else max(int(s) for s in slots) + 1
+            cal = torch.zeros(n_slots, 3, K, dtype=torch.int64, device=pred.device)
+        _check_cal(cal, K, pred.device)
+        tab = _slot_args(slots, B, cal.shape[0])
+        lib.call("mmsa_eval_calibration", pred.data_ptr(), conf.data_ptr(), largs[0], B, H, W, largs[1], largs[2], largs[3], C, largs[4], largs[5], tab,
+                 cal.shape[0], K, cal.data_ptr(), ops._stream())
+    return cal
+
+
 @torch.no_grad()
 def slide_argmax_eval(lg, n, windows, out, B, H, W, hc, wc, unc, labels, prep, counts, slots=None):
     """mmsa_slide_argmax on the head-resolution logits lg [n, C, hs, ws] AND the counts of its class map in one launch; `out` = None writes no map."""
@@ -262,7 +402,42 @@ def slide_argmax_eval(lg, n, windows, out, B, H, W, hc, wc, unc, labels, prep, c
              unc.data_ptr(), largs[0], largs[1], largs[2], largs[3], largs[4], largs[5], tab, counts.shape[0], counts.data_ptr(), ops._stream())
 
 
-class Evaluator:
+class _SlotOwner:
+    """The slot bookkeeping of a buffer with one slot per image or per case: Evaluator's counts and Calibration's bins."""
+    _who, _read, _one = "Evaluator", "areas()", "an Evaluator"
+
+    def _init_slots(self, cases, images):
+        self.cases = None if cases is None else list(cases)
+        self.n_slots = int(images) if self.cases is None else len(self.cases)
+        if self.n_slots < 1:
+            raise ValueError(f"mmsa.{self._who}: at least one slot")
+        self.used = 0           # per-image mode: slots taken so far
+
+    def slots_for(self, B, case=None, slots=None):
+        """The count slots the NEXT batch of B images gets (nothing is taken yet: add / add_fused take them once their launch has gone through).
+        `slots=` names them outright (a captured call that must hit the same slots on every replay)."""
+        if slots is not None:
+            return [int(s) for s in slots]
+        if self.cases is not None:
+            if case not in self.cases:
+                raise KeyError(f"mmsa.{self._who}: case {case!r} is not one of {self.cases}")
+            return [self.cases.index(case)] * B
+        if case is not None:
+            raise KeyError(f"mmsa.{self._who}: case= needs {self._one} made with cases=[...]")
+        if self.used + B > self.n_slots:
+            raise RuntimeError(f"mmsa.{self._who}: {self.used} + {B} images but {self.n_slots} per-image slots (read {self._read}, reset(), or make it with images=)")
+        return list(range(self.used, self.used + B))
+
+    def _taken(self, B, case, slots):
+        """A launch went through: in per-image mode its images now own their slots (a call that raised has consumed none)."""
+        if slots is None and self.cases is None and case is None:
+            self.used += B
+
+    def _slot_index(self, slot):
+        return self.cases.index(slot) if self.cases is not None and not isinstance(slot, int) else int(slot)
+
+
+class Evaluator(_SlotOwner):
     """Owns the count buffer of an evaluation run.  `cases` = None: one slot per IMAGE, in the order the images are added (what `pre_eval` returns per
     image), `images` slots in all; `cases` = a list of names: one slot per case, every image of an add(..., case=name) goes into that case's slot (the
     `case=[...]` breakdown of the DELIVER configs) with no extra launch.  Pass `device` to have the buffer before the first add (graph capture).
@@ -270,12 +445,8 @@ class Evaluator:
 
     def __init__(self, prep, cases=None, images=MAX_IMAGES, device=None):
         self.prep = prep
-        self.cases = None if cases is None else list(cases)
-        self.n_slots = int(images) if self.cases is None else len(self.cases)
-        if self.n_slots < 1:
-            raise ValueError("mmsa.Evaluator: at least one slot")
+        self._init_slots(cases, images)
         self.counts = None
-        self.used = 0           # per-image mode: slots taken so far
         if device is not None:
             self._buffer(torch.device(device))
 
@@ -288,26 +459,6 @@ class Evaluator:
         elif self.counts.device != device:
             raise RuntimeError(f"mmsa.Evaluator: the counts live on {self.counts.device}, this batch on {device}")
         return self.counts
-
-    def slots_for(self, B, case=None, slots=None):
-        """The count slots the NEXT batch of B images gets (nothing is taken yet: add / add_fused take them once their launch has gone through).
-        `slots=` names them outright (a captured call that must hit the same slots on every replay)."""
-        if slots is not None:
-            return [int(s) for s in slots]
-        if self.cases is not None:
-            if case not in self.cases:
-                raise KeyError(f"mmsa.Evaluator: case {case!r} is not one of {self.cases}")
-            return [self.cases.index(case)] * B
-        if case is not None:
-            raise KeyError("mmsa.Evaluator: case= needs an Evaluator made with cases=[...]")
-        if self.used + B > self.n_slots:
-            raise RuntimeError(f"mmsa.Evaluator: {self.used} + {B} images but {self.n_slots} per-image slots (read areas(), reset(), or make it with images=)")
-        return list(range(self.used, self.used + B))
-
-    def _taken(self, B, case, slots):
-        """A launch went through: in per-image mode its images now own their slots (a call that raised has consumed none)."""
-        if slots is None and self.cases is None and case is None:
-            self.used += B
 
     def add(self, pred, labels, case=None, slots=None):
         """Count a batch of stored class maps (one launch)."""
@@ -343,9 +494,6 @@ class Evaluator:
         """(area_intersect, area_union, area_pred_label, area_label): int64 numpy [n, C] each, row per image (per case with cases=)."""
         return areas_of(self.host_counts())
 
-    def _slot_index(self, slot):
-        return self.cases.index(slot) if self.cases is not None and not isinstance(slot, int) else int(slot)
-
     def metrics(self, metric=("mIoU",), nan_to_num=None, beta=1, slot=None):
         """`total_area_to_metrics` of the totals over every slot (the reference's 'global' entry) or of one slot (index or case name), in float64."""
         a = self.areas()
@@ -355,3 +503,85 @@ class Evaluator:
     def summary(self, metric=("mIoU",), nan_to_num=None, beta=1, slot=None):
         """aAcc / mIoU / mAcc / ... as `evaluate` forms them from the per-class values: nanmean, rounded to two places of a percent."""
         return summary_of(self.metrics(metric, nan_to_num, beta, slot))
+
+
+class Calibration(_SlotOwner):
+    """Owns the reliability bins of a calibration run, as Evaluator owns the confusion counts: int64 [n_slots, 3, K] on the device (`.bins`; rows total,
+    correct, conf_sum), `bins` = K confidence bins of width 1 / K.  `cases` = None: one slot per IMAGE in the order the images are added, `images` slots in
+    all; `cases` = a list of names: one slot per case (the `case=[...]` breakdown of the DELIVER configs, where calibration drifts).  Pass `device` to
+    have the buffer before the first add, and `slots=` to add(), for a call that is captured in a HIP graph.  Only host_bins() copies anything to the
+    host: 3 K integers per slot; every metric is formed from them in float64, of one slot (`slot=` index or case name) or of the sum over all slots
+    (`slot=None`), and raises OverflowError once a bin holds 2^39 pixels.  Across ranks: mmsa.dist.allreduce_counts(cal.bins)."""
+    _who, _read, _one = "Calibration", "host_bins()", "a Calibration"
+
+    def __init__(self, prep, bins=DEFAULT_BINS, cases=None, images=MAX_IMAGES, device=None):
+        self.prep = prep
+        self.n_bins = _check_bins(bins)
+        self._init_slots(cases, images)
+        self.bins = None
+        if device is not None:
+            self._buffer(torch.device(device))
+
+    def _buffer(self, device):
+        if self.bins is None:
+            if _capturing(device):
+                raise RuntimeError("mmsa.Calibration: the bin buffer cannot be allocated during a graph capture: construct the Calibration with device=")
+            self.bins = torch.zeros(self.n_slots, 3, self.n_bins, dtype=torch.int64, device=device)
+        elif self.bins.device != device:
+            raise RuntimeError(f"mmsa.Calibration: the bins live on {self.bins.device}, this batch on {device}")
+        return self.bins
+
+    def add(self, pred, conf, labels, case=None, slots=None):
+        """Bin a batch of stored class maps and their confidence maps (one launch; no host sync, no allocation once the buffer exists)."""
+        pred = _check_pred(pred)
+        conf = _check_confmap(conf, pred)
+        with torch.cuda.device(pred.device):
+            cal = self._buffer(pred.device)
+        calibration(pred, conf, labels, self.prep, bins=self.n_bins, cal=cal, slots=self.slots_for(pred.shape[0], case, slots))
+        self._taken(pred.shape[0], case, slots)
+        return self
+
+    def reset(self):
+        if self.bins is not None:
+            self.bins.zero_()
+        self.used = 0
+
+    def host_bins(self):
+        """The bins on the host (the ONE device-to-host copy of a calibration run): int64 numpy [n, 3, K], n = images added so far / cases."""
+        if self.bins is None:
+            return np.zeros((0 if self.cases is None else self.n_slots, 3, self.n_bins), dtype=np.int64)
+        b = self.bins.cpu().numpy()
+        return b[:self.used] if self.cases is None else b
+
+    def _of(self, slot):
+        """int64 [3, K] of one slot (index or case name), or of the sum over every slot.  A slot at its capacity raises here, before a sum over slots
+        could wrap; a sum whose totals stay below 2^39 has confidence sums below 2^63."""
+        b = self.host_bins()
+        for one in b:
+            _bins3(one)
+        return b.sum(0) if slot is None else b[self._slot_index(slot)]
+
+    def reliability(self, slot=None):
+        """`reliability_of` the slot's bins: edges, count, accuracy and confidence per bin."""
+        return reliability_of(self._of(slot))
+
+    def ece(self, slot=None):
+        return ece_of(self._of(slot))
+
+    def mce(self, slot=None):
+        return mce_of(self._of(slot))
+
+    def accuracy(self, slot=None):
+        """sum(correct) / sum(total): the unrounded aAcc of Evaluator.metrics on the same maps."""
+        return accuracy_of(self._of(slot))
+
+    def mean_confidence(self, slot=None):
+        return mean_confidence_of(self._of(slot))
+
+    def risk_coverage(self, slot=None):
+        """(coverage [K], selective_accuracy [K]): entry k keeps the pixels of the bins k .. K - 1."""
+        return risk_coverage_of(self._of(slot))
+
+    def summary(self, slot=None):
+        """ECE / MCE / aAcc / mConf in percent, rounded to two places."""
+        return calibration_summary_of(self._of(slot))

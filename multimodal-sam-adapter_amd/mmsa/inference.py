@@ -12,6 +12,7 @@ canvases), `aug_class_map` (its argmax, from the canvas path or from ONE launch 
 
 Confidence maps (`confidence=` of the class-map entries, `conf=` of the plans, `argmax_max_map`): the probability of the predicted class, max over the
 classes of what `probabilities` / `aug_inference` return (ED:449,460), float32 [B, Ho, Wo], written by the launch that writes the class map.
+`calibration=` (mmsa.evaluate.Calibration) of the same entries bins that map against `labels=` on device: one more launch over the stored map and confidence.
 
 What a frame's output looks like -- its windows, the size after the second resize and after the cut, which class-map kernel that takes -- is decided once,
 in `MapPlan`, a record without device state; the entries read the frame (`_intake`), make the plan, and launch from it."""
@@ -233,6 +234,29 @@ def _confidence(confidence, size, device, what, fused=None, return_map=True):
     return _check_conf(confidence, size, device, what)
 
 
+def _check_calibration(calibration, labels, confidence, what, fused=None, return_map=True):
+    """`calibration=` of an entry, refused by name before anything is launched: it bins the confidence map against the labels, so it needs both, and the
+    stored map (the fused class-map + evaluation launch writes no confidence).  `confidence`: the entry's `confidence=`, or a runner's buffer."""
+    if calibration is None:
+        return
+    from .evaluate import Calibration
+    if not isinstance(calibration, Calibration):
+        raise RuntimeError(f"mmsa.{what}: calibration= takes an mmsa.evaluate.Calibration, got {type(calibration).__name__}")
+    if labels is None:
+        raise RuntimeError(f"mmsa.{what}: calibration= needs labels= (the raw uint8 label maps the confidence is checked against)")
+    if confidence is None or confidence is False:
+        raise RuntimeError(f"mmsa.{what}: calibration= needs the confidence map: pass confidence=True or an output tensor (a SlideRunner: make it with "
+                           "confidence=True)")
+    if fused or not return_map:
+        raise RuntimeError(f"mmsa.{what}: {_NO_CONF_FUSED}")
+
+
+def _check_labels(labels, evaluator, calibration):
+    """`labels=` feed an evaluator, a calibration or both; an evaluator needs them."""
+    if (labels is None) != (evaluator is None) and not (labels is not None and calibration is not None):
+        raise RuntimeError("mmsa.inference: labels= and evaluator= come together")
+
+
 @dataclasses.dataclass(frozen=True)
 class MapPlan:
     """The output geometry of one frame batch, decided on the host before anything is launched: B x (H x W) is the canvas the windows cover, hc x wc the
@@ -321,7 +345,7 @@ class MapPlan:
         """mmsa_slide_argmax, or its sibling that also writes `conf`."""
         lib.call("mmsa_slide_argmax" if conf is None else "mmsa_slide_argmax_conf", *self._args(lg, out, conf), unc.data_ptr(), ops._stream())
 
-    def class_map(self, lg, out, unc, labels=None, evaluator=None, case=None, fused=None, return_map=True, one_pass=None, conf=None):
+    def class_map(self, lg, out, unc, labels=None, evaluator=None, case=None, fused=None, return_map=True, one_pass=None, conf=None, calibration=None):
         """The class-map launch of the three class-map calls, from the head-resolution logits lg [n, C, hs, ws] into out uint8 [B, Ho, Wo] and the
         uncovered-pixel word `unc`.  Without `labels`: mmsa_slide_argmax.  With `labels` (raw uint8 label maps [B, Hl, Wl]) and `evaluator`
         (mmsa.evaluate.Evaluator): the confusion counts of the map are ADDED to the evaluator's buffer as well -- by the same launch
@@ -332,14 +356,16 @@ class MapPlan:
         `conf` (a contiguous float32 [B, Ho, Wo] tensor on the map's device): the confidence map max_c softmax(logits)[c] (ED:449,460) is written too, by
         the `_conf` sibling of the launch the plan takes (mmsa_slide_argmax_conf / mmsa_slide_argmax_resized_conf; on the canvas path
         mmsa_softmax_flip_accum_nchw + mmsa_argmax_max_nchw): bit for bit probabilities(...).max(1), 0 where the map is 255.  The fused evaluation launch
-        has no such sibling: `fused=True` / `return_map=False` are refused, and counts go through the stored map."""
+        has no such sibling: `fused=True` / `return_map=False` are refused, and counts go through the stored map.
+        `calibration` (mmsa.evaluate.Calibration; needs `labels` and `conf`, `evaluator` is optional with it): the reliability bins of the map and its
+        confidence are ADDED to its buffer by one more launch over the stored map and confidence (mmsa_eval_calibration), whatever launch wrote them."""
+        _check_calibration(calibration, labels, conf, "inference", fused, return_map)
         if conf is not None:
             if fused or not return_map:
                 raise RuntimeError(f"mmsa.inference: {_NO_CONF_FUSED}")
             _check_conf(conf, (self.B, self.Ho, self.Wo), out.device)
         if self.rescaled:
-            if (labels is None) != (evaluator is None):
-                raise RuntimeError("mmsa.inference: labels= and evaluator= come together")
+            _check_labels(labels, evaluator, calibration)
             if fused or not return_map:
                 raise RuntimeError("mmsa.inference: fused=True / return_map=False need the fused class-map + evaluation launch, and that launch has no variant at "
                                    "a rescaled or cut size: the counts of a rescaled map go through the stored map (drop fused= / return_map=)")
@@ -352,6 +378,8 @@ class MapPlan:
                 _rescaled_map_canvas(self, lg, out, unc, conf)
             if evaluator is not None:
                 evaluator.add(out, labels, case=case)
+            if calibration is not None:
+                calibration.add(out, conf, labels, case=case)
             return
         if one_pass is not None:
             raise RuntimeError("mmsa.inference: one_pass= chooses the launch of a RESCALED class map; this map has the frame's size")
@@ -360,8 +388,11 @@ class MapPlan:
                 raise RuntimeError("mmsa.inference: return_map=False only makes sense with labels= and evaluator=")
             self._plain(lg, out, unc, conf)
             return
-        if labels is None or evaluator is None:
-            raise RuntimeError("mmsa.inference: labels= and evaluator= come together")
+        _check_labels(labels, evaluator, calibration)
+        if evaluator is None:                              # labels for the calibration alone
+            self._plain(lg, out, unc, conf)
+            calibration.add(out, conf, labels, case=case)
+            return
         if fused is False and not return_map:
             raise RuntimeError("mmsa.inference: return_map=False needs the fused launch (two launches go through the stored map); drop fused=False")
         from . import evaluate
@@ -370,6 +401,8 @@ class MapPlan:
         else:
             self._plain(lg, out, unc, conf)
             evaluator.add(out, labels, case=case)
+        if calibration is not None:
+            calibration.add(out, conf, labels, case=case)
 
 
 def _canvas_logits(plan, lg, unc):
@@ -403,7 +436,7 @@ def _rescaled_map_canvas(plan, lg, out, unc, conf=None):
 @_on_device
 @torch.no_grad()
 def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preprocess=None, labels=None, evaluator=None, case=None, fused=None,
-                    return_map=True, render=None, ori_shape=None, one_pass=None, confidence=False):
+                    return_map=True, render=None, ori_shape=None, one_pass=None, confidence=False, calibration=None):
     """`simple_test` of a sliding-window frame (ED:191-234 + ED:449,477) -> uint8 class map [B, H, W], without the
     [B, classes, H, W] logits canvas: every window's logits stay at head resolution and ONE kernel (mmsa_slide_argmax) resizes,
     sums the overlapping windows in window order, divides by the count and takes the argmax -- the same additions in the same order
@@ -421,7 +454,11 @@ def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preproc
     `confidence=` True, or a contiguous float32 [B, h, w] tensor on the device to write into (nothing is allocated for it, so the launch can be captured):
     the confidence map -- the probability of the predicted class, bit for bit probabilities(...).max(1).values, 0 where the map is 255 -- is written by the
     same launch and returned as the LAST element: (map, unc[, picture], conf).  Refused with `fused=True` / `return_map=False`; `labels=` count through the
-    stored map."""
+    stored map.
+    `calibration=` (mmsa.evaluate.Calibration; `case=` with a per-case one): the reliability bins of the map and its confidence against `labels=` are
+    added to it on device by one more launch (mmsa_eval_calibration), no host sync; it needs `labels=` and `confidence=`, `evaluator=` is optional with
+    it, and what is returned does not change."""
+    _check_calibration(calibration, labels, confidence, "slide_class_map", fused, return_map)
     B, H, W, device, frame, cut = _intake(img, preprocess, "slide_class_map")
     plan = MapPlan.slide(B, H, W, crop_size, stride, ori_shape)
     src = None if render is None else slide_source(render, preprocess, frame, plan, return_map, "slide_class_map")
@@ -435,7 +472,7 @@ def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preproc
     lg = lgs[0] if len(lgs) == 1 else torch.cat(lgs, 0)
     out = torch.empty(B, plan.Ho, plan.Wo, dtype=torch.uint8, device=device)
     unc = torch.zeros(1, dtype=torch.int32, device=device)
-    plan.class_map(lg, out, unc, labels, evaluator, case, fused, return_map, one_pass, conf)
+    plan.class_map(lg, out, unc, labels, evaluator, case, fused, return_map, one_pass, conf, calibration)
     r = (out, unc, render(out, src)) if render is not None else ((out if return_map else None), unc)   # unc[0] != 0 <=> some pixel is not covered (ED:220); checked by the caller outside a capture
     return r if conf is None else r + (conf,)
 
@@ -443,7 +480,7 @@ def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preproc
 @_on_device
 @torch.no_grad()
 def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator=None, case=None, fused=None, return_map=True, render=None,
-                    ori_shape=None, dim=None, cut_dim=None, rescale=True, one_pass=None, confidence=False):
+                    ori_shape=None, dim=None, cut_dim=None, rescale=True, one_pass=None, confidence=False, calibration=None):
     """Whole-image `simple_test`: resize x4 (bilinear, align_corners=False) + argmax fused (ED:90-94,449,477) -> uint8 [B, H, W].
     `preprocess=` (mmsa.preprocess.Preprocess): img is the pair (rgb, aux) of raw frames, normalised (and padded) by one launch.
     `labels=` + `evaluator=` (+ `case=`): as in slide_class_map.
@@ -457,7 +494,9 @@ def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator
                                 crop [:cut_dim[1], :cut_dim[0]] of the map at `dim` (rescale) or at the input size (`rescale=False`, the FMB configs).
     A LabelPrep for `labels=` must be built for that size; `fused=True` / `return_map=False` are refused; `render=` needs a source of the map's size: raw
     uint8 frames of the size before the cut, or -- for a cut alone -- the input tensor.
-    `confidence=`: as in slide_class_map; the confidence map float32 [B, Ho, Wo] comes as the last element, (map[, picture], conf)."""
+    `confidence=`: as in slide_class_map; the confidence map float32 [B, Ho, Wo] comes as the last element, (map[, picture], conf).
+    `calibration=`: as in slide_class_map (needs `labels=` and `confidence=`); at a rescaled or cut size the pass reads the map and confidence stored there."""
+    _check_calibration(calibration, labels, confidence, "whole_class_map", fused, return_map)
     rgb = None
     if preprocess is not None:
         rgb, aux, B, H, W = _raw(preprocess, img, "whole_class_map")
@@ -476,7 +515,7 @@ def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator
     lg = head(feats)
     out = torch.empty(B, plan.Ho, plan.Wo, dtype=torch.uint8, device=img.device)
     unc = torch.zeros(1, dtype=torch.int32, device=img.device)
-    plan.class_map(lg, out, unc, labels, evaluator, case, fused, return_map, one_pass, conf)
+    plan.class_map(lg, out, unc, labels, evaluator, case, fused, return_map, one_pass, conf, calibration)
     if render is not None:
         return (out, render(out, src)) if conf is None else (out, render(out, src), conf)
     if conf is not None:
@@ -545,16 +584,19 @@ def inference(backbone, head, img, test_cfg, rescale=True, preprocess=None, ori_
 @_on_device
 @torch.no_grad()
 def class_map(backbone, head, img, test_cfg, rescale=True, ori_shape=None, preprocess=None, labels=None, evaluator=None, case=None, render=None, one_pass=None,
-              confidence=False):
+              confidence=False, calibration=None):
     """`simple_test` (ED:471-477) by mode: the dispatch of `inference` (ED:417-447) onto the class-map calls -> uint8 map, bit for bit
     argmax_map(inference(...)) of the same arguments, without a logits canvas: [B, H, W], or at the size `rescale` gives ('slide' / 'whole': `ori_shape`;
     'whole_dim': test_cfg['dim']; 'whole_dim_cut': the crop of the map at `dim`, or at the input size without `rescale`).  What `inference` refuses is
     refused here ('slide_mod_sel'; 'whole_dim' with rescale=False).  'slide' reads the kernel's uncovered-pixel word back (one host sync, as
     slide_inference's coverage check is) and raises on a window grid that does not cover the frame (ED:220).
     `preprocess=`, `labels=` + `evaluator=` (+ `case=`; through the stored map), `render=` (-> (map, picture)), `one_pass=`: as in the calls it goes to.
-    `confidence=` (True or an output tensor): the confidence map, probabilities(...).max(1).values bit for bit, as the last element: (map[, picture], conf)."""
+    `confidence=` (True or an output tensor): the confidence map, probabilities(...).max(1).values bit for bit, as the last element: (map[, picture], conf).
+    `calibration=` (mmsa.evaluate.Calibration; needs `labels=` and `confidence=`): as in the calls it goes to."""
     mode = test_cfg["mode"]
-    kw = dict(preprocess=preprocess, labels=labels, evaluator=evaluator, case=case, render=render, one_pass=one_pass, confidence=confidence)
+    _check_calibration(calibration, labels, confidence, "class_map")
+    kw = dict(preprocess=preprocess, labels=labels, evaluator=evaluator, case=case, render=render, one_pass=one_pass, confidence=confidence,
+              calibration=calibration)
     if mode == "slide":
         r = slide_class_map(backbone, head, img, tuple(test_cfg["crop_size"]), tuple(test_cfg["stride"]), ori_shape=ori_shape if rescale else None, **kw)
         if int(r[1].item()) != 0:
@@ -840,7 +882,7 @@ def aug_inference(backbone, head, imgs, test_cfg, ori_shape=None, flips=None, pr
 @_on_views_device
 @torch.no_grad()
 def aug_class_map(backbone, head, imgs, test_cfg, ori_shape=None, flips=None, preprocess=None, max_batch=8, labels=None, evaluator=None, case=None,
-                  one_pass=None, confidence=False):
+                  one_pass=None, confidence=False, calibration=None):
     """`aug_test` (ED:509-546) -> (uint8 class map [B, Ho, Wo], uncovered-pixel word), bit for bit argmax_map(aug_inference(...)) of the same arguments.
     Every view goes through backbone and head (`max_batch` windows per call, per view); then ONE launch (mmsa_aug_argmax) resizes every view's
     head-resolution logits as `class_map` would, takes the softmax, un-flips, averages over the views and takes the argmax, with no logits or probability
@@ -849,9 +891,11 @@ def aug_class_map(backbone, head, imgs, test_cfg, ori_shape=None, flips=None, pr
     has put the plan's window table on the device.  unc[0] != 0 <=> some view's windows do not cover its frame (ED:220): checked by the caller.
     `labels=` + `evaluator=` (+ `case=`): the map's confusion counts are added to the evaluator through the stored map, as at any rescaled size.
     `confidence=` (True or a contiguous float32 [B, Ho, Wo] output tensor): the confidence map -- the mean probability of the predicted class, bit for bit
-    aug_inference(...).max(1).values, 0 where the map is 255 -- from the same launch, as the last element: (map, unc, conf)."""
-    if (labels is None) != (evaluator is None):
-        raise RuntimeError("mmsa.inference: labels= and evaluator= come together")
+    aug_inference(...).max(1).values, 0 where the map is 255 -- from the same launch, as the last element: (map, unc, conf).
+    `calibration=` (mmsa.evaluate.Calibration; needs `labels=` and `confidence=`, `evaluator=` is optional with it): the reliability bins of the averaged map
+    and its confidence are added to it by one more launch over the stored map and confidence."""
+    _check_calibration(calibration, labels, confidence, "aug_class_map")
+    _check_labels(labels, evaluator, calibration)
     imgs, flips, pre = AugPlan.views(imgs, flips, preprocess, "aug_class_map")
     frames = [_intake(img, p, "aug_class_map") for img, p in zip(imgs, pre)]
     plan = AugPlan.of(test_cfg, [f[:3] for f in frames], flips, ori_shape)
@@ -871,6 +915,8 @@ def aug_class_map(backbone, head, imgs, test_cfg, ori_shape=None, flips=None, pr
     plan.class_map(lgs, out, unc, one_pass, conf)
     if evaluator is not None:
         evaluator.add(out, labels, case=case)
+    if calibration is not None:
+        calibration.add(out, conf, labels, case=case)
     return (out, unc) if conf is None else (out, unc, conf)
 
 
@@ -945,14 +991,17 @@ class SlideRunner:
                 self.pic = torch.empty(B, plan.Ho, plan.Wo, 3, dtype=torch.uint8, device=self.device)
 
     @torch.no_grad()
-    def run(self, frame=None, labels=None, evaluator=None, case=None, fused=None, return_map=True):
+    def run(self, frame=None, labels=None, evaluator=None, case=None, fused=None, return_map=True, calibration=None):
         """Enqueue one frame on the current stream (asynchronous) -> FrameResult; `.outputs()` = (class map uint8 [B, H, W], uncovered-pixel flag) once the
         attention logit guard of this pass has been inspected.  The inspection costs one 4 * depth-byte copy per `check_every` frames and an event wait,
         no device sync; a frame that scored logits beyond the fp16 range raises mmsa.chains.AttentionRangeError from outputs() -- or from the next run(),
         whichever comes first -- after the blocks concerned have been moved to fp16 hi/lo pairs and the graphs captured again: run that frame again.
         `labels=` + `evaluator=` (mmsa.evaluate.Evaluator, best one made with cases=[...] and device=; `case=`): the frame's confusion counts are ADDED to the
         evaluator on device (see MapPlan.class_map); a frame that has to be run again has been counted, so reset the evaluator or subtract what it added.
-        `return_map=False` (always the fused launch) leaves the runner's map buffer untouched; the FrameResult's map is then None."""
+        `return_map=False` (always the fused launch) leaves the runner's map buffer untouched; the FrameResult's map is then None.
+        `calibration=` (mmsa.evaluate.Calibration, best one made with cases=[...] and device=; a runner made with confidence=True; needs `labels=`): the
+        frame's reliability bins are ADDED to it on device by one more launch; a frame that has to be run again has been binned, as it has been counted."""
+        _check_calibration(calibration, labels, self.conf, "SlideRunner.run", fused, return_map)
         if self.conf is not None and (fused or not return_map):
             raise RuntimeError(f"mmsa.SlideRunner.run: {_NO_CONF_FUSED}")
         if frame is None:
@@ -969,7 +1018,7 @@ class SlideRunner:
             rp = self.chains.replay()
             lg = rp.unverified          # the argmax kernel below is enqueued behind the pass; nothing is read on the host before outputs() verifies it
             self.unc.zero_()
-            self.plan.class_map(lg, self.out, self.unc, labels, evaluator, case, fused, return_map, self.one_pass, self.conf)
+            self.plan.class_map(lg, self.out, self.unc, labels, evaluator, case, fused, return_map, self.one_pass, self.conf, calibration)
             if self.render is not None:
                 self.render(self.out, src, out=self.pic)
         return FrameResult(self, rp, has_map=return_map)
