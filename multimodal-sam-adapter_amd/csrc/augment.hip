@@ -50,56 +50,22 @@ extern "C" int mmsa_softmax_flip_accum_nchw(const float* logits, float* acc, int
 struct AugView { const float* logits; int w0, n, hs, ws, H, W, hc, wc, flip; float rh, rw, rh2, rw2; };
 struct AugViews { int A; AugView v[MMSA_MAX_AUGS]; };
 
-// The logits of view `v` at position (Y, X) of its Hd x Wd map -> xs[c * T], c = 0 .. C-1: the body of slide_argmax_resized_kernel (segment.hip) with the
-// argmax taken out -- the same formulas in the same order, the same per-tap window counts.  false: a tap has no window, or more than 8.
+// The logits of view `v` at position (Y, X) of its Hd x Wd map -> xs[c * T], c = 0 .. C-1: the two-stage pixel of slide_taps.h, as slide_argmax_resized_kernel
+// (segment.hip) takes it, with the argmax taken out.  false: a tap has no window, or more than 8.  The view's fields are copied to locals first, as this
+// function always did: handing v.* straight to the two functions is the same arithmetic in another instruction stream, and aug_argmax_conf_kernel measured
+// 75 us (1 %) slower that way (profiles/class_map_pixel_refactor.txt).
 __device__ __forceinline__ bool aug_view_logits(const AugView& v, const int* __restrict__ windows, int C, int b, int Y, int X, float* xs, int T) {
   const float* __restrict__ logits = v.logits;
   const DevWindows wt = {windows + 3 * (long)v.w0, v.n};
   const int hs = v.hs, ws = v.ws, H = v.H, W = v.W, hc = v.hc, wc = v.wc;
   const float rh = v.rh, rw = v.rw;
-  // second stage: the taps of output pixel (Y, X) in the H x W canvas (bilinear_accum_kernel with src = the canvas)
-  float sh2 = ((float)Y + 0.5f) * v.rh2 - 0.5f, sw2 = ((float)X + 0.5f) * v.rw2 - 0.5f;
-  sh2 = sh2 < 0.f ? 0.f : sh2;
-  sw2 = sw2 < 0.f ? 0.f : sw2;
-  const int y0 = min((int)sh2, H - 1), x0 = min((int)sw2, W - 1);
-  const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
-  const float lh2 = sh2 - (float)y0, lw2 = sw2 - (float)x0;
-  // first stage: the covering windows of each tap (tap t: row y0 / y1 = t >> 1, column x0 / x1 = t & 1).  Slot arrays only ever indexed by unrolled constants.
-  TapSlots tp[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    tp[t].nk = 0;
-#pragma unroll
-    for (int q = 0; q < RESIZED_SLOTS; ++q) { tp[t].o[q] = tp[t].kf[q] = 0; tp[t].lh[q] = tp[t].lw[q] = 0.f; }
-  }
-  for (int k = 0; k < wt.n; ++k) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      int o, kf;
-      float lh, lw;
-      if (!tap_coords(wt, k, b, t >> 1 ? y1 : y0, t & 1 ? x1 : x0, hc, wc, hs, ws, rh, rw, o, kf, lh, lw)) continue;
-#pragma unroll
-      for (int q = 0; q < RESIZED_SLOTS; ++q)
-        if (q == tp[t].nk) { tp[t].o[q] = o; tp[t].kf[q] = kf; tp[t].lh[q] = lh; tp[t].lw[q] = lw; }
-      ++tp[t].nk;
-    }
-  }
-  const int nmin = min(min(tp[0].nk, tp[1].nk), min(tp[2].nk, tp[3].nk)), nmax = max(max(tp[0].nk, tp[1].nk), max(tp[2].nk, tp[3].nk));
-  if (nmin == 0 || nmax > 8) return false;
-  if (nmax <= RESIZED_SLOTS) {
-    for (int c = 0; c < C; ++c) {
-      const float p00 = tap_value(tp[0], logits, C, c, hs, ws), p01 = tap_value(tp[1], logits, C, c, hs, ws);
-      const float p10 = tap_value(tp[2], logits, C, c, hs, ws), p11 = tap_value(tp[3], logits, C, c, hs, ws);
-      xs[c * T] = (1.f - lh2) * ((1.f - lw2) * p00 + lw2 * p01) + lh2 * ((1.f - lw2) * p10 + lw2 * p11);
-    }
+  TwoStagePixel px;
+  two_stage_setup(px, wt, b, Y, X, H, W, hc, wc, hs, ws, rh, rw, v.rh2, v.rw2);
+  if (px.nmin == 0 || px.nmax > 8) return false;
+  if (px.nmax <= RESIZED_SLOTS) {
+    for (int c = 0; c < C; ++c) xs[c * T] = two_stage_value<false>(px, wt, b, logits, C, c, hs, ws, hc, wc, rh, rw);
   } else {
-    for (int c = 0; c < C; ++c) {
-      const float p00 = tap_value_scan(wt, b, y0, x0, tp[0].nk, logits, C, c, hs, ws, hc, wc, rh, rw);
-      const float p01 = tap_value_scan(wt, b, y0, x1, tp[1].nk, logits, C, c, hs, ws, hc, wc, rh, rw);
-      const float p10 = tap_value_scan(wt, b, y1, x0, tp[2].nk, logits, C, c, hs, ws, hc, wc, rh, rw);
-      const float p11 = tap_value_scan(wt, b, y1, x1, tp[3].nk, logits, C, c, hs, ws, hc, wc, rh, rw);
-      xs[c * T] = (1.f - lh2) * ((1.f - lw2) * p00 + lw2 * p01) + lh2 * ((1.f - lw2) * p10 + lw2 * p11);
-    }
+    for (int c = 0; c < C; ++c) xs[c * T] = two_stage_value<true>(px, wt, b, logits, C, c, hs, ws, hc, wc, rh, rw);
   }
   return true;
 }
@@ -181,10 +147,9 @@ static int aug_argmax_launch(const char* name, const float* const* logits, const
     MMSA_CHECK_ARG(Hd > 0 && Wd > 0 && Ho <= Hd && Wo <= Wd, "%s: view %d: the cut %dx%d must lie inside the target %dx%d", name, a, Ho, Wo, Hd, Wd);
     MMSA_CHECK_ARG(v.n > 0 && v.n <= MMSA_MAX_WINDOWS && v.w0 >= 0 && (long)v.w0 + v.n <= total, "%s: view %d: 1..%d windows per view, inside the table of %d rows",
                    name, a, MMSA_MAX_WINDOWS, total);
-    for (int k = 0; k < v.n; ++k) {      // as fill_windows of segment.hip
+    for (int k = 0; k < v.n; ++k) {
       const int* w = windows_host + 3 * (long)(v.w0 + k);
-      MMSA_CHECK_ARG(w[0] >= 0 && w[0] < B && w[1] >= 0 && w[2] >= 0 && w[1] + v.hc <= v.H && w[2] + v.wc <= v.W,
-                     "%s: view %d window %d (image %d, y0 %d, x0 %d, %dx%d) outside the [%d, %d, %d] input", name, a, k, w[0], w[1], w[2], v.hc, v.wc, B, v.H, v.W);
+      if (int rc = check_window(name, a, k, w[0], w[1], w[2], v.hc, v.wc, B, v.H, v.W)) return rc;
     }
     v.rh = (float)v.hs / (float)v.hc; v.rw = (float)v.ws / (float)v.wc;
     v.rh2 = (float)v.H / (float)Hd; v.rw2 = (float)v.W / (float)Wd;

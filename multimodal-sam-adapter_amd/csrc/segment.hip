@@ -14,7 +14,7 @@
 // (slide_argmax) must round the SAME interpolation formula identically, or an exact tie between two classes in one of them is not a
 // tie in the other (seen once in 2 073 600 pixels of a 1080 x 1920 frame, where the compiler had contracted the two differently).
 #pragma clang fp contract(off)
-#include "slide_taps.h"   // WindowTable and the tap arithmetic of the rescaled class map (shared with augment.hip)
+#include "slide_taps.h"   // WindowTable, the tap arithmetic and the two-stage pixel of the rescaled class map (shared with augment.hip)
 #include "softmax_px.h"   // the softmax of the confidence variants (shared with augment.hip)
 
 __global__ __launch_bounds__(256) void bilinear_accum_kernel(const float* __restrict__ src, int C, int hs, int ws, long sstrideB,
@@ -104,8 +104,7 @@ static int fill_windows(WindowTable& wt, const int* windows, int n, int B, int H
   wt.n = n;
   for (int k = 0; k < n; ++k) {
     wt.b[k] = windows[3 * k]; wt.y0[k] = windows[3 * k + 1]; wt.x0[k] = windows[3 * k + 2];
-    MMSA_CHECK_ARG(wt.b[k] >= 0 && wt.b[k] < B && wt.y0[k] >= 0 && wt.x0[k] >= 0 && wt.y0[k] + hc <= H && wt.x0[k] + wc <= W,
-                   "%s: window %d (image %d, y0 %d, x0 %d, %dx%d) outside the [%d, %d, %d] input", name, k, wt.b[k], wt.y0[k], wt.x0[k], hc, wc, B, H, W);
+    if (int rc = check_window(name, -1, k, wt.b[k], wt.y0[k], wt.x0[k], hc, wc, B, H, W)) return rc;
   }
   return MMSA_OK;
 }
@@ -169,18 +168,7 @@ __global__ __launch_bounds__(256) void slide_argmax_eval_kernel(const float* __r
   eval_hist_flush(eval_lds, ev.counts + (long)es.s[blockIdx.z] * nbins, nbins);
 }
 
-extern "C" int mmsa_slide_argmax(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out,
-                                 int B, int H, int W, int hc, int wc, int* uncovered /* device int, zeroed by the caller */, hipStream_t stream) {
-  MMSA_CHECK_ARG(logits && out && uncovered && C > 0 && C <= 255 && hs > 0 && ws > 0 && hc > 0 && wc > 0 && B > 0 && H <= 65535 && B <= 65535, "slide_argmax: bad args");
-  WindowTable wt;
-  int rc = fill_windows(wt, windows, n, B, H, W, hc, wc, "slide_argmax");
-  if (rc) return rc;
-  hipLaunchKernelGGL(slide_argmax_kernel, dim3(cdiv(W, 256), H, B), dim3(256), 0, stream, logits, C, hs, ws, out, H, W, hc, wc,
-                     (float)hs / (float)hc, (float)ws / (float)wc, wt, uncovered);
-  MMSA_CHECK_LAUNCH("slide_argmax");
-  return MMSA_OK;
-}
-
+// (mmsa_slide_argmax: below, with mmsa_slide_argmax_conf and the launch helper they share)
 extern "C" int mmsa_slide_argmax_eval(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out /* or NULL */,
                                       int B, int H, int W, int hc, int wc, int* uncovered, const unsigned char* label, int Hl, int Wl,
                                       const unsigned char* lut, const int* ymap, const int* xmap, const int* slots /* HOST [B] */, int n_slots,
@@ -209,30 +197,56 @@ extern "C" int mmsa_slide_argmax_eval(const float* logits, int n, int C, int hs,
 // with its own covering windows and its own count.  Both stages are the file's formula in the file's operation order (no contraction, see the top), so
 // the map equals bilinear_accum + div_count + bilinear_accum + argmax + crop bit for bit.  A pixel with a tap that no window covers, or more than 8
 // windows, gets 255 and is counted in `uncovered`.
-// The taps (TapSlots, tap_coords, tap_term, tap_value, tap_value_scan; why a tap keeps four windows in registers): csrc/slide_taps.h.
+// The pixel (TwoStagePixel: set-up and value; why a tap keeps four windows in registers): csrc/slide_taps.h.
+// CONF: the probability of the predicted class also goes to `conf` float [B, Hcut, Wcut] (0 for a 255 pixel), by a second pass over the classes in the form
+// the first one took (slots or scanning), for the reason slide_pixel.inc gives: the same values again, now that their maximum `best` is known.
+template <bool CONF>
+__device__ __forceinline__ void slide_resized_pixel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out, float* __restrict__ conf,
+                                                    int H, int W, int hc, int wc, float rh, float rw, int Hcut, int Wcut, float rh2, float rw2,
+                                                    const WindowTable& wt, int* __restrict__ uncovered) {
+  const int X = blockIdx.x * 256 + threadIdx.x, Y = blockIdx.y, b = blockIdx.z;
+  if (X >= Wcut) return;
+  TwoStagePixel px;
+  two_stage_setup(px, wt, b, Y, X, H, W, hc, wc, hs, ws, rh, rw, rh2, rw2);
+  const long op = ((long)b * Hcut + Y) * Wcut + X;
+  if (px.nmin == 0 || px.nmax > 8) {      // a tap without a window, or with more than 8: counted once per output pixel, and the pixel gets 255
+    atomicAdd(uncovered, 1);
+    out[op] = 255;
+    if constexpr (CONF) conf[op] = 0.f;
+    return;
+  }
+  const bool slots = px.nmax <= RESIZED_SLOTS;
+  float best = -INFINITY;
+  int bi = 0;
+  if (slots) {
+    for (int c = 0; c < C; ++c) {
+      const float p = two_stage_value<false>(px, wt, b, logits, C, c, hs, ws, hc, wc, rh, rw);
+      if (c == 0 || p > best) { best = p; bi = c; }      // first maximum wins, like torch.argmax on ties
+    }
+  } else {
+    for (int c = 0; c < C; ++c) {
+      const float p = two_stage_value<true>(px, wt, b, logits, C, c, hs, ws, hc, wc, rh, rw);
+      if (c == 0 || p > best) { best = p; bi = c; }
+    }
+  }
+  out[op] = (unsigned char)bi;
+  if constexpr (CONF) {
+    float s = 0.f;
+    if (slots)
+      for (int c = 0; c < C; ++c) s = softmax_px_sum(s, softmax_px_exp(two_stage_value<false>(px, wt, b, logits, C, c, hs, ws, hc, wc, rh, rw), best), c == 0);
+    else
+      for (int c = 0; c < C; ++c) s = softmax_px_sum(s, softmax_px_exp(two_stage_value<true>(px, wt, b, logits, C, c, hs, ws, hc, wc, rh, rw), best), c == 0);
+    conf[op] = softmax_px_prob(softmax_px_exp(best, best), s);
+  }
+}
+
 __global__ __launch_bounds__(256) void slide_argmax_resized_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
                                                                    int H, int W, int hc, int wc, float rh, float rw, int Hcut, int Wcut, float rh2, float rw2,
                                                                    WindowTable wt, int* __restrict__ uncovered) {
-#define RESIZED_CONF 0
-#include "slide_resized_pixel.inc"
-#undef RESIZED_CONF
+  slide_resized_pixel<false>(logits, C, hs, ws, out, nullptr, H, W, hc, wc, rh, rw, Hcut, Wcut, rh2, rw2, wt, uncovered);
 }
 
-extern "C" int mmsa_slide_argmax_resized(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out,
-                                         int B, int H, int W, int hc, int wc, int Hd, int Wd, int Hcut, int Wcut,
-                                         int* uncovered /* device int, zeroed by the caller */, hipStream_t stream) {
-  MMSA_CHECK_ARG(logits && out && uncovered && C > 0 && C <= 255 && hs > 0 && ws > 0 && hc > 0 && wc > 0 && B > 0 && H > 0 && W > 0 && B <= 65535,
-                 "slide_argmax_resized: bad args");
-  MMSA_CHECK_ARG(Hd > 0 && Wd > 0 && Hcut > 0 && Wcut > 0 && Hcut <= Hd && Wcut <= Wd && Hcut <= 65535,
-                 "slide_argmax_resized: the cut %dx%d must lie inside the target %dx%d (and have at most 65535 rows)", Hcut, Wcut, Hd, Wd);
-  WindowTable wt;
-  int rc = fill_windows(wt, windows, n, B, H, W, hc, wc, "slide_argmax_resized");
-  if (rc) return rc;
-  hipLaunchKernelGGL(slide_argmax_resized_kernel, dim3(cdiv(Wcut, 256), Hcut, B), dim3(256), 0, stream, logits, C, hs, ws, out, H, W, hc, wc,
-                     (float)hs / (float)hc, (float)ws / (float)wc, Hcut, Wcut, (float)H / (float)Hd, (float)W / (float)Wd, wt, uncovered);
-  MMSA_CHECK_LAUNCH("slide_argmax_resized");
-  return MMSA_OK;
-}
+// (mmsa_slide_argmax_resized: below, with mmsa_slide_argmax_resized_conf and the launch helper they share)
 
 // ---- confidence maps: the probability of the predicted class next to every class map, conf[b, y, x] = max_c P[b, c, y, x] with P the probabilities of
 // EncoderDecoder.inference (F.softmax(seg_logit, dim=1), ED:449,460), written by the launch that writes the map.  The arithmetic is csrc/softmax_px.h:
@@ -306,49 +320,75 @@ __global__ __launch_bounds__(256) void slide_argmax_conf_lds_kernel(const float*
 #undef SLIDE_EXIT
 }
 
-extern "C" int mmsa_slide_argmax_conf(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out, float* conf,
-                                      int B, int H, int W, int hc, int wc, int* uncovered /* device int, zeroed by the caller */, hipStream_t stream) {
-  MMSA_CHECK_ARG(logits && out && conf && uncovered && C > 0 && C <= 255 && hs > 0 && ws > 0 && hc > 0 && wc > 0 && B > 0 && H <= 65535 && B <= 65535,
-                 "slide_argmax_conf: bad args");
+// the checks and the launch of mmsa_slide_argmax and mmsa_slide_argmax_conf; `conf` given: the LDS-column form where it fits, the second-pass form otherwise
+static int slide_argmax_launch(const char* name, const float* logits, int n, int C, int hs, int ws, const int* windows, unsigned char* out, float* conf, int B, int H,
+                               int W, int hc, int wc, int* uncovered, hipStream_t stream) {
+  MMSA_CHECK_ARG(logits && out && uncovered && C > 0 && C <= 255 && hs > 0 && ws > 0 && hc > 0 && wc > 0 && B > 0 && H <= 65535 && B <= 65535, "%s: bad args", name);
   WindowTable wt;
-  int rc = fill_windows(wt, windows, n, B, H, W, hc, wc, "slide_argmax_conf");
+  int rc = fill_windows(wt, windows, n, B, H, W, hc, wc, name);
   if (rc) return rc;
 #ifdef MMSA_CONF_SECOND_PASS      // measurement build only (tools/exp/confidence_bench.py): the second-pass form for every C
   const bool lds = false;
 #else
   const bool lds = C <= SLIDE_CONF_LDS_CLASSES;
 #endif
-  if (lds)
-    hipLaunchKernelGGL(slide_argmax_conf_lds_kernel, dim3(cdiv(W, 256), H, B), dim3(256), (size_t)C * 256 * sizeof(float), stream, logits, C, hs, ws, out, conf,
-                       H, W, hc, wc, (float)hs / (float)hc, (float)ws / (float)wc, wt, uncovered);
-  else
-    hipLaunchKernelGGL(slide_argmax_conf_kernel, dim3(cdiv(W, 256), H, B), dim3(256), 0, stream, logits, C, hs, ws, out, conf, H, W, hc, wc,
-                       (float)hs / (float)hc, (float)ws / (float)wc, wt, uncovered);
-  MMSA_CHECK_LAUNCH("slide_argmax_conf");
+  const dim3 grid(cdiv(W, 256), H, B);
+  const float rh = (float)hs / (float)hc, rw = (float)ws / (float)wc;
+  if (!conf) hipLaunchKernelGGL(slide_argmax_kernel, grid, dim3(256), 0, stream, logits, C, hs, ws, out, H, W, hc, wc, rh, rw, wt, uncovered);
+  else if (lds)
+    hipLaunchKernelGGL(slide_argmax_conf_lds_kernel, grid, dim3(256), (size_t)C * 256 * sizeof(float), stream, logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, wt,
+                       uncovered);
+  else hipLaunchKernelGGL(slide_argmax_conf_kernel, grid, dim3(256), 0, stream, logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, wt, uncovered);
+  MMSA_CHECK_LAUNCH(name);
   return MMSA_OK;
+}
+
+extern "C" int mmsa_slide_argmax(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out,
+                                 int B, int H, int W, int hc, int wc, int* uncovered /* device int, zeroed by the caller */, hipStream_t stream) {
+  return slide_argmax_launch("slide_argmax", logits, n, C, hs, ws, windows, out, nullptr, B, H, W, hc, wc, uncovered, stream);
+}
+
+extern "C" int mmsa_slide_argmax_conf(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out, float* conf,
+                                      int B, int H, int W, int hc, int wc, int* uncovered /* device int, zeroed by the caller */, hipStream_t stream) {
+  MMSA_CHECK_ARG(conf, "slide_argmax_conf: bad args");
+  return slide_argmax_launch("slide_argmax_conf", logits, n, C, hs, ws, windows, out, conf, B, H, W, hc, wc, uncovered, stream);
 }
 
 // slide_argmax_resized_kernel + the confidence map at the rescaled / cut size: conf = max_c softmax(resized)[c] (ED:449,460), slot form and scanning form.
 __global__ __launch_bounds__(256) void slide_argmax_resized_conf_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
                                                                         float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, int Hcut,
                                                                         int Wcut, float rh2, float rw2, WindowTable wt, int* __restrict__ uncovered) {
-#define RESIZED_CONF 1
-#include "slide_resized_pixel.inc"
-#undef RESIZED_CONF
+  slide_resized_pixel<true>(logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, Hcut, Wcut, rh2, rw2, wt, uncovered);
+}
+
+// the checks and the launch of mmsa_slide_argmax_resized and mmsa_slide_argmax_resized_conf; `conf` given: slide_argmax_resized_conf_kernel
+static int slide_argmax_resized_launch(const char* name, const float* logits, int n, int C, int hs, int ws, const int* windows, unsigned char* out, float* conf, int B,
+                                       int H, int W, int hc, int wc, int Hd, int Wd, int Hcut, int Wcut, int* uncovered, hipStream_t stream) {
+  MMSA_CHECK_ARG(logits && out && uncovered && C > 0 && C <= 255 && hs > 0 && ws > 0 && hc > 0 && wc > 0 && B > 0 && H > 0 && W > 0 && B <= 65535, "%s: bad args", name);
+  MMSA_CHECK_ARG(Hd > 0 && Wd > 0 && Hcut > 0 && Wcut > 0 && Hcut <= Hd && Wcut <= Wd && Hcut <= 65535,
+                 "%s: the cut %dx%d must lie inside the target %dx%d (and have at most 65535 rows)", name, Hcut, Wcut, Hd, Wd);
+  WindowTable wt;
+  int rc = fill_windows(wt, windows, n, B, H, W, hc, wc, name);
+  if (rc) return rc;
+  const dim3 grid(cdiv(Wcut, 256), Hcut, B);
+  const float rh = (float)hs / (float)hc, rw = (float)ws / (float)wc, rh2 = (float)H / (float)Hd, rw2 = (float)W / (float)Wd;
+  if (conf)
+    hipLaunchKernelGGL(slide_argmax_resized_conf_kernel, grid, dim3(256), 0, stream, logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, Hcut, Wcut, rh2, rw2, wt,
+                       uncovered);
+  else hipLaunchKernelGGL(slide_argmax_resized_kernel, grid, dim3(256), 0, stream, logits, C, hs, ws, out, H, W, hc, wc, rh, rw, Hcut, Wcut, rh2, rw2, wt, uncovered);
+  MMSA_CHECK_LAUNCH(name);
+  return MMSA_OK;
+}
+
+extern "C" int mmsa_slide_argmax_resized(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out,
+                                         int B, int H, int W, int hc, int wc, int Hd, int Wd, int Hcut, int Wcut,
+                                         int* uncovered /* device int, zeroed by the caller */, hipStream_t stream) {
+  return slide_argmax_resized_launch("slide_argmax_resized", logits, n, C, hs, ws, windows, out, nullptr, B, H, W, hc, wc, Hd, Wd, Hcut, Wcut, uncovered, stream);
 }
 
 extern "C" int mmsa_slide_argmax_resized_conf(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out,
                                               float* conf, int B, int H, int W, int hc, int wc, int Hd, int Wd, int Hcut, int Wcut,
                                               int* uncovered /* device int, zeroed by the caller */, hipStream_t stream) {
-  MMSA_CHECK_ARG(logits && out && conf && uncovered && C > 0 && C <= 255 && hs > 0 && ws > 0 && hc > 0 && wc > 0 && B > 0 && H > 0 && W > 0 && B <= 65535,
-                 "slide_argmax_resized_conf: bad args");
-  MMSA_CHECK_ARG(Hd > 0 && Wd > 0 && Hcut > 0 && Wcut > 0 && Hcut <= Hd && Wcut <= Wd && Hcut <= 65535,
-                 "slide_argmax_resized_conf: the cut %dx%d must lie inside the target %dx%d (and have at most 65535 rows)", Hcut, Wcut, Hd, Wd);
-  WindowTable wt;
-  int rc = fill_windows(wt, windows, n, B, H, W, hc, wc, "slide_argmax_resized_conf");
-  if (rc) return rc;
-  hipLaunchKernelGGL(slide_argmax_resized_conf_kernel, dim3(cdiv(Wcut, 256), Hcut, B), dim3(256), 0, stream, logits, C, hs, ws, out, conf, H, W, hc, wc,
-                     (float)hs / (float)hc, (float)ws / (float)wc, Hcut, Wcut, (float)H / (float)Hd, (float)W / (float)Wd, wt, uncovered);
-  MMSA_CHECK_LAUNCH("slide_argmax_resized_conf");
-  return MMSA_OK;
+  MMSA_CHECK_ARG(conf, "slide_argmax_resized_conf: bad args");
+  return slide_argmax_resized_launch("slide_argmax_resized_conf", logits, n, C, hs, ws, windows, out, conf, B, H, W, hc, wc, Hd, Wd, Hcut, Wcut, uncovered, stream);
 }

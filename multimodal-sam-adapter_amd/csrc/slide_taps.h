@@ -1,6 +1,7 @@
 // The tap arithmetic of the rescaled class map, shared by csrc/segment.hip (mmsa_slide_argmax_resized) and csrc/augment.hip (mmsa_aug_argmax): which windows
-// cover a canvas pixel, one window's interpolated term, and a canvas pixel's averaged value in window order.  The functions are templates on the window
-// table, which says where a window's (image, y0, x0) comes from:
+// cover a canvas pixel, one window's interpolated term, a canvas pixel's averaged value in window order, and the two-stage pixel built of four such canvas
+// pixels (TwoStagePixel: its set-up and its value for one class -- the ONE copy of that text; the kernels of both files only loop over the classes).  The
+// functions are templates on the window table, which says where a window's (image, y0, x0) comes from:
 //   WindowTable : by value in the launch arguments (at most MMSA_MAX_WINDOWS windows; segment.hip);
 //   DevWindows  : a device int [n, 3] array (augment.hip: the tables of all views of an augmented frame do not fit the argument block).
 // Include it AFTER `#pragma clang fp contract(off)`: both files must round these formulas the same way (see the top of segment.hip).
@@ -18,6 +19,15 @@ __device__ __forceinline__ int win_n(const DevWindows& wt) { return wt.n; }
 __device__ __forceinline__ int win_b(const DevWindows& wt, int k) { return wt.t[3 * k]; }
 __device__ __forceinline__ int win_y0(const DevWindows& wt, int k) { return wt.t[3 * k + 1]; }
 __device__ __forceinline__ int win_x0(const DevWindows& wt, int k) { return wt.t[3 * k + 2]; }
+
+// host: window k (image wb, y0, x0; hc x wc) lies inside the [B, H, W] input, or the call fails in `name`'s name (view >= 0: a view of an augmented frame)
+static inline int check_window(const char* name, int view, int k, int wb, int y0, int x0, int hc, int wc, int B, int H, int W) {
+  if (wb >= 0 && wb < B && y0 >= 0 && x0 >= 0 && y0 + hc <= H && x0 + wc <= W) return MMSA_OK;
+  char of_view[24] = "";
+  if (view >= 0) snprintf(of_view, sizeof of_view, "view %d ", view);
+  mmsa_set_error("%s: %swindow %d (image %d, y0 %d, x0 %d, %dx%d) outside the [%d, %d, %d] input", name, of_view, k, wb, y0, x0, hc, wc, B, H, W);
+  return MMSA_ERR_ARG;
+}
 
 // Registers: four taps with the eight slots of slide_pixel.inc would need 4 x 56 (the first form did: 372 registers, one wave per SIMD).  Here a tap
 // keeps RESIZED_SLOTS = 4 windows, each packed to four registers (offset of the top-left logit, window index | "has a row below" << 8 | "has a column
@@ -77,4 +87,63 @@ __device__ __forceinline__ float tap_value_scan(const WT& wt, int b, int ty, int
     first = false;
   }
   return acc / (float)nk;
+}
+
+// ---- the two-stage pixel: output pixel (Y, X) of the second bilinear resize (align_corners=False) of the averaged H x W canvas.  Each of its four taps
+// (tap t: row y0 / y1 = t >> 1, column x0 / x1 = t & 1) is a canvas pixel with its own covering windows and its own count.
+struct TwoStagePixel { TapSlots tp[4]; int y0, y1, x0, x1; float lh2, lw2; int nmin, nmax; };
+
+// nmin == 0: a tap without a window; nmax > 8: a tap under more than 8 -- the callers refuse both.  nmax <= RESIZED_SLOTS: the slots hold every window.
+template <class WT>
+__device__ __forceinline__ void two_stage_setup(TwoStagePixel& px, const WT& wt, int b, int Y, int X, int H, int W, int hc, int wc, int hs, int ws,
+                                                float rh, float rw, float rh2, float rw2) {
+  // second stage: the taps of output pixel (Y, X) in the H x W canvas (bilinear_accum_kernel with src = the canvas)
+  float sh2 = ((float)Y + 0.5f) * rh2 - 0.5f, sw2 = ((float)X + 0.5f) * rw2 - 0.5f;
+  sh2 = sh2 < 0.f ? 0.f : sh2;
+  sw2 = sw2 < 0.f ? 0.f : sw2;
+  const int y0 = min((int)sh2, H - 1), x0 = min((int)sw2, W - 1);
+  const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
+  px.y0 = y0; px.y1 = y1; px.x0 = x0; px.x1 = x1;
+  px.lh2 = sh2 - (float)y0; px.lw2 = sw2 - (float)x0;
+  // first stage: the covering windows of each tap.  Slot arrays only ever indexed by unrolled constants.
+  TapSlots (&tp)[4] = px.tp;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    tp[t].nk = 0;
+#pragma unroll
+    for (int q = 0; q < RESIZED_SLOTS; ++q) { tp[t].o[q] = tp[t].kf[q] = 0; tp[t].lh[q] = tp[t].lw[q] = 0.f; }
+  }
+  for (int k = 0; k < win_n(wt); ++k) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      int o, kf;
+      float lh, lw;
+      if (!tap_coords(wt, k, b, t >> 1 ? y1 : y0, t & 1 ? x1 : x0, hc, wc, hs, ws, rh, rw, o, kf, lh, lw)) continue;
+#pragma unroll
+      for (int q = 0; q < RESIZED_SLOTS; ++q)
+        if (q == tp[t].nk) { tp[t].o[q] = o; tp[t].kf[q] = kf; tp[t].lh[q] = lh; tp[t].lw[q] = lw; }
+      ++tp[t].nk;
+    }
+  }
+  px.nmin = min(min(tp[0].nk, tp[1].nk), min(tp[2].nk, tp[3].nk));
+  px.nmax = max(max(tp[0].nk, tp[1].nk), max(tp[2].nk, tp[3].nk));
+}
+
+// The pixel's value for class c.  SCAN false: from the slots (tap_value; needs nmax <= RESIZED_SLOTS); true: the scanning form (tap_value_scan).  The caller
+// makes that choice once, outside its loop over c.
+template <bool SCAN, class WT>
+__device__ __forceinline__ float two_stage_value(const TwoStagePixel& px, const WT& wt, int b, const float* __restrict__ logits, int C, int c, int hs, int ws,
+                                                 int hc, int wc, float rh, float rw) {
+  float p00, p01, p10, p11;
+  if constexpr (SCAN) {
+    p00 = tap_value_scan(wt, b, px.y0, px.x0, px.tp[0].nk, logits, C, c, hs, ws, hc, wc, rh, rw);
+    p01 = tap_value_scan(wt, b, px.y0, px.x1, px.tp[1].nk, logits, C, c, hs, ws, hc, wc, rh, rw);
+    p10 = tap_value_scan(wt, b, px.y1, px.x0, px.tp[2].nk, logits, C, c, hs, ws, hc, wc, rh, rw);
+    p11 = tap_value_scan(wt, b, px.y1, px.x1, px.tp[3].nk, logits, C, c, hs, ws, hc, wc, rh, rw);
+  } else {
+    p00 = tap_value(px.tp[0], logits, C, c, hs, ws); p01 = tap_value(px.tp[1], logits, C, c, hs, ws);
+    p10 = tap_value(px.tp[2], logits, C, c, hs, ws); p11 = tap_value(px.tp[3], logits, C, c, hs, ws);
+  }
+  const float lh2 = px.lh2, lw2 = px.lw2;
+  return (1.f - lh2) * ((1.f - lw2) * p00 + lw2 * p01) + lh2 * ((1.f - lw2) * p10 + lw2 * p11);
 }

@@ -644,6 +644,27 @@ def test_gemm_kernels_do_not_spill_into_their_k_loops():
         assert v["scratch"] == 0, f"{k}: {v['scratch']} scratch instructions"
 
 
+def test_class_map_kernels_keep_their_registers_and_do_not_spill():
+    """The class-map kernels of segment.hip and augment.hip hold their tap slots in registers; the two-stage ones sit at or next to the 256-register limit,
+    where one more register is a spill.  Every kernel of both files has no scratch, and the class-map kernels stay at or below the registers they took
+    when the two-stage pixel was written out per kernel (profiles/class_map_pixel_isa.txt)."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("isa_scratch", os.path.join(ROOT, "tools", "isa_scratch.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    res = {}
+    for f in ("segment.hip", "augment.hip"):
+        res.update(mod.census(os.path.join(ROOT, "multimodal-sam-adapter_amd", "csrc", f)))
+    for k, v in res.items():
+        assert v["scratch_bytes"] == 0, f"{k}: {v['scratch_bytes']} scratch bytes"
+    bounds = dict(slide_argmax=158, slide_argmax_eval=160, slide_argmax_conf=160, slide_argmax_conf_lds=160, slide_argmax_resized=216,
+                  slide_argmax_resized_conf=256, aug_argmax=226, aug_argmax_conf=228)
+    for base, bound in bounds.items():
+        hit = [k for k in res if re.match(r"_Z\d+%s_kernel[A-Z0-9]" % base, k)]
+        assert len(hit) == 1, (base, hit)
+        assert res[hit[0]]["vgprs"] <= bound, f"{base}_kernel: {res[hit[0]]['vgprs']} VGPRs, bound {bound}"
+
+
 def test_kernel_gelu_coefficients_hold_their_error_bound():
     """csrc/common.h evaluates GELU as x/2 + |x/2| (1 - exp2(P(min(|x|, 6)))) with a fitted P (tools/gelu_fit.py).  The coefficients compiled into the kernels,
     evaluated in fp32 in the kernels' operation order, stay within 4e-7 of the erf-form GELU (nn.GELU's default, the reference's activation: IE:154-167, TC:107-111)
