@@ -186,6 +186,7 @@ __global__ __launch_bounds__(256) void dwconv7_tiled_kernel(const float* __restr
 #define DW7B_LDS ((22 * DW7B_PITCH * 32 + 50 * 32) * 4)
 // Persistent: gridDim.x workgroups (two per CU: what LDS admits) walk the nt tiles; the NEXT tile's halo and weights are requested into registers before
 // the current tile's arithmetic -- which touches LDS only, so nothing in it waits on the vector-memory counter -- and written to LDS after it.
+// The tile loop's second and third trip are held to float64 and to the bits of one-tile launches by tests/test_persistent_walks_gpu.py (test_dwconv7_block_walk).
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void dwconv7_blk_kernel(const float* __restrict__ x, long ldx, long xstrideB,
                                                           const float* __restrict__ w, const float* __restrict__ bias,
                                                           float* __restrict__ y, long ldy, long ystrideB,

@@ -76,6 +76,7 @@ extern "C" int mmsa_debug_wattn_stamps(long long* p) { g_wattn_stamps = p; retur
 //   #1  K(i) landed for everyone, everyone is past PV(i-1)     -> V(i) DMA issued;   T / bias operand / S(i)
 //   #2  everyone has its scores (K image free)                 -> K(i+1) DMA issued;   softmax statistics
 //   #3  V(i) landed for everyone (counted vmcnt: K(i+1) stays in flight)             PV(i), store, Q(i+1) loads
+// The item loop's second and third trip are held to float64 and to the bits of one-item launches by tests/test_persistent_walks_gpu.py (test_window_attention_*).
 #define WP_NKV 208
 #define WP_V_BYTES (WP_NKV * 128)
 #define WP_R_BYTES (2 * 64 * 128)        // rel-pos table image: [ks][64 rows] of 128 B (GEMM LDS image)
