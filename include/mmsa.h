@@ -461,6 +461,27 @@ int mmsa_eval_calibration(const unsigned char* pred, const float* conf, const un
                           const unsigned char* lut, int C, const int* ymap, const int* xmap, const int* slots, int n_slots, int bins, int64_t* cal,
                           mmsa_stream_t stream);
 
+/* --- selective evaluation: one confusion matrix per confidence bin, and the thresholded map those counts describe.  The project's own definitions (the
+ *     reference has no such step), each reused verbatim from the two entries above so that the three reductions agree exactly:
+ *       label side (mmsa_eval_confusion_u8): l = lut[label byte]; a pixel with l == 255 is ignored and counted nowhere; otherwise row = min(l, C) and
+ *         col = min(pred, C); with ymap / xmap (both or neither) the label is read at [ymap[y], xmap[x]], clamped into the label map;
+ *       confidence side (mmsa_eval_calibration): c = conf with NaN, negative values and -0.0 -> 0.0f, values above 1 and +inf -> 1.0f;
+ *         bin k = min(bins - 1, (int)(c * (float)bins)): ONE float32 product, truncated, no contraction;
+ *       counts[slot][k][row][col] += 1 for every pixel that is not ignored: int64 [n_slots, bins, C + 1, C + 1].  Row C (kept labels outside [0, C)) is
+ *         counted, as in mmsa_eval_confusion_u8; mmsa_eval_calibration drops those pixels.
+ *     What follows: (1) the sum over k is mmsa_eval_confusion_u8's [C + 1, C + 1] matrix of the same map; (2) the rows < C of bin k sum to
+ *     mmsa_eval_calibration's total[k], and the trace of its [:C, :C] block is correct[k]; (3) the plain confusion counts of the map mmsa_abstain_u8 writes at
+ *     min_bin = k0 are counts[k0:].sum(0) with the row sums of counts[:k0] added into column C.
+ *     The call ADDS into counts (the caller zeroes it): integer sums, the same bytes whatever the order of arrival.  pred and label may sit at any byte
+ *     address, conf at any 4-byte aligned one.  2 <= C <= 126 (a workgroup keeps (C + 1)^2 uint32 cells per resident bin in 64 KiB of LDS; where not all
+ *     bins fit, groups of bins each make a pass over the pixels within the one launch), 1 <= bins <= 64, 1 <= B <= 64; slots: HOST int [B].
+ *   abstain_u8: out[i] = pred[i] where bin(conf[i]) >= min_bin, 255 elsewhere, i < n, with the SAME clamp and bin; 0 <= min_bin <= bins (min_bin == bins
+ *     abstains everywhere, 0 copies); out may be pred itself (any other overlap is an error of the caller); 1 <= n < 2^40. --- */
+int mmsa_eval_selective(const unsigned char* pred, const float* conf, const unsigned char* label, int B, int H, int W, int Hl, int Wl,
+                        const unsigned char* lut, int C, const int* ymap, const int* xmap, const int* slots, int n_slots, int bins, int64_t* counts,
+                        mmsa_stream_t stream);
+int mmsa_abstain_u8(const unsigned char* pred, const float* conf, long n, int bins, int min_bin, unsigned char* out, mmsa_stream_t stream);
+
 /* --- the picture of a prediction (segmentation/mmseg_custom/apis/test_bs.py:257-349, the `--show` / `--show-dir` output): `tensor2imgs` (test_bs.py:18-63) on
  *     planes 0..2 of the input tensor -> the crop `img[:h, :w]` (test_bs.py:275-276) -> `show_result` (tools/color_gt_according_palette.py:23-81:
  *     color_seg[seg == label] = color, channels reversed, img * (1 - opacity) + color_seg * opacity, .astype(uint8)), in one pass.

@@ -18,6 +18,7 @@
 // maps where the confusion pass takes 14.1, the lane merge 23.8, and two workgroups per CU -- CAL_CHUNK below -- 16.2.)
 // Integer sums only, in LDS and in the int64 result: the same bytes whatever the order of arrival.
 #include "common.h"
+#include "conf_bin.h"
 #include "eval_hist.h"
 
 // Pixels per workgroup.  Timed at 2048 / 4096 / 8192 (profiles/calibration.txt; -DCAL_CHUNK with tools/build_variant.sh): at 8192 (EVAL_CHUNK) a CU
@@ -45,10 +46,10 @@ struct CalArgs {
 __device__ __forceinline__ int cal_pixel(const unsigned char* lut_s, unsigned label_byte, unsigned pred_byte, float c, int C, int K, float Kf, bool& ok,
                                          unsigned& q) {
   const int l = lut_s[label_byte & 255u];
-  c = c > 0.0f ? (c > 1.0f ? 1.0f : c) : 0.0f;                       // NaN, negatives and -0.0 -> 0; above 1 (and +inf) -> 1
+  c = conf_clamp(c);                                                 // NaN, negatives and -0.0 -> 0; above 1 (and +inf) -> 1
   ok = (int)pred_byte == l;
   q = (unsigned)(c * 16777216.0f);                                   // exact scaling, truncated: 0 .. 2^24
-  const int k = min(K - 1, (int)(c * Kf));                           // ONE float32 product, truncated
+  const int k = conf_bin(c, K, Kf);                                  // ONE float32 product, truncated (csrc/conf_bin.h)
   return l < C ? k : CAL_NONE;
 }
 

@@ -15,6 +15,7 @@ from .preprocess import FrameFeeder, Preprocess
 from . import evaluate  # noqa: F401  (confusion counts and mIoU on device: LabelPrep, confusion, Evaluator)
 from .evaluate import Evaluator, LabelPrep, confusion
 from .evaluate import Calibration, calibration  # noqa: F401  (reliability bins, ECE and risk-coverage of the confidence map on device)
+from .evaluate import SelectiveEvaluator, selective, abstain  # noqa: F401  (confusion counts per confidence bin: mIoU against coverage; the thresholded map)
 from . import render  # noqa: F401  (the picture of a prediction on device: palette map over the frame, show_result)
 from .render import Renderer
 from .registry import BACKBONES, HEADS, build_backbone, build_head
@@ -39,5 +40,5 @@ if not _HAVE_MMSEG:     # local registry (no mmseg in the process): nothing to o
 
 __all__ = ["SegformerHead", "HEADS", "build_head", "register_head", "SAMAdapterbimodalMixModNewInTwinConvNEW", "SAMAdapterbimodalMixModNewInTwinConvNEWwithcp",
            "BACKBONES", "build_backbone", "ops", "lib", "inference", "Chains", "Replay", "AttentionRangeError", "OperandRangeError",
-           "preprocess", "Preprocess", "FrameFeeder", "evaluate", "Evaluator", "LabelPrep", "confusion", "Calibration", "calibration", "render", "Renderer",
+           "preprocess", "Preprocess", "FrameFeeder", "evaluate", "Evaluator", "LabelPrep", "confusion", "Calibration", "calibration", "SelectiveEvaluator", "selective", "abstain", "render", "Renderer",
            "probabilities", "aug_inference", "aug_class_map", "AugPlan", "argmax_max_map"]

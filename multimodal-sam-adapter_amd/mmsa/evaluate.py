@@ -14,8 +14,16 @@ class and case; the int64 counts here are exact at any size, and the metrics are
 Calibration of the confidence map (the probability of the predicted class, `confidence=` of the class-map calls) is the second half: `calibration` /
 `Calibration` reduce (class map, confidence map, label map) to int64 [3, K] reliability bins per slot -- total, correct, and the confidence sum in 24-bit
 fixed point (mmsa_eval_calibration, csrc/calibrate.hip) -- from which `reliability_of`, `ece_of`, `mce_of` and `risk_coverage_of` form the reliability
-diagram, the expected / maximum calibration error and accuracy against coverage in float64 on the host.  The reference has no such step."""
+diagram, the expected / maximum calibration error and accuracy against coverage in float64 on the host.  The reference has no such step.
+
+Selective evaluation joins the two: `selective` / `SelectiveEvaluator` keep ONE confusion matrix PER CONFIDENCE BIN, int64 [K, C + 1, C + 1] per slot
+(mmsa_eval_selective, csrc/selective.hip), with the label side of the confusion counts and the confidence side of the reliability bins, both verbatim:
+their sum over the bins is the Evaluator's matrix, the rows < C of bin k give Calibration's total[k] / correct[k], and the suffix sums over the bins are
+the confusion counts of the map with the pixels below a confidence threshold taken out.  `selective_metrics_of` forms the reference's metrics at every
+such threshold in float64 -- mIoU against coverage -- and `abstain` (mmsa_abstain_u8) writes the thresholded map (255 where the bin is below) that
+those counts describe, from the same clamp and bin.  The reference has no such step either."""
 import ctypes
+import warnings
 from collections import OrderedDict
 
 import numpy as np
@@ -36,6 +44,9 @@ MAX_BINS = 64           # confidence bins per launch (csrc/calibrate.hip CAL_MAX
 DEFAULT_BINS = 15       # the usual reliability diagram
 CONF_ONE = 1 << 24      # the fixed-point unit of a bin's confidence sum: conf_sum = sum of floor(conf * 2^24)
 BIN_CAPACITY = 1 << 39  # participating pixels per bin and slot before the int64 confidence sum can overflow (2^39 * 2^24 = 2^63)
+
+MAX_SELECTIVE_CLASSES = 126        # csrc/eval_hist.h MMSA_EVAL_MAX_CLASSES: one bin's (C + 1)^2 uint32 cells must fit a workgroup's 64 KiB of LDS
+MAX_SELECTIVE_BYTES = 1 << 30      # the largest count buffer a SelectiveEvaluator allocates (64 slots x 64 bins x 127^2 cells x 8 bytes is 528 MB)
 
 
 # ---- host-side restatements (numpy) ----
@@ -183,6 +194,125 @@ def calibration_summary_of(bins):
     """ECE, MCE, aAcc and the mean confidence in PERCENT, rounded to two places as `summary_of` rounds (np.round(v * 100, 2)); NaN when N == 0."""
     vals = (("ECE", ece_of(bins)), ("MCE", mce_of(bins)), ("aAcc", accuracy_of(bins)), ("mConf", mean_confidence_of(bins)))
     return OrderedDict((k, np.round(v * 100, 2)) for k, v in vals)
+
+
+# ---- selective evaluation from the per-bin confusion counts (numpy; integers, then float64) ----
+def _counts3(counts):
+    """int64 [K, C + 1, C + 1] of one slot, checked; OverflowError where a cell is negative (an int64 count that has wrapped)."""
+    c = np.asarray(counts)
+    if c.ndim != 3 or c.shape[0] < 1 or c.shape[1] != c.shape[2] or c.shape[1] < 3 or c.dtype.kind not in "iu":
+        raise ValueError(f"mmsa.evaluate: selective counts are an integer [K, C + 1, C + 1] array, got {c.dtype} {c.shape}")
+    if c.dtype.kind == "u" and c.size and int(c.max()) > np.iinfo(np.int64).max:
+        raise OverflowError(f"mmsa.evaluate: a selective count of {int(c.max())} does not fit int64")
+    c = c.astype(np.int64, copy=False)
+    if c.size and int(c.min()) < 0:
+        raise OverflowError("mmsa.evaluate: a selective count is negative: an int64 cell has wrapped (read and reset() the SelectiveEvaluator more often)")
+    return c
+
+
+def _sum_bins(c):
+    """c.sum(0) of checked counts [k, C + 1, C + 1] in int64.  Where the float64 estimate of the largest sum comes near 2^63 the cells are summed as
+    Python integers instead, and OverflowError is raised if one of them has passed it."""
+    if c.shape[0] == 0 or float(c.astype(np.float64).sum(0).max()) < 2.0 ** 62:
+        return c.sum(0)
+    s = c.astype(object).sum(0)
+    if int(s.max()) > np.iinfo(np.int64).max:
+        raise OverflowError(f"mmsa.evaluate: the selective counts of one cell sum to {int(s.max())} over the bins, which int64 cannot hold")
+    return s.astype(np.int64)
+
+
+def _suffix_sums(c):
+    """S[k] = c[k:].sum(0) of checked counts, int64 [K, C + 1, C + 1]; no cell of an S[k] exceeds S[0]'s, which _sum_bins checks."""
+    _sum_bins(c)
+    return np.cumsum(c[::-1], axis=0)[::-1].copy()
+
+
+def selective_counts_of(counts, min_bin=0):
+    """The confusion counts of the pixels kept at `min_bin`: counts[min_bin:].sum(0), int64 [C + 1, C + 1]; min_bin == K keeps nothing.  (The map
+    `abstain` writes at min_bin has these counts with the row sums of counts[:min_bin] added into column C: its abstained pixels predict 255.)"""
+    c = _counts3(counts)
+    K = c.shape[0]
+    if isinstance(min_bin, bool) or not isinstance(min_bin, (int, np.integer)) or not 0 <= int(min_bin) <= K:
+        raise ValueError(f"mmsa.evaluate: min_bin = {min_bin!r}; 0..{K} for {K} bins")
+    return _sum_bins(c[int(min_bin):])
+
+
+def selective_areas_of(counts):
+    """(area_intersect, area_union, area_pred_label, area_label) per threshold, int64 [K, C] each: entry k keeps the bins k .. K - 1 (`areas_of` on the
+    suffix sums)."""
+    return areas_of(_suffix_sums(_counts3(counts)))
+
+
+def selective_metrics_of(counts, metric=("mIoU",), nan_to_num=None, beta=1):
+    """The reference's metrics against coverage from int64 [K, C + 1, C + 1] counts -> OrderedDict: 'coverage' float64 [K] (entry k keeps the bins
+    k .. K - 1; kept / all pixels whose label row is < C: numerator and denominator of `risk_coverage_of`), `area_metrics`' entries stacked per
+    threshold ('aAcc' [K], 'IoU' / 'Acc' / ... [K, C]) and their np.nanmean per threshold ('mIoU', 'mAcc', ... [K]).  Entry 0 is
+    area_metrics(*areas_of(counts.sum(0))); a threshold that keeps nothing gives NaN.  'aAcc' at threshold k is sum(intersect) / sum(area_label[:C])
+    over the kept pixels -- `risk_coverage_of`'s selective accuracy, since kept pixels of the label rows < C are exactly Calibration's `total`."""
+    c = _counts3(counts)
+    C = c.shape[1] - 1
+    S = _suffix_sums(c)
+    kept = S[:, :C, :].sum((1, 2))
+    areas = areas_of(S)
+    per = [area_metrics(*(a[k] for a in areas), metric=metric, nan_to_num=nan_to_num, beta=beta) for k in range(S.shape[0])]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out = OrderedDict(coverage=kept.astype(np.float64) / np.float64(kept[0]))
+    for key in per[0]:
+        out[key] = np.stack([np.asarray(m[key], dtype=np.float64) for m in per])
+    for key in list(per[0]):
+        if key != "aAcc":
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore", RuntimeWarning)                   # "Mean of empty slice": a threshold where every class is NaN gives NaN
+                out["m" + key] = np.nanmean(out[key], axis=1)
+    return out
+
+
+def reliability_counts_of(counts):
+    """Calibration's first two rows from the per-bin confusion counts: int64 [..., 2, K] (total, correct) of [..., K, C + 1, C + 1] counts -- total[k] = the
+    sum of the rows < C of bin k, correct[k] = the trace of its [:C, :C] block."""
+    c = np.asarray(counts)
+    if c.ndim < 3 or c.shape[-1] != c.shape[-2] or c.shape[-1] < 3 or c.dtype.kind not in "iu":
+        raise ValueError(f"mmsa.evaluate: selective counts are an integer [..., K, C + 1, C + 1] array, got {c.dtype} {c.shape}")
+    c = c.astype(np.int64, copy=False)
+    C = c.shape[-1] - 1
+    return np.stack([c[..., :C, :].sum((-2, -1)), np.trace(c[..., :C, :C], axis1=-2, axis2=-1)], axis=-2)
+
+
+def bin_of(conf, bins):
+    """The bin of confidences as the device forms it (csrc/conf_bin.h): clamp (NaN, negatives, -0.0 -> 0; above 1 -> 1), ONE float32 product, truncated,
+    capped at bins - 1 -> int64 array."""
+    c = np.asarray(conf, dtype=np.float32)
+    with np.errstate(invalid="ignore"):
+        c = np.where(c > 0, np.minimum(c, np.float32(1)), np.float32(0)).astype(np.float32)
+    return np.minimum(int(bins) - 1, (c * np.float32(bins)).astype(np.int64))
+
+
+def bin_edge(j, bins):
+    """The lower edge of bin j as the device sees it: the smallest float32 confidence whose bin is >= j (j / bins, or its float32 neighbour where the
+    product rounds); 0 <= j <= bins - 1."""
+    e = np.float32(j / bins)
+    while e > 0 and bin_of(np.nextafter(e, np.float32(0)), bins) >= j:
+        e = np.nextafter(e, np.float32(0))
+    while bin_of(e, bins) < j:
+        e = np.nextafter(e, np.float32(1))
+    return e
+
+
+def threshold_bin(threshold, bins):
+    """`threshold=` of `abstain` -> min_bin.  The threshold (rounded to float32) goes through the SAME float32 product as a confidence, and must be a bin
+    edge: the smallest float32 of its bin, so that 'bin >= min_bin' and 'confidence >= threshold' are the same pixels and the map agrees with the
+    per-bin counts.  Anything else raises ValueError naming the nearest edges."""
+    K = _check_bins(bins)
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)) or not 0 <= float(threshold) <= 1:
+        raise ValueError(f"mmsa.evaluate: threshold = {threshold!r}; a confidence in [0, 1] is expected")
+    t = np.float32(threshold)
+    j = int(bin_of(t, K))
+    if t != bin_edge(j, K):
+        lo, hi = float(bin_edge(j, K)), (float(bin_edge(j + 1, K)) if j + 1 < K else None)
+        nxt = f"{hi!r} (min_bin {j + 1})" if hi is not None else f"min_bin={K} (abstain everywhere)"
+        raise ValueError(f"mmsa.evaluate: threshold {float(threshold)!r} is not a bin edge of {K} bins: the map would keep a part of bin {j} that the per-bin "
+                         f"counts cannot split; the nearest edges are {lo!r} (min_bin {j}) and {nxt}")
+    return j
 
 
 # ---- the label side of a launch ----
@@ -389,6 +519,72 @@ def calibration(pred, conf, labels, prep, bins=None, cal=None, slots=None):
     return cal
 
 
+def _check_selective_classes(C):
+    if C > MAX_SELECTIVE_CLASSES:
+        raise RuntimeError(f"mmsa.evaluate: {C} classes; selective evaluation supports 2..{MAX_SELECTIVE_CLASSES} (one bin's (C + 1)^2 uint32 histogram must "
+                           "fit a workgroup's 64 KiB of LDS)")
+    return C
+
+
+def _check_selective_counts(counts, K, C, device):
+    if (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int64 or counts.dim() != 4 or tuple(counts.shape[1:]) != (K, C + 1, C + 1)
+            or counts.device != device or not counts.is_contiguous()):
+        raise RuntimeError(f"mmsa.evaluate: counts must be a contiguous int64 [n_slots, {K}, {C + 1}, {C + 1}] tensor on {device}")
+    return counts
+
+
+@torch.no_grad()
+def selective(pred, conf, labels, prep, bins=None, counts=None, slots=None):
+    """ADD one confusion matrix per confidence bin of the uint8 class maps pred [B, H, W] and their float32 confidence maps conf [B, H, W] against the raw
+    labels [B, Hl, Wl] into counts[slots[b]] (one launch, mmsa_eval_selective) -> counts, int64 [n_slots, K, C + 1, C + 1] on the device:
+    counts[s, k, row, col] += 1 for every pixel whose label is not ignored, row / col as in `confusion` (index C = outside [0, C)), k as in `calibration`
+    (min(K - 1, int(float32(c) * float32(K))) of the confidence clamped to [0, 1], NaN -> 0).  `bins` = K defaults to counts', or to 15; `slots` defaults
+    to 0 .. B - 1 (per-image counts); `counts` defaults to a zeroed buffer of max(slots) + 1 slots."""
+    pred = _check_pred(pred)
+    conf = _check_confmap(conf, pred)
+    B, H, W = (int(v) for v in pred.shape)
+    C = _check_selective_classes(prep.num_classes)
+    if bins is None:
+        bins = int(counts.shape[1]) if isinstance(counts, torch.Tensor) and counts.dim() == 4 else DEFAULT_BINS
+    K = _check_bins(bins)
+    with torch.cuda.device(pred.device):
+        largs = prep.launch_args(labels, B, H, W, pred.device)
+        if counts is None:
+            n_slots = B if slots is None else max(int(s) for s in slots) + 1
+            counts = torch.zeros(n_slots, K, C + 1, C + 1, dtype=torch.int64, device=pred.device)
+        _check_selective_counts(counts, K, C, pred.device)
+        tab = _slot_args(slots, B, counts.shape[0])
+        lib.call("mmsa_eval_selective", pred.data_ptr(), conf.data_ptr(), largs[0], B, H, W, largs[1], largs[2], largs[3], C, largs[4], largs[5], tab,
+                 counts.shape[0], K, counts.data_ptr(), ops._stream())
+    return counts
+
+
+@torch.no_grad()
+def abstain(pred, conf, bins, min_bin=None, out=None, threshold=None):
+    """The class map thresholded by confidence (one launch, mmsa_abstain_u8) -> uint8 [B, H, W]: pred where the confidence's bin (of `bins`, as in
+    `selective` / `calibration`) is >= `min_bin`, 255 elsewhere.  0 <= min_bin <= bins: 0 copies, `bins` abstains everywhere.  `threshold=` in place
+    of min_bin: a confidence in [0, 1] that is a bin edge (`threshold_bin`); any other is refused, since the per-bin counts cannot describe its map.
+    `out`: the uint8 tensor to write, pred's shape; it may be pred itself (in place); a new tensor by default."""
+    pred = _check_pred(pred)
+    conf = _check_confmap(conf, pred)
+    K = _check_bins(bins)
+    if (min_bin is None) == (threshold is None):
+        raise ValueError("mmsa.evaluate: abstain takes min_bin= or threshold=, one of them")
+    if threshold is not None:
+        min_bin = threshold_bin(threshold, K)
+    if isinstance(min_bin, bool) or not isinstance(min_bin, (int, np.integer)) or not 0 <= int(min_bin) <= K:
+        raise ValueError(f"mmsa.evaluate: min_bin = {min_bin!r}; 0..{K} for {K} bins ({K} abstains everywhere)")
+    with torch.cuda.device(pred.device):
+        if out is None:
+            out = torch.empty_like(pred)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != tuple(pred.shape) or out.device != pred.device
+              or not out.is_contiguous()):
+            raise RuntimeError(f"mmsa.evaluate: out must be a contiguous uint8 {tuple(pred.shape)} tensor on {pred.device}")
+        if pred.numel():
+            lib.call("mmsa_abstain_u8", pred.data_ptr(), conf.data_ptr(), pred.numel(), K, int(min_bin), out.data_ptr(), ops._stream())
+    return out
+
+
 @torch.no_grad()
 def slide_argmax_eval(lg, n, windows, out, B, H, W, hc, wc, unc, labels, prep, counts, slots=None):
     """mmsa_slide_argmax on the head-resolution logits lg [n, C, hs, ws] AND the counts of its class map in one launch; `out` = None writes no map."""
@@ -585,3 +781,97 @@ class Calibration(_SlotOwner):
     def summary(self, slot=None):
         """ECE / MCE / aAcc / mConf in percent, rounded to two places."""
         return calibration_summary_of(self._of(slot))
+
+
+class SelectiveEvaluator(_SlotOwner):
+    """Owns the per-bin confusion counts of a selective evaluation run, as Evaluator owns the confusion counts and Calibration the reliability bins: int64
+    [n_slots, K, C + 1, C + 1] on the device (`.counts`), `bins` = K confidence bins of width 1 / K.  `cases` / `images` / `device` and `slots=` of add():
+    as for Calibration.  Only host_counts() copies anything to the host (81 KB per slot at 25 classes and 15 bins); everything else is formed from those
+    integers: `min_bin=` keeps the bins min_bin .. K - 1 (the pixels `abstain` leaves in the map), and at min_bin=0 metrics / summary / areas are the
+    Evaluator's.  A buffer above 1 GiB is refused.  Across ranks: mmsa.dist.allreduce_counts(se.counts)."""
+    _who, _read, _one = "SelectiveEvaluator", "host_counts()", "a SelectiveEvaluator"
+
+    def __init__(self, prep, bins=DEFAULT_BINS, cases=None, images=MAX_IMAGES, device=None):
+        self.prep = prep
+        self.n_bins = _check_bins(bins)
+        C = _check_selective_classes(prep.num_classes)
+        self._init_slots(cases, images)
+        nbytes = self.n_slots * self.n_bins * (C + 1) * (C + 1) * 8
+        if nbytes > MAX_SELECTIVE_BYTES:
+            raise ValueError(f"mmsa.SelectiveEvaluator: {self.n_slots} slots x {self.n_bins} bins x {C + 1} x {C + 1} int64 counts are {nbytes} bytes, above "
+                             f"the {MAX_SELECTIVE_BYTES} (1 GiB) a count buffer may take: fewer slots (cases= or images=) or fewer bins")
+        self.counts = None
+        if device is not None:
+            self._buffer(torch.device(device))
+
+    def _buffer(self, device):
+        if self.counts is None:
+            if _capturing(device):
+                raise RuntimeError("mmsa.SelectiveEvaluator: the count buffer cannot be allocated during a graph capture: construct the SelectiveEvaluator "
+                                   "with device=")
+            C = self.prep.num_classes
+            self.counts = torch.zeros(self.n_slots, self.n_bins, C + 1, C + 1, dtype=torch.int64, device=device)
+        elif self.counts.device != device:
+            raise RuntimeError(f"mmsa.SelectiveEvaluator: the counts live on {self.counts.device}, this batch on {device}")
+        return self.counts
+
+    def add(self, pred, conf, labels, case=None, slots=None):
+        """Count a batch of stored class maps and their confidence maps (one launch; no host sync, no allocation once the buffer exists)."""
+        pred = _check_pred(pred)
+        conf = _check_confmap(conf, pred)
+        with torch.cuda.device(pred.device):
+            counts = self._buffer(pred.device)
+        selective(pred, conf, labels, self.prep, bins=self.n_bins, counts=counts, slots=self.slots_for(pred.shape[0], case, slots))
+        self._taken(pred.shape[0], case, slots)
+        return self
+
+    def reset(self):
+        if self.counts is not None:
+            self.counts.zero_()
+        self.used = 0
+
+    def host_counts(self):
+        """The counts on the host (the ONE device-to-host copy of a run): int64 numpy [n, K, C + 1, C + 1], n = images added so far / cases."""
+        C = self.prep.num_classes
+        if self.counts is None:
+            return np.zeros((0 if self.cases is None else self.n_slots, self.n_bins, C + 1, C + 1), dtype=np.int64)
+        c = self.counts.cpu().numpy()
+        return c[:self.used] if self.cases is None else c
+
+    def _of(self, slot):
+        """int64 [K, C + 1, C + 1] of one slot (index or case name), or of the sum over every slot."""
+        c = self.host_counts()
+        for one in c:
+            _counts3(one)
+        if slot is not None:
+            return c[self._slot_index(slot)]
+        return _sum_bins(c.reshape(c.shape[0], -1, c.shape[-1])).reshape(c.shape[1:])
+
+    def evaluator_counts(self):
+        """The sum over the bins: Evaluator.host_counts() of the same maps, int64 [n, C + 1, C + 1]."""
+        c = self.host_counts()
+        return np.stack([selective_counts_of(one, 0) for one in c]) if len(c) else c.sum(1)
+
+    def reliability_counts(self, slot=None):
+        """`reliability_counts_of`: Calibration.host_bins()[:, :2] of the same maps, int64 [n, 2, K] (total, correct) -- or [2, K] of one slot."""
+        c = self.host_counts()
+        return reliability_counts_of(c if slot is None else c[self._slot_index(slot)])
+
+    def areas(self, min_bin=0):
+        """(area_intersect, area_union, area_pred_label, area_label) of the pixels kept at `min_bin`: int64 numpy [n, C] each, row per image / case."""
+        c = self.host_counts()
+        C = self.prep.num_classes
+        kept = np.stack([selective_counts_of(one, min_bin) for one in c]) if len(c) else np.zeros((0, C + 1, C + 1), dtype=np.int64)
+        return areas_of(kept)
+
+    def metrics(self, min_bin=0, slot=None, metric=("mIoU",), nan_to_num=None, beta=1):
+        """`total_area_to_metrics` of the pixels kept at `min_bin`, over every slot or of one slot; at min_bin=0 Evaluator.metrics of the same maps."""
+        return area_metrics(*areas_of(selective_counts_of(self._of(slot), min_bin)), metric=metric, nan_to_num=nan_to_num, beta=beta)
+
+    def summary(self, min_bin=0, slot=None, metric=("mIoU",), nan_to_num=None, beta=1):
+        """aAcc / mIoU / mAcc / ... of the pixels kept at `min_bin`, as Evaluator.summary rounds them."""
+        return summary_of(self.metrics(min_bin, slot, metric, nan_to_num, beta))
+
+    def coverage_curve(self, metric=("mIoU",), slot=None, nan_to_num=None, beta=1):
+        """`selective_metrics_of`: coverage and every metric at every threshold k = 0 .. K - 1 (mIoU against coverage)."""
+        return selective_metrics_of(self._of(slot), metric=metric, nan_to_num=nan_to_num, beta=beta)

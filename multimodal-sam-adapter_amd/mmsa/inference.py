@@ -13,6 +13,7 @@ canvases), `aug_class_map` (its argmax, from the canvas path or from ONE launch 
 Confidence maps (`confidence=` of the class-map entries, `conf=` of the plans, `argmax_max_map`): the probability of the predicted class, max over the
 classes of what `probabilities` / `aug_inference` return (ED:449,460), float32 [B, Ho, Wo], written by the launch that writes the class map.
 `calibration=` (mmsa.evaluate.Calibration) of the same entries bins that map against `labels=` on device: one more launch over the stored map and confidence.
+`selective=` (mmsa.evaluate.SelectiveEvaluator) of the same entries keeps one confusion matrix per confidence bin, likewise by one more launch: mIoU at a coverage.
 
 What a frame's output looks like -- its windows, the size after the second resize and after the cut, which class-map kernel that takes -- is decided once,
 in `MapPlan`, a record without device state; the entries read the frame (`_intake`), make the plan, and launch from it."""
@@ -234,27 +235,45 @@ def _confidence(confidence, size, device, what, fused=None, return_map=True):
     return _check_conf(confidence, size, device, what)
 
 
-def _check_calibration(calibration, labels, confidence, what, fused=None, return_map=True):
-    """`calibration=` of an entry, refused by name before anything is launched: it bins the confidence map against the labels, so it needs both, and the
-    stored map (the fused class-map + evaluation launch writes no confidence).  `confidence`: the entry's `confidence=`, or a runner's buffer."""
-    if calibration is None:
+def _check_binned(kw, cls, owner, labels, confidence, what, fused=None, return_map=True):
+    """`calibration=` / `selective=` of an entry (`kw`: the keyword's name, `cls`: the mmsa.evaluate class it takes), refused by name before anything is
+    launched: both reduce the confidence map against the labels, so they need both, and the stored map (the fused class-map + evaluation launch writes
+    no confidence).  `confidence`: the entry's `confidence=`, or a runner's buffer."""
+    if owner is None:
         return
-    from .evaluate import Calibration
-    if not isinstance(calibration, Calibration):
-        raise RuntimeError(f"mmsa.{what}: calibration= takes an mmsa.evaluate.Calibration, got {type(calibration).__name__}")
+    from . import evaluate
+    if not isinstance(owner, getattr(evaluate, cls)):
+        raise RuntimeError(f"mmsa.{what}: {kw}= takes an mmsa.evaluate.{cls}, got {type(owner).__name__}")
     if labels is None:
-        raise RuntimeError(f"mmsa.{what}: calibration= needs labels= (the raw uint8 label maps the confidence is checked against)")
+        raise RuntimeError(f"mmsa.{what}: {kw}= needs labels= (the raw uint8 label maps the confidence is checked against)")
     if confidence is None or confidence is False:
-        raise RuntimeError(f"mmsa.{what}: calibration= needs the confidence map: pass confidence=True or an output tensor (a SlideRunner: make it with "
+        raise RuntimeError(f"mmsa.{what}: {kw}= needs the confidence map: pass confidence=True or an output tensor (a SlideRunner: make it with "
                            "confidence=True)")
     if fused or not return_map:
         raise RuntimeError(f"mmsa.{what}: {_NO_CONF_FUSED}")
 
 
-def _check_labels(labels, evaluator, calibration):
-    """`labels=` feed an evaluator, a calibration or both; an evaluator needs them."""
-    if (labels is None) != (evaluator is None) and not (labels is not None and calibration is not None):
+def _check_calibration(calibration, labels, confidence, what, fused=None, return_map=True):
+    _check_binned("calibration", "Calibration", calibration, labels, confidence, what, fused, return_map)
+
+
+def _check_selective(selective, labels, confidence, what, fused=None, return_map=True):
+    _check_binned("selective", "SelectiveEvaluator", selective, labels, confidence, what, fused, return_map)
+
+
+def _check_labels(labels, evaluator, *binned):
+    """`labels=` feed an evaluator, a calibration, a selective evaluator or several of them; an evaluator needs them."""
+    if (labels is None) != (evaluator is None) and not (labels is not None and any(b is not None for b in binned)):
         raise RuntimeError("mmsa.inference: labels= and evaluator= come together")
+
+
+def _add_binned(out, conf, labels, case, calibration, selective):
+    """One more launch each over the stored map and confidence: the reliability bins (mmsa_eval_calibration) and the per-bin confusion counts
+    (mmsa_eval_selective)."""
+    if calibration is not None:
+        calibration.add(out, conf, labels, case=case)
+    if selective is not None:
+        selective.add(out, conf, labels, case=case)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -345,7 +364,8 @@ class MapPlan:
         """mmsa_slide_argmax, or its sibling that also writes `conf`."""
         lib.call("mmsa_slide_argmax" if conf is None else "mmsa_slide_argmax_conf", *self._args(lg, out, conf), unc.data_ptr(), ops._stream())
 
-    def class_map(self, lg, out, unc, labels=None, evaluator=None, case=None, fused=None, return_map=True, one_pass=None, conf=None, calibration=None):
+    def class_map(self, lg, out, unc, labels=None, evaluator=None, case=None, fused=None, return_map=True, one_pass=None, conf=None, calibration=None,
+                  selective=None):
         """The class-map launch of the three class-map calls, from the head-resolution logits lg [n, C, hs, ws] into out uint8 [B, Ho, Wo] and the
         uncovered-pixel word `unc`.  Without `labels`: mmsa_slide_argmax.  With `labels` (raw uint8 label maps [B, Hl, Wl]) and `evaluator`
         (mmsa.evaluate.Evaluator): the confusion counts of the map are ADDED to the evaluator's buffer as well -- by the same launch
@@ -358,14 +378,17 @@ class MapPlan:
         mmsa_softmax_flip_accum_nchw + mmsa_argmax_max_nchw): bit for bit probabilities(...).max(1), 0 where the map is 255.  The fused evaluation launch
         has no such sibling: `fused=True` / `return_map=False` are refused, and counts go through the stored map.
         `calibration` (mmsa.evaluate.Calibration; needs `labels` and `conf`, `evaluator` is optional with it): the reliability bins of the map and its
-        confidence are ADDED to its buffer by one more launch over the stored map and confidence (mmsa_eval_calibration), whatever launch wrote them."""
+        confidence are ADDED to its buffer by one more launch over the stored map and confidence (mmsa_eval_calibration), whatever launch wrote them.
+        `selective` (mmsa.evaluate.SelectiveEvaluator; needs `labels` and `conf`, `evaluator` and `calibration` are optional next to it): the confusion
+        counts per confidence bin are ADDED to its buffer in the same way (mmsa_eval_selective)."""
         _check_calibration(calibration, labels, conf, "inference", fused, return_map)
+        _check_selective(selective, labels, conf, "inference", fused, return_map)
         if conf is not None:
             if fused or not return_map:
                 raise RuntimeError(f"mmsa.inference: {_NO_CONF_FUSED}")
             _check_conf(conf, (self.B, self.Ho, self.Wo), out.device)
         if self.rescaled:
-            _check_labels(labels, evaluator, calibration)
+            _check_labels(labels, evaluator, calibration, selective)
             if fused or not return_map:
                 raise RuntimeError("mmsa.inference: fused=True / return_map=False need the fused class-map + evaluation launch, and that launch has no variant at "
                                    "a rescaled or cut size: the counts of a rescaled map go through the stored map (drop fused= / return_map=)")
@@ -378,8 +401,7 @@ class MapPlan:
                 _rescaled_map_canvas(self, lg, out, unc, conf)
             if evaluator is not None:
                 evaluator.add(out, labels, case=case)
-            if calibration is not None:
-                calibration.add(out, conf, labels, case=case)
+            _add_binned(out, conf, labels, case, calibration, selective)
             return
         if one_pass is not None:
             raise RuntimeError("mmsa.inference: one_pass= chooses the launch of a RESCALED class map; this map has the frame's size")
@@ -388,10 +410,10 @@ class MapPlan:
                 raise RuntimeError("mmsa.inference: return_map=False only makes sense with labels= and evaluator=")
             self._plain(lg, out, unc, conf)
             return
-        _check_labels(labels, evaluator, calibration)
-        if evaluator is None:                              # labels for the calibration alone
+        _check_labels(labels, evaluator, calibration, selective)
+        if evaluator is None:                              # labels for the calibration / the selective evaluator alone
             self._plain(lg, out, unc, conf)
-            calibration.add(out, conf, labels, case=case)
+            _add_binned(out, conf, labels, case, calibration, selective)
             return
         if fused is False and not return_map:
             raise RuntimeError("mmsa.inference: return_map=False needs the fused launch (two launches go through the stored map); drop fused=False")
@@ -401,8 +423,7 @@ class MapPlan:
         else:
             self._plain(lg, out, unc, conf)
             evaluator.add(out, labels, case=case)
-        if calibration is not None:
-            calibration.add(out, conf, labels, case=case)
+        _add_binned(out, conf, labels, case, calibration, selective)
 
 
 def _canvas_logits(plan, lg, unc):
@@ -436,7 +457,7 @@ def _rescaled_map_canvas(plan, lg, out, unc, conf=None):
 @_on_device
 @torch.no_grad()
 def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preprocess=None, labels=None, evaluator=None, case=None, fused=None,
-                    return_map=True, render=None, ori_shape=None, one_pass=None, confidence=False, calibration=None):
+                    return_map=True, render=None, ori_shape=None, one_pass=None, confidence=False, calibration=None, selective=None):
     """`simple_test` of a sliding-window frame (ED:191-234 + ED:449,477) -> uint8 class map [B, H, W], without the
     [B, classes, H, W] logits canvas: every window's logits stay at head resolution and ONE kernel (mmsa_slide_argmax) resizes,
     sums the overlapping windows in window order, divides by the count and takes the argmax -- the same additions in the same order
@@ -457,8 +478,12 @@ def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preproc
     stored map.
     `calibration=` (mmsa.evaluate.Calibration; `case=` with a per-case one): the reliability bins of the map and its confidence against `labels=` are
     added to it on device by one more launch (mmsa_eval_calibration), no host sync; it needs `labels=` and `confidence=`, `evaluator=` is optional with
-    it, and what is returned does not change."""
+    it, and what is returned does not change.
+    `selective=` (mmsa.evaluate.SelectiveEvaluator; `case=` with a per-case one): one confusion matrix per confidence bin of the map and its confidence
+    against `labels=` is added to it on device by one more launch (mmsa_eval_selective), no host sync; it needs `labels=` and `confidence=`, `evaluator=`
+    and `calibration=` are optional next to it, and what is returned does not change."""
     _check_calibration(calibration, labels, confidence, "slide_class_map", fused, return_map)
+    _check_selective(selective, labels, confidence, "slide_class_map", fused, return_map)
     B, H, W, device, frame, cut = _intake(img, preprocess, "slide_class_map")
     plan = MapPlan.slide(B, H, W, crop_size, stride, ori_shape)
     src = None if render is None else slide_source(render, preprocess, frame, plan, return_map, "slide_class_map")
@@ -472,7 +497,7 @@ def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preproc
     lg = lgs[0] if len(lgs) == 1 else torch.cat(lgs, 0)
     out = torch.empty(B, plan.Ho, plan.Wo, dtype=torch.uint8, device=device)
     unc = torch.zeros(1, dtype=torch.int32, device=device)
-    plan.class_map(lg, out, unc, labels, evaluator, case, fused, return_map, one_pass, conf, calibration)
+    plan.class_map(lg, out, unc, labels, evaluator, case, fused, return_map, one_pass, conf, calibration, selective)
     r = (out, unc, render(out, src)) if render is not None else ((out if return_map else None), unc)   # unc[0] != 0 <=> some pixel is not covered (ED:220); checked by the caller outside a capture
     return r if conf is None else r + (conf,)
 
@@ -480,7 +505,7 @@ def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preproc
 @_on_device
 @torch.no_grad()
 def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator=None, case=None, fused=None, return_map=True, render=None,
-                    ori_shape=None, dim=None, cut_dim=None, rescale=True, one_pass=None, confidence=False, calibration=None):
+                    ori_shape=None, dim=None, cut_dim=None, rescale=True, one_pass=None, confidence=False, calibration=None, selective=None):
     """Whole-image `simple_test`: resize x4 (bilinear, align_corners=False) + argmax fused (ED:90-94,449,477) -> uint8 [B, H, W].
     `preprocess=` (mmsa.preprocess.Preprocess): img is the pair (rgb, aux) of raw frames, normalised (and padded) by one launch.
     `labels=` + `evaluator=` (+ `case=`): as in slide_class_map.
@@ -495,8 +520,10 @@ def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator
     A LabelPrep for `labels=` must be built for that size; `fused=True` / `return_map=False` are refused; `render=` needs a source of the map's size: raw
     uint8 frames of the size before the cut, or -- for a cut alone -- the input tensor.
     `confidence=`: as in slide_class_map; the confidence map float32 [B, Ho, Wo] comes as the last element, (map[, picture], conf).
-    `calibration=`: as in slide_class_map (needs `labels=` and `confidence=`); at a rescaled or cut size the pass reads the map and confidence stored there."""
+    `calibration=`: as in slide_class_map (needs `labels=` and `confidence=`); at a rescaled or cut size the pass reads the map and confidence stored there.
+    `selective=`: as in slide_class_map (needs `labels=` and `confidence=`), over the map and confidence stored at the size returned."""
     _check_calibration(calibration, labels, confidence, "whole_class_map", fused, return_map)
+    _check_selective(selective, labels, confidence, "whole_class_map", fused, return_map)
     rgb = None
     if preprocess is not None:
         rgb, aux, B, H, W = _raw(preprocess, img, "whole_class_map")
@@ -515,7 +542,7 @@ def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator
     lg = head(feats)
     out = torch.empty(B, plan.Ho, plan.Wo, dtype=torch.uint8, device=img.device)
     unc = torch.zeros(1, dtype=torch.int32, device=img.device)
-    plan.class_map(lg, out, unc, labels, evaluator, case, fused, return_map, one_pass, conf, calibration)
+    plan.class_map(lg, out, unc, labels, evaluator, case, fused, return_map, one_pass, conf, calibration, selective)
     if render is not None:
         return (out, render(out, src)) if conf is None else (out, render(out, src), conf)
     if conf is not None:
@@ -584,7 +611,7 @@ def inference(backbone, head, img, test_cfg, rescale=True, preprocess=None, ori_
 @_on_device
 @torch.no_grad()
 def class_map(backbone, head, img, test_cfg, rescale=True, ori_shape=None, preprocess=None, labels=None, evaluator=None, case=None, render=None, one_pass=None,
-              confidence=False, calibration=None):
+              confidence=False, calibration=None, selective=None):
     """`simple_test` (ED:471-477) by mode: the dispatch of `inference` (ED:417-447) onto the class-map calls -> uint8 map, bit for bit
     argmax_map(inference(...)) of the same arguments, without a logits canvas: [B, H, W], or at the size `rescale` gives ('slide' / 'whole': `ori_shape`;
     'whole_dim': test_cfg['dim']; 'whole_dim_cut': the crop of the map at `dim`, or at the input size without `rescale`).  What `inference` refuses is
@@ -592,11 +619,13 @@ def class_map(backbone, head, img, test_cfg, rescale=True, ori_shape=None, prepr
     slide_inference's coverage check is) and raises on a window grid that does not cover the frame (ED:220).
     `preprocess=`, `labels=` + `evaluator=` (+ `case=`; through the stored map), `render=` (-> (map, picture)), `one_pass=`: as in the calls it goes to.
     `confidence=` (True or an output tensor): the confidence map, probabilities(...).max(1).values bit for bit, as the last element: (map[, picture], conf).
-    `calibration=` (mmsa.evaluate.Calibration; needs `labels=` and `confidence=`): as in the calls it goes to."""
+    `calibration=` (mmsa.evaluate.Calibration; needs `labels=` and `confidence=`): as in the calls it goes to.
+    `selective=` (mmsa.evaluate.SelectiveEvaluator; needs `labels=` and `confidence=`): as in the calls it goes to."""
     mode = test_cfg["mode"]
     _check_calibration(calibration, labels, confidence, "class_map")
+    _check_selective(selective, labels, confidence, "class_map")
     kw = dict(preprocess=preprocess, labels=labels, evaluator=evaluator, case=case, render=render, one_pass=one_pass, confidence=confidence,
-              calibration=calibration)
+              calibration=calibration, selective=selective)
     if mode == "slide":
         r = slide_class_map(backbone, head, img, tuple(test_cfg["crop_size"]), tuple(test_cfg["stride"]), ori_shape=ori_shape if rescale else None, **kw)
         if int(r[1].item()) != 0:
@@ -882,7 +911,7 @@ def aug_inference(backbone, head, imgs, test_cfg, ori_shape=None, flips=None, pr
 @_on_views_device
 @torch.no_grad()
 def aug_class_map(backbone, head, imgs, test_cfg, ori_shape=None, flips=None, preprocess=None, max_batch=8, labels=None, evaluator=None, case=None,
-                  one_pass=None, confidence=False, calibration=None):
+                  one_pass=None, confidence=False, calibration=None, selective=None):
     """`aug_test` (ED:509-546) -> (uint8 class map [B, Ho, Wo], uncovered-pixel word), bit for bit argmax_map(aug_inference(...)) of the same arguments.
     Every view goes through backbone and head (`max_batch` windows per call, per view); then ONE launch (mmsa_aug_argmax) resizes every view's
     head-resolution logits as `class_map` would, takes the softmax, un-flips, averages over the views and takes the argmax, with no logits or probability
@@ -893,9 +922,11 @@ def aug_class_map(backbone, head, imgs, test_cfg, ori_shape=None, flips=None, pr
     `confidence=` (True or a contiguous float32 [B, Ho, Wo] output tensor): the confidence map -- the mean probability of the predicted class, bit for bit
     aug_inference(...).max(1).values, 0 where the map is 255 -- from the same launch, as the last element: (map, unc, conf).
     `calibration=` (mmsa.evaluate.Calibration; needs `labels=` and `confidence=`, `evaluator=` is optional with it): the reliability bins of the averaged map
-    and its confidence are added to it by one more launch over the stored map and confidence."""
+    and its confidence are added to it by one more launch over the stored map and confidence.
+    `selective=` (mmsa.evaluate.SelectiveEvaluator; needs `labels=` and `confidence=`): the averaged map's confusion counts per confidence bin, likewise."""
     _check_calibration(calibration, labels, confidence, "aug_class_map")
-    _check_labels(labels, evaluator, calibration)
+    _check_selective(selective, labels, confidence, "aug_class_map")
+    _check_labels(labels, evaluator, calibration, selective)
     imgs, flips, pre = AugPlan.views(imgs, flips, preprocess, "aug_class_map")
     frames = [_intake(img, p, "aug_class_map") for img, p in zip(imgs, pre)]
     plan = AugPlan.of(test_cfg, [f[:3] for f in frames], flips, ori_shape)
@@ -915,8 +946,7 @@ def aug_class_map(backbone, head, imgs, test_cfg, ori_shape=None, flips=None, pr
     plan.class_map(lgs, out, unc, one_pass, conf)
     if evaluator is not None:
         evaluator.add(out, labels, case=case)
-    if calibration is not None:
-        calibration.add(out, conf, labels, case=case)
+    _add_binned(out, conf, labels, case, calibration, selective)
     return (out, unc) if conf is None else (out, unc, conf)
 
 
@@ -991,7 +1021,7 @@ class SlideRunner:
                 self.pic = torch.empty(B, plan.Ho, plan.Wo, 3, dtype=torch.uint8, device=self.device)
 
     @torch.no_grad()
-    def run(self, frame=None, labels=None, evaluator=None, case=None, fused=None, return_map=True, calibration=None):
+    def run(self, frame=None, labels=None, evaluator=None, case=None, fused=None, return_map=True, calibration=None, selective=None):
         """Enqueue one frame on the current stream (asynchronous) -> FrameResult; `.outputs()` = (class map uint8 [B, H, W], uncovered-pixel flag) once the
         attention logit guard of this pass has been inspected.  The inspection costs one 4 * depth-byte copy per `check_every` frames and an event wait,
         no device sync; a frame that scored logits beyond the fp16 range raises mmsa.chains.AttentionRangeError from outputs() -- or from the next run(),
@@ -1000,8 +1030,11 @@ class SlideRunner:
         evaluator on device (see MapPlan.class_map); a frame that has to be run again has been counted, so reset the evaluator or subtract what it added.
         `return_map=False` (always the fused launch) leaves the runner's map buffer untouched; the FrameResult's map is then None.
         `calibration=` (mmsa.evaluate.Calibration, best one made with cases=[...] and device=; a runner made with confidence=True; needs `labels=`): the
-        frame's reliability bins are ADDED to it on device by one more launch; a frame that has to be run again has been binned, as it has been counted."""
+        frame's reliability bins are ADDED to it on device by one more launch; a frame that has to be run again has been binned, as it has been counted.
+        `selective=` (mmsa.evaluate.SelectiveEvaluator, made the same way; needs `labels=` and a runner made with confidence=True): the frame's confusion
+        counts per confidence bin are ADDED to it on device by one more launch, under the same terms."""
         _check_calibration(calibration, labels, self.conf, "SlideRunner.run", fused, return_map)
+        _check_selective(selective, labels, self.conf, "SlideRunner.run", fused, return_map)
         if self.conf is not None and (fused or not return_map):
             raise RuntimeError(f"mmsa.SlideRunner.run: {_NO_CONF_FUSED}")
         if frame is None:
@@ -1018,7 +1051,7 @@ class SlideRunner:
             rp = self.chains.replay()
             lg = rp.unverified          # the argmax kernel below is enqueued behind the pass; nothing is read on the host before outputs() verifies it
             self.unc.zero_()
-            self.plan.class_map(lg, self.out, self.unc, labels, evaluator, case, fused, return_map, self.one_pass, self.conf, calibration)
+            self.plan.class_map(lg, self.out, self.unc, labels, evaluator, case, fused, return_map, self.one_pass, self.conf, calibration, selective)
             if self.render is not None:
                 self.render(self.out, src, out=self.pic)
         return FrameResult(self, rp, has_map=return_map)
