@@ -3,9 +3,7 @@
 // floor(conf * 2^24), the confidence in 24-bit fixed point) -- int64 [n_slots, 3, K].  ECE, MCE, the reliability diagram and accuracy against coverage
 // are formed from these integers in float64 on the host (mmsa/evaluate.py).  The label side (LUT, nearest-neighbour tables, clamping) is the one of
 // csrc/evaluate.hip.
-// One pass over 6 bytes per pixel, shaped like eval_confusion_kernel: a workgroup walks CAL_CHUNK pixels (whole rows where the tables apply, one flat
-// run per image otherwise); pred as dwords, conf as float4 where that span's address is 16-byte aligned (four dword loads otherwise), the label as
-// dwords where it shares pred's alignment and no table is in the way; an edge path, one pixel per lane, serves the unaligned head and tail.
+// The walk over (pred, conf, label) is the one of csrc/eval_walk.h, CAL_CHUNK pixels per workgroup.
 //
 // Bin updates.  Confidence is not patchy like a class map: there are few bins, most pixels of a trained model fall into the top one, and 64 lanes would
 // queue on a handful of LDS addresses.  So a lane first merges those of its four pixels that share a bin (neighbours usually do), and a wave then
@@ -19,7 +17,7 @@
 // Integer sums only, in LDS and in the int64 result: the same bytes whatever the order of arrival.
 #include "common.h"
 #include "conf_bin.h"
-#include "eval_hist.h"
+#include "eval_walk.h"
 
 // Pixels per workgroup.  Timed at 2048 / 4096 / 8192 (profiles/calibration.txt; -DCAL_CHUNK with tools/build_variant.sh): at 8192 (EVAL_CHUNK) a CU
 // holds one workgroup, one wave per SIMD, and nothing hides a round's dependent steps or the loads in front of them; at 2048 four times as many
@@ -30,17 +28,6 @@
 #define CAL_MAX_BINS 64
 #define CAL_MAX_CLASSES 254      // the LUT's limit (255 = ignored); there is no (C + 1)^2 histogram here
 #define CAL_NONE (-1)            // a lane without a participating pixel
-
-struct CalArgs {
-  const unsigned char* pred;     // [B, H, W]
-  const float* conf;             // [B, H, W]
-  const unsigned char* label;    // [B, Hl, Wl]
-  const unsigned char* lut;      // [256]
-  const int* ymap;               // [H] / [W], or both NULL
-  const int* xmap;
-  unsigned long long* cal;       // [n_slots, 3, K]
-  int H, W, Hl, Wl, C, K;
-};
 
 // one pixel -> its bin (CAL_NONE: takes no part), whether it is correct, and its confidence in 24-bit fixed point
 __device__ __forceinline__ int cal_pixel(const unsigned char* lut_s, unsigned label_byte, unsigned pred_byte, float c, int C, int K, float Kf, bool& ok,
@@ -86,59 +73,36 @@ __device__ __forceinline__ void cal_wave_add(unsigned long long* tc, unsigned lo
   }
 }
 
-template <bool TABLES>
-__device__ __forceinline__ unsigned cal_label_at(const unsigned char* __restrict__ l, const int* __restrict__ xmap, int Wl, int i) {
-  if (TABLES) return l[min(max(xmap[i], 0), Wl - 1)];
-  return l[i];
-}
+struct CalArgs : EvalWalkArgs {};       // out: the bins, [n_slots, 3, K]
 
-// n pixels: pred p[0..n) and conf c[0..n) against label l[0..n) (TABLES: l[xmap[0..n)], a label ROW)
-template <bool TABLES>
-__device__ __forceinline__ void cal_span(const unsigned char* __restrict__ p, const float* __restrict__ c, const unsigned char* __restrict__ l,
-                                         const int* __restrict__ xmap, int Wl, int n, unsigned long long* tc, unsigned long long* cs,
-                                         const unsigned char* lut_s, int C, int K) {
-  const float Kf = (float)K;
-  const int head = min(n, (int)((4u - (unsigned)((uintptr_t)p & 3u)) & 3u));     // bytes in front of the first aligned pred dword
-  const int ndw = (n - head) >> 2;
-  const int tail0 = head + (ndw << 2);
-  const int nedge = head + (n - tail0);                                          // edge path: at most 3 + 3 pixels, one lane each
-  if (nedge > 0 && threadIdx.x < 64u) {                                          // the first wave, all of its lanes
-    int bin = CAL_NONE;
-    bool ok = false;
-    unsigned q = 0u;
-    if ((int)threadIdx.x < nedge) {
-      const int i = (int)threadIdx.x < head ? (int)threadIdx.x : tail0 + ((int)threadIdx.x - head);
-      bin = cal_pixel(lut_s, cal_label_at<TABLES>(l, xmap, Wl, i), p[i], c[i], C, K, Kf, ok, q);
-    }
-    cal_wave_add(tc, cs, bin, 1u | ((unsigned)ok << 16), q);
+struct CalPixel {                // what the bins keep of one pixel
+  int bin;                       // CAL_NONE: takes no part
+  bool ok;
+  unsigned q;
+};
+
+struct CalBins {
+  static constexpr bool CONF = true;
+  using Px = CalPixel;
+  unsigned long long *tc, *cs;
+  const unsigned char* lut_s;
+  int C, K;
+  float Kf;
+
+  __device__ __forceinline__ CalPixel none() const { return {CAL_NONE, false, 0u}; }
+  __device__ __forceinline__ CalPixel pixel(unsigned label_byte, unsigned pred_byte, float c) const {
+    CalPixel px;
+    px.bin = cal_pixel(lut_s, label_byte, pred_byte, c, C, K, Kf, px.ok, px.q);
+    return px;
   }
-  const unsigned* __restrict__ pw = (const unsigned*)(p + head);
-  const float* __restrict__ cw = c + head;
-  const bool c16 = (((uintptr_t)cw) & 15u) == 0;                                 // this span's confidences start on a 16-byte boundary: float4 loads
-  const bool ldw = !TABLES && (((uintptr_t)(l + head)) & 3u) == 0;               // the label shares pred's alignment: dwords too
-  for (int i0 = 0; i0 < ndw; i0 += 256) {
-    const int i = i0 + (int)threadIdx.x;
+  // cal_wave_add needs whole waves: the edge path (at most 6 pixels) runs in the first wave only, all of its lanes
+  __device__ __forceinline__ bool edge_lanes(int nedge) const { return nedge > 0 && threadIdx.x < 64u; }
+  __device__ __forceinline__ void add1(const CalPixel& px) const { cal_wave_add(tc, cs, px.bin, 1u | ((unsigned)px.ok << 16), px.q); }
+  __device__ __forceinline__ void add4(bool has, unsigned lv, unsigned pv, float4 cv) const {
     int b[4] = {CAL_NONE, CAL_NONE, CAL_NONE, CAL_NONE};
     bool ok[4] = {false, false, false, false};
     unsigned q[4] = {0u, 0u, 0u, 0u};
-    if (i < ndw) {
-      const unsigned pv = pw[i];
-      const int base = head + 4 * i;
-      unsigned lv;
-      if (ldw)
-        lv = ((const unsigned*)(l + head))[i];
-      else
-        lv = cal_label_at<TABLES>(l, xmap, Wl, base) | (cal_label_at<TABLES>(l, xmap, Wl, base + 1) << 8) |
-             (cal_label_at<TABLES>(l, xmap, Wl, base + 2) << 16) | (cal_label_at<TABLES>(l, xmap, Wl, base + 3) << 24);
-      float4 cv;
-      if (c16) {
-        cv = ((const float4*)cw)[i];
-      } else {
-        cv.x = cw[4 * i];
-        cv.y = cw[4 * i + 1];
-        cv.z = cw[4 * i + 2];
-        cv.w = cw[4 * i + 3];
-      }
+    if (has) {
       b[0] = cal_pixel(lut_s, lv, pv & 255u, cv.x, C, K, Kf, ok[0], q[0]);
       b[1] = cal_pixel(lut_s, lv >> 8, (pv >> 8) & 255u, cv.y, C, K, Kf, ok[1], q[1]);
       b[2] = cal_pixel(lut_s, lv >> 16, (pv >> 16) & 255u, cv.z, C, K, Kf, ok[2], q[2]);
@@ -161,7 +125,7 @@ __device__ __forceinline__ void cal_span(const unsigned char* __restrict__ p, co
 #pragma unroll
     for (int j = 0; j < 4; ++j) cal_wave_add(tc, cs, b[j], cn[j], q[j]);
   }
-}
+};
 
 template <bool TABLES>
 __global__ __launch_bounds__(256) void eval_calibration_kernel(CalArgs a, EvalSlots es, int rows) {
@@ -175,23 +139,11 @@ __global__ __launch_bounds__(256) void eval_calibration_kernel(CalArgs a, EvalSl
   }
   lut_s[threadIdx.x] = a.lut[threadIdx.x];             // 256 threads, 256 bytes
   __syncthreads();
-  const int b = blockIdx.y, H = a.H, W = a.W;
-  if (TABLES) {
-    const int y1 = min(H, ((int)blockIdx.x + 1) * rows);
-    for (int y = (int)blockIdx.x * rows; y < y1; ++y) {
-      const int ys = min(max(a.ymap[y], 0), a.Hl - 1);
-      const long at = ((long)b * H + y) * W;
-      cal_span<true>(a.pred + at, a.conf + at, a.label + ((long)b * a.Hl + ys) * a.Wl, a.xmap, a.Wl, W, tc, cs, lut_s, a.C, K);
-    }
-  } else {                                             // same size: image b is one run of H * W pixels
-    const long HW = (long)H * W, start = (long)blockIdx.x * CAL_CHUNK;
-    const int n = (int)min((long)CAL_CHUNK, HW - start);
-    const long at = b * HW + start;
-    cal_span<false>(a.pred + at, a.conf + at, a.label + at, nullptr, 0, n, tc, cs, lut_s, a.C, K);
-  }
+  const int b = blockIdx.y;
+  eval_walk<TABLES, CAL_CHUNK>(a, b, rows, CalBins{tc, cs, lut_s, a.C, K, (float)K});
   __syncthreads();
   if ((int)threadIdx.x < K) {
-    unsigned long long* dst = a.cal + (long)es.s[b] * 3 * K;
+    unsigned long long* dst = a.out + (long)es.s[b] * 3 * K;
     const unsigned long long t = tc[threadIdx.x], s = cs[threadIdx.x];
     if (t) {                                           // conf_sum and correct are zero wherever total is
       atomicAdd(&dst[threadIdx.x], t & 0xffffffffull);
@@ -207,26 +159,12 @@ extern "C" int mmsa_eval_calibration(const unsigned char* pred, const float* con
   const char* name = "eval_calibration";
   MMSA_CHECK_ARG(pred && conf && label && lut && slots && cal, "%s: pred, conf, label, lut, slots and cal are required", name);
   MMSA_CHECK_ARG(((uintptr_t)conf & 3u) == 0, "%s: conf must be 4-byte aligned", name);
-  MMSA_CHECK_ARG(C >= 2 && C <= CAL_MAX_CLASSES, "%s: %d classes; 2..%d are supported (a uint8 label LUT; 255 means ignored)", name, C, CAL_MAX_CLASSES);
   MMSA_CHECK_ARG(bins >= 1 && bins <= CAL_MAX_BINS, "%s: %d bins; 1..%d are supported", name, bins, CAL_MAX_BINS);
-  MMSA_CHECK_ARG(B > 0 && B <= MMSA_EVAL_MAX_IMAGES, "%s: 1..%d images per call, got %d", name, MMSA_EVAL_MAX_IMAGES, B);
-  MMSA_CHECK_ARG(H > 0 && W > 0 && Hl > 0 && Wl > 0 && (long)H * W < (1l << 31) && (long)Hl * Wl < (1l << 31), "%s: bad map size", name);
-  MMSA_CHECK_ARG((ymap != NULL) == (xmap != NULL), "%s: ymap and xmap come together", name);
-  MMSA_CHECK_ARG(ymap || (Hl == H && Wl == W), "%s: size mismatch: the label is %d x %d, the prediction %d x %d, and no ymap / xmap tables were given",
-                 name, Hl, Wl, H, W);
-  MMSA_CHECK_ARG(n_slots > 0, "%s: n_slots must be positive", name);
   EvalSlots es;
-  for (int b = 0; b < B; ++b) {
-    MMSA_CHECK_ARG(slots[b] >= 0 && slots[b] < n_slots, "%s: slots[%d] = %d outside the %d count slots", name, b, slots[b], n_slots);
-    es.s[b] = slots[b];
-  }
-  const CalArgs a = {pred, conf, label, lut, ymap, xmap, (unsigned long long*)cal, H, W, Hl, Wl, C, bins};
-  if (ymap) {
-    const int rows = max(1, cdiv(CAL_CHUNK, W));
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(eval_calibration_kernel<true>), dim3(cdiv(H, rows), B), dim3(256), 0, stream, a, es, rows);
-  } else {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(eval_calibration_kernel<false>), dim3(cdiv((long)H * W, (long)CAL_CHUNK), B), dim3(256), 0, stream, a, es, 0);
-  }
+  int rc = eval_check(name, label, B, H, W, Hl, Wl, lut, C, ymap, xmap, slots, n_slots, cal, es, CAL_MAX_CLASSES, "a uint8 label LUT; 255 means ignored");
+  if (rc) return rc;
+  const CalArgs a = {{pred, conf, label, lut, ymap, xmap, (unsigned long long*)cal, H, W, Hl, Wl, C, bins}};
+  eval_walk_launch(eval_calibration_kernel<true>, eval_calibration_kernel<false>, ymap != NULL, CAL_CHUNK, B, H, W, 1, 0, stream, a, es);
   MMSA_CHECK_LAUNCH("eval_calibration");
   return MMSA_OK;
 }

@@ -64,12 +64,14 @@ __device__ __forceinline__ void eval_hist_flush(const unsigned* hist, unsigned l
   }
 }
 
-// host: the label-side arguments of both entries, checked before anything is launched
+// host: the label-side arguments of every entry, checked before anything is launched; `max_classes` and its reason `why` are the entry's own (the
+// histogram's LDS for the passes that keep one)
 static inline int eval_check(const char* name, const unsigned char* label, int B, int H, int W, int Hl, int Wl, const unsigned char* lut, int C,
-                             const int* ymap, const int* xmap, const int* slots, int n_slots, const int64_t* counts, EvalSlots& es) {
+                             const int* ymap, const int* xmap, const int* slots, int n_slots, const int64_t* counts, EvalSlots& es,
+                             int max_classes = MMSA_EVAL_MAX_CLASSES,
+                             const char* why = "the (C + 1)^2 uint32 histogram of a workgroup must fit 64 KiB of LDS") {
   MMSA_CHECK_ARG(label && lut && slots && counts, "%s: label, lut, slots and counts are required", name);
-  MMSA_CHECK_ARG(C >= 2 && C <= MMSA_EVAL_MAX_CLASSES, "%s: %d classes; 2..%d are supported (the (C + 1)^2 uint32 histogram of a workgroup must fit 64 KiB of LDS)",
-                 name, C, MMSA_EVAL_MAX_CLASSES);
+  MMSA_CHECK_ARG(C >= 2 && C <= max_classes, "%s: %d classes; 2..%d are supported (%s)", name, C, max_classes, why);
   MMSA_CHECK_ARG(B > 0 && B <= MMSA_EVAL_MAX_IMAGES, "%s: 1..%d images per call, got %d", name, MMSA_EVAL_MAX_IMAGES, B);
   MMSA_CHECK_ARG(H > 0 && W > 0 && Hl > 0 && Wl > 0 && (long)H * W < (1l << 31) && (long)Hl * Wl < (1l << 31), "%s: bad map size", name);
   MMSA_CHECK_ARG((ymap != NULL) == (xmap != NULL), "%s: ymap and xmap come together", name);

@@ -4,49 +4,31 @@
 //   the nearest-neighbour label resize of `Resize_multimodal._resize_seg` (datasets/pipelines/transform.py:1169-1188) is a pair of per-axis source
 //   index tables (the label is read at [ymap[y], xmap[x]], clamped into the label map whatever the tables hold);
 //   the four histograms follow from counts[label class][pred class] (csrc/eval_hist.h).
-// One pass over 2 bytes per pixel, HBM-bound: a workgroup walks EVAL_CHUNK pixels (several rows), pred -- and the label where no table is in the way
-// and its alignment matches -- read as dwords, into its private LDS histogram, then adds its non-zero bins to the int64 counts.
+// The walk over (pred, label) is the one of csrc/eval_walk.h, EVAL_CHUNK pixels per workgroup, into the workgroup's private LDS histogram; its non-zero
+// bins are then added to the int64 counts.
 #include "common.h"
-#include "eval_hist.h"
+#include "eval_walk.h"
 
+#ifndef EVAL_CHUNK
 #define EVAL_CHUNK 8192      // pixels per workgroup: 32 per lane, so that the flush (at most (C + 1)^2 atomics, usually a few dozen) is amortised
+#endif
 
-template <bool TABLES>
-__device__ __forceinline__ unsigned eval_label_at(const unsigned char* __restrict__ l, const int* __restrict__ xmap, int Wl, int i) {
-  if (TABLES) return l[min(max(xmap[i], 0), Wl - 1)];
-  return l[i];
-}
+// Same-bin merging.  Class maps are patchy: a lane whose four pixels share a bin makes one add of 4, merged across the wave by eval_hist_add's
+// broadcast rounds; the pixels of any other lane (edges, noise) are plain LDS atomics.
+struct EvalConfusion {
+  static constexpr bool CONF = false;
+  unsigned* hist;
+  const unsigned char* lut_s;
+  int C;
 
-// n pixels: pred p[0..n) against label l[0..n) (TABLES: l[xmap[0..n)], a label ROW)
-template <bool TABLES>
-__device__ __forceinline__ void eval_span(const unsigned char* __restrict__ p, const unsigned char* __restrict__ l, const int* __restrict__ xmap, int Wl,
-                                          int n, unsigned* hist, const unsigned char* lut_s, int C) {
-  const int head = min(n, (int)((4u - (unsigned)((uintptr_t)p & 3u)) & 3u));     // bytes in front of the first aligned pred dword
-  const int ndw = (n - head) >> 2;
-  const int tail0 = head + (ndw << 2);
-  const int nedge = head + (n - tail0);                                          // edge path: at most 3 + 3 pixels, one lane each
-  {
-    int bin = -1;
-    if ((int)threadIdx.x < nedge) {
-      const int i = (int)threadIdx.x < head ? (int)threadIdx.x : tail0 + ((int)threadIdx.x - head);
-      bin = eval_bin(lut_s, eval_label_at<TABLES>(l, xmap, Wl, i), p[i], C);
-    }
-    eval_hist_add(hist, bin, 1u);
-  }
-  const unsigned* __restrict__ pw = (const unsigned*)(p + head);
-  const bool ldw = !TABLES && (((uintptr_t)(l + head)) & 3u) == 0;               // the label shares pred's alignment: dwords too
-  for (int i0 = 0; i0 < ndw; i0 += 256) {
-    const int i = i0 + (int)threadIdx.x;
+  using Px = int;                                                                // the pixel's bin, or -1: ignored label / no pixel
+  __device__ __forceinline__ int none() const { return -1; }
+  __device__ __forceinline__ int pixel(unsigned label_byte, unsigned pred_byte, float) const { return eval_bin(lut_s, label_byte, pred_byte, C); }
+  __device__ __forceinline__ bool edge_lanes(int) const { return true; }
+  __device__ __forceinline__ void add1(int bin) const { eval_hist_add(hist, bin, 1u); }
+  __device__ __forceinline__ void add4(bool has, unsigned lv, unsigned pv, float4) const {
     int b0 = -1, b1 = -1, b2 = -1, b3 = -1;
-    if (i < ndw) {
-      const unsigned pv = pw[i];
-      const int base = head + 4 * i;
-      unsigned lv;
-      if (ldw)
-        lv = ((const unsigned*)(l + head))[i];
-      else
-        lv = eval_label_at<TABLES>(l, xmap, Wl, base) | (eval_label_at<TABLES>(l, xmap, Wl, base + 1) << 8) |
-             (eval_label_at<TABLES>(l, xmap, Wl, base + 2) << 16) | (eval_label_at<TABLES>(l, xmap, Wl, base + 3) << 24);
+    if (has) {
       b0 = eval_bin(lut_s, lv, pv & 255u, C);
       b1 = eval_bin(lut_s, lv >> 8, (pv >> 8) & 255u, C);
       b2 = eval_bin(lut_s, lv >> 16, (pv >> 16) & 255u, C);
@@ -61,7 +43,7 @@ __device__ __forceinline__ void eval_span(const unsigned char* __restrict__ p, c
       if (b3 >= 0) atomicAdd(&hist[b3], 1u);
     }
   }
-}
+};
 
 template <bool TABLES>
 __global__ __launch_bounds__(256) void eval_confusion_kernel(const unsigned char* __restrict__ pred, int H, int W, EvalLabel ev, EvalSlots es, int rows) {
@@ -70,18 +52,9 @@ __global__ __launch_bounds__(256) void eval_confusion_kernel(const unsigned char
   unsigned* hist = eval_lds;
   unsigned char* lut_s = (unsigned char*)(eval_lds + nbins);
   eval_hist_init(hist, lut_s, ev.lut, nbins);
+  const EvalWalkArgs a = {pred, nullptr, ev.label, ev.lut, ev.ymap, ev.xmap, ev.counts, H, W, ev.Hl, ev.Wl, C, 0};
   const int b = blockIdx.y;
-  if (TABLES) {
-    const int y1 = min(H, ((int)blockIdx.x + 1) * rows);
-    for (int y = (int)blockIdx.x * rows; y < y1; ++y) {
-      const int ys = min(max(ev.ymap[y], 0), ev.Hl - 1);
-      eval_span<true>(pred + ((long)b * H + y) * W, ev.label + ((long)b * ev.Hl + ys) * ev.Wl, ev.xmap, ev.Wl, W, hist, lut_s, C);
-    }
-  } else {                                          // same size: image b is one run of H * W byte pairs
-    const long HW = (long)H * W, start = (long)blockIdx.x * EVAL_CHUNK;
-    const int n = (int)min((long)EVAL_CHUNK, HW - start);
-    eval_span<false>(pred + b * HW + start, ev.label + b * HW + start, nullptr, 0, n, hist, lut_s, C);
-  }
+  eval_walk<TABLES, EVAL_CHUNK>(a, b, rows, EvalConfusion{hist, lut_s, C});
   eval_hist_flush(hist, ev.counts + (long)es.s[b] * nbins, nbins);
 }
 
@@ -94,12 +67,7 @@ extern "C" int mmsa_eval_confusion_u8(const unsigned char* pred, const unsigned 
   if (rc) return rc;
   const EvalLabel ev = {label, lut, ymap, xmap, (unsigned long long*)counts, Hl, Wl, C};
   const size_t lds = (size_t)(C + 1) * (C + 1) * 4 + 256;
-  if (ymap) {
-    const int rows = max(1, cdiv(EVAL_CHUNK, W));
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(eval_confusion_kernel<true>), dim3(cdiv(H, rows), B), dim3(256), lds, stream, pred, H, W, ev, es, rows);
-  } else {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(eval_confusion_kernel<false>), dim3(cdiv((long)H * W, (long)EVAL_CHUNK), B), dim3(256), lds, stream, pred, H, W, ev, es, 0);
-  }
+  eval_walk_launch(eval_confusion_kernel<true>, eval_confusion_kernel<false>, ymap != NULL, EVAL_CHUNK, B, H, W, 1, lds, stream, pred, H, W, ev, es);
   MMSA_CHECK_LAUNCH("eval_confusion_u8");
   return MMSA_OK;
 }

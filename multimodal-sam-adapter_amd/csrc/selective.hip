@@ -5,10 +5,7 @@
 // Calibration's total[k] and the trace of its [:C, :C] block is correct[k]; the suffix sums over k are the confusion counts of the map with the pixels
 // below a confidence threshold taken out -- mIoU against coverage, formed in float64 on the host (mmsa/evaluate.py).  mmsa_abstain_u8 below writes
 // that thresholded map from the same clamp and bin.
-// One pass over 6 bytes per pixel, shaped like eval_confusion_kernel and eval_calibration_kernel: a workgroup walks SEL_CHUNK pixels (whole rows where
-// the tables apply, one flat run per image otherwise); pred as dwords, conf as float4 where that span's address is 16-byte aligned (four dword loads
-// otherwise), the label as dwords where it shares pred's alignment and no table is in the way; an edge path, one pixel per lane, serves the unaligned
-// head and tail.
+// The walk over (pred, conf, label) is the one of csrc/eval_walk.h, SEL_CHUNK pixels per workgroup.
 //
 // LDS budget and bin groups.  A workgroup keeps a private uint32 histogram of the bins it is responsible for: (C + 1)^2 * 4 bytes per bin, 40 560 B for
 // the model's 25 classes and 15 bins.  The launch stays within the 64 KiB a launch may ask for without a function attribute (as evaluate.hip does):
@@ -21,14 +18,18 @@
 //   0  every pixel through eval_hist_add's two broadcast rounds on the combined key k * (C + 1)^2 + row * (C + 1) + col;
 //   1  evaluate.hip's form: a lane whose four pixels share a key makes one add of 4 through the broadcast rounds, any other lane four plain LDS atomics;
 //   2  as 1, but the pixels of a mixed lane go through the broadcast rounds as well (merged among the mixed lanes).
+// Form 1 is the fastest on every leg: on the model's confidences form 0 takes 1.3 us more (16.9 against 15.6) and form 2 2.5 - 2.9 us more, on uniform
+// confidences 3.4 - 5.0 us more.
 // Integer sums only, in LDS and in the int64 result: the same bytes whatever the order of arrival.  Plain C++ and HIP atomics; no inline assembly.
 #include "common.h"
 #include "conf_bin.h"
-#include "eval_hist.h"
+#include "eval_walk.h"
 
 // Pixels per workgroup.  A workgroup zeroes and scans its whole histogram (K * (C + 1)^2 words: 40 per lane at 25 classes and 15 bins) whatever it
 // walked, so the chunk is evaluate.hip's 8192 rather than calibrate.hip's 4096: 32 pixels per lane against those 80 LDS accesses, and two 1024 x 1024
-// maps are 256 workgroups, one per CU of the chip.
+// maps are 256 workgroups, one per CU of the chip.  Timed (profiles/selective.txt): 4096 is 0.4 - 0.6 us faster on the model's confidences with one bin
+// group (15.15 against 15.56 us, 14.94 against 15.54: within that leg's own p90 - p10), 2 - 6 us slower on uniform confidences and 9 - 11 us slower with
+// six bin groups, where every group zeroes and scans twice as often.
 #ifndef SEL_CHUNK
 #define SEL_CHUNK 8192
 #endif
@@ -38,15 +39,8 @@
 #define SEL_MAX_BINS 64
 #define SEL_LDS_BYTES (65536 - 256)       // the histogram's share of the 64 KiB; the LUT takes the rest
 
-struct SelArgs {
-  const unsigned char* pred;     // [B, H, W]
-  const float* conf;             // [B, H, W]
-  const unsigned char* label;    // [B, Hl, Wl]
-  const unsigned char* lut;      // [256]
-  const int* ymap;               // [H] / [W], or both NULL
-  const int* xmap;
-  unsigned long long* counts;    // [n_slots, K, C + 1, C + 1]
-  int H, W, Hl, Wl, C, K, G;     // G: bins per group
+struct SelArgs : EvalWalkArgs {  // out: the counts, [n_slots, K, C + 1, C + 1]
+  int G;                         // bins per group
 };
 
 struct SelGroup {                // what a workgroup's bin group needs per pixel
@@ -62,53 +56,19 @@ __device__ __forceinline__ int sel_key(const SelGroup& g, unsigned label_byte, u
   return (cell >= 0 && (unsigned)k < (unsigned)g.kn) ? k * g.nb + cell : -1;
 }
 
-template <bool TABLES>
-__device__ __forceinline__ unsigned sel_label_at(const unsigned char* __restrict__ l, const int* __restrict__ xmap, int Wl, int i) {
-  if (TABLES) return l[min(max(xmap[i], 0), Wl - 1)];
-  return l[i];
-}
+struct SelCounts {
+  static constexpr bool CONF = true;
+  using Px = int;                                                                // the pixel's key, or -1
+  unsigned* hist;
+  const SelGroup& g;
 
-// n pixels: pred p[0..n) and conf c[0..n) against label l[0..n) (TABLES: l[xmap[0..n)], a label ROW)
-template <bool TABLES>
-__device__ __forceinline__ void sel_span(const unsigned char* __restrict__ p, const float* __restrict__ c, const unsigned char* __restrict__ l,
-                                         const int* __restrict__ xmap, int Wl, int n, unsigned* hist, const SelGroup& g) {
-  const int head = min(n, (int)((4u - (unsigned)((uintptr_t)p & 3u)) & 3u));     // bytes in front of the first aligned pred dword
-  const int ndw = (n - head) >> 2;
-  const int tail0 = head + (ndw << 2);
-  const int nedge = head + (n - tail0);                                          // edge path: at most 3 + 3 pixels, one lane each
-  {
-    int key = -1;
-    if ((int)threadIdx.x < nedge) {
-      const int i = (int)threadIdx.x < head ? (int)threadIdx.x : tail0 + ((int)threadIdx.x - head);
-      key = sel_key(g, sel_label_at<TABLES>(l, xmap, Wl, i), p[i], c[i]);
-    }
-    eval_hist_add(hist, key, 1u);
-  }
-  const unsigned* __restrict__ pw = (const unsigned*)(p + head);
-  const float* __restrict__ cw = c + head;
-  const bool c16 = (((uintptr_t)cw) & 15u) == 0;                                 // this span's confidences start on a 16-byte boundary: float4 loads
-  const bool ldw = !TABLES && (((uintptr_t)(l + head)) & 3u) == 0;               // the label shares pred's alignment: dwords too
-  for (int i0 = 0; i0 < ndw; i0 += 256) {
-    const int i = i0 + (int)threadIdx.x;
+  __device__ __forceinline__ int none() const { return -1; }
+  __device__ __forceinline__ int pixel(unsigned label_byte, unsigned pred_byte, float c) const { return sel_key(g, label_byte, pred_byte, c); }
+  __device__ __forceinline__ bool edge_lanes(int) const { return true; }
+  __device__ __forceinline__ void add1(int key) const { eval_hist_add(hist, key, 1u); }
+  __device__ __forceinline__ void add4(bool has, unsigned lv, unsigned pv, float4 cv) const {
     int b0 = -1, b1 = -1, b2 = -1, b3 = -1;
-    if (i < ndw) {
-      const unsigned pv = pw[i];
-      const int base = head + 4 * i;
-      unsigned lv;
-      if (ldw)
-        lv = ((const unsigned*)(l + head))[i];
-      else
-        lv = sel_label_at<TABLES>(l, xmap, Wl, base) | (sel_label_at<TABLES>(l, xmap, Wl, base + 1) << 8) |
-             (sel_label_at<TABLES>(l, xmap, Wl, base + 2) << 16) | (sel_label_at<TABLES>(l, xmap, Wl, base + 3) << 24);
-      float4 cv;
-      if (c16) {
-        cv = ((const float4*)cw)[i];
-      } else {
-        cv.x = cw[4 * i];
-        cv.y = cw[4 * i + 1];
-        cv.z = cw[4 * i + 2];
-        cv.w = cw[4 * i + 3];
-      }
+    if (has) {
       b0 = sel_key(g, lv, pv & 255u, cv.x);
       b1 = sel_key(g, lv >> 8, (pv >> 8) & 255u, cv.y);
       b2 = sel_key(g, lv >> 16, (pv >> 16) & 255u, cv.z);
@@ -137,7 +97,7 @@ __device__ __forceinline__ void sel_span(const unsigned char* __restrict__ p, co
     }
 #endif
   }
-}
+};
 
 template <bool TABLES>
 __global__ __launch_bounds__(256) void eval_selective_kernel(SelArgs a, EvalSlots es, int rows) {
@@ -148,21 +108,9 @@ __global__ __launch_bounds__(256) void eval_selective_kernel(SelArgs a, EvalSlot
   unsigned char* lut_s = (unsigned char*)(sel_lds + min(a.G, K) * nb);
   eval_hist_init(hist, lut_s, a.lut, kn * nb);
   const SelGroup g = {lut_s, C, nb, K, k0, kn, (float)K};
-  const int b = blockIdx.y, H = a.H, W = a.W;
-  if (TABLES) {
-    const int y1 = min(H, ((int)blockIdx.x + 1) * rows);
-    for (int y = (int)blockIdx.x * rows; y < y1; ++y) {
-      const int ys = min(max(a.ymap[y], 0), a.Hl - 1);
-      const long at = ((long)b * H + y) * W;
-      sel_span<true>(a.pred + at, a.conf + at, a.label + ((long)b * a.Hl + ys) * a.Wl, a.xmap, a.Wl, W, hist, g);
-    }
-  } else {                                             // same size: image b is one run of H * W pixels
-    const long HW = (long)H * W, start = (long)blockIdx.x * SEL_CHUNK;
-    const int n = (int)min((long)SEL_CHUNK, HW - start);
-    const long at = b * HW + start;
-    sel_span<false>(a.pred + at, a.conf + at, a.label + at, nullptr, 0, n, hist, g);
-  }
-  eval_hist_flush(hist, a.counts + ((long)es.s[b] * K + k0) * nb, kn * nb);
+  const int b = blockIdx.y;
+  eval_walk<TABLES, SEL_CHUNK>(a, b, rows, SelCounts{hist, g});
+  eval_hist_flush(hist, a.out + ((long)es.s[b] * K + k0) * nb, kn * nb);
 }
 
 extern "C" int mmsa_eval_selective(const unsigned char* pred, const float* conf, const unsigned char* label, int B, int H, int W, int Hl, int Wl,
@@ -179,13 +127,8 @@ extern "C" int mmsa_eval_selective(const unsigned char* pred, const float* conf,
   const int G = SEL_LDS_BYTES / (nb * 4);              // >= 1 for C <= MMSA_EVAL_MAX_CLASSES
   const int groups = cdiv(bins, G);
   const size_t lds = (size_t)min(G, bins) * nb * 4 + 256;
-  const SelArgs a = {pred, conf, label, lut, ymap, xmap, (unsigned long long*)counts, H, W, Hl, Wl, C, bins, G};
-  if (ymap) {
-    const int rows = max(1, cdiv(SEL_CHUNK, W));
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(eval_selective_kernel<true>), dim3(cdiv(H, rows), B, groups), dim3(256), lds, stream, a, es, rows);
-  } else {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(eval_selective_kernel<false>), dim3(cdiv((long)H * W, (long)SEL_CHUNK), B, groups), dim3(256), lds, stream, a, es, 0);
-  }
+  const SelArgs a = {{pred, conf, label, lut, ymap, xmap, (unsigned long long*)counts, H, W, Hl, Wl, C, bins}, G};
+  eval_walk_launch(eval_selective_kernel<true>, eval_selective_kernel<false>, ymap != NULL, SEL_CHUNK, B, H, W, groups, lds, stream, a, es);
   MMSA_CHECK_LAUNCH("eval_selective");
   return MMSA_OK;
 }

@@ -24,7 +24,7 @@ such threshold in float64 -- mIoU against coverage -- and `abstain` (mmsa_abstai
 those counts describe, from the same clamp and bin.  The reference has no such step either."""
 import ctypes
 import warnings
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 import torch
@@ -428,11 +428,12 @@ def _slot_args(slots, B, n_slots):
     return (ctypes.c_int * B)(*slots)
 
 
-def _check_counts(counts, C, device):
-    if (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int64 or counts.dim() != 3 or tuple(counts.shape[1:]) != (C + 1, C + 1)
-            or counts.device != device or not counts.is_contiguous()):
-        raise RuntimeError(f"mmsa.evaluate: counts must be a contiguous int64 [n_slots, {C + 1}, {C + 1}] tensor on {device}")
-    return counts
+def _check_buffer(buf, name, shape, device):
+    """`buf` is a pass's result buffer: a contiguous int64 [n_slots, *shape] tensor on `device`."""
+    if (not isinstance(buf, torch.Tensor) or buf.dtype != torch.int64 or buf.dim() != len(shape) + 1 or tuple(buf.shape[1:]) != tuple(shape)
+            or buf.device != device or not buf.is_contiguous()):
+        raise RuntimeError(f"mmsa.evaluate: {name} must be a contiguous int64 [n_slots, {', '.join(str(v) for v in shape)}] tensor on {device}")
+    return buf
 
 
 def _check_pred(pred):
@@ -443,26 +444,6 @@ def _check_pred(pred):
     if pred.dim() != 3 or not pred.is_contiguous():
         raise RuntimeError(f"mmsa.evaluate: pred must be a contiguous [B, H, W] tensor, got {tuple(pred.shape)}")
     return pred
-
-
-@torch.no_grad()
-def confusion(pred, labels, prep, counts=None, slots=None):
-    """ADD the confusion counts of the uint8 class maps pred [B, H, W] against the raw labels [B, Hl, Wl] into counts[slots[b]] (one launch,
-    mmsa_eval_confusion_u8) -> counts, int64 [n_slots, C + 1, C + 1] on the device.  `slots` defaults to 0 .. B - 1 (per-image counts, as `pre_eval`
-    returns them); `counts` defaults to a zeroed buffer of max(slots) + 1 slots."""
-    pred = _check_pred(pred)
-    B, H, W = (int(v) for v in pred.shape)
-    C = prep.num_classes
-    with torch.cuda.device(pred.device):
-        largs = prep.launch_args(labels, B, H, W, pred.device)
-        if counts is None:
-            n_slots = B if slots is None else max(int(s) for s in slots) + 1
-            counts = torch.zeros(n_slots, C + 1, C + 1, dtype=torch.int64, device=pred.device)
-        _check_counts(counts, C, pred.device)
-        tab = _slot_args(slots, B, counts.shape[0])
-        lib.call("mmsa_eval_confusion_u8", pred.data_ptr(), largs[0], B, H, W, largs[1], largs[2], largs[3], C, largs[4], largs[5], tab, counts.shape[0],
-                 counts.data_ptr(), ops._stream())
-    return counts
 
 
 def _check_confmap(conf, pred):
@@ -486,11 +467,53 @@ def _check_bins(bins):
     return int(bins)
 
 
-def _check_cal(cal, K, device):
-    if (not isinstance(cal, torch.Tensor) or cal.dtype != torch.int64 or cal.dim() != 3 or tuple(cal.shape[1:]) != (3, K) or cal.device != device
-            or not cal.is_contiguous()):
-        raise RuntimeError(f"mmsa.evaluate: cal must be a contiguous int64 [n_slots, 3, {K}] tensor on {device}")
-    return cal
+def _check_selective_classes(C):
+    if C > MAX_SELECTIVE_CLASSES:
+        raise RuntimeError(f"mmsa.evaluate: {C} classes; selective evaluation supports 2..{MAX_SELECTIVE_CLASSES} (one bin's (C + 1)^2 uint32 histogram must "
+                           "fit a workgroup's 64 KiB of LDS)")
+    return C
+
+
+# A pass over stored maps (csrc/eval_walk.h): its entry, the name of its result buffer, the trailing shape of that int64 [n_slots, ...] buffer for C
+# classes and K bins, the axis of K in the buffer (None: a pass without a confidence map), and the pass's own check of the class count.
+_Pass = namedtuple("_Pass", "entry name shape k_axis check_classes")
+_CONFUSION = _Pass("mmsa_eval_confusion_u8", "counts", lambda C, K: (C + 1, C + 1), None, None)
+_CALIBRATION = _Pass("mmsa_eval_calibration", "cal", lambda C, K: (3, K), 2, None)
+_SELECTIVE = _Pass("mmsa_eval_selective", "counts", lambda C, K: (K, C + 1, C + 1), 1, _check_selective_classes)
+
+
+def _launch(which, pred, conf, labels, prep, bins, buf, slots):
+    """One launch of a pass: the maps and the buffer checked, the buffer allocated (zeroed, max(slots) + 1 slots) where none is given -> the buffer."""
+    pred = _check_pred(pred)
+    B, H, W = (int(v) for v in pred.shape)
+    C = prep.num_classes
+    confs = ()
+    if which.k_axis is not None:
+        confs = (_check_confmap(conf, pred).data_ptr(),)
+        if which.check_classes is not None:
+            which.check_classes(C)
+        if bins is None:
+            bins = int(buf.shape[which.k_axis]) if isinstance(buf, torch.Tensor) and buf.dim() == len(which.shape(C, 0)) + 1 else DEFAULT_BINS
+        bins = _check_bins(bins)
+    shape = which.shape(C, bins)
+    with torch.cuda.device(pred.device):
+        largs = prep.launch_args(labels, B, H, W, pred.device)
+        if buf is None:
+            n_slots = B if slots is None else max(int(s) for s in slots) + 1
+            buf = torch.zeros(n_slots, *shape, dtype=torch.int64, device=pred.device)
+        _check_buffer(buf, which.name, shape, pred.device)
+        tab = _slot_args(slots, B, buf.shape[0])
+        lib.call(which.entry, pred.data_ptr(), *confs, largs[0], B, H, W, largs[1], largs[2], largs[3], C, largs[4], largs[5], tab, buf.shape[0],
+                 *(() if which.k_axis is None else (bins,)), buf.data_ptr(), ops._stream())
+    return buf
+
+
+@torch.no_grad()
+def confusion(pred, labels, prep, counts=None, slots=None):
+    """ADD the confusion counts of the uint8 class maps pred [B, H, W] against the raw labels [B, Hl, Wl] into counts[slots[b]] (one launch,
+    mmsa_eval_confusion_u8) -> counts, int64 [n_slots, C + 1, C + 1] on the device.  `slots` defaults to 0 .. B - 1 (per-image counts, as `pre_eval`
+    returns them); `counts` defaults to a zeroed buffer of max(slots) + 1 slots."""
+    return _launch(_CONFUSION, pred, None, labels, prep, None, counts, slots)
 
 
 @torch.no_grad()
@@ -500,37 +523,7 @@ def calibration(pred, conf, labels, prep, bins=None, cal=None, slots=None):
     A pixel takes part iff its transformed label is a class (< C); it is correct iff pred equals it; its bin is min(K - 1, int(float32(c) * float32(K)))
     of its confidence c clamped to [0, 1] (NaN -> 0); conf_sum adds floor(c * 2^24).  `bins` = K defaults to cal's, or to 15; `slots` defaults to
     0 .. B - 1 (per-image bins); `cal` defaults to a zeroed buffer of max(slots) + 1 slots."""
-    pred = _check_pred(pred)
-    conf = _check_confmap(conf, pred)
-    B, H, W = (int(v) for v in pred.shape)
-    C = prep.num_classes
-    if bins is None:
-        bins = int(cal.shape[-1]) if isinstance(cal, torch.Tensor) and cal.dim() == 3 else DEFAULT_BINS
-    K = _check_bins(bins)
-    with torch.cuda.device(pred.device):
-        largs = prep.launch_args(labels, B, H, W, pred.device)
-        if cal is None:
-            n_slots = B if slots is None else max(int(s) for s in slots) + 1
-            cal = torch.zeros(n_slots, 3, K, dtype=torch.int64, device=pred.device)
-        _check_cal(cal, K, pred.device)
-        tab = _slot_args(slots, B, cal.shape[0])
-        lib.call("mmsa_eval_calibration", pred.data_ptr(), conf.data_ptr(), largs[0], B, H, W, largs[1], largs[2], largs[3], C, largs[4], largs[5], tab,
-                 cal.shape[0], K, cal.data_ptr(), ops._stream())
-    return cal
-
-
-def _check_selective_classes(C):
-    if C > MAX_SELECTIVE_CLASSES:
-        raise RuntimeError(f"mmsa.evaluate: {C} classes; selective evaluation supports 2..{MAX_SELECTIVE_CLASSES} (one bin's (C + 1)^2 uint32 histogram must "
-                           "fit a workgroup's 64 KiB of LDS)")
-    return C
-
-
-def _check_selective_counts(counts, K, C, device):
-    if (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int64 or counts.dim() != 4 or tuple(counts.shape[1:]) != (K, C + 1, C + 1)
-            or counts.device != device or not counts.is_contiguous()):
-        raise RuntimeError(f"mmsa.evaluate: counts must be a contiguous int64 [n_slots, {K}, {C + 1}, {C + 1}] tensor on {device}")
-    return counts
+    return _launch(_CALIBRATION, pred, conf, labels, prep, bins, cal, slots)
 
 
 @torch.no_grad()
@@ -540,23 +533,7 @@ def selective(pred, conf, labels, prep, bins=None, counts=None, slots=None):
     counts[s, k, row, col] += 1 for every pixel whose label is not ignored, row / col as in `confusion` (index C = outside [0, C)), k as in `calibration`
     (min(K - 1, int(float32(c) * float32(K))) of the confidence clamped to [0, 1], NaN -> 0).  `bins` = K defaults to counts', or to 15; `slots` defaults
     to 0 .. B - 1 (per-image counts); `counts` defaults to a zeroed buffer of max(slots) + 1 slots."""
-    pred = _check_pred(pred)
-    conf = _check_confmap(conf, pred)
-    B, H, W = (int(v) for v in pred.shape)
-    C = _check_selective_classes(prep.num_classes)
-    if bins is None:
-        bins = int(counts.shape[1]) if isinstance(counts, torch.Tensor) and counts.dim() == 4 else DEFAULT_BINS
-    K = _check_bins(bins)
-    with torch.cuda.device(pred.device):
-        largs = prep.launch_args(labels, B, H, W, pred.device)
-        if counts is None:
-            n_slots = B if slots is None else max(int(s) for s in slots) + 1
-            counts = torch.zeros(n_slots, K, C + 1, C + 1, dtype=torch.int64, device=pred.device)
-        _check_selective_counts(counts, K, C, pred.device)
-        tab = _slot_args(slots, B, counts.shape[0])
-        lib.call("mmsa_eval_selective", pred.data_ptr(), conf.data_ptr(), largs[0], B, H, W, largs[1], largs[2], largs[3], C, largs[4], largs[5], tab,
-                 counts.shape[0], K, counts.data_ptr(), ops._stream())
-    return counts
+    return _launch(_SELECTIVE, pred, conf, labels, prep, bins, counts, slots)
 
 
 @torch.no_grad()
@@ -592,15 +569,17 @@ def slide_argmax_eval(lg, n, windows, out, B, H, W, hc, wc, unc, labels, prep, c
     if C != prep.num_classes:
         raise RuntimeError(f"mmsa.evaluate: the head has {C} classes, the LabelPrep {prep.num_classes}")
     largs = prep.launch_args(labels, B, H, W, lg.device)
-    _check_counts(counts, C, lg.device)
+    _check_buffer(counts, "counts", (C + 1, C + 1), lg.device)
     tab = _slot_args(slots, B, counts.shape[0])
     lib.call("mmsa_slide_argmax_eval", lg.data_ptr(), n, C, lg.shape[2], lg.shape[3], windows, None if out is None else out.data_ptr(), B, H, W, hc, wc,
              unc.data_ptr(), largs[0], largs[1], largs[2], largs[3], largs[4], largs[5], tab, counts.shape[0], counts.data_ptr(), ops._stream())
 
 
 class _SlotOwner:
-    """The slot bookkeeping of a buffer with one slot per image or per case: Evaluator's counts and Calibration's bins."""
-    _who, _read, _one = "Evaluator", "areas()", "an Evaluator"
+    """A pass's int64 [n_slots, ...] buffer with one slot per image or per case, and its bookkeeping: Evaluator's and SelectiveEvaluator's counts,
+    Calibration's bins.  A subclass names itself (`_who`, `_one`, `_read`), its pass and the public attribute that holds the buffer (`_attr`)."""
+    _who, _read, _one, _attr, _pass = "Evaluator", "areas()", "an Evaluator", "counts", _CONFUSION
+    n_bins = None               # the passes with a confidence map set it
 
     def _init_slots(self, cases, images):
         self.cases = None if cases is None else list(cases)
@@ -608,6 +587,52 @@ class _SlotOwner:
         if self.n_slots < 1:
             raise ValueError(f"mmsa.{self._who}: at least one slot")
         self.used = 0           # per-image mode: slots taken so far
+
+    def _init_buffer(self, device):
+        """The buffer is made by the first add, or here where a device is given."""
+        setattr(self, self._attr, None)
+        if device is not None:
+            self._buffer(torch.device(device))
+
+    def _trailing(self):
+        return self._pass.shape(self.prep.num_classes, self.n_bins)
+
+    def _buffer(self, device):
+        buf = getattr(self, self._attr)
+        if buf is None:
+            if _capturing(device):
+                raise RuntimeError(f"mmsa.{self._who}: the {self._attr[:-1]} buffer cannot be allocated during a graph capture: construct the {self._who} "
+                                   "with device=")
+            buf = torch.zeros(self.n_slots, *self._trailing(), dtype=torch.int64, device=device)
+            setattr(self, self._attr, buf)
+        elif buf.device != device:
+            raise RuntimeError(f"mmsa.{self._who}: the {self._attr} live on {buf.device}, this batch on {device}")
+        return buf
+
+    def _add(self, pred, conf, labels, case, slots):
+        """One launch of the pass into the buffer; the slots are taken once it has gone through."""
+        pred = _check_pred(pred)
+        if self._pass.k_axis is not None:
+            _check_confmap(conf, pred)
+        with torch.cuda.device(pred.device):
+            buf = self._buffer(pred.device)
+        _launch(self._pass, pred, conf, labels, self.prep, self.n_bins, buf, self.slots_for(pred.shape[0], case, slots))
+        self._taken(pred.shape[0], case, slots)
+        return self
+
+    def reset(self):
+        buf = getattr(self, self._attr)
+        if buf is not None:
+            buf.zero_()
+        self.used = 0
+
+    def _host(self):
+        """The buffer on the host, int64 numpy [n, ...]: n = images added so far (per-image mode) / cases."""
+        buf = getattr(self, self._attr)
+        if buf is None:
+            return np.zeros((0 if self.cases is None else self.n_slots, *self._trailing()), dtype=np.int64)
+        h = buf.cpu().numpy()
+        return h[:self.used] if self.cases is None else h
 
     def slots_for(self, B, case=None, slots=None):
         """The count slots the NEXT batch of B images gets (nothing is taken yet: add / add_fused take them once their launch has gone through).
@@ -642,28 +667,11 @@ class Evaluator(_SlotOwner):
     def __init__(self, prep, cases=None, images=MAX_IMAGES, device=None):
         self.prep = prep
         self._init_slots(cases, images)
-        self.counts = None
-        if device is not None:
-            self._buffer(torch.device(device))
-
-    def _buffer(self, device):
-        if self.counts is None:
-            if _capturing(device):
-                raise RuntimeError("mmsa.Evaluator: the count buffer cannot be allocated during a graph capture: construct the Evaluator with device=")
-            C = self.prep.num_classes
-            self.counts = torch.zeros(self.n_slots, C + 1, C + 1, dtype=torch.int64, device=device)
-        elif self.counts.device != device:
-            raise RuntimeError(f"mmsa.Evaluator: the counts live on {self.counts.device}, this batch on {device}")
-        return self.counts
+        self._init_buffer(device)
 
     def add(self, pred, labels, case=None, slots=None):
         """Count a batch of stored class maps (one launch)."""
-        pred = _check_pred(pred)
-        with torch.cuda.device(pred.device):
-            counts = self._buffer(pred.device)
-        confusion(pred, labels, self.prep, counts=counts, slots=self.slots_for(pred.shape[0], case, slots))
-        self._taken(pred.shape[0], case, slots)
-        return self
+        return self._add(pred, None, labels, case, slots)
 
     def add_fused(self, lg, plan, out, unc, labels, case=None, slots=None):
         """Class map + counts in one launch (mmsa.inference's class-map calls with labels= / evaluator=); `plan`: the frame's mmsa.inference.MapPlan."""
@@ -673,18 +681,9 @@ class Evaluator(_SlotOwner):
         self._taken(plan.B, case, slots)
         return self
 
-    def reset(self):
-        if self.counts is not None:
-            self.counts.zero_()
-        self.used = 0
-
     def host_counts(self):
         """The counts on the host (the ONE device-to-host copy of an evaluation): int64 numpy [n, C + 1, C + 1], n = images added so far / cases."""
-        C = self.prep.num_classes
-        if self.counts is None:
-            return np.zeros((0 if self.cases is None else self.n_slots, C + 1, C + 1), dtype=np.int64)
-        c = self.counts.cpu().numpy()
-        return c[:self.used] if self.cases is None else c
+        return self._host()
 
     def areas(self):
         """(area_intersect, area_union, area_pred_label, area_label): int64 numpy [n, C] each, row per image (per case with cases=)."""
@@ -708,46 +707,21 @@ class Calibration(_SlotOwner):
     have the buffer before the first add, and `slots=` to add(), for a call that is captured in a HIP graph.  Only host_bins() copies anything to the
     host: 3 K integers per slot; every metric is formed from them in float64, of one slot (`slot=` index or case name) or of the sum over all slots
     (`slot=None`), and raises OverflowError once a bin holds 2^39 pixels.  Across ranks: mmsa.dist.allreduce_counts(cal.bins)."""
-    _who, _read, _one = "Calibration", "host_bins()", "a Calibration"
+    _who, _read, _one, _attr, _pass = "Calibration", "host_bins()", "a Calibration", "bins", _CALIBRATION
 
     def __init__(self, prep, bins=DEFAULT_BINS, cases=None, images=MAX_IMAGES, device=None):
         self.prep = prep
         self.n_bins = _check_bins(bins)
         self._init_slots(cases, images)
-        self.bins = None
-        if device is not None:
-            self._buffer(torch.device(device))
-
-    def _buffer(self, device):
-        if self.bins is None:
-            if _capturing(device):
-                raise RuntimeError("mmsa.Calibration: the bin buffer cannot be allocated during a graph capture: construct the Calibration with device=")
-            self.bins = torch.zeros(self.n_slots, 3, self.n_bins, dtype=torch.int64, device=device)
-        elif self.bins.device != device:
-            raise RuntimeError(f"mmsa.Calibration: the bins live on {self.bins.device}, this batch on {device}")
-        return self.bins
+        self._init_buffer(device)
 
     def add(self, pred, conf, labels, case=None, slots=None):
         """Bin a batch of stored class maps and their confidence maps (one launch; no host sync, no allocation once the buffer exists)."""
-        pred = _check_pred(pred)
-        conf = _check_confmap(conf, pred)
-        with torch.cuda.device(pred.device):
-            cal = self._buffer(pred.device)
-        calibration(pred, conf, labels, self.prep, bins=self.n_bins, cal=cal, slots=self.slots_for(pred.shape[0], case, slots))
-        self._taken(pred.shape[0], case, slots)
-        return self
-
-    def reset(self):
-        if self.bins is not None:
-            self.bins.zero_()
-        self.used = 0
+        return self._add(pred, conf, labels, case, slots)
 
     def host_bins(self):
         """The bins on the host (the ONE device-to-host copy of a calibration run): int64 numpy [n, 3, K], n = images added so far / cases."""
-        if self.bins is None:
-            return np.zeros((0 if self.cases is None else self.n_slots, 3, self.n_bins), dtype=np.int64)
-        b = self.bins.cpu().numpy()
-        return b[:self.used] if self.cases is None else b
+        return self._host()
 
     def _of(self, slot):
         """int64 [3, K] of one slot (index or case name), or of the sum over every slot.  A slot at its capacity raises here, before a sum over slots
@@ -789,7 +763,7 @@ class SelectiveEvaluator(_SlotOwner):
     as for Calibration.  Only host_counts() copies anything to the host (81 KB per slot at 25 classes and 15 bins); everything else is formed from those
     integers: `min_bin=` keeps the bins min_bin .. K - 1 (the pixels `abstain` leaves in the map), and at min_bin=0 metrics / summary / areas are the
     Evaluator's.  A buffer above 1 GiB is refused.  Across ranks: mmsa.dist.allreduce_counts(se.counts)."""
-    _who, _read, _one = "SelectiveEvaluator", "host_counts()", "a SelectiveEvaluator"
+    _who, _read, _one, _attr, _pass = "SelectiveEvaluator", "host_counts()", "a SelectiveEvaluator", "counts", _SELECTIVE
 
     def __init__(self, prep, bins=DEFAULT_BINS, cases=None, images=MAX_IMAGES, device=None):
         self.prep = prep
@@ -800,43 +774,15 @@ class SelectiveEvaluator(_SlotOwner):
         if nbytes > MAX_SELECTIVE_BYTES:
             raise ValueError(f"mmsa.SelectiveEvaluator: {self.n_slots} slots x {self.n_bins} bins x {C + 1} x {C + 1} int64 counts are {nbytes} bytes, above "
                              f"the {MAX_SELECTIVE_BYTES} (1 GiB) a count buffer may take: fewer slots (cases= or images=) or fewer bins")
-        self.counts = None
-        if device is not None:
-            self._buffer(torch.device(device))
-
-    def _buffer(self, device):
-        if self.counts is None:
-            if _capturing(device):
-                raise RuntimeError("mmsa.SelectiveEvaluator: the count buffer cannot be allocated during a graph capture: construct the SelectiveEvaluator "
-                                   "with device=")
-            C = self.prep.num_classes
-            self.counts = torch.zeros(self.n_slots, self.n_bins, C + 1, C + 1, dtype=torch.int64, device=device)
-        elif self.counts.device != device:
-            raise RuntimeError(f"mmsa.SelectiveEvaluator: the counts live on {self.counts.device}, this batch on {device}")
-        return self.counts
+        self._init_buffer(device)
 
     def add(self, pred, conf, labels, case=None, slots=None):
         """Count a batch of stored class maps and their confidence maps (one launch; no host sync, no allocation once the buffer exists)."""
-        pred = _check_pred(pred)
-        conf = _check_confmap(conf, pred)
-        with torch.cuda.device(pred.device):
-            counts = self._buffer(pred.device)
-        selective(pred, conf, labels, self.prep, bins=self.n_bins, counts=counts, slots=self.slots_for(pred.shape[0], case, slots))
-        self._taken(pred.shape[0], case, slots)
-        return self
-
-    def reset(self):
-        if self.counts is not None:
-            self.counts.zero_()
-        self.used = 0
+        return self._add(pred, conf, labels, case, slots)
 
     def host_counts(self):
         """The counts on the host (the ONE device-to-host copy of a run): int64 numpy [n, K, C + 1, C + 1], n = images added so far / cases."""
-        C = self.prep.num_classes
-        if self.counts is None:
-            return np.zeros((0 if self.cases is None else self.n_slots, self.n_bins, C + 1, C + 1), dtype=np.int64)
-        c = self.counts.cpu().numpy()
-        return c[:self.used] if self.cases is None else c
+        return self._host()
 
     def _of(self, slot):
         """int64 [K, C + 1, C + 1] of one slot (index or case name), or of the sum over every slot."""
