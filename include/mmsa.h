@@ -482,6 +482,35 @@ int mmsa_eval_selective(const unsigned char* pred, const float* conf, const unsi
                         mmsa_stream_t stream);
 int mmsa_abstain_u8(const unsigned char* pred, const float* conf, long n, int bins, int min_bin, unsigned char* out, mmsa_stream_t stream);
 
+/* --- temperature scaling (the reference has no such step): the confidence of softmax(x / T) in place of softmax(x), and the fit of T.
+ *     The tempered softmax is the confidence maps' softmax with ONE more float32 product: e_c = expf((x_c - m) * it), it = float32(1 / float64(T)) made by
+ *     the caller (finite and > 0, else MMSA_ERR_ARG); m, the sum in class order and the division are unchanged, and conf = expf((m - m) * it) / s.  No
+ *     contraction.  With it == 1.0f the product is exact: each `_t` entry then writes the bytes of its sibling.  T > 0 never changes a class map.
+ *   APPLY: each `_t` entry is its sibling above with `inv_temperature` before `stream`: same arguments, same checks, same class map, the same choice of
+ *     kernel form (slide_argmax_conf_t: the per-lane LDS column up to 64 classes, the second pass from 65 on; slide_argmax_resized_conf_t: slots / scanning).
+ *   FIT, temperature_sweep_nchw: ONE pass over a logits canvas [B, C, H, W] (what mmsa_bilinear_accum_nchw / mmsa_div_count_nchw leave, at any size or cut)
+ *     for J temperatures at once.  sweep = int64 [n_slots, J, 4, bins], rows total / correct / conf_sum / nll_sum per temperature and confidence bin.  The
+ *     label side -- lut, ymap / xmap (both or neither, clamped into the label map), slots (HOST int [B]) -- is mmsa_eval_confusion_u8's.  Per pixel:
+ *       it takes part iff l = lut[label byte] is a class, l < C (mmsa_eval_calibration's rule);
+ *       m = max_c x_c from x_0; p = the first argmax (mmsa_argmax_nchw's); correct iff p == l;
+ *       for every j: s_j = e_0, s_j += e_c in class order, e_c = expf((x_c - m) * it_j); conf_j = expf((m - m) * it_j) / s_j, clamped and binned as in
+ *         mmsa_eval_calibration (bin k = min(bins - 1, (int)(c * (float)bins)), conf_sum gets floor(c * 2^24));
+ *         nll_j = logf(s_j) - (x_l - m) * it_j (no contraction), nll_sum gets floor(clamp(nll_j, 0, 1024) * 2^20), NaN counting as 1024.
+ *     So rows 0 .. 2 of temperature j are mmsa_eval_calibration's bins of (mmsa_argmax_nchw of the canvas, the maximum over C of
+ *     mmsa_softmax_flip_accum_nchw_t at it_j), bit for bit, and the sum of row 3 over the bins / (2^20 * the sum of row 0) is the mean NLL at T_j.
+ *     The call ADDS into sweep (the caller zeroes it): integer sums, the same bytes whatever the order of arrival; int64 holds 2^33 capped pixels per cell.
+ *     inv_temperatures: HOST float [J], copied into the launch arguments.  logits at any 4-byte aligned address, label at any byte address.
+ *     2 <= C <= 254, 1 <= J <= 16, 1 <= bins <= 64, 1 <= B <= 64. --- */
+int mmsa_slide_argmax_conf_t(const float* logits, int n, int C, int hs, int ws, const int* windows, unsigned char* out, float* conf, int B, int H, int W,
+                             int hc, int wc, int* uncovered, float inv_temperature, mmsa_stream_t stream);
+int mmsa_slide_argmax_resized_conf_t(const float* logits, int n, int C, int hs, int ws, const int* windows, unsigned char* out, float* conf, int B, int H,
+                                     int W, int hc, int wc, int Hd, int Wd, int Hcut, int Wcut, int* uncovered, float inv_temperature, mmsa_stream_t stream);
+int mmsa_softmax_flip_accum_nchw_t(const float* logits, float* acc, int B, int C, int H, int W, int flip, int accumulate, int finish_div,
+                                   float inv_temperature, mmsa_stream_t stream);
+int mmsa_temperature_sweep_nchw(const float* logits, const unsigned char* label, int B, int C, int H, int W, int Hl, int Wl, const unsigned char* lut,
+                                const int* ymap, const int* xmap, const int* slots, int n_slots, const float* inv_temperatures, int J, int bins,
+                                int64_t* sweep, mmsa_stream_t stream);
+
 /* --- the picture of a prediction (segmentation/mmseg_custom/apis/test_bs.py:257-349, the `--show` / `--show-dir` output): `tensor2imgs` (test_bs.py:18-63) on
  *     planes 0..2 of the input tensor -> the crop `img[:h, :w]` (test_bs.py:275-276) -> `show_result` (tools/color_gt_according_palette.py:23-81:
  *     color_seg[seg == label] = color, channels reversed, img * (1 - opacity) + color_seg * opacity, .astype(uint8)), in one pass.

@@ -12,8 +12,10 @@
  * 110: new entries mmsa_softmax_flip_accum_nchw / mmsa_aug_argmax (test-time augmentation: softmax, un-flip, mean over the views and argmax, as a canvas step or in one launch).
  * 111: new entries mmsa_argmax_max_nchw / mmsa_slide_argmax_conf / mmsa_slide_argmax_resized_conf / mmsa_aug_argmax_conf (the confidence map, max class probability, next to every class map).
  * 112: new entry mmsa_eval_calibration (reliability bins of a class map and its confidence map against a label map: total / correct / confidence sum per bin).
- * 113: new entries mmsa_eval_selective / mmsa_abstain_u8 (one confusion matrix per confidence bin of a class map and its confidence map, and the map thresholded by confidence bin). */
+ * 113: new entries mmsa_eval_selective / mmsa_abstain_u8 (one confusion matrix per confidence bin of a class map and its confidence map, and the map thresholded by confidence bin).
+ * 114: new entries mmsa_slide_argmax_conf_t / mmsa_slide_argmax_resized_conf_t / mmsa_softmax_flip_accum_nchw_t (the confidence of softmax(x / T)) and
+ *      mmsa_temperature_sweep_nchw (reliability bins and NLL of a logits canvas for a grid of temperatures in one pass). */
 #ifndef MMSA_VERSION_H
 #define MMSA_VERSION_H
-#define MMSA_ABI_VERSION 113
+#define MMSA_ABI_VERSION 114
 #endif

@@ -14,8 +14,10 @@
 // One lane per pixel of logits [B, C, H, W]: p = softmax over C, written (accumulate = 0) or added to acc [B, C, H, W] at the pixel's mirror image
 // (flip 1: horizontal, x' = W - 1 - x; 2: vertical, y' = H - 1 - y); finish_div > 0: the stored value is divided by it.  The exponentials are evaluated
 // twice (once for the sum, once for p) instead of being kept: the same instructions on the same inputs, the same bits.
-__global__ __launch_bounds__(256) void softmax_flip_accum_kernel(const float* __restrict__ logits, float* __restrict__ acc, int C, int H, int W, int flip,
-                                                                 int accumulate, int finish_div) {
+// TEMP: the softmax of x / T -- every exponential is softmax_px_exp_t with the inverse temperature `it` (softmax_flip_accum_t_kernel, at the end of the file).
+template <bool TEMP>
+__device__ __forceinline__ void softmax_flip_accum_pixel(const float* __restrict__ logits, float* __restrict__ acc, int C, int H, int W, int flip, int accumulate,
+                                                         int finish_div, float it) {
   const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, b = blockIdx.z;
   if (x >= W) return;
   const long HW = (long)H * W;
@@ -24,22 +26,44 @@ __global__ __launch_bounds__(256) void softmax_flip_accum_kernel(const float* __
   float m = xp[0];
   for (int c = 1; c < C; ++c) m = softmax_px_max(m, xp[c * HW]);
   float s = 0.f;
-  for (int c = 0; c < C; ++c) s = softmax_px_sum(s, softmax_px_exp(xp[c * HW], m), c == 0);
+  for (int c = 0; c < C; ++c) s = softmax_px_sum(s, TEMP ? softmax_px_exp_t(xp[c * HW], m, it) : softmax_px_exp(xp[c * HW], m), c == 0);
   for (int c = 0; c < C; ++c) {
-    const float p = softmax_px_prob(softmax_px_exp(xp[c * HW], m), s);
+    const float p = softmax_px_prob(TEMP ? softmax_px_exp_t(xp[c * HW], m, it) : softmax_px_exp(xp[c * HW], m), s);
     float v = softmax_px_accum(accumulate ? ap[c * HW] : 0.f, p, !accumulate);
     if (finish_div > 0) v = softmax_px_mean(v, finish_div);
     ap[c * HW] = v;
   }
 }
 
+__global__ __launch_bounds__(256) void softmax_flip_accum_kernel(const float* __restrict__ logits, float* __restrict__ acc, int C, int H, int W, int flip,
+                                                                 int accumulate, int finish_div) {
+  softmax_flip_accum_pixel<false>(logits, acc, C, H, W, flip, accumulate, finish_div, 1.f);
+}
+
+__global__ void softmax_flip_accum_t_kernel(const float* __restrict__ logits, float* __restrict__ acc, int C, int H, int W, int flip, int accumulate, int finish_div,
+                                            float it);      // at the end of the file, below the kernels that were here before it (profiles/temperature_isa.txt)
+
+// the checks and the launch of mmsa_softmax_flip_accum_nchw and mmsa_softmax_flip_accum_nchw_t (`it` given)
+static int softmax_flip_accum_launch(const char* name, const float* logits, float* acc, int B, int C, int H, int W, int flip, int accumulate, int finish_div,
+                                     hipStream_t stream, const float* it = nullptr) {
+  MMSA_CHECK_ARG(logits && acc && logits != acc && B > 0 && C > 0 && H > 0 && W > 0 && H <= 65535 && B <= 65535, "%s: bad args", name);
+  MMSA_CHECK_ARG(flip >= 0 && flip <= 2 && finish_div >= 0, "%s: flip is 0 (none), 1 (horizontal) or 2 (vertical), finish_div >= 0", name);
+  if (it) MMSA_CHECK_INV_TEMPERATURE(name, *it);
+  if (it)
+    hipLaunchKernelGGL(softmax_flip_accum_t_kernel, dim3(cdiv(W, 256), H, B), dim3(256), 0, stream, logits, acc, C, H, W, flip, accumulate, finish_div, *it);
+  else hipLaunchKernelGGL(softmax_flip_accum_kernel, dim3(cdiv(W, 256), H, B), dim3(256), 0, stream, logits, acc, C, H, W, flip, accumulate, finish_div);
+  MMSA_CHECK_LAUNCH(name);
+  return MMSA_OK;
+}
+
 extern "C" int mmsa_softmax_flip_accum_nchw(const float* logits, float* acc, int B, int C, int H, int W, int flip, int accumulate, int finish_div,
                                             hipStream_t stream) {
-  MMSA_CHECK_ARG(logits && acc && logits != acc && B > 0 && C > 0 && H > 0 && W > 0 && H <= 65535 && B <= 65535, "softmax_flip_accum_nchw: bad args");
-  MMSA_CHECK_ARG(flip >= 0 && flip <= 2 && finish_div >= 0, "softmax_flip_accum_nchw: flip is 0 (none), 1 (horizontal) or 2 (vertical), finish_div >= 0");
-  hipLaunchKernelGGL(softmax_flip_accum_kernel, dim3(cdiv(W, 256), H, B), dim3(256), 0, stream, logits, acc, C, H, W, flip, accumulate, finish_div);
-  MMSA_CHECK_LAUNCH("softmax_flip_accum_nchw");
-  return MMSA_OK;
+  return softmax_flip_accum_launch("softmax_flip_accum_nchw", logits, acc, B, C, H, W, flip, accumulate, finish_div, stream);
+}
+
+extern "C" int mmsa_softmax_flip_accum_nchw_t(const float* logits, float* acc, int B, int C, int H, int W, int flip, int accumulate, int finish_div,
+                                              float inv_temperature, hipStream_t stream) {
+  return softmax_flip_accum_launch("softmax_flip_accum_nchw_t", logits, acc, B, C, H, W, flip, accumulate, finish_div, stream, &inv_temperature);
 }
 
 // ---- the class map of an augmented frame in ONE pass.  A view is what mmsa_slide_argmax_resized takes for one frame: head-resolution logits
@@ -173,4 +197,11 @@ extern "C" int mmsa_aug_argmax_conf(const float* const* logits /* HOST [A] devic
                                     float* conf, int B, int Ho, int Wo, int* uncovered /* device int, zeroed by the caller */, hipStream_t stream) {
   MMSA_CHECK_ARG(conf, "aug_argmax_conf: bad args (conf is NULL)");
   return aug_argmax_launch("aug_argmax_conf", logits, views, A, C, windows, windows_host, total, out, conf, B, Ho, Wo, uncovered, stream);
+}
+
+// ---- the canvas softmax of x / T: softmax_flip_accum_kernel with softmax_px_exp_t (csrc/softmax_px.h), for `probabilities(..., temperature=)` and the canvas
+// path of a tempered confidence map.  At it == 1.0f it is that kernel bit for bit.
+__global__ __launch_bounds__(256) void softmax_flip_accum_t_kernel(const float* __restrict__ logits, float* __restrict__ acc, int C, int H, int W, int flip,
+                                                                   int accumulate, int finish_div, float it) {
+  softmax_flip_accum_pixel<true>(logits, acc, C, H, W, flip, accumulate, finish_div, it);
 }

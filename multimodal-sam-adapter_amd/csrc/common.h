@@ -43,6 +43,10 @@ static inline int mmsa_knob_env(const char* name, int dflt) { const char* v = ge
     }                                                                        \
   } while (0)
 
+// an inverse temperature (the `_t` entries, mmsa_temperature_sweep_nchw) is a finite positive float32; mmsa.evaluate.inv_temperature makes it: float32(1 / float64(T))
+#define MMSA_CHECK_INV_TEMPERATURE(name, it) \
+  MMSA_CHECK_ARG((it) > 0.f && (it) <= 3.402823466e38f, "%s: inv_temperature = %g; a finite value > 0 is expected (float32(1 / T))", name, (double)(it))
+
 // XCD-aware workgroup order (round 4).  The dispatcher deals the workgroups of a launch round-robin to the 8 XCDs in dispatch order (x fastest, then
 // y, z), and each XCD has its own L2: neighbouring workgroups -- the rows above and below in a 3 x 3 stencil, the query blocks that read the same
 // K / V, the queries that gather from the same patch of the value map -- land on eight different L2s and each fetches its own copy (measured: 3 x the

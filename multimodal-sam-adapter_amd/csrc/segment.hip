@@ -130,11 +130,13 @@ __global__ __launch_bounds__(256) void slide_argmax_kernel(const float* __restri
                                                            int H, int W, int hc, int wc, float rh, float rw, WindowTable wt, int* __restrict__ uncovered) {
 #define SLIDE_EVAL 0
 #define SLIDE_CONF 0
+#define SLIDE_TEMP 0
 #define SLIDE_Y blockIdx.y
 #define SLIDE_EXIT return
 #include "slide_pixel.inc"
 #undef SLIDE_EVAL
 #undef SLIDE_CONF
+#undef SLIDE_TEMP
 #undef SLIDE_Y
 #undef SLIDE_EXIT
 }
@@ -157,11 +159,13 @@ __global__ __launch_bounds__(256) void slide_argmax_eval_kernel(const float* __r
   for (int row = (int)blockIdx.y * SLIDE_EVAL_ROWS; row < row1; ++row) {
 #define SLIDE_EVAL 1
 #define SLIDE_CONF 0
+#define SLIDE_TEMP 0
 #define SLIDE_Y row
 #define SLIDE_EXIT continue
 #include "slide_pixel.inc"
 #undef SLIDE_EVAL
 #undef SLIDE_CONF
+#undef SLIDE_TEMP
 #undef SLIDE_Y
 #undef SLIDE_EXIT
   }
@@ -200,10 +204,11 @@ extern "C" int mmsa_slide_argmax_eval(const float* logits, int n, int C, int hs,
 // The pixel (TwoStagePixel: set-up and value; why a tap keeps four windows in registers): csrc/slide_taps.h.
 // CONF: the probability of the predicted class also goes to `conf` float [B, Hcut, Wcut] (0 for a 255 pixel), by a second pass over the classes in the form
 // the first one took (slots or scanning), for the reason slide_pixel.inc gives: the same values again, now that their maximum `best` is known.
-template <bool CONF>
+// TEMP (with CONF): the confidence of softmax(x / T) -- the exponentials are softmax_px_exp_t with the inverse temperature `it`; the map does not depend on it.
+template <bool CONF, bool TEMP = false>
 __device__ __forceinline__ void slide_resized_pixel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out, float* __restrict__ conf,
                                                     int H, int W, int hc, int wc, float rh, float rw, int Hcut, int Wcut, float rh2, float rw2,
-                                                    const WindowTable& wt, int* __restrict__ uncovered) {
+                                                    const WindowTable& wt, int* __restrict__ uncovered, float it = 1.f) {
   const int X = blockIdx.x * 256 + threadIdx.x, Y = blockIdx.y, b = blockIdx.z;
   if (X >= Wcut) return;
   TwoStagePixel px;
@@ -230,13 +235,23 @@ __device__ __forceinline__ void slide_resized_pixel(const float* __restrict__ lo
     }
   }
   out[op] = (unsigned char)bi;
-  if constexpr (CONF) {
+  if constexpr (CONF && !TEMP) {
     float s = 0.f;
     if (slots)
       for (int c = 0; c < C; ++c) s = softmax_px_sum(s, softmax_px_exp(two_stage_value<false>(px, wt, b, logits, C, c, hs, ws, hc, wc, rh, rw), best), c == 0);
     else
       for (int c = 0; c < C; ++c) s = softmax_px_sum(s, softmax_px_exp(two_stage_value<true>(px, wt, b, logits, C, c, hs, ws, hc, wc, rh, rw), best), c == 0);
     conf[op] = softmax_px_prob(softmax_px_exp(best, best), s);
+  }
+  // The tempered block is written out next to the untempered one, not folded into it with `TEMP ? ... : ...` on a named value: that form, the same
+  // arithmetic, gave slide_argmax_resized_conf_kernel another instruction stream (profiles/temperature_isa.txt); this one leaves it as it was.
+  if constexpr (CONF && TEMP) {
+    float s = 0.f;
+    if (slots)
+      for (int c = 0; c < C; ++c) s = softmax_px_sum(s, softmax_px_exp_t(two_stage_value<false>(px, wt, b, logits, C, c, hs, ws, hc, wc, rh, rw), best, it), c == 0);
+    else
+      for (int c = 0; c < C; ++c) s = softmax_px_sum(s, softmax_px_exp_t(two_stage_value<true>(px, wt, b, logits, C, c, hs, ws, hc, wc, rh, rw), best, it), c == 0);
+    conf[op] = softmax_px_prob(softmax_px_exp_t(best, best, it), s);
   }
 }
 
@@ -295,11 +310,13 @@ __global__ __launch_bounds__(256) void slide_argmax_conf_kernel(const float* __r
                                                                 int* __restrict__ uncovered) {
 #define SLIDE_EVAL 0
 #define SLIDE_CONF 1
+#define SLIDE_TEMP 0
 #define SLIDE_Y blockIdx.y
 #define SLIDE_EXIT return
 #include "slide_pixel.inc"
 #undef SLIDE_EVAL
 #undef SLIDE_CONF
+#undef SLIDE_TEMP
 #undef SLIDE_Y
 #undef SLIDE_EXIT
 }
@@ -311,19 +328,33 @@ __global__ __launch_bounds__(256) void slide_argmax_conf_lds_kernel(const float*
   float* conf_col = conf_lds + threadIdx.x;      // private to the lane: no barrier
 #define SLIDE_EVAL 0
 #define SLIDE_CONF 2
+#define SLIDE_TEMP 0
 #define SLIDE_Y blockIdx.y
 #define SLIDE_EXIT return
 #include "slide_pixel.inc"
 #undef SLIDE_EVAL
 #undef SLIDE_CONF
+#undef SLIDE_TEMP
 #undef SLIDE_Y
 #undef SLIDE_EXIT
 }
 
-// the checks and the launch of mmsa_slide_argmax and mmsa_slide_argmax_conf; `conf` given: the LDS-column form where it fits, the second-pass form otherwise
+// The tempered siblings of the three confidence kernels (the confidence of softmax(x / T), `it` = the inverse temperature): defined at the END of the file, below
+// every kernel that was here before them, so that those keep their place and their instruction streams (profiles/temperature_isa.txt).
+__global__ void slide_argmax_conf_t_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out, float* __restrict__ conf, int H,
+                                           int W, int hc, int wc, float rh, float rw, WindowTable wt, int* __restrict__ uncovered, float it);
+__global__ void slide_argmax_conf_lds_t_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out, float* __restrict__ conf,
+                                               int H, int W, int hc, int wc, float rh, float rw, WindowTable wt, int* __restrict__ uncovered, float it);
+__global__ void slide_argmax_resized_conf_t_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out, float* __restrict__ conf,
+                                                   int H, int W, int hc, int wc, float rh, float rw, int Hcut, int Wcut, float rh2, float rw2, WindowTable wt,
+                                                   int* __restrict__ uncovered, float it);
+
+// the checks and the launch of mmsa_slide_argmax, mmsa_slide_argmax_conf and mmsa_slide_argmax_conf_t; `conf` given: the LDS-column form where it fits, the
+// second-pass form otherwise; `it` given (with `conf`): the tempered sibling of that form
 static int slide_argmax_launch(const char* name, const float* logits, int n, int C, int hs, int ws, const int* windows, unsigned char* out, float* conf, int B, int H,
-                               int W, int hc, int wc, int* uncovered, hipStream_t stream) {
+                               int W, int hc, int wc, int* uncovered, hipStream_t stream, const float* it = nullptr) {
   MMSA_CHECK_ARG(logits && out && uncovered && C > 0 && C <= 255 && hs > 0 && ws > 0 && hc > 0 && wc > 0 && B > 0 && H <= 65535 && B <= 65535, "%s: bad args", name);
+  if (it) MMSA_CHECK_INV_TEMPERATURE(name, *it);
   WindowTable wt;
   int rc = fill_windows(wt, windows, n, B, H, W, hc, wc, name);
   if (rc) return rc;
@@ -335,6 +366,11 @@ static int slide_argmax_launch(const char* name, const float* logits, int n, int
   const dim3 grid(cdiv(W, 256), H, B);
   const float rh = (float)hs / (float)hc, rw = (float)ws / (float)wc;
   if (!conf) hipLaunchKernelGGL(slide_argmax_kernel, grid, dim3(256), 0, stream, logits, C, hs, ws, out, H, W, hc, wc, rh, rw, wt, uncovered);
+  else if (it && lds)
+    hipLaunchKernelGGL(slide_argmax_conf_lds_t_kernel, grid, dim3(256), (size_t)C * 256 * sizeof(float), stream, logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, wt,
+                       uncovered, *it);
+  else if (it)
+    hipLaunchKernelGGL(slide_argmax_conf_t_kernel, grid, dim3(256), 0, stream, logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, wt, uncovered, *it);
   else if (lds)
     hipLaunchKernelGGL(slide_argmax_conf_lds_kernel, grid, dim3(256), (size_t)C * 256 * sizeof(float), stream, logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, wt,
                        uncovered);
@@ -361,10 +397,13 @@ __global__ __launch_bounds__(256) void slide_argmax_resized_conf_kernel(const fl
   slide_resized_pixel<true>(logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, Hcut, Wcut, rh2, rw2, wt, uncovered);
 }
 
-// the checks and the launch of mmsa_slide_argmax_resized and mmsa_slide_argmax_resized_conf; `conf` given: slide_argmax_resized_conf_kernel
+// the checks and the launch of mmsa_slide_argmax_resized, mmsa_slide_argmax_resized_conf and mmsa_slide_argmax_resized_conf_t; `conf` given:
+// slide_argmax_resized_conf_kernel; `it` given (with `conf`): slide_argmax_resized_conf_t_kernel
 static int slide_argmax_resized_launch(const char* name, const float* logits, int n, int C, int hs, int ws, const int* windows, unsigned char* out, float* conf, int B,
-                                       int H, int W, int hc, int wc, int Hd, int Wd, int Hcut, int Wcut, int* uncovered, hipStream_t stream) {
+                                       int H, int W, int hc, int wc, int Hd, int Wd, int Hcut, int Wcut, int* uncovered, hipStream_t stream,
+                                       const float* it = nullptr) {
   MMSA_CHECK_ARG(logits && out && uncovered && C > 0 && C <= 255 && hs > 0 && ws > 0 && hc > 0 && wc > 0 && B > 0 && H > 0 && W > 0 && B <= 65535, "%s: bad args", name);
+  if (it) MMSA_CHECK_INV_TEMPERATURE(name, *it);
   MMSA_CHECK_ARG(Hd > 0 && Wd > 0 && Hcut > 0 && Wcut > 0 && Hcut <= Hd && Wcut <= Wd && Hcut <= 65535,
                  "%s: the cut %dx%d must lie inside the target %dx%d (and have at most 65535 rows)", name, Hcut, Wcut, Hd, Wd);
   WindowTable wt;
@@ -372,7 +411,10 @@ static int slide_argmax_resized_launch(const char* name, const float* logits, in
   if (rc) return rc;
   const dim3 grid(cdiv(Wcut, 256), Hcut, B);
   const float rh = (float)hs / (float)hc, rw = (float)ws / (float)wc, rh2 = (float)H / (float)Hd, rw2 = (float)W / (float)Wd;
-  if (conf)
+  if (conf && it)
+    hipLaunchKernelGGL(slide_argmax_resized_conf_t_kernel, grid, dim3(256), 0, stream, logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, Hcut, Wcut, rh2, rw2, wt,
+                       uncovered, *it);
+  else if (conf)
     hipLaunchKernelGGL(slide_argmax_resized_conf_kernel, grid, dim3(256), 0, stream, logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, Hcut, Wcut, rh2, rw2, wt,
                        uncovered);
   else hipLaunchKernelGGL(slide_argmax_resized_kernel, grid, dim3(256), 0, stream, logits, C, hs, ws, out, H, W, hc, wc, rh, rw, Hcut, Wcut, rh2, rw2, wt, uncovered);
@@ -391,4 +433,62 @@ extern "C" int mmsa_slide_argmax_resized_conf(const float* logits, int n, int C,
                                               int* uncovered /* device int, zeroed by the caller */, hipStream_t stream) {
   MMSA_CHECK_ARG(conf, "slide_argmax_resized_conf: bad args");
   return slide_argmax_resized_launch("slide_argmax_resized_conf", logits, n, C, hs, ws, windows, out, conf, B, H, W, hc, wc, Hd, Wd, Hcut, Wcut, uncovered, stream);
+}
+
+// ---- tempered confidence: the three confidence kernels above with softmax(x / T) in place of softmax(x) -- `it` = float32(1 / float64(T)) from the host, and
+// every exponential is softmax_px_exp_t (csrc/softmax_px.h: ONE more float32 product, exact at it == 1.0f, where these kernels are their siblings bit for bit).
+// The class map does not depend on T > 0.  They stand here, at the end, for the reason given above argmax_max_nchw_kernel.
+__global__ __launch_bounds__(256) void slide_argmax_conf_t_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
+                                                                  float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, WindowTable wt,
+                                                                  int* __restrict__ uncovered, float it) {
+#define SLIDE_EVAL 0
+#define SLIDE_CONF 1
+#define SLIDE_TEMP 1
+#define SLIDE_Y blockIdx.y
+#define SLIDE_EXIT return
+#include "slide_pixel.inc"
+#undef SLIDE_EVAL
+#undef SLIDE_CONF
+#undef SLIDE_TEMP
+#undef SLIDE_Y
+#undef SLIDE_EXIT
+}
+
+__global__ __launch_bounds__(256) void slide_argmax_conf_lds_t_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
+                                                                      float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, WindowTable wt,
+                                                                      int* __restrict__ uncovered, float it) {
+  extern __shared__ float conf_lds[];
+  float* conf_col = conf_lds + threadIdx.x;      // private to the lane: no barrier
+#define SLIDE_EVAL 0
+#define SLIDE_CONF 2
+#define SLIDE_TEMP 1
+#define SLIDE_Y blockIdx.y
+#define SLIDE_EXIT return
+#include "slide_pixel.inc"
+#undef SLIDE_EVAL
+#undef SLIDE_CONF
+#undef SLIDE_TEMP
+#undef SLIDE_Y
+#undef SLIDE_EXIT
+}
+
+__global__ __launch_bounds__(256) void slide_argmax_resized_conf_t_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
+                                                                          float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, int Hcut,
+                                                                          int Wcut, float rh2, float rw2, WindowTable wt, int* __restrict__ uncovered, float it) {
+  slide_resized_pixel<true, true>(logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, Hcut, Wcut, rh2, rw2, wt, uncovered, it);
+}
+
+extern "C" int mmsa_slide_argmax_conf_t(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out, float* conf,
+                                        int B, int H, int W, int hc, int wc, int* uncovered /* device int, zeroed by the caller */, float inv_temperature,
+                                        hipStream_t stream) {
+  MMSA_CHECK_ARG(conf, "slide_argmax_conf_t: bad args");
+  return slide_argmax_launch("slide_argmax_conf_t", logits, n, C, hs, ws, windows, out, conf, B, H, W, hc, wc, uncovered, stream, &inv_temperature);
+}
+
+extern "C" int mmsa_slide_argmax_resized_conf_t(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out,
+                                                float* conf, int B, int H, int W, int hc, int wc, int Hd, int Wd, int Hcut, int Wcut,
+                                                int* uncovered /* device int, zeroed by the caller */, float inv_temperature, hipStream_t stream) {
+  MMSA_CHECK_ARG(conf, "slide_argmax_resized_conf_t: bad args");
+  return slide_argmax_resized_launch("slide_argmax_resized_conf_t", logits, n, C, hs, ws, windows, out, conf, B, H, W, hc, wc, Hd, Wd, Hcut, Wcut, uncovered, stream,
+                                     &inv_temperature);
 }

@@ -8,10 +8,17 @@
 //                 same bits): no LDS, no limit on C beyond the map's.  An uncovered pixel (map 255) gets 0.
 //   SLIDE_CONF 2: slide_argmax_conf_lds_kernel -- the same, but the first pass keeps the pixel's values in the per-lane LDS column conf_col[c * 256], as
 //                 aug_argmax_kernel does, and the second pass reads them back: the faster form (segment.hip has the figures), for C * 256 floats <= 64 KiB.
+//   SLIDE_TEMP 1: (with SLIDE_CONF 1 / 2) slide_argmax_conf_t_kernel / slide_argmax_conf_lds_t_kernel -- the confidence of softmax(x / T): the exponentials are
+//                 softmax_px_exp_t with the launch's inverse temperature `it`; the map does not depend on it.  SLIDE_TEMP 0: softmax_px_exp, no `it` in scope.
 // SLIDE_Y is the pixel's row: blockIdx.y in the first kernel, the row variable of the second kernel's loop over its workgroup's rows.
 // SLIDE_EXIT leaves the body: `return` in the first kernel, `continue` with the next row in the second, which still has its histogram to flush.
 // SLIDE_EXIT MUST NOT be used inside a loop of this body: there `continue` would go on with that loop in the second kernel only, where `return`
 // leaves the first (every use below is at the body's top level).  In scope: logits, C, hs, ws, out, H, W, hc, wc, rh, rw, wt, uncovered (and conf).
+#if SLIDE_TEMP
+#define SLIDE_EXP(v, m) softmax_px_exp_t(v, m, it)
+#else
+#define SLIDE_EXP(v, m) softmax_px_exp(v, m)
+#endif
   const int x = blockIdx.x * 256 + threadIdx.x, y = SLIDE_Y, b = blockIdx.z;
   if (x >= W) SLIDE_EXIT;
 #if SLIDE_EVAL
@@ -86,8 +93,8 @@
 #endif
 #if SLIDE_CONF == 2
   float s = 0.f;
-  for (int c = 0; c < C; ++c) s = softmax_px_sum(s, softmax_px_exp(conf_col[c * 256], best), c == 0);
-  conf[((long)b * H + y) * W + x] = softmax_px_prob(softmax_px_exp(best, best), s);
+  for (int c = 0; c < C; ++c) s = softmax_px_sum(s, SLIDE_EXP(conf_col[c * 256], best), c == 0);
+  conf[((long)b * H + y) * W + x] = softmax_px_prob(SLIDE_EXP(best, best), s);
 #elif SLIDE_CONF
   float s = 0.f;
   for (int c = 0; c < C; ++c) {
@@ -101,7 +108,8 @@
         acc = q == 0 ? v : acc + v;
       }
     }
-    s = softmax_px_sum(s, softmax_px_exp(acc / cnt, best), c == 0);
+    s = softmax_px_sum(s, SLIDE_EXP(acc / cnt, best), c == 0);
   }
-  conf[((long)b * H + y) * W + x] = softmax_px_prob(softmax_px_exp(best, best), s);      // e_c / s at the first maximum: the largest probability
+  conf[((long)b * H + y) * W + x] = softmax_px_prob(SLIDE_EXP(best, best), s);      // e_c / s at the first maximum: the largest probability
 #endif
+#undef SLIDE_EXP

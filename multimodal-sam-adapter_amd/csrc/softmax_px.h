@@ -3,6 +3,10 @@
 // ED:538-541).  Both kernels of csrc/augment.hip are made of these pieces and nothing else, so the canvas path and the one-pass class map round alike:
 //   m   = max_c x_c                               softmax_px_max, in class order from m = x_0
 //   e_c = expf(x_c - m)                           softmax_px_exp  (ocml's expf, not the hardware approximation: it is the same instruction sequence wherever it is inlined)
+//   e_c = expf((x_c - m) * it)                    softmax_px_exp_t: the softmax of x / T, `it` = float32(1 / float64(T)) made on the host (mmsa.evaluate.inv_temperature);
+//                                                 ONE float32 product behind the subtraction, no contraction.  With it == 1.0f the product is exact, so a
+//                                                 tempered kernel is bit for bit its untempered sibling; max, sum and division do not change, and the
+//                                                 confidence is softmax_px_prob(softmax_px_exp_t(m, m, it), s)
 //   s   = e_0; s += e_c for c = 1 .. C-1          softmax_px_sum, in class order
 //   p_c = e_c / s                                 softmax_px_prob
 //   acc_c = p_c (first view) | acc_c + p_c        softmax_px_accum, in view order
@@ -13,6 +17,7 @@
 
 __device__ __forceinline__ float softmax_px_max(float m, float x) { return x > m ? x : m; }
 __device__ __forceinline__ float softmax_px_exp(float x, float m) { return expf(x - m); }
+__device__ __forceinline__ float softmax_px_exp_t(float x, float m, float it) { return expf((x - m) * it); }
 __device__ __forceinline__ float softmax_px_sum(float s, float e, bool first) { return first ? e : s + e; }
 __device__ __forceinline__ float softmax_px_prob(float e, float s) { return e / s; }
 __device__ __forceinline__ float softmax_px_accum(float acc, float p, bool first) { return first ? p : acc + p; }

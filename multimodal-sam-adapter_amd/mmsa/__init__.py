@@ -16,6 +16,7 @@ from . import evaluate  # noqa: F401  (confusion counts and mIoU on device: Labe
 from .evaluate import Evaluator, LabelPrep, confusion
 from .evaluate import Calibration, calibration  # noqa: F401  (reliability bins, ECE and risk-coverage of the confidence map on device)
 from .evaluate import SelectiveEvaluator, selective, abstain  # noqa: F401  (confusion counts per confidence bin: mIoU against coverage; the thresholded map)
+from .evaluate import TemperatureSweep, temperature_sweep  # noqa: F401  (temperature scaling: NLL and reliability bins of a logits canvas over a grid of T)
 from . import render  # noqa: F401  (the picture of a prediction on device: palette map over the frame, show_result)
 from .render import Renderer
 from .registry import BACKBONES, HEADS, build_backbone, build_head
@@ -40,5 +41,5 @@ if not _HAVE_MMSEG:     # local registry (no mmseg in the process): nothing to o
 
 __all__ = ["SegformerHead", "HEADS", "build_head", "register_head", "SAMAdapterbimodalMixModNewInTwinConvNEW", "SAMAdapterbimodalMixModNewInTwinConvNEWwithcp",
            "BACKBONES", "build_backbone", "ops", "lib", "inference", "Chains", "Replay", "AttentionRangeError", "OperandRangeError",
-           "preprocess", "Preprocess", "FrameFeeder", "evaluate", "Evaluator", "LabelPrep", "confusion", "Calibration", "calibration", "SelectiveEvaluator", "selective", "abstain", "render", "Renderer",
+           "preprocess", "Preprocess", "FrameFeeder", "evaluate", "Evaluator", "LabelPrep", "confusion", "Calibration", "calibration", "SelectiveEvaluator", "selective", "abstain", "TemperatureSweep", "temperature_sweep", "render", "Renderer",
            "probabilities", "aug_inference", "aug_class_map", "AugPlan", "argmax_max_map"]

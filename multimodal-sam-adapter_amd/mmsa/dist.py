@@ -66,7 +66,7 @@ def allreduce_counts(counts):
     every rank whatever the reduction order.  The slots must mean the same on every rank (cases, or a per-rank image range in a shared buffer).
     Any int64 tensor of sums goes the same way: `Calibration.bins` ([n_slots, 3, K] reliability bins, 360 bytes per slot at 15 bins) is the one collective
     of a multi-GPU calibration run, and `SelectiveEvaluator.counts` ([n_slots, K, C + 1, C + 1] confusion counts per confidence bin) is the one collective
-    of a multi-GPU selective evaluation run."""
+    of a multi-GPU selective evaluation run, and `TemperatureSweep.counts` ([n_slots, J, 4, K]) of a multi-GPU temperature fit."""
     if counts.dtype != torch.int64:
         raise ValueError(f"allreduce_counts: int64 counts expected, got {counts.dtype}")
     if world() > 1:

@@ -21,7 +21,13 @@ Selective evaluation joins the two: `selective` / `SelectiveEvaluator` keep ONE 
 their sum over the bins is the Evaluator's matrix, the rows < C of bin k give Calibration's total[k] / correct[k], and the suffix sums over the bins are
 the confusion counts of the map with the pixels below a confidence threshold taken out.  `selective_metrics_of` forms the reference's metrics at every
 such threshold in float64 -- mIoU against coverage -- and `abstain` (mmsa_abstain_u8) writes the thresholded map (255 where the bin is below) that
-those counts describe, from the same clamp and bin.  The reference has no such step either."""
+those counts describe, from the same clamp and bin.  The reference has no such step either.
+
+Temperature scaling closes the loop from a poor ECE to a better confidence: `temperature_sweep` / `TemperatureSweep` reduce a LOGITS canvas (what
+`mmsa.inference.inference` returns) against the labels, for a whole grid of temperatures in one launch (mmsa_temperature_sweep_nchw, csrc/temperature.hip),
+to int64 [J, 4, K] per slot -- per temperature, Calibration's three rows of the confidence max_c softmax(x / T)_c, and the NLL of the label's class in 20-bit
+fixed point.  `best()` names the grid's minimum of the NLL or of the ECE; a second, narrower `geometric_grid` around it refines; there is no iterative
+optimiser.  The fitted T then goes to `temperature=` of the class-map entries of mmsa.inference, whose confidence maps everything above reads unchanged."""
 import ctypes
 import warnings
 from collections import OrderedDict, namedtuple
@@ -44,6 +50,10 @@ MAX_BINS = 64           # confidence bins per launch (csrc/calibrate.hip CAL_MAX
 DEFAULT_BINS = 15       # the usual reliability diagram
 CONF_ONE = 1 << 24      # the fixed-point unit of a bin's confidence sum: conf_sum = sum of floor(conf * 2^24)
 BIN_CAPACITY = 1 << 39  # participating pixels per bin and slot before the int64 confidence sum can overflow (2^39 * 2^24 = 2^63)
+
+MAX_TEMPERATURES = 16   # temperatures per sweep launch (csrc/temperature.hip SWEEP_MAX_TEMPS: their sums of exponentials live in registers)
+NLL_ONE = 1 << 20       # the fixed-point unit of a sweep's NLL sum: nll_sum = sum of floor(min(max(nll, 0), NLL_CAP) * 2^20)
+NLL_CAP = 1024          # a pixel's NLL is capped here (NaN counts as the cap)
 
 MAX_SELECTIVE_CLASSES = 126        # csrc/eval_hist.h MMSA_EVAL_MAX_CLASSES: one bin's (C + 1)^2 uint32 cells must fit a workgroup's 64 KiB of LDS
 MAX_SELECTIVE_BYTES = 1 << 30      # the largest count buffer a SelectiveEvaluator allocates (64 slots x 64 bins x 127^2 cells x 8 bytes is 528 MB)
@@ -194,6 +204,85 @@ def calibration_summary_of(bins):
     """ECE, MCE, aAcc and the mean confidence in PERCENT, rounded to two places as `summary_of` rounds (np.round(v * 100, 2)); NaN when N == 0."""
     vals = (("ECE", ece_of(bins)), ("MCE", mce_of(bins)), ("aAcc", accuracy_of(bins)), ("mConf", mean_confidence_of(bins)))
     return OrderedDict((k, np.round(v * 100, 2)) for k, v in vals)
+
+
+# ---- temperature scaling: the scalar the kernels take, the grids, and the metrics of a sweep's integers (numpy, float64) ----
+def inv_temperature(T):
+    """The inverse temperature the `_t` kernels and the sweep multiply by: float32(1 / float64(T)) -> a Python float that holds that float32 exactly.
+    T must be finite and positive and the float32 must come out finite and positive (T = 1e-40 or 1e50 do not), else ValueError."""
+    if isinstance(T, bool) or not isinstance(T, (int, float, np.integer, np.floating)):
+        raise ValueError(f"mmsa.evaluate: temperature = {T!r}; a finite number > 0 is expected")
+    t = np.float64(T)
+    if not np.isfinite(t) or not t > 0:
+        raise ValueError(f"mmsa.evaluate: temperature = {T!r}; a finite number > 0 is expected")
+    with np.errstate(over="ignore", under="ignore"):
+        it = np.float32(np.float64(1.0) / t)
+    if not np.isfinite(it) or not it > 0:
+        raise ValueError(f"mmsa.evaluate: temperature = {T!r}: its inverse {float(np.float64(1.0) / t)!r} is not a finite positive float32")
+    return float(it)
+
+
+def geometric_grid(lo, hi, J):
+    """J temperatures from lo to hi with a constant ratio, float64 [J] (J == 1: [lo]); both ends are exact.  0 < lo <= hi, 1 <= J <= 16.  A first sweep
+    over a wide grid and a second over geometric_grid(T / r, T * r, J) around its best() is the whole fit."""
+    if isinstance(J, bool) or not isinstance(J, (int, np.integer)) or not 1 <= int(J) <= MAX_TEMPERATURES:
+        raise ValueError(f"mmsa.evaluate: J = {J!r}; 1..{MAX_TEMPERATURES} temperatures per sweep")
+    lo, hi = np.float64(lo), np.float64(hi)
+    if not (np.isfinite(lo) and np.isfinite(hi) and 0 < lo <= hi):
+        raise ValueError(f"mmsa.evaluate: a temperature grid needs finite 0 < lo <= hi, got {float(lo)!r}, {float(hi)!r}")
+    J = int(J)
+    if J == 1:
+        return np.array([lo], dtype=np.float64)
+    g = lo * (hi / lo) ** (np.arange(J, dtype=np.float64) / (J - 1))
+    g[0], g[-1] = lo, hi
+    return g
+
+
+def _sweep4(sweep):
+    """int64 [J, 4, K] (per temperature: total, correct, conf_sum, nll_sum) of one slot, checked."""
+    s = np.asarray(sweep)
+    if s.ndim != 3 or s.shape[1] != 4 or s.shape[0] < 1 or s.shape[2] < 1 or s.dtype.kind not in "iu":
+        raise ValueError(f"mmsa.evaluate: a temperature sweep is an integer [J, 4, K] array (total, correct, conf_sum, nll_sum per temperature), got {s.dtype} {s.shape}")
+    s = s.astype(np.int64, copy=False)
+    if s.size and int(s.min()) < 0:
+        raise OverflowError("mmsa.evaluate: a cell of the temperature sweep is negative: an int64 sum has wrapped (read and reset() the TemperatureSweep more often)")
+    return s
+
+
+def sweep_bins_of(sweep, j):
+    """Calibration's int64 [3, K] bins at temperature j of an int64 [J, 4, K] sweep: what reliability_of / ece_of / mce_of / risk_coverage_of take."""
+    s = _sweep4(sweep)
+    if isinstance(j, bool) or not isinstance(j, (int, np.integer)) or not 0 <= int(j) < s.shape[0]:
+        raise ValueError(f"mmsa.evaluate: temperature index j = {j!r}; 0..{s.shape[0] - 1}")
+    return s[int(j), :3].copy()
+
+
+def sweep_nll_of(sweep):
+    """The mean NLL per temperature, float64 [J]: sum_k nll_sum / (2^20 * sum_k total); NaN when nothing took part.  Below the float64 mean of the
+    float32 per-pixel values by less than 2^-20 (every term is truncated to 20 fractional bits).  Summed as Python integers."""
+    s = _sweep4(sweep)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.array([np.float64(sum(int(v) for v in one[3])) / (np.float64(NLL_ONE) * np.float64(one[0].sum())) for one in s], dtype=np.float64)
+
+
+def sweep_ece_of(sweep):
+    """`ece_of` per temperature, float64 [J]."""
+    s = _sweep4(sweep)
+    return np.array([ece_of(one[:3]) for one in s], dtype=np.float64)
+
+
+def sweep_best_of(sweep, temperatures, by="nll"):
+    """(T, j) of the grid's minimum of the mean NLL (`by`="nll") or of the ECE ("ece"); the FIRST minimum wins.  ValueError when nothing took part."""
+    if by not in ("nll", "ece"):
+        raise ValueError(f"mmsa.evaluate: best(by={by!r}); 'nll' or 'ece'")
+    v = sweep_nll_of(sweep) if by == "nll" else sweep_ece_of(sweep)
+    t = np.asarray(temperatures, dtype=np.float64)
+    if t.shape != v.shape:
+        raise ValueError(f"mmsa.evaluate: {t.size} temperatures for a sweep of {v.size}")
+    if np.isnan(v).any():
+        raise ValueError("mmsa.evaluate: the sweep has no participating pixel (or a NaN metric): there is no best temperature")
+    j = int(np.argmin(v))
+    return float(t[j]), j
 
 
 # ---- selective evaluation from the per-bin confusion counts (numpy; integers, then float64) ----
@@ -536,6 +625,52 @@ def selective(pred, conf, labels, prep, bins=None, counts=None, slots=None):
     return _launch(_SELECTIVE, pred, conf, labels, prep, bins, counts, slots)
 
 
+def _check_logits(logits):
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda:
+        raise RuntimeError("mmsa.evaluate: logits must be a GPU tensor (there is no CPU path)")
+    if logits.dtype != torch.float32:
+        raise RuntimeError(f"mmsa.evaluate: logits are {logits.dtype}; a float32 logits canvas is expected")
+    if logits.dim() != 4 or not logits.is_contiguous():
+        raise RuntimeError(f"mmsa.evaluate: logits must be a contiguous [B, C, H, W] tensor, got {tuple(logits.shape)}")
+    return logits
+
+
+def _inv_temperatures(temperatures):
+    """`temperatures` (a sequence of 1..16 numbers) -> the inverse temperatures as Python floats, each checked by `inv_temperature`."""
+    ts = [temperatures] if isinstance(temperatures, (int, float, np.integer, np.floating)) and not isinstance(temperatures, bool) else list(temperatures)
+    if not 1 <= len(ts) <= MAX_TEMPERATURES:
+        raise ValueError(f"mmsa.evaluate: {len(ts)} temperatures; 1..{MAX_TEMPERATURES} per sweep (sweep a longer grid in parts)")
+    return [inv_temperature(t) for t in ts]
+
+
+@torch.no_grad()
+def temperature_sweep(logits, labels, prep, temperatures, bins=None, out=None, slots=None):
+    """ADD the sweep of the float32 logits canvas [B, C, H, W] against the raw labels [B, Hl, Wl] over `temperatures` (1..16) into out[slots[b]] (one
+    launch, mmsa_temperature_sweep_nchw) -> out, int64 [n_slots, J, 4, K] on the device: per temperature j, rows total / correct / conf_sum (what
+    `calibration` gives for the canvas path's class map and its confidence at T_j, bit for bit) and nll_sum = the sum of floor(min(max(nll, 0), 1024) * 2^20),
+    nll = -log softmax(x / T_j)[label class].  A pixel takes part iff its transformed label is a class (< C).  `bins` = K defaults to out's, or to 15;
+    `slots` defaults to 0 .. B - 1 (per-image sweeps); `out` defaults to a zeroed buffer of max(slots) + 1 slots."""
+    logits = _check_logits(logits)
+    B, C, H, W = (int(v) for v in logits.shape)
+    if C != prep.num_classes:
+        raise RuntimeError(f"mmsa.evaluate: the logits have {C} classes, the LabelPrep {prep.num_classes}")
+    its = _inv_temperatures(temperatures)
+    J = len(its)
+    if bins is None:
+        bins = int(out.shape[3]) if isinstance(out, torch.Tensor) and out.dim() == 4 else DEFAULT_BINS
+    bins = _check_bins(bins)
+    with torch.cuda.device(logits.device):
+        largs = prep.launch_args(labels, B, H, W, logits.device)
+        if out is None:
+            n_slots = B if slots is None else max(int(s) for s in slots) + 1
+            out = torch.zeros(n_slots, J, 4, bins, dtype=torch.int64, device=logits.device)
+        _check_buffer(out, "out", (J, 4, bins), logits.device)
+        tab = _slot_args(slots, B, out.shape[0])
+        lib.call("mmsa_temperature_sweep_nchw", logits.data_ptr(), largs[0], B, C, H, W, largs[1], largs[2], largs[3], largs[4], largs[5], tab, out.shape[0],
+                 (ctypes.c_float * J)(*its), J, bins, out.data_ptr(), ops._stream())
+    return out
+
+
 @torch.no_grad()
 def abstain(pred, conf, bins, min_bin=None, out=None, threshold=None):
     """The class map thresholded by confidence (one launch, mmsa_abstain_u8) -> uint8 [B, H, W]: pred where the confidence's bin (of `bins`, as in
@@ -821,3 +956,72 @@ class SelectiveEvaluator(_SlotOwner):
     def coverage_curve(self, metric=("mIoU",), slot=None, nan_to_num=None, beta=1):
         """`selective_metrics_of`: coverage and every metric at every threshold k = 0 .. K - 1 (mIoU against coverage)."""
         return selective_metrics_of(self._of(slot), metric=metric, nan_to_num=nan_to_num, beta=beta)
+
+
+class TemperatureSweep(_SlotOwner):
+    """Owns the sweep buffer of a temperature fit, as Calibration owns the reliability bins: int64 [n_slots, J, 4, K] on the device (`.counts`; per
+    temperature the rows total, correct, conf_sum, nll_sum), over the fixed grid `temperatures` (1..16; `geometric_grid`) and `bins` = K confidence bins.
+    `cases` / `images` / `device` and `slots=` of add(): as for Calibration.  add() takes the LOGITS canvas of a batch (mmsa.inference.inference in any test
+    mode, with or without rescale) and its raw labels: one launch, no host sync.  Only host() copies anything to the host: 4 J K integers per slot; every
+    metric is formed from them in float64, of one slot (`slot=` index or case name) or of the sum over all slots.  Across ranks:
+    mmsa.dist.allreduce_counts(sw.counts).  The fit is best(); refining it is a second TemperatureSweep over a narrower grid around it."""
+    _who, _read, _one, _attr = "TemperatureSweep", "host()", "a TemperatureSweep", "counts"
+
+    def __init__(self, prep, temperatures, bins=DEFAULT_BINS, cases=None, images=MAX_IMAGES, device=None):
+        self.prep = prep
+        self.inv_temperatures = _inv_temperatures(temperatures)
+        self.temperatures = np.array([float(t) for t in (temperatures if np.ndim(temperatures) else [temperatures])], dtype=np.float64)
+        self.n_bins = _check_bins(bins)
+        self._init_slots(cases, images)
+        self._init_buffer(device)
+
+    def _trailing(self):
+        return (len(self.inv_temperatures), 4, self.n_bins)
+
+    def add(self, logits, labels, case=None, slots=None):
+        """Sweep a batch's logits canvas [B, C, H, W] against its labels (one launch; no host sync, no allocation once the buffer exists)."""
+        logits = _check_logits(logits)
+        with torch.cuda.device(logits.device):
+            buf = self._buffer(logits.device)
+        temperature_sweep(logits, labels, self.prep, self.temperatures, self.n_bins, buf, self.slots_for(logits.shape[0], case, slots))
+        self._taken(logits.shape[0], case, slots)
+        return self
+
+    def host(self):
+        """The sweeps on the host (the ONE device-to-host copy of a fit): int64 numpy [n, J, 4, K], n = images added so far / cases."""
+        return self._host()
+
+    def _of(self, slot):
+        """int64 [J, 4, K] of one slot (index or case name), or of the sum over every slot."""
+        h = self.host()
+        for one in h:
+            _sweep4(one)
+        return h.sum(0) if slot is None else h[self._slot_index(slot)]
+
+    def bins(self, j, slot=None):
+        """Calibration's int64 [3, K] bins at temperature j: what reliability_of / ece_of / mce_of / risk_coverage_of take."""
+        return sweep_bins_of(self._of(slot), j)
+
+    def nll(self, slot=None):
+        """The mean NLL of the label's class per temperature, float64 [J]."""
+        return sweep_nll_of(self._of(slot))
+
+    def ece(self, slot=None):
+        """The expected calibration error per temperature, float64 [J]."""
+        return sweep_ece_of(self._of(slot))
+
+    def best(self, by="nll", slot=None):
+        """(T, j): the grid's temperature with the smallest mean NLL (`by`="nll") or ECE ("ece"); the first minimum wins."""
+        return sweep_best_of(self._of(slot), self.temperatures, by)
+
+    def summary(self, slot=None):
+        """Per temperature: T, the mean NLL rounded to four places, ECE and aAcc in percent rounded to two; and the best T by either measure."""
+        s = self._of(slot)
+        out = OrderedDict(T=self.temperatures.copy(), NLL=np.round(sweep_nll_of(s), 4), ECE=np.round(sweep_ece_of(s) * 100, 2),
+                          aAcc=np.round(accuracy_of(s[0, :3]) * 100, 2))
+        for by in ("nll", "ece"):
+            try:
+                out["best_" + by] = sweep_best_of(s, self.temperatures, by)[0]
+            except ValueError:
+                out["best_" + by] = np.float64(np.nan)
+        return out

@@ -14,6 +14,8 @@ Confidence maps (`confidence=` of the class-map entries, `conf=` of the plans, `
 classes of what `probabilities` / `aug_inference` return (ED:449,460), float32 [B, Ho, Wo], written by the launch that writes the class map.
 `calibration=` (mmsa.evaluate.Calibration) of the same entries bins that map against `labels=` on device: one more launch over the stored map and confidence.
 `selective=` (mmsa.evaluate.SelectiveEvaluator) of the same entries keeps one confusion matrix per confidence bin, likewise by one more launch: mIoU at a coverage.
+`temperature=` of the same entries (and of `probabilities`) writes the confidence of softmax(x / T) instead, by the `_t` sibling of whatever launch the plan takes; T
+comes from mmsa.evaluate.TemperatureSweep.  The class map does not depend on it, and `temperature=None` takes exactly the launches it always took.
 
 What a frame's output looks like -- its windows, the size after the second resize and after the cut, which class-map kernel that takes -- is decided once,
 in `MapPlan`, a record without device state; the entries read the frame (`_intake`), make the plan, and launch from it."""
@@ -235,6 +237,18 @@ def _confidence(confidence, size, device, what, fused=None, return_map=True):
     return _check_conf(confidence, size, device, what)
 
 
+def _inv_temperature(temperature, confidence, what):
+    """`temperature=` of an entry -> the float32 inverse temperature of the `_t` launches (mmsa.evaluate.inv_temperature; ValueError for a T that is not
+    finite and positive), or None.  Refused without a confidence map (`confidence`: the entry's `confidence=`, or the buffer)."""
+    if temperature is None:
+        return None
+    if confidence is None or confidence is False:
+        raise RuntimeError(f"mmsa.{what}: temperature= without confidence=: the class map does not depend on the temperature (the argmax of x / T is the argmax "
+                           "of x for every T > 0), only the confidence map does; pass confidence=True or an output tensor as well")
+    from .evaluate import inv_temperature
+    return inv_temperature(temperature)
+
+
 def _check_binned(kw, cls, owner, labels, confidence, what, fused=None, return_map=True):
     """`calibration=` / `selective=` of an entry (`kw`: the keyword's name, `cls`: the mmsa.evaluate class it takes), refused by name before anything is
     launched: both reduce the confidence map against the labels, so they need both, and the stored map (the fused class-map + evaluation launch writes
@@ -360,12 +374,15 @@ class MapPlan:
         outs = (out.data_ptr(),) if conf is None else (out.data_ptr(), conf.data_ptr())
         return (lg.data_ptr(), self.n, lg.shape[1], lg.shape[2], lg.shape[3], self.tab) + outs + (self.B, self.H, self.W, self.hc, self.wc)
 
-    def _plain(self, lg, out, unc, conf):
-        """mmsa_slide_argmax, or its sibling that also writes `conf`."""
-        lib.call("mmsa_slide_argmax" if conf is None else "mmsa_slide_argmax_conf", *self._args(lg, out, conf), unc.data_ptr(), ops._stream())
+    def _plain(self, lg, out, unc, conf, it=None):
+        """mmsa_slide_argmax, or its sibling that also writes `conf`; `it` (an inverse temperature, with `conf`): mmsa_slide_argmax_conf_t."""
+        if it is None:
+            lib.call("mmsa_slide_argmax" if conf is None else "mmsa_slide_argmax_conf", *self._args(lg, out, conf), unc.data_ptr(), ops._stream())
+        else:
+            lib.call("mmsa_slide_argmax_conf_t", *self._args(lg, out, conf), unc.data_ptr(), it, ops._stream())
 
     def class_map(self, lg, out, unc, labels=None, evaluator=None, case=None, fused=None, return_map=True, one_pass=None, conf=None, calibration=None,
-                  selective=None):
+                  selective=None, temperature=None):
         """The class-map launch of the three class-map calls, from the head-resolution logits lg [n, C, hs, ws] into out uint8 [B, Ho, Wo] and the
         uncovered-pixel word `unc`.  Without `labels`: mmsa_slide_argmax.  With `labels` (raw uint8 label maps [B, Hl, Wl]) and `evaluator`
         (mmsa.evaluate.Evaluator): the confusion counts of the map are ADDED to the evaluator's buffer as well -- by the same launch
@@ -380,7 +397,12 @@ class MapPlan:
         `calibration` (mmsa.evaluate.Calibration; needs `labels` and `conf`, `evaluator` is optional with it): the reliability bins of the map and its
         confidence are ADDED to its buffer by one more launch over the stored map and confidence (mmsa_eval_calibration), whatever launch wrote them.
         `selective` (mmsa.evaluate.SelectiveEvaluator; needs `labels` and `conf`, `evaluator` and `calibration` are optional next to it): the confusion
-        counts per confidence bin are ADDED to its buffer in the same way (mmsa_eval_selective)."""
+        counts per confidence bin are ADDED to its buffer in the same way (mmsa_eval_selective).
+        `temperature` (T > 0; needs `conf`): `conf` gets the confidence of softmax(logits / T), max_c of probabilities(..., temperature=T) bit for bit, from the
+        `_t` sibling of the launch the plan takes (mmsa_slide_argmax_conf_t / mmsa_slide_argmax_resized_conf_t; on the canvas path
+        mmsa_softmax_flip_accum_nchw_t); the map is the same for every T, and `calibration` / `selective` see the tempered confidence.  None: the launches
+        above, with the arguments above."""
+        it = _inv_temperature(temperature, conf, "inference")
         _check_calibration(calibration, labels, conf, "inference", fused, return_map)
         _check_selective(selective, labels, conf, "inference", fused, return_map)
         if conf is not None:
@@ -395,10 +417,12 @@ class MapPlan:
             if ONE_PASS_RESCALE_DEFAULT["up" if self.Hd * self.Wd > self.H * self.W else "down"] if one_pass is None else one_pass:
                 if conf is None:
                     lib.call("mmsa_slide_argmax_resized", *self._args(lg, out), *self.rs, unc.data_ptr(), ops._stream())
-                else:
+                elif it is None:
                     lib.call("mmsa_slide_argmax_resized_conf", *self._args(lg, out, conf), *self.rs, unc.data_ptr(), ops._stream())
+                else:
+                    lib.call("mmsa_slide_argmax_resized_conf_t", *self._args(lg, out, conf), *self.rs, unc.data_ptr(), it, ops._stream())
             else:
-                _rescaled_map_canvas(self, lg, out, unc, conf)
+                _rescaled_map_canvas(self, lg, out, unc, conf, it)
             if evaluator is not None:
                 evaluator.add(out, labels, case=case)
             _add_binned(out, conf, labels, case, calibration, selective)
@@ -408,11 +432,11 @@ class MapPlan:
         if labels is None and evaluator is None:
             if not return_map:
                 raise RuntimeError("mmsa.inference: return_map=False only makes sense with labels= and evaluator=")
-            self._plain(lg, out, unc, conf)
+            self._plain(lg, out, unc, conf, it)
             return
         _check_labels(labels, evaluator, calibration, selective)
         if evaluator is None:                              # labels for the calibration / the selective evaluator alone
-            self._plain(lg, out, unc, conf)
+            self._plain(lg, out, unc, conf, it)
             _add_binned(out, conf, labels, case, calibration, selective)
             return
         if fused is False and not return_map:
@@ -421,7 +445,7 @@ class MapPlan:
         if conf is None and ((evaluate.FUSED_DEFAULT or not return_map) if fused is None else fused):      # no map wanted: only the fused launch can leave it unwritten
             evaluator.add_fused(lg, self, out if return_map else None, unc, labels, case=case)
         else:
-            self._plain(lg, out, unc, conf)
+            self._plain(lg, out, unc, conf, it)
             evaluator.add(out, labels, case=case)
         _add_binned(out, conf, labels, case, calibration, selective)
 
@@ -440,24 +464,25 @@ def _canvas_logits(plan, lg, unc):
     return _rescaled_logits(canvas, (plan.Hd, plan.Wd) if plan.resized else None)
 
 
-def _rescaled_map_canvas(plan, lg, out, unc, conf=None):
+def _rescaled_map_canvas(plan, lg, out, unc, conf=None, it=None):
     """The rescaled class map the long way round: _canvas_logits, argmax, crop -- the launches slide_inference / encode_decode + argmax_map make.  With
     `conf`: also the softmax of the cut logits (what `probabilities` launches) and mmsa_argmax_max_nchw for its maximum.  The MAP stays the argmax of the
-    logits, as without `conf` and as in the one-pass kernels: the softmax can round two distinct logits to one probability, and the first class would win."""
+    logits, as without `conf` and as in the one-pass kernels: the softmax can round two distinct logits to one probability, and the first class would win.
+    `it` (an inverse temperature, with `conf`): the softmax of logits / T (mmsa_softmax_flip_accum_nchw_t)."""
     y = _canvas_logits(plan, lg, unc)
     out.copy_(argmax_map(y)[:, :plan.Ho, :plan.Wo])
     if conf is None:
         return
     y = y[:, :, :plan.Ho, :plan.Wo].contiguous()
     prob = torch.empty_like(y)
-    _softmax_accum(y, prob)
+    _softmax_accum(y, prob, it=it)
     _argmax_max_into(prob, torch.empty_like(out), conf)
 
 
 @_on_device
 @torch.no_grad()
 def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preprocess=None, labels=None, evaluator=None, case=None, fused=None,
-                    return_map=True, render=None, ori_shape=None, one_pass=None, confidence=False, calibration=None, selective=None):
+                    return_map=True, render=None, ori_shape=None, one_pass=None, confidence=False, calibration=None, selective=None, temperature=None):
     """`simple_test` of a sliding-window frame (ED:191-234 + ED:449,477) -> uint8 class map [B, H, W], without the
     [B, classes, H, W] logits canvas: every window's logits stay at head resolution and ONE kernel (mmsa_slide_argmax) resizes,
     sums the overlapping windows in window order, divides by the count and takes the argmax -- the same additions in the same order
@@ -481,7 +506,11 @@ def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preproc
     it, and what is returned does not change.
     `selective=` (mmsa.evaluate.SelectiveEvaluator; `case=` with a per-case one): one confusion matrix per confidence bin of the map and its confidence
     against `labels=` is added to it on device by one more launch (mmsa_eval_selective), no host sync; it needs `labels=` and `confidence=`, `evaluator=`
-    and `calibration=` are optional next to it, and what is returned does not change."""
+    and `calibration=` are optional next to it, and what is returned does not change.
+    `temperature=` (T > 0, from mmsa.evaluate.TemperatureSweep.best(); needs `confidence=`): the confidence map is that of softmax(logits / T) --
+    probabilities(..., temperature=T).max(1).values bit for bit -- written by the `_t` sibling of the same launch; the map is the same for every T, and
+    `calibration=` / `selective=` see the tempered confidence.  Without `confidence=` it is refused: the map does not depend on it."""
+    _inv_temperature(temperature, confidence, "slide_class_map")
     _check_calibration(calibration, labels, confidence, "slide_class_map", fused, return_map)
     _check_selective(selective, labels, confidence, "slide_class_map", fused, return_map)
     B, H, W, device, frame, cut = _intake(img, preprocess, "slide_class_map")
@@ -497,7 +526,7 @@ def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preproc
     lg = lgs[0] if len(lgs) == 1 else torch.cat(lgs, 0)
     out = torch.empty(B, plan.Ho, plan.Wo, dtype=torch.uint8, device=device)
     unc = torch.zeros(1, dtype=torch.int32, device=device)
-    plan.class_map(lg, out, unc, labels, evaluator, case, fused, return_map, one_pass, conf, calibration, selective)
+    plan.class_map(lg, out, unc, labels, evaluator, case, fused, return_map, one_pass, conf, calibration, selective, temperature)
     r = (out, unc, render(out, src)) if render is not None else ((out if return_map else None), unc)   # unc[0] != 0 <=> some pixel is not covered (ED:220); checked by the caller outside a capture
     return r if conf is None else r + (conf,)
 
@@ -505,7 +534,7 @@ def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preproc
 @_on_device
 @torch.no_grad()
 def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator=None, case=None, fused=None, return_map=True, render=None,
-                    ori_shape=None, dim=None, cut_dim=None, rescale=True, one_pass=None, confidence=False, calibration=None, selective=None):
+                    ori_shape=None, dim=None, cut_dim=None, rescale=True, one_pass=None, confidence=False, calibration=None, selective=None, temperature=None):
     """Whole-image `simple_test`: resize x4 (bilinear, align_corners=False) + argmax fused (ED:90-94,449,477) -> uint8 [B, H, W].
     `preprocess=` (mmsa.preprocess.Preprocess): img is the pair (rgb, aux) of raw frames, normalised (and padded) by one launch.
     `labels=` + `evaluator=` (+ `case=`): as in slide_class_map.
@@ -521,7 +550,9 @@ def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator
     uint8 frames of the size before the cut, or -- for a cut alone -- the input tensor.
     `confidence=`: as in slide_class_map; the confidence map float32 [B, Ho, Wo] comes as the last element, (map[, picture], conf).
     `calibration=`: as in slide_class_map (needs `labels=` and `confidence=`); at a rescaled or cut size the pass reads the map and confidence stored there.
-    `selective=`: as in slide_class_map (needs `labels=` and `confidence=`), over the map and confidence stored at the size returned."""
+    `selective=`: as in slide_class_map (needs `labels=` and `confidence=`), over the map and confidence stored at the size returned.
+    `temperature=`: as in slide_class_map (needs `confidence=`): the confidence of softmax(logits / T) at the size returned."""
+    _inv_temperature(temperature, confidence, "whole_class_map")
     _check_calibration(calibration, labels, confidence, "whole_class_map", fused, return_map)
     _check_selective(selective, labels, confidence, "whole_class_map", fused, return_map)
     rgb = None
@@ -542,7 +573,7 @@ def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator
     lg = head(feats)
     out = torch.empty(B, plan.Ho, plan.Wo, dtype=torch.uint8, device=img.device)
     unc = torch.zeros(1, dtype=torch.int32, device=img.device)
-    plan.class_map(lg, out, unc, labels, evaluator, case, fused, return_map, one_pass, conf, calibration, selective)
+    plan.class_map(lg, out, unc, labels, evaluator, case, fused, return_map, one_pass, conf, calibration, selective, temperature)
     if render is not None:
         return (out, render(out, src)) if conf is None else (out, render(out, src), conf)
     if conf is not None:
@@ -611,7 +642,7 @@ def inference(backbone, head, img, test_cfg, rescale=True, preprocess=None, ori_
 @_on_device
 @torch.no_grad()
 def class_map(backbone, head, img, test_cfg, rescale=True, ori_shape=None, preprocess=None, labels=None, evaluator=None, case=None, render=None, one_pass=None,
-              confidence=False, calibration=None, selective=None):
+              confidence=False, calibration=None, selective=None, temperature=None):
     """`simple_test` (ED:471-477) by mode: the dispatch of `inference` (ED:417-447) onto the class-map calls -> uint8 map, bit for bit
     argmax_map(inference(...)) of the same arguments, without a logits canvas: [B, H, W], or at the size `rescale` gives ('slide' / 'whole': `ori_shape`;
     'whole_dim': test_cfg['dim']; 'whole_dim_cut': the crop of the map at `dim`, or at the input size without `rescale`).  What `inference` refuses is
@@ -620,12 +651,14 @@ def class_map(backbone, head, img, test_cfg, rescale=True, ori_shape=None, prepr
     `preprocess=`, `labels=` + `evaluator=` (+ `case=`; through the stored map), `render=` (-> (map, picture)), `one_pass=`: as in the calls it goes to.
     `confidence=` (True or an output tensor): the confidence map, probabilities(...).max(1).values bit for bit, as the last element: (map[, picture], conf).
     `calibration=` (mmsa.evaluate.Calibration; needs `labels=` and `confidence=`): as in the calls it goes to.
-    `selective=` (mmsa.evaluate.SelectiveEvaluator; needs `labels=` and `confidence=`): as in the calls it goes to."""
+    `selective=` (mmsa.evaluate.SelectiveEvaluator; needs `labels=` and `confidence=`): as in the calls it goes to.
+    `temperature=` (T > 0; needs `confidence=`): the confidence of softmax(logits / T), as in the calls it goes to."""
     mode = test_cfg["mode"]
+    _inv_temperature(temperature, confidence, "class_map")
     _check_calibration(calibration, labels, confidence, "class_map")
     _check_selective(selective, labels, confidence, "class_map")
     kw = dict(preprocess=preprocess, labels=labels, evaluator=evaluator, case=case, render=render, one_pass=one_pass, confidence=confidence,
-              calibration=calibration, selective=selective)
+              calibration=calibration, selective=selective, temperature=temperature)
     if mode == "slide":
         r = slide_class_map(backbone, head, img, tuple(test_cfg["crop_size"]), tuple(test_cfg["stride"]), ori_shape=ori_shape if rescale else None, **kw)
         if int(r[1].item()) != 0:
@@ -693,10 +726,14 @@ def _flip_code(flip, what):
     return FLIPS[flip]
 
 
-def _softmax_accum(logits, acc, flip=0, accumulate=False, finish_div=0):
-    """ED:448-469 + ED:540-541 on a logits canvas: acc (=|+=) flip(softmax(logits)) [/ finish_div]."""
+def _softmax_accum(logits, acc, flip=0, accumulate=False, finish_div=0, it=None):
+    """ED:448-469 + ED:540-541 on a logits canvas: acc (=|+=) flip(softmax(logits)) [/ finish_div]; `it` (an inverse temperature): softmax(logits * it), by
+    mmsa_softmax_flip_accum_nchw_t."""
     B, C, H, W = logits.shape
-    lib.call("mmsa_softmax_flip_accum_nchw", logits.data_ptr(), acc.data_ptr(), B, C, H, W, flip, 1 if accumulate else 0, finish_div, ops._stream())
+    if it is None:
+        lib.call("mmsa_softmax_flip_accum_nchw", logits.data_ptr(), acc.data_ptr(), B, C, H, W, flip, 1 if accumulate else 0, finish_div, ops._stream())
+    else:
+        lib.call("mmsa_softmax_flip_accum_nchw_t", logits.data_ptr(), acc.data_ptr(), B, C, H, W, flip, 1 if accumulate else 0, finish_div, it, ops._stream())
 
 
 def _plan_of(test_cfg, B, H, W, rescale, ori_shape, what):
@@ -715,14 +752,16 @@ def _plan_of(test_cfg, B, H, W, rescale, ori_shape, what):
 
 @_on_device
 @torch.no_grad()
-def probabilities(backbone, head, img, test_cfg, rescale=True, ori_shape=None, flip=None, preprocess=None, max_batch=8):
+def probabilities(backbone, head, img, test_cfg, rescale=True, ori_shape=None, flip=None, preprocess=None, max_batch=8, temperature=None):
     """What the reference's `inference` returns (ED:417-469): F.softmax(seg_logit, dim=1) of `inference(...)`'s logits, flipped back when the view `img`
     was flipped (`flip` = None, 'horizontal' or 'vertical': img_meta's flip_direction) -> float32 [B, classes, Ho, Wo].  One more launch
-    (mmsa_softmax_flip_accum_nchw) on the logits; `inference` itself keeps returning logits."""
+    (mmsa_softmax_flip_accum_nchw) on the logits; `inference` itself keeps returning logits.
+    `temperature=` (T > 0): F.softmax(seg_logit / T, dim=1) instead, by mmsa_softmax_flip_accum_nchw_t (exponent (x - m) * float32(1 / T))."""
     code = _flip_code(flip, "probabilities")
+    it = _inv_temperature(temperature, True, "probabilities")
     y = inference(backbone, head, img, test_cfg, rescale=rescale, preprocess=preprocess, ori_shape=ori_shape, max_batch=max_batch).contiguous()
     out = torch.empty_like(y)
-    _softmax_accum(y, out, code)
+    _softmax_accum(y, out, code, it=it)
     return out
 
 
@@ -995,12 +1034,15 @@ class SlideRunner:
     With `ori_shape=` (h, w[, 3]) the class map -- and the static `out` buffer -- is the one of `rescale=True` at [B, h, w] (slide_class_map's `ori_shape=`:
     mmsa_slide_argmax_resized in place of mmsa_slide_argmax, or the canvas path with `one_pass=False`).
     With `confidence=True` every run() also writes the frame's confidence map (slide_class_map's `confidence=`) into a static float32 [B, h, w] buffer, by the
-    `_conf` sibling of the class-map launch: FrameResult.confidence().  Such a runner refuses run(fused=True) and run(return_map=False)."""
+    `_conf` sibling of the class-map launch: FrameResult.confidence().  Such a runner refuses run(fused=True) and run(return_map=False).
+    With `temperature=` (T > 0; needs confidence=True) that confidence is the one of softmax(logits / T) (slide_class_map's `temperature=`).  It belongs to the
+    runner and not to run(): the scalar is an argument of the launch, and a captured launch keeps the one it was captured with."""
 
     def __init__(self, backbone, head, frame, crop_size, stride, chains=2, check_every=1, preprocess=None, render=None, ori_shape=None, one_pass=None,
-                 confidence=False):
+                 confidence=False, temperature=None):
         from .chains import Chains
-        self.preprocess, self.render, self.one_pass = preprocess, render, one_pass
+        _inv_temperature(temperature, confidence, "SlideRunner")
+        self.preprocess, self.render, self.one_pass, self.temperature = preprocess, render, one_pass, temperature
         B, H, W, self.device, self.frame, self._cut = _intake(frame, preprocess, "SlideRunner")
         self.plan = plan = MapPlan.slide(B, H, W, tuple(crop_size), stride, ori_shape, what="SlideRunner")
         if render is not None:
@@ -1051,7 +1093,8 @@ class SlideRunner:
             rp = self.chains.replay()
             lg = rp.unverified          # the argmax kernel below is enqueued behind the pass; nothing is read on the host before outputs() verifies it
             self.unc.zero_()
-            self.plan.class_map(lg, self.out, self.unc, labels, evaluator, case, fused, return_map, self.one_pass, self.conf, calibration, selective)
+            self.plan.class_map(lg, self.out, self.unc, labels, evaluator, case, fused, return_map, self.one_pass, self.conf, calibration, selective,
+                                self.temperature)
             if self.render is not None:
                 self.render(self.out, src, out=self.pic)
         return FrameResult(self, rp, has_map=return_map)

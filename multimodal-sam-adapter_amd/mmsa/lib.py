@@ -93,6 +93,10 @@ SIGNATURES = {
     "mmsa_eval_calibration": [P, P, P, I, I, I, I, I, P, I, P, P, P, I, I, P, P],
     "mmsa_eval_selective": [P, P, P, I, I, I, I, I, P, I, P, P, P, I, I, P, P],
     "mmsa_abstain_u8": [P, P, L, I, I, P, P],
+    "mmsa_slide_argmax_conf_t": [P, I, I, I, I, P, P, P, I, I, I, I, I, P, F, P],
+    "mmsa_slide_argmax_resized_conf_t": [P, I, I, I, I, P, P, P, I, I, I, I, I, I, I, I, I, P, F, P],
+    "mmsa_softmax_flip_accum_nchw_t": [P, P, I, I, I, I, I, I, I, F, P],
+    "mmsa_temperature_sweep_nchw": [P, P, I, I, I, I, I, I, P, P, P, P, I, P, I, I, P, P],
     "mmsa_slide_argmax_eval": [P, I, I, I, I, P, P, I, I, I, I, I, P, P, I, I, P, P, P, P, I, P, P],
     "mmsa_render_u8": [P, L, L, I, I, I, P, I, I, P, I, I, I, c_double, c_double, P, P],
     "mmsa_render_denorm_f32": [P, L, L, I, I, I, P, I, I, P, I, I, I, P, P, I, I, c_double, c_double, P, P],
@@ -107,7 +111,7 @@ for _name, _args in SIGNATURES.items():
 
 # The C ABI is not self-describing: a library built from another tree (MMSA_LIB variants, a stale in-tree .so) may export every symbol and still take
 # different argument lists.  include/mmsa.h MMSA_ABI_VERSION is bumped with every such change; this binding was written for:
-ABI_VERSION = 113
+ABI_VERSION = 114
 if _lib.mmsa_version() != ABI_VERSION:
     raise RuntimeError(f"{LIB_PATH}: ABI version {_lib.mmsa_version()} but mmsa/lib.py binds version {ABI_VERSION} (include/mmsa.h MMSA_ABI_VERSION): "
                        "rebuild with python multimodal-sam-adapter_amd/build.py")
