@@ -511,6 +511,25 @@ int mmsa_temperature_sweep_nchw(const float* logits, const unsigned char* label,
                                 const int* ymap, const int* xmap, const int* slots, int n_slots, const float* inv_temperatures, int J, int bins,
                                 int64_t* sweep, mmsa_stream_t stream);
 
+/* --- uncertainty maps (the reference has no such step): one of the two other standard per-pixel scores in the confidence's place, score float32 [B, Ho, Wo] in
+ *     [0, 1], higher = more certain, 0 where the map is 255 -- what mmsa_eval_calibration, mmsa_eval_selective and mmsa_abstain_u8 take as `conf`.  Both are
+ *     formed from the float32 probabilities p_c the confidence paths produce (one view: e_c / s of the tempered softmax above; several views: their mean), with
+ *     bi the class the map names, no contraction:
+ *       kind 1, top-2 margin:  p[bi] - p2, p2 = the largest p_c over c != bi (class order, `>`): one float32 subtraction; C == 1: p[bi];
+ *       kind 2, entropy score: max(0, 1 - H * inv_log_c), H = sum_c (p_c > 0 ? -(p_c * logf(p_c)) : 0) in class order from the first term;
+ *         inv_log_c = float32(1 / log(float64(C))) made by the caller, 0 for C == 1 (the score is then 1); finite and >= 0, else MMSA_ERR_ARG.
+ *     Any other kind: MMSA_ERR_ARG.  inv_temperature as in the `_t` entries (1.0f: the untempered softmax, exactly).
+ *   argmax_score_nchw: mmsa_argmax_max_nchw with the score in the maximum's place, on a canvas of probabilities [B, C, H, W]; bi = their first maximum.
+ *   slide_argmax_score / slide_argmax_resized_score: mmsa_slide_argmax_conf_t / mmsa_slide_argmax_resized_conf_t with the score in the confidence's place
+ *     (same arguments, same checks, same class map; `kind` before inv_temperature, inv_log_c behind it): bit for bit argmax_score_nchw on the
+ *     probabilities of the canvas path.  Frame size: a per-lane LDS column up to 64 classes, three recomputing passes from 65 on; rescaled: recomputing. --- */
+int mmsa_argmax_score_nchw(const float* prob, unsigned char* out, float* score, int B, int C, int H, int W, int kind, float inv_log_c, mmsa_stream_t stream);
+int mmsa_slide_argmax_score(const float* logits, int n, int C, int hs, int ws, const int* windows, unsigned char* out, float* score, int B, int H, int W,
+                            int hc, int wc, int* uncovered, int kind, float inv_temperature, float inv_log_c, mmsa_stream_t stream);
+int mmsa_slide_argmax_resized_score(const float* logits, int n, int C, int hs, int ws, const int* windows, unsigned char* out, float* score, int B, int H,
+                                    int W, int hc, int wc, int Hd, int Wd, int Hcut, int Wcut, int* uncovered, int kind, float inv_temperature,
+                                    float inv_log_c, mmsa_stream_t stream);
+
 /* --- the picture of a prediction (segmentation/mmseg_custom/apis/test_bs.py:257-349, the `--show` / `--show-dir` output): `tensor2imgs` (test_bs.py:18-63) on
  *     planes 0..2 of the input tensor -> the crop `img[:h, :w]` (test_bs.py:275-276) -> `show_result` (tools/color_gt_according_palette.py:23-81:
  *     color_seg[seg == label] = color, channels reversed, img * (1 - opacity) + color_seg * opacity, .astype(uint8)), in one pass.

@@ -14,7 +14,10 @@
  * 112: new entry mmsa_eval_calibration (reliability bins of a class map and its confidence map against a label map: total / correct / confidence sum per bin).
  * 113: new entries mmsa_eval_selective / mmsa_abstain_u8 (one confusion matrix per confidence bin of a class map and its confidence map, and the map thresholded by confidence bin).
  * 114: new entries mmsa_slide_argmax_conf_t / mmsa_slide_argmax_resized_conf_t / mmsa_softmax_flip_accum_nchw_t (the confidence of softmax(x / T)) and
- *      mmsa_temperature_sweep_nchw (reliability bins and NLL of a logits canvas for a grid of temperatures in one pass). */
+ *      mmsa_temperature_sweep_nchw (reliability bins and NLL of a logits canvas for a grid of temperatures in one pass).
+ *      Still 114: new entries mmsa_argmax_score_nchw / mmsa_slide_argmax_score / mmsa_slide_argmax_resized_score (the top-2 margin or the entropy score in the
+ *      confidence's place).  No existing entry changed its arguments or their meaning, and a library without the new symbols fails the binding's symbol lookup
+ *      (mmsa/lib.py) before the number is read, so the number that tests/test_temperature_cpu.py pins stays. */
 #ifndef MMSA_VERSION_H
 #define MMSA_VERSION_H
 #define MMSA_ABI_VERSION 114

@@ -205,10 +205,12 @@ extern "C" int mmsa_slide_argmax_eval(const float* logits, int n, int C, int hs,
 // CONF: the probability of the predicted class also goes to `conf` float [B, Hcut, Wcut] (0 for a 255 pixel), by a second pass over the classes in the form
 // the first one took (slots or scanning), for the reason slide_pixel.inc gives: the same values again, now that their maximum `best` is known.
 // TEMP (with CONF): the confidence of softmax(x / T) -- the exponentials are softmax_px_exp_t with the inverse temperature `it`; the map does not depend on it.
-template <bool CONF, bool TEMP = false>
+// SCORE (without CONF / TEMP): an uncertainty score of csrc/softmax_px.h (`kind`, `ilc`) goes to `conf` in the confidence's place, from the probabilities of
+// softmax(x * it) -- a third pass over the classes in the recomputing form: the sum needs the maximum, the probabilities need the sum.
+template <bool CONF, bool TEMP = false, bool SCORE = false>
 __device__ __forceinline__ void slide_resized_pixel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out, float* __restrict__ conf,
                                                     int H, int W, int hc, int wc, float rh, float rw, int Hcut, int Wcut, float rh2, float rw2,
-                                                    const WindowTable& wt, int* __restrict__ uncovered, float it = 1.f) {
+                                                    const WindowTable& wt, int* __restrict__ uncovered, float it = 1.f, int kind = 0, float ilc = 0.f) {
   const int X = blockIdx.x * 256 + threadIdx.x, Y = blockIdx.y, b = blockIdx.z;
   if (X >= Wcut) return;
   TwoStagePixel px;
@@ -218,6 +220,7 @@ __device__ __forceinline__ void slide_resized_pixel(const float* __restrict__ lo
     atomicAdd(uncovered, 1);
     out[op] = 255;
     if constexpr (CONF) conf[op] = 0.f;
+    if constexpr (SCORE) conf[op] = 0.f;
     return;
   }
   const bool slots = px.nmax <= RESIZED_SLOTS;
@@ -252,6 +255,18 @@ __device__ __forceinline__ void slide_resized_pixel(const float* __restrict__ lo
     else
       for (int c = 0; c < C; ++c) s = softmax_px_sum(s, softmax_px_exp_t(two_stage_value<true>(px, wt, b, logits, C, c, hs, ws, hc, wc, rh, rw), best, it), c == 0);
     conf[op] = softmax_px_prob(softmax_px_exp_t(best, best, it), s);
+  }
+  if constexpr (SCORE) {
+    float s = 0.f, sa = 0.f, spb = 0.f;
+    bool snone = true;
+    for (int pass = 0; pass < 2; ++pass)      // 0: the sum of the exponentials; 1: the probabilities, class by class, into the score
+      for (int c = 0; c < C; ++c) {
+        const float v = slots ? two_stage_value<false>(px, wt, b, logits, C, c, hs, ws, hc, wc, rh, rw) : two_stage_value<true>(px, wt, b, logits, C, c, hs, ws, hc, wc, rh, rw);
+        const float e = softmax_px_exp_t(v, best, it);
+        if (pass == 0) s = softmax_px_sum(s, e, c == 0);
+        else score_px_class(kind, bi, c, softmax_px_prob(e, s), sa, spb, snone);
+      }
+    conf[op] = score_px_finish(kind, sa, spb, snone, ilc);
   }
 }
 
@@ -491,4 +506,143 @@ extern "C" int mmsa_slide_argmax_resized_conf_t(const float* logits, int n, int 
   MMSA_CHECK_ARG(conf, "slide_argmax_resized_conf_t: bad args");
   return slide_argmax_resized_launch("slide_argmax_resized_conf_t", logits, n, C, hs, ws, windows, out, conf, B, H, W, hc, wc, Hd, Wd, Hcut, Wcut, uncovered, stream,
                                      &inv_temperature);
+}
+
+// ---- uncertainty maps: the top-2 margin or the entropy score (csrc/softmax_px.h: `kind` SCORE_MARGIN / SCORE_ENTROPY) in the confidence's place, float32
+// [B, Ho, Wo] in [0, 1], higher = more certain, 0 where the map is 255 -- so that csrc/conf_bin.h and everything behind it take it unchanged.  Both are formed
+// from the float32 probabilities p_c, the same operations in the canvas kernel (which reads p_c) and in the one-pass kernels (which form p_c = e_c / s of
+// softmax(x * it) themselves: `it` is always an argument, its product exact at 1.0f): bit for bit the same score.  They stand here, at the end, for the reason
+// given above argmax_max_nchw_kernel (profiles/uncertainty_isa.txt).
+
+// argmax_max_nchw_kernel with the score in the maximum's place: on a canvas of probabilities (one view's, or the mean over augmented views).  `bi` is the
+// first maximum of the probabilities; where the logits' argmax is a later class of the same probability, p[bi] and p2 are the same two values.
+__global__ __launch_bounds__(256) void argmax_score_nchw_kernel(const float* __restrict__ x, unsigned char* __restrict__ out, float* __restrict__ score, int C,
+                                                                long HW, long total, int kind, float ilc) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;   // b * HW + p
+  if (i >= total) return;
+  const long b = i / HW, p = i - b * HW;
+  const float* xp = x + b * C * HW + p;
+  float best = xp[0];
+  int bi = 0;
+  for (int c = 1; c < C; ++c) {
+    const float v = xp[(long)c * HW];
+    if (v > best) { best = v; bi = c; }
+  }
+  out[i] = (unsigned char)bi;
+  float sa = 0.f, spb = 0.f;
+  bool snone = true;
+  for (int c = 0; c < C; ++c) score_px_class(kind, bi, c, xp[(long)c * HW], sa, spb, snone);
+  score[i] = score_px_finish(kind, sa, spb, snone, ilc);
+}
+
+#define MMSA_CHECK_SCORE_KIND(name, kind) MMSA_CHECK_ARG((kind) == SCORE_MARGIN || (kind) == SCORE_ENTROPY, "%s: kind %d is neither 1 (top-2 margin) nor 2 (entropy score)", name, kind)
+
+extern "C" int mmsa_argmax_score_nchw(const float* prob, unsigned char* out, float* score, int B, int C, int H, int W, int kind, float inv_log_c,
+                                      hipStream_t stream) {
+  MMSA_CHECK_ARG(prob && out && score && B > 0 && C > 0 && C <= 256 && H > 0 && W > 0, "argmax_score_nchw: bad args (C <= 256 for the uint8 map)");
+  MMSA_CHECK_SCORE_KIND("argmax_score_nchw", kind);
+  MMSA_CHECK_ARG(inv_log_c >= 0.f && inv_log_c < INFINITY, "argmax_score_nchw: inv_log_c must be finite and not negative (1 / log C; 0 for one class)");
+  const long HW = (long)H * W, total = (long)B * HW;
+  hipLaunchKernelGGL(argmax_score_nchw_kernel, dim3(cdiv(total, 256)), dim3(256), 0, stream, prob, out, score, C, HW, total, kind, inv_log_c);
+  MMSA_CHECK_LAUNCH("argmax_score_nchw");
+  return MMSA_OK;
+}
+
+// slide_argmax_kernel + the score map, in the two forms of the confidence (slide_pixel.inc SLIDE_SCORE): the per-lane LDS column up to SLIDE_CONF_LDS_CLASSES
+// classes -- written with x_c by the class-map pass, overwritten with e_c by the sum pass, read once more for p_c = e_c / s -- and three recomputing passes
+// above that (65 .. 255 classes; slow, and allowed to be).
+__global__ __launch_bounds__(256) void slide_argmax_score_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
+                                                                 float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, WindowTable wt,
+                                                                 int* __restrict__ uncovered, int kind, float it, float ilc) {
+#define SLIDE_EVAL 0
+#define SLIDE_CONF 0
+#define SLIDE_TEMP 0
+#define SLIDE_SCORE 1
+#define SLIDE_Y blockIdx.y
+#define SLIDE_EXIT return
+#include "slide_pixel.inc"
+#undef SLIDE_EVAL
+#undef SLIDE_CONF
+#undef SLIDE_TEMP
+#undef SLIDE_SCORE
+#undef SLIDE_Y
+#undef SLIDE_EXIT
+}
+
+__global__ __launch_bounds__(256) void slide_argmax_score_lds_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
+                                                                     float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, WindowTable wt,
+                                                                     int* __restrict__ uncovered, int kind, float it, float ilc) {
+  extern __shared__ float conf_lds[];
+  float* conf_col = conf_lds + threadIdx.x;      // private to the lane: no barrier
+#define SLIDE_EVAL 0
+#define SLIDE_CONF 0
+#define SLIDE_TEMP 0
+#define SLIDE_SCORE 2
+#define SLIDE_Y blockIdx.y
+#define SLIDE_EXIT return
+#include "slide_pixel.inc"
+#undef SLIDE_EVAL
+#undef SLIDE_CONF
+#undef SLIDE_TEMP
+#undef SLIDE_SCORE
+#undef SLIDE_Y
+#undef SLIDE_EXIT
+}
+
+__global__ __launch_bounds__(256) void slide_argmax_resized_score_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
+                                                                         float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, int Hcut,
+                                                                         int Wcut, float rh2, float rw2, WindowTable wt, int* __restrict__ uncovered, int kind,
+                                                                         float it, float ilc) {
+  slide_resized_pixel<false, false, true>(logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, Hcut, Wcut, rh2, rw2, wt, uncovered, it, kind, ilc);
+}
+
+static int score_check(const char* name, const float* score, int kind, float it, float ilc) {
+  MMSA_CHECK_ARG(score, "%s: bad args", name);
+  MMSA_CHECK_SCORE_KIND(name, kind);
+  MMSA_CHECK_INV_TEMPERATURE(name, it);
+  MMSA_CHECK_ARG(ilc >= 0.f && ilc < INFINITY, "%s: inv_log_c must be finite and not negative (1 / log C; 0 for one class)", name);
+  return MMSA_OK;
+}
+
+extern "C" int mmsa_slide_argmax_score(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out, float* score,
+                                       int B, int H, int W, int hc, int wc, int* uncovered /* device int, zeroed by the caller */, int kind, float inv_temperature,
+                                       float inv_log_c, hipStream_t stream) {
+  const char* name = "slide_argmax_score";
+  MMSA_CHECK_ARG(logits && out && uncovered && C > 0 && C <= 255 && hs > 0 && ws > 0 && hc > 0 && wc > 0 && B > 0 && H <= 65535 && B <= 65535, "%s: bad args", name);
+  int rc = score_check(name, score, kind, inv_temperature, inv_log_c);
+  if (rc) return rc;
+  WindowTable wt;
+  rc = fill_windows(wt, windows, n, B, H, W, hc, wc, name);
+  if (rc) return rc;
+  const dim3 grid(cdiv(W, 256), H, B);
+  const float rh = (float)hs / (float)hc, rw = (float)ws / (float)wc;
+  if (C <= SLIDE_CONF_LDS_CLASSES)
+    hipLaunchKernelGGL(slide_argmax_score_lds_kernel, grid, dim3(256), (size_t)C * 256 * sizeof(float), stream, logits, C, hs, ws, out, score, H, W, hc, wc, rh, rw, wt,
+                       uncovered, kind, inv_temperature, inv_log_c);
+  else
+    hipLaunchKernelGGL(slide_argmax_score_kernel, grid, dim3(256), 0, stream, logits, C, hs, ws, out, score, H, W, hc, wc, rh, rw, wt, uncovered, kind,
+                       inv_temperature, inv_log_c);
+  MMSA_CHECK_LAUNCH(name);
+  return MMSA_OK;
+}
+
+extern "C" int mmsa_slide_argmax_resized_score(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out,
+                                               float* score, int B, int H, int W, int hc, int wc, int Hd, int Wd, int Hcut, int Wcut,
+                                               int* uncovered /* device int, zeroed by the caller */, int kind, float inv_temperature, float inv_log_c,
+                                               hipStream_t stream) {
+  const char* name = "slide_argmax_resized_score";
+  MMSA_CHECK_ARG(logits && out && uncovered && C > 0 && C <= 255 && hs > 0 && ws > 0 && hc > 0 && wc > 0 && B > 0 && H > 0 && W > 0 && B <= 65535, "%s: bad args", name);
+  int rc = score_check(name, score, kind, inv_temperature, inv_log_c);
+  if (rc) return rc;
+  MMSA_CHECK_ARG(Hd > 0 && Wd > 0 && Hcut > 0 && Wcut > 0 && Hcut <= Hd && Wcut <= Wd && Hcut <= 65535,
+                 "%s: the cut %dx%d must lie inside the target %dx%d (and have at most 65535 rows)", name, Hcut, Wcut, Hd, Wd);
+  WindowTable wt;
+  rc = fill_windows(wt, windows, n, B, H, W, hc, wc, name);
+  if (rc) return rc;
+  const dim3 grid(cdiv(Wcut, 256), Hcut, B);
+  const float rh = (float)hs / (float)hc, rw = (float)ws / (float)wc, rh2 = (float)H / (float)Hd, rw2 = (float)W / (float)Wd;
+  hipLaunchKernelGGL(slide_argmax_resized_score_kernel, grid, dim3(256), 0, stream, logits, C, hs, ws, out, score, H, W, hc, wc, rh, rw, Hcut, Wcut, rh2, rw2, wt,
+                     uncovered, kind, inv_temperature, inv_log_c);
+  MMSA_CHECK_LAUNCH(name);
+  return MMSA_OK;
 }

@@ -10,10 +10,20 @@
 //                 aug_argmax_kernel does, and the second pass reads them back: the faster form (segment.hip has the figures), for C * 256 floats <= 64 KiB.
 //   SLIDE_TEMP 1: (with SLIDE_CONF 1 / 2) slide_argmax_conf_t_kernel / slide_argmax_conf_lds_t_kernel -- the confidence of softmax(x / T): the exponentials are
 //                 softmax_px_exp_t with the launch's inverse temperature `it`; the map does not depend on it.  SLIDE_TEMP 0: softmax_px_exp, no `it` in scope.
+//   SLIDE_SCORE 1 / 2: (with SLIDE_EVAL 0, SLIDE_CONF 0, SLIDE_TEMP 0; not defined = 0) slide_argmax_score_kernel / slide_argmax_score_lds_kernel -- an uncertainty
+//                 score of csrc/softmax_px.h (`kind`: top-2 margin or entropy score, `ilc` = 1 / log C for the latter) goes to `conf` in the confidence's place,
+//                 formed from the probabilities p_c = e_c / s of softmax(x * it) (`it` always given: the product is exact at 1.0f), which need s first: hence a
+//                 THIRD pass over the classes.  1: both later passes recompute acc / cnt, any C the map allows.  2: the per-lane LDS column of SLIDE_CONF 2;
+//                 the sum pass overwrites x_c with e_c, so the third pass calls no expf.  An uncovered pixel (map 255) gets 0.
 // SLIDE_Y is the pixel's row: blockIdx.y in the first kernel, the row variable of the second kernel's loop over its workgroup's rows.
 // SLIDE_EXIT leaves the body: `return` in the first kernel, `continue` with the next row in the second, which still has its histogram to flush.
 // SLIDE_EXIT MUST NOT be used inside a loop of this body: there `continue` would go on with that loop in the second kernel only, where `return`
-// leaves the first (every use below is at the body's top level).  In scope: logits, C, hs, ws, out, H, W, hc, wc, rh, rw, wt, uncovered (and conf).
+// leaves the first (every use below is at the body's top level).  In scope: logits, C, hs, ws, out, H, W, hc, wc, rh, rw, wt, uncovered (and conf; with SLIDE_SCORE also
+// kind, it, ilc).
+#ifndef SLIDE_SCORE
+#define SLIDE_SCORE 0
+#define SLIDE_SCORE_DEFAULTED
+#endif
 #if SLIDE_TEMP
 #define SLIDE_EXP(v, m) softmax_px_exp_t(v, m, it)
 #else
@@ -63,6 +73,9 @@
 #if SLIDE_CONF
     conf[((long)b * H + y) * W + x] = 0.f;
 #endif
+#if SLIDE_SCORE
+    conf[((long)b * H + y) * W + x] = 0.f;
+#endif
     SLIDE_EXIT;
   }
   const float cnt = (float)nk;
@@ -81,6 +94,9 @@
     }
     const float p = acc / cnt;
 #if SLIDE_CONF == 2
+    conf_col[c * 256] = p;
+#endif
+#if SLIDE_SCORE == 2
     conf_col[c * 256] = p;
 #endif
     if (c == 0 || p > best) { best = p; bi = c; }
@@ -112,4 +128,40 @@
   }
   conf[((long)b * H + y) * W + x] = softmax_px_prob(SLIDE_EXP(best, best), s);      // e_c / s at the first maximum: the largest probability
 #endif
+#if SLIDE_SCORE == 2
+  float s = 0.f;
+  for (int c = 0; c < C; ++c) {
+    const float e = softmax_px_exp_t(conf_col[c * 256], best, it);
+    conf_col[c * 256] = e;
+    s = softmax_px_sum(s, e, c == 0);
+  }
+  float sa = 0.f, spb = 0.f;
+  bool snone = true;
+  for (int c = 0; c < C; ++c) score_px_class(kind, bi, c, softmax_px_prob(conf_col[c * 256], s), sa, spb, snone);
+  conf[((long)b * H + y) * W + x] = score_px_finish(kind, sa, spb, snone, ilc);
+#elif SLIDE_SCORE
+  float s = 0.f, sa = 0.f, spb = 0.f;
+  bool snone = true;
+  for (int pass = 0; pass < 2; ++pass)      // 0: the sum of the exponentials; 1: the probabilities, class by class, into the score
+    for (int c = 0; c < C; ++c) {
+      float acc = 0.f;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        if (q < nk) {
+          const float* sp = logits + ((long)kk[q] * C + c) * hs * ws;
+          const float lh = lhs[q], lw = lws[q];
+          const float v = (1.f - lh) * ((1.f - lw) * sp[o00[q]] + lw * sp[o01[q]]) + lh * ((1.f - lw) * sp[o10[q]] + lw * sp[o11[q]]);
+          acc = q == 0 ? v : acc + v;
+        }
+      }
+      const float e = softmax_px_exp_t(acc / cnt, best, it);
+      if (pass == 0) s = softmax_px_sum(s, e, c == 0);
+      else score_px_class(kind, bi, c, softmax_px_prob(e, s), sa, spb, snone);
+    }
+  conf[((long)b * H + y) * W + x] = score_px_finish(kind, sa, spb, snone, ilc);
+#endif
 #undef SLIDE_EXP
+#ifdef SLIDE_SCORE_DEFAULTED
+#undef SLIDE_SCORE
+#undef SLIDE_SCORE_DEFAULTED
+#endif

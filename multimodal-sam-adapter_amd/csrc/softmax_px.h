@@ -12,6 +12,13 @@
 //   acc_c = p_c (first view) | acc_c + p_c        softmax_px_accum, in view order
 //   acc_c / (float)A  after the last view         softmax_px_mean -- kept although it does not change the argmax of exact values: it can round two distinct
 //                                                 sums to the same float, and the first class must then win, as in the reference
+// The two uncertainty scores of a pixel beside its confidence p[bi] (bi = the class the map names), stated ONCE as well: both are formed from the float32
+// probabilities p_c above (one view: softmax_px_prob(e_c, s); several views: softmax_px_mean), so that the one-pass kernels and the canvas kernel
+// (argmax_score_nchw_kernel of csrc/segment.hip, which READS p_c) perform the same operations and agree bit for bit:
+//   kind 1, top-2 margin:   p[bi] - p2, p2 = the largest p_c over c != bi in class order with `>`; ONE float32 subtraction; C == 1: p[bi]
+//   kind 2, entropy score:  max(0, 1 - H * ilc), H = sum_c (p_c > 0 ? -(p_c * logf(p_c)) : 0) in class order from the first term (ocml's logf, as expf
+//                           above), `ilc` = float32(1 / log(float64(C))) made on the host (mmsa.evaluate.inv_log_classes), 0 for C == 1 (score 1)
+// Higher = more certain, in [0, 1], as the confidence is.  score_px_class is one class's step (class order), score_px_finish the pixel's score.
 // Include it AFTER `#pragma clang fp contract(off)`.
 #pragma once
 
@@ -22,3 +29,27 @@ __device__ __forceinline__ float softmax_px_sum(float s, float e, bool first) { 
 __device__ __forceinline__ float softmax_px_prob(float e, float s) { return e / s; }
 __device__ __forceinline__ float softmax_px_accum(float acc, float p, bool first) { return first ? p : acc + p; }
 __device__ __forceinline__ float softmax_px_mean(float acc, int A) { return acc / (float)A; }
+
+#define SCORE_MARGIN 1
+#define SCORE_ENTROPY 2
+__device__ __forceinline__ float score_px_second(float p2, float p, bool first) { return first || p > p2 ? p : p2; }
+__device__ __forceinline__ float score_px_margin(float pb, float p2) { return pb - p2; }
+__device__ __forceinline__ float score_px_h_term(float p) { return p > 0.f ? -(p * logf(p)) : 0.f; }
+__device__ __forceinline__ float score_px_h_sum(float h, float t, bool first) { return first ? t : h + t; }
+__device__ __forceinline__ float score_px_entropy(float h, float ilc) {
+  const float v = 1.f - h * ilc;
+  return v > 0.f ? v : 0.f;
+}
+// class c of the pixel, probability p: `a` is p2 (kind 1) or H (kind 2) so far, `pb` becomes p[bi], `none` = no class other than bi seen yet
+__device__ __forceinline__ void score_px_class(int kind, int bi, int c, float p, float& a, float& pb, bool& none) {
+  if (c == bi) pb = p;
+  if (kind == SCORE_MARGIN) {
+    if (c != bi) { a = score_px_second(a, p, none); none = false; }
+  } else {
+    a = score_px_h_sum(a, score_px_h_term(p), c == 0);
+  }
+}
+__device__ __forceinline__ float score_px_finish(int kind, float a, float pb, bool none, float ilc) {
+  if (kind == SCORE_MARGIN) return none ? pb : score_px_margin(pb, a);
+  return score_px_entropy(a, ilc);
+}

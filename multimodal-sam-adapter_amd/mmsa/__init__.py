@@ -7,6 +7,7 @@ from . import ops  # noqa: F401
 from . import inference  # noqa: F401  (encode_decode / slide_inference / argmax map of the reference's EncoderDecoder)
 from .inference import AugPlan, aug_class_map, aug_inference, probabilities  # noqa: F401  (test-time augmentation: aug_test)
 from .inference import argmax_max_map  # noqa: F401  (class map + confidence map of a probability canvas)
+from .inference import argmax_score_map  # noqa: F401  (class map + uncertainty map -- top-2 margin or entropy score -- of a probability canvas)
 from .backbone import OperandRangeError, SAMAdapterbimodalMixModNewInTwinConvNEW, SAMAdapterbimodalMixModNewInTwinConvNEWwithcp
 from .head import SegformerHead
 from .chains import AttentionRangeError, Chains, Replay
@@ -42,4 +43,4 @@ if not _HAVE_MMSEG:     # local registry (no mmseg in the process): nothing to o
 __all__ = ["SegformerHead", "HEADS", "build_head", "register_head", "SAMAdapterbimodalMixModNewInTwinConvNEW", "SAMAdapterbimodalMixModNewInTwinConvNEWwithcp",
            "BACKBONES", "build_backbone", "ops", "lib", "inference", "Chains", "Replay", "AttentionRangeError", "OperandRangeError",
            "preprocess", "Preprocess", "FrameFeeder", "evaluate", "Evaluator", "LabelPrep", "confusion", "Calibration", "calibration", "SelectiveEvaluator", "selective", "abstain", "TemperatureSweep", "temperature_sweep", "render", "Renderer",
-           "probabilities", "aug_inference", "aug_class_map", "AugPlan", "argmax_max_map"]
+           "probabilities", "aug_inference", "aug_class_map", "AugPlan", "argmax_max_map", "argmax_score_map"]

@@ -222,6 +222,17 @@ def inv_temperature(T):
     return float(it)
 
 
+SCORES = {"max": 0, "margin": 1, "entropy": 2}      # `score=` of the class-map entries -> `kind` of the score launches (0: the confidence launches)
+
+
+def inv_log_classes(C):
+    """The factor of the entropy score 1 - H / log C (csrc/softmax_px.h): float32(1 / log(float64(C))) -> a Python float that holds that float32 exactly; 0 for
+    one class, whose entropy is 0 and whose score is 1."""
+    if isinstance(C, bool) or not isinstance(C, (int, np.integer)) or int(C) < 1:
+        raise ValueError(f"mmsa.evaluate: {C!r} classes; a positive integer is expected")
+    return 0.0 if int(C) == 1 else float(np.float32(np.float64(1.0) / np.log(np.float64(int(C)))))
+
+
 def geometric_grid(lo, hi, J):
     """J temperatures from lo to hi with a constant ratio, float64 [J] (J == 1: [lo]); both ends are exact.  0 < lo <= hi, 1 <= J <= 16.  A first sweep
     over a wide grid and a second over geometric_grid(T / r, T * r, J) around its best() is the whole fit."""
@@ -354,6 +365,34 @@ def selective_metrics_of(counts, metric=("mIoU",), nan_to_num=None, beta=1):
                 warnings.simplefilter("ignore", RuntimeWarning)                   # "Mean of empty slice": a threshold where every class is NaN gives NaN
                 out["m" + key] = np.nanmean(out[key], axis=1)
     return out
+
+
+AUC_METRICS = ("risk", "mIoU", "aAcc")
+
+
+def selective_auc_of(counts, metric="risk"):
+    """The area under a selective curve of int64 [K, C + 1, C + 1] counts, one float64: `metric` = 'risk' (1 - aAcc: the AURC, lower is better), 'mIoU' or
+    'aAcc' (higher is better) against coverage, from the K points `selective_metrics_of` gives at the thresholds k / K.  The rule:
+      thresholds whose coverage is 0 are dropped (they keep nothing; their metric is NaN);
+      the others are taken in threshold order, which is coverage descending from coverage 1 at k = 0 (empty bins repeat a point: zero width);
+      the metric is integrated over coverage with the trapezoid rule between neighbouring points;
+      from the smallest non-zero coverage down to coverage 0 the curve is extended FLAT with that point's value (the bins cannot order the pixels inside
+        the top bin, so every coverage below it is served by a random subset of it, whose expected metric -- for aAcc and risk -- is the bin's own).
+    A NaN metric at a kept point makes the result NaN, and so does a curve without a kept point (no pixel took part).  The value is a mean of the metric over
+    coverage in [0, 1]: a score that ranks the errors last has a smaller AURC / a larger area under mIoU on the same maps."""
+    if metric not in AUC_METRICS:
+        raise ValueError(f"mmsa.evaluate: selective_auc_of(metric={metric!r}); one of {AUC_METRICS}")
+    m = selective_metrics_of(counts, metric=("mIoU",))
+    cov = m["coverage"]
+    val = 1.0 - m["aAcc"] if metric == "risk" else m[metric]
+    keep = cov > 0                                                        # False for NaN (nothing took part at all)
+    cov, val = cov[keep], np.asarray(val, dtype=np.float64)[keep]
+    if cov.size == 0:
+        return np.float64("nan")
+    area = np.float64(0.0)
+    for i in range(cov.size - 1):
+        area += (cov[i] - cov[i + 1]) * (val[i] + val[i + 1]) / 2.0
+    return np.float64(area + cov[-1] * val[-1])
 
 
 def reliability_counts_of(counts):
@@ -949,13 +988,22 @@ class SelectiveEvaluator(_SlotOwner):
         """`total_area_to_metrics` of the pixels kept at `min_bin`, over every slot or of one slot; at min_bin=0 Evaluator.metrics of the same maps."""
         return area_metrics(*areas_of(selective_counts_of(self._of(slot), min_bin)), metric=metric, nan_to_num=nan_to_num, beta=beta)
 
-    def summary(self, min_bin=0, slot=None, metric=("mIoU",), nan_to_num=None, beta=1):
-        """aAcc / mIoU / mAcc / ... of the pixels kept at `min_bin`, as Evaluator.summary rounds them."""
-        return summary_of(self.metrics(min_bin, slot, metric, nan_to_num, beta))
+    def summary(self, min_bin=0, slot=None, metric=("mIoU",), nan_to_num=None, beta=1, auc=False):
+        """aAcc / mIoU / mAcc / ... of the pixels kept at `min_bin`, as Evaluator.summary rounds them.  `auc=True`: the entry 'AURC' is added, `auc()` of the
+        risk over ALL bins (it does not depend on `min_bin`), rounded the same way; without it the summary is Evaluator.summary's, key for key."""
+        s = summary_of(self.metrics(min_bin, slot, metric, nan_to_num, beta))
+        if auc:
+            s["AURC"] = np.round(self.auc("risk", slot) * 100, 2) / 100.0
+        return s
 
     def coverage_curve(self, metric=("mIoU",), slot=None, nan_to_num=None, beta=1):
         """`selective_metrics_of`: coverage and every metric at every threshold k = 0 .. K - 1 (mIoU against coverage)."""
         return selective_metrics_of(self._of(slot), metric=metric, nan_to_num=nan_to_num, beta=beta)
+
+    def auc(self, metric="risk", slot=None):
+        """`selective_auc_of`: the area under coverage_curve()'s risk (AURC), mIoU or aAcc against coverage -- one number per score map, which is what says
+        which of confidence, margin and entropy score ranks the errors best on the data counted."""
+        return selective_auc_of(self._of(slot), metric)
 
 
 class TemperatureSweep(_SlotOwner):

@@ -16,6 +16,9 @@ classes of what `probabilities` / `aug_inference` return (ED:449,460), float32 [
 `selective=` (mmsa.evaluate.SelectiveEvaluator) of the same entries keeps one confusion matrix per confidence bin, likewise by one more launch: mIoU at a coverage.
 `temperature=` of the same entries (and of `probabilities`) writes the confidence of softmax(x / T) instead, by the `_t` sibling of whatever launch the plan takes; T
 comes from mmsa.evaluate.TemperatureSweep.  The class map does not depend on it, and `temperature=None` takes exactly the launches it always took.
+`score=` of the same entries ("max" | "margin" | "entropy") chooses what the confidence slot holds: the confidence, the top-2 margin P_(1) - P_(2) or the entropy
+score 1 - H / log C (csrc/softmax_px.h), each in [0, 1] with higher = more certain, so `calibration=` / `selective=` / `abstain` take any of them; the two new
+ones come from the `_score` sibling of the launch the plan takes (`argmax_score_map` on a probability canvas), and "max" takes exactly the launches it always took.
 
 What a frame's output looks like -- its windows, the size after the second resize and after the cut, which class-map kernel that takes -- is decided once,
 in `MapPlan`, a record without device state; the entries read the frame (`_intake`), make the plan, and launch from it."""
@@ -206,6 +209,15 @@ def _check_overlap(boxes, what):
 ONE_PASS_RESCALE_DEFAULT = dict(up=True, down=True)   # not measured yet (tools/exp/rescale_class_map_bench.py)
 
 
+# The same choice where the launch also writes an uncertainty score (`score=` "margin" / "entropy"): the one-pass kernel (mmsa_slide_argmax_resized_score)
+# recomputes the pixel's values in three passes, and the canvas path (_rescaled_map_canvas + mmsa_argmax_score_nchw; the same map and score bit for bit) wins
+# far outside the spread of the yardstick, the `confidence=True` launch on the same inputs (profiles/uncertainty.txt, 25 classes): 0.98 / 0.99 ms against
+# 1.95 / 1.96 ms for two 1024 x 1024 maps to 1200 x 1200 (margin / entropy), 0.88 / 0.90 ms against 3.53 / 3.52 ms for the six-window 1080 x 1920 frame to
+# 720 x 1280; the yardstick's p10 .. p90 spans 9 / 37 us.  One pass remains the choice where memory is: it allocates nothing, the canvas path three
+# [B, C, h, w] float32 arrays.  At the frame's own size there is no such choice: the one-pass launch (+ 4 .. 32 us over the confidence launch) is the only one.
+ONE_PASS_SCORE_RESCALE_DEFAULT = dict(up=False, down=False)
+
+
 _NO_CONF_FUSED = ("confidence with fused=True / return_map=False: the fused class-map + evaluation launch (mmsa_slide_argmax_eval) has no confidence variant; "
                   "with labels= the counts of a map with confidence go through the stored map (drop fused= / return_map=)")
 
@@ -247,6 +259,28 @@ def _inv_temperature(temperature, confidence, what):
                            "of x for every T > 0), only the confidence map does; pass confidence=True or an output tensor as well")
     from .evaluate import inv_temperature
     return inv_temperature(temperature)
+
+
+_NO_SCORE_AUG_ONE_PASS = ("with one_pass=True: the one-pass augmented launch (mmsa_aug_argmax_conf) has no score sibling; the margin and the entropy score of "
+                          "augmented views come from the canvas path (drop one_pass=, or pass one_pass=False)")
+
+
+def _score_kind(score, confidence, what):
+    """`score=` of an entry -> the `kind` of the score launches: 0 for "max" (the confidence launches, exactly as without `score=`), 1 for "margin" (top-2
+    margin), 2 for "entropy" (1 - H / log C); csrc/softmax_px.h.  Refused when unknown, and other than "max" without a confidence map (`confidence`: the
+    entry's `confidence=`, or the buffer), in whose place the score is written."""
+    from .evaluate import SCORES
+    if not isinstance(score, str) or score not in SCORES:
+        raise RuntimeError(f"mmsa.{what}: score= must be one of {tuple(SCORES)}, got {score!r}")
+    if SCORES[score] and (confidence is None or confidence is False):
+        raise RuntimeError(f"mmsa.{what}: score={score!r} without confidence=: the score is written in the confidence map's place and the class map does not "
+                           "depend on it; pass confidence=True or an output tensor as well")
+    return SCORES[score]
+
+
+def _inv_log_c(C):
+    from .evaluate import inv_log_classes
+    return inv_log_classes(int(C))
 
 
 def _check_binned(kw, cls, owner, labels, confidence, what, fused=None, return_map=True):
@@ -374,15 +408,18 @@ class MapPlan:
         outs = (out.data_ptr(),) if conf is None else (out.data_ptr(), conf.data_ptr())
         return (lg.data_ptr(), self.n, lg.shape[1], lg.shape[2], lg.shape[3], self.tab) + outs + (self.B, self.H, self.W, self.hc, self.wc)
 
-    def _plain(self, lg, out, unc, conf, it=None):
-        """mmsa_slide_argmax, or its sibling that also writes `conf`; `it` (an inverse temperature, with `conf`): mmsa_slide_argmax_conf_t."""
-        if it is None:
+    def _plain(self, lg, out, unc, conf, it=None, kind=0):
+        """mmsa_slide_argmax, or its sibling that also writes `conf`; `it` (an inverse temperature, with `conf`): mmsa_slide_argmax_conf_t; `kind` (1 / 2, with
+        `conf`): mmsa_slide_argmax_score, which always takes an inverse temperature (1.0 without `it`: the untempered softmax, exactly)."""
+        if kind:
+            lib.call("mmsa_slide_argmax_score", *self._args(lg, out, conf), unc.data_ptr(), kind, 1.0 if it is None else it, _inv_log_c(lg.shape[1]), ops._stream())
+        elif it is None:
             lib.call("mmsa_slide_argmax" if conf is None else "mmsa_slide_argmax_conf", *self._args(lg, out, conf), unc.data_ptr(), ops._stream())
         else:
             lib.call("mmsa_slide_argmax_conf_t", *self._args(lg, out, conf), unc.data_ptr(), it, ops._stream())
 
     def class_map(self, lg, out, unc, labels=None, evaluator=None, case=None, fused=None, return_map=True, one_pass=None, conf=None, calibration=None,
-                  selective=None, temperature=None):
+                  selective=None, temperature=None, score="max"):
         """The class-map launch of the three class-map calls, from the head-resolution logits lg [n, C, hs, ws] into out uint8 [B, Ho, Wo] and the
         uncovered-pixel word `unc`.  Without `labels`: mmsa_slide_argmax.  With `labels` (raw uint8 label maps [B, Hl, Wl]) and `evaluator`
         (mmsa.evaluate.Evaluator): the confusion counts of the map are ADDED to the evaluator's buffer as well -- by the same launch
@@ -401,7 +438,14 @@ class MapPlan:
         `temperature` (T > 0; needs `conf`): `conf` gets the confidence of softmax(logits / T), max_c of probabilities(..., temperature=T) bit for bit, from the
         `_t` sibling of the launch the plan takes (mmsa_slide_argmax_conf_t / mmsa_slide_argmax_resized_conf_t; on the canvas path
         mmsa_softmax_flip_accum_nchw_t); the map is the same for every T, and `calibration` / `selective` see the tempered confidence.  None: the launches
-        above, with the arguments above."""
+        above, with the arguments above.
+        `score` ("max" | "margin" | "entropy"; other than "max" needs `conf`): what `conf` gets -- the confidence above, the top-2 margin P_(1) - P_(2) or the
+        entropy score 1 - H / log C (csrc/softmax_px.h), each in [0, 1] with higher = more certain and 0 where the map is 255, so `calibration` / `selective`
+        take any of them.  "margin" / "entropy" go to the `_score` launch in the place of the `_conf` one (mmsa_slide_argmax_score /
+        mmsa_slide_argmax_resized_score; on the canvas path mmsa_argmax_score_nchw on the probabilities), with `temperature` as above: bit for bit the score of
+        probabilities(..., temperature=T).  At a rescaled size `one_pass=None` follows ONE_PASS_SCORE_RESCALE_DEFAULT for them (measured: the canvas path).
+        "max": the launches above, with the arguments above."""
+        kind = _score_kind(score, conf, "inference")
         it = _inv_temperature(temperature, conf, "inference")
         _check_calibration(calibration, labels, conf, "inference", fused, return_map)
         _check_selective(selective, labels, conf, "inference", fused, return_map)
@@ -414,15 +458,19 @@ class MapPlan:
             if fused or not return_map:
                 raise RuntimeError("mmsa.inference: fused=True / return_map=False need the fused class-map + evaluation launch, and that launch has no variant at "
                                    "a rescaled or cut size: the counts of a rescaled map go through the stored map (drop fused= / return_map=)")
-            if ONE_PASS_RESCALE_DEFAULT["up" if self.Hd * self.Wd > self.H * self.W else "down"] if one_pass is None else one_pass:
+            default = ONE_PASS_SCORE_RESCALE_DEFAULT if kind else ONE_PASS_RESCALE_DEFAULT
+            if default["up" if self.Hd * self.Wd > self.H * self.W else "down"] if one_pass is None else one_pass:
                 if conf is None:
                     lib.call("mmsa_slide_argmax_resized", *self._args(lg, out), *self.rs, unc.data_ptr(), ops._stream())
+                elif kind:
+                    lib.call("mmsa_slide_argmax_resized_score", *self._args(lg, out, conf), *self.rs, unc.data_ptr(), kind, 1.0 if it is None else it,
+                             _inv_log_c(lg.shape[1]), ops._stream())
                 elif it is None:
                     lib.call("mmsa_slide_argmax_resized_conf", *self._args(lg, out, conf), *self.rs, unc.data_ptr(), ops._stream())
                 else:
                     lib.call("mmsa_slide_argmax_resized_conf_t", *self._args(lg, out, conf), *self.rs, unc.data_ptr(), it, ops._stream())
             else:
-                _rescaled_map_canvas(self, lg, out, unc, conf, it)
+                _rescaled_map_canvas(self, lg, out, unc, conf, it, kind)
             if evaluator is not None:
                 evaluator.add(out, labels, case=case)
             _add_binned(out, conf, labels, case, calibration, selective)
@@ -432,11 +480,11 @@ class MapPlan:
         if labels is None and evaluator is None:
             if not return_map:
                 raise RuntimeError("mmsa.inference: return_map=False only makes sense with labels= and evaluator=")
-            self._plain(lg, out, unc, conf, it)
+            self._plain(lg, out, unc, conf, it, kind)
             return
         _check_labels(labels, evaluator, calibration, selective)
         if evaluator is None:                              # labels for the calibration / the selective evaluator alone
-            self._plain(lg, out, unc, conf, it)
+            self._plain(lg, out, unc, conf, it, kind)
             _add_binned(out, conf, labels, case, calibration, selective)
             return
         if fused is False and not return_map:
@@ -445,7 +493,7 @@ class MapPlan:
         if conf is None and ((evaluate.FUSED_DEFAULT or not return_map) if fused is None else fused):      # no map wanted: only the fused launch can leave it unwritten
             evaluator.add_fused(lg, self, out if return_map else None, unc, labels, case=case)
         else:
-            self._plain(lg, out, unc, conf, it)
+            self._plain(lg, out, unc, conf, it, kind)
             evaluator.add(out, labels, case=case)
         _add_binned(out, conf, labels, case, calibration, selective)
 
@@ -464,11 +512,12 @@ def _canvas_logits(plan, lg, unc):
     return _rescaled_logits(canvas, (plan.Hd, plan.Wd) if plan.resized else None)
 
 
-def _rescaled_map_canvas(plan, lg, out, unc, conf=None, it=None):
+def _rescaled_map_canvas(plan, lg, out, unc, conf=None, it=None, kind=0):
     """The rescaled class map the long way round: _canvas_logits, argmax, crop -- the launches slide_inference / encode_decode + argmax_map make.  With
     `conf`: also the softmax of the cut logits (what `probabilities` launches) and mmsa_argmax_max_nchw for its maximum.  The MAP stays the argmax of the
     logits, as without `conf` and as in the one-pass kernels: the softmax can round two distinct logits to one probability, and the first class would win.
-    `it` (an inverse temperature, with `conf`): the softmax of logits / T (mmsa_softmax_flip_accum_nchw_t)."""
+    `it` (an inverse temperature, with `conf`): the softmax of logits / T (mmsa_softmax_flip_accum_nchw_t).
+    `kind` (1 / 2, with `conf`): mmsa_argmax_score_nchw in the place of mmsa_argmax_max_nchw -- the margin or the entropy score of those probabilities."""
     y = _canvas_logits(plan, lg, unc)
     out.copy_(argmax_map(y)[:, :plan.Ho, :plan.Wo])
     if conf is None:
@@ -476,13 +525,17 @@ def _rescaled_map_canvas(plan, lg, out, unc, conf=None, it=None):
     y = y[:, :, :plan.Ho, :plan.Wo].contiguous()
     prob = torch.empty_like(y)
     _softmax_accum(y, prob, it=it)
-    _argmax_max_into(prob, torch.empty_like(out), conf)
+    if kind:
+        _argmax_score_into(prob, torch.empty_like(out), conf, kind)
+    else:
+        _argmax_max_into(prob, torch.empty_like(out), conf)
 
 
 @_on_device
 @torch.no_grad()
 def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preprocess=None, labels=None, evaluator=None, case=None, fused=None,
-                    return_map=True, render=None, ori_shape=None, one_pass=None, confidence=False, calibration=None, selective=None, temperature=None):
+                    return_map=True, render=None, ori_shape=None, one_pass=None, confidence=False, calibration=None, selective=None, temperature=None,
+                    score="max"):
     """`simple_test` of a sliding-window frame (ED:191-234 + ED:449,477) -> uint8 class map [B, H, W], without the
     [B, classes, H, W] logits canvas: every window's logits stay at head resolution and ONE kernel (mmsa_slide_argmax) resizes,
     sums the overlapping windows in window order, divides by the count and takes the argmax -- the same additions in the same order
@@ -509,7 +562,13 @@ def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preproc
     and `calibration=` are optional next to it, and what is returned does not change.
     `temperature=` (T > 0, from mmsa.evaluate.TemperatureSweep.best(); needs `confidence=`): the confidence map is that of softmax(logits / T) --
     probabilities(..., temperature=T).max(1).values bit for bit -- written by the `_t` sibling of the same launch; the map is the same for every T, and
-    `calibration=` / `selective=` see the tempered confidence.  Without `confidence=` it is refused: the map does not depend on it."""
+    `calibration=` / `selective=` see the tempered confidence.  Without `confidence=` it is refused: the map does not depend on it.
+    `score=` "max" (the confidence above), "margin" (the top-2 margin P_(1) - P_(2)) or "entropy" (1 - H / log C, H the predictive entropy): what the map in
+    the confidence slot holds -- each in [0, 1], higher = more certain, 0 where the map is 255, written by the launch that writes the class map
+    (mmsa_slide_argmax_score) or, with `ori_shape=`, by mmsa_argmax_score_nchw on the canvas path's probabilities -- the default there, being the faster of the
+    two where measured (ONE_PASS_SCORE_RESCALE_DEFAULT) -- or by mmsa_slide_argmax_resized_score (`one_pass=True`: no canvas in memory); the same bits either way.
+    `temperature=` combines with it; `calibration=` / `selective=` see whatever score was written.  Other than "max" it is refused without `confidence=`."""
+    _score_kind(score, confidence, "slide_class_map")
     _inv_temperature(temperature, confidence, "slide_class_map")
     _check_calibration(calibration, labels, confidence, "slide_class_map", fused, return_map)
     _check_selective(selective, labels, confidence, "slide_class_map", fused, return_map)
@@ -526,7 +585,7 @@ def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preproc
     lg = lgs[0] if len(lgs) == 1 else torch.cat(lgs, 0)
     out = torch.empty(B, plan.Ho, plan.Wo, dtype=torch.uint8, device=device)
     unc = torch.zeros(1, dtype=torch.int32, device=device)
-    plan.class_map(lg, out, unc, labels, evaluator, case, fused, return_map, one_pass, conf, calibration, selective, temperature)
+    plan.class_map(lg, out, unc, labels, evaluator, case, fused, return_map, one_pass, conf, calibration, selective, temperature, score)
     r = (out, unc, render(out, src)) if render is not None else ((out if return_map else None), unc)   # unc[0] != 0 <=> some pixel is not covered (ED:220); checked by the caller outside a capture
     return r if conf is None else r + (conf,)
 
@@ -534,7 +593,8 @@ def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preproc
 @_on_device
 @torch.no_grad()
 def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator=None, case=None, fused=None, return_map=True, render=None,
-                    ori_shape=None, dim=None, cut_dim=None, rescale=True, one_pass=None, confidence=False, calibration=None, selective=None, temperature=None):
+                    ori_shape=None, dim=None, cut_dim=None, rescale=True, one_pass=None, confidence=False, calibration=None, selective=None, temperature=None,
+                    score="max"):
     """Whole-image `simple_test`: resize x4 (bilinear, align_corners=False) + argmax fused (ED:90-94,449,477) -> uint8 [B, H, W].
     `preprocess=` (mmsa.preprocess.Preprocess): img is the pair (rgb, aux) of raw frames, normalised (and padded) by one launch.
     `labels=` + `evaluator=` (+ `case=`): as in slide_class_map.
@@ -551,7 +611,9 @@ def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator
     `confidence=`: as in slide_class_map; the confidence map float32 [B, Ho, Wo] comes as the last element, (map[, picture], conf).
     `calibration=`: as in slide_class_map (needs `labels=` and `confidence=`); at a rescaled or cut size the pass reads the map and confidence stored there.
     `selective=`: as in slide_class_map (needs `labels=` and `confidence=`), over the map and confidence stored at the size returned.
-    `temperature=`: as in slide_class_map (needs `confidence=`): the confidence of softmax(logits / T) at the size returned."""
+    `temperature=`: as in slide_class_map (needs `confidence=`): the confidence of softmax(logits / T) at the size returned.
+    `score=`: as in slide_class_map ("margin" / "entropy" need `confidence=`): the map in the confidence slot is that score, at the size returned."""
+    _score_kind(score, confidence, "whole_class_map")
     _inv_temperature(temperature, confidence, "whole_class_map")
     _check_calibration(calibration, labels, confidence, "whole_class_map", fused, return_map)
     _check_selective(selective, labels, confidence, "whole_class_map", fused, return_map)
@@ -573,7 +635,7 @@ def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator
     lg = head(feats)
     out = torch.empty(B, plan.Ho, plan.Wo, dtype=torch.uint8, device=img.device)
     unc = torch.zeros(1, dtype=torch.int32, device=img.device)
-    plan.class_map(lg, out, unc, labels, evaluator, case, fused, return_map, one_pass, conf, calibration, selective, temperature)
+    plan.class_map(lg, out, unc, labels, evaluator, case, fused, return_map, one_pass, conf, calibration, selective, temperature, score)
     if render is not None:
         return (out, render(out, src)) if conf is None else (out, render(out, src), conf)
     if conf is not None:
@@ -642,7 +704,7 @@ def inference(backbone, head, img, test_cfg, rescale=True, preprocess=None, ori_
 @_on_device
 @torch.no_grad()
 def class_map(backbone, head, img, test_cfg, rescale=True, ori_shape=None, preprocess=None, labels=None, evaluator=None, case=None, render=None, one_pass=None,
-              confidence=False, calibration=None, selective=None, temperature=None):
+              confidence=False, calibration=None, selective=None, temperature=None, score="max"):
     """`simple_test` (ED:471-477) by mode: the dispatch of `inference` (ED:417-447) onto the class-map calls -> uint8 map, bit for bit
     argmax_map(inference(...)) of the same arguments, without a logits canvas: [B, H, W], or at the size `rescale` gives ('slide' / 'whole': `ori_shape`;
     'whole_dim': test_cfg['dim']; 'whole_dim_cut': the crop of the map at `dim`, or at the input size without `rescale`).  What `inference` refuses is
@@ -652,13 +714,15 @@ def class_map(backbone, head, img, test_cfg, rescale=True, ori_shape=None, prepr
     `confidence=` (True or an output tensor): the confidence map, probabilities(...).max(1).values bit for bit, as the last element: (map[, picture], conf).
     `calibration=` (mmsa.evaluate.Calibration; needs `labels=` and `confidence=`): as in the calls it goes to.
     `selective=` (mmsa.evaluate.SelectiveEvaluator; needs `labels=` and `confidence=`): as in the calls it goes to.
-    `temperature=` (T > 0; needs `confidence=`): the confidence of softmax(logits / T), as in the calls it goes to."""
+    `temperature=` (T > 0; needs `confidence=`): the confidence of softmax(logits / T), as in the calls it goes to.
+    `score=` ("max" | "margin" | "entropy"; other than "max" needs `confidence=`): what the confidence slot holds, as in the calls it goes to."""
     mode = test_cfg["mode"]
+    _score_kind(score, confidence, "class_map")
     _inv_temperature(temperature, confidence, "class_map")
     _check_calibration(calibration, labels, confidence, "class_map")
     _check_selective(selective, labels, confidence, "class_map")
     kw = dict(preprocess=preprocess, labels=labels, evaluator=evaluator, case=case, render=render, one_pass=one_pass, confidence=confidence,
-              calibration=calibration, selective=selective, temperature=temperature)
+              calibration=calibration, selective=selective, temperature=temperature, score=score)
     if mode == "slide":
         r = slide_class_map(backbone, head, img, tuple(test_cfg["crop_size"]), tuple(test_cfg["stride"]), ori_shape=ori_shape if rescale else None, **kw)
         if int(r[1].item()) != 0:
@@ -691,6 +755,11 @@ def _argmax_max_into(prob, out, conf):
     lib.call("mmsa_argmax_max_nchw", prob.data_ptr(), out.data_ptr(), conf.data_ptr(), B, C, H * W, ops._stream())
 
 
+def _argmax_score_into(prob, out, score, kind):
+    B, C, H, W = prob.shape
+    lib.call("mmsa_argmax_score_nchw", prob.data_ptr(), out.data_ptr(), score.data_ptr(), B, C, H, W, kind, _inv_log_c(C), ops._stream())
+
+
 @_on_device
 @torch.no_grad()
 def argmax_max_map(prob):
@@ -702,6 +771,25 @@ def argmax_max_map(prob):
     out = torch.empty(B, H, W, dtype=torch.uint8, device=prob.device)
     conf = torch.empty(B, H, W, dtype=torch.float32, device=prob.device)
     _argmax_max_into(prob, out, conf)
+    return out, conf
+
+
+@_on_device
+@torch.no_grad()
+def argmax_score_map(prob, score="margin"):
+    """argmax_max_map with an uncertainty score in the maximum's place -> (uint8 [B, H, W], float32 [B, H, W]), one launch (mmsa_argmax_score_nchw) on a
+    canvas of probabilities (`probabilities` / `aug_inference`): `score=` "margin", the top-2 margin P_(1) - P_(2), or "entropy", 1 - H / log C with H the
+    predictive entropy -- on the mean probabilities of augmented views, the usual TTA uncertainty.  Both lie in [0, 1], higher = more certain.  "max" is
+    argmax_max_map itself."""
+    kind = _score_kind(score, True, "argmax_score_map")
+    if not kind:
+        return argmax_max_map(prob)
+    _check(prob)
+    prob = prob.contiguous()
+    B, C, H, W = prob.shape
+    out = torch.empty(B, H, W, dtype=torch.uint8, device=prob.device)
+    conf = torch.empty(B, H, W, dtype=torch.float32, device=prob.device)
+    _argmax_score_into(prob, out, conf, kind)
     return out, conf
 
 
@@ -879,18 +967,25 @@ class AugPlan:
             _softmax_accum(y, acc, f, accumulate=a > 0, finish_div=self.A if a == self.A - 1 else 0)
         return acc
 
-    def class_map(self, lgs, out, unc, one_pass=None, conf=None):
+    def class_map(self, lgs, out, unc, one_pass=None, conf=None, score="max"):
         """The class map of the views' head-resolution logits `lgs` (one [n_a, C, hs_a, ws_a] per view) into out uint8 [B, Ho, Wo] and the uncovered-pixel
         word `unc`: ONE launch (mmsa_aug_argmax; no host sync, no allocation once the table is on the device) where `one_pass=True` / ONE_PASS_AUG_DEFAULT
         say so and the classes fit the kernel (at most MAX_AUG_CLASSES), else the canvas path + argmax_map.  The same map bit for bit.
         `conf` (a contiguous float32 [B, Ho, Wo] tensor on the map's device): the confidence map max_c of the mean probabilities is written too, by
-        mmsa_aug_argmax_conf or, on the canvas path, by mmsa_argmax_max_nchw in place of mmsa_argmax_nchw: bit for bit mean_probabilities(...).max(1)."""
+        mmsa_aug_argmax_conf or, on the canvas path, by mmsa_argmax_max_nchw in place of mmsa_argmax_nchw: bit for bit mean_probabilities(...).max(1).
+        `score` ("margin" / "entropy", with `conf`): the top-2 margin or the entropy score of the MEAN probabilities goes to `conf` instead, by
+        mmsa_argmax_score_nchw on the canvas path, whatever ONE_PASS_AUG_DEFAULT says; `one_pass=True` is refused (mmsa_aug_argmax_conf has no sibling)."""
+        kind = _score_kind(score, conf, "inference")
+        if kind and one_pass:
+            raise RuntimeError(f"mmsa.inference: score={score!r} {_NO_SCORE_AUG_ONE_PASS}")
         if conf is not None:
             _check_conf(conf, self.size, out.device)
         if len(lgs) != self.A or any(lg.shape[0] != p.n for lg, p in zip(lgs, self.plans)):
             raise RuntimeError("mmsa.inference: AugPlan.class_map takes one logits tensor per view, one row per window of that view")
         C = int(lgs[0].shape[1])
-        if (ONE_PASS_AUG_DEFAULT and C <= MAX_AUG_CLASSES) if one_pass is None else one_pass:
+        if kind:
+            _argmax_score_into(self.mean_probabilities(lgs, unc), out, conf, kind)
+        elif (ONE_PASS_AUG_DEFAULT and C <= MAX_AUG_CLASSES) if one_pass is None else one_pass:
             lgs = [lg.contiguous() for lg in lgs]
             ptrs = (ctypes.c_void_p * self.A)(*[lg.data_ptr() for lg in lgs])
             rows = (ctypes.c_int * (11 * self.A))(*[v for r in self.rows(lgs) for v in r])
@@ -950,7 +1045,7 @@ def aug_inference(backbone, head, imgs, test_cfg, ori_shape=None, flips=None, pr
 @_on_views_device
 @torch.no_grad()
 def aug_class_map(backbone, head, imgs, test_cfg, ori_shape=None, flips=None, preprocess=None, max_batch=8, labels=None, evaluator=None, case=None,
-                  one_pass=None, confidence=False, calibration=None, selective=None):
+                  one_pass=None, confidence=False, calibration=None, selective=None, score="max"):
     """`aug_test` (ED:509-546) -> (uint8 class map [B, Ho, Wo], uncovered-pixel word), bit for bit argmax_map(aug_inference(...)) of the same arguments.
     Every view goes through backbone and head (`max_batch` windows per call, per view); then ONE launch (mmsa_aug_argmax) resizes every view's
     head-resolution logits as `class_map` would, takes the softmax, un-flips, averages over the views and takes the argmax, with no logits or probability
@@ -962,7 +1057,12 @@ def aug_class_map(backbone, head, imgs, test_cfg, ori_shape=None, flips=None, pr
     aug_inference(...).max(1).values, 0 where the map is 255 -- from the same launch, as the last element: (map, unc, conf).
     `calibration=` (mmsa.evaluate.Calibration; needs `labels=` and `confidence=`, `evaluator=` is optional with it): the reliability bins of the averaged map
     and its confidence are added to it by one more launch over the stored map and confidence.
-    `selective=` (mmsa.evaluate.SelectiveEvaluator; needs `labels=` and `confidence=`): the averaged map's confusion counts per confidence bin, likewise."""
+    `selective=` (mmsa.evaluate.SelectiveEvaluator; needs `labels=` and `confidence=`): the averaged map's confusion counts per confidence bin, likewise.
+    `score=` "max" | "margin" | "entropy" (other than "max" needs `confidence=`): the map in the confidence slot is the top-2 margin or the entropy score
+    1 - H / log C of the MEAN probabilities -- the usual TTA uncertainty -- bit for bit argmax_score_map(aug_inference(...), score)[1].  Those two go through
+    the canvas path (mmsa_argmax_score_nchw), whatever the default; with `one_pass=True` they are refused: mmsa_aug_argmax_conf has no score sibling."""
+    if _score_kind(score, confidence, "aug_class_map") and one_pass:
+        raise RuntimeError(f"mmsa.aug_class_map: score={score!r} {_NO_SCORE_AUG_ONE_PASS}")
     _check_calibration(calibration, labels, confidence, "aug_class_map")
     _check_selective(selective, labels, confidence, "aug_class_map")
     _check_labels(labels, evaluator, calibration, selective)
@@ -982,7 +1082,7 @@ def aug_class_map(backbone, head, imgs, test_cfg, ori_shape=None, flips=None, pr
     B, Ho, Wo = plan.size
     out = torch.empty(B, Ho, Wo, dtype=torch.uint8, device=device)
     unc = torch.zeros(1, dtype=torch.int32, device=device)
-    plan.class_map(lgs, out, unc, one_pass, conf)
+    plan.class_map(lgs, out, unc, one_pass, conf, score)
     if evaluator is not None:
         evaluator.add(out, labels, case=case)
     _add_binned(out, conf, labels, case, calibration, selective)
@@ -1011,8 +1111,8 @@ class FrameResult:
         return self._runner.pic
 
     def confidence(self):
-        """The frame's confidence map float32 [B, H, W] of a runner made with confidence=True -- verified, exactly as outputs() is.  The runner's static
-        buffer: read it before the next run()."""
+        """The frame's confidence map float32 [B, H, W] of a runner made with confidence=True -- or the score the runner was made with (`score=`) -- verified,
+        exactly as outputs() is.  The runner's static buffer: read it before the next run()."""
         if self._runner.conf is None:
             raise RuntimeError("mmsa.FrameResult.confidence: the SlideRunner was made without confidence=True")
         self._replay._owner._verify(self._replay.seq)
@@ -1036,13 +1136,16 @@ class SlideRunner:
     With `confidence=True` every run() also writes the frame's confidence map (slide_class_map's `confidence=`) into a static float32 [B, h, w] buffer, by the
     `_conf` sibling of the class-map launch: FrameResult.confidence().  Such a runner refuses run(fused=True) and run(return_map=False).
     With `temperature=` (T > 0; needs confidence=True) that confidence is the one of softmax(logits / T) (slide_class_map's `temperature=`).  It belongs to the
-    runner and not to run(): the scalar is an argument of the launch, and a captured launch keeps the one it was captured with."""
+    runner and not to run(): the scalar is an argument of the launch, and a captured launch keeps the one it was captured with.
+    With `score=` "margin" / "entropy" (needs confidence=True) the static buffer FrameResult.confidence() returns holds that score instead (slide_class_map's
+    `score=`), by the `_score` sibling of the class-map launch; it belongs to the runner for the same reason."""
 
     def __init__(self, backbone, head, frame, crop_size, stride, chains=2, check_every=1, preprocess=None, render=None, ori_shape=None, one_pass=None,
-                 confidence=False, temperature=None):
+                 confidence=False, temperature=None, score="max"):
         from .chains import Chains
+        _score_kind(score, confidence, "SlideRunner")
         _inv_temperature(temperature, confidence, "SlideRunner")
-        self.preprocess, self.render, self.one_pass, self.temperature = preprocess, render, one_pass, temperature
+        self.preprocess, self.render, self.one_pass, self.temperature, self.score = preprocess, render, one_pass, temperature, score
         B, H, W, self.device, self.frame, self._cut = _intake(frame, preprocess, "SlideRunner")
         self.plan = plan = MapPlan.slide(B, H, W, tuple(crop_size), stride, ori_shape, what="SlideRunner")
         if render is not None:
@@ -1094,7 +1197,7 @@ class SlideRunner:
             lg = rp.unverified          # the argmax kernel below is enqueued behind the pass; nothing is read on the host before outputs() verifies it
             self.unc.zero_()
             self.plan.class_map(lg, self.out, self.unc, labels, evaluator, case, fused, return_map, self.one_pass, self.conf, calibration, selective,
-                                self.temperature)
+                                self.temperature, self.score)
             if self.render is not None:
                 self.render(self.out, src, out=self.pic)
         return FrameResult(self, rp, has_map=return_map)

@@ -97,6 +97,9 @@ SIGNATURES = {
     "mmsa_slide_argmax_resized_conf_t": [P, I, I, I, I, P, P, P, I, I, I, I, I, I, I, I, I, P, F, P],
     "mmsa_softmax_flip_accum_nchw_t": [P, P, I, I, I, I, I, I, I, F, P],
     "mmsa_temperature_sweep_nchw": [P, P, I, I, I, I, I, I, P, P, P, P, I, P, I, I, P, P],
+    "mmsa_argmax_score_nchw": [P, P, P, I, I, I, I, I, F, P],
+    "mmsa_slide_argmax_score": [P, I, I, I, I, P, P, P, I, I, I, I, I, P, I, F, F, P],
+    "mmsa_slide_argmax_resized_score": [P, I, I, I, I, P, P, P, I, I, I, I, I, I, I, I, I, P, I, F, F, P],
     "mmsa_slide_argmax_eval": [P, I, I, I, I, P, P, I, I, I, I, I, P, P, I, I, P, P, P, P, I, P, P],
     "mmsa_render_u8": [P, L, L, I, I, I, P, I, I, P, I, I, I, c_double, c_double, P, P],
     "mmsa_render_denorm_f32": [P, L, L, I, I, I, P, I, I, P, I, I, I, P, P, I, I, c_double, c_double, P, P],
