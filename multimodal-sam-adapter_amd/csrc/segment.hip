@@ -128,17 +128,9 @@ extern "C" int mmsa_crop_batch_nchw(const float* src, int B, int C, int H, int W
 // the whole-image `resize x4 + argmax` of ED:90-94,477.  Pixels no window covers make the call fail (ED:220 asserts the same).
 __global__ __launch_bounds__(256) void slide_argmax_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
                                                            int H, int W, int hc, int wc, float rh, float rw, WindowTable wt, int* __restrict__ uncovered) {
-#define SLIDE_EVAL 0
-#define SLIDE_CONF 0
-#define SLIDE_TEMP 0
 #define SLIDE_Y blockIdx.y
 #define SLIDE_EXIT return
 #include "slide_pixel.inc"
-#undef SLIDE_EVAL
-#undef SLIDE_CONF
-#undef SLIDE_TEMP
-#undef SLIDE_Y
-#undef SLIDE_EXIT
 }
 
 // slide_argmax_kernel + the confusion counts of its class map in the same pass (csrc/evaluate.hip does the same from a stored map): the workgroup's
@@ -158,21 +150,14 @@ __global__ __launch_bounds__(256) void slide_argmax_eval_kernel(const float* __r
   const int row1 = min(H, ((int)blockIdx.y + 1) * SLIDE_EVAL_ROWS);
   for (int row = (int)blockIdx.y * SLIDE_EVAL_ROWS; row < row1; ++row) {
 #define SLIDE_EVAL 1
-#define SLIDE_CONF 0
-#define SLIDE_TEMP 0
 #define SLIDE_Y row
 #define SLIDE_EXIT continue
 #include "slide_pixel.inc"
-#undef SLIDE_EVAL
-#undef SLIDE_CONF
-#undef SLIDE_TEMP
-#undef SLIDE_Y
-#undef SLIDE_EXIT
   }
   eval_hist_flush(eval_lds, ev.counts + (long)es.s[blockIdx.z] * nbins, nbins);
 }
 
-// (mmsa_slide_argmax: below, with mmsa_slide_argmax_conf and the launch helper they share)
+// (mmsa_slide_argmax: at the end of the file, with its siblings and the launcher they share)
 extern "C" int mmsa_slide_argmax_eval(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out /* or NULL */,
                                       int B, int H, int W, int hc, int wc, int* uncovered, const unsigned char* label, int Hl, int Wl,
                                       const unsigned char* lut, const int* ymap, const int* xmap, const int* slots /* HOST [B] */, int n_slots,
@@ -276,7 +261,7 @@ __global__ __launch_bounds__(256) void slide_argmax_resized_kernel(const float* 
   slide_resized_pixel<false>(logits, C, hs, ws, out, nullptr, H, W, hc, wc, rh, rw, Hcut, Wcut, rh2, rw2, wt, uncovered);
 }
 
-// (mmsa_slide_argmax_resized: below, with mmsa_slide_argmax_resized_conf and the launch helper they share)
+// (mmsa_slide_argmax_resized: at the end of the file, with its siblings and the launcher they share)
 
 // ---- confidence maps: the probability of the predicted class next to every class map, conf[b, y, x] = max_c P[b, c, y, x] with P the probabilities of
 // EncoderDecoder.inference (F.softmax(seg_logit, dim=1), ED:449,460), written by the launch that writes the map.  The arithmetic is csrc/softmax_px.h:
@@ -323,17 +308,10 @@ extern "C" int mmsa_argmax_max_nchw(const float* x, unsigned char* out, float* m
 __global__ __launch_bounds__(256) void slide_argmax_conf_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
                                                                 float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, WindowTable wt,
                                                                 int* __restrict__ uncovered) {
-#define SLIDE_EVAL 0
 #define SLIDE_CONF 1
-#define SLIDE_TEMP 0
 #define SLIDE_Y blockIdx.y
 #define SLIDE_EXIT return
 #include "slide_pixel.inc"
-#undef SLIDE_EVAL
-#undef SLIDE_CONF
-#undef SLIDE_TEMP
-#undef SLIDE_Y
-#undef SLIDE_EXIT
 }
 
 __global__ __launch_bounds__(256) void slide_argmax_conf_lds_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
@@ -341,68 +319,10 @@ __global__ __launch_bounds__(256) void slide_argmax_conf_lds_kernel(const float*
                                                                     int* __restrict__ uncovered) {
   extern __shared__ float conf_lds[];
   float* conf_col = conf_lds + threadIdx.x;      // private to the lane: no barrier
-#define SLIDE_EVAL 0
 #define SLIDE_CONF 2
-#define SLIDE_TEMP 0
 #define SLIDE_Y blockIdx.y
 #define SLIDE_EXIT return
 #include "slide_pixel.inc"
-#undef SLIDE_EVAL
-#undef SLIDE_CONF
-#undef SLIDE_TEMP
-#undef SLIDE_Y
-#undef SLIDE_EXIT
-}
-
-// The tempered siblings of the three confidence kernels (the confidence of softmax(x / T), `it` = the inverse temperature): defined at the END of the file, below
-// every kernel that was here before them, so that those keep their place and their instruction streams (profiles/temperature_isa.txt).
-__global__ void slide_argmax_conf_t_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out, float* __restrict__ conf, int H,
-                                           int W, int hc, int wc, float rh, float rw, WindowTable wt, int* __restrict__ uncovered, float it);
-__global__ void slide_argmax_conf_lds_t_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out, float* __restrict__ conf,
-                                               int H, int W, int hc, int wc, float rh, float rw, WindowTable wt, int* __restrict__ uncovered, float it);
-__global__ void slide_argmax_resized_conf_t_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out, float* __restrict__ conf,
-                                                   int H, int W, int hc, int wc, float rh, float rw, int Hcut, int Wcut, float rh2, float rw2, WindowTable wt,
-                                                   int* __restrict__ uncovered, float it);
-
-// the checks and the launch of mmsa_slide_argmax, mmsa_slide_argmax_conf and mmsa_slide_argmax_conf_t; `conf` given: the LDS-column form where it fits, the
-// second-pass form otherwise; `it` given (with `conf`): the tempered sibling of that form
-static int slide_argmax_launch(const char* name, const float* logits, int n, int C, int hs, int ws, const int* windows, unsigned char* out, float* conf, int B, int H,
-                               int W, int hc, int wc, int* uncovered, hipStream_t stream, const float* it = nullptr) {
-  MMSA_CHECK_ARG(logits && out && uncovered && C > 0 && C <= 255 && hs > 0 && ws > 0 && hc > 0 && wc > 0 && B > 0 && H <= 65535 && B <= 65535, "%s: bad args", name);
-  if (it) MMSA_CHECK_INV_TEMPERATURE(name, *it);
-  WindowTable wt;
-  int rc = fill_windows(wt, windows, n, B, H, W, hc, wc, name);
-  if (rc) return rc;
-#ifdef MMSA_CONF_SECOND_PASS      // measurement build only (tools/exp/confidence_bench.py): the second-pass form for every C
-  const bool lds = false;
-#else
-  const bool lds = C <= SLIDE_CONF_LDS_CLASSES;
-#endif
-  const dim3 grid(cdiv(W, 256), H, B);
-  const float rh = (float)hs / (float)hc, rw = (float)ws / (float)wc;
-  if (!conf) hipLaunchKernelGGL(slide_argmax_kernel, grid, dim3(256), 0, stream, logits, C, hs, ws, out, H, W, hc, wc, rh, rw, wt, uncovered);
-  else if (it && lds)
-    hipLaunchKernelGGL(slide_argmax_conf_lds_t_kernel, grid, dim3(256), (size_t)C * 256 * sizeof(float), stream, logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, wt,
-                       uncovered, *it);
-  else if (it)
-    hipLaunchKernelGGL(slide_argmax_conf_t_kernel, grid, dim3(256), 0, stream, logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, wt, uncovered, *it);
-  else if (lds)
-    hipLaunchKernelGGL(slide_argmax_conf_lds_kernel, grid, dim3(256), (size_t)C * 256 * sizeof(float), stream, logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, wt,
-                       uncovered);
-  else hipLaunchKernelGGL(slide_argmax_conf_kernel, grid, dim3(256), 0, stream, logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, wt, uncovered);
-  MMSA_CHECK_LAUNCH(name);
-  return MMSA_OK;
-}
-
-extern "C" int mmsa_slide_argmax(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out,
-                                 int B, int H, int W, int hc, int wc, int* uncovered /* device int, zeroed by the caller */, hipStream_t stream) {
-  return slide_argmax_launch("slide_argmax", logits, n, C, hs, ws, windows, out, nullptr, B, H, W, hc, wc, uncovered, stream);
-}
-
-extern "C" int mmsa_slide_argmax_conf(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out, float* conf,
-                                      int B, int H, int W, int hc, int wc, int* uncovered /* device int, zeroed by the caller */, hipStream_t stream) {
-  MMSA_CHECK_ARG(conf, "slide_argmax_conf: bad args");
-  return slide_argmax_launch("slide_argmax_conf", logits, n, C, hs, ws, windows, out, conf, B, H, W, hc, wc, uncovered, stream);
 }
 
 // slide_argmax_resized_kernel + the confidence map at the rescaled / cut size: conf = max_c softmax(resized)[c] (ED:449,460), slot form and scanning form.
@@ -412,61 +332,17 @@ __global__ __launch_bounds__(256) void slide_argmax_resized_conf_kernel(const fl
   slide_resized_pixel<true>(logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, Hcut, Wcut, rh2, rw2, wt, uncovered);
 }
 
-// the checks and the launch of mmsa_slide_argmax_resized, mmsa_slide_argmax_resized_conf and mmsa_slide_argmax_resized_conf_t; `conf` given:
-// slide_argmax_resized_conf_kernel; `it` given (with `conf`): slide_argmax_resized_conf_t_kernel
-static int slide_argmax_resized_launch(const char* name, const float* logits, int n, int C, int hs, int ws, const int* windows, unsigned char* out, float* conf, int B,
-                                       int H, int W, int hc, int wc, int Hd, int Wd, int Hcut, int Wcut, int* uncovered, hipStream_t stream,
-                                       const float* it = nullptr) {
-  MMSA_CHECK_ARG(logits && out && uncovered && C > 0 && C <= 255 && hs > 0 && ws > 0 && hc > 0 && wc > 0 && B > 0 && H > 0 && W > 0 && B <= 65535, "%s: bad args", name);
-  if (it) MMSA_CHECK_INV_TEMPERATURE(name, *it);
-  MMSA_CHECK_ARG(Hd > 0 && Wd > 0 && Hcut > 0 && Wcut > 0 && Hcut <= Hd && Wcut <= Wd && Hcut <= 65535,
-                 "%s: the cut %dx%d must lie inside the target %dx%d (and have at most 65535 rows)", name, Hcut, Wcut, Hd, Wd);
-  WindowTable wt;
-  int rc = fill_windows(wt, windows, n, B, H, W, hc, wc, name);
-  if (rc) return rc;
-  const dim3 grid(cdiv(Wcut, 256), Hcut, B);
-  const float rh = (float)hs / (float)hc, rw = (float)ws / (float)wc, rh2 = (float)H / (float)Hd, rw2 = (float)W / (float)Wd;
-  if (conf && it)
-    hipLaunchKernelGGL(slide_argmax_resized_conf_t_kernel, grid, dim3(256), 0, stream, logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, Hcut, Wcut, rh2, rw2, wt,
-                       uncovered, *it);
-  else if (conf)
-    hipLaunchKernelGGL(slide_argmax_resized_conf_kernel, grid, dim3(256), 0, stream, logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, Hcut, Wcut, rh2, rw2, wt,
-                       uncovered);
-  else hipLaunchKernelGGL(slide_argmax_resized_kernel, grid, dim3(256), 0, stream, logits, C, hs, ws, out, H, W, hc, wc, rh, rw, Hcut, Wcut, rh2, rw2, wt, uncovered);
-  MMSA_CHECK_LAUNCH(name);
-  return MMSA_OK;
-}
-
-extern "C" int mmsa_slide_argmax_resized(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out,
-                                         int B, int H, int W, int hc, int wc, int Hd, int Wd, int Hcut, int Wcut,
-                                         int* uncovered /* device int, zeroed by the caller */, hipStream_t stream) {
-  return slide_argmax_resized_launch("slide_argmax_resized", logits, n, C, hs, ws, windows, out, nullptr, B, H, W, hc, wc, Hd, Wd, Hcut, Wcut, uncovered, stream);
-}
-
-extern "C" int mmsa_slide_argmax_resized_conf(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out,
-                                              float* conf, int B, int H, int W, int hc, int wc, int Hd, int Wd, int Hcut, int Wcut,
-                                              int* uncovered /* device int, zeroed by the caller */, hipStream_t stream) {
-  MMSA_CHECK_ARG(conf, "slide_argmax_resized_conf: bad args");
-  return slide_argmax_resized_launch("slide_argmax_resized_conf", logits, n, C, hs, ws, windows, out, conf, B, H, W, hc, wc, Hd, Wd, Hcut, Wcut, uncovered, stream);
-}
-
 // ---- tempered confidence: the three confidence kernels above with softmax(x / T) in place of softmax(x) -- `it` = float32(1 / float64(T)) from the host, and
 // every exponential is softmax_px_exp_t (csrc/softmax_px.h: ONE more float32 product, exact at it == 1.0f, where these kernels are their siblings bit for bit).
-// The class map does not depend on T > 0.  They stand here, at the end, for the reason given above argmax_max_nchw_kernel.
+// The class map does not depend on T > 0.  They stand here, behind the kernels that were there before them, for the reason given above argmax_max_nchw_kernel.
 __global__ __launch_bounds__(256) void slide_argmax_conf_t_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
                                                                   float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, WindowTable wt,
                                                                   int* __restrict__ uncovered, float it) {
-#define SLIDE_EVAL 0
 #define SLIDE_CONF 1
 #define SLIDE_TEMP 1
 #define SLIDE_Y blockIdx.y
 #define SLIDE_EXIT return
 #include "slide_pixel.inc"
-#undef SLIDE_EVAL
-#undef SLIDE_CONF
-#undef SLIDE_TEMP
-#undef SLIDE_Y
-#undef SLIDE_EXIT
 }
 
 __global__ __launch_bounds__(256) void slide_argmax_conf_lds_t_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
@@ -474,17 +350,11 @@ __global__ __launch_bounds__(256) void slide_argmax_conf_lds_t_kernel(const floa
                                                                       int* __restrict__ uncovered, float it) {
   extern __shared__ float conf_lds[];
   float* conf_col = conf_lds + threadIdx.x;      // private to the lane: no barrier
-#define SLIDE_EVAL 0
 #define SLIDE_CONF 2
 #define SLIDE_TEMP 1
 #define SLIDE_Y blockIdx.y
 #define SLIDE_EXIT return
 #include "slide_pixel.inc"
-#undef SLIDE_EVAL
-#undef SLIDE_CONF
-#undef SLIDE_TEMP
-#undef SLIDE_Y
-#undef SLIDE_EXIT
 }
 
 __global__ __launch_bounds__(256) void slide_argmax_resized_conf_t_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
@@ -493,26 +363,11 @@ __global__ __launch_bounds__(256) void slide_argmax_resized_conf_t_kernel(const 
   slide_resized_pixel<true, true>(logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, Hcut, Wcut, rh2, rw2, wt, uncovered, it);
 }
 
-extern "C" int mmsa_slide_argmax_conf_t(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out, float* conf,
-                                        int B, int H, int W, int hc, int wc, int* uncovered /* device int, zeroed by the caller */, float inv_temperature,
-                                        hipStream_t stream) {
-  MMSA_CHECK_ARG(conf, "slide_argmax_conf_t: bad args");
-  return slide_argmax_launch("slide_argmax_conf_t", logits, n, C, hs, ws, windows, out, conf, B, H, W, hc, wc, uncovered, stream, &inv_temperature);
-}
-
-extern "C" int mmsa_slide_argmax_resized_conf_t(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out,
-                                                float* conf, int B, int H, int W, int hc, int wc, int Hd, int Wd, int Hcut, int Wcut,
-                                                int* uncovered /* device int, zeroed by the caller */, float inv_temperature, hipStream_t stream) {
-  MMSA_CHECK_ARG(conf, "slide_argmax_resized_conf_t: bad args");
-  return slide_argmax_resized_launch("slide_argmax_resized_conf_t", logits, n, C, hs, ws, windows, out, conf, B, H, W, hc, wc, Hd, Wd, Hcut, Wcut, uncovered, stream,
-                                     &inv_temperature);
-}
-
 // ---- uncertainty maps: the top-2 margin or the entropy score (csrc/softmax_px.h: `kind` SCORE_MARGIN / SCORE_ENTROPY) in the confidence's place, float32
 // [B, Ho, Wo] in [0, 1], higher = more certain, 0 where the map is 255 -- so that csrc/conf_bin.h and everything behind it take it unchanged.  Both are formed
 // from the float32 probabilities p_c, the same operations in the canvas kernel (which reads p_c) and in the one-pass kernels (which form p_c = e_c / s of
-// softmax(x * it) themselves: `it` is always an argument, its product exact at 1.0f): bit for bit the same score.  They stand here, at the end, for the reason
-// given above argmax_max_nchw_kernel (profiles/uncertainty_isa.txt).
+// softmax(x * it) themselves: `it` is always an argument, its product exact at 1.0f): bit for bit the same score.  They stand here, behind every other kernel, for the
+// reason given above argmax_max_nchw_kernel (profiles/uncertainty_isa.txt).
 
 // argmax_max_nchw_kernel with the score in the maximum's place: on a canvas of probabilities (one view's, or the mean over augmented views).  `bi` is the
 // first maximum of the probabilities; where the logits' argmax is a later class of the same probability, p[bi] and p2 are the same two values.
@@ -554,19 +409,10 @@ extern "C" int mmsa_argmax_score_nchw(const float* prob, unsigned char* out, flo
 __global__ __launch_bounds__(256) void slide_argmax_score_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
                                                                  float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, WindowTable wt,
                                                                  int* __restrict__ uncovered, int kind, float it, float ilc) {
-#define SLIDE_EVAL 0
-#define SLIDE_CONF 0
-#define SLIDE_TEMP 0
 #define SLIDE_SCORE 1
 #define SLIDE_Y blockIdx.y
 #define SLIDE_EXIT return
 #include "slide_pixel.inc"
-#undef SLIDE_EVAL
-#undef SLIDE_CONF
-#undef SLIDE_TEMP
-#undef SLIDE_SCORE
-#undef SLIDE_Y
-#undef SLIDE_EXIT
 }
 
 __global__ __launch_bounds__(256) void slide_argmax_score_lds_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
@@ -574,19 +420,10 @@ __global__ __launch_bounds__(256) void slide_argmax_score_lds_kernel(const float
                                                                      int* __restrict__ uncovered, int kind, float it, float ilc) {
   extern __shared__ float conf_lds[];
   float* conf_col = conf_lds + threadIdx.x;      // private to the lane: no barrier
-#define SLIDE_EVAL 0
-#define SLIDE_CONF 0
-#define SLIDE_TEMP 0
 #define SLIDE_SCORE 2
 #define SLIDE_Y blockIdx.y
 #define SLIDE_EXIT return
 #include "slide_pixel.inc"
-#undef SLIDE_EVAL
-#undef SLIDE_CONF
-#undef SLIDE_TEMP
-#undef SLIDE_SCORE
-#undef SLIDE_Y
-#undef SLIDE_EXIT
 }
 
 __global__ __launch_bounds__(256) void slide_argmax_resized_score_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
@@ -596,6 +433,10 @@ __global__ __launch_bounds__(256) void slide_argmax_resized_score_kernel(const f
   slide_resized_pixel<false, false, true>(logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, Hcut, Wcut, rh2, rw2, wt, uncovered, it, kind, ilc);
 }
 
+// ---- the host side of the eight class-map entries mmsa_slide_argmax[_resized][_conf[_t] | _score]: one launcher per geometry, below every kernel it may launch.
+// `conf`: the confidence (or score) map, NULL for the plain map; `it` (with `conf`): the inverse temperature of the `_t` and `_score` kernels; `kind` (with
+// `conf` and `it`): the score the `_score` kernels write there, with `ilc` = 1 / log C.  The checks come in one order for every entry: the "bad args" of the
+// geometry, the score arguments or the inverse temperature, the cut, the windows.
 static int score_check(const char* name, const float* score, int kind, float it, float ilc) {
   MMSA_CHECK_ARG(score, "%s: bad args", name);
   MMSA_CHECK_SCORE_KIND(name, kind);
@@ -604,45 +445,110 @@ static int score_check(const char* name, const float* score, int kind, float it,
   return MMSA_OK;
 }
 
+// frame size.  With `conf`: the LDS-column form of the kernel where it fits, the recomputing form otherwise.
+static int slide_argmax_launch(const char* name, const float* logits, int n, int C, int hs, int ws, const int* windows, unsigned char* out, float* conf, int B, int H,
+                               int W, int hc, int wc, int* uncovered, hipStream_t stream, const float* it = nullptr, const int* kind = nullptr, float ilc = 0.f) {
+  MMSA_CHECK_ARG(logits && out && uncovered && C > 0 && C <= 255 && hs > 0 && ws > 0 && hc > 0 && wc > 0 && B > 0 && H <= 65535 && B <= 65535, "%s: bad args", name);
+  if (kind) {
+    if (int rc = score_check(name, conf, *kind, *it, ilc)) return rc;
+  } else if (it) MMSA_CHECK_INV_TEMPERATURE(name, *it);
+  WindowTable wt;
+  if (int rc = fill_windows(wt, windows, n, B, H, W, hc, wc, name)) return rc;
+#ifdef MMSA_CONF_SECOND_PASS      // measurement build only (tools/exp/confidence_bench.py): the second-pass form of the confidence for every C
+  const bool lds = kind && C <= SLIDE_CONF_LDS_CLASSES;
+#else
+  const bool lds = C <= SLIDE_CONF_LDS_CLASSES;
+#endif
+  const dim3 grid(cdiv(W, 256), H, B);
+  const size_t col = lds ? (size_t)C * 256 * sizeof(float) : 0;      // the per-lane LDS column
+  const float rh = (float)hs / (float)hc, rw = (float)ws / (float)wc;
+#define SLIDE_LAUNCH(kernel, ...) hipLaunchKernelGGL(kernel, grid, dim3(256), col, stream, logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, wt, uncovered, ##__VA_ARGS__)
+  if (!conf) hipLaunchKernelGGL(slide_argmax_kernel, grid, dim3(256), 0, stream, logits, C, hs, ws, out, H, W, hc, wc, rh, rw, wt, uncovered);
+  else if (kind && lds) SLIDE_LAUNCH(slide_argmax_score_lds_kernel, *kind, *it, ilc);
+  else if (kind) SLIDE_LAUNCH(slide_argmax_score_kernel, *kind, *it, ilc);
+  else if (it && lds) SLIDE_LAUNCH(slide_argmax_conf_lds_t_kernel, *it);
+  else if (it) SLIDE_LAUNCH(slide_argmax_conf_t_kernel, *it);
+  else if (lds) SLIDE_LAUNCH(slide_argmax_conf_lds_kernel);
+  else SLIDE_LAUNCH(slide_argmax_conf_kernel);
+#undef SLIDE_LAUNCH
+  MMSA_CHECK_LAUNCH(name);
+  return MMSA_OK;
+}
+
+// rescaled or cut size
+static int slide_argmax_resized_launch(const char* name, const float* logits, int n, int C, int hs, int ws, const int* windows, unsigned char* out, float* conf, int B,
+                                       int H, int W, int hc, int wc, int Hd, int Wd, int Hcut, int Wcut, int* uncovered, hipStream_t stream,
+                                       const float* it = nullptr, const int* kind = nullptr, float ilc = 0.f) {
+  MMSA_CHECK_ARG(logits && out && uncovered && C > 0 && C <= 255 && hs > 0 && ws > 0 && hc > 0 && wc > 0 && B > 0 && H > 0 && W > 0 && B <= 65535, "%s: bad args", name);
+  if (kind) {
+    if (int rc = score_check(name, conf, *kind, *it, ilc)) return rc;
+  } else if (it) MMSA_CHECK_INV_TEMPERATURE(name, *it);
+  MMSA_CHECK_ARG(Hd > 0 && Wd > 0 && Hcut > 0 && Wcut > 0 && Hcut <= Hd && Wcut <= Wd && Hcut <= 65535,
+                 "%s: the cut %dx%d must lie inside the target %dx%d (and have at most 65535 rows)", name, Hcut, Wcut, Hd, Wd);
+  WindowTable wt;
+  if (int rc = fill_windows(wt, windows, n, B, H, W, hc, wc, name)) return rc;
+  const dim3 grid(cdiv(Wcut, 256), Hcut, B);
+  const float rh = (float)hs / (float)hc, rw = (float)ws / (float)wc, rh2 = (float)H / (float)Hd, rw2 = (float)W / (float)Wd;
+#define SLIDE_LAUNCH(kernel, ...) \
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, Hcut, Wcut, rh2, rw2, wt, uncovered, ##__VA_ARGS__)
+  if (!conf) hipLaunchKernelGGL(slide_argmax_resized_kernel, grid, dim3(256), 0, stream, logits, C, hs, ws, out, H, W, hc, wc, rh, rw, Hcut, Wcut, rh2, rw2, wt, uncovered);
+  else if (kind) SLIDE_LAUNCH(slide_argmax_resized_score_kernel, *kind, *it, ilc);
+  else if (it) SLIDE_LAUNCH(slide_argmax_resized_conf_t_kernel, *it);
+  else SLIDE_LAUNCH(slide_argmax_resized_conf_kernel);
+#undef SLIDE_LAUNCH
+  MMSA_CHECK_LAUNCH(name);
+  return MMSA_OK;
+}
+
+extern "C" int mmsa_slide_argmax(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out,
+                                 int B, int H, int W, int hc, int wc, int* uncovered /* device int, zeroed by the caller */, hipStream_t stream) {
+  return slide_argmax_launch("slide_argmax", logits, n, C, hs, ws, windows, out, nullptr, B, H, W, hc, wc, uncovered, stream);
+}
+
+extern "C" int mmsa_slide_argmax_conf(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out, float* conf,
+                                      int B, int H, int W, int hc, int wc, int* uncovered /* device int, zeroed by the caller */, hipStream_t stream) {
+  MMSA_CHECK_ARG(conf, "slide_argmax_conf: bad args");
+  return slide_argmax_launch("slide_argmax_conf", logits, n, C, hs, ws, windows, out, conf, B, H, W, hc, wc, uncovered, stream);
+}
+
+extern "C" int mmsa_slide_argmax_conf_t(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out, float* conf,
+                                        int B, int H, int W, int hc, int wc, int* uncovered /* device int, zeroed by the caller */, float inv_temperature,
+                                        hipStream_t stream) {
+  MMSA_CHECK_ARG(conf, "slide_argmax_conf_t: bad args");
+  return slide_argmax_launch("slide_argmax_conf_t", logits, n, C, hs, ws, windows, out, conf, B, H, W, hc, wc, uncovered, stream, &inv_temperature);
+}
+
 extern "C" int mmsa_slide_argmax_score(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out, float* score,
                                        int B, int H, int W, int hc, int wc, int* uncovered /* device int, zeroed by the caller */, int kind, float inv_temperature,
                                        float inv_log_c, hipStream_t stream) {
-  const char* name = "slide_argmax_score";
-  MMSA_CHECK_ARG(logits && out && uncovered && C > 0 && C <= 255 && hs > 0 && ws > 0 && hc > 0 && wc > 0 && B > 0 && H <= 65535 && B <= 65535, "%s: bad args", name);
-  int rc = score_check(name, score, kind, inv_temperature, inv_log_c);
-  if (rc) return rc;
-  WindowTable wt;
-  rc = fill_windows(wt, windows, n, B, H, W, hc, wc, name);
-  if (rc) return rc;
-  const dim3 grid(cdiv(W, 256), H, B);
-  const float rh = (float)hs / (float)hc, rw = (float)ws / (float)wc;
-  if (C <= SLIDE_CONF_LDS_CLASSES)
-    hipLaunchKernelGGL(slide_argmax_score_lds_kernel, grid, dim3(256), (size_t)C * 256 * sizeof(float), stream, logits, C, hs, ws, out, score, H, W, hc, wc, rh, rw, wt,
-                       uncovered, kind, inv_temperature, inv_log_c);
-  else
-    hipLaunchKernelGGL(slide_argmax_score_kernel, grid, dim3(256), 0, stream, logits, C, hs, ws, out, score, H, W, hc, wc, rh, rw, wt, uncovered, kind,
-                       inv_temperature, inv_log_c);
-  MMSA_CHECK_LAUNCH(name);
-  return MMSA_OK;
+  return slide_argmax_launch("slide_argmax_score", logits, n, C, hs, ws, windows, out, score, B, H, W, hc, wc, uncovered, stream, &inv_temperature, &kind, inv_log_c);
+}
+
+extern "C" int mmsa_slide_argmax_resized(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out,
+                                         int B, int H, int W, int hc, int wc, int Hd, int Wd, int Hcut, int Wcut,
+                                         int* uncovered /* device int, zeroed by the caller */, hipStream_t stream) {
+  return slide_argmax_resized_launch("slide_argmax_resized", logits, n, C, hs, ws, windows, out, nullptr, B, H, W, hc, wc, Hd, Wd, Hcut, Wcut, uncovered, stream);
+}
+
+extern "C" int mmsa_slide_argmax_resized_conf(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out,
+                                              float* conf, int B, int H, int W, int hc, int wc, int Hd, int Wd, int Hcut, int Wcut,
+                                              int* uncovered /* device int, zeroed by the caller */, hipStream_t stream) {
+  MMSA_CHECK_ARG(conf, "slide_argmax_resized_conf: bad args");
+  return slide_argmax_resized_launch("slide_argmax_resized_conf", logits, n, C, hs, ws, windows, out, conf, B, H, W, hc, wc, Hd, Wd, Hcut, Wcut, uncovered, stream);
+}
+
+extern "C" int mmsa_slide_argmax_resized_conf_t(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out,
+                                                float* conf, int B, int H, int W, int hc, int wc, int Hd, int Wd, int Hcut, int Wcut,
+                                                int* uncovered /* device int, zeroed by the caller */, float inv_temperature, hipStream_t stream) {
+  MMSA_CHECK_ARG(conf, "slide_argmax_resized_conf_t: bad args");
+  return slide_argmax_resized_launch("slide_argmax_resized_conf_t", logits, n, C, hs, ws, windows, out, conf, B, H, W, hc, wc, Hd, Wd, Hcut, Wcut, uncovered, stream,
+                                     &inv_temperature);
 }
 
 extern "C" int mmsa_slide_argmax_resized_score(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out,
                                                float* score, int B, int H, int W, int hc, int wc, int Hd, int Wd, int Hcut, int Wcut,
                                                int* uncovered /* device int, zeroed by the caller */, int kind, float inv_temperature, float inv_log_c,
                                                hipStream_t stream) {
-  const char* name = "slide_argmax_resized_score";
-  MMSA_CHECK_ARG(logits && out && uncovered && C > 0 && C <= 255 && hs > 0 && ws > 0 && hc > 0 && wc > 0 && B > 0 && H > 0 && W > 0 && B <= 65535, "%s: bad args", name);
-  int rc = score_check(name, score, kind, inv_temperature, inv_log_c);
-  if (rc) return rc;
-  MMSA_CHECK_ARG(Hd > 0 && Wd > 0 && Hcut > 0 && Wcut > 0 && Hcut <= Hd && Wcut <= Wd && Hcut <= 65535,
-                 "%s: the cut %dx%d must lie inside the target %dx%d (and have at most 65535 rows)", name, Hcut, Wcut, Hd, Wd);
-  WindowTable wt;
-  rc = fill_windows(wt, windows, n, B, H, W, hc, wc, name);
-  if (rc) return rc;
-  const dim3 grid(cdiv(Wcut, 256), Hcut, B);
-  const float rh = (float)hs / (float)hc, rw = (float)ws / (float)wc, rh2 = (float)H / (float)Hd, rw2 = (float)W / (float)Wd;
-  hipLaunchKernelGGL(slide_argmax_resized_score_kernel, grid, dim3(256), 0, stream, logits, C, hs, ws, out, score, H, W, hc, wc, rh, rw, Hcut, Wcut, rh2, rw2, wt,
-                     uncovered, kind, inv_temperature, inv_log_c);
-  MMSA_CHECK_LAUNCH(name);
-  return MMSA_OK;
+  return slide_argmax_resized_launch("slide_argmax_resized_score", logits, n, C, hs, ws, windows, out, score, B, H, W, hc, wc, Hd, Wd, Hcut, Wcut, uncovered, stream,
+                                     &inv_temperature, &kind, inv_log_c);
 }

@@ -20,15 +20,35 @@
 // SLIDE_EXIT MUST NOT be used inside a loop of this body: there `continue` would go on with that loop in the second kernel only, where `return`
 // leaves the first (every use below is at the body's top level).  In scope: logits, C, hs, ws, out, H, W, hc, wc, rh, rw, wt, uncovered (and conf; with SLIDE_SCORE also
 // kind, it, ilc).
+// A kernel defines SLIDE_Y, SLIDE_EXIT and the switches it turns on (one not defined = 0) in front of the #include; the file undefines all of them at its end.
+#ifndef SLIDE_EVAL
+#define SLIDE_EVAL 0
+#endif
+#ifndef SLIDE_CONF
+#define SLIDE_CONF 0
+#endif
+#ifndef SLIDE_TEMP
+#define SLIDE_TEMP 0
+#endif
 #ifndef SLIDE_SCORE
 #define SLIDE_SCORE 0
-#define SLIDE_SCORE_DEFAULTED
 #endif
 #if SLIDE_TEMP
 #define SLIDE_EXP(v, m) softmax_px_exp_t(v, m, it)
 #else
 #define SLIDE_EXP(v, m) softmax_px_exp(v, m)
 #endif
+// float acc = class c's sum over the pixel's covering windows, in window order, of bilinear(logits_k)[c]: the first window WRITES (0 + v == v), later ones add
+#define SLIDE_WINDOW_SUM(acc, c)                                                                                                         \
+  float acc = 0.f;                                                                                                                       \
+  _Pragma("unroll") for (int q = 0; q < 8; ++q) {                                                                                        \
+    if (q < nk) {                                                                                                                        \
+      const float* sp = logits + ((long)kk[q] * C + c) * hs * ws;                                                                        \
+      const float lh = lhs[q], lw = lws[q];                                                                                              \
+      const float v = (1.f - lh) * ((1.f - lw) * sp[o00[q]] + lw * sp[o01[q]]) + lh * ((1.f - lw) * sp[o10[q]] + lw * sp[o11[q]]);       \
+      acc = q == 0 ? v : acc + v;                                                                                                        \
+    }                                                                                                                                    \
+  }
   const int x = blockIdx.x * 256 + threadIdx.x, y = SLIDE_Y, b = blockIdx.z;
   if (x >= W) SLIDE_EXIT;
 #if SLIDE_EVAL
@@ -70,10 +90,7 @@
 #else
     out[((long)b * H + y) * W + x] = 255;
 #endif
-#if SLIDE_CONF
-    conf[((long)b * H + y) * W + x] = 0.f;
-#endif
-#if SLIDE_SCORE
+#if SLIDE_CONF || SLIDE_SCORE
     conf[((long)b * H + y) * W + x] = 0.f;
 #endif
     SLIDE_EXIT;
@@ -82,21 +99,9 @@
   float best = -INFINITY;
   int bi = 0;
   for (int c = 0; c < C; ++c) {
-    float acc = 0.f;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      if (q < nk) {
-        const float* sp = logits + ((long)kk[q] * C + c) * hs * ws;
-        const float lh = lhs[q], lw = lws[q];
-        const float v = (1.f - lh) * ((1.f - lw) * sp[o00[q]] + lw * sp[o01[q]]) + lh * ((1.f - lw) * sp[o10[q]] + lw * sp[o11[q]]);
-        acc = q == 0 ? v : acc + v;     // window order: the first window WRITES (0 + v == v), later ones add
-      }
-    }
+    SLIDE_WINDOW_SUM(acc, c)
     const float p = acc / cnt;
-#if SLIDE_CONF == 2
-    conf_col[c * 256] = p;
-#endif
-#if SLIDE_SCORE == 2
+#if SLIDE_CONF == 2 || SLIDE_SCORE == 2
     conf_col[c * 256] = p;
 #endif
     if (c == 0 || p > best) { best = p; bi = c; }
@@ -114,16 +119,7 @@
 #elif SLIDE_CONF
   float s = 0.f;
   for (int c = 0; c < C; ++c) {
-    float acc = 0.f;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      if (q < nk) {
-        const float* sp = logits + ((long)kk[q] * C + c) * hs * ws;
-        const float lh = lhs[q], lw = lws[q];
-        const float v = (1.f - lh) * ((1.f - lw) * sp[o00[q]] + lw * sp[o01[q]]) + lh * ((1.f - lw) * sp[o10[q]] + lw * sp[o11[q]]);
-        acc = q == 0 ? v : acc + v;
-      }
-    }
+    SLIDE_WINDOW_SUM(acc, c)
     s = softmax_px_sum(s, SLIDE_EXP(acc / cnt, best), c == 0);
   }
   conf[((long)b * H + y) * W + x] = softmax_px_prob(SLIDE_EXP(best, best), s);      // e_c / s at the first maximum: the largest probability
@@ -144,24 +140,18 @@
   bool snone = true;
   for (int pass = 0; pass < 2; ++pass)      // 0: the sum of the exponentials; 1: the probabilities, class by class, into the score
     for (int c = 0; c < C; ++c) {
-      float acc = 0.f;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        if (q < nk) {
-          const float* sp = logits + ((long)kk[q] * C + c) * hs * ws;
-          const float lh = lhs[q], lw = lws[q];
-          const float v = (1.f - lh) * ((1.f - lw) * sp[o00[q]] + lw * sp[o01[q]]) + lh * ((1.f - lw) * sp[o10[q]] + lw * sp[o11[q]]);
-          acc = q == 0 ? v : acc + v;
-        }
-      }
+      SLIDE_WINDOW_SUM(acc, c)
       const float e = softmax_px_exp_t(acc / cnt, best, it);
       if (pass == 0) s = softmax_px_sum(s, e, c == 0);
       else score_px_class(kind, bi, c, softmax_px_prob(e, s), sa, spb, snone);
     }
   conf[((long)b * H + y) * W + x] = score_px_finish(kind, sa, spb, snone, ilc);
 #endif
+#undef SLIDE_WINDOW_SUM
 #undef SLIDE_EXP
-#ifdef SLIDE_SCORE_DEFAULTED
+#undef SLIDE_EVAL
+#undef SLIDE_CONF
+#undef SLIDE_TEMP
 #undef SLIDE_SCORE
-#undef SLIDE_SCORE_DEFAULTED
-#endif
+#undef SLIDE_Y
+#undef SLIDE_EXIT

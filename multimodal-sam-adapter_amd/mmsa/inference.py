@@ -21,7 +21,8 @@ score 1 - H / log C (csrc/softmax_px.h), each in [0, 1] with higher = more certa
 ones come from the `_score` sibling of the launch the plan takes (`argmax_score_map` on a probability canvas), and "max" takes exactly the launches it always took.
 
 What a frame's output looks like -- its windows, the size after the second resize and after the cut, which class-map kernel that takes -- is decided once,
-in `MapPlan`, a record without device state; the entries read the frame (`_intake`), make the plan, and launch from it."""
+in `MapPlan`, a record without device state; the entries read the frame (`_intake`), make the plan, and launch from it.  What the keywords above ask of
+that launch is decided once as well, in `MapOptions`: every entry validates the family under its own name, and the plan picks its launch from the record."""
 import ctypes
 import dataclasses
 import functools
@@ -301,27 +302,62 @@ def _check_binned(kw, cls, owner, labels, confidence, what, fused=None, return_m
         raise RuntimeError(f"mmsa.{what}: {_NO_CONF_FUSED}")
 
 
-def _check_calibration(calibration, labels, confidence, what, fused=None, return_map=True):
-    _check_binned("calibration", "Calibration", calibration, labels, confidence, what, fused, return_map)
-
-
-def _check_selective(selective, labels, confidence, what, fused=None, return_map=True):
-    _check_binned("selective", "SelectiveEvaluator", selective, labels, confidence, what, fused, return_map)
-
-
 def _check_labels(labels, evaluator, *binned):
     """`labels=` feed an evaluator, a calibration, a selective evaluator or several of them; an evaluator needs them."""
     if (labels is None) != (evaluator is None) and not (labels is not None and any(b is not None for b in binned)):
         raise RuntimeError("mmsa.inference: labels= and evaluator= come together")
 
 
-def _add_binned(out, conf, labels, case, calibration, selective):
-    """One more launch each over the stored map and confidence: the reliability bins (mmsa_eval_calibration) and the per-bin confusion counts
-    (mmsa_eval_selective)."""
-    if calibration is not None:
-        calibration.add(out, conf, labels, case=case)
-    if selective is not None:
-        selective.add(out, conf, labels, case=case)
+@dataclasses.dataclass(frozen=True)
+class MapOptions:
+    """The option family of the class-map entries, validated: what a plan's launch needs, and nothing a callee has to check or derive again.  Built once per
+    call, under the calling entry's name `what` (the `mmsa.<what>:` of every refusal), in two steps that own every refusal of the family, in this order:
+    `of` -- `score=`, `temperature=`, `calibration=`, `selective=`, all before the frame is looked at; `at` -- once the map's size and device are known and
+    before the backbone runs: `confidence=` with fused=True / return_map=False, the confidence buffer (made, or checked), `labels=`.
+    What depends on the plan (`one_pass=` at frame size, `fused=` / `return_map=` at a rescaled size or without an evaluator) is refused by MapPlan.class_map."""
+    conf: object = None          # the float32 [B, Ho, Wo] buffer the launch writes the confidence (or score) map into, or None; before `at`: the entry's `confidence=`
+    it: object = None            # the float32 inverse temperature of the `_t` / `_score` launches (mmsa.evaluate.inv_temperature), or None
+    kind: int = 0                # 0: the confidence; 1 / 2: the top-2 margin / the entropy score (mmsa.evaluate.SCORES)
+    labels: object = None
+    evaluator: object = None
+    case: object = None
+    calibration: object = None
+    selective: object = None
+    fused: object = None
+    return_map: bool = True
+    one_pass: object = None
+
+    @classmethod
+    def of(cls, what, confidence=False, temperature=None, score="max", one_pass=None, aug=False, **per_call):
+        """`aug`: the entries of augmented views, whose one-pass launch has no score sibling.  A SlideRunner makes its record without `per_call` and adds
+        them per frame (`with_call`)."""
+        kind = _score_kind(score, confidence, what)
+        if aug and kind and one_pass:
+            raise RuntimeError(f"mmsa.{what}: score={score!r} {_NO_SCORE_AUG_ONE_PASS}")
+        it = _inv_temperature(temperature, confidence, what)
+        return cls(conf=confidence, it=it, kind=kind, one_pass=one_pass).with_call(what, **per_call)
+
+    def with_call(self, what, labels=None, evaluator=None, case=None, calibration=None, selective=None, fused=None, return_map=True):
+        for kw, name, owner in (("calibration", "Calibration", calibration), ("selective", "SelectiveEvaluator", selective)):
+            _check_binned(kw, name, owner, labels, self.conf, what, fused, return_map)
+        return dataclasses.replace(self, labels=labels, evaluator=evaluator, case=case, calibration=calibration, selective=selective, fused=fused,
+                                   return_map=return_map)
+
+    def at(self, size, device, what, make=True):
+        """`make=False`: a plan's `conf=`, which is the buffer itself -- True makes none there."""
+        conf = _confidence(self.conf, size, device, what, self.fused, self.return_map) if make or self.conf is not True else _check_conf(True, size, device, what)
+        _check_labels(self.labels, self.evaluator, self.calibration, self.selective)
+        return dataclasses.replace(self, conf=conf)
+
+    def count(self, out):
+        """What `labels=` feed, from the stored map `out` (and the confidence next to it): one more launch each -- the confusion counts
+        (mmsa_eval_confusion_u8), the reliability bins (mmsa_eval_calibration), the per-bin confusion counts (mmsa_eval_selective)."""
+        if self.evaluator is not None:
+            self.evaluator.add(out, self.labels, case=self.case)
+        if self.calibration is not None:
+            self.calibration.add(out, self.conf, self.labels, case=self.case)
+        if self.selective is not None:
+            self.selective.add(out, self.conf, self.labels, case=self.case)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -408,15 +444,19 @@ class MapPlan:
         outs = (out.data_ptr(),) if conf is None else (out.data_ptr(), conf.data_ptr())
         return (lg.data_ptr(), self.n, lg.shape[1], lg.shape[2], lg.shape[3], self.tab) + outs + (self.B, self.H, self.W, self.hc, self.wc)
 
-    def _plain(self, lg, out, unc, conf, it=None, kind=0):
-        """mmsa_slide_argmax, or its sibling that also writes `conf`; `it` (an inverse temperature, with `conf`): mmsa_slide_argmax_conf_t; `kind` (1 / 2, with
-        `conf`): mmsa_slide_argmax_score, which always takes an inverse temperature (1.0 without `it`: the untempered softmax, exactly)."""
-        if kind:
-            lib.call("mmsa_slide_argmax_score", *self._args(lg, out, conf), unc.data_ptr(), kind, 1.0 if it is None else it, _inv_log_c(lg.shape[1]), ops._stream())
-        elif it is None:
-            lib.call("mmsa_slide_argmax" if conf is None else "mmsa_slide_argmax_conf", *self._args(lg, out, conf), unc.data_ptr(), ops._stream())
+    def _launch(self, lg, out, unc, o):
+        """The one-pass launch of the plan, mmsa_slide_argmax[_resized], or the sibling that also writes o.conf: `_conf`; `_conf_t` with an inverse temperature
+        o.it; `_score` with o.kind 1 / 2, which always takes an inverse temperature (1.0 without o.it: the untempered softmax, exactly) and 1 / log C."""
+        if o.conf is None:
+            suffix, tail = "", ()
+        elif o.kind:
+            suffix, tail = "_score", (o.kind, 1.0 if o.it is None else o.it, _inv_log_c(lg.shape[1]))
+        elif o.it is None:
+            suffix, tail = "_conf", ()
         else:
-            lib.call("mmsa_slide_argmax_conf_t", *self._args(lg, out, conf), unc.data_ptr(), it, ops._stream())
+            suffix, tail = "_conf_t", (o.it,)
+        lib.call("mmsa_slide_argmax" + ("_resized" if self.rescaled else "") + suffix, *self._args(lg, out, o.conf), *(self.rs or ()), unc.data_ptr(), *tail,
+                 ops._stream())
 
     def class_map(self, lg, out, unc, labels=None, evaluator=None, case=None, fused=None, return_map=True, one_pass=None, conf=None, calibration=None,
                   selective=None, temperature=None, score="max"):
@@ -445,57 +485,37 @@ class MapPlan:
         mmsa_slide_argmax_resized_score; on the canvas path mmsa_argmax_score_nchw on the probabilities), with `temperature` as above: bit for bit the score of
         probabilities(..., temperature=T).  At a rescaled size `one_pass=None` follows ONE_PASS_SCORE_RESCALE_DEFAULT for them (measured: the canvas path).
         "max": the launches above, with the arguments above."""
-        kind = _score_kind(score, conf, "inference")
-        it = _inv_temperature(temperature, conf, "inference")
-        _check_calibration(calibration, labels, conf, "inference", fused, return_map)
-        _check_selective(selective, labels, conf, "inference", fused, return_map)
-        if conf is not None:
-            if fused or not return_map:
-                raise RuntimeError(f"mmsa.inference: {_NO_CONF_FUSED}")
-            _check_conf(conf, (self.B, self.Ho, self.Wo), out.device)
+        o = MapOptions.of("inference", conf, temperature, score, one_pass, labels=labels, evaluator=evaluator, case=case, calibration=calibration,
+                          selective=selective, fused=fused, return_map=return_map)
+        self._class_map(lg, out, unc, o.at((self.B, self.Ho, self.Wo), out.device if conf is not None else None, "inference", make=False))
+
+    def _class_map(self, lg, out, unc, o):
+        """`class_map` for the entries, which have made their MapOptions `o` under their own name: nothing of the family is checked again."""
         if self.rescaled:
-            _check_labels(labels, evaluator, calibration, selective)
-            if fused or not return_map:
+            if o.fused or not o.return_map:
                 raise RuntimeError("mmsa.inference: fused=True / return_map=False need the fused class-map + evaluation launch, and that launch has no variant at "
                                    "a rescaled or cut size: the counts of a rescaled map go through the stored map (drop fused= / return_map=)")
-            default = ONE_PASS_SCORE_RESCALE_DEFAULT if kind else ONE_PASS_RESCALE_DEFAULT
-            if default["up" if self.Hd * self.Wd > self.H * self.W else "down"] if one_pass is None else one_pass:
-                if conf is None:
-                    lib.call("mmsa_slide_argmax_resized", *self._args(lg, out), *self.rs, unc.data_ptr(), ops._stream())
-                elif kind:
-                    lib.call("mmsa_slide_argmax_resized_score", *self._args(lg, out, conf), *self.rs, unc.data_ptr(), kind, 1.0 if it is None else it,
-                             _inv_log_c(lg.shape[1]), ops._stream())
-                elif it is None:
-                    lib.call("mmsa_slide_argmax_resized_conf", *self._args(lg, out, conf), *self.rs, unc.data_ptr(), ops._stream())
-                else:
-                    lib.call("mmsa_slide_argmax_resized_conf_t", *self._args(lg, out, conf), *self.rs, unc.data_ptr(), it, ops._stream())
-            else:
-                _rescaled_map_canvas(self, lg, out, unc, conf, it, kind)
-            if evaluator is not None:
-                evaluator.add(out, labels, case=case)
-            _add_binned(out, conf, labels, case, calibration, selective)
-            return
-        if one_pass is not None:
-            raise RuntimeError("mmsa.inference: one_pass= chooses the launch of a RESCALED class map; this map has the frame's size")
-        if labels is None and evaluator is None:
-            if not return_map:
-                raise RuntimeError("mmsa.inference: return_map=False only makes sense with labels= and evaluator=")
-            self._plain(lg, out, unc, conf, it, kind)
-            return
-        _check_labels(labels, evaluator, calibration, selective)
-        if evaluator is None:                              # labels for the calibration / the selective evaluator alone
-            self._plain(lg, out, unc, conf, it, kind)
-            _add_binned(out, conf, labels, case, calibration, selective)
-            return
-        if fused is False and not return_map:
-            raise RuntimeError("mmsa.inference: return_map=False needs the fused launch (two launches go through the stored map); drop fused=False")
-        from . import evaluate
-        if conf is None and ((evaluate.FUSED_DEFAULT or not return_map) if fused is None else fused):      # no map wanted: only the fused launch can leave it unwritten
-            evaluator.add_fused(lg, self, out if return_map else None, unc, labels, case=case)
+            default = ONE_PASS_SCORE_RESCALE_DEFAULT if o.kind else ONE_PASS_RESCALE_DEFAULT
+            one_pass = default["up" if self.Hd * self.Wd > self.H * self.W else "down"] if o.one_pass is None else o.one_pass
+            fused = False
         else:
-            self._plain(lg, out, unc, conf, it, kind)
-            evaluator.add(out, labels, case=case)
-        _add_binned(out, conf, labels, case, calibration, selective)
+            if o.one_pass is not None:
+                raise RuntimeError("mmsa.inference: one_pass= chooses the launch of a RESCALED class map; this map has the frame's size")
+            if o.evaluator is None and not o.return_map:
+                raise RuntimeError("mmsa.inference: return_map=False only makes sense with labels= and evaluator=")
+            if o.fused is False and not o.return_map:
+                raise RuntimeError("mmsa.inference: return_map=False needs the fused launch (two launches go through the stored map); drop fused=False")
+            from . import evaluate
+            one_pass = True      # fused: never with `conf`; no map wanted: only the fused launch can leave it unwritten
+            fused = o.evaluator is not None and o.conf is None and ((evaluate.FUSED_DEFAULT or not o.return_map) if o.fused is None else o.fused)
+        if fused:
+            o.evaluator.add_fused(lg, self, out if o.return_map else None, unc, o.labels, case=o.case)
+            return
+        if one_pass:
+            self._launch(lg, out, unc, o)
+        else:
+            _rescaled_map_canvas(self, lg, out, unc, o.conf, o.it, o.kind)
+        o.count(out)
 
 
 def _canvas_logits(plan, lg, unc):
@@ -525,10 +545,13 @@ def _rescaled_map_canvas(plan, lg, out, unc, conf=None, it=None, kind=0):
     y = y[:, :, :plan.Ho, :plan.Wo].contiguous()
     prob = torch.empty_like(y)
     _softmax_accum(y, prob, it=it)
-    if kind:
-        _argmax_score_into(prob, torch.empty_like(out), conf, kind)
-    else:
-        _argmax_max_into(prob, torch.empty_like(out), conf)
+    _argmax_into(prob, torch.empty_like(out), conf, kind)
+
+
+def _window_logits(backbone, head, cut, windows, max_batch):
+    """The windows through backbone and head in batches of `max_batch`, concatenated -> the head-resolution logits [n, classes, hs, ws]."""
+    lgs = [head(backbone(cut(windows[s:s + max_batch]))[0]) for s in range(0, len(windows), max_batch)]
+    return lgs[0] if len(lgs) == 1 else torch.cat(lgs, 0)
 
 
 @_on_device
@@ -568,26 +591,25 @@ def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preproc
     (mmsa_slide_argmax_score) or, with `ori_shape=`, by mmsa_argmax_score_nchw on the canvas path's probabilities -- the default there, being the faster of the
     two where measured (ONE_PASS_SCORE_RESCALE_DEFAULT) -- or by mmsa_slide_argmax_resized_score (`one_pass=True`: no canvas in memory); the same bits either way.
     `temperature=` combines with it; `calibration=` / `selective=` see whatever score was written.  Other than "max" it is refused without `confidence=`."""
-    _score_kind(score, confidence, "slide_class_map")
-    _inv_temperature(temperature, confidence, "slide_class_map")
-    _check_calibration(calibration, labels, confidence, "slide_class_map", fused, return_map)
-    _check_selective(selective, labels, confidence, "slide_class_map", fused, return_map)
+    o = MapOptions.of("slide_class_map", confidence, temperature, score, one_pass, labels=labels, evaluator=evaluator, case=case, calibration=calibration,
+                      selective=selective, fused=fused, return_map=return_map)
+    return _slide_class_map(o, backbone, head, img, crop_size, stride, max_batch, preprocess, render, ori_shape)
+
+
+def _slide_class_map(o, backbone, head, img, crop_size, stride, max_batch=8, preprocess=None, render=None, ori_shape=None):
+    """slide_class_map behind its options (`class_map` comes here with its own)."""
     B, H, W, device, frame, cut = _intake(img, preprocess, "slide_class_map")
     plan = MapPlan.slide(B, H, W, crop_size, stride, ori_shape)
-    src = None if render is None else slide_source(render, preprocess, frame, plan, return_map, "slide_class_map")
+    src = None if render is None else slide_source(render, preprocess, frame, plan, o.return_map, "slide_class_map")
     plan.check_windows("slide_class_map")
-    conf = _confidence(confidence, (B, plan.Ho, plan.Wo), device, "slide_class_map", fused, return_map)
+    o = o.at((B, plan.Ho, plan.Wo), device, "slide_class_map")
     _pair(backbone, head)
-    lgs = []
-    for s in range(0, plan.n, max_batch):
-        feats, _ = backbone(cut(plan.windows[s:s + max_batch]))
-        lgs.append(head(feats))
-    lg = lgs[0] if len(lgs) == 1 else torch.cat(lgs, 0)
+    lg = _window_logits(backbone, head, cut, plan.windows, max_batch)
     out = torch.empty(B, plan.Ho, plan.Wo, dtype=torch.uint8, device=device)
     unc = torch.zeros(1, dtype=torch.int32, device=device)
-    plan.class_map(lg, out, unc, labels, evaluator, case, fused, return_map, one_pass, conf, calibration, selective, temperature, score)
-    r = (out, unc, render(out, src)) if render is not None else ((out if return_map else None), unc)   # unc[0] != 0 <=> some pixel is not covered (ED:220); checked by the caller outside a capture
-    return r if conf is None else r + (conf,)
+    plan._class_map(lg, out, unc, o)
+    r = (out, unc, render(out, src)) if render is not None else ((out if o.return_map else None), unc)   # unc[0] != 0 <=> some pixel is not covered (ED:220); checked by the caller outside a capture
+    return r if o.conf is None else r + (o.conf,)
 
 
 @_on_device
@@ -613,10 +635,13 @@ def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator
     `selective=`: as in slide_class_map (needs `labels=` and `confidence=`), over the map and confidence stored at the size returned.
     `temperature=`: as in slide_class_map (needs `confidence=`): the confidence of softmax(logits / T) at the size returned.
     `score=`: as in slide_class_map ("margin" / "entropy" need `confidence=`): the map in the confidence slot is that score, at the size returned."""
-    _score_kind(score, confidence, "whole_class_map")
-    _inv_temperature(temperature, confidence, "whole_class_map")
-    _check_calibration(calibration, labels, confidence, "whole_class_map", fused, return_map)
-    _check_selective(selective, labels, confidence, "whole_class_map", fused, return_map)
+    o = MapOptions.of("whole_class_map", confidence, temperature, score, one_pass, labels=labels, evaluator=evaluator, case=case, calibration=calibration,
+                      selective=selective, fused=fused, return_map=return_map)
+    return _whole_class_map(o, backbone, head, img, preprocess, render, ori_shape, dim, cut_dim, rescale)
+
+
+def _whole_class_map(o, backbone, head, img, preprocess=None, render=None, ori_shape=None, dim=None, cut_dim=None, rescale=True):
+    """whole_class_map behind its options (`class_map` comes here with its own)."""
     rgb = None
     if preprocess is not None:
         rgb, aux, B, H, W = _raw(preprocess, img, "whole_class_map")
@@ -624,8 +649,8 @@ def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator
         _check(img)
         B, _, H, W = (int(v) for v in img.shape)
     plan = MapPlan.whole(B, H, W, ori_shape, dim, cut_dim, rescale)
-    src = None if render is None else whole_source(render, rgb, plan, return_map, "whole_class_map")      # the raw frames, or None: the tensor below
-    conf = _confidence(confidence, (B, plan.Ho, plan.Wo), (rgb if rgb is not None else img).device, "whole_class_map", fused, return_map)
+    src = None if render is None else whole_source(render, rgb, plan, o.return_map, "whole_class_map")      # the raw frames, or None: the tensor below
+    o = o.at((B, plan.Ho, plan.Wo), (rgb if rgb is not None else img).device, "whole_class_map")
     if preprocess is not None:
         img = preprocess(rgb, aux)
     if render is not None and src is None:
@@ -635,12 +660,12 @@ def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator
     lg = head(feats)
     out = torch.empty(B, plan.Ho, plan.Wo, dtype=torch.uint8, device=img.device)
     unc = torch.zeros(1, dtype=torch.int32, device=img.device)
-    plan.class_map(lg, out, unc, labels, evaluator, case, fused, return_map, one_pass, conf, calibration, selective, temperature, score)
+    plan._class_map(lg, out, unc, o)
     if render is not None:
-        return (out, render(out, src)) if conf is None else (out, render(out, src), conf)
-    if conf is not None:
-        return out, conf
-    return out if return_map else None
+        return (out, render(out, src)) if o.conf is None else (out, render(out, src), o.conf)
+    if o.conf is not None:
+        return out, o.conf
+    return out if o.return_map else None
 
 
 @_on_device
@@ -717,24 +742,21 @@ def class_map(backbone, head, img, test_cfg, rescale=True, ori_shape=None, prepr
     `temperature=` (T > 0; needs `confidence=`): the confidence of softmax(logits / T), as in the calls it goes to.
     `score=` ("max" | "margin" | "entropy"; other than "max" needs `confidence=`): what the confidence slot holds, as in the calls it goes to."""
     mode = test_cfg["mode"]
-    _score_kind(score, confidence, "class_map")
-    _inv_temperature(temperature, confidence, "class_map")
-    _check_calibration(calibration, labels, confidence, "class_map")
-    _check_selective(selective, labels, confidence, "class_map")
-    kw = dict(preprocess=preprocess, labels=labels, evaluator=evaluator, case=case, render=render, one_pass=one_pass, confidence=confidence,
-              calibration=calibration, selective=selective, temperature=temperature, score=score)
+    o = MapOptions.of("class_map", confidence, temperature, score, one_pass, labels=labels, evaluator=evaluator, case=case, calibration=calibration,
+                      selective=selective)
+    kw = dict(preprocess=preprocess, render=render)
     if mode == "slide":
-        r = slide_class_map(backbone, head, img, tuple(test_cfg["crop_size"]), tuple(test_cfg["stride"]), ori_shape=ori_shape if rescale else None, **kw)
+        r = _slide_class_map(o, backbone, head, img, tuple(test_cfg["crop_size"]), tuple(test_cfg["stride"]), ori_shape=ori_shape if rescale else None, **kw)
         if int(r[1].item()) != 0:
             raise RuntimeError("mmsa.class_map: windows do not cover the image")   # ED:220
         r = (r[0],) + tuple(r[2:])           # without the uncovered-pixel word: (map[, picture][, conf])
         return r[0] if len(r) == 1 else r
     if mode == "whole":
-        return whole_class_map(backbone, head, img, ori_shape=ori_shape if rescale else None, **kw)
+        return _whole_class_map(o, backbone, head, img, ori_shape=ori_shape if rescale else None, **kw)
     if mode == "whole_dim":
-        return whole_class_map(backbone, head, img, dim=tuple(test_cfg["dim"]), rescale=rescale, **kw)
+        return _whole_class_map(o, backbone, head, img, dim=tuple(test_cfg["dim"]), rescale=rescale, **kw)
     if mode == "whole_dim_cut":
-        return whole_class_map(backbone, head, img, dim=tuple(test_cfg["dim"]), cut_dim=tuple(test_cfg["cut_dim"]), rescale=rescale, **kw)
+        return _whole_class_map(o, backbone, head, img, dim=tuple(test_cfg["dim"]), cut_dim=tuple(test_cfg["cut_dim"]), rescale=rescale, **kw)
     raise RuntimeError(f"mmsa.class_map: test_cfg.mode '{mode}' is not one of slide / whole / whole_dim / whole_dim_cut")
 
 
@@ -760,18 +782,31 @@ def _argmax_score_into(prob, out, score, kind):
     lib.call("mmsa_argmax_score_nchw", prob.data_ptr(), out.data_ptr(), score.data_ptr(), B, C, H, W, kind, _inv_log_c(C), ops._stream())
 
 
-@_on_device
-@torch.no_grad()
-def argmax_max_map(prob):
-    """argmax_map that also returns the maximum -> (uint8 [B, H, W], float32 [B, H, W]), one launch (mmsa_argmax_max_nchw).  On the probabilities of
-    `probabilities` / `aug_inference` (ED:449,460) the second is the confidence map: the probability of the predicted class."""
+def _argmax_into(prob, out, conf, kind=0):
+    """The argmax of a canvas of probabilities into `out`, with their maximum (`kind` 0) or the score `kind` into `conf`: one launch."""
+    if kind:
+        _argmax_score_into(prob, out, conf, kind)
+    else:
+        _argmax_max_into(prob, out, conf)
+
+
+def _argmax_pair(prob, kind):
+    """_argmax_into with new outputs -> (uint8 [B, H, W], float32 [B, H, W])."""
     _check(prob)
     prob = prob.contiguous()
     B, C, H, W = prob.shape
     out = torch.empty(B, H, W, dtype=torch.uint8, device=prob.device)
     conf = torch.empty(B, H, W, dtype=torch.float32, device=prob.device)
-    _argmax_max_into(prob, out, conf)
+    _argmax_into(prob, out, conf, kind)
     return out, conf
+
+
+@_on_device
+@torch.no_grad()
+def argmax_max_map(prob):
+    """argmax_map that also returns the maximum -> (uint8 [B, H, W], float32 [B, H, W]), one launch (mmsa_argmax_max_nchw).  On the probabilities of
+    `probabilities` / `aug_inference` (ED:449,460) the second is the confidence map: the probability of the predicted class."""
+    return _argmax_pair(prob, 0)
 
 
 @_on_device
@@ -781,16 +816,7 @@ def argmax_score_map(prob, score="margin"):
     canvas of probabilities (`probabilities` / `aug_inference`): `score=` "margin", the top-2 margin P_(1) - P_(2), or "entropy", 1 - H / log C with H the
     predictive entropy -- on the mean probabilities of augmented views, the usual TTA uncertainty.  Both lie in [0, 1], higher = more certain.  "max" is
     argmax_max_map itself."""
-    kind = _score_kind(score, True, "argmax_score_map")
-    if not kind:
-        return argmax_max_map(prob)
-    _check(prob)
-    prob = prob.contiguous()
-    B, C, H, W = prob.shape
-    out = torch.empty(B, H, W, dtype=torch.uint8, device=prob.device)
-    conf = torch.empty(B, H, W, dtype=torch.float32, device=prob.device)
-    _argmax_score_into(prob, out, conf, kind)
-    return out, conf
+    return _argmax_pair(prob, _score_kind(score, True, "argmax_score_map"))
 
 
 # ---- test-time augmentation: EncoderDecoder.aug_test (ED:509-546) -- several views of a frame (flipped, at several scales), whose probabilities are averaged
@@ -975,17 +1001,16 @@ class AugPlan:
         mmsa_aug_argmax_conf or, on the canvas path, by mmsa_argmax_max_nchw in place of mmsa_argmax_nchw: bit for bit mean_probabilities(...).max(1).
         `score` ("margin" / "entropy", with `conf`): the top-2 margin or the entropy score of the MEAN probabilities goes to `conf` instead, by
         mmsa_argmax_score_nchw on the canvas path, whatever ONE_PASS_AUG_DEFAULT says; `one_pass=True` is refused (mmsa_aug_argmax_conf has no sibling)."""
-        kind = _score_kind(score, conf, "inference")
-        if kind and one_pass:
-            raise RuntimeError(f"mmsa.inference: score={score!r} {_NO_SCORE_AUG_ONE_PASS}")
-        if conf is not None:
-            _check_conf(conf, self.size, out.device)
+        o = MapOptions.of("inference", conf, None, score, one_pass, aug=True)
+        self._class_map(lgs, out, unc, o.at(self.size, out.device if conf is not None else None, "inference", make=False))
+
+    def _class_map(self, lgs, out, unc, o):
+        """`class_map` for aug_class_map, which has made its MapOptions `o` under its own name."""
+        conf = o.conf
         if len(lgs) != self.A or any(lg.shape[0] != p.n for lg, p in zip(lgs, self.plans)):
             raise RuntimeError("mmsa.inference: AugPlan.class_map takes one logits tensor per view, one row per window of that view")
         C = int(lgs[0].shape[1])
-        if kind:
-            _argmax_score_into(self.mean_probabilities(lgs, unc), out, conf, kind)
-        elif (ONE_PASS_AUG_DEFAULT and C <= MAX_AUG_CLASSES) if one_pass is None else one_pass:
+        if not o.kind and ((ONE_PASS_AUG_DEFAULT and C <= MAX_AUG_CLASSES) if o.one_pass is None else o.one_pass):
             lgs = [lg.contiguous() for lg in lgs]
             ptrs = (ctypes.c_void_p * self.A)(*[lg.data_ptr() for lg in lgs])
             rows = (ctypes.c_int * (11 * self.A))(*[v for r in self.rows(lgs) for v in r])
@@ -996,7 +1021,7 @@ class AugPlan:
         elif conf is None:
             out.copy_(argmax_map(self.mean_probabilities(lgs, unc)))
         else:
-            _argmax_max_into(self.mean_probabilities(lgs, unc), out, conf)
+            _argmax_into(self.mean_probabilities(lgs, unc), out, conf, o.kind)
 
 
 _AUG_PLANS = {}
@@ -1061,32 +1086,25 @@ def aug_class_map(backbone, head, imgs, test_cfg, ori_shape=None, flips=None, pr
     `score=` "max" | "margin" | "entropy" (other than "max" needs `confidence=`): the map in the confidence slot is the top-2 margin or the entropy score
     1 - H / log C of the MEAN probabilities -- the usual TTA uncertainty -- bit for bit argmax_score_map(aug_inference(...), score)[1].  Those two go through
     the canvas path (mmsa_argmax_score_nchw), whatever the default; with `one_pass=True` they are refused: mmsa_aug_argmax_conf has no score sibling."""
-    if _score_kind(score, confidence, "aug_class_map") and one_pass:
-        raise RuntimeError(f"mmsa.aug_class_map: score={score!r} {_NO_SCORE_AUG_ONE_PASS}")
-    _check_calibration(calibration, labels, confidence, "aug_class_map")
-    _check_selective(selective, labels, confidence, "aug_class_map")
-    _check_labels(labels, evaluator, calibration, selective)
+    o = MapOptions.of("aug_class_map", confidence, None, score, one_pass, aug=True, labels=labels, evaluator=evaluator, case=case, calibration=calibration,
+                      selective=selective)
     imgs, flips, pre = AugPlan.views(imgs, flips, preprocess, "aug_class_map")
     frames = [_intake(img, p, "aug_class_map") for img, p in zip(imgs, pre)]
     plan = AugPlan.of(test_cfg, [f[:3] for f in frames], flips, ori_shape)
-    conf = _confidence(confidence, plan.size, frames[0][3], "aug_class_map")
+    device = frames[0][3]
+    o = o.at(plan.size, device, "aug_class_map")
     _pair(backbone, head)
     lgs = []
     for mp, p, (_, _, _, _, frame, cut) in zip(plan.plans, pre, frames):
         if test_cfg["mode"] == "slide":
-            part = [head(backbone(cut(mp.windows[s:s + max_batch]))[0]) for s in range(0, mp.n, max_batch)]
-            lgs.append(part[0] if len(part) == 1 else torch.cat(part, 0))
+            lgs.append(_window_logits(backbone, head, cut, mp.windows, max_batch))
         else:
             lgs.append(head(backbone(p(*frame) if p is not None else frame)[0]))
-    device = frames[0][3]
-    B, Ho, Wo = plan.size
-    out = torch.empty(B, Ho, Wo, dtype=torch.uint8, device=device)
+    out = torch.empty(plan.size, dtype=torch.uint8, device=device)
     unc = torch.zeros(1, dtype=torch.int32, device=device)
-    plan.class_map(lgs, out, unc, one_pass, conf, score)
-    if evaluator is not None:
-        evaluator.add(out, labels, case=case)
-    _add_binned(out, conf, labels, case, calibration, selective)
-    return (out, unc) if conf is None else (out, unc, conf)
+    plan._class_map(lgs, out, unc, o)
+    o.count(out)
+    return (out, unc) if o.conf is None else (out, unc, o.conf)
 
 
 class FrameResult:
@@ -1143,8 +1161,7 @@ class SlideRunner:
     def __init__(self, backbone, head, frame, crop_size, stride, chains=2, check_every=1, preprocess=None, render=None, ori_shape=None, one_pass=None,
                  confidence=False, temperature=None, score="max"):
         from .chains import Chains
-        _score_kind(score, confidence, "SlideRunner")
-        _inv_temperature(temperature, confidence, "SlideRunner")
+        o = MapOptions.of("SlideRunner", confidence, temperature, score, one_pass)
         self.preprocess, self.render, self.one_pass, self.temperature, self.score = preprocess, render, one_pass, temperature, score
         B, H, W, self.device, self.frame, self._cut = _intake(frame, preprocess, "SlideRunner")
         self.plan = plan = MapPlan.slide(B, H, W, tuple(crop_size), stride, ori_shape, what="SlideRunner")
@@ -1160,6 +1177,7 @@ class SlideRunner:
             self.out = torch.empty(B, plan.Ho, plan.Wo, dtype=torch.uint8, device=self.device)
             self.unc = torch.zeros(1, dtype=torch.int32, device=self.device)
             self.conf = torch.empty(B, plan.Ho, plan.Wo, dtype=torch.float32, device=self.device) if confidence else None
+            self.options = dataclasses.replace(o, conf=self.conf)      # the runner's half of the family: the scalars a captured launch keeps; run() adds the frame's
             self.pic = None
             if render is not None:
                 render.palette_on(self.device)
@@ -1178,10 +1196,8 @@ class SlideRunner:
         frame's reliability bins are ADDED to it on device by one more launch; a frame that has to be run again has been binned, as it has been counted.
         `selective=` (mmsa.evaluate.SelectiveEvaluator, made the same way; needs `labels=` and a runner made with confidence=True): the frame's confusion
         counts per confidence bin are ADDED to it on device by one more launch, under the same terms."""
-        _check_calibration(calibration, labels, self.conf, "SlideRunner.run", fused, return_map)
-        _check_selective(selective, labels, self.conf, "SlideRunner.run", fused, return_map)
-        if self.conf is not None and (fused or not return_map):
-            raise RuntimeError(f"mmsa.SlideRunner.run: {_NO_CONF_FUSED}")
+        o = self.options.with_call("SlideRunner.run", labels, evaluator, case, calibration, selective, fused, return_map)
+        o = o.at(self.out.shape, self.device, "SlideRunner.run")
         if frame is None:
             frame = self.frame
         else:
@@ -1196,8 +1212,7 @@ class SlideRunner:
             rp = self.chains.replay()
             lg = rp.unverified          # the argmax kernel below is enqueued behind the pass; nothing is read on the host before outputs() verifies it
             self.unc.zero_()
-            self.plan.class_map(lg, self.out, self.unc, labels, evaluator, case, fused, return_map, self.one_pass, self.conf, calibration, selective,
-                                self.temperature, self.score)
+            self.plan._class_map(lg, self.out, self.unc, o)
             if self.render is not None:
                 self.render(self.out, src, out=self.pic)
         return FrameResult(self, rp, has_map=return_map)

@@ -89,10 +89,10 @@ def _calls(models):
 
 
 def _recorded(monkeypatch, head, fn):
-    """The names of the library entries and allocations `fn` makes after its last head call."""
+    """The names of the library entries and allocations `fn` makes after its last head call; `head` None: a call at plan level, all it makes."""
     from mmsa import lib
     names = []
-    real_call, real_forward = lib.call, head.forward
+    real_call, real_forward = lib.call, getattr(head, "forward", None)
 
     def call(name, *args):
         names.append(name)
@@ -113,11 +113,14 @@ def _recorded(monkeypatch, head, fn):
 
     with monkeypatch.context() as mp:
         mp.setattr(lib, "call", call)
-        mp.setattr(head, "forward", forward)
+        if head is not None:
+            mp.setattr(head, "forward", forward)
         for name in ("empty", "zeros"):
             mp.setattr(torch, name, allocator(name))
         fn()
     torch.cuda.synchronize()
+    if head is None:
+        return names
     assert names.count("<head>") == 1, "one encoder batch per case"
     return names[names.index("<head>") + 1:]
 
@@ -131,3 +134,88 @@ def test_launches_after_the_head(models, monkeypatch, case):
 
 def test_every_case_has_a_list(models):
     assert sorted(_calls(models)) == sorted(EXPECTED)
+
+
+# ---- the same recorder at plan level: MapPlan.class_map / AugPlan.class_map on random head-resolution logits, without backbone or head, so the record is
+# the WHOLE call.  Which launch a plan takes for every combination of conf / temperature / score / labels / evaluator / calibration / selective / return_map /
+# one_pass, written out by reading mmsa/inference.py and evaluate.py at the commit before the option record and the launch table, and confirmed by running
+# this file on that commit (an MI355X: every case passed there before the code was touched).  The 40 x 56 frame in
+# 32 x 32 windows at stride 24 (four windows), at its own size and rescaled to 30 x 50; five classes, logits [4, 5, 8, 8].
+P_CANVAS = CANVAS                                                                      # canvas and count, four accumulating resizes, the division
+P_CANVAS_MAP = CANVAS + RESIZE + ["torch.empty", "mmsa_argmax_nchw"]                   # ... the second resize, argmax_map
+PLAN_EXPECTED = {
+    "conf_canvas": P_CANVAS_MAP + ["mmsa_softmax_flip_accum_nchw", "mmsa_argmax_max_nchw"],
+    "conf_t_canvas": P_CANVAS_MAP + ["mmsa_softmax_flip_accum_nchw_t", "mmsa_argmax_max_nchw"],
+    "margin_rescaled_default": P_CANVAS_MAP + ["mmsa_softmax_flip_accum_nchw", "mmsa_argmax_score_nchw"],      # ONE_PASS_SCORE_RESCALE_DEFAULT: the canvas path
+    "margin_rescaled_one_pass": ["mmsa_slide_argmax_resized_score"],
+    "conf_rescaled_default": ["mmsa_slide_argmax_resized_conf"],                                               # ONE_PASS_RESCALE_DEFAULT: one pass
+    "conf_t_rescaled_labels": ["mmsa_slide_argmax_resized_conf_t", "mmsa_eval_confusion_u8", "mmsa_eval_calibration", "mmsa_eval_selective"],
+    "labels_evaluator_conf": ["mmsa_slide_argmax_conf", "mmsa_eval_confusion_u8"],                             # never the fused launch
+    "labels_evaluator_conf_fused_none": ["mmsa_slide_argmax_conf", "mmsa_eval_confusion_u8"],
+    "labels_binned_no_evaluator": ["mmsa_slide_argmax_conf", "mmsa_eval_calibration", "mmsa_eval_selective"],
+    "labels_all_three_entropy_t": ["mmsa_slide_argmax_score", "mmsa_eval_confusion_u8", "mmsa_eval_calibration", "mmsa_eval_selective"],
+    "labels_evaluator_no_map": ["mmsa_slide_argmax_eval"],                                                    # the fused launch alone
+    "labels_evaluator_two_launches": ["mmsa_slide_argmax", "mmsa_eval_confusion_u8"],
+    "labels_evaluator_rescaled": ["mmsa_slide_argmax_resized", "mmsa_eval_confusion_u8"],                      # a rescaled plan counts through the stored map
+    "aug_conf": 2 * (P_CANVAS + ["mmsa_softmax_flip_accum_nchw"]) + ["mmsa_argmax_max_nchw"],
+    "aug_entropy": 2 * (P_CANVAS + RESIZE + ["mmsa_softmax_flip_accum_nchw"]) + ["mmsa_argmax_score_nchw"],     # its views are rescaled to 30 x 50
+    "aug_plain": 2 * (P_CANVAS + ["mmsa_softmax_flip_accum_nchw"]) + ["torch.empty", "mmsa_argmax_nchw"],
+}
+
+
+@pytest.fixture(scope="module")
+def plan_calls():
+    """name -> the plan-level call of that case; everything a first call uploads or allocates is on the device before any of them is recorded."""
+    from mmsa.evaluate import Calibration, Evaluator, LabelPrep, SelectiveEvaluator
+    from mmsa.inference import AugPlan, MapPlan
+    g = torch.Generator().manual_seed(11)
+    C, lp = 5, LabelPrep(5)
+    lp.lut_on(torch.device(DEV))
+    lg = torch.randn(4, C, 8, 8, generator=g).to(DEV)
+    lg2 = torch.randn(4, C, 8, 8, generator=g).to(DEV)
+    plans = {None: MapPlan.slide(1, 40, 56, (32, 32), (24, 24)), "ori": MapPlan.slide(1, 40, 56, (32, 32), (24, 24), ori_shape=(30, 50))}
+    labs = {k: torch.randint(0, C, (1, p.Ho, p.Wo), generator=g, dtype=torch.uint8).to(DEV) for k, p in plans.items()}
+    cfg = dict(mode="slide", crop_size=(32, 32), stride=(24, 24))
+    augs = {k: AugPlan.make(cfg, [(1, 40, 56)] * 2, [None, "horizontal"], ori_shape=o) for k, o in ((None, None), ("ori", (30, 50)))}
+    ev, cal, sel = (cls(lp, images=64, device=DEV) for cls in (Evaluator, Calibration, SelectiveEvaluator))
+
+    def run(key=None, conf=True, aug=False, **kw):
+        plan = (augs if aug else plans)[key]
+        B, Ho, Wo = plan.size if aug else (plan.B, plan.Ho, plan.Wo)
+        out = torch.empty(B, Ho, Wo, dtype=torch.uint8, device=DEV)
+        unc = torch.zeros(1, dtype=torch.int32, device=DEV)
+        cf = torch.empty(B, Ho, Wo, dtype=torch.float32, device=DEV) if conf else None
+        if "labels" in kw:
+            kw["labels"] = labs[key]
+
+        return lambda: plan.class_map([lg, lg2] if aug else lg, out, unc, conf=cf, **kw)
+
+    return dict(
+        conf_canvas=run("ori", one_pass=False),
+        conf_t_canvas=run("ori", one_pass=False, temperature=1.7),
+        margin_rescaled_default=run("ori", score="margin"),
+        margin_rescaled_one_pass=run("ori", score="margin", one_pass=True),
+        conf_rescaled_default=run("ori"),
+        conf_t_rescaled_labels=run("ori", temperature=1.7, labels=True, evaluator=ev, calibration=cal, selective=sel),
+        labels_evaluator_conf=run(labels=True, evaluator=ev, fused=False),
+        labels_evaluator_conf_fused_none=run(labels=True, evaluator=ev),
+        labels_binned_no_evaluator=run(labels=True, calibration=cal, selective=sel),
+        labels_all_three_entropy_t=run(score="entropy", temperature=1.7, labels=True, evaluator=ev, calibration=cal, selective=sel),
+        labels_evaluator_no_map=run(conf=False, labels=True, evaluator=ev, return_map=False),
+        labels_evaluator_two_launches=run(conf=False, labels=True, evaluator=ev, fused=False),
+        labels_evaluator_rescaled=run("ori", conf=False, labels=True, evaluator=ev),
+        aug_conf=run(aug=True),
+        aug_entropy=run("ori", aug=True, score="entropy"),
+        aug_plain=run(aug=True, conf=False),
+    )
+
+
+@pytest.mark.parametrize("case", sorted(PLAN_EXPECTED))
+def test_launches_of_a_plan(plan_calls, monkeypatch, case):
+    got = _recorded(monkeypatch, None, plan_calls[case])
+    print(f"{case}: {got}")
+    assert got == PLAN_EXPECTED[case]
+
+
+def test_every_plan_case_has_a_list(plan_calls):
+    assert sorted(plan_calls) == sorted(PLAN_EXPECTED)

@@ -96,3 +96,61 @@ def test_plan_is_immutable():
     p = MapPlan.whole(1, 64, 88)
     with pytest.raises(dataclasses.FrozenInstanceError):
         p.H = 65
+
+
+# ---- which library entry a plan's class_map calls, and with which arguments, as a literal table: mmsa.lib.call is recorded, nothing runs.  Logits
+# [1, 5, 2, 2] of one full-size 8 x 8 window; the rescaled plan ends at 12 x 10.  `tail`: what stands between the uncovered-pixel word and the stream --
+# nothing, the inverse temperature of the `_t` entries, or (kind, inverse temperature, 1 / log C) of the `_score` entries (1.0 where no temperature is given).
+def _dispatch_options():
+    from mmsa.evaluate import inv_log_classes, inv_temperature
+    it, ilc = inv_temperature(2.0), inv_log_classes(5)
+    return [    # keywords besides conf=, takes conf, suffix of the entry's name, tail
+        (dict(), False, "", ()),
+        (dict(), True, "_conf", ()),
+        (dict(temperature=2.0), True, "_conf_t", (it,)),
+        (dict(score="margin"), True, "_score", (1, 1.0, ilc)),
+        (dict(score="entropy", temperature=2.0), True, "_score", (2, it, ilc)),
+    ]
+
+
+def _dispatched(monkeypatch, plan, kw, with_conf):
+    """The (name, args) of every mmsa.lib.call that plan.class_map(...) makes on CPU tensors, and the tensors."""
+    import torch
+    from mmsa import lib, ops
+    calls = []
+    lg = torch.zeros(plan.n, 5, 2, 2)
+    out = torch.zeros(plan.B, plan.Ho, plan.Wo, dtype=torch.uint8)
+    unc = torch.zeros(1, dtype=torch.int32)
+    conf = torch.zeros(plan.B, plan.Ho, plan.Wo) if with_conf else None
+    with monkeypatch.context() as mp:
+        mp.setattr(lib, "call", lambda name, *args: calls.append((name, args)))
+        mp.setattr(ops, "_stream", lambda: None)
+        plan.class_map(lg, out, unc, conf=conf, **kw)
+    return calls, lg, out, unc, conf
+
+
+def test_class_map_dispatch_at_frame_size(monkeypatch):
+    from mmsa.inference import MapPlan
+    plan = MapPlan.whole(1, 8, 8)
+    for kw, with_conf, suffix, tail in _dispatch_options():
+        calls, lg, out, unc, conf = _dispatched(monkeypatch, plan, kw, with_conf)
+        assert len(calls) == 1, (kw, calls)
+        name, args = calls[0]
+        outs = (out.data_ptr(), conf.data_ptr()) if with_conf else (out.data_ptr(),)
+        assert name == "mmsa_slide_argmax" + suffix, kw
+        assert args == (lg.data_ptr(), 1, 5, 2, 2, plan.tab) + outs + (1, 8, 8, 8, 8, unc.data_ptr()) + tail + (None,), (kw, args)
+        assert len(args) == 14 + with_conf + len(tail)       # no (Hd, Wd, Ho, Wo), and no scalar the entry does not take
+
+
+def test_class_map_dispatch_at_a_rescaled_size(monkeypatch):
+    from mmsa.inference import MapPlan
+    plan = MapPlan.whole(1, 8, 8, ori_shape=(12, 10))
+    for kw, with_conf, suffix, tail in _dispatch_options():
+        for one_pass in (True,) if "score" in kw else (True, None):      # None follows ONE_PASS_RESCALE_DEFAULT: one pass; with a score the default is the canvas path (a device)
+            calls, lg, out, unc, conf = _dispatched(monkeypatch, plan, dict(kw, one_pass=one_pass), with_conf)
+            assert len(calls) == 1, (kw, one_pass, calls)
+            name, args = calls[0]
+            outs = (out.data_ptr(), conf.data_ptr()) if with_conf else (out.data_ptr(),)
+            assert name == "mmsa_slide_argmax_resized" + suffix, (kw, one_pass)
+            assert args == (lg.data_ptr(), 1, 5, 2, 2, plan.tab) + outs + (1, 8, 8, 8, 8, 12, 10, 12, 10, unc.data_ptr()) + tail + (None,), (kw, one_pass, args)
+            assert len(args) == 18 + with_conf + len(tail)
