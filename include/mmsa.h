@@ -530,6 +530,34 @@ int mmsa_slide_argmax_resized_score(const float* logits, int n, int C, int hs, i
                                     int W, int hc, int wc, int Hd, int Wd, int Hcut, int Wcut, int* uncovered, int kind, float inv_temperature,
                                     float inv_log_c, mmsa_stream_t stream);
 
+/* --- top-k maps (the reference has no such step): the first K classes of every pixel and their probabilities, 1 <= K <= 8, rank-major:
+ *     classes uint8 [K, B, Ho, Wo], probs float32 [K, B, Ho, Wo] -- every rank plane is a class map / confidence map in the format every other entry takes.
+ *     The probabilities are the float32 p_c the confidence paths form (one view: e_c / s of the tempered softmax above; several views: their mean); only
+ *     comparisons and moves are added, no rounding:
+ *       rank 0      = bi, the class the map names, with p[bi]: classes[0] IS the class map, probs[0] IS the confidence map, bit for bit;
+ *       rank r >= 1 = among the classes not yet ranked the one with the largest p_c, the lowest class index among equal values (class order, `>`):
+ *                     probs[0] - probs[1], one float32 subtraction, IS the top-2 margin for C >= 2;
+ *       rank r >= C = class 255 with probability 0; a pixel whose map byte is 255 (uncovered) has 255 / 0 at every rank.
+ *     K outside 1..8, C > 255 or a null pointer: MMSA_ERR_ARG with a message.
+ *   slide_argmax_topk: mmsa_slide_argmax_conf_t with the K planes in the place of out / conf (same arguments, same checks, same class map in plane 0; K before
+ *     inv_temperature, which is always given: 1.0f is the untempered softmax, exactly).  A per-lane LDS column up to 64 classes, three recomputing passes from
+ *     65 on; the rank list of a pixel stays in registers (2 / 4 / 8 slots, the smallest that holds K).
+ *   argmax_topk_nchw: on a canvas of probabilities [B, C, H, W].  first == NULL: bi = their first maximum (the augmented path's map, as argmax_score_nchw).
+ *     first = a uint8 map [B, H, W]: bi = its byte -- the one-view canvas path, whose map is the argmax of the LOGITS (two logits can round to one
+ *     probability); a byte that is no class of the canvas (255) gives 255 / 0 at every rank.  first may be `classes` itself (plane 0, in place): a lane reads
+ *     its byte before it writes.  Bit for bit slide_argmax_topk on the probabilities of the canvas path.
+ *   eval_topk_u8: counts int64 [n_slots, C, K + 1], ADDED to (the caller zeroes it).  The label side -- lut, ymap / xmap (both or neither, clamped into the
+ *     label map), slots (HOST int [B]) -- is mmsa_eval_confusion_u8's.  A pixel takes part iff l = lut[label byte] is a class, l < C; it adds 1 at
+ *     [slot, l, r], r = the first rank whose class byte equals l, K if none does.  Column r is the diagonal of mmsa_eval_confusion_u8 on plane r, row l sums to
+ *     row l of plane 0's matrix; the cumulative column sums are the top-1 .. top-K pixel accuracies.  Integer sums: the same bytes whatever the order of
+ *     arrival.  2 <= C <= 255, 1 <= B <= 64. --- */
+int mmsa_slide_argmax_topk(const float* logits, int n, int C, int hs, int ws, const int* windows, unsigned char* classes, float* probs, int B, int H, int W,
+                           int hc, int wc, int* uncovered, int K, float inv_temperature, mmsa_stream_t stream);
+int mmsa_argmax_topk_nchw(const float* prob, const unsigned char* first, unsigned char* classes, float* probs, int B, int C, int H, int W, int K,
+                          mmsa_stream_t stream);
+int mmsa_eval_topk_u8(const unsigned char* classes, int K, const unsigned char* label, int B, int H, int W, int Hl, int Wl, const unsigned char* lut, int C,
+                      const int* ymap, const int* xmap, const int* slots, int n_slots, int64_t* counts, mmsa_stream_t stream);
+
 /* --- the picture of a prediction (segmentation/mmseg_custom/apis/test_bs.py:257-349, the `--show` / `--show-dir` output): `tensor2imgs` (test_bs.py:18-63) on
  *     planes 0..2 of the input tensor -> the crop `img[:h, :w]` (test_bs.py:275-276) -> `show_result` (tools/color_gt_according_palette.py:23-81:
  *     color_seg[seg == label] = color, channels reversed, img * (1 - opacity) + color_seg * opacity, .astype(uint8)), in one pass.

@@ -17,7 +17,9 @@
  *      mmsa_temperature_sweep_nchw (reliability bins and NLL of a logits canvas for a grid of temperatures in one pass).
  *      Still 114: new entries mmsa_argmax_score_nchw / mmsa_slide_argmax_score / mmsa_slide_argmax_resized_score (the top-2 margin or the entropy score in the
  *      confidence's place).  No existing entry changed its arguments or their meaning, and a library without the new symbols fails the binding's symbol lookup
- *      (mmsa/lib.py) before the number is read, so the number that tests/test_temperature_cpu.py pins stays. */
+ *      (mmsa/lib.py) before the number is read, so the number that tests/test_temperature_cpu.py pins stays.
+ *      Still 114, for the same reason: new entries mmsa_slide_argmax_topk / mmsa_argmax_topk_nchw / mmsa_eval_topk_u8 (the first K classes of every pixel and
+ *      their probabilities as rank-major planes, and the rank of the label's class counted per class). */
 #ifndef MMSA_VERSION_H
 #define MMSA_VERSION_H
 #define MMSA_ABI_VERSION 114

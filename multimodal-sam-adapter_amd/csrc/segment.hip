@@ -552,3 +552,114 @@ extern "C" int mmsa_slide_argmax_resized_score(const float* logits, int n, int C
   return slide_argmax_resized_launch("slide_argmax_resized_score", logits, n, C, hs, ws, windows, out, score, B, H, W, hc, wc, Hd, Wd, Hcut, Wcut, uncovered, stream,
                                      &inv_temperature, &kind, inv_log_c);
 }
+
+// ---- top-k maps: the first K classes of every pixel and their probabilities (csrc/softmax_px.h: TopkPx<S>, comparisons and moves on the float32 probabilities
+// p_c the confidence paths form), classes uint8 / probs float32 [K, B, Ho, Wo], rank-major: plane 0 of the classes IS the class map, plane 0 of the
+// probabilities IS the confidence map, and probs[0] - probs[1] is the top-2 margin, bit for bit.  The rank list lives in registers (S = 2 / 4 / 8 slots, the
+// smallest that holds K: the predicates of the unrolled insert are paid per class).  They stand here, behind every other kernel and below the launchers of the
+// entries above, for the reason given above argmax_max_nchw_kernel (profiles/topk_isa.txt).
+#define MMSA_CHECK_TOPK(name, K) MMSA_CHECK_ARG((K) >= 1 && (K) <= TOPK_MAX, "%s: K = %d; 1..%d ranks are supported (the rank list of a pixel is kept in registers)", name, K, TOPK_MAX)
+#define TOPK_DISPATCH(K, LAUNCH) \
+  do {                           \
+    if ((K) <= 2) LAUNCH(2);     \
+    else if ((K) <= 4) LAUNCH(4); \
+    else LAUNCH(8);              \
+  } while (0)
+
+// argmax_score_nchw_kernel with the rank list in the score's place: on a canvas of probabilities (one view's, or the mean over augmented views).  `first` NULL:
+// bi = the first maximum of the probabilities (the augmented path's map); else bi = first[i], the map of the one-view canvas path, which is the argmax of the
+// LOGITS (two logits can round to one probability, and the later one may be the map's).  A lane reads first[i] before it writes classes[i]: `first` may be plane 0.
+template <int S>
+__global__ __launch_bounds__(256) void argmax_topk_nchw_kernel(const float* __restrict__ x, const unsigned char* first, unsigned char* classes,
+                                                               float* __restrict__ probs, int C, long HW, long total, int K) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;   // b * HW + p
+  if (i >= total) return;
+  const long b = i / HW, p = i - b * HW;
+  const float* xp = x + b * C * HW + p;
+  int bi = 0;
+  if (first) {
+    bi = first[i];
+    if (bi >= C) {      // 255 = uncovered (any byte that is no class of the canvas is treated alike)
+      topk_px_store_none(classes, probs, total, i, K, 0);
+      return;
+    }
+  } else {
+    float best = xp[0];
+    for (int c = 1; c < C; ++c) {
+      const float v = xp[(long)c * HW];
+      if (v > best) { best = v; bi = c; }
+    }
+  }
+  TopkPx<S> tk;
+  topk_px_init(tk);
+  for (int c = 0; c < C; ++c) topk_px_class(tk, bi, c, xp[(long)c * HW]);
+  topk_px_store(tk, classes, probs, total, i, K, 0);
+}
+
+extern "C" int mmsa_argmax_topk_nchw(const float* prob, const unsigned char* first, unsigned char* classes, float* probs, int B, int C, int H, int W, int K,
+                                     hipStream_t stream) {
+  MMSA_CHECK_ARG(prob && classes && probs, "argmax_topk_nchw: prob, classes and probs are required");
+  MMSA_CHECK_ARG(C > 0 && C <= 255, "argmax_topk_nchw: %d classes; 1..255 are supported (255 is the byte of a rank without a class)", C);
+  MMSA_CHECK_TOPK("argmax_topk_nchw", K);
+  MMSA_CHECK_ARG(B > 0 && H > 0 && W > 0, "argmax_topk_nchw: bad args");
+  const long HW = (long)H * W, total = (long)B * HW;
+#define TOPK_LAUNCH(S) hipLaunchKernelGGL(argmax_topk_nchw_kernel<S>, dim3(cdiv(total, 256)), dim3(256), 0, stream, prob, first, classes, probs, C, HW, total, K)
+  TOPK_DISPATCH(K, TOPK_LAUNCH);
+#undef TOPK_LAUNCH
+  MMSA_CHECK_LAUNCH("argmax_topk_nchw");
+  return MMSA_OK;
+}
+
+// slide_argmax_kernel + the rank planes, in the two forms of the score (slide_pixel.inc SLIDE_TOPK): the per-lane LDS column up to SLIDE_CONF_LDS_CLASSES
+// classes, three recomputing passes above that (65 .. 255 classes).  `out` / `conf` are the planes [K, B, H, W], `plane` = B * H * W.
+template <int S>
+__global__ __launch_bounds__(256) void slide_argmax_topk_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
+                                                                float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, WindowTable wt,
+                                                                int* __restrict__ uncovered, int K, long plane, float it) {
+#define SLIDE_TOPK 1
+#define SLIDE_Y blockIdx.y
+#define SLIDE_EXIT return
+#include "slide_pixel.inc"
+}
+
+template <int S>
+__global__ __launch_bounds__(256) void slide_argmax_topk_lds_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
+                                                                    float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, WindowTable wt,
+                                                                    int* __restrict__ uncovered, int K, long plane, float it) {
+  extern __shared__ float conf_lds[];
+  float* conf_col = conf_lds + threadIdx.x;      // private to the lane: no barrier
+#define SLIDE_TOPK 2
+#define SLIDE_Y blockIdx.y
+#define SLIDE_EXIT return
+#include "slide_pixel.inc"
+}
+
+// mmsa_slide_argmax_conf_t with the K planes in the place of out / conf: the same checks in the same order, K's behind the geometry's.
+extern "C" int mmsa_slide_argmax_topk(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* classes, float* probs,
+                                      int B, int H, int W, int hc, int wc, int* uncovered /* device int, zeroed by the caller */, int K, float inv_temperature,
+                                      hipStream_t stream) {
+  const char* name = "slide_argmax_topk";
+  MMSA_CHECK_ARG(logits && classes && probs && uncovered, "%s: logits, classes, probs and uncovered are required", name);
+  MMSA_CHECK_ARG(C > 0 && C <= 255, "%s: %d classes; 1..255 are supported (255 is the byte of a rank without a class)", name, C);
+  MMSA_CHECK_ARG(hs > 0 && ws > 0 && hc > 0 && wc > 0 && B > 0 && H <= 65535 && B <= 65535, "%s: bad args", name);
+  MMSA_CHECK_TOPK(name, K);
+  MMSA_CHECK_INV_TEMPERATURE(name, inv_temperature);
+  WindowTable wt;
+  if (int rc = fill_windows(wt, windows, n, B, H, W, hc, wc, name)) return rc;
+  const bool lds = C <= SLIDE_CONF_LDS_CLASSES;
+  const dim3 grid(cdiv(W, 256), H, B);
+  const size_t col = lds ? (size_t)C * 256 * sizeof(float) : 0;      // the per-lane LDS column
+  const float rh = (float)hs / (float)hc, rw = (float)ws / (float)wc;
+  const long plane = (long)B * H * W;
+#define TOPK_LAUNCH(S)                                                                                                                                    \
+  do {                                                                                                                                                    \
+    if (lds) hipLaunchKernelGGL(slide_argmax_topk_lds_kernel<S>, grid, dim3(256), col, stream, logits, C, hs, ws, classes, probs, H, W, hc, wc, rh, rw, wt, \
+                                uncovered, K, plane, inv_temperature);                                                                                    \
+    else hipLaunchKernelGGL(slide_argmax_topk_kernel<S>, grid, dim3(256), 0, stream, logits, C, hs, ws, classes, probs, H, W, hc, wc, rh, rw, wt,         \
+                            uncovered, K, plane, inv_temperature);                                                                                        \
+  } while (0)
+  TOPK_DISPATCH(K, TOPK_LAUNCH);
+#undef TOPK_LAUNCH
+  MMSA_CHECK_LAUNCH(name);
+  return MMSA_OK;
+}

@@ -15,6 +15,10 @@
 //                 formed from the probabilities p_c = e_c / s of softmax(x * it) (`it` always given: the product is exact at 1.0f), which need s first: hence a
 //                 THIRD pass over the classes.  1: both later passes recompute acc / cnt, any C the map allows.  2: the per-lane LDS column of SLIDE_CONF 2;
 //                 the sum pass overwrites x_c with e_c, so the third pass calls no expf.  An uncovered pixel (map 255) gets 0.
+//   SLIDE_TOPK 1 / 2: (with every other switch 0; not defined = 0) slide_argmax_topk_kernel<S> / slide_argmax_topk_lds_kernel<S> -- the pixel's first K classes
+//                 and their probabilities (csrc/softmax_px.h, TopkPx<S>) go to the rank-major planes `out` uint8 / `conf` float [K, B, H, W] (`plane` = B * H * W):
+//                 the map's own store writes plane 0 of the classes, the rank list the rest.  The three passes of SLIDE_SCORE 1 / 2 with topk_px_class in
+//                 score_px_class's place.  An uncovered pixel gets 255 / 0 at every rank.  In scope beside SLIDE_SCORE's: S, K, plane (no kind, no ilc).
 // SLIDE_Y is the pixel's row: blockIdx.y in the first kernel, the row variable of the second kernel's loop over its workgroup's rows.
 // SLIDE_EXIT leaves the body: `return` in the first kernel, `continue` with the next row in the second, which still has its histogram to flush.
 // SLIDE_EXIT MUST NOT be used inside a loop of this body: there `continue` would go on with that loop in the second kernel only, where `return`
@@ -32,6 +36,9 @@
 #endif
 #ifndef SLIDE_SCORE
 #define SLIDE_SCORE 0
+#endif
+#ifndef SLIDE_TOPK
+#define SLIDE_TOPK 0
 #endif
 #if SLIDE_TEMP
 #define SLIDE_EXP(v, m) softmax_px_exp_t(v, m, it)
@@ -93,6 +100,9 @@
 #if SLIDE_CONF || SLIDE_SCORE
     conf[((long)b * H + y) * W + x] = 0.f;
 #endif
+#if SLIDE_TOPK
+    topk_px_store_none(out, conf, plane, ((long)b * H + y) * W + x, K, 1);
+#endif
     SLIDE_EXIT;
   }
   const float cnt = (float)nk;
@@ -101,7 +111,7 @@
   for (int c = 0; c < C; ++c) {
     SLIDE_WINDOW_SUM(acc, c)
     const float p = acc / cnt;
-#if SLIDE_CONF == 2 || SLIDE_SCORE == 2
+#if SLIDE_CONF == 2 || SLIDE_SCORE == 2 || SLIDE_TOPK == 2
     conf_col[c * 256] = p;
 #endif
     if (c == 0 || p > best) { best = p; bi = c; }
@@ -147,8 +157,33 @@
     }
   conf[((long)b * H + y) * W + x] = score_px_finish(kind, sa, spb, snone, ilc);
 #endif
+#if SLIDE_TOPK == 2
+  float s = 0.f;
+  for (int c = 0; c < C; ++c) {
+    const float e = softmax_px_exp_t(conf_col[c * 256], best, it);
+    conf_col[c * 256] = e;
+    s = softmax_px_sum(s, e, c == 0);
+  }
+  TopkPx<S> tk;
+  topk_px_init(tk);
+  for (int c = 0; c < C; ++c) topk_px_class(tk, bi, c, softmax_px_prob(conf_col[c * 256], s));
+  topk_px_store(tk, out, conf, plane, ((long)b * H + y) * W + x, K, 1);
+#elif SLIDE_TOPK
+  float s = 0.f;
+  TopkPx<S> tk;
+  topk_px_init(tk);
+  for (int pass = 0; pass < 2; ++pass)      // 0: the sum of the exponentials; 1: the probabilities, class by class, into the rank list
+    for (int c = 0; c < C; ++c) {
+      SLIDE_WINDOW_SUM(acc, c)
+      const float e = softmax_px_exp_t(acc / cnt, best, it);
+      if (pass == 0) s = softmax_px_sum(s, e, c == 0);
+      else topk_px_class(tk, bi, c, softmax_px_prob(e, s));
+    }
+  topk_px_store(tk, out, conf, plane, ((long)b * H + y) * W + x, K, 1);
+#endif
 #undef SLIDE_WINDOW_SUM
 #undef SLIDE_EXP
+#undef SLIDE_TOPK
 #undef SLIDE_EVAL
 #undef SLIDE_CONF
 #undef SLIDE_TEMP

@@ -19,6 +19,14 @@
 //   kind 2, entropy score:  max(0, 1 - H * ilc), H = sum_c (p_c > 0 ? -(p_c * logf(p_c)) : 0) in class order from the first term (ocml's logf, as expf
 //                           above), `ilc` = float32(1 / log(float64(C))) made on the host (mmsa.evaluate.inv_log_classes), 0 for C == 1 (score 1)
 // Higher = more certain, in [0, 1], as the confidence is.  score_px_class is one class's step (class order), score_px_finish the pixel's score.
+// The top-K of a pixel, 1 <= K <= 8, stated ONCE too: the first K classes of the pixel and their float32 probabilities p_c above -- comparisons and moves only,
+// no arithmetic, so every path that forms the same p_c names the same classes and writes the same bits:
+//   rank 0      = bi, the class the map names, with p[bi] (so plane 0 of the classes IS the map and plane 0 of the probabilities IS the confidence);
+//   rank r >= 1 = among the classes not yet ranked the one with the largest p_c, the lowest class index among equal values: classes come in class order and
+//                 one moves ahead of a ranked class only with `>`, as score_px_second does (rank 1's probability is its p2);
+//   rank r >= C = class 255 with probability 0; a pixel whose map byte is 255 gets 255 / 0 at every rank.
+// TopkPx<S> is the rank list, S = 2 / 4 / 8 slots >= K, indexed by unrolled constants only (predicated inserts: it stays in registers); an empty slot is
+// class 255 with "probability" -1, which every p_c >= 0 beats.  topk_px_init, then topk_px_class once per class in class order, then topk_px_store.
 // Include it AFTER `#pragma clang fp contract(off)`.
 #pragma once
 
@@ -52,4 +60,51 @@ __device__ __forceinline__ void score_px_class(int kind, int bi, int c, float p,
 __device__ __forceinline__ float score_px_finish(int kind, float a, float pb, bool none, float ilc) {
   if (kind == SCORE_MARGIN) return none ? pb : score_px_margin(pb, a);
   return score_px_entropy(a, ilc);
+}
+
+#define TOPK_MAX 8
+#define TOPK_NONE 255
+template <int S>
+struct TopkPx {
+  float p[S];
+  int c[S];
+};
+template <int S>
+__device__ __forceinline__ void topk_px_init(TopkPx<S>& t) {
+#pragma unroll
+  for (int q = 0; q < S; ++q) { t.p[q] = -1.f; t.c[q] = TOPK_NONE; }
+}
+// class c of the pixel, probability p: bi takes slot 0 whatever its value; any other class goes in front of the first slot of 1 .. S-1 it beats with `>`, and
+// the slots from there on move one down (the last one drops out).  Slot q is rewritten before slot q - 1, so each move reads a value not yet overwritten.
+// Written as selects on the values, never as a store under a branch: the compiler merges two such stores into ONE store through a selected address, and a
+// rank list addressed at run time goes to scratch.
+template <int S>
+__device__ __forceinline__ void topk_px_class(TopkPx<S>& t, int bi, int c, float p) {
+  const bool is = c == bi;
+  t.p[0] = is ? p : t.p[0];
+  t.c[0] = is ? c : t.c[0];
+#pragma unroll
+  for (int q = S - 1; q >= 1; --q) {
+    const bool in = !is && p > t.p[q];                             // c stands at slot q or in front of it
+    const bool here = q == 1 || !(p > t.p[q - 1]);                 // ... at slot q
+    t.p[q] = in ? (here ? p : t.p[q - 1]) : t.p[q];
+    t.c[q] = in ? (here ? c : t.c[q - 1]) : t.c[q];
+  }
+}
+// ranks r0 .. K-1 of the classes (r0 = 1 where the map's own store has written plane 0) and 0 .. K-1 of the probabilities go to pixel i of their planes
+template <int S>
+__device__ __forceinline__ void topk_px_store(const TopkPx<S>& t, unsigned char* classes, float* probs, long plane, long i, int K, int r0) {
+#pragma unroll
+  for (int q = 0; q < S; ++q)
+    if (q < K) {
+      if (q >= r0) classes[q * plane + i] = (unsigned char)t.c[q];
+      probs[q * plane + i] = t.c[q] == TOPK_NONE ? 0.f : t.p[q];
+    }
+}
+// the pixel without a class (map byte 255): 255 / 0 at ranks r0 .. K-1 / 0 .. K-1
+__device__ __forceinline__ void topk_px_store_none(unsigned char* classes, float* probs, long plane, long i, int K, int r0) {
+  for (int r = 0; r < K; ++r) {
+    if (r >= r0) classes[r * plane + i] = TOPK_NONE;
+    probs[r * plane + i] = 0.f;
+  }
 }

@@ -8,6 +8,7 @@ from . import inference  # noqa: F401  (encode_decode / slide_inference / argmax
 from .inference import AugPlan, aug_class_map, aug_inference, probabilities  # noqa: F401  (test-time augmentation: aug_test)
 from .inference import argmax_max_map  # noqa: F401  (class map + confidence map of a probability canvas)
 from .inference import argmax_score_map  # noqa: F401  (class map + uncertainty map -- top-2 margin or entropy score -- of a probability canvas)
+from .inference import TopK, argmax_topk_map  # noqa: F401  (the first K classes of every pixel and their probabilities, as rank-major planes)
 from .backbone import OperandRangeError, SAMAdapterbimodalMixModNewInTwinConvNEW, SAMAdapterbimodalMixModNewInTwinConvNEWwithcp
 from .head import SegformerHead
 from .chains import AttentionRangeError, Chains, Replay
@@ -18,6 +19,7 @@ from .evaluate import Evaluator, LabelPrep, confusion
 from .evaluate import Calibration, calibration  # noqa: F401  (reliability bins, ECE and risk-coverage of the confidence map on device)
 from .evaluate import SelectiveEvaluator, selective, abstain  # noqa: F401  (confusion counts per confidence bin: mIoU against coverage; the thresholded map)
 from .evaluate import TemperatureSweep, temperature_sweep  # noqa: F401  (temperature scaling: NLL and reliability bins of a logits canvas over a grid of T)
+from .evaluate import TopKEvaluator, topk_counts  # noqa: F401  (the rank of the label's class in a top-k map: top-k pixel accuracy and recall@k)
 from . import render  # noqa: F401  (the picture of a prediction on device: palette map over the frame, show_result)
 from .render import Renderer
 from .registry import BACKBONES, HEADS, build_backbone, build_head
@@ -43,4 +45,5 @@ if not _HAVE_MMSEG:     # local registry (no mmseg in the process): nothing to o
 __all__ = ["SegformerHead", "HEADS", "build_head", "register_head", "SAMAdapterbimodalMixModNewInTwinConvNEW", "SAMAdapterbimodalMixModNewInTwinConvNEWwithcp",
            "BACKBONES", "build_backbone", "ops", "lib", "inference", "Chains", "Replay", "AttentionRangeError", "OperandRangeError",
            "preprocess", "Preprocess", "FrameFeeder", "evaluate", "Evaluator", "LabelPrep", "confusion", "Calibration", "calibration", "SelectiveEvaluator", "selective", "abstain", "TemperatureSweep", "temperature_sweep", "render", "Renderer",
-           "probabilities", "aug_inference", "aug_class_map", "AugPlan", "argmax_max_map", "argmax_score_map"]
+           "probabilities", "aug_inference", "aug_class_map", "AugPlan", "argmax_max_map", "argmax_score_map", "TopK", "argmax_topk_map",
+           "TopKEvaluator", "topk_counts"]

@@ -27,7 +27,12 @@ Temperature scaling closes the loop from a poor ECE to a better confidence: `tem
 `mmsa.inference.inference` returns) against the labels, for a whole grid of temperatures in one launch (mmsa_temperature_sweep_nchw, csrc/temperature.hip),
 to int64 [J, 4, K] per slot -- per temperature, Calibration's three rows of the confidence max_c softmax(x / T)_c, and the NLL of the label's class in 20-bit
 fixed point.  `best()` names the grid's minimum of the NLL or of the ECE; a second, narrower `geometric_grid` around it refines; there is no iterative
-optimiser.  The fitted T then goes to `temperature=` of the class-map entries of mmsa.inference, whose confidence maps everything above reads unchanged."""
+optimiser.  The fitted T then goes to `temperature=` of the class-map entries of mmsa.inference, whose confidence maps everything above reads unchanged.
+
+Top-k evaluation asks at which rank of a top-k map (`topk=` of the class-map entries: uint8 class planes [K, B, H, W]) the label's class stands: `topk_counts` /
+`TopKEvaluator` reduce (class planes, label map) to int64 [C, K + 1] per slot (mmsa_eval_topk_u8, csrc/topk_eval.hip), with the label side of the confusion
+counts verbatim -- column r is the diagonal of the confusion matrix of plane r, column K "not among the K" -- from which `topk_accuracy_of` and
+`topk_recall_of` form the top-1 .. top-K pixel accuracy (the first is the Evaluator's aAcc) and the per-class recall@j in float64 on the host."""
 import ctypes
 import warnings
 from collections import OrderedDict, namedtuple
@@ -1072,4 +1077,122 @@ class TemperatureSweep(_SlotOwner):
                 out["best_" + by] = sweep_best_of(s, self.temperatures, by)[0]
             except ValueError:
                 out["best_" + by] = np.float64(np.nan)
+        return out
+
+
+# ---- top-k evaluation: at which rank of a top-k class map the label's class stands (csrc/topk_eval.hip) ----
+MAX_TOPK = 8            # ranks of a top-k map (csrc/softmax_px.h TOPK_MAX: the rank list of a pixel lives in registers)
+
+
+def check_topk(k, who="mmsa.evaluate"):
+    """`k`, the number of ranks of a top-k map: an int in 1..MAX_TOPK."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= MAX_TOPK:
+        raise ValueError(f"{who}: topk = {k!r}; 1..{MAX_TOPK} ranks are supported")
+    return int(k)
+
+
+def _check_rank_planes(classes):
+    """The class planes of a top-k map: a contiguous uint8 [K, B, H, W] GPU tensor, rank-major (`TopK.classes`)."""
+    if not isinstance(classes, torch.Tensor) or not classes.is_cuda:
+        raise RuntimeError("mmsa.evaluate: classes must be a GPU tensor (there is no CPU path)")
+    if classes.dtype != torch.uint8:
+        raise RuntimeError(f"mmsa.evaluate: classes are {classes.dtype}; uint8 class planes are expected")
+    if classes.dim() != 4 or not classes.is_contiguous():
+        raise RuntimeError(f"mmsa.evaluate: classes must be a contiguous [K, B, H, W] tensor (rank-major), got {tuple(classes.shape)}")
+    if not 1 <= classes.shape[0] <= MAX_TOPK:
+        raise RuntimeError(f"mmsa.evaluate: {classes.shape[0]} rank planes; 1..{MAX_TOPK} are supported")
+    return classes
+
+
+@torch.no_grad()
+def topk_counts(classes, labels, prep, counts=None, slots=None):
+    """ADD the rank counts of the uint8 class planes classes [K, B, H, W] of a top-k map against the raw labels [B, Hl, Wl] into counts[slots[b]] (one
+    launch, mmsa_eval_topk_u8) -> counts, int64 [n_slots, C, K + 1] on the device: a pixel takes part iff its transformed label l is a class (< C), and adds
+    1 at [slot, l, r], r = the first rank whose class equals l, K where none does.  Column r is the diagonal of `confusion(classes[r], ...)`, row l sums to
+    row l of plane 0's matrix.  `slots` defaults to 0 .. B - 1 (per-image counts); `counts` defaults to a zeroed buffer of max(slots) + 1 slots."""
+    classes = _check_rank_planes(classes)
+    K, B, H, W = (int(v) for v in classes.shape)
+    C = prep.num_classes
+    with torch.cuda.device(classes.device):
+        largs = prep.launch_args(labels, B, H, W, classes.device)
+        if counts is None:
+            n_slots = B if slots is None else max(int(s) for s in slots) + 1
+            counts = torch.zeros(n_slots, C, K + 1, dtype=torch.int64, device=classes.device)
+        _check_buffer(counts, "counts", (C, K + 1), classes.device)
+        tab = _slot_args(slots, B, counts.shape[0])
+        lib.call("mmsa_eval_topk_u8", classes.data_ptr(), K, largs[0], B, H, W, largs[1], largs[2], largs[3], C, largs[4], largs[5], tab, counts.shape[0],
+                 counts.data_ptr(), ops._stream())
+    return counts
+
+
+def topk_accuracy_of(counts):
+    """int64 [..., C, K + 1] rank counts -> the top-1 .. top-K pixel accuracies, float64 [..., K]: the cumulative column sums over the participating
+    pixels.  0 / 0 is NaN."""
+    c = np.asarray(counts, dtype=np.int64)
+    hit = np.cumsum(c.sum(-2)[..., :-1], axis=-1).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return hit / np.float64(c.sum((-2, -1)))[..., None]
+
+
+def topk_recall_of(counts):
+    """int64 [..., C, K + 1] rank counts -> the per-class recall@1 .. recall@K, float64 [..., C, K]; NaN for a class without pixels."""
+    c = np.asarray(counts, dtype=np.int64)
+    hit = np.cumsum(c[..., :-1], axis=-1).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return hit / c.sum(-1).astype(np.float64)[..., None]
+
+
+class TopKEvaluator(_SlotOwner):
+    """Owns the rank counts of a top-k evaluation run, as Evaluator owns the confusion counts: int64 [n_slots, C, k + 1] on the device (`.counts`).
+    `cases` / `images` / `device` as in Evaluator.  accuracy()[0] is Evaluator's aAcc of plane 0; mmsa.dist.allreduce_counts(te.counts) is the one collective of
+    a multi-GPU run."""
+    _who, _read, _one, _attr, _pass = "TopKEvaluator", "accuracy()", "a TopKEvaluator", "counts", None
+
+    def __init__(self, prep, k, cases=None, images=MAX_IMAGES, device=None):
+        self.prep = prep
+        self.k = check_topk(k, "mmsa.TopKEvaluator")
+        self._init_slots(cases, images)
+        self._init_buffer(device)
+
+    def _trailing(self):
+        return (self.prep.num_classes, self.k + 1)
+
+    def add(self, classes, labels, case=None, slots=None):
+        """Count the class planes [k, B, H, W] of a batch of top-k maps (one launch)."""
+        classes = _check_rank_planes(classes)
+        if classes.shape[0] != self.k:
+            raise RuntimeError(f"mmsa.TopKEvaluator: {classes.shape[0]} rank planes, this evaluator counts {self.k}")
+        B = int(classes.shape[1])
+        with torch.cuda.device(classes.device):
+            buf = self._buffer(classes.device)
+        topk_counts(classes, labels, self.prep, buf, self.slots_for(B, case, slots))
+        self._taken(B, case, slots)
+        return self
+
+    def host_counts(self):
+        """The counts on the host (the ONE device-to-host copy): int64 numpy [n, C, k + 1], n = images added so far / cases."""
+        return self._host()
+
+    def _of(self, slot):
+        c = self.host_counts()
+        return c.sum(0) if slot is None else c[self._slot_index(slot)]
+
+    def accuracy(self, slot=None):
+        """The top-j pixel accuracy for j = 1 .. k, float64 [k], over every slot or of one slot (index or case name)."""
+        return topk_accuracy_of(self._of(slot))
+
+    def recall(self, slot=None):
+        """The per-class recall@j, float64 [C, k]; NaN for a class without pixels."""
+        return topk_recall_of(self._of(slot))
+
+    def summary(self, slot=None):
+        """OrderedDict top1 .. topk (pixel accuracy) and mRecall1 .. mRecallk (nanmean over the classes), rounded as `Evaluator.summary` rounds."""
+        acc, rec = self.accuracy(slot), self.recall(slot)
+        out = OrderedDict()
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)
+            for j in range(self.k):
+                out[f"top{j + 1}"] = np.round(acc[j] * 100, 2) / 100.0
+            for j in range(self.k):
+                out[f"mRecall{j + 1}"] = np.round(np.nanmean(rec[:, j]) * 100, 2) / 100.0
         return out

@@ -26,6 +26,7 @@ that launch is decided once as well, in `MapOptions`: every entry validates the 
 import ctypes
 import dataclasses
 import functools
+from collections import namedtuple
 
 import torch
 
@@ -302,6 +303,75 @@ def _check_binned(kw, cls, owner, labels, confidence, what, fused=None, return_m
         raise RuntimeError(f"mmsa.{what}: {_NO_CONF_FUSED}")
 
 
+TopK = namedtuple("TopK", "classes probs")      # the top-k map of a call: uint8 / float32 [K, B, Ho, Wo], rank-major (csrc/softmax_px.h); classes[0] IS the class map
+
+_NO_TOPK_ONE_PASS = ("with one_pass=True: there is no one-pass top-k launch at a rescaled or cut size or over augmented views; both are served by the canvas "
+                     "path (mmsa_argmax_topk_nchw on the probabilities; drop one_pass=, or pass one_pass=False)")
+
+
+def _check_topk_buffers(topk, size, device, what):
+    """A TopK of caller buffers must be what the kernels write: contiguous uint8 / float32 [K, B, Ho, Wo] tensors on the map's device, 1 <= K <= MAX_TOPK."""
+    from .evaluate import MAX_TOPK
+    for name, buf, dtype in (("classes", topk.classes, torch.uint8), ("probs", topk.probs, torch.float32)):
+        if not isinstance(buf, torch.Tensor):
+            raise RuntimeError(f"mmsa.{what}: the top-k {name} buffer must be a tensor, got {type(buf).__name__}")
+        if buf.dim() != 4 or tuple(buf.shape[1:]) != tuple(size) or not 1 <= buf.shape[0] <= MAX_TOPK:
+            raise RuntimeError(f"mmsa.{what}: the top-k {name} buffer has shape {tuple(buf.shape)}, the class map is [B, Ho, Wo] = {tuple(size)}: "
+                               f"[K, B, Ho, Wo] with 1 <= K <= {MAX_TOPK} is expected (rank-major)")
+        if buf.dtype != dtype:
+            raise RuntimeError(f"mmsa.{what}: the top-k {name} buffer must be {str(dtype).replace('torch.', '')}, got {buf.dtype}")
+        if device is not None and buf.device != torch.device(device):
+            raise RuntimeError(f"mmsa.{what}: the top-k {name} buffer is on {buf.device}, the class map on {torch.device(device)}")
+        if not buf.is_contiguous():
+            raise RuntimeError(f"mmsa.{what}: the top-k {name} buffer must be contiguous (every rank plane has the class map's layout)")
+    if topk.classes.shape[0] != topk.probs.shape[0] or topk.classes.device != topk.probs.device:
+        raise RuntimeError(f"mmsa.{what}: the top-k buffers disagree: classes {tuple(topk.classes.shape)} on {topk.classes.device}, probs "
+                           f"{tuple(topk.probs.shape)} on {topk.probs.device}")
+    return topk
+
+
+def _topk_option(topk, what, confidence=False, score="max", one_pass=None, aug=False):
+    """`topk=` of an entry, checked before the frame is looked at -> None, the int K, or the TopK of caller buffers (checked against the map by
+    MapOptions.at).  Refuses by name what a top-k map replaces: `confidence=` and `score=`, whose maps are planes of it."""
+    if topk is None:
+        return None
+    if not isinstance(topk, TopK):
+        from .evaluate import check_topk
+        topk = check_topk(topk, f"mmsa.{what}")
+    if not (confidence is None or confidence is False):
+        raise RuntimeError(f"mmsa.{what}: topk= with confidence=: the confidence map is plane 0 of the top-k probabilities; take topk.probs[0]")
+    if score != "max":
+        raise RuntimeError(f"mmsa.{what}: topk= with score={score!r}: the score is written in the confidence map's place, which a top-k map has none of; the "
+                           "top-2 margin is topk.probs[0] - topk.probs[1], the confidence topk.probs[0]; make a second call without topk= for another score")
+    if aug and one_pass:
+        raise RuntimeError(f"mmsa.{what}: topk= {_NO_TOPK_ONE_PASS}")
+    return topk
+
+
+def _check_topk_call(topk, topk_evaluator, labels, calibration, selective, fused, return_map, what):
+    """The per-call half of `topk=`: what has no top-k variant is refused by name, and `topk_evaluator=` needs `labels=` and `topk=`."""
+    if topk_evaluator is not None:
+        from .evaluate import TopKEvaluator
+        if not isinstance(topk_evaluator, TopKEvaluator):
+            raise RuntimeError(f"mmsa.{what}: topk_evaluator= takes an mmsa.evaluate.TopKEvaluator, got {type(topk_evaluator).__name__}")
+        if labels is None:
+            raise RuntimeError(f"mmsa.{what}: topk_evaluator= needs labels= (the raw uint8 label maps the ranks are checked against)")
+        if topk is None:
+            raise RuntimeError(f"mmsa.{what}: topk_evaluator= needs the top-k map: pass topk=K or a TopK of buffers (a SlideRunner: make it with topk=)")
+        K = topk.classes.shape[0] if isinstance(topk, TopK) else topk
+        if K != topk_evaluator.k:
+            raise RuntimeError(f"mmsa.{what}: topk_evaluator= counts {topk_evaluator.k} ranks, topk= gives {K}")
+    if topk is None:
+        return
+    for kw, owner, fn in (("calibration", calibration, "mmsa.calibration"), ("selective", selective, "mmsa.selective")):
+        if owner is not None:
+            raise RuntimeError(f"mmsa.{what}: topk= with {kw}=: the pass reads a confidence map, which a top-k call returns as planes; run "
+                               f"{fn}(topk.classes[r], topk.probs[r], labels, prep) on the planes (rank 0: the map and its confidence)")
+    if fused or not return_map:
+        raise RuntimeError(f"mmsa.{what}: topk= with fused=True / return_map=False: the fused class-map + evaluation launch (mmsa_slide_argmax_eval) has no top-k "
+                           "variant, and the map is plane 0 of the top-k classes; with labels= the counts go through the stored map (drop fused= / return_map=)")
+
+
 def _check_labels(labels, evaluator, *binned):
     """`labels=` feed an evaluator, a calibration, a selective evaluator or several of them; an evaluator needs them."""
     if (labels is None) != (evaluator is None) and not (labels is not None and any(b is not None for b in binned)):
@@ -314,6 +384,8 @@ class MapOptions:
     call, under the calling entry's name `what` (the `mmsa.<what>:` of every refusal), in two steps that own every refusal of the family, in this order:
     `of` -- `score=`, `temperature=`, `calibration=`, `selective=`, all before the frame is looked at; `at` -- once the map's size and device are known and
     before the backbone runs: `confidence=` with fused=True / return_map=False, the confidence buffer (made, or checked), `labels=`.
+    `topk=` / `topk_evaluator=` follow the same two steps: `of` and `with_call` refuse by name what a top-k map replaces or has no variant of, `at` checks or
+    makes the TopK buffers; with `topk=None` neither step does anything it did not do before.
     What depends on the plan (`one_pass=` at frame size, `fused=` / `return_map=` at a rescaled size or without an evaluator) is refused by MapPlan.class_map."""
     conf: object = None          # the float32 [B, Ho, Wo] buffer the launch writes the confidence (or score) map into, or None; before `at`: the entry's `confidence=`
     it: object = None            # the float32 inverse temperature of the `_t` / `_score` launches (mmsa.evaluate.inv_temperature), or None
@@ -326,28 +398,44 @@ class MapOptions:
     fused: object = None
     return_map: bool = True
     one_pass: object = None
+    topk: object = None          # the TopK of uint8 / float32 [K, B, Ho, Wo] buffers the launch writes, or None; before `at`: the entry's `topk=` (None, K or a TopK)
+    topk_evaluator: object = None
 
     @classmethod
-    def of(cls, what, confidence=False, temperature=None, score="max", one_pass=None, aug=False, **per_call):
+    def of(cls, what, confidence=False, temperature=None, score="max", one_pass=None, aug=False, topk=None, **per_call):
         """`aug`: the entries of augmented views, whose one-pass launch has no score sibling.  A SlideRunner makes its record without `per_call` and adds
-        them per frame (`with_call`)."""
+        them per frame (`with_call`).  `topk=` comes first: its refusals name what a top-k map replaces, and without it nothing here changes."""
+        topk = _topk_option(topk, what, confidence, score, one_pass, aug)
         kind = _score_kind(score, confidence, what)
         if aug and kind and one_pass:
             raise RuntimeError(f"mmsa.{what}: score={score!r} {_NO_SCORE_AUG_ONE_PASS}")
-        it = _inv_temperature(temperature, confidence, what)
-        return cls(conf=confidence, it=it, kind=kind, one_pass=one_pass).with_call(what, **per_call)
+        it = _inv_temperature(temperature, confidence if topk is None else True, what)      # the probabilities of a top-k map depend on T as the confidence does
+        return cls(conf=confidence, it=it, kind=kind, one_pass=one_pass, topk=topk).with_call(what, **per_call)
 
-    def with_call(self, what, labels=None, evaluator=None, case=None, calibration=None, selective=None, fused=None, return_map=True):
+    def with_call(self, what, labels=None, evaluator=None, case=None, calibration=None, selective=None, fused=None, return_map=True, topk_evaluator=None):
+        _check_topk_call(self.topk, topk_evaluator, labels, calibration, selective, fused, return_map, what)
         for kw, name, owner in (("calibration", "Calibration", calibration), ("selective", "SelectiveEvaluator", selective)):
             _check_binned(kw, name, owner, labels, self.conf, what, fused, return_map)
         return dataclasses.replace(self, labels=labels, evaluator=evaluator, case=case, calibration=calibration, selective=selective, fused=fused,
-                                   return_map=return_map)
+                                   return_map=return_map, topk_evaluator=topk_evaluator)
 
     def at(self, size, device, what, make=True):
-        """`make=False`: a plan's `conf=`, which is the buffer itself -- True makes none there."""
+        """`make=False`: a plan's `conf=` / `topk=`, which are the buffers themselves -- True / K make none there."""
         conf = _confidence(self.conf, size, device, what, self.fused, self.return_map) if make or self.conf is not True else _check_conf(True, size, device, what)
-        _check_labels(self.labels, self.evaluator, self.calibration, self.selective)
-        return dataclasses.replace(self, conf=conf)
+        topk = self.topk
+        if isinstance(topk, TopK):
+            topk = _check_topk_buffers(topk, size, device, what)
+        elif topk is not None:
+            if not make:
+                raise RuntimeError(f"mmsa.{what}: a plan's topk= is the TopK of buffers itself (classes uint8, probs float32, both [K, B, Ho, Wo]); `out` is its "
+                                   "classes[0]")
+            topk = TopK(torch.empty((topk,) + tuple(size), dtype=torch.uint8, device=device), torch.empty((topk,) + tuple(size), dtype=torch.float32, device=device))
+        _check_labels(self.labels, self.evaluator, self.calibration, self.selective, self.topk_evaluator)
+        return dataclasses.replace(self, conf=conf, topk=topk)
+
+    def map_buffer(self, size, device):
+        """The uint8 [B, Ho, Wo] buffer the map is written into: plane 0 of the top-k classes where there are any (the same storage, no second store)."""
+        return self.topk.classes[0] if self.topk is not None else torch.empty(tuple(size), dtype=torch.uint8, device=device)
 
     def count(self, out):
         """What `labels=` feed, from the stored map `out` (and the confidence next to it): one more launch each -- the confusion counts
@@ -358,6 +446,8 @@ class MapOptions:
             self.calibration.add(out, self.conf, self.labels, case=self.case)
         if self.selective is not None:
             self.selective.add(out, self.conf, self.labels, case=self.case)
+        if self.topk_evaluator is not None:      # the rank counts (mmsa_eval_topk_u8), from the stored planes
+            self.topk_evaluator.add(self.topk.classes, self.labels, case=self.case)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -446,7 +536,13 @@ class MapPlan:
 
     def _launch(self, lg, out, unc, o):
         """The one-pass launch of the plan, mmsa_slide_argmax[_resized], or the sibling that also writes o.conf: `_conf`; `_conf_t` with an inverse temperature
-        o.it; `_score` with o.kind 1 / 2, which always takes an inverse temperature (1.0 without o.it: the untempered softmax, exactly) and 1 / log C."""
+        o.it; `_score` with o.kind 1 / 2, which always takes an inverse temperature (1.0 without o.it: the untempered softmax, exactly) and 1 / log C.
+        With o.topk (frame size only): mmsa_slide_argmax_topk, the K planes in the place of out / conf (`out` is plane 0 of the classes), K and the inverse
+        temperature behind the uncovered-pixel word."""
+        if o.topk is not None:
+            lib.call("mmsa_slide_argmax_topk", *self._args(lg, o.topk.classes, o.topk.probs), unc.data_ptr(), o.topk.classes.shape[0],
+                     1.0 if o.it is None else o.it, ops._stream())
+            return
         if o.conf is None:
             suffix, tail = "", ()
         elif o.kind:
@@ -459,7 +555,7 @@ class MapPlan:
                  ops._stream())
 
     def class_map(self, lg, out, unc, labels=None, evaluator=None, case=None, fused=None, return_map=True, one_pass=None, conf=None, calibration=None,
-                  selective=None, temperature=None, score="max"):
+                  selective=None, temperature=None, score="max", topk=None, topk_evaluator=None):
         """The class-map launch of the three class-map calls, from the head-resolution logits lg [n, C, hs, ws] into out uint8 [B, Ho, Wo] and the
         uncovered-pixel word `unc`.  Without `labels`: mmsa_slide_argmax.  With `labels` (raw uint8 label maps [B, Hl, Wl]) and `evaluator`
         (mmsa.evaluate.Evaluator): the confusion counts of the map are ADDED to the evaluator's buffer as well -- by the same launch
@@ -484,10 +580,19 @@ class MapPlan:
         take any of them.  "margin" / "entropy" go to the `_score` launch in the place of the `_conf` one (mmsa_slide_argmax_score /
         mmsa_slide_argmax_resized_score; on the canvas path mmsa_argmax_score_nchw on the probabilities), with `temperature` as above: bit for bit the score of
         probabilities(..., temperature=T).  At a rescaled size `one_pass=None` follows ONE_PASS_SCORE_RESCALE_DEFAULT for them (measured: the canvas path).
-        "max": the launches above, with the arguments above."""
-        o = MapOptions.of("inference", conf, temperature, score, one_pass, labels=labels, evaluator=evaluator, case=case, calibration=calibration,
-                          selective=selective, fused=fused, return_map=return_map)
-        self._class_map(lg, out, unc, o.at((self.B, self.Ho, self.Wo), out.device if conf is not None else None, "inference", make=False))
+        "max": the launches above, with the arguments above.
+        `topk` (a TopK of contiguous buffers, classes uint8 and probs float32 [K, B, Ho, Wo], 1 <= K <= 8; `out` must be its classes[0]): the first K classes
+        of every pixel and their probabilities (csrc/softmax_px.h) are written rank-major -- plane 0 is the map and its confidence, bit for bit -- by
+        mmsa_slide_argmax_topk at the frame's size, and at a rescaled or cut size by the canvas path with mmsa_argmax_topk_nchw(first = the stored map) on its
+        probabilities (`one_pass=True` is refused there: no one-pass launch is built).  `temperature` is accepted with it; `conf`, `score` other than "max",
+        `calibration`, `selective`, `fused=True` and `return_map=False` are refused.  `topk_evaluator` (mmsa.evaluate.TopKEvaluator; needs `labels` and `topk`):
+        the rank counts of the planes are ADDED to its buffer by one more launch (mmsa_eval_topk_u8).  None: the launches above, with the arguments above."""
+        o = MapOptions.of("inference", conf, temperature, score, one_pass, topk=topk, labels=labels, evaluator=evaluator, case=case, calibration=calibration,
+                          selective=selective, fused=fused, return_map=return_map, topk_evaluator=topk_evaluator)
+        o = o.at((self.B, self.Ho, self.Wo), out.device if conf is not None or topk is not None else None, "inference", make=False)
+        if o.topk is not None and (out.data_ptr() != o.topk.classes.data_ptr() or tuple(out.shape) != tuple(o.topk.classes.shape[1:]) or not out.is_contiguous()):
+            raise RuntimeError("mmsa.inference: with topk= the map is plane 0 of the top-k classes: pass out=topk.classes[0]")
+        self._class_map(lg, out, unc, o)
 
     def _class_map(self, lg, out, unc, o):
         """`class_map` for the entries, which have made their MapOptions `o` under their own name: nothing of the family is checked again."""
@@ -497,6 +602,10 @@ class MapPlan:
                                    "a rescaled or cut size: the counts of a rescaled map go through the stored map (drop fused= / return_map=)")
             default = ONE_PASS_SCORE_RESCALE_DEFAULT if o.kind else ONE_PASS_RESCALE_DEFAULT
             one_pass = default["up" if self.Hd * self.Wd > self.H * self.W else "down"] if o.one_pass is None else o.one_pass
+            if o.topk is not None:
+                if o.one_pass:
+                    raise RuntimeError(f"mmsa.inference: topk= {_NO_TOPK_ONE_PASS}")
+                one_pass = False
             fused = False
         else:
             if o.one_pass is not None:
@@ -507,14 +616,14 @@ class MapPlan:
                 raise RuntimeError("mmsa.inference: return_map=False needs the fused launch (two launches go through the stored map); drop fused=False")
             from . import evaluate
             one_pass = True      # fused: never with `conf`; no map wanted: only the fused launch can leave it unwritten
-            fused = o.evaluator is not None and o.conf is None and ((evaluate.FUSED_DEFAULT or not o.return_map) if o.fused is None else o.fused)
+            fused = o.evaluator is not None and o.conf is None and o.topk is None and ((evaluate.FUSED_DEFAULT or not o.return_map) if o.fused is None else o.fused)
         if fused:
             o.evaluator.add_fused(lg, self, out if o.return_map else None, unc, o.labels, case=o.case)
             return
         if one_pass:
             self._launch(lg, out, unc, o)
         else:
-            _rescaled_map_canvas(self, lg, out, unc, o.conf, o.it, o.kind)
+            _rescaled_map_canvas(self, lg, out, unc, o.conf, o.it, o.kind, o.topk)
         o.count(out)
 
 
@@ -532,20 +641,33 @@ def _canvas_logits(plan, lg, unc):
     return _rescaled_logits(canvas, (plan.Hd, plan.Wd) if plan.resized else None)
 
 
-def _rescaled_map_canvas(plan, lg, out, unc, conf=None, it=None, kind=0):
+def _argmax_topk_into(prob, first, topk):
+    """mmsa_argmax_topk_nchw on a canvas of probabilities [B, C, H, W] into the planes of `topk`; `first`: None, or the uint8 [B, H, W] map that names rank 0
+    (it may be topk.classes[0] itself)."""
+    B, C, H, W = prob.shape
+    lib.call("mmsa_argmax_topk_nchw", prob.data_ptr(), None if first is None else first.data_ptr(), topk.classes.data_ptr(), topk.probs.data_ptr(), B, C, H, W,
+             topk.classes.shape[0], ops._stream())
+
+
+def _rescaled_map_canvas(plan, lg, out, unc, conf=None, it=None, kind=0, topk=None):
     """The rescaled class map the long way round: _canvas_logits, argmax, crop -- the launches slide_inference / encode_decode + argmax_map make.  With
     `conf`: also the softmax of the cut logits (what `probabilities` launches) and mmsa_argmax_max_nchw for its maximum.  The MAP stays the argmax of the
     logits, as without `conf` and as in the one-pass kernels: the softmax can round two distinct logits to one probability, and the first class would win.
     `it` (an inverse temperature, with `conf`): the softmax of logits / T (mmsa_softmax_flip_accum_nchw_t).
-    `kind` (1 / 2, with `conf`): mmsa_argmax_score_nchw in the place of mmsa_argmax_max_nchw -- the margin or the entropy score of those probabilities."""
+    `kind` (1 / 2, with `conf`): mmsa_argmax_score_nchw in the place of mmsa_argmax_max_nchw -- the margin or the entropy score of those probabilities.
+    `topk` (a TopK whose classes[0] is `out`, without `conf`): the top-k tail -- the same softmax, then mmsa_argmax_topk_nchw with first = the stored map, in
+    place: rank 0 stays the argmax of the LOGITS."""
     y = _canvas_logits(plan, lg, unc)
     out.copy_(argmax_map(y)[:, :plan.Ho, :plan.Wo])
-    if conf is None:
+    if conf is None and topk is None:
         return
     y = y[:, :, :plan.Ho, :plan.Wo].contiguous()
     prob = torch.empty_like(y)
     _softmax_accum(y, prob, it=it)
-    _argmax_into(prob, torch.empty_like(out), conf, kind)
+    if topk is not None:
+        _argmax_topk_into(prob, out, topk)
+    else:
+        _argmax_into(prob, torch.empty_like(out), conf, kind)
 
 
 def _window_logits(backbone, head, cut, windows, max_batch):
@@ -558,7 +680,7 @@ def _window_logits(backbone, head, cut, windows, max_batch):
 @torch.no_grad()
 def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preprocess=None, labels=None, evaluator=None, case=None, fused=None,
                     return_map=True, render=None, ori_shape=None, one_pass=None, confidence=False, calibration=None, selective=None, temperature=None,
-                    score="max"):
+                    score="max", topk=None, topk_evaluator=None):
     """`simple_test` of a sliding-window frame (ED:191-234 + ED:449,477) -> uint8 class map [B, H, W], without the
     [B, classes, H, W] logits canvas: every window's logits stay at head resolution and ONE kernel (mmsa_slide_argmax) resizes,
     sums the overlapping windows in window order, divides by the count and takes the argmax -- the same additions in the same order
@@ -590,9 +712,19 @@ def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preproc
     the confidence slot holds -- each in [0, 1], higher = more certain, 0 where the map is 255, written by the launch that writes the class map
     (mmsa_slide_argmax_score) or, with `ori_shape=`, by mmsa_argmax_score_nchw on the canvas path's probabilities -- the default there, being the faster of the
     two where measured (ONE_PASS_SCORE_RESCALE_DEFAULT) -- or by mmsa_slide_argmax_resized_score (`one_pass=True`: no canvas in memory); the same bits either way.
-    `temperature=` combines with it; `calibration=` / `selective=` see whatever score was written.  Other than "max" it is refused without `confidence=`."""
-    o = MapOptions.of("slide_class_map", confidence, temperature, score, one_pass, labels=labels, evaluator=evaluator, case=case, calibration=calibration,
-                      selective=selective, fused=fused, return_map=return_map)
+    `temperature=` combines with it; `calibration=` / `selective=` see whatever score was written.  Other than "max" it is refused without `confidence=`.
+    `topk=` K (1 .. 8), or a TopK of two buffers to write into (classes uint8, probs float32, both contiguous [K, B, h, w] on the device: nothing is allocated,
+    so the launch can be captured): the first K classes of every pixel and their probabilities, rank-major -- rank 0 the class the map names, rank r >= 1 the
+    largest remaining probability (the lowest class among equal ones), 255 / 0 from rank C on and where the map is 255 -- written by the launch that writes
+    the class map (mmsa_slide_argmax_topk) or, with `ori_shape=`, by mmsa_argmax_topk_nchw on the canvas path's probabilities (`one_pass=True` is refused:
+    no one-pass launch is built there).  Returned as the LAST element: (map, unc[, picture], topk), where map IS topk.classes[0] (the same storage),
+    topk.probs[0] is the `confidence=True` map and topk.probs[0] - topk.probs[1] the `score="margin"` map, bit for bit; every plane is a map the evaluation
+    passes take.  `temperature=` is accepted with it.  `confidence=`, `score=` other than "max", `calibration=`, `selective=`, `fused=True` and
+    `return_map=False` are refused with it.
+    `topk_evaluator=` (mmsa.evaluate.TopKEvaluator of the same K; needs `labels=` and `topk=`): the rank of the label's class is counted on device by one
+    more launch (mmsa_eval_topk_u8) -- top-k pixel accuracy next to mIoU; `evaluator=` is optional with it."""
+    o = MapOptions.of("slide_class_map", confidence, temperature, score, one_pass, topk=topk, labels=labels, evaluator=evaluator, case=case,
+                      calibration=calibration, selective=selective, fused=fused, return_map=return_map, topk_evaluator=topk_evaluator)
     return _slide_class_map(o, backbone, head, img, crop_size, stride, max_batch, preprocess, render, ori_shape)
 
 
@@ -605,10 +737,12 @@ def _slide_class_map(o, backbone, head, img, crop_size, stride, max_batch=8, pre
     o = o.at((B, plan.Ho, plan.Wo), device, "slide_class_map")
     _pair(backbone, head)
     lg = _window_logits(backbone, head, cut, plan.windows, max_batch)
-    out = torch.empty(B, plan.Ho, plan.Wo, dtype=torch.uint8, device=device)
+    out = o.map_buffer((B, plan.Ho, plan.Wo), device)
     unc = torch.zeros(1, dtype=torch.int32, device=device)
     plan._class_map(lg, out, unc, o)
     r = (out, unc, render(out, src)) if render is not None else ((out if o.return_map else None), unc)   # unc[0] != 0 <=> some pixel is not covered (ED:220); checked by the caller outside a capture
+    if o.topk is not None:
+        return r + (o.topk,)
     return r if o.conf is None else r + (o.conf,)
 
 
@@ -616,7 +750,7 @@ def _slide_class_map(o, backbone, head, img, crop_size, stride, max_batch=8, pre
 @torch.no_grad()
 def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator=None, case=None, fused=None, return_map=True, render=None,
                     ori_shape=None, dim=None, cut_dim=None, rescale=True, one_pass=None, confidence=False, calibration=None, selective=None, temperature=None,
-                    score="max"):
+                    score="max", topk=None, topk_evaluator=None):
     """Whole-image `simple_test`: resize x4 (bilinear, align_corners=False) + argmax fused (ED:90-94,449,477) -> uint8 [B, H, W].
     `preprocess=` (mmsa.preprocess.Preprocess): img is the pair (rgb, aux) of raw frames, normalised (and padded) by one launch.
     `labels=` + `evaluator=` (+ `case=`): as in slide_class_map.
@@ -634,9 +768,11 @@ def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator
     `calibration=`: as in slide_class_map (needs `labels=` and `confidence=`); at a rescaled or cut size the pass reads the map and confidence stored there.
     `selective=`: as in slide_class_map (needs `labels=` and `confidence=`), over the map and confidence stored at the size returned.
     `temperature=`: as in slide_class_map (needs `confidence=`): the confidence of softmax(logits / T) at the size returned.
-    `score=`: as in slide_class_map ("margin" / "entropy" need `confidence=`): the map in the confidence slot is that score, at the size returned."""
-    o = MapOptions.of("whole_class_map", confidence, temperature, score, one_pass, labels=labels, evaluator=evaluator, case=case, calibration=calibration,
-                      selective=selective, fused=fused, return_map=return_map)
+    `score=`: as in slide_class_map ("margin" / "entropy" need `confidence=`): the map in the confidence slot is that score, at the size returned.
+    `topk=` / `topk_evaluator=`: as in slide_class_map; the TopK (planes [K, B, Ho, Wo]) comes as the last element, (map[, picture], topk), at the size
+    returned: mmsa_slide_argmax_topk at the input size, the canvas path + mmsa_argmax_topk_nchw at a rescaled or cut size (`one_pass=True` is refused)."""
+    o = MapOptions.of("whole_class_map", confidence, temperature, score, one_pass, topk=topk, labels=labels, evaluator=evaluator, case=case,
+                      calibration=calibration, selective=selective, fused=fused, return_map=return_map, topk_evaluator=topk_evaluator)
     return _whole_class_map(o, backbone, head, img, preprocess, render, ori_shape, dim, cut_dim, rescale)
 
 
@@ -658,9 +794,11 @@ def _whole_class_map(o, backbone, head, img, preprocess=None, render=None, ori_s
     _pair(backbone, head)
     feats, _ = backbone(img)
     lg = head(feats)
-    out = torch.empty(B, plan.Ho, plan.Wo, dtype=torch.uint8, device=img.device)
+    out = o.map_buffer((B, plan.Ho, plan.Wo), img.device)
     unc = torch.zeros(1, dtype=torch.int32, device=img.device)
     plan._class_map(lg, out, unc, o)
+    if o.topk is not None:
+        return (out, o.topk) if render is None else (out, render(out, src), o.topk)
     if render is not None:
         return (out, render(out, src)) if o.conf is None else (out, render(out, src), o.conf)
     if o.conf is not None:
@@ -729,7 +867,7 @@ def inference(backbone, head, img, test_cfg, rescale=True, preprocess=None, ori_
 @_on_device
 @torch.no_grad()
 def class_map(backbone, head, img, test_cfg, rescale=True, ori_shape=None, preprocess=None, labels=None, evaluator=None, case=None, render=None, one_pass=None,
-              confidence=False, calibration=None, selective=None, temperature=None, score="max"):
+              confidence=False, calibration=None, selective=None, temperature=None, score="max", topk=None, topk_evaluator=None):
     """`simple_test` (ED:471-477) by mode: the dispatch of `inference` (ED:417-447) onto the class-map calls -> uint8 map, bit for bit
     argmax_map(inference(...)) of the same arguments, without a logits canvas: [B, H, W], or at the size `rescale` gives ('slide' / 'whole': `ori_shape`;
     'whole_dim': test_cfg['dim']; 'whole_dim_cut': the crop of the map at `dim`, or at the input size without `rescale`).  What `inference` refuses is
@@ -740,16 +878,18 @@ def class_map(backbone, head, img, test_cfg, rescale=True, ori_shape=None, prepr
     `calibration=` (mmsa.evaluate.Calibration; needs `labels=` and `confidence=`): as in the calls it goes to.
     `selective=` (mmsa.evaluate.SelectiveEvaluator; needs `labels=` and `confidence=`): as in the calls it goes to.
     `temperature=` (T > 0; needs `confidence=`): the confidence of softmax(logits / T), as in the calls it goes to.
-    `score=` ("max" | "margin" | "entropy"; other than "max" needs `confidence=`): what the confidence slot holds, as in the calls it goes to."""
+    `score=` ("max" | "margin" | "entropy"; other than "max" needs `confidence=`): what the confidence slot holds, as in the calls it goes to.
+    `topk=` (K, or a TopK of output buffers) / `topk_evaluator=` (needs `labels=` and `topk=`): the first K classes and their probabilities as rank-major
+    planes, as the last element: (map[, picture], topk) with map = topk.classes[0], as in the calls it goes to."""
     mode = test_cfg["mode"]
-    o = MapOptions.of("class_map", confidence, temperature, score, one_pass, labels=labels, evaluator=evaluator, case=case, calibration=calibration,
-                      selective=selective)
+    o = MapOptions.of("class_map", confidence, temperature, score, one_pass, topk=topk, labels=labels, evaluator=evaluator, case=case, calibration=calibration,
+                      selective=selective, topk_evaluator=topk_evaluator)
     kw = dict(preprocess=preprocess, render=render)
     if mode == "slide":
         r = _slide_class_map(o, backbone, head, img, tuple(test_cfg["crop_size"]), tuple(test_cfg["stride"]), ori_shape=ori_shape if rescale else None, **kw)
         if int(r[1].item()) != 0:
             raise RuntimeError("mmsa.class_map: windows do not cover the image")   # ED:220
-        r = (r[0],) + tuple(r[2:])           # without the uncovered-pixel word: (map[, picture][, conf])
+        r = (r[0],) + tuple(r[2:])           # without the uncovered-pixel word: (map[, picture][, conf | topk])
         return r[0] if len(r) == 1 else r
     if mode == "whole":
         return _whole_class_map(o, backbone, head, img, ori_shape=ori_shape if rescale else None, **kw)
@@ -817,6 +957,27 @@ def argmax_score_map(prob, score="margin"):
     predictive entropy -- on the mean probabilities of augmented views, the usual TTA uncertainty.  Both lie in [0, 1], higher = more certain.  "max" is
     argmax_max_map itself."""
     return _argmax_pair(prob, _score_kind(score, True, "argmax_score_map"))
+
+
+@_on_device
+@torch.no_grad()
+def argmax_topk_map(prob, k, first=None):
+    """The top-k map of a canvas of probabilities [B, C, H, W] (`probabilities` / `aug_inference`) -> TopK(classes uint8 [k, B, H, W], probs float32
+    [k, B, H, W]), rank-major, one launch (mmsa_argmax_topk_nchw): rank 0 is the first maximum -- or, with `first=` (a uint8 [B, H, W] class map of the same
+    logits, e.g. argmax_map's: two logits can round to one probability), the class that map names, 255 / 0 at every rank where it is 255 -- and rank r >= 1
+    the largest remaining probability, the lowest class among equal ones; 255 / 0 from rank C on."""
+    from .evaluate import check_topk
+    k = check_topk(k, "mmsa.argmax_topk_map")
+    _check(prob)
+    prob = prob.contiguous()
+    B, C, H, W = prob.shape
+    if first is not None:
+        if (not isinstance(first, torch.Tensor) or first.dtype != torch.uint8 or tuple(first.shape) != (B, H, W) or first.device != prob.device
+                or not first.is_contiguous()):
+            raise RuntimeError(f"mmsa.argmax_topk_map: first= must be a contiguous uint8 [B, H, W] = {(B, H, W)} class map on {prob.device}")
+    topk = TopK(torch.empty(k, B, H, W, dtype=torch.uint8, device=prob.device), torch.empty(k, B, H, W, dtype=torch.float32, device=prob.device))
+    _argmax_topk_into(prob, first, topk)
+    return topk
 
 
 # ---- test-time augmentation: EncoderDecoder.aug_test (ED:509-546) -- several views of a frame (flipped, at several scales), whose probabilities are averaged
@@ -993,16 +1154,21 @@ class AugPlan:
             _softmax_accum(y, acc, f, accumulate=a > 0, finish_div=self.A if a == self.A - 1 else 0)
         return acc
 
-    def class_map(self, lgs, out, unc, one_pass=None, conf=None, score="max"):
+    def class_map(self, lgs, out, unc, one_pass=None, conf=None, score="max", topk=None):
         """The class map of the views' head-resolution logits `lgs` (one [n_a, C, hs_a, ws_a] per view) into out uint8 [B, Ho, Wo] and the uncovered-pixel
         word `unc`: ONE launch (mmsa_aug_argmax; no host sync, no allocation once the table is on the device) where `one_pass=True` / ONE_PASS_AUG_DEFAULT
         say so and the classes fit the kernel (at most MAX_AUG_CLASSES), else the canvas path + argmax_map.  The same map bit for bit.
         `conf` (a contiguous float32 [B, Ho, Wo] tensor on the map's device): the confidence map max_c of the mean probabilities is written too, by
         mmsa_aug_argmax_conf or, on the canvas path, by mmsa_argmax_max_nchw in place of mmsa_argmax_nchw: bit for bit mean_probabilities(...).max(1).
         `score` ("margin" / "entropy", with `conf`): the top-2 margin or the entropy score of the MEAN probabilities goes to `conf` instead, by
-        mmsa_argmax_score_nchw on the canvas path, whatever ONE_PASS_AUG_DEFAULT says; `one_pass=True` is refused (mmsa_aug_argmax_conf has no sibling)."""
-        o = MapOptions.of("inference", conf, None, score, one_pass, aug=True)
-        self._class_map(lgs, out, unc, o.at(self.size, out.device if conf is not None else None, "inference", make=False))
+        mmsa_argmax_score_nchw on the canvas path, whatever ONE_PASS_AUG_DEFAULT says; `one_pass=True` is refused (mmsa_aug_argmax_conf has no sibling).
+        `topk` (a TopK of buffers [K, B, Ho, Wo] whose classes[0] is `out`; without `conf`): the top-k map of the MEAN probabilities, by mmsa_argmax_topk_nchw
+        (first = NULL: rank 0 is their first maximum, the map above) on the canvas path, whatever ONE_PASS_AUG_DEFAULT says; `one_pass=True` is refused."""
+        o = MapOptions.of("inference", conf, None, score, one_pass, aug=True, topk=topk)
+        o = o.at(self.size, out.device if conf is not None or topk is not None else None, "inference", make=False)
+        if o.topk is not None and (out.data_ptr() != o.topk.classes.data_ptr() or tuple(out.shape) != tuple(o.topk.classes.shape[1:]) or not out.is_contiguous()):
+            raise RuntimeError("mmsa.inference: with topk= the map is plane 0 of the top-k classes: pass out=topk.classes[0]")
+        self._class_map(lgs, out, unc, o)
 
     def _class_map(self, lgs, out, unc, o):
         """`class_map` for aug_class_map, which has made its MapOptions `o` under its own name."""
@@ -1010,7 +1176,9 @@ class AugPlan:
         if len(lgs) != self.A or any(lg.shape[0] != p.n for lg, p in zip(lgs, self.plans)):
             raise RuntimeError("mmsa.inference: AugPlan.class_map takes one logits tensor per view, one row per window of that view")
         C = int(lgs[0].shape[1])
-        if not o.kind and ((ONE_PASS_AUG_DEFAULT and C <= MAX_AUG_CLASSES) if o.one_pass is None else o.one_pass):
+        if o.topk is not None:      # plane 0 of the classes is `out`
+            _argmax_topk_into(self.mean_probabilities(lgs, unc), None, o.topk)
+        elif not o.kind and ((ONE_PASS_AUG_DEFAULT and C <= MAX_AUG_CLASSES) if o.one_pass is None else o.one_pass):
             lgs = [lg.contiguous() for lg in lgs]
             ptrs = (ctypes.c_void_p * self.A)(*[lg.data_ptr() for lg in lgs])
             rows = (ctypes.c_int * (11 * self.A))(*[v for r in self.rows(lgs) for v in r])
@@ -1070,7 +1238,7 @@ def aug_inference(backbone, head, imgs, test_cfg, ori_shape=None, flips=None, pr
 @_on_views_device
 @torch.no_grad()
 def aug_class_map(backbone, head, imgs, test_cfg, ori_shape=None, flips=None, preprocess=None, max_batch=8, labels=None, evaluator=None, case=None,
-                  one_pass=None, confidence=False, calibration=None, selective=None, score="max"):
+                  one_pass=None, confidence=False, calibration=None, selective=None, score="max", topk=None, topk_evaluator=None):
     """`aug_test` (ED:509-546) -> (uint8 class map [B, Ho, Wo], uncovered-pixel word), bit for bit argmax_map(aug_inference(...)) of the same arguments.
     Every view goes through backbone and head (`max_batch` windows per call, per view); then ONE launch (mmsa_aug_argmax) resizes every view's
     head-resolution logits as `class_map` would, takes the softmax, un-flips, averages over the views and takes the argmax, with no logits or probability
@@ -1085,9 +1253,13 @@ def aug_class_map(backbone, head, imgs, test_cfg, ori_shape=None, flips=None, pr
     `selective=` (mmsa.evaluate.SelectiveEvaluator; needs `labels=` and `confidence=`): the averaged map's confusion counts per confidence bin, likewise.
     `score=` "max" | "margin" | "entropy" (other than "max" needs `confidence=`): the map in the confidence slot is the top-2 margin or the entropy score
     1 - H / log C of the MEAN probabilities -- the usual TTA uncertainty -- bit for bit argmax_score_map(aug_inference(...), score)[1].  Those two go through
-    the canvas path (mmsa_argmax_score_nchw), whatever the default; with `one_pass=True` they are refused: mmsa_aug_argmax_conf has no score sibling."""
-    o = MapOptions.of("aug_class_map", confidence, None, score, one_pass, aug=True, labels=labels, evaluator=evaluator, case=case, calibration=calibration,
-                      selective=selective)
+    the canvas path (mmsa_argmax_score_nchw), whatever the default; with `one_pass=True` they are refused: mmsa_aug_argmax_conf has no score sibling.
+    `topk=` K (1 .. 8) or a TopK of output buffers (uint8 / float32 [K, B, Ho, Wo]): the first K classes of the MEAN probabilities and their values, rank-major,
+    bit for bit argmax_topk_map(aug_inference(...), K), as the last element: (map, unc, topk) with map = topk.classes[0].  It goes through the canvas path
+    (mmsa_argmax_topk_nchw), whatever the default; `one_pass=True`, `confidence=`, `score=` other than "max", `calibration=` and `selective=` are refused
+    with it.  `topk_evaluator=` (mmsa.evaluate.TopKEvaluator; needs `labels=` and `topk=`): the rank counts of the planes, by one more launch."""
+    o = MapOptions.of("aug_class_map", confidence, None, score, one_pass, aug=True, topk=topk, labels=labels, evaluator=evaluator, case=case,
+                      calibration=calibration, selective=selective, topk_evaluator=topk_evaluator)
     imgs, flips, pre = AugPlan.views(imgs, flips, preprocess, "aug_class_map")
     frames = [_intake(img, p, "aug_class_map") for img, p in zip(imgs, pre)]
     plan = AugPlan.of(test_cfg, [f[:3] for f in frames], flips, ori_shape)
@@ -1100,10 +1272,12 @@ def aug_class_map(backbone, head, imgs, test_cfg, ori_shape=None, flips=None, pr
             lgs.append(_window_logits(backbone, head, cut, mp.windows, max_batch))
         else:
             lgs.append(head(backbone(p(*frame) if p is not None else frame)[0]))
-    out = torch.empty(plan.size, dtype=torch.uint8, device=device)
+    out = o.map_buffer(plan.size, device)
     unc = torch.zeros(1, dtype=torch.int32, device=device)
     plan._class_map(lgs, out, unc, o)
     o.count(out)
+    if o.topk is not None:
+        return out, unc, o.topk
     return (out, unc) if o.conf is None else (out, unc, o.conf)
 
 
@@ -1136,6 +1310,14 @@ class FrameResult:
         self._replay._owner._verify(self._replay.seq)
         return self._runner.conf
 
+    def topk(self):
+        """The frame's top-k map, TopK(classes uint8 [K, B, H, W], probs float32 [K, B, H, W]), of a runner made with topk= -- verified, exactly as outputs()
+        is.  The runner's static buffers (classes[0] is the map of outputs()): read them before the next run()."""
+        if self._runner.topk is None:
+            raise RuntimeError("mmsa.FrameResult.topk: the SlideRunner was made without topk=")
+        self._replay._owner._verify(self._replay.seq)
+        return self._runner.topk
+
     @property
     def unverified(self):
         return (self._runner.out if self._has_map else None), self._runner.unc
@@ -1156,12 +1338,15 @@ class SlideRunner:
     With `temperature=` (T > 0; needs confidence=True) that confidence is the one of softmax(logits / T) (slide_class_map's `temperature=`).  It belongs to the
     runner and not to run(): the scalar is an argument of the launch, and a captured launch keeps the one it was captured with.
     With `score=` "margin" / "entropy" (needs confidence=True) the static buffer FrameResult.confidence() returns holds that score instead (slide_class_map's
-    `score=`), by the `_score` sibling of the class-map launch; it belongs to the runner for the same reason."""
+    `score=`), by the `_score` sibling of the class-map launch; it belongs to the runner for the same reason.
+    With `topk=` K (or a TopK of buffers, which become the runner's) every run() also writes the frame's top-k map (slide_class_map's `topk=`) into static
+    uint8 / float32 [K, B, h, w] buffers: FrameResult.topk(); the static `out` buffer is plane 0 of its classes.  `temperature=` is accepted with it; such a
+    runner refuses `confidence=`, `score=` other than "max", run(fused=True), run(return_map=False), run(calibration=) and run(selective=)."""
 
     def __init__(self, backbone, head, frame, crop_size, stride, chains=2, check_every=1, preprocess=None, render=None, ori_shape=None, one_pass=None,
-                 confidence=False, temperature=None, score="max"):
+                 confidence=False, temperature=None, score="max", topk=None):
         from .chains import Chains
-        o = MapOptions.of("SlideRunner", confidence, temperature, score, one_pass)
+        o = MapOptions.of("SlideRunner", confidence, temperature, score, one_pass, topk=topk)
         self.preprocess, self.render, self.one_pass, self.temperature, self.score = preprocess, render, one_pass, temperature, score
         B, H, W, self.device, self.frame, self._cut = _intake(frame, preprocess, "SlideRunner")
         self.plan = plan = MapPlan.slide(B, H, W, tuple(crop_size), stride, ori_shape, what="SlideRunner")
@@ -1174,17 +1359,18 @@ class SlideRunner:
         with torch.cuda.device(self.device):
             self.crops = self._cut(plan.windows)          # also the static input buffer of the chains
             self.chains = Chains(backbone, head, n=chains, check_every=check_every).capture(self.crops)
-            self.out = torch.empty(B, plan.Ho, plan.Wo, dtype=torch.uint8, device=self.device)
+            self.topk = o.at((B, plan.Ho, plan.Wo), self.device, "SlideRunner").topk if o.topk is not None else None
+            self.out = self.topk.classes[0] if self.topk is not None else torch.empty(B, plan.Ho, plan.Wo, dtype=torch.uint8, device=self.device)
             self.unc = torch.zeros(1, dtype=torch.int32, device=self.device)
             self.conf = torch.empty(B, plan.Ho, plan.Wo, dtype=torch.float32, device=self.device) if confidence else None
-            self.options = dataclasses.replace(o, conf=self.conf)      # the runner's half of the family: the scalars a captured launch keeps; run() adds the frame's
+            self.options = dataclasses.replace(o, conf=self.conf, topk=self.topk)      # the runner's half of the family: the scalars a captured launch keeps; run() adds the frame's
             self.pic = None
             if render is not None:
                 render.palette_on(self.device)
                 self.pic = torch.empty(B, plan.Ho, plan.Wo, 3, dtype=torch.uint8, device=self.device)
 
     @torch.no_grad()
-    def run(self, frame=None, labels=None, evaluator=None, case=None, fused=None, return_map=True, calibration=None, selective=None):
+    def run(self, frame=None, labels=None, evaluator=None, case=None, fused=None, return_map=True, calibration=None, selective=None, topk_evaluator=None):
         """Enqueue one frame on the current stream (asynchronous) -> FrameResult; `.outputs()` = (class map uint8 [B, H, W], uncovered-pixel flag) once the
         attention logit guard of this pass has been inspected.  The inspection costs one 4 * depth-byte copy per `check_every` frames and an event wait,
         no device sync; a frame that scored logits beyond the fp16 range raises mmsa.chains.AttentionRangeError from outputs() -- or from the next run(),
@@ -1195,8 +1381,10 @@ class SlideRunner:
         `calibration=` (mmsa.evaluate.Calibration, best one made with cases=[...] and device=; a runner made with confidence=True; needs `labels=`): the
         frame's reliability bins are ADDED to it on device by one more launch; a frame that has to be run again has been binned, as it has been counted.
         `selective=` (mmsa.evaluate.SelectiveEvaluator, made the same way; needs `labels=` and a runner made with confidence=True): the frame's confusion
-        counts per confidence bin are ADDED to it on device by one more launch, under the same terms."""
-        o = self.options.with_call("SlideRunner.run", labels, evaluator, case, calibration, selective, fused, return_map)
+        counts per confidence bin are ADDED to it on device by one more launch, under the same terms.
+        `topk_evaluator=` (mmsa.evaluate.TopKEvaluator of the runner's K, made the same way; needs `labels=` and a runner made with topk=): the rank counts of
+        the frame's top-k planes are ADDED to it on device by one more launch, under the same terms."""
+        o = self.options.with_call("SlideRunner.run", labels, evaluator, case, calibration, selective, fused, return_map, topk_evaluator)
         o = o.at(self.out.shape, self.device, "SlideRunner.run")
         if frame is None:
             frame = self.frame
