@@ -110,7 +110,14 @@ int mmsa_ms_deform_attn_forward(const void* value, const int64_t* spatial_shapes
  * ms_deform_im2col_cuda.cuh:301-920).  grad_output [N,Lq,M*D]; grad_value / grad_sampling_loc / grad_attn_weight have the
  * shapes of value / sampling_loc / attn_weight and are caller-allocated; the call zero-fills and then fully writes them on
  * `stream` (the reference returns freshly allocated zeros-initialised tensors, :121-123).  grad_value is a scatter of
- * floating-point atomic adds like the reference's, so its last bits depend on the arrival order. */
+ * floating-point atomic adds like the reference's, so its last bits depend on the arrival order.
+ * f16: 16-bit float atomics work on aligned pairs, so grad_value must be 4-byte aligned, and so must grad_sampling_loc and
+ * grad_attn_weight when `channels` is not a power of two <= 64 (they are then summed with atomics too); the call refuses
+ * anything else.  The call changes no byte outside the three buffers.  One 32-bit word can reach past one: when a buffer
+ * that is summed with atomics has an ODD element count (batch = 1 with odd S*M*D, or odd Lq*M*L*P), its last element shares
+ * an aligned word with the half word behind the buffer.  That word is read and rewritten by compare-and-swap with the
+ * neighbouring half word's own bits, so its value never changes (a -0.0 stays -0.0, a NaN keeps its payload); it must be
+ * readable and writable memory, which it is inside any allocation, whose sizes are multiples of 4 bytes. */
 int mmsa_ms_deform_attn_backward(const void* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
                                  const void* sampling_loc, const void* attn_weight, const void* grad_output,
                                  void* grad_value, void* grad_sampling_loc, void* grad_attn_weight, int batch,

@@ -269,14 +269,29 @@ __global__ __launch_bounds__(256) void msda_scalar_kernel(
 // One lane per (b, q, m, c): the lanes of a (q, m) pair hold the channel partials of the two per-sample gradients; when D is a
 // power of two <= 64 they are summed with xor-shuffles inside the lane group and written once (no atomics, deterministic, where
 // the reference block-reduces through shared memory); any other D adds the partials with float atomics into zeroed outputs.
-__device__ __forceinline__ void msda_atomic_add(float* p, float v) { atomicAdd(p, v); }
-__device__ __forceinline__ void msda_atomic_add(double* p, double v) { atomicAdd(p, v); }
-__device__ __forceinline__ void msda_atomic_add(__half* p, float v) {
-  // 16-bit float atomics are packed pairs on gfx950 (global_atomic_pk_add_f16): add (v, 0) or (0, v) to the aligned pair
-  const uintptr_t a = (uintptr_t)p;
-  __half2* p2 = reinterpret_cast<__half2*>(a & ~(uintptr_t)3);
-  const __half hv = __float2half(v), z = __float2half(0.f);
-  unsafeAtomicAdd(p2, (a & 2) ? __halves2half2(z, hv) : __halves2half2(hv, z));
+
+// msda_atomic_add: base[i] += v, atomically, for a buffer of n elements
+__device__ __forceinline__ void msda_atomic_add(float* base, long i, long, float v) { atomicAdd(base + i, v); }
+__device__ __forceinline__ void msda_atomic_add(double* base, long i, long, double v) { atomicAdd(base + i, v); }
+__device__ __forceinline__ void msda_atomic_add(__half* base, long i, long n, float v) {
+  // 16-bit float atomics are packed pairs on gfx950 (global_atomic_pk_add_f16): add (v, 0) or (0, v) to the aligned pair.  `base` is 4-byte aligned
+  // (the launcher checks every buffer that comes here), so the pair of element i is (i & ~1, i | 1) and lies inside the buffer -- except for the last
+  // element of an odd count, whose partner is the half word BEHIND the buffer: a packed add of +0 would turn a -0.0 there into +0.0 and race with a
+  // neighbour's plain stores.  That one element is added with a 32-bit compare-and-swap that writes the neighbour's own bits back unchanged.
+  const __half hv = __float2half(v);
+  if ((n & 1) && i == n - 1) {
+    unsigned* w = reinterpret_cast<unsigned*>(base + i);
+    unsigned seen = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (;;) {
+      const __half s = __hadd(__ushort_as_half((unsigned short)(seen & 0xffffu)), hv);
+      const unsigned old = atomicCAS(w, seen, (seen & 0xffff0000u) | (unsigned)__half_as_ushort(s));
+      if (old == seen) break;
+      seen = old;
+    }
+    return;
+  }
+  const __half z = __float2half(0.f);
+  unsafeAtomicAdd(reinterpret_cast<__half2*>(base + (i & ~1L)), (i & 1) ? __halves2half2(z, hv) : __halves2half2(hv, z));
 }
 
 template <typename T, bool SHFL>
@@ -297,6 +312,7 @@ __global__ __launch_bounds__(256) void msda_bwd_kernel(
   const long lw = pair * L * P;
   const long vstride = (long)M * D;
   const long voff = (long)b * S * vstride + (long)m * D + c;
+  const long nvalue = (long)N * S * vstride, nsamp = (long)N * Lq * M * L * P;   // element counts of grad_value and grad_attn_weight
   const AT g = active ? (AT)gout[idx] : (AT)0;
   for (int l = 0; l < L; ++l) {
     const int H = (int)shapes[2 * l], W = (int)shapes[2 * l + 1];
@@ -317,25 +333,25 @@ __global__ __launch_bounds__(256) void msda_bwd_kernel(
           const long o = lbase + ((long)h_low * W + w_low) * vstride;
           const AT v = (AT)value[o];
           val += hh * hw * v; dh -= hw * v; dw -= hh * v;
-          if (active) msda_atomic_add(gvalue + o, hh * hw * tg);
+          if (active) msda_atomic_add(gvalue, o, nvalue, hh * hw * tg);
         }
         if (h_low >= 0 && w_high <= W - 1) {
           const long o = lbase + ((long)h_low * W + w_high) * vstride;
           const AT v = (AT)value[o];
           val += hh * lwf * v; dh -= lwf * v; dw += hh * v;
-          if (active) msda_atomic_add(gvalue + o, hh * lwf * tg);
+          if (active) msda_atomic_add(gvalue, o, nvalue, hh * lwf * tg);
         }
         if (h_high <= H - 1 && w_low >= 0) {
           const long o = lbase + ((long)h_high * W + w_low) * vstride;
           const AT v = (AT)value[o];
           val += lh * hw * v; dh += hw * v; dw -= lh * v;
-          if (active) msda_atomic_add(gvalue + o, lh * hw * tg);
+          if (active) msda_atomic_add(gvalue, o, nvalue, lh * hw * tg);
         }
         if (h_high <= H - 1 && w_high <= W - 1) {
           const long o = lbase + ((long)h_high * W + w_high) * vstride;
           const AT v = (AT)value[o];
           val += lh * lwf * v; dh += lwf * v; dw += lh * v;
-          if (active) msda_atomic_add(gvalue + o, lh * lwf * tg);
+          if (active) msda_atomic_add(gvalue, o, nvalue, lh * lwf * tg);
         }
         g_w = g * val;
         g_x = (AT)W * dw * tg;
@@ -353,9 +369,9 @@ __global__ __launch_bounds__(256) void msda_bwd_kernel(
           gloc[si * 2 + 1] = (T)g_y;
         }
       } else if (active) {
-        msda_atomic_add(gaw + si, g_w);
-        msda_atomic_add(gloc + si * 2, g_x);
-        msda_atomic_add(gloc + si * 2 + 1, g_y);
+        msda_atomic_add(gaw, si, nsamp, g_w);
+        msda_atomic_add(gloc, si * 2, nsamp * 2, g_x);
+        msda_atomic_add(gloc, si * 2 + 1, nsamp * 2, g_y);
       }
     }
   }
@@ -416,6 +432,7 @@ extern "C" int mmsa_ms_deform_attn_forward(const void* value, const int64_t* spa
 // Drop-in for ms_deform_attn_backward (vision.cpp:15 -> ms_deform_attn_cuda.cu:83-151).  grad_output [N,Lq,M*D]; the three
 // gradients have the shapes of value / sampling_loc / attn_weight and are fully (over)written: the library zero-fills
 // grad_value (and, on the atomics path, the other two) on `stream` first, where the reference allocates zeros (:121-123).
+// f16: the buffers the kernel adds into must be 4-byte aligned; an odd element count is fine (include/mmsa.h says what happens to the half word behind).
 extern "C" int mmsa_ms_deform_attn_backward(const void* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
                                             const void* sampling_loc, const void* attn_weight, const void* grad_output,
                                             void* grad_value, void* grad_sampling_loc, void* grad_attn_weight, int batch,
@@ -428,10 +445,13 @@ extern "C" int mmsa_ms_deform_attn_backward(const void* value, const int64_t* sp
   if (rc) return rc;
   const int step = batch < im2col_step ? batch : im2col_step;
   MMSA_CHECK_ARG(step > 0 && batch % step == 0, "batch(%d) must divide im2col_step(%d)", batch, step);
+  const bool shfl = channels <= 64 && (channels & (channels - 1)) == 0;
+  // every f16 buffer the kernel adds into goes through the packed-pair atomic, which rounds the address down to the aligned pair
   MMSA_CHECK_ARG(dtype != MMSA_DT_F16 || (((uintptr_t)grad_value) & 3) == 0, "ms_deform_attn_backward: f16 grad_value must be 4-byte aligned");
+  MMSA_CHECK_ARG(dtype != MMSA_DT_F16 || shfl || ((((uintptr_t)grad_sampling_loc) | ((uintptr_t)grad_attn_weight)) & 3) == 0,
+                 "ms_deform_attn_backward: f16 grad_sampling_loc / grad_attn_weight must be 4-byte aligned when channels (%d) is not a power of two <= 64", channels);
   const size_t es = msda_elt(dtype);
   const long nsamp = (long)batch * num_query * num_heads * num_levels * num_point;
-  const bool shfl = channels <= 64 && (channels & (channels - 1)) == 0;
   if (hipMemsetAsync(grad_value, 0, (size_t)batch * spatial_size * num_heads * channels * es, stream) != hipSuccess ||
       (!shfl && (hipMemsetAsync(grad_sampling_loc, 0, (size_t)nsamp * 2 * es, stream) != hipSuccess ||
                  hipMemsetAsync(grad_attn_weight, 0, (size_t)nsamp * es, stream) != hipSuccess))) {

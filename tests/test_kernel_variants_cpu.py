@@ -1,8 +1,9 @@
 """Keeps the bound of tests/variant_ref.py honest, on the CPU, for every case of the table in tests/test_kernel_variants_gpu.py: torch's own fp32
 evaluation of the same statement stays inside the bound (the float64 reference and the bound are consistent with plain fp32 arithmetic), and a
 result with ONE border element moved by 8x its bound is rejected (the check is per element, nothing is averaged away).  The MSDA restatement is
-checked once against the oracle's msda_core, and deliberately wrong restatements of LayerNorm and MSDA must land outside the bound: the width of the
-bound is a checked property too."""
+checked once against the oracle's msda_core, the MSDA backward restatement against float64 autograd through the forward restatement and through msda_core,
+and deliberately wrong restatements of LayerNorm and MSDA (forward and backward) must land outside the bound: the width of the bound is a checked
+property too."""
 import pytest
 import torch
 
@@ -65,14 +66,32 @@ def test_msda_restatement_agrees_with_the_oracle(cid):
     assert float((want - r).abs().max()) <= 1e-12 * float(want.abs().max())
 
 
-MUTANTS = {"layernorm_rows": ("mean_drop4", "var_cm1", "eps", "group0"), "msda": ("nohalf", "swap", "start"), "msda_fused": ("nohalf", "swap", "start", "softmaxP")}
+@pytest.mark.parametrize("cid", ["msdab-f32-shfl-m3d8-q33", "msdab-f32-atom-m4d40-q26"])
+def test_msda_backward_restatement_agrees_with_autograd(cid):
+    """The direct statement of the three gradients against float64 autograd through variant_ref._gather (floor-based taps, like the statement) and through
+    oracle.ref_encoder.msda_core (grid_sample based), to 1e-12 relative per gradient."""
+    from oracle.ref_encoder import msda_core
+    _, op, p = next(c for c in CASES if c[0] == cid)
+    i, r, _ = V.case_data(cid, op, p)
+    levels, starts, _ = V.msda_geometry(p)
+    parts = V.msda_bwd_slices(p)
+    for fwd in (lambda v, lo, a: V._gather(v, levels, starts, lo, a)[0], lambda v, lo, a: msda_core(v, torch.tensor(levels), lo, a).view(i["gout"].shape)):
+        v, lo, a = (i[k].double().requires_grad_(True) for k in ("value", "loc", "aw"))
+        (fwd(v, lo, a) * i["gout"].double()).sum().backward()
+        for name, got in (("gvalue", v.grad), ("gloc", lo.grad), ("gaw", a.grad)):
+            assert float((got.reshape(-1) - r[parts[name]]).abs().max()) <= 1e-12 * float(got.abs().max()), name
+
+
+MUTANTS = {"layernorm_rows": ("mean_drop4", "var_cm1", "eps", "group0"), "msda": ("nohalf", "swap", "start"), "msda_fused": ("nohalf", "swap", "start", "softmaxP"),
+           "msda_bwd": ("swapWH", "noaw", "awaw", "dhsign", "start")}
 
 
 @pytest.mark.parametrize("op,mut", [(op, m) for op, ms in MUTANTS.items() for m in ms])
 def test_bound_rejects_wrong_statements(op, mut):
     """A float64 restatement that is wrong in one respect -- LayerNorm: the mean without the row's last four channels, the variance over C - 1, the other
     eps, every group given group 0's weights; MSDA: no -0.5, H and W exchanged in the normalisation, the second level's start index one row too late, the
-    softmax over P instead of L * P -- lands outside the bound in at least one element of at least one case of the family."""
+    softmax over P instead of L * P; MSDA backward: W and H exchanged in the scale of grad_sampling_loc, grad_sampling_loc without the attention weight,
+    grad_attn_weight times the attention weight, the sign of one tap's dh flipped, the second level's start index one row too late -- lands outside the bound in at least one element of at least one case of the family."""
     caught = 0
     for cid, cop, p in CASES:
         if cop != op or p.get("rows", 0) > 1000 or caught >= 3:

@@ -1,4 +1,4 @@
-"""Float64 restatements of the conv / norm / neck / tail / head, LayerNorm-rows, row-statistics and deformable-attention operations and the per-element bound the kernel-variant tests hold the
+"""Float64 restatements of the conv / norm / neck / tail / head, LayerNorm-rows, row-statistics and deformable-attention (forward and backward) operations and the per-element bound the kernel-variant tests hold the
 device to (tests/test_kernel_variants_gpu.py; tests/test_kernel_variants_cpu.py keeps the bound itself honest).
 
 Every `ref_<op>(i, p)` takes the case's inputs `i` (a dict of CPU tensors, all of ONE floating dtype) and its parameters `p` and returns
@@ -44,7 +44,39 @@ Fused weights: exp(logit - max) / sum: the subtraction (u |logit - max| on the e
 product with the reciprocal: relative (L P + 6 + max |logit - max|) u, times S1 -- plus what the runtime's expf adds, which the source cannot tell:
 EXPF_EXCESS below, handled like SIGMOID_EXCESS (measured against float64 on an MI355X, twice the measured value allowed, relative to S1).
 Scalar kernels: f16 computes in fp32 on the fp16 inputs as given and rounds once: the fp32 bound + 2^-11 |r| + 2^-24; f64: the formula with u = 2^-53.
-Planes-only outputs: bnd + FMT_REL |r|."""
+Planes-only outputs: bnd + FMT_REL |r|.
+
+msda_bwd (msda_bwd_kernel<T, SHFL>).  Reference: the three gradients of the gather above, stated directly (the comment above the kernel).  Per sample
+s = (b, q, m, l, p) inside the map, with the fractions lh, lw of its pixel coordinate, hh = 1 - lh, hw = 1 - lw, the four taps k = (dy, dx) with bilinear
+weights c_k = (lh | hh)(lw | hw), tap values v_k (zero outside the map), A_s the attention weight and g_c = grad_output[b, q, m, c]:
+    grad_value[tap k, c]     += c_k A_s g_c                                            over every sample and tap that lands on the element
+    grad_attn_weight[s]       = sum_c g_c sum_k c_k v_k
+    grad_sampling_loc[s, x]   = W_l A_s sum_c g_c sum_k (+-)(lh | hh) v_k              (+ for dx = 1, - for dx = 0; the factor is the tap's row weight)
+    grad_sampling_loc[s, y]   = H_l A_s sum_c g_c sum_k (+-)(lw | hw) v_k              (+ for dy = 1, - for dy = 0; the factor is the tap's column weight)
+A sample outside the map contributes nothing and has gradient zero.  The device forms the pixel coordinate as above (error eps_h, eps_w), then lh by a
+subtraction of the floor (one rounding when the coordinate is negative) and hh = 1 - lh (one more): every one of lh, hh carries at most
+e_h = eps_h + 2 u, every one of lw, hw at most e_w = eps_w + 2 u, absolute, and all four lie in [0, 1].  T_c = the sum of |v_k| over the existing taps of
+channel c, as T_s above.
+    grad_value element e.  n_e = the number of (sample, tap) contributions that land on it, S_e = sum c_k |A_s| |g_c| over them.  An addend is
+        fl(fl(hh hw) fl(g A)): three roundings relative to itself, and the weight c_k moves by at most hw e_h + hh e_w <= e_h + e_w; the n_e addends
+        meet in atomics, n_e - 1 roundings on any path whatever the order (the first lands on the memset zero, exactly); two more u absorb the second-order
+        terms (n_e stays below 2^10):                   bnd = (n_e + 4) u S_e + sum |A_s g_c| (e_h + e_w)
+        An element no sample touches: r = 0, bnd = 0 -- the device must leave the memset zero.
+    grad_attn_weight[s].  Per channel: the weight product and the product with v_k (2 u on each term), three additions over the taps, the product with
+        g_c; then D channels meet (log2 D shuffle steps, or D - 1 atomic additions: D bounds both):
+                                                        bnd = (D + 8) u sum_c |g_c| sum_k c_k |v_k| + sum_c |g_c| (e_h + e_w) T_c
+    grad_sampling_loc[s, x].  Per channel: one product per tap, three additions, the roundings of g A, of W_l dw and of their product; D channels meet;
+        the coefficients (lh | hh) carry e_h:           bnd = (D + 8) u W_l |A_s| sum_c |g_c| sum_k (lh | hh) |v_k| + W_l |A_s| e_h sum_c |g_c| T_c
+        and [s, y] likewise with H_l, (lw | hw) and e_w.  A sample outside the map: r = 0, bnd = 0.
+In the dyadic cases every coordinate, fraction and weight product is exact, so e_h = e_w = 0 there.  f64: the same formulas with u = 2^-53.
+f16: the inputs are the fp16 numbers as given and the arithmetic is fp32, so the fp32 bound b32 holds for what the device has before it stores.
+    shuffle path, grad_sampling_loc and grad_attn_weight: one rounding to fp16:          b32 + 2^-11 |r| + 2^-24   (inside the map; outside r = bnd = 0)
+    atomics path, and grad_value always: every addend is rounded to fp16 and so is every partial sum (global_atomic_pk_add_f16).  With n addends
+    (n_e, or D for a sample inside the map) of magnitude sum S' <= S + b32, n roundings of relative size 2^-11 lie on any path:
+                                                        b32 + ((1 + 2^-11)^n - 1) (S + b32) + n (2^-14 + 2^-24)
+    The last term is the one thing the source cannot tell: whether the packed fp16 atomic keeps subnormal addends and sums or flushes them to zero.
+    It is NOT measured: 2^-14, the smallest normal fp16 number, is the most a flush can cost per addend, and 2^-24 covers the conversion's rounding in the
+    subnormal range when they are kept."""
 import zlib
 
 import torch
@@ -628,6 +660,118 @@ def ref_msda(i, p, mut=None):
     return r, bnd
 
 
+def make_msda_bwd(p, g):
+    """make_msda's value, loc and aw (the same draws) and a grad_output of O(1), [B, Lq, M, D]."""
+    i = make_msda(p, g)
+    gout = torch.randn(p["B"], p["Lq"], p["M"], p["D"], generator=g)
+    i["gout"] = gout.half().float() if p.get("dtype") == "f16" else gout
+    return i
+
+
+def msda_bwd_shfl(p):
+    """The launcher's choice: the xor-shuffle tree when D is a power of two <= 64, atomics into zeroed buffers for any other D."""
+    return p["D"] <= 64 and p["D"] & (p["D"] - 1) == 0
+
+
+def msda_bwd_slices(p):
+    """Where (grad_value [B, S, M, D] | grad_sampling_loc [B, Lq, M, L, P, 2] | grad_attn_weight [B, Lq, M, L, P]) lie in the flat result."""
+    _, _, S = msda_geometry(p)
+    ns = p["B"] * p["Lq"] * p["M"] * len(p["levels"]) * p["P"]
+    nv = p["B"] * S * p["M"] * p["D"]
+    return {"gvalue": slice(0, nv), "gloc": slice(nv, nv + 2 * ns), "gaw": slice(nv + 2 * ns, nv + 3 * ns)}
+
+
+def ref_msda_bwd(i, p, mut=None):
+    """The three gradients, flattened and concatenated (msda_bwd_slices).  `mut`: swapWH (W and H exchanged in the scale of grad_sampling_loc), noaw
+    (grad_sampling_loc without the attention weight), awaw (grad_attn_weight times the attention weight), dhsign (the sign of the first tap's dh
+    flipped), start (the second level's start index one row too late)."""
+    levels, starts, S = msda_geometry(p)
+    value, loc, aw, g = i["value"], i["loc"], i["aw"], i["gout"]
+    if p.get("dtype") == "f64":                              # the device computes this case in double: so does its plain torch statement
+        value, loc, aw, g = value.double(), loc.double(), aw.double(), g.double()
+    dt = value.dtype
+    Bn, M, D, Lq, P, L = p["B"], p["M"], p["D"], p["Lq"], p["P"], len(levels)
+    want = i["_dt"] == torch.float64 and not mut
+    Sx = S
+    if mut == "start":
+        starts = [s + (levels[1][1] if l >= 1 else 0) for l, s in enumerate(starts)]
+        Sx = S + levels[1][1]
+        value = torch.cat([value, value.new_zeros(Bn, levels[1][1], M, D)], 1)
+    vbm = value.permute(0, 2, 1, 3).reshape(Bn * M * Sx, D)                                       # rows (b, m, s)
+    bm = (torch.arange(Bn).view(Bn, 1, 1, 1) * M + torch.arange(M).view(1, 1, M, 1)) * Sx
+    u = _msda_u(p)
+    gv = value.new_zeros(Bn * M * Sx, D)
+    gl = value.new_zeros(Bn, Lq, M, L, P, 2)
+    ga = value.new_zeros(Bn, Lq, M, L, P)
+    n_v, s_v, pos_v = value.new_zeros(Bn * M * Sx), torch.zeros_like(gv), torch.zeros_like(gv)
+    s_l, pos_l, s_a, pos_a = torch.zeros_like(gl), torch.zeros_like(gl), torch.zeros_like(ga), torch.zeros_like(ga)
+    ins = torch.zeros(Bn, Lq, M, L, P, dtype=torch.bool)
+    gq = g[:, :, :, None, :]                                                                      # [B, Lq, M, 1, D]
+    for l, (H, W) in enumerate(levels):
+        x, y = loc[:, :, :, l, :, 0] * W - 0.5, loc[:, :, :, l, :, 1] * H - 0.5                    # [B, Lq, M, P]
+        inside = (y > -1) & (x > -1) & (y < H) & (x < W)
+        ins[:, :, :, l] = inside
+        y0, x0 = torch.floor(y), torch.floor(x)
+        lh, lw = y - y0, x - x0
+        hh, hw = 1 - lh, 1 - lw
+        a = aw[:, :, :, l, :]
+        ag = a[..., None] * gq                                                                    # [B, Lq, M, P, D]
+        if p.get("dyadic"):
+            e_h = e_w = torch.zeros_like(x)
+        else:
+            e_h, e_w = 2 * u * ((loc[:, :, :, l, :, 1] * H).abs() + 0.5) + 2 * u, 2 * u * ((loc[:, :, :, l, :, 0] * W).abs() + 0.5) + 2 * u
+        val, dh, dw = (value.new_zeros(Bn, Lq, M, P, D) for _ in range(3))
+        sval, sdh, sdw, T = (value.new_zeros(Bn, Lq, M, P, D) for _ in range(4))
+        for dy, dx in ((0, 0), (0, 1), (1, 0), (1, 1)):
+            wy, wx = (lh if dy else hh), (lw if dx else hw)
+            cw = wy * wx
+            yy, xx = y0 + dy, x0 + dx
+            ok = inside & (yy >= 0) & (yy <= H - 1) & (xx >= 0) & (xx <= W - 1)
+            okf = ok.to(dt)
+            row = (bm + starts[l] + (yy.clamp(0, H - 1) * W + xx.clamp(0, W - 1)).long()).flatten()
+            v = vbm[row].view(Bn, Lq, M, P, D) * okf[..., None]
+            val = val + cw[..., None] * v
+            dh = dh + (-1 if (dy == 0) != (mut == "dhsign" and (dy, dx) == (0, 0)) else 1) * wx[..., None] * v
+            dw = dw + (1 if dx else -1) * wy[..., None] * v
+            gv.index_add_(0, row, ((cw * okf)[..., None] * ag).reshape(-1, D))
+            if want:
+                n_v.index_add_(0, row, okf.flatten())
+                s_v.index_add_(0, row, ((cw * okf)[..., None] * ag.abs()).reshape(-1, D))
+                pos_v.index_add_(0, row, ((okf * (e_h + e_w))[..., None] * ag.abs()).reshape(-1, D))
+                sval, sdh, sdw, T = sval + cw[..., None] * v.abs(), sdh + wx[..., None] * v.abs(), sdw + wy[..., None] * v.abs(), T + v.abs()
+        ga[:, :, :, l] = (gq * val).sum(-1) * (a if mut == "awaw" else 1)
+        sx, sy = (H, W) if mut == "swapWH" else (W, H)
+        al = 1 if mut == "noaw" else a
+        gl[:, :, :, l, :, 0] = (gq * dw).sum(-1) * al * sx
+        gl[:, :, :, l, :, 1] = (gq * dh).sum(-1) * al * sy
+        if want:
+            gT = (gq.abs() * T).sum(-1)
+            s_a[:, :, :, l], pos_a[:, :, :, l] = (gq.abs() * sval).sum(-1), (e_h + e_w) * gT
+            s_l[:, :, :, l, :, 0], pos_l[:, :, :, l, :, 0] = W * a.abs() * (gq.abs() * sdw).sum(-1), W * a.abs() * e_h * gT
+            s_l[:, :, :, l, :, 1], pos_l[:, :, :, l, :, 1] = H * a.abs() * (gq.abs() * sdh).sum(-1), H * a.abs() * e_w * gT
+
+    def v_layout(t):
+        return t.view(Bn, M, Sx, -1)[:, :, :S].permute(0, 2, 1, 3).expand(Bn, S, M, D).reshape(-1)
+    r = torch.cat([v_layout(gv), gl.reshape(-1), ga.reshape(-1)])
+    if not want:
+        return r, None
+    n_v = v_layout(n_v)
+    b_v = (n_v + 4) * u * v_layout(s_v) + v_layout(pos_v)
+    b_l, b_a = ((D + 8) * u * s + pos for s, pos in ((s_l, pos_l), (s_a, pos_a)))
+    if p.get("dtype") == "f16":
+        h, sub = 2.0 ** -11, 2.0 ** -14 + 2.0 ** -24
+
+        def atomics16(b32, s, n):
+            return b32 + ((1 + h) ** n - 1) * (s + b32) + n * sub
+        b_v = atomics16(b_v, v_layout(s_v), n_v)
+        if msda_bwd_shfl(p):
+            b_l = b_l + h * gl.abs() + 2.0 ** -24 * ins[..., None]
+            b_a = b_a + h * ga.abs() + 2.0 ** -24 * ins
+        else:
+            b_l, b_a = atomics16(b_l, s_l, D * ins[..., None].to(dt)), atomics16(b_a, s_a, D * ins.to(dt))
+    return r, torch.cat([b_v, b_l.reshape(-1), b_a.reshape(-1)])
+
+
 def h8_exact(t, g):
     """(h, h + l / 2048): values the h8 planes hold exactly.  h is an fp16 number (|h| >= 2^-4), l an e5m2 number of h's sign with |l| < 2^e (2^e <= |h|):
     |l / 2048| stays below half an ulp of h, so fp16 rounding returns h and the remainder is l / 2048 exactly; the sum spans 15 bits: exact in fp32."""
@@ -706,7 +850,7 @@ def ref_msda_fused(i, p, mut=None, parts=False):
 
 OPS = {
     "layernorm_rows": (make_layernorm_rows, ref_layernorm_rows), "rowstats": (make_rowstats, ref_rowstats), "msda": (make_msda, ref_msda),
-    "msda_fused": (make_msda_fused, ref_msda_fused),
+    "msda_fused": (make_msda_fused, ref_msda_fused), "msda_bwd": (make_msda_bwd, ref_msda_bwd),
     "dwconv": (make_dwconv, ref_dwconv), "gconv": (make_gconv, ref_gconv), "gfe_qkv": (make_gfe_qkv, ref_gfe_qkv),
     "dwpair_gate": (make_dwpair_gate, ref_dwpair_gate), "ca_apply": (make_ca_apply, ref_ca_apply), "gelu_gate": (make_gelu_gate, ref_gelu_gate),
     "pool_hw": (make_pool_hw, ref_pool_hw), "colstats": (make_colstats, ref_colstats), "ffrm": (make_ffrm, ref_ffrm), "lnhw": (make_lnhw, ref_lnhw),
