@@ -565,6 +565,21 @@ int mmsa_argmax_topk_nchw(const float* prob, const unsigned char* first, unsigne
 int mmsa_eval_topk_u8(const unsigned char* classes, int K, const unsigned char* label, int B, int H, int W, int Hl, int Wl, const unsigned char* lut, int C,
                       const int* ymap, const int* xmap, const int* slots, int n_slots, int64_t* counts, mmsa_stream_t stream);
 
+/* --- boundary evaluation (csrc/boundary.hip): the confusion counts of a stored uint8 class map pred [B, H, W] against a label map, split into four zones by
+ *     whether the pixel lies near a boundary of the label map and near a boundary of the prediction -- the integers the trimap accuracy / mIoU and the Boundary
+ *     IoU are formed from.  The label side -- lut, ymap / xmap (both or neither, clamped into the label map), slots (HOST int [B]) -- is
+ *     mmsa_eval_confusion_u8's.  For a pixel p of the prediction grid: the label code L(p) = lut[label[ymap[y], xmap[x]]] normalised to a class < C, C (kept
+ *     but out of range: any LUT value in [C, 254]) or 255 (ignored); the prediction code P(p) = min(pred[p], C).  near_label(p) iff some pixel q OF THE IMAGE at
+ *     Chebyshev distance max(|dy|, |dx|) <= radius from p has L(q) != L(p) (an ignored label is a code like any other as a neighbour); near_pred(p) the same
+ *     for P.  border = 0: neighbours outside the image do not exist; border = 1: a pixel with y < radius, x < radius, y >= H - radius or x >= W - radius is near
+ *     a boundary on both sides (the zero-padded erosion).
+ *     counts int64 [n_slots, 4, C + 1, C + 1], ADDED to (the caller zeroes it): every pixel whose own L is not 255 adds 1 at
+ *     [slot, 2 * near_label + near_pred, min(L, C), P].  The sum over the four zones is mmsa_eval_confusion_u8's matrix, bit for bit.  One launch; integer sums:
+ *     the same bytes whatever the order of arrival.  1 <= radius <= 32 (a radius larger than the image is legal: every window is then the whole image),
+ *     2 <= C <= 82 (one zone's histogram must fit a workgroup's LDS next to the tiles of radius 32), 1 <= B <= 64. --- */
+int mmsa_eval_boundary_u8(const unsigned char* pred, const unsigned char* label, int B, int H, int W, int Hl, int Wl, const unsigned char* lut, int C,
+                          const int* ymap, const int* xmap, const int* slots, int n_slots, int radius, int border, int64_t* counts, mmsa_stream_t stream);
+
 /* --- the picture of a prediction (segmentation/mmseg_custom/apis/test_bs.py:257-349, the `--show` / `--show-dir` output): `tensor2imgs` (test_bs.py:18-63) on
  *     planes 0..2 of the input tensor -> the crop `img[:h, :w]` (test_bs.py:275-276) -> `show_result` (tools/color_gt_according_palette.py:23-81:
  *     color_seg[seg == label] = color, channels reversed, img * (1 - opacity) + color_seg * opacity, .astype(uint8)), in one pass.

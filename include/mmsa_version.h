@@ -19,7 +19,9 @@
  *      confidence's place).  No existing entry changed its arguments or their meaning, and a library without the new symbols fails the binding's symbol lookup
  *      (mmsa/lib.py) before the number is read, so the number that tests/test_temperature_cpu.py pins stays.
  *      Still 114, for the same reason: new entries mmsa_slide_argmax_topk / mmsa_argmax_topk_nchw / mmsa_eval_topk_u8 (the first K classes of every pixel and
- *      their probabilities as rank-major planes, and the rank of the label's class counted per class). */
+ *      their probabilities as rank-major planes, and the rank of the label's class counted per class).
+ *      Still 114, for the same reason: new entry mmsa_eval_boundary_u8 (the confusion counts of a class map split by whether the pixel lies within a Chebyshev
+ *      radius of a label boundary and of a prediction boundary: trimap metrics and Boundary IoU). */
 #ifndef MMSA_VERSION_H
 #define MMSA_VERSION_H
 #define MMSA_ABI_VERSION 114

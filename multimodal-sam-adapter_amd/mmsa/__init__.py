@@ -20,6 +20,7 @@ from .evaluate import Calibration, calibration  # noqa: F401  (reliability bins,
 from .evaluate import SelectiveEvaluator, selective, abstain  # noqa: F401  (confusion counts per confidence bin: mIoU against coverage; the thresholded map)
 from .evaluate import TemperatureSweep, temperature_sweep  # noqa: F401  (temperature scaling: NLL and reliability bins of a logits canvas over a grid of T)
 from .evaluate import TopKEvaluator, topk_counts  # noqa: F401  (the rank of the label's class in a top-k map: top-k pixel accuracy and recall@k)
+from .evaluate import BoundaryEvaluator, boundary_counts, boundary_zone_sum_of, trimap_counts_of, boundary_iou_of  # noqa: F401  (confusion counts by nearness to a label / prediction boundary: trimap metrics and Boundary IoU)
 from . import render  # noqa: F401  (the picture of a prediction on device: palette map over the frame, show_result)
 from .render import Renderer
 from .registry import BACKBONES, HEADS, build_backbone, build_head
@@ -46,4 +47,4 @@ __all__ = ["SegformerHead", "HEADS", "build_head", "register_head", "SAMAdapterb
            "BACKBONES", "build_backbone", "ops", "lib", "inference", "Chains", "Replay", "AttentionRangeError", "OperandRangeError",
            "preprocess", "Preprocess", "FrameFeeder", "evaluate", "Evaluator", "LabelPrep", "confusion", "Calibration", "calibration", "SelectiveEvaluator", "selective", "abstain", "TemperatureSweep", "temperature_sweep", "render", "Renderer",
            "probabilities", "aug_inference", "aug_class_map", "AugPlan", "argmax_max_map", "argmax_score_map", "TopK", "argmax_topk_map",
-           "TopKEvaluator", "topk_counts"]
+           "TopKEvaluator", "topk_counts", "BoundaryEvaluator", "boundary_counts", "boundary_zone_sum_of", "trimap_counts_of", "boundary_iou_of"]

@@ -32,7 +32,12 @@ optimiser.  The fitted T then goes to `temperature=` of the class-map entries of
 Top-k evaluation asks at which rank of a top-k map (`topk=` of the class-map entries: uint8 class planes [K, B, H, W]) the label's class stands: `topk_counts` /
 `TopKEvaluator` reduce (class planes, label map) to int64 [C, K + 1] per slot (mmsa_eval_topk_u8, csrc/topk_eval.hip), with the label side of the confusion
 counts verbatim -- column r is the diagonal of the confusion matrix of plane r, column K "not among the K" -- from which `topk_accuracy_of` and
-`topk_recall_of` form the top-1 .. top-K pixel accuracy (the first is the Evaluator's aAcc) and the per-class recall@j in float64 on the host."""
+`topk_recall_of` form the top-1 .. top-K pixel accuracy (the first is the Evaluator's aAcc) and the per-class recall@j in float64 on the host.
+
+Boundary evaluation asks how good the contours are: `boundary_counts` / `BoundaryEvaluator` reduce (class map, label map) to int64 [4, C + 1, C + 1] per slot
+(mmsa_eval_boundary_u8, csrc/boundary.hip) -- the confusion matrix split into the zones 2 * near_label + near_pred, "near" = within a Chebyshev radius of a pixel
+with another code -- whose zone sum is the Evaluator's matrix; `trimap_counts_of` (zones 2 + 3: the band around the label boundaries, fed to `areas_of` /
+`area_metrics`) and `boundary_iou_of` (Cheng et al., CVPR 2021) form the trimap metrics and the Boundary IoU in float64 on the host."""
 import ctypes
 import warnings
 from collections import OrderedDict, namedtuple
@@ -1196,3 +1201,161 @@ class TopKEvaluator(_SlotOwner):
             for j in range(self.k):
                 out[f"mRecall{j + 1}"] = np.round(np.nanmean(rec[:, j]) * 100, 2) / 100.0
         return out
+
+
+# ---- boundary evaluation: the confusion counts split by nearness to a label boundary and to a prediction boundary (csrc/boundary.hip) ----
+MAX_BOUNDARY_RADIUS = 32      # csrc/boundary.hip BOUNDARY_MAX_RADIUS: the usual trimap widths, and 0.5 % - 2 % of the diagonal up to 1024 x 1024
+MAX_BOUNDARY_CLASSES = 82     # csrc/boundary.hip BOUNDARY_MAX_CLASSES: one zone's (C + 1)^2 uint32 histogram next to the tiles of radius 32 in 64 KiB of LDS
+_BOUNDARY_TILE_W = 64
+_BOUNDARY_LDS = 65536
+
+
+def check_boundary_radius(radius, who="mmsa.evaluate"):
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= MAX_BOUNDARY_RADIUS:
+        raise ValueError(f"{who}: radius = {radius!r}; 1..{MAX_BOUNDARY_RADIUS} pixels (Chebyshev) are supported")
+    return int(radius)
+
+
+def _check_boundary_classes(C, who="mmsa.evaluate"):
+    if C > MAX_BOUNDARY_CLASSES:
+        raise RuntimeError(f"{who}: {C} classes; boundary evaluation supports 2..{MAX_BOUNDARY_CLASSES} (one zone's (C + 1)^2 uint32 histogram must fit a "
+                           f"workgroup's 64 KiB of LDS next to the tiles of radius {MAX_BOUNDARY_RADIUS})")
+    return C
+
+
+def boundary_launch_shape(num_classes, radius):
+    """The launch mmsa_eval_boundary_u8 makes for `num_classes` and `radius`, by the arithmetic of csrc/boundary.hip -> (zone groups, LDS bytes of a
+    workgroup, tile rows, tile columns): the tile is 64 columns x 64 rows up to radius 16 and 32 rows above, staged with a halo of `radius` for both maps
+    (row pitch 17 + radius // 2 dwords) next to 16 dwords per staged row of row-pass bytes, the 256-byte LUT and 4 / groups zone histograms; the groups
+    are the fewest of 1, 2, 4 that stay inside 64 KiB."""
+    C, r = _check_boundary_classes(int(num_classes)), check_boundary_radius(radius)
+    th = 64 if r <= 16 else 32
+    tiles = 2 * (th + 2 * r) * (_BOUNDARY_TILE_W // 4 + r // 2 + 1 + _BOUNDARY_TILE_W // 4) * 4
+    for groups in (1, 2, 4):
+        lds = (4 // groups) * (C + 1) * (C + 1) * 4 + tiles + 256
+        if lds <= _BOUNDARY_LDS:
+            break
+    return groups, lds, th, _BOUNDARY_TILE_W
+
+
+@torch.no_grad()
+def boundary_counts(pred, labels, prep, radius, border=False, counts=None, slots=None):
+    """ADD the boundary counts of the uint8 class maps pred [B, H, W] against the raw labels [B, Hl, Wl] into counts[slots[b]] (one launch,
+    mmsa_eval_boundary_u8) -> counts, int64 [n_slots, 4, C + 1, C + 1] on the device.  With L the transformed label code (a class, C = kept but out of range,
+    255 = ignored) and P = min(pred, C): a pixel is near a label boundary iff some pixel of the image within Chebyshev distance `radius` has another L (an
+    ignored label counts as a neighbour), near a prediction boundary likewise for P; `border=True` also puts every pixel closer than `radius` to the image
+    border near both (the zero-padded erosion).  Every pixel whose own label is not ignored adds 1 at [slot, 2 * near_label + near_pred, min(L, C), P]:
+    counts.sum(1) is `confusion(pred, labels, prep)`, bit for bit.  `slots` defaults to 0 .. B - 1; `counts` to a zeroed buffer of max(slots) + 1 slots."""
+    pred = _check_pred(pred)
+    radius = check_boundary_radius(radius)
+    B, H, W = (int(v) for v in pred.shape)
+    C = _check_boundary_classes(prep.num_classes)
+    with torch.cuda.device(pred.device):
+        largs = prep.launch_args(labels, B, H, W, pred.device)
+        if counts is None:
+            n_slots = B if slots is None else max(int(s) for s in slots) + 1
+            counts = torch.zeros(n_slots, 4, C + 1, C + 1, dtype=torch.int64, device=pred.device)
+        _check_buffer(counts, "counts", (4, C + 1, C + 1), pred.device)
+        tab = _slot_args(slots, B, counts.shape[0])
+        lib.call("mmsa_eval_boundary_u8", pred.data_ptr(), largs[0], B, H, W, largs[1], largs[2], largs[3], C, largs[4], largs[5], tab, counts.shape[0],
+                 radius, 1 if border else 0, counts.data_ptr(), ops._stream())
+    return counts
+
+
+def _zones(counts):
+    c = np.asarray(counts)
+    if c.ndim < 3 or c.shape[-3] != 4 or c.shape[-1] != c.shape[-2] or c.shape[-1] < 3 or c.dtype.kind not in "iu":
+        raise ValueError(f"mmsa.evaluate: boundary counts are an integer [..., 4, C + 1, C + 1] array, got {c.dtype} {c.shape}")
+    return c.astype(np.int64, copy=False)
+
+
+def boundary_zone_sum_of(counts):
+    """int64 [..., 4, C + 1, C + 1] boundary counts -> their sum over the zones, int64 [..., C + 1, C + 1]: the confusion counts of the whole map."""
+    return _zones(counts).sum(-3)
+
+
+def trimap_counts_of(counts, interior=False):
+    """int64 [..., 4, C + 1, C + 1] boundary counts -> the confusion counts of the band around the label boundaries (zones 2 + 3), int64 [..., C + 1, C + 1]:
+    what `areas_of` / `area_metrics` turn into the trimap aAcc / IoU / Acc.  `interior=True`: zones 0 + 1, the rest of the map."""
+    c = _zones(counts)
+    return c[..., 0, :, :] + c[..., 1, :, :] if interior else c[..., 2, :, :] + c[..., 3, :, :]
+
+
+def boundary_iou_of(counts):
+    """int64 [..., 4, C + 1, C + 1] boundary counts -> the Boundary IoU per class (Cheng et al., CVPR 2021), float64 [..., C]: with G_c the pixels of label c
+    near a label boundary (row c of zones 2 + 3), Pd_c the pixels predicted c near a prediction boundary (column c of zones 1 + 3; pixels with an ignored
+    label are in no count, as `intersect_and_union` masks them) and I_c = counts[3][c][c], BIoU_c = I_c / (G_c + Pd_c - I_c); 0 / 0 is NaN."""
+    c = _zones(counts)
+    C = c.shape[-1] - 1
+    G = (c[..., 2, :, :] + c[..., 3, :, :]).sum(-1)[..., :C]
+    Pd = (c[..., 1, :, :] + c[..., 3, :, :]).sum(-2)[..., :C]
+    I = np.diagonal(c[..., 3, :, :], axis1=-2, axis2=-1)[..., :C]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return I.astype(np.float64) / (G + Pd - I).astype(np.float64)
+
+
+class BoundaryEvaluator(_SlotOwner):
+    """Owns the boundary counts of an evaluation run, as Evaluator owns the confusion counts: int64 [n_slots, 4, C + 1, C + 1] on the device (`.counts`), zone
+    2 * near_label + near_pred at Chebyshev `radius` (`boundary_counts`).  `cases` / `images` / `device` and `slots=` of add(): as for Evaluator.  Only
+    host_counts() copies anything to the host; the trimap metrics and the Boundary IoU are formed from those integers in float64.  Across ranks:
+    mmsa.dist.allreduce_counts(be.counts)."""
+    _who, _read, _one, _attr, _pass = "BoundaryEvaluator", "host_counts()", "a BoundaryEvaluator", "counts", None
+
+    def __init__(self, prep, radius, border=False, cases=None, images=MAX_IMAGES, device=None):
+        self.prep = prep
+        self.radius = check_boundary_radius(radius, "mmsa.BoundaryEvaluator")
+        self.border = bool(border)
+        _check_boundary_classes(prep.num_classes, "mmsa.BoundaryEvaluator")
+        self._init_slots(cases, images)
+        self._init_buffer(device)
+
+    def _trailing(self):
+        return (4, self.prep.num_classes + 1, self.prep.num_classes + 1)
+
+    def add(self, pred, labels, case=None, slots=None):
+        """Count a batch of stored class maps (one launch; no host sync, no allocation once the buffer exists)."""
+        pred = _check_pred(pred)
+        B = int(pred.shape[0])
+        with torch.cuda.device(pred.device):
+            buf = self._buffer(pred.device)
+        boundary_counts(pred, labels, self.prep, self.radius, self.border, buf, self.slots_for(B, case, slots))
+        self._taken(B, case, slots)
+        return self
+
+    def host_counts(self):
+        """The counts on the host (the ONE device-to-host copy): int64 numpy [n, 4, C + 1, C + 1], n = images added so far / cases."""
+        return self._host()
+
+    def _of(self, slot):
+        c = self.host_counts()
+        return c.sum(0) if slot is None else c[self._slot_index(slot)]
+
+    def evaluator_counts(self):
+        """The sum over the zones: Evaluator.host_counts() of the same maps, int64 [n, C + 1, C + 1]."""
+        return boundary_zone_sum_of(self.host_counts())
+
+    def trimap_metrics(self, slot=None, metric=("mIoU",), nan_to_num=None, beta=1):
+        """`area_metrics` of the band around the label boundaries (zones 2 + 3), over every slot or of one slot (index or case name)."""
+        return area_metrics(*areas_of(trimap_counts_of(self._of(slot))), metric=metric, nan_to_num=nan_to_num, beta=beta)
+
+    def interior_metrics(self, slot=None, metric=("mIoU",), nan_to_num=None, beta=1):
+        """`area_metrics` of the pixels away from the label boundaries (zones 0 + 1)."""
+        return area_metrics(*areas_of(trimap_counts_of(self._of(slot), interior=True)), metric=metric, nan_to_num=nan_to_num, beta=beta)
+
+    def boundary_iou(self, slot=None):
+        """`boundary_iou_of`: the Boundary IoU per class, float64 [C]; NaN for a class with no pixel in either band."""
+        return boundary_iou_of(self._of(slot))
+
+    def summary(self, slot=None):
+        """OrderedDict aAcc, mIoU (the whole map: Evaluator's numbers), trimap_aAcc, trimap_mIoU, mBIoU (nanmean over the classes) and band (the share of the
+        counted pixels in zones 2 + 3), rounded as `Evaluator.summary` rounds."""
+        c = self._of(slot)
+        band = trimap_counts_of(c)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)
+            whole = summary_of(area_metrics(*areas_of(boundary_zone_sum_of(c))))
+            tri = summary_of(area_metrics(*areas_of(band)))
+            with np.errstate(divide="ignore", invalid="ignore"):
+                share = np.float64(band.sum()) / np.float64(c.sum())
+            return OrderedDict(aAcc=whole["aAcc"], mIoU=whole["mIoU"], trimap_aAcc=tri["aAcc"], trimap_mIoU=tri["mIoU"],
+                               mBIoU=np.round(np.nanmean(self.boundary_iou(slot)) * 100, 2) / 100.0, band=np.round(share * 100, 2) / 100.0)
