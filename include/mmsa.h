@@ -601,6 +601,47 @@ int mmsa_render_denorm_f32(const unsigned char* pred, long pred_image_stride, lo
                            int palette_reverse, const float* src, int Cs, int Hs, int Ws, const float* mean, const float* std, int to_rgb, int mul255,
                            double opacity, double one_minus_opacity, unsigned char* out, mmsa_stream_t stream);
 
+/* --- diagnostic pictures (csrc/render_diag.hip; the reference paints the ground truth through show_result in tools/color_gt_according_palette.py and has no
+ *     other): every pixel gets ONE paint chosen by a rule, then the blend of the block above.  out: uint8 [B, h, w, 3] contiguous.
+ *     table: DEVICE uint32 [ntab], packed by the CALLER: bits 0..23 the colour c0 | c1 << 8 | c2 << 16 in the PICTURE's channel order (no palette_reverse
+ *       here), bit 24 PAINT (0: the pixel is the source pixel unchanged, black without a source), bit 25 MARK (the blend uses mark_opacity /
+ *       one_minus_mark_opacity in the place of opacity / one_minus_opacity).  All four weights are formed by the caller, each pair as in the block above.
+ *       ntab must be exactly the size the picture's index rule needs (below), else MMSA_ERR_ARG.
+ *     src, src_form: 0 = none (src ignored), 1 = the raw uint8 frames [B, Hs, Ws, 3] (src_reverse swaps channels 0 and 2 first), 2 = the normalised float32
+ *       tensor [B, Cs >= 3, Hs, Ws] with HOST mean[3], std[3], to_rgb, mul255, de-normalised exactly as mmsa_render_denorm_f32 does it (mean / std / to_rgb /
+ *       mul255 / Cs are ignored otherwise).  Hs >= h, Ws >= w: the top-left h x w is used.
+ *     pred: uint8 class map, pixel (b, y, x) at pred[b * pred_image_stride + y * pred_row_stride + x].
+ *     The label side -- label uint8 [B, Hl, Wl], lut [256], ymap / xmap (both or neither; the label is read at [ymap[y], xmap[x]], clamped into the label map)
+ *       -- is mmsa_eval_confusion_u8's, and L is the label code of mmsa_eval_boundary_u8: a class < C, C (kept, out of range) or 255 (ignored).
+ *   render_labels_u8, 1 <= C <= 254:
+ *     mode 0, the ground truth: index = L < C ? L : C, ntab = C + 1; pred is not read.
+ *     mode 1, the wrong pixels: index = 0 where L == 255 (ignored); 1 + pred where L < C and pred == L (correct); 257 + (wrong_by_label ? L : pred)
+ *       elsewhere (wrong: L == C and pred == 255 included, as mmsa_eval_confusion_u8 counts them); ntab = 513.
+ *   render_values_f32: values float32 [B, h, w] contiguous; k = min(bins - 1, (int)(c * (float)bins)) of c = the value clamped as in mmsa_eval_calibration
+ *       (NaN, negatives, -0.0 -> 0; above 1, +inf -> 1), 1 <= bins <= 256.
+ *     pred == NULL, the heat map: index = k, ntab = bins.
+ *     pred given, the abstained pixels: index = pred where k >= min_bin, 256 + k elsewhere, 0 <= min_bin <= bins, ntab = 256 + bins: with entries 0..255 a
+ *       palette and the others one MARKED colour, the picture of the map mmsa_abstain_u8 writes, without writing that map.
+ *   render_band_u8: near_pred / near_label EXACTLY as mmsa_eval_boundary_u8 defines them for (radius, border), with P = min(pred, C); 1 <= radius <= 32,
+ *       1 <= C <= 253 (the kernel marks a mixed window with the byte 0xFE).  pred or label may be NULL (not both): the missing map has no band.
+ *     marked = ((where & 1) and near_pred) or ((where & 2) and near_label), and never a pixel whose own L is 255; where = 1, 2 or 3.
+ *     index = marked ? (mark_by_label ? L : P) : 256 + (inside_by_label ? L : P); ntab = 512.  A paint by L needs label.
+ *   Any limit broken, a null out / table, a source smaller than the map: MMSA_ERR_ARG with a message, before any launch. --- */
+int mmsa_render_labels_u8(const unsigned char* pred, long pred_image_stride, long pred_row_stride, const unsigned char* label, int B, int h, int w, int Hl, int Wl,
+                          const unsigned char* lut, int C, const int* ymap, const int* xmap, int mode, int wrong_by_label, const unsigned* table, int ntab,
+                          const void* src, int src_form, int Cs, int Hs, int Ws, int src_reverse, const float* mean, const float* std, int to_rgb, int mul255,
+                          double opacity, double one_minus_opacity, double mark_opacity, double one_minus_mark_opacity, unsigned char* out,
+                          mmsa_stream_t stream);
+int mmsa_render_values_f32(const float* values, const unsigned char* pred, long pred_image_stride, long pred_row_stride, int B, int h, int w, int bins,
+                           int min_bin, const unsigned* table, int ntab, const void* src, int src_form, int Cs, int Hs, int Ws, int src_reverse,
+                           const float* mean, const float* std, int to_rgb, int mul255, double opacity, double one_minus_opacity, double mark_opacity,
+                           double one_minus_mark_opacity, unsigned char* out, mmsa_stream_t stream);
+int mmsa_render_band_u8(const unsigned char* pred, long pred_image_stride, long pred_row_stride, const unsigned char* label, int B, int H, int W, int Hl, int Wl,
+                        const unsigned char* lut, int C, const int* ymap, const int* xmap, int radius, int border, int where, int mark_by_label,
+                        int inside_by_label, const unsigned* table, int ntab, const void* src, int src_form, int Cs, int Hs, int Ws, int src_reverse,
+                        const float* mean, const float* std, int to_rgb, int mul255, double opacity, double one_minus_opacity, double mark_opacity,
+                        double one_minus_mark_opacity, unsigned char* out, mmsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,7 +21,10 @@
  *      Still 114, for the same reason: new entries mmsa_slide_argmax_topk / mmsa_argmax_topk_nchw / mmsa_eval_topk_u8 (the first K classes of every pixel and
  *      their probabilities as rank-major planes, and the rank of the label's class counted per class).
  *      Still 114, for the same reason: new entry mmsa_eval_boundary_u8 (the confusion counts of a class map split by whether the pixel lies within a Chebyshev
- *      radius of a label boundary and of a prediction boundary: trimap metrics and Boundary IoU). */
+ *      radius of a label boundary and of a prediction boundary: trimap metrics and Boundary IoU).
+ *      Still 114, for the same reason: new entries mmsa_render_labels_u8 / mmsa_render_values_f32 / mmsa_render_band_u8 (the diagnostic pictures: the ground
+ *      truth and the wrong pixels, a heat map of any float32 score and the abstained pixels, the boundary band, each one paint per pixel from a packed table
+ *      and the blend of mmsa_render_u8). */
 #ifndef MMSA_VERSION_H
 #define MMSA_VERSION_H
 #define MMSA_ABI_VERSION 114

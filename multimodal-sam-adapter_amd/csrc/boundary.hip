@@ -31,14 +31,14 @@
 // csrc/selective.hip splits its bins: every group stages the tile and counts only its zones.  25 classes: 10 816 B of histograms, one group at every radius.
 #include "common.h"
 #include "eval_hist.h"
+#include "boundary_px.h"     // the tile geometry, the row pass and the column pass: shared with csrc/render_diag.hip
 
 #define BOUNDARY_MAX_RADIUS 32
+static_assert(BOUNDARY_MAX_RADIUS == BND_MAX_RADIUS, "the radius limit is the shared tile geometry's");
 // The largest C for which ONE zone's histogram fits next to the tiles at the maximum radius: 65536 - 256 - 37632 = 27648 bytes = 6912 cells >= (C + 1)^2
 // gives C + 1 <= 83 (83^2 = 6889, 84^2 = 7056).
 #define BOUNDARY_MAX_CLASSES 82
-#define BND_TILE_W 64                 // tile columns: 16 dwords of row-pass bytes per row
 #define BND_LDS_BYTES 65536
-#define BND_MIXED 0xFEFEFEFEu         // the row-pass byte of a window that is not uniform, in every byte
 
 static_assert(256 + 37632 + 83 * 83 * 4 <= BND_LDS_BYTES && 256 + 37632 + 84 * 84 * 4 > BND_LDS_BYTES, "BOUNDARY_MAX_CLASSES");
 
@@ -48,40 +48,8 @@ struct BndGeom {                      // the geometry of a launch, formed once o
   int tiles_x, zn;                    // tiles per row of tiles; zones per group
 };
 
-static inline int bnd_tile_h(int r) { return r <= 16 ? 64 : 32; }
-static inline int bnd_pitch_dw(int r) { return BND_TILE_W / 4 + r / 2 + 1; }
 static inline size_t bnd_lds_bytes(int r, int C, int zn) {
   return ((size_t)zn * (C + 1) * (C + 1) + (size_t)2 * (bnd_tile_h(r) + 2 * r) * (bnd_pitch_dw(r) + BND_TILE_W / 4)) * 4 + 256;
-}
-
-// bytes s .. s + 3 of the dword pair (lo, hi)
-__device__ __forceinline__ unsigned bnd_bytes(unsigned lo, unsigned hi, int s) { return (unsigned)(((((unsigned long long)hi) << 32) | lo) >> (8 * s)); }
-// 0x80 in every byte of x that is not zero
-__device__ __forceinline__ unsigned bnd_nonzero(unsigned x) { return (((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u; }
-
-// one staged row of one map, four tile columns from dword `row`: the row-pass dword
-__device__ __forceinline__ unsigned bnd_row_pass(const unsigned* row, int r) {
-  const unsigned c = bnd_bytes(row[r >> 2], row[(r >> 2) + 1], r & 3);
-  const int n = 2 * r + 1, nfull = n >> 2, rem = n & 3;        // n is odd: rem is 1 or 3
-  unsigned acc = 0u, lo = row[0];
-  for (int j = 0; j < nfull; ++j) {
-    const unsigned hi = row[j + 1];
-    acc |= (lo ^ c) | (bnd_bytes(lo, hi, 1) ^ c) | (bnd_bytes(lo, hi, 2) ^ c) | (bnd_bytes(lo, hi, 3) ^ c);
-    lo = hi;
-  }
-  const unsigned hi = row[nfull + 1];                          // nfull + 1 <= r / 2 + 1: inside the row's pitch
-  acc |= lo ^ c;
-  if (rem == 3) acc |= (bnd_bytes(lo, hi, 1) ^ c) | (bnd_bytes(lo, hi, 2) ^ c);
-  const unsigned mixed = (bnd_nonzero(acc) >> 7) * 0xffu;      // 0xff in every byte whose window is not uniform
-  return (c & ~mixed) | (BND_MIXED & mixed);
-}
-
-// four tile pixels from dword `col` of the row-pass image (16 dwords per row): 0x80 in the byte of every pixel near a boundary
-__device__ __forceinline__ unsigned bnd_col_pass(const unsigned* col, int r) {
-  const unsigned c = col[r * (BND_TILE_W / 4)];
-  unsigned acc = 0u;
-  for (int k = 0; k <= 2 * r; ++k) acc |= col[k * (BND_TILE_W / 4)] ^ c;
-  return bnd_nonzero(acc) | (~bnd_nonzero(c ^ BND_MIXED) & 0x80808080u);
 }
 
 __global__ __launch_bounds__(256) void eval_boundary_kernel(const unsigned char* __restrict__ pred, EvalLabel ev, EvalSlots es, BndGeom g) {

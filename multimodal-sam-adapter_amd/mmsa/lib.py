@@ -30,6 +30,8 @@ L = c_long
 F = c_float
 
 # name -> argtypes (restype is int unless listed in _RESTYPES)
+# the tail every diagnostic-picture entry shares: table, ntab, src, src_form, Cs, Hs, Ws, src_reverse, mean, std, to_rgb, mul255, the four weights, out, stream
+_PAINT_TAIL = [P, I, P, I, I, I, I, I, P, P, I, I, c_double, c_double, c_double, c_double, P, P]
 SIGNATURES = {
     "mmsa_version": [],
     "mmsa_last_error": [],
@@ -107,6 +109,9 @@ SIGNATURES = {
     "mmsa_slide_argmax_eval": [P, I, I, I, I, P, P, I, I, I, I, I, P, P, I, I, P, P, P, P, I, P, P],
     "mmsa_render_u8": [P, L, L, I, I, I, P, I, I, P, I, I, I, c_double, c_double, P, P],
     "mmsa_render_denorm_f32": [P, L, L, I, I, I, P, I, I, P, I, I, I, P, P, I, I, c_double, c_double, P, P],
+    "mmsa_render_labels_u8": [P, L, L, P, I, I, I, I, I, P, I, P, P, I, I] + _PAINT_TAIL,
+    "mmsa_render_values_f32": [P, P, L, L, I, I, I, I, I] + _PAINT_TAIL,
+    "mmsa_render_band_u8": [P, L, L, P, I, I, I, I, I, P, I, P, P, I, I, I, I, I] + _PAINT_TAIL,
 }
 _RESTYPES = {"mmsa_last_error": c_char_p, "mmsa_gram_tn_scratch_bytes": c_long}
 
