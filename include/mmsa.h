@@ -580,6 +580,35 @@ int mmsa_eval_topk_u8(const unsigned char* classes, int K, const unsigned char* 
 int mmsa_eval_boundary_u8(const unsigned char* pred, const unsigned char* label, int B, int H, int W, int Hl, int Wl, const unsigned char* lut, int C,
                           const int* ymap, const int* xmap, const int* slots, int n_slots, int radius, int border, int64_t* counts, mmsa_stream_t stream);
 
+/* --- Euclidean boundary evaluation (csrc/distance.hip): exact squared distance maps of code maps, and what is counted from two of them.
+ *   boundary_distance_u8: for the code map M(y, x) = lut[src[b, ymap[y], xmap[x]]] on the grid [H, W] (lut == NULL: the byte itself; ymap / xmap both or
+ *     neither, clamped into the source; without them Hs == H and Ws == W) the kernel compares BYTES and knows nothing of classes: the caller's LUT makes the
+ *     codes (v -> min(v, C) for a class map; the label LUT with every value in [C, 254] mapped to C for a label map).
+ *       D2(p) = min over pixels q OF THE IMAGE with M(q) != M(p) of (qy - py)^2 + (qx - px)^2; border = 1: additionally D2(p) <= db^2,
+ *       db = min(y, x, H - 1 - y, W - 1 - x) + 1 (the first pixel outside the image: the Euclidean counterpart of mmsa_eval_boundary_u8's border rule).
+ *     d2 uint16 [B, H, W] = D2 where D2 <= cap^2, else 65535 (FAR); 1 <= cap <= 255.  Images of a batch never see each other.  scratch: uint16 [B, H, W] of the
+ *     caller's, written and read by the two launches of the call (a row pass and a column pass), never allocated here.  Every loop is bounded by the row
+ *     length, by cap or by the image height.
+ *   eval_boundary_d2: mmsa_eval_boundary_u8's counts with "near" = within a Euclidean radius: every pixel whose own label code L is not 255 adds 1 at
+ *     [slot, 2 * (d2_label <= t) + (d2_pred <= t), min(L, C), P] of counts int64 [n_slots, 4, C + 1, C + 1], ADDED to.  pred, the label side (lut, ymap / xmap,
+ *     slots: HOST int [B]) and the codes L, P are mmsa_eval_boundary_u8's; d2_pred / d2_label are uint16 [B, H, W] as boundary_distance_u8 writes them for P and
+ *     for L; t = floor(radius^2), 1 <= t <= 65025 (t <= cap^2 of the maps is the caller's to keep: FAR is above every t).  The zone sum is
+ *     mmsa_eval_confusion_u8's matrix.  2 <= C <= 126 (one zone's histogram in a workgroup's LDS; the zones are split over gridDim.z where four do not fit).
+ *   eval_boundary_displacement: hist int64 [n_slots, 2, C + 1, cap + 2], ADDED to; bin 0 stays 0.  For every pixel whose own L is not 255: where
+ *     d2_label <= 2 (a label-boundary pixel: a pixel with another label code among its 8 neighbours) 1 is added at [slot, 0, min(L, C), k(d2_pred)]; where
+ *     d2_pred <= 2, 1 at [slot, 1, P, k(d2_label)].  k(d2) = the smallest integer k >= 1 with k^2 >= d2, exact; cap + 1 for FAR.  cap is the maps' cap
+ *     (with cap = 1 the value 2 is FAR, and only pixels with another code among their 4 neighbours are boundary pixels).  (C + 1) * (cap + 2) <= 16320 (one
+ *     side's uint32 histogram in a workgroup's LDS): 62 classes at cap 255, 246 at cap 64.
+ *   A limit broken or a null pointer: MMSA_ERR_ARG with a message, before any launch.  Integer sums: the same bytes whatever the order of arrival. --- */
+int mmsa_boundary_distance_u8(const unsigned char* src, int B, int Hs, int Ws, const unsigned char* lut, const int* ymap, const int* xmap, int H, int W,
+                              int cap, int border, unsigned short* scratch, unsigned short* d2, mmsa_stream_t stream);
+int mmsa_eval_boundary_d2(const unsigned char* pred, const unsigned char* label, int B, int H, int W, int Hl, int Wl, const unsigned char* lut, int C,
+                          const int* ymap, const int* xmap, const int* slots, int n_slots, const unsigned short* d2_pred, const unsigned short* d2_label,
+                          int t, int64_t* counts, mmsa_stream_t stream);
+int mmsa_eval_boundary_displacement(const unsigned char* pred, const unsigned char* label, int B, int H, int W, int Hl, int Wl, const unsigned char* lut,
+                                    int C, const int* ymap, const int* xmap, const int* slots, int n_slots, const unsigned short* d2_pred,
+                                    const unsigned short* d2_label, int cap, int64_t* hist, mmsa_stream_t stream);
+
 /* --- the picture of a prediction (segmentation/mmseg_custom/apis/test_bs.py:257-349, the `--show` / `--show-dir` output): `tensor2imgs` (test_bs.py:18-63) on
  *     planes 0..2 of the input tensor -> the crop `img[:h, :w]` (test_bs.py:275-276) -> `show_result` (tools/color_gt_according_palette.py:23-81:
  *     color_seg[seg == label] = color, channels reversed, img * (1 - opacity) + color_seg * opacity, .astype(uint8)), in one pass.

@@ -24,7 +24,10 @@
  *      radius of a label boundary and of a prediction boundary: trimap metrics and Boundary IoU).
  *      Still 114, for the same reason: new entries mmsa_render_labels_u8 / mmsa_render_values_f32 / mmsa_render_band_u8 (the diagnostic pictures: the ground
  *      truth and the wrong pixels, a heat map of any float32 score and the abstained pixels, the boundary band, each one paint per pixel from a packed table
- *      and the blend of mmsa_render_u8). */
+ *      and the blend of mmsa_render_u8).
+ *      Still 114, for the same reason: new entries mmsa_boundary_distance_u8 / mmsa_eval_boundary_d2 / mmsa_eval_boundary_displacement (the exact squared
+ *      Euclidean distance map of a code map, the boundary counts at a Euclidean radius from two such maps, and the displacement histogram of the two contours:
+ *      boundary F-score and Hausdorff percentiles). */
 #ifndef MMSA_VERSION_H
 #define MMSA_VERSION_H
 #define MMSA_ABI_VERSION 114

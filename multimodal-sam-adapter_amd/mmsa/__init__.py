@@ -21,6 +21,8 @@ from .evaluate import SelectiveEvaluator, selective, abstain  # noqa: F401  (con
 from .evaluate import TemperatureSweep, temperature_sweep  # noqa: F401  (temperature scaling: NLL and reliability bins of a logits canvas over a grid of T)
 from .evaluate import TopKEvaluator, topk_counts  # noqa: F401  (the rank of the label's class in a top-k map: top-k pixel accuracy and recall@k)
 from .evaluate import BoundaryEvaluator, boundary_counts, boundary_zone_sum_of, trimap_counts_of, boundary_iou_of  # noqa: F401  (confusion counts by nearness to a label / prediction boundary: trimap metrics and Boundary IoU)
+from .evaluate import (EuclideanBoundaryEvaluator, boundary_distance, boundary_counts_d2, boundary_displacement, boundary_f_of,  # noqa: F401  (exact distance
+                       boundary_f_curve_of, boundary_distance_percentile_of)  # maps of the code maps: Euclidean bands up to 255 pixels, boundary F-score, Hausdorff percentiles)
 from . import render  # noqa: F401  (the picture of a prediction on device: palette map over the frame, show_result)
 from .render import Renderer
 from .registry import BACKBONES, HEADS, build_backbone, build_head
@@ -47,4 +49,6 @@ __all__ = ["SegformerHead", "HEADS", "build_head", "register_head", "SAMAdapterb
            "BACKBONES", "build_backbone", "ops", "lib", "inference", "Chains", "Replay", "AttentionRangeError", "OperandRangeError",
            "preprocess", "Preprocess", "FrameFeeder", "evaluate", "Evaluator", "LabelPrep", "confusion", "Calibration", "calibration", "SelectiveEvaluator", "selective", "abstain", "TemperatureSweep", "temperature_sweep", "render", "Renderer",
            "probabilities", "aug_inference", "aug_class_map", "AugPlan", "argmax_max_map", "argmax_score_map", "TopK", "argmax_topk_map",
-           "TopKEvaluator", "topk_counts", "BoundaryEvaluator", "boundary_counts", "boundary_zone_sum_of", "trimap_counts_of", "boundary_iou_of"]
+           "TopKEvaluator", "topk_counts", "BoundaryEvaluator", "boundary_counts", "boundary_zone_sum_of", "trimap_counts_of", "boundary_iou_of",
+           "EuclideanBoundaryEvaluator", "boundary_distance", "boundary_counts_d2", "boundary_displacement", "boundary_f_of", "boundary_f_curve_of",
+           "boundary_distance_percentile_of"]

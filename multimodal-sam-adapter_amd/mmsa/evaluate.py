@@ -37,10 +37,20 @@ counts verbatim -- column r is the diagonal of the confusion matrix of plane r, 
 Boundary evaluation asks how good the contours are: `boundary_counts` / `BoundaryEvaluator` reduce (class map, label map) to int64 [4, C + 1, C + 1] per slot
 (mmsa_eval_boundary_u8, csrc/boundary.hip) -- the confusion matrix split into the zones 2 * near_label + near_pred, "near" = within a Chebyshev radius of a pixel
 with another code -- whose zone sum is the Evaluator's matrix; `trimap_counts_of` (zones 2 + 3: the band around the label boundaries, fed to `areas_of` /
-`area_metrics`) and `boundary_iou_of` (Cheng et al., CVPR 2021) form the trimap metrics and the Boundary IoU in float64 on the host."""
+`area_metrics`) and `boundary_iou_of` (Cheng et al., CVPR 2021) form the trimap metrics and the Boundary IoU in float64 on the host.
+
+Euclidean boundary evaluation rests on one more primitive, the exact distance map of a code map: `boundary_distance` writes, per pixel, the squared Euclidean
+distance to the nearest pixel of the image with another code as uint16, up to a cap of 255 pixels (mmsa_boundary_distance_u8, csrc/distance.hip).  A band at any
+radius is a threshold on two such maps (`boundary_counts_d2`, mmsa_eval_boundary_d2: the four zones above, so every `_of` function above reads them), several radii
+are several pointwise launches over one pair of maps, and `boundary_displacement` (mmsa_eval_boundary_displacement) bins every contour pixel of one map by its
+distance to the other map's contour, int64 [2, C + 1, cap + 2] per slot -- from which `boundary_f_of` / `boundary_f_curve_of` form the boundary F-score at a
+tolerance (Csurka et al.; the DAVIS F measure) and `boundary_distance_percentile_of` the Hausdorff percentile HD95 in float64 on the host.
+`EuclideanBoundaryEvaluator` is a BoundaryEvaluator that owns both buffers."""
 import ctypes
+import math
 import warnings
 from collections import OrderedDict, namedtuple
+from fractions import Fraction
 
 import numpy as np
 import torch
@@ -1359,3 +1369,381 @@ class BoundaryEvaluator(_SlotOwner):
                 share = np.float64(band.sum()) / np.float64(c.sum())
             return OrderedDict(aAcc=whole["aAcc"], mIoU=whole["mIoU"], trimap_aAcc=tri["aAcc"], trimap_mIoU=tri["mIoU"],
                                mBIoU=np.round(np.nanmean(self.boundary_iou(slot)) * 100, 2) / 100.0, band=np.round(share * 100, 2) / 100.0)
+
+
+# ---- Euclidean boundary evaluation: exact squared distance maps of the code maps, and what is counted from two of them (csrc/distance.hip) ----
+# For a code map M (the label codes L or the prediction codes P of the boundary pass above) D2(p) = the smallest (qy - py)^2 + (qx - px)^2 over the pixels q OF
+# THE IMAGE with M(q) != M(p): an integer >= 1, kept where it is <= cap^2 and FAR elsewhere; `border=True` also bounds it by db^2, db = min(y, x, H - 1 - y,
+# W - 1 - x) + 1 (the first pixel outside the image).  "Near at Euclidean radius rho" is D2 <= floor(rho^2); the adjacent pixel is at distance 1, and two
+# coincident contours give D2 in {1, 2}: TOLERANCES COUNT FROM 1.  With the Chebyshev band `near(., d)` of the boundary pass: D2 <= 2 <=> near(., 1);
+# near(., d) => D2 <= 2 d^2; D2 <= d^2 => near(., d).
+MAX_DISTANCE_CAP = 255             # csrc/distance.hip DIST_MAX_CAP: cap^2 = 65025 is the largest value a uint16 map holds below FAR
+DISTANCE_FAR = 65535               # csrc/distance.hip DIST_FAR: "further than cap", and "no other code in the image"
+MAX_EUCLIDEAN_CLASSES = 126        # csrc/distance.hip DIST_MAX_CLASSES: one zone's (C + 1)^2 uint32 histogram in a workgroup's 64 KiB of LDS
+MAX_DISPLACEMENT_CELLS = 16320     # csrc/distance.hip DIST_MAX_SIDE_CELLS: (C + 1) * (cap + 2) uint32 cells of one side of the displacement histogram in LDS
+_CODE_LUTS = {}                    # (codes, device) -> the device LUT of a distance launch
+_DISTANCE_SCRATCH = {}             # (device, stream) -> the uint16 row-run plane of boundary_distance calls without scratch=
+
+
+def check_distance_cap(cap, who="mmsa.evaluate"):
+    if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or not 1 <= int(cap) <= MAX_DISTANCE_CAP:
+        raise ValueError(f"{who}: cap = {cap!r}; 1..{MAX_DISTANCE_CAP} pixels are supported (cap^2 must fit the uint16 distance map)")
+    return int(cap)
+
+
+def euclidean_threshold(radius=None, radius2=None, who="mmsa.evaluate"):
+    """`radius` (an int or float in [1, 255]) or `radius2` (an int in 1..65025), one of them -> (t, smallest cap): t = floor(radius^2) formed exactly (the float's
+    own value, squared as a fraction), or radius2 itself; the smallest cap is ceil(radius), for radius2 the smallest integer k with k^2 >= radius2."""
+    if (radius is None) == (radius2 is None):
+        raise ValueError(f"{who}: radius= or radius2=, one of them")
+    if radius2 is not None:
+        if isinstance(radius2, bool) or not isinstance(radius2, (int, np.integer)) or not 1 <= int(radius2) <= MAX_DISTANCE_CAP ** 2:
+            raise ValueError(f"{who}: radius2 = {radius2!r}; an integer squared radius in 1..{MAX_DISTANCE_CAP ** 2} is expected")
+        t = int(radius2)
+        return t, math.isqrt(t - 1) + 1
+    if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)) or not 1 <= float(radius) <= MAX_DISTANCE_CAP:
+        raise ValueError(f"{who}: radius = {radius!r}; 1..{MAX_DISTANCE_CAP} pixels (Euclidean; an int or a float) are supported")
+    r = Fraction(int(radius)) if isinstance(radius, (int, np.integer)) else Fraction(float(radius))
+    return math.floor(r * r), math.ceil(r)
+
+
+def _check_displacement_size(C, cap, who="mmsa.evaluate"):
+    if (C + 1) * (cap + 2) > MAX_DISPLACEMENT_CELLS:
+        raise RuntimeError(f"{who}: {C} classes at cap {cap}: (C + 1) * (cap + 2) = {(C + 1) * (cap + 2)} cells per side of the displacement histogram; at most "
+                           f"{MAX_DISPLACEMENT_CELLS} are supported (one side's uint32 histogram must fit a workgroup's 64 KiB of LDS): 62 classes at cap 255, "
+                           "246 at cap 64")
+
+
+def _check_euclidean_classes(C, who="mmsa.evaluate"):
+    if C > MAX_EUCLIDEAN_CLASSES:
+        raise RuntimeError(f"{who}: {C} classes; Euclidean boundary evaluation supports 2..{MAX_EUCLIDEAN_CLASSES} (one zone's (C + 1)^2 uint32 histogram must "
+                           "fit a workgroup's 64 KiB of LDS)")
+    return C
+
+
+def _check_map(t, name, dtype, what, like=None, shape_only=False):
+    """A stored map of a Euclidean pass: a contiguous [B, H, W] GPU tensor of `dtype`; with `like`, of that tensor's shape and device.  Type, dtype and shape
+    are looked at before the device (`shape_only`: and the device not at all), so that they are refused without one."""
+    if not isinstance(t, torch.Tensor):
+        raise RuntimeError(f"mmsa.evaluate: {name} must be a tensor, got {type(t).__name__}")
+    if t.dtype != dtype:
+        raise RuntimeError(f"mmsa.evaluate: {name} is {t.dtype}; {what} is expected")
+    if t.dim() != 3 or not t.is_contiguous():
+        raise RuntimeError(f"mmsa.evaluate: {name} must be a contiguous [B, H, W] tensor, got {tuple(t.shape)}")
+    if like is not None and tuple(t.shape) != tuple(like.shape):
+        raise RuntimeError(f"mmsa.evaluate: {name} has shape {tuple(t.shape)}, the map is [B, H, W] = {tuple(like.shape)}")
+    if shape_only:
+        return t
+    if not t.is_cuda:
+        raise RuntimeError(f"mmsa.evaluate: {name} must be a GPU tensor (there is no CPU path)")
+    if like is not None and t.device != like.device:
+        raise RuntimeError(f"mmsa.evaluate: {name} is on {t.device}, the map on {like.device}")
+    return t
+
+
+def code_lut(num_classes=None, prep=None):
+    """The 256-byte LUT a distance launch compares codes through, uint8 numpy [256]: v -> min(v, C) for a stored class map (`num_classes`), or the label LUT
+    of `prep` with every value in [C, 254] mapped to C (255 stays: an ignored label is a code like any other)."""
+    if prep is not None:
+        lut = np.asarray(prep.lut, dtype=np.uint8)
+        return np.where(lut == IGNORE, IGNORE, np.minimum(lut, prep.num_classes)).astype(np.uint8)
+    C = int(num_classes)
+    if not 1 <= C <= 254:
+        raise ValueError(f"mmsa.evaluate: num_classes {num_classes}; a uint8 class map has 1..254 classes")
+    return np.minimum(np.arange(256), C).astype(np.uint8)
+
+
+def _code_lut_on(device, num_classes=None, prep=None):
+    lut = code_lut(num_classes, prep)
+    key = (lut.tobytes(), torch.device(device))
+    t = _CODE_LUTS.get(key)
+    if t is None:
+        if _capturing(key[1]):
+            raise RuntimeError("mmsa.evaluate: the code LUT of the distance launch is not on the device yet and cannot be uploaded during a graph capture: run "
+                               "one call before capturing")
+        t = _CODE_LUTS[key] = torch.from_numpy(lut).to(key[1])
+    return t
+
+
+def _distance_scratch(n, device):
+    key = (torch.device(device), ops._stream())
+    t = _DISTANCE_SCRATCH.get(key)
+    if t is None or t.numel() < n:
+        if _capturing(key[0]):
+            raise RuntimeError("mmsa.evaluate: the scratch plane of the distance launch cannot be allocated during a graph capture: pass scratch=, or run one "
+                               "call of this size before capturing")
+        t = _DISTANCE_SCRATCH[key] = torch.empty(n, dtype=torch.uint16, device=key[0])
+    return t
+
+
+@torch.no_grad()
+def boundary_distance(map, cap, border=False, *, labels_prep=None, num_classes=None, size=None, scratch=None, out=None):
+    """The squared Euclidean distance of every pixel to the nearest pixel of its image with another code (two launches, mmsa_boundary_distance_u8) -> uint16
+    [B, H, W] on the device: D2 where D2 <= cap^2, DISTANCE_FAR (65535) elsewhere -- further than `cap`, or an image of one code.  The adjacent pixel is at
+    D2 = 1: distances count from 1.  `border=True` also bounds D2 by the squared distance to the first pixel outside the image.  Two uses, one of the keywords:
+      num_classes=C     `map` is a stored uint8 class map [B, H, W]; the codes are P = min(map, C), as every boundary pass reads a prediction;
+      labels_prep=prep  `map` holds raw uint8 labels [B, Hl, Wl]; the codes are the label codes L of `prep` (a class, C = kept but out of range, 255 = ignored: a
+                        code like any other) on the grid `size=(H, W)` -- by default the size `prep` resizes an Hl x Wl label map to -- through the
+                        nearest-neighbour tables of the label side.
+    `out=` (uint16 [B, H, W]) and `scratch=` (a uint16 tensor of at least B * H * W elements, the row pass's plane) make the call allocation-free; without
+    scratch= a buffer cached per device and stream is used, which a repeated call does not allocate again."""
+    cap = check_distance_cap(cap)
+    if (labels_prep is None) == (num_classes is None):
+        raise ValueError("mmsa.evaluate: boundary_distance takes num_classes= (a stored class map) or labels_prep= (raw labels), one of them")
+    src = _check_map(map, "map", torch.uint8, "a uint8 class map or raw uint8 labels", shape_only=True)
+    B, Hs, Ws = (int(v) for v in src.shape)
+    if labels_prep is None:
+        if size is not None and tuple(size) != (Hs, Ws):
+            raise RuntimeError(f"mmsa.evaluate: size={tuple(size)} for a stored {Hs} x {Ws} class map: only labels are resized (labels_prep=)")
+        H, W = Hs, Ws
+    else:
+        H, W = labels_prep.resized(Hs, Ws) if size is None else (int(size[0]), int(size[1]))
+        if labels_prep.resized(Hs, Ws) != (H, W):
+            raise RuntimeError(f"mmsa.evaluate: size mismatch: the label maps are {Hs} x {Ws}, which the LabelPrep reads on a grid of "
+                               f"{labels_prep.resized(Hs, Ws)[0]} x {labels_prep.resized(Hs, Ws)[1]}, not {H} x {W}")
+    if B * H * W == 0:
+        raise RuntimeError(f"mmsa.evaluate: an empty map {tuple(src.shape)}")
+    _check_map(src, "map", torch.uint8, "a uint8 class map or raw uint8 labels")
+    with torch.cuda.device(src.device):
+        if out is None:
+            out = torch.empty(B, H, W, dtype=torch.uint16, device=src.device)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint16 or tuple(out.shape) != (B, H, W) or out.device != src.device
+              or not out.is_contiguous()):
+            raise RuntimeError(f"mmsa.evaluate: out must be a contiguous uint16 {(B, H, W)} tensor on {src.device}")
+        if scratch is None:
+            scratch = _distance_scratch(B * H * W, src.device)
+        elif (not isinstance(scratch, torch.Tensor) or scratch.dtype != torch.uint16 or scratch.numel() < B * H * W or scratch.device != src.device
+              or not scratch.is_contiguous() or scratch.data_ptr() == out.data_ptr()):
+            raise RuntimeError(f"mmsa.evaluate: scratch must be a contiguous uint16 tensor of at least {B * H * W} elements on {src.device}, and not `out`")
+        lut = _code_lut_on(src.device, num_classes, labels_prep)
+        ymap, xmap = (None, None) if labels_prep is None else labels_prep.tables(Hs, Ws, H, W, src.device)
+        lib.call("mmsa_boundary_distance_u8", src.data_ptr(), B, Hs, Ws, lut.data_ptr(), None if ymap is None else ymap.data_ptr(),
+                 None if xmap is None else xmap.data_ptr(), H, W, cap, 1 if border else 0, scratch.data_ptr(), out.data_ptr(), ops._stream())
+    return out
+
+
+def _d2_launch(entry, pred, labels, prep, d2_pred, d2_label, scalar, buf, name, shape, slots):
+    """One launch of a pointwise pass over (pred, labels, d2_pred, d2_label) into the int64 buffer `buf` [n_slots, *shape] -> the buffer."""
+    for only in (True, False):      # dtypes and shapes of all three first, then the devices
+        pred = _check_map(pred, "pred", torch.uint8, "a uint8 class map", shape_only=only)
+        d2_pred = _check_map(d2_pred, "d2_pred", torch.uint16, "a uint16 distance map (mmsa.boundary_distance)", like=pred, shape_only=only)
+        d2_label = _check_map(d2_label, "d2_label", torch.uint16, "a uint16 distance map (mmsa.boundary_distance)", like=pred, shape_only=only)
+    B, H, W = (int(v) for v in pred.shape)
+    C = prep.num_classes
+    with torch.cuda.device(pred.device):
+        largs = prep.launch_args(labels, B, H, W, pred.device)
+        if buf is None:
+            n_slots = B if slots is None else max(int(s) for s in slots) + 1
+            buf = torch.zeros(n_slots, *shape, dtype=torch.int64, device=pred.device)
+        _check_buffer(buf, name, shape, pred.device)
+        tab = _slot_args(slots, B, buf.shape[0])
+        lib.call(entry, pred.data_ptr(), largs[0], B, H, W, largs[1], largs[2], largs[3], C, largs[4], largs[5], tab, buf.shape[0], d2_pred.data_ptr(),
+                 d2_label.data_ptr(), scalar, buf.data_ptr(), ops._stream())
+    return buf
+
+
+@torch.no_grad()
+def boundary_counts_d2(pred, labels, prep, d2_pred, d2_label, t, counts=None, slots=None):
+    """ADD the boundary counts at a Euclidean radius into counts[slots[b]] (one launch, mmsa_eval_boundary_d2) -> counts, int64 [n_slots, 4, C + 1, C + 1] on the
+    device, `boundary_counts`' layout and meaning with near_label = (d2_label <= t), near_pred = (d2_pred <= t): every pixel whose own label is not ignored adds
+    1 at [slot, 2 * near_label + near_pred, min(L, C), P].  d2_pred = boundary_distance(pred, cap, border, num_classes=C) and d2_label =
+    boundary_distance(labels, cap, border, labels_prep=prep); t = floor(radius^2), an integer in 1..cap^2 (t = 2 is `boundary_counts` at radius 1, bit for
+    bit; several radii are several of these launches over one pair of maps).  counts.sum(1) is `confusion(pred, labels, prep)`."""
+    if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 1 <= int(t) <= MAX_DISTANCE_CAP ** 2:
+        raise ValueError(f"mmsa.evaluate: t = {t!r}; an integer squared radius in 1..{MAX_DISTANCE_CAP ** 2} is expected (floor(radius^2), at most cap^2 of the maps)")
+    C = _check_euclidean_classes(prep.num_classes)
+    return _d2_launch("mmsa_eval_boundary_d2", pred, labels, prep, d2_pred, d2_label, int(t), counts, "counts", (4, C + 1, C + 1), slots)
+
+
+@torch.no_grad()
+def boundary_displacement(pred, labels, prep, d2_pred, d2_label, cap, hist=None, slots=None):
+    """ADD the displacement histogram of the two contours into hist[slots[b]] (one launch, mmsa_eval_boundary_displacement) -> hist, int64
+    [n_slots, 2, C + 1, cap + 2] on the device.  For every pixel whose own label is not ignored: a label-boundary pixel (d2_label <= 2: another label code
+    among its 8 neighbours) adds 1 at [slot, 0, min(L, C), k(d2_pred)], a prediction-boundary pixel (d2_pred <= 2) adds 1 at [slot, 1, P, k(d2_label)];
+    k(d2) = the smallest integer k >= 1 with k^2 >= d2 -- the distance rounded UP to whole pixels, counted from 1: coincident contours land in bins 1 and 2
+    (D2 = 1 or 2), bin 0 stays 0 -- and cap + 1 for DISTANCE_FAR.  `cap` is the cap the two maps were made with."""
+    cap = check_distance_cap(cap)
+    C = prep.num_classes
+    _check_displacement_size(C, cap)
+    return _d2_launch("mmsa_eval_boundary_displacement", pred, labels, prep, d2_pred, d2_label, cap, hist, "hist", (2, C + 1, cap + 2), slots)
+
+
+def _displacement(hist):
+    h = np.asarray(hist)
+    if h.ndim < 3 or h.shape[-3] != 2 or h.shape[-2] < 2 or h.shape[-1] < 3 or h.dtype.kind not in "iu":
+        raise ValueError(f"mmsa.evaluate: a displacement histogram is an integer [..., 2, C + 1, cap + 2] array, got {h.dtype} {h.shape}")
+    return h.astype(np.int64, copy=False)
+
+
+def _f_of(matched, total):
+    """matched / total int64 [..., 2, rows]: side 0 (label-boundary pixels: recall), side 1 (prediction-boundary pixels: precision) -> precision, recall, F."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        prec = matched[..., 1, :].astype(np.float64) / total[..., 1, :].astype(np.float64)
+        rec = matched[..., 0, :].astype(np.float64) / total[..., 0, :].astype(np.float64)
+        return prec, rec, 2 * prec * rec / (prec + rec)
+
+
+def boundary_f_curve_of(hist):
+    """The boundary F-score (Csurka et al.; the DAVIS F measure; the "BF score") at EVERY tolerance 1 .. cap from int64 [..., 2, C + 1, cap + 2] displacement
+    counts -> OrderedDict: 'tolerance' int64 [cap]; 'precision', 'recall', 'F' float64 [..., C, cap] per class c < C; 'precision_all', 'recall_all', 'F_all'
+    float64 [..., cap], class-agnostic: every row, the out-of-range row C included.  At tolerance T the matched pixels are the bins 1 .. T -- of side 1 for the
+    precision (prediction-boundary pixels within T of a label boundary), of side 0 for the recall -- over the sum of all bins; F = 2 P R / (P + R); 0 / 0 is
+    NaN.  Tolerances count from 1: the adjacent pixel is at distance 1, coincident contours at 1 or sqrt(2) (bins 1 and 2)."""
+    h = _displacement(hist)
+    cap, C = h.shape[-1] - 2, h.shape[-2] - 1
+    total = h.sum(-1)
+    matched = np.cumsum(h[..., 1:cap + 1], axis=-1)                          # [..., 2, C + 1, cap]
+    prec, rec, f = _f_of(np.moveaxis(matched, -1, -3), total[..., None, :, :])      # [..., cap, C + 1]
+    pa, ra, fa = _f_of(np.moveaxis(matched.sum(-2), -1, -2)[..., None], total.sum(-1)[..., None, :, None])
+    out = OrderedDict(tolerance=np.arange(1, cap + 1, dtype=np.int64))
+    for k, v in (("precision", prec), ("recall", rec), ("F", f)):
+        out[k] = np.moveaxis(v[..., :C], -2, -1)
+    for k, v in (("precision_all", pa), ("recall_all", ra), ("F_all", fa)):
+        out[k] = v[..., 0]
+    return out
+
+
+def boundary_f_of(hist, tolerance):
+    """The boundary F-score at one tolerance (an integer in 1 .. cap, counted from 1: the adjacent pixel is at distance 1) from int64
+    [..., 2, C + 1, cap + 2] displacement counts -> OrderedDict 'precision', 'recall', 'F' float64 [..., C] and 'precision_all', 'recall_all', 'F_all'
+    float64 [...]: `boundary_f_curve_of` at that tolerance."""
+    h = _displacement(hist)
+    cap = h.shape[-1] - 2
+    if isinstance(tolerance, bool) or not isinstance(tolerance, (int, np.integer)) or not 1 <= int(tolerance) <= cap:
+        raise ValueError(f"mmsa.evaluate: tolerance = {tolerance!r}; an integer in 1..{cap} (the histogram's cap; tolerances count from 1) is expected")
+    c = boundary_f_curve_of(h)
+    return OrderedDict((k, v[..., int(tolerance) - 1]) for k, v in c.items() if k != "tolerance")
+
+
+def boundary_distance_percentile_of(hist, q=0.95):
+    """The symmetric Hausdorff percentile HD-q from int64 [2, C + 1, cap + 2] displacement counts of ONE slot (or of a sum over slots) -> OrderedDict
+    'label_to_pred', 'pred_to_label' (per side, over every row: the smallest bin k whose cumulative count reaches q * total, compared exactly in integers) and
+    'hd' = the larger of the two, float64: "at most k pixels", counted from 1 as the bins are; inf where that bin is cap + 1 (further than the cap); NaN for a
+    side without boundary pixels (and then for 'hd')."""
+    h = _displacement(hist)
+    if h.ndim != 3:
+        raise ValueError(f"mmsa.evaluate: boundary_distance_percentile_of takes the [2, C + 1, cap + 2] counts of one slot, got {h.shape}")
+    if isinstance(q, bool) or not isinstance(q, (int, float, np.integer, np.floating)) or not 0 < float(q) <= 1:
+        raise ValueError(f"mmsa.evaluate: q = {q!r}; a share in (0, 1] is expected")
+    cap = h.shape[-1] - 2
+    frac = Fraction(float(q))
+    vals = []
+    for side in range(2):
+        bins = [int(v) for v in h[side].sum(0)]
+        total, cum, k = sum(bins), 0, None
+        for k, v in enumerate(bins):
+            cum += v
+            if total and cum * frac.denominator >= frac.numerator * total:
+                break
+        vals.append(np.float64(np.nan) if total == 0 else np.float64(np.inf) if k == cap + 1 else np.float64(k))
+    return OrderedDict(label_to_pred=vals[0], pred_to_label=vals[1], hd=np.float64(np.nan) if np.isnan(vals).any() else np.float64(max(vals)))
+
+
+class EuclideanBoundaryEvaluator(BoundaryEvaluator):
+    """BoundaryEvaluator at a EUCLIDEAN radius of up to 255 pixels, with the boundary F-score and the Hausdorff percentiles next to it.  `radius` (an int or a
+    float in [1, 255]; the band is D2 <= floor(radius^2), formed exactly) or `radius2=` (that integer outright); `cap` (default ceil(radius); cap >= ceil(radius),
+    cap <= 255): how far the distance maps -- and with them the displacement histogram, the tolerances of boundary_f() and distance_percentile() -- reach.
+    `.counts` is the parent's int64 [n_slots, 4, C + 1, C + 1] buffer, zone 2 * near_label + near_pred, and trimap_metrics / interior_metrics / boundary_iou /
+    summary / evaluator_counts / host_counts read it as the parent's; radius2=2 counts what BoundaryEvaluator(radius=1) counts, bit for bit.  `.displacement`
+    (displacement=True) is the second device buffer, int64 [n_slots, 2, C + 1, cap + 2] (`boundary_displacement`).  Every entry's `boundary=` takes it.  add()
+    makes two distance launches into buffers cached per shape and stream, one zone-count launch and one histogram launch: no host sync, and no allocation
+    once the buffers of a shape exist.  Across ranks: mmsa.dist.allreduce_counts(be.counts) and allreduce_counts(be.displacement).  Tolerances and bins count
+    from 1 (the adjacent pixel is at distance 1).  Up to 126 classes; with the histogram (C + 1) * (cap + 2) <= 16320."""
+    _who, _read, _one = "EuclideanBoundaryEvaluator", "host_counts()", "a EuclideanBoundaryEvaluator"
+    metric = "euclidean"
+
+    def __init__(self, prep, radius=None, cap=None, border=False, displacement=True, cases=None, images=MAX_IMAGES, device=None, *, radius2=None):
+        who = "mmsa.EuclideanBoundaryEvaluator"
+        self.prep = prep
+        self.radius2, least = euclidean_threshold(radius, radius2, who)
+        self.tolerance = least      # the default tolerance of boundary_f(): ceil(radius)
+        self.radius = radius if radius is not None else math.sqrt(self.radius2)
+        self.cap = least if cap is None else check_distance_cap(cap, who)
+        if self.cap < least:
+            raise ValueError(f"{who}: cap = {cap} is below ceil(radius) = {least}: the distance maps would not reach the band's edge")
+        self.border = bool(border)
+        self.with_displacement = bool(displacement)
+        C = _check_euclidean_classes(prep.num_classes, who)
+        if self.with_displacement:
+            _check_displacement_size(C, self.cap, who)
+        self._init_slots(cases, images)
+        self.displacement = None
+        self._maps = {}         # (B, H, W, device, stream) -> (d2_pred, d2_label, scratch)
+        self._init_buffer(device)
+
+    def _buffer(self, device):
+        buf = super()._buffer(device)
+        if self.with_displacement and self.displacement is None:
+            self.displacement = torch.zeros(self.n_slots, 2, self.prep.num_classes + 1, self.cap + 2, dtype=torch.int64, device=buf.device)
+        return buf
+
+    def _maps_for(self, B, H, W, device):
+        key = (B, H, W, device, ops._stream())
+        m = self._maps.get(key)
+        if m is None:
+            if _capturing(device):
+                raise RuntimeError(f"mmsa.{self._who}: the distance maps of a {B} x {H} x {W} batch cannot be allocated during a graph capture: run one add() "
+                                   "of this shape before capturing")
+            m = self._maps[key] = tuple(torch.empty(B, H, W, dtype=torch.uint16, device=device) for _ in range(3))
+        return m
+
+    def add(self, pred, labels, case=None, slots=None):
+        """Count a batch of stored class maps: the distance maps of both sides (two launches each), the zone counts and, with displacement=True, the
+        histogram; no host sync, no allocation once the buffers for the shape exist."""
+        pred = _check_pred(pred)
+        B, H, W = (int(v) for v in pred.shape)
+        with torch.cuda.device(pred.device):
+            self.prep.launch_args(labels, B, H, W, pred.device)      # the label side checked before the first launch
+            buf = self._buffer(pred.device)
+            d2p, d2l, scratch = self._maps_for(B, H, W, pred.device)
+            boundary_distance(pred, self.cap, self.border, num_classes=self.prep.num_classes, scratch=scratch, out=d2p)
+            boundary_distance(labels, self.cap, self.border, labels_prep=self.prep, size=(H, W), scratch=scratch, out=d2l)
+            use = self.slots_for(B, case, slots)
+            boundary_counts_d2(pred, labels, self.prep, d2p, d2l, self.radius2, buf, use)
+            if self.with_displacement:
+                boundary_displacement(pred, labels, self.prep, d2p, d2l, self.cap, self.displacement, use)
+        self._taken(B, case, slots)
+        return self
+
+    def reset(self):
+        super().reset()
+        if self.displacement is not None:
+            self.displacement.zero_()
+
+    def host_displacement(self):
+        """The displacement histogram on the host: int64 numpy [n, 2, C + 1, cap + 2], n = images added so far / cases."""
+        if not self.with_displacement:
+            raise RuntimeError(f"mmsa.{self._who}: made with displacement=False: there is no displacement histogram (boundary F-score, Hausdorff percentiles)")
+        if self.displacement is None:
+            return np.zeros((0 if self.cases is None else self.n_slots, 2, self.prep.num_classes + 1, self.cap + 2), dtype=np.int64)
+        h = self.displacement.cpu().numpy()
+        return h[:self.used] if self.cases is None else h
+
+    def _displacement_of(self, slot):
+        h = self.host_displacement()
+        return h.sum(0) if slot is None else h[self._slot_index(slot)]
+
+    def boundary_f(self, tolerance=None, slot=None):
+        """`boundary_f_of` at `tolerance` (an integer in 1 .. cap, counted from 1; default: ceil(radius)), over every slot or
+        of one slot."""
+        return boundary_f_of(self._displacement_of(slot), self.tolerance if tolerance is None else tolerance)
+
+    def boundary_f_curve(self, slot=None):
+        """`boundary_f_curve_of`: precision, recall and F at every tolerance 1 .. cap."""
+        return boundary_f_curve_of(self._displacement_of(slot))
+
+    def distance_percentile(self, q=0.95, slot=None):
+        """`boundary_distance_percentile_of`: the symmetric Hausdorff percentile, "at most k pixels"; inf beyond the cap."""
+        return boundary_distance_percentile_of(self._displacement_of(slot), q)
+
+    def summary(self, slot=None):
+        """The parent's entries at the Euclidean band, then mBF (nanmean over the classes of the F-score at tolerance ceil(radius), rounded as the others)
+        and HD95 in pixels (displacement=True), radius, radius2 and metric = 'euclidean'."""
+        s = super().summary(slot)
+        if self.with_displacement:
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore", RuntimeWarning)
+                s["mBF"] = np.round(np.nanmean(self.boundary_f(slot=slot)["F"]) * 100, 2) / 100.0
+            s["HD95"] = self.distance_percentile(0.95, slot)["hd"]
+        s["radius"], s["radius2"], s["metric"] = self.radius, self.radius2, self.metric
+        return s
