@@ -49,7 +49,7 @@ tolerance (Csurka et al.; the DAVIS F measure) and `boundary_distance_percentile
 import ctypes
 import math
 import warnings
-from collections import OrderedDict, namedtuple
+from collections import OrderedDict
 from fractions import Fraction
 
 import numpy as np
@@ -144,10 +144,20 @@ def area_metrics(area_intersect, area_union, area_pred_label, area_label, metric
     return out
 
 
+def _is_int(x, lo, hi):
+    """`x` is an int (numpy's too; no bool) in lo .. hi."""
+    return not (isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not lo <= int(x) <= hi)
+
+
+def _round_percent(v):
+    """v x 100 rounded to two places, / 100: how every summary rounds."""
+    return np.round(v * 100, 2) / 100.0
+
+
 def summary_of(metrics):
     """The summary `evaluate` forms from such a dict (DELIVER.py:327-367): nanmean per entry, x 100 rounded to two places, / 100; every key but
     'aAcc' gets the 'm' prefix."""
-    return OrderedDict((k if k == "aAcc" else "m" + k, np.round(np.nanmean(v) * 100, 2) / 100.0) for k, v in metrics.items())
+    return OrderedDict((k if k == "aAcc" else "m" + k, _round_percent(np.nanmean(v))) for k, v in metrics.items())
 
 
 # ---- calibration metrics from the integer bins (numpy, float64) ----
@@ -248,7 +258,7 @@ SCORES = {"max": 0, "margin": 1, "entropy": 2}      # `score=` of the class-map 
 def inv_log_classes(C):
     """The factor of the entropy score 1 - H / log C (csrc/softmax_px.h): float32(1 / log(float64(C))) -> a Python float that holds that float32 exactly; 0 for
     one class, whose entropy is 0 and whose score is 1."""
-    if isinstance(C, bool) or not isinstance(C, (int, np.integer)) or int(C) < 1:
+    if not _is_int(C, 1, math.inf):
         raise ValueError(f"mmsa.evaluate: {C!r} classes; a positive integer is expected")
     return 0.0 if int(C) == 1 else float(np.float32(np.float64(1.0) / np.log(np.float64(int(C)))))
 
@@ -256,7 +266,7 @@ def inv_log_classes(C):
 def geometric_grid(lo, hi, J):
     """J temperatures from lo to hi with a constant ratio, float64 [J] (J == 1: [lo]); both ends are exact.  0 < lo <= hi, 1 <= J <= 16.  A first sweep
     over a wide grid and a second over geometric_grid(T / r, T * r, J) around its best() is the whole fit."""
-    if isinstance(J, bool) or not isinstance(J, (int, np.integer)) or not 1 <= int(J) <= MAX_TEMPERATURES:
+    if not _is_int(J, 1, MAX_TEMPERATURES):
         raise ValueError(f"mmsa.evaluate: J = {J!r}; 1..{MAX_TEMPERATURES} temperatures per sweep")
     lo, hi = np.float64(lo), np.float64(hi)
     if not (np.isfinite(lo) and np.isfinite(hi) and 0 < lo <= hi):
@@ -283,7 +293,7 @@ def _sweep4(sweep):
 def sweep_bins_of(sweep, j):
     """Calibration's int64 [3, K] bins at temperature j of an int64 [J, 4, K] sweep: what reliability_of / ece_of / mce_of / risk_coverage_of take."""
     s = _sweep4(sweep)
-    if isinstance(j, bool) or not isinstance(j, (int, np.integer)) or not 0 <= int(j) < s.shape[0]:
+    if not _is_int(j, 0, s.shape[0] - 1):
         raise ValueError(f"mmsa.evaluate: temperature index j = {j!r}; 0..{s.shape[0] - 1}")
     return s[int(j), :3].copy()
 
@@ -352,7 +362,7 @@ def selective_counts_of(counts, min_bin=0):
     `abstain` writes at min_bin has these counts with the row sums of counts[:min_bin] added into column C: its abstained pixels predict 255.)"""
     c = _counts3(counts)
     K = c.shape[0]
-    if isinstance(min_bin, bool) or not isinstance(min_bin, (int, np.integer)) or not 0 <= int(min_bin) <= K:
+    if not _is_int(min_bin, 0, K):
         raise ValueError(f"mmsa.evaluate: min_bin = {min_bin!r}; 0..{K} for {K} bins")
     return _sum_bins(c[int(min_bin):])
 
@@ -584,6 +594,18 @@ def _check_buffer(buf, name, shape, device):
     return buf
 
 
+def _slot_launch(prep, labels, B, H, W, device, buf, name, shape, slots, default=True):
+    """What every launch into an int64 [n_slots, *shape] buffer does before its `lib.call`, in the caller's device guard: the label side of a [B, H, W]
+    map checked, the buffer `name` allocated where none is given (zeroed, max(slots) + 1 slots; `default=False`: an entry without that default) and
+    checked, the slots checked against it -> (LabelPrep.launch_args, the buffer, the slot table)."""
+    largs = prep.launch_args(labels, B, H, W, device)
+    if buf is None and default:
+        n_slots = B if slots is None else max(int(s) for s in slots) + 1
+        buf = torch.zeros(n_slots, *shape, dtype=torch.int64, device=device)
+    _check_buffer(buf, name, shape, device)
+    return largs, buf, _slot_args(slots, B, buf.shape[0])
+
+
 def _check_pred(pred):
     if not isinstance(pred, torch.Tensor) or not pred.is_cuda:
         raise RuntimeError("mmsa.evaluate: pred must be a GPU tensor (there is no CPU path)")
@@ -610,7 +632,7 @@ def _check_confmap(conf, pred):
 
 
 def _check_bins(bins):
-    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 1 <= int(bins) <= MAX_BINS:
+    if not _is_int(bins, 1, MAX_BINS):
         raise ValueError(f"mmsa.evaluate: bins = {bins!r}; 1..{MAX_BINS} confidence bins are supported")
     return int(bins)
 
@@ -622,38 +644,11 @@ def _check_selective_classes(C):
     return C
 
 
-# A pass over stored maps (csrc/eval_walk.h): its entry, the name of its result buffer, the trailing shape of that int64 [n_slots, ...] buffer for C
-# classes and K bins, the axis of K in the buffer (None: a pass without a confidence map), and the pass's own check of the class count.
-_Pass = namedtuple("_Pass", "entry name shape k_axis check_classes")
-_CONFUSION = _Pass("mmsa_eval_confusion_u8", "counts", lambda C, K: (C + 1, C + 1), None, None)
-_CALIBRATION = _Pass("mmsa_eval_calibration", "cal", lambda C, K: (3, K), 2, None)
-_SELECTIVE = _Pass("mmsa_eval_selective", "counts", lambda C, K: (K, C + 1, C + 1), 1, _check_selective_classes)
-
-
-def _launch(which, pred, conf, labels, prep, bins, buf, slots):
-    """One launch of a pass: the maps and the buffer checked, the buffer allocated (zeroed, max(slots) + 1 slots) where none is given -> the buffer."""
-    pred = _check_pred(pred)
-    B, H, W = (int(v) for v in pred.shape)
-    C = prep.num_classes
-    confs = ()
-    if which.k_axis is not None:
-        confs = (_check_confmap(conf, pred).data_ptr(),)
-        if which.check_classes is not None:
-            which.check_classes(C)
-        if bins is None:
-            bins = int(buf.shape[which.k_axis]) if isinstance(buf, torch.Tensor) and buf.dim() == len(which.shape(C, 0)) + 1 else DEFAULT_BINS
-        bins = _check_bins(bins)
-    shape = which.shape(C, bins)
-    with torch.cuda.device(pred.device):
-        largs = prep.launch_args(labels, B, H, W, pred.device)
-        if buf is None:
-            n_slots = B if slots is None else max(int(s) for s in slots) + 1
-            buf = torch.zeros(n_slots, *shape, dtype=torch.int64, device=pred.device)
-        _check_buffer(buf, which.name, shape, pred.device)
-        tab = _slot_args(slots, B, buf.shape[0])
-        lib.call(which.entry, pred.data_ptr(), *confs, largs[0], B, H, W, largs[1], largs[2], largs[3], C, largs[4], largs[5], tab, buf.shape[0],
-                 *(() if which.k_axis is None else (bins,)), buf.data_ptr(), ops._stream())
-    return buf
+def _default_bins(bins, buf, k_axis, ndim):
+    """`bins=` of an entry with confidence bins: K itself, by default that of the buffer given (axis `k_axis` of its `ndim` axes), or 15."""
+    if bins is None:
+        bins = int(buf.shape[k_axis]) if isinstance(buf, torch.Tensor) and buf.dim() == ndim else DEFAULT_BINS
+    return _check_bins(bins)
 
 
 @torch.no_grad()
@@ -661,7 +656,14 @@ def confusion(pred, labels, prep, counts=None, slots=None):
     """ADD the confusion counts of the uint8 class maps pred [B, H, W] against the raw labels [B, Hl, Wl] into counts[slots[b]] (one launch,
     mmsa_eval_confusion_u8) -> counts, int64 [n_slots, C + 1, C + 1] on the device.  `slots` defaults to 0 .. B - 1 (per-image counts, as `pre_eval`
     returns them); `counts` defaults to a zeroed buffer of max(slots) + 1 slots."""
-    return _launch(_CONFUSION, pred, None, labels, prep, None, counts, slots)
+    pred = _check_pred(pred)
+    B, H, W = (int(v) for v in pred.shape)
+    C = prep.num_classes
+    with torch.cuda.device(pred.device):
+        largs, counts, tab = _slot_launch(prep, labels, B, H, W, pred.device, counts, "counts", (C + 1, C + 1), slots)
+        lib.call("mmsa_eval_confusion_u8", pred.data_ptr(), largs[0], B, H, W, largs[1], largs[2], largs[3], C, largs[4], largs[5], tab, counts.shape[0],
+                 counts.data_ptr(), ops._stream())
+    return counts
 
 
 @torch.no_grad()
@@ -671,7 +673,16 @@ def calibration(pred, conf, labels, prep, bins=None, cal=None, slots=None):
     A pixel takes part iff its transformed label is a class (< C); it is correct iff pred equals it; its bin is min(K - 1, int(float32(c) * float32(K)))
     of its confidence c clamped to [0, 1] (NaN -> 0); conf_sum adds floor(c * 2^24).  `bins` = K defaults to cal's, or to 15; `slots` defaults to
     0 .. B - 1 (per-image bins); `cal` defaults to a zeroed buffer of max(slots) + 1 slots."""
-    return _launch(_CALIBRATION, pred, conf, labels, prep, bins, cal, slots)
+    pred = _check_pred(pred)
+    conf = _check_confmap(conf, pred)
+    B, H, W = (int(v) for v in pred.shape)
+    C = prep.num_classes
+    bins = _default_bins(bins, cal, 2, 3)
+    with torch.cuda.device(pred.device):
+        largs, cal, tab = _slot_launch(prep, labels, B, H, W, pred.device, cal, "cal", (3, bins), slots)
+        lib.call("mmsa_eval_calibration", pred.data_ptr(), conf.data_ptr(), largs[0], B, H, W, largs[1], largs[2], largs[3], C, largs[4], largs[5], tab,
+                 cal.shape[0], bins, cal.data_ptr(), ops._stream())
+    return cal
 
 
 @torch.no_grad()
@@ -681,7 +692,16 @@ def selective(pred, conf, labels, prep, bins=None, counts=None, slots=None):
     counts[s, k, row, col] += 1 for every pixel whose label is not ignored, row / col as in `confusion` (index C = outside [0, C)), k as in `calibration`
     (min(K - 1, int(float32(c) * float32(K))) of the confidence clamped to [0, 1], NaN -> 0).  `bins` = K defaults to counts', or to 15; `slots` defaults
     to 0 .. B - 1 (per-image counts); `counts` defaults to a zeroed buffer of max(slots) + 1 slots."""
-    return _launch(_SELECTIVE, pred, conf, labels, prep, bins, counts, slots)
+    pred = _check_pred(pred)
+    conf = _check_confmap(conf, pred)
+    B, H, W = (int(v) for v in pred.shape)
+    C = _check_selective_classes(prep.num_classes)
+    bins = _default_bins(bins, counts, 1, 4)
+    with torch.cuda.device(pred.device):
+        largs, counts, tab = _slot_launch(prep, labels, B, H, W, pred.device, counts, "counts", (bins, C + 1, C + 1), slots)
+        lib.call("mmsa_eval_selective", pred.data_ptr(), conf.data_ptr(), largs[0], B, H, W, largs[1], largs[2], largs[3], C, largs[4], largs[5], tab,
+                 counts.shape[0], bins, counts.data_ptr(), ops._stream())
+    return counts
 
 
 def _check_logits(logits):
@@ -715,16 +735,9 @@ def temperature_sweep(logits, labels, prep, temperatures, bins=None, out=None, s
         raise RuntimeError(f"mmsa.evaluate: the logits have {C} classes, the LabelPrep {prep.num_classes}")
     its = _inv_temperatures(temperatures)
     J = len(its)
-    if bins is None:
-        bins = int(out.shape[3]) if isinstance(out, torch.Tensor) and out.dim() == 4 else DEFAULT_BINS
-    bins = _check_bins(bins)
+    bins = _default_bins(bins, out, 3, 4)
     with torch.cuda.device(logits.device):
-        largs = prep.launch_args(labels, B, H, W, logits.device)
-        if out is None:
-            n_slots = B if slots is None else max(int(s) for s in slots) + 1
-            out = torch.zeros(n_slots, J, 4, bins, dtype=torch.int64, device=logits.device)
-        _check_buffer(out, "out", (J, 4, bins), logits.device)
-        tab = _slot_args(slots, B, out.shape[0])
+        largs, out, tab = _slot_launch(prep, labels, B, H, W, logits.device, out, "out", (J, 4, bins), slots)
         lib.call("mmsa_temperature_sweep_nchw", logits.data_ptr(), largs[0], B, C, H, W, largs[1], largs[2], largs[3], largs[4], largs[5], tab, out.shape[0],
                  (ctypes.c_float * J)(*its), J, bins, out.data_ptr(), ops._stream())
     return out
@@ -743,7 +756,7 @@ def abstain(pred, conf, bins, min_bin=None, out=None, threshold=None):
         raise ValueError("mmsa.evaluate: abstain takes min_bin= or threshold=, one of them")
     if threshold is not None:
         min_bin = threshold_bin(threshold, K)
-    if isinstance(min_bin, bool) or not isinstance(min_bin, (int, np.integer)) or not 0 <= int(min_bin) <= K:
+    if not _is_int(min_bin, 0, K):
         raise ValueError(f"mmsa.evaluate: min_bin = {min_bin!r}; 0..{K} for {K} bins ({K} abstains everywhere)")
     with torch.cuda.device(pred.device):
         if out is None:
@@ -762,17 +775,16 @@ def slide_argmax_eval(lg, n, windows, out, B, H, W, hc, wc, unc, labels, prep, c
     C = int(lg.shape[1])
     if C != prep.num_classes:
         raise RuntimeError(f"mmsa.evaluate: the head has {C} classes, the LabelPrep {prep.num_classes}")
-    largs = prep.launch_args(labels, B, H, W, lg.device)
-    _check_buffer(counts, "counts", (C + 1, C + 1), lg.device)
-    tab = _slot_args(slots, B, counts.shape[0])
+    largs, counts, tab = _slot_launch(prep, labels, B, H, W, lg.device, counts, "counts", (C + 1, C + 1), slots, default=False)
     lib.call("mmsa_slide_argmax_eval", lg.data_ptr(), n, C, lg.shape[2], lg.shape[3], windows, None if out is None else out.data_ptr(), B, H, W, hc, wc,
              unc.data_ptr(), largs[0], largs[1], largs[2], largs[3], largs[4], largs[5], tab, counts.shape[0], counts.data_ptr(), ops._stream())
 
 
 class _SlotOwner:
     """A pass's int64 [n_slots, ...] buffer with one slot per image or per case, and its bookkeeping: Evaluator's and SelectiveEvaluator's counts,
-    Calibration's bins.  A subclass names itself (`_who`, `_one`, `_read`), its pass and the public attribute that holds the buffer (`_attr`)."""
-    _who, _read, _one, _attr, _pass = "Evaluator", "areas()", "an Evaluator", "counts", _CONFUSION
+    Calibration's bins, and so on.  A subclass names itself (`_who`, `_one`, `_read`) and the public attribute that holds the buffer (`_attr`), states the
+    shape of one slot (`_trailing()`) and hands `_add` the entry that launches its pass; buffer, slots, reading and resetting are here."""
+    _who, _read, _one, _attr = "Evaluator", "areas()", "an Evaluator", "counts"
     n_bins = None               # the passes with a confidence map set it
 
     def _init_slots(self, cases, images):
@@ -789,7 +801,8 @@ class _SlotOwner:
             self._buffer(torch.device(device))
 
     def _trailing(self):
-        return self._pass.shape(self.prep.num_classes, self.n_bins)
+        """The shape of one slot of the buffer: every owner states its own."""
+        raise NotImplementedError
 
     def _buffer(self, device):
         buf = getattr(self, self._attr)
@@ -803,15 +816,17 @@ class _SlotOwner:
             raise RuntimeError(f"mmsa.{self._who}: the {self._attr} live on {buf.device}, this batch on {device}")
         return buf
 
-    def _add(self, pred, conf, labels, case, slots):
-        """One launch of the pass into the buffer; the slots are taken once it has gone through."""
-        pred = _check_pred(pred)
-        if self._pass.k_axis is not None:
-            _check_confmap(conf, pred)
-        with torch.cuda.device(pred.device):
-            buf = self._buffer(pred.device)
-        _launch(self._pass, pred, conf, labels, self.prep, self.n_bins, buf, self.slots_for(pred.shape[0], case, slots))
-        self._taken(pred.shape[0], case, slots)
+    def _add(self, lead, B, case, slots, launch, *args, guard=True):
+        """The add() of every owner, behind its check of `lead` (the tensor that names the device): the buffer (made under the device guard; add_fused
+        makes it without; one that exists needs none), the slots of the next B images, `launch(*args, buffer, slots)` -- every entry ends in these two --
+        and the slots taken once it has gone through."""
+        if guard and getattr(self, self._attr) is None:
+            with torch.cuda.device(lead.device):
+                buf = self._buffer(lead.device)
+        else:
+            buf = self._buffer(lead.device)
+        launch(*args, buf, self.slots_for(B, case, slots))
+        self._taken(B, case, slots)
         return self
 
     def reset(self):
@@ -820,11 +835,11 @@ class _SlotOwner:
             buf.zero_()
         self.used = 0
 
-    def _host(self):
-        """The buffer on the host, int64 numpy [n, ...]: n = images added so far (per-image mode) / cases."""
-        buf = getattr(self, self._attr)
+    def _host(self, attr=None, trailing=None):
+        """The buffer (or the one `attr` names, of that trailing shape) on the host, int64 numpy [n, ...]: n = images added so far (per-image mode) / cases."""
+        buf = getattr(self, attr or self._attr)
         if buf is None:
-            return np.zeros((0 if self.cases is None else self.n_slots, *self._trailing()), dtype=np.int64)
+            return np.zeros((0 if self.cases is None else self.n_slots, *(trailing or self._trailing())), dtype=np.int64)
         h = buf.cpu().numpy()
         return h[:self.used] if self.cases is None else h
 
@@ -851,6 +866,16 @@ class _SlotOwner:
     def _slot_index(self, slot):
         return self.cases.index(slot) if self.cases is not None and not isinstance(slot, int) else int(slot)
 
+    def _pick(self, h, slot, check=None, total=None):
+        """Of the host array h [n, ...]: the slot `slot` (index or case name), or with None the sum over every slot (`total(h)` where an owner sums with
+        care).  `check` is called on every slot first, so that a slot at its capacity raises before a sum over slots could wrap."""
+        if check is not None:
+            for one in h:
+                check(one)
+        if slot is not None:
+            return h[self._slot_index(slot)]
+        return h.sum(0) if total is None else total(h)
+
 
 class Evaluator(_SlotOwner):
     """Owns the count buffer of an evaluation run.  `cases` = None: one slot per IMAGE, in the order the images are added (what `pre_eval` returns per
@@ -863,17 +888,18 @@ class Evaluator(_SlotOwner):
         self._init_slots(cases, images)
         self._init_buffer(device)
 
+    def _trailing(self):
+        return (self.prep.num_classes + 1, self.prep.num_classes + 1)
+
     def add(self, pred, labels, case=None, slots=None):
         """Count a batch of stored class maps (one launch)."""
-        return self._add(pred, None, labels, case, slots)
+        pred = _check_pred(pred)
+        return self._add(pred, pred.shape[0], case, slots, confusion, pred, labels, self.prep)
 
     def add_fused(self, lg, plan, out, unc, labels, case=None, slots=None):
         """Class map + counts in one launch (mmsa.inference's class-map calls with labels= / evaluator=); `plan`: the frame's mmsa.inference.MapPlan."""
-        counts = self._buffer(lg.device)
-        slide_argmax_eval(lg, plan.n, plan.tab, out, plan.B, plan.H, plan.W, plan.hc, plan.wc, unc, labels, self.prep, counts,
-                          slots=self.slots_for(plan.B, case, slots))
-        self._taken(plan.B, case, slots)
-        return self
+        return self._add(lg, plan.B, case, slots, slide_argmax_eval, lg, plan.n, plan.tab, out, plan.B, plan.H, plan.W, plan.hc, plan.wc, unc, labels,
+                         self.prep, guard=False)
 
     def host_counts(self):
         """The counts on the host (the ONE device-to-host copy of an evaluation): int64 numpy [n, C + 1, C + 1], n = images added so far / cases."""
@@ -885,9 +911,7 @@ class Evaluator(_SlotOwner):
 
     def metrics(self, metric=("mIoU",), nan_to_num=None, beta=1, slot=None):
         """`total_area_to_metrics` of the totals over every slot (the reference's 'global' entry) or of one slot (index or case name), in float64."""
-        a = self.areas()
-        a = [x.sum(0) for x in a] if slot is None else [x[self._slot_index(slot)] for x in a]
-        return area_metrics(*a, metric=metric, nan_to_num=nan_to_num, beta=beta)
+        return area_metrics(*(self._pick(a, slot) for a in self.areas()), metric=metric, nan_to_num=nan_to_num, beta=beta)
 
     def summary(self, metric=("mIoU",), nan_to_num=None, beta=1, slot=None):
         """aAcc / mIoU / mAcc / ... as `evaluate` forms them from the per-class values: nanmean, rounded to two places of a percent."""
@@ -901,7 +925,7 @@ class Calibration(_SlotOwner):
     have the buffer before the first add, and `slots=` to add(), for a call that is captured in a HIP graph.  Only host_bins() copies anything to the
     host: 3 K integers per slot; every metric is formed from them in float64, of one slot (`slot=` index or case name) or of the sum over all slots
     (`slot=None`), and raises OverflowError once a bin holds 2^39 pixels.  Across ranks: mmsa.dist.allreduce_counts(cal.bins)."""
-    _who, _read, _one, _attr, _pass = "Calibration", "host_bins()", "a Calibration", "bins", _CALIBRATION
+    _who, _read, _one, _attr = "Calibration", "host_bins()", "a Calibration", "bins"
 
     def __init__(self, prep, bins=DEFAULT_BINS, cases=None, images=MAX_IMAGES, device=None):
         self.prep = prep
@@ -909,9 +933,13 @@ class Calibration(_SlotOwner):
         self._init_slots(cases, images)
         self._init_buffer(device)
 
+    def _trailing(self):
+        return (3, self.n_bins)
+
     def add(self, pred, conf, labels, case=None, slots=None):
         """Bin a batch of stored class maps and their confidence maps (one launch; no host sync, no allocation once the buffer exists)."""
-        return self._add(pred, conf, labels, case, slots)
+        _check_confmap(conf, _check_pred(pred))
+        return self._add(pred, pred.shape[0], case, slots, calibration, pred, conf, labels, self.prep, self.n_bins)
 
     def host_bins(self):
         """The bins on the host (the ONE device-to-host copy of a calibration run): int64 numpy [n, 3, K], n = images added so far / cases."""
@@ -920,10 +948,7 @@ class Calibration(_SlotOwner):
     def _of(self, slot):
         """int64 [3, K] of one slot (index or case name), or of the sum over every slot.  A slot at its capacity raises here, before a sum over slots
         could wrap; a sum whose totals stay below 2^39 has confidence sums below 2^63."""
-        b = self.host_bins()
-        for one in b:
-            _bins3(one)
-        return b.sum(0) if slot is None else b[self._slot_index(slot)]
+        return self._pick(self.host_bins(), slot, _bins3)
 
     def reliability(self, slot=None):
         """`reliability_of` the slot's bins: edges, count, accuracy and confidence per bin."""
@@ -957,7 +982,7 @@ class SelectiveEvaluator(_SlotOwner):
     as for Calibration.  Only host_counts() copies anything to the host (81 KB per slot at 25 classes and 15 bins); everything else is formed from those
     integers: `min_bin=` keeps the bins min_bin .. K - 1 (the pixels `abstain` leaves in the map), and at min_bin=0 metrics / summary / areas are the
     Evaluator's.  A buffer above 1 GiB is refused.  Across ranks: mmsa.dist.allreduce_counts(se.counts)."""
-    _who, _read, _one, _attr, _pass = "SelectiveEvaluator", "host_counts()", "a SelectiveEvaluator", "counts", _SELECTIVE
+    _who, _read, _one, _attr = "SelectiveEvaluator", "host_counts()", "a SelectiveEvaluator", "counts"
 
     def __init__(self, prep, bins=DEFAULT_BINS, cases=None, images=MAX_IMAGES, device=None):
         self.prep = prep
@@ -970,9 +995,13 @@ class SelectiveEvaluator(_SlotOwner):
                              f"the {MAX_SELECTIVE_BYTES} (1 GiB) a count buffer may take: fewer slots (cases= or images=) or fewer bins")
         self._init_buffer(device)
 
+    def _trailing(self):
+        return (self.n_bins, self.prep.num_classes + 1, self.prep.num_classes + 1)
+
     def add(self, pred, conf, labels, case=None, slots=None):
         """Count a batch of stored class maps and their confidence maps (one launch; no host sync, no allocation once the buffer exists)."""
-        return self._add(pred, conf, labels, case, slots)
+        _check_confmap(conf, _check_pred(pred))
+        return self._add(pred, pred.shape[0], case, slots, selective, pred, conf, labels, self.prep, self.n_bins)
 
     def host_counts(self):
         """The counts on the host (the ONE device-to-host copy of a run): int64 numpy [n, K, C + 1, C + 1], n = images added so far / cases."""
@@ -980,12 +1009,7 @@ class SelectiveEvaluator(_SlotOwner):
 
     def _of(self, slot):
         """int64 [K, C + 1, C + 1] of one slot (index or case name), or of the sum over every slot."""
-        c = self.host_counts()
-        for one in c:
-            _counts3(one)
-        if slot is not None:
-            return c[self._slot_index(slot)]
-        return _sum_bins(c.reshape(c.shape[0], -1, c.shape[-1])).reshape(c.shape[1:])
+        return self._pick(self.host_counts(), slot, _counts3, lambda c: _sum_bins(c.reshape(c.shape[0], -1, c.shape[-1])).reshape(c.shape[1:]))
 
     def evaluator_counts(self):
         """The sum over the bins: Evaluator.host_counts() of the same maps, int64 [n, C + 1, C + 1]."""
@@ -1013,7 +1037,7 @@ class SelectiveEvaluator(_SlotOwner):
         risk over ALL bins (it does not depend on `min_bin`), rounded the same way; without it the summary is Evaluator.summary's, key for key."""
         s = summary_of(self.metrics(min_bin, slot, metric, nan_to_num, beta))
         if auc:
-            s["AURC"] = np.round(self.auc("risk", slot) * 100, 2) / 100.0
+            s["AURC"] = _round_percent(self.auc("risk", slot))
         return s
 
     def coverage_curve(self, metric=("mIoU",), slot=None, nan_to_num=None, beta=1):
@@ -1049,11 +1073,7 @@ class TemperatureSweep(_SlotOwner):
     def add(self, logits, labels, case=None, slots=None):
         """Sweep a batch's logits canvas [B, C, H, W] against its labels (one launch; no host sync, no allocation once the buffer exists)."""
         logits = _check_logits(logits)
-        with torch.cuda.device(logits.device):
-            buf = self._buffer(logits.device)
-        temperature_sweep(logits, labels, self.prep, self.temperatures, self.n_bins, buf, self.slots_for(logits.shape[0], case, slots))
-        self._taken(logits.shape[0], case, slots)
-        return self
+        return self._add(logits, logits.shape[0], case, slots, temperature_sweep, logits, labels, self.prep, self.temperatures, self.n_bins)
 
     def host(self):
         """The sweeps on the host (the ONE device-to-host copy of a fit): int64 numpy [n, J, 4, K], n = images added so far / cases."""
@@ -1061,10 +1081,7 @@ class TemperatureSweep(_SlotOwner):
 
     def _of(self, slot):
         """int64 [J, 4, K] of one slot (index or case name), or of the sum over every slot."""
-        h = self.host()
-        for one in h:
-            _sweep4(one)
-        return h.sum(0) if slot is None else h[self._slot_index(slot)]
+        return self._pick(self.host(), slot, _sweep4)
 
     def bins(self, j, slot=None):
         """Calibration's int64 [3, K] bins at temperature j: what reliability_of / ece_of / mce_of / risk_coverage_of take."""
@@ -1101,7 +1118,7 @@ MAX_TOPK = 8            # ranks of a top-k map (csrc/softmax_px.h TOPK_MAX: the 
 
 def check_topk(k, who="mmsa.evaluate"):
     """`k`, the number of ranks of a top-k map: an int in 1..MAX_TOPK."""
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= MAX_TOPK:
+    if not _is_int(k, 1, MAX_TOPK):
         raise ValueError(f"{who}: topk = {k!r}; 1..{MAX_TOPK} ranks are supported")
     return int(k)
 
@@ -1129,12 +1146,7 @@ def topk_counts(classes, labels, prep, counts=None, slots=None):
     K, B, H, W = (int(v) for v in classes.shape)
     C = prep.num_classes
     with torch.cuda.device(classes.device):
-        largs = prep.launch_args(labels, B, H, W, classes.device)
-        if counts is None:
-            n_slots = B if slots is None else max(int(s) for s in slots) + 1
-            counts = torch.zeros(n_slots, C, K + 1, dtype=torch.int64, device=classes.device)
-        _check_buffer(counts, "counts", (C, K + 1), classes.device)
-        tab = _slot_args(slots, B, counts.shape[0])
+        largs, counts, tab = _slot_launch(prep, labels, B, H, W, classes.device, counts, "counts", (C, K + 1), slots)
         lib.call("mmsa_eval_topk_u8", classes.data_ptr(), K, largs[0], B, H, W, largs[1], largs[2], largs[3], C, largs[4], largs[5], tab, counts.shape[0],
                  counts.data_ptr(), ops._stream())
     return counts
@@ -1161,7 +1173,7 @@ class TopKEvaluator(_SlotOwner):
     """Owns the rank counts of a top-k evaluation run, as Evaluator owns the confusion counts: int64 [n_slots, C, k + 1] on the device (`.counts`).
     `cases` / `images` / `device` as in Evaluator.  accuracy()[0] is Evaluator's aAcc of plane 0; mmsa.dist.allreduce_counts(te.counts) is the one collective of
     a multi-GPU run."""
-    _who, _read, _one, _attr, _pass = "TopKEvaluator", "accuracy()", "a TopKEvaluator", "counts", None
+    _who, _read, _one, _attr = "TopKEvaluator", "accuracy()", "a TopKEvaluator", "counts"
 
     def __init__(self, prep, k, cases=None, images=MAX_IMAGES, device=None):
         self.prep = prep
@@ -1177,20 +1189,14 @@ class TopKEvaluator(_SlotOwner):
         classes = _check_rank_planes(classes)
         if classes.shape[0] != self.k:
             raise RuntimeError(f"mmsa.TopKEvaluator: {classes.shape[0]} rank planes, this evaluator counts {self.k}")
-        B = int(classes.shape[1])
-        with torch.cuda.device(classes.device):
-            buf = self._buffer(classes.device)
-        topk_counts(classes, labels, self.prep, buf, self.slots_for(B, case, slots))
-        self._taken(B, case, slots)
-        return self
+        return self._add(classes, int(classes.shape[1]), case, slots, topk_counts, classes, labels, self.prep)
 
     def host_counts(self):
         """The counts on the host (the ONE device-to-host copy): int64 numpy [n, C, k + 1], n = images added so far / cases."""
         return self._host()
 
     def _of(self, slot):
-        c = self.host_counts()
-        return c.sum(0) if slot is None else c[self._slot_index(slot)]
+        return self._pick(self.host_counts(), slot)
 
     def accuracy(self, slot=None):
         """The top-j pixel accuracy for j = 1 .. k, float64 [k], over every slot or of one slot (index or case name)."""
@@ -1207,9 +1213,9 @@ class TopKEvaluator(_SlotOwner):
         with warnings.catch_warnings():
             warnings.simplefilter("ignore", RuntimeWarning)
             for j in range(self.k):
-                out[f"top{j + 1}"] = np.round(acc[j] * 100, 2) / 100.0
+                out[f"top{j + 1}"] = _round_percent(acc[j])
             for j in range(self.k):
-                out[f"mRecall{j + 1}"] = np.round(np.nanmean(rec[:, j]) * 100, 2) / 100.0
+                out[f"mRecall{j + 1}"] = _round_percent(np.nanmean(rec[:, j]))
         return out
 
 
@@ -1221,7 +1227,7 @@ _BOUNDARY_LDS = 65536
 
 
 def check_boundary_radius(radius, who="mmsa.evaluate"):
-    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= MAX_BOUNDARY_RADIUS:
+    if not _is_int(radius, 1, MAX_BOUNDARY_RADIUS):
         raise ValueError(f"{who}: radius = {radius!r}; 1..{MAX_BOUNDARY_RADIUS} pixels (Chebyshev) are supported")
     return int(radius)
 
@@ -1261,12 +1267,7 @@ def boundary_counts(pred, labels, prep, radius, border=False, counts=None, slots
     B, H, W = (int(v) for v in pred.shape)
     C = _check_boundary_classes(prep.num_classes)
     with torch.cuda.device(pred.device):
-        largs = prep.launch_args(labels, B, H, W, pred.device)
-        if counts is None:
-            n_slots = B if slots is None else max(int(s) for s in slots) + 1
-            counts = torch.zeros(n_slots, 4, C + 1, C + 1, dtype=torch.int64, device=pred.device)
-        _check_buffer(counts, "counts", (4, C + 1, C + 1), pred.device)
-        tab = _slot_args(slots, B, counts.shape[0])
+        largs, counts, tab = _slot_launch(prep, labels, B, H, W, pred.device, counts, "counts", (4, C + 1, C + 1), slots)
         lib.call("mmsa_eval_boundary_u8", pred.data_ptr(), largs[0], B, H, W, largs[1], largs[2], largs[3], C, largs[4], largs[5], tab, counts.shape[0],
                  radius, 1 if border else 0, counts.data_ptr(), ops._stream())
     return counts
@@ -1309,7 +1310,7 @@ class BoundaryEvaluator(_SlotOwner):
     2 * near_label + near_pred at Chebyshev `radius` (`boundary_counts`).  `cases` / `images` / `device` and `slots=` of add(): as for Evaluator.  Only
     host_counts() copies anything to the host; the trimap metrics and the Boundary IoU are formed from those integers in float64.  Across ranks:
     mmsa.dist.allreduce_counts(be.counts)."""
-    _who, _read, _one, _attr, _pass = "BoundaryEvaluator", "host_counts()", "a BoundaryEvaluator", "counts", None
+    _who, _read, _one, _attr = "BoundaryEvaluator", "host_counts()", "a BoundaryEvaluator", "counts"
 
     def __init__(self, prep, radius, border=False, cases=None, images=MAX_IMAGES, device=None):
         self.prep = prep
@@ -1325,20 +1326,14 @@ class BoundaryEvaluator(_SlotOwner):
     def add(self, pred, labels, case=None, slots=None):
         """Count a batch of stored class maps (one launch; no host sync, no allocation once the buffer exists)."""
         pred = _check_pred(pred)
-        B = int(pred.shape[0])
-        with torch.cuda.device(pred.device):
-            buf = self._buffer(pred.device)
-        boundary_counts(pred, labels, self.prep, self.radius, self.border, buf, self.slots_for(B, case, slots))
-        self._taken(B, case, slots)
-        return self
+        return self._add(pred, int(pred.shape[0]), case, slots, boundary_counts, pred, labels, self.prep, self.radius, self.border)
 
     def host_counts(self):
         """The counts on the host (the ONE device-to-host copy): int64 numpy [n, 4, C + 1, C + 1], n = images added so far / cases."""
         return self._host()
 
     def _of(self, slot):
-        c = self.host_counts()
-        return c.sum(0) if slot is None else c[self._slot_index(slot)]
+        return self._pick(self.host_counts(), slot)
 
     def evaluator_counts(self):
         """The sum over the zones: Evaluator.host_counts() of the same maps, int64 [n, C + 1, C + 1]."""
@@ -1368,7 +1363,7 @@ class BoundaryEvaluator(_SlotOwner):
             with np.errstate(divide="ignore", invalid="ignore"):
                 share = np.float64(band.sum()) / np.float64(c.sum())
             return OrderedDict(aAcc=whole["aAcc"], mIoU=whole["mIoU"], trimap_aAcc=tri["aAcc"], trimap_mIoU=tri["mIoU"],
-                               mBIoU=np.round(np.nanmean(self.boundary_iou(slot)) * 100, 2) / 100.0, band=np.round(share * 100, 2) / 100.0)
+                               mBIoU=_round_percent(np.nanmean(self.boundary_iou(slot))), band=_round_percent(share))
 
 
 # ---- Euclidean boundary evaluation: exact squared distance maps of the code maps, and what is counted from two of them (csrc/distance.hip) ----
@@ -1386,7 +1381,7 @@ _DISTANCE_SCRATCH = {}             # (device, stream) -> the uint16 row-run plan
 
 
 def check_distance_cap(cap, who="mmsa.evaluate"):
-    if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or not 1 <= int(cap) <= MAX_DISTANCE_CAP:
+    if not _is_int(cap, 1, MAX_DISTANCE_CAP):
         raise ValueError(f"{who}: cap = {cap!r}; 1..{MAX_DISTANCE_CAP} pixels are supported (cap^2 must fit the uint16 distance map)")
     return int(cap)
 
@@ -1397,7 +1392,7 @@ def euclidean_threshold(radius=None, radius2=None, who="mmsa.evaluate"):
     if (radius is None) == (radius2 is None):
         raise ValueError(f"{who}: radius= or radius2=, one of them")
     if radius2 is not None:
-        if isinstance(radius2, bool) or not isinstance(radius2, (int, np.integer)) or not 1 <= int(radius2) <= MAX_DISTANCE_CAP ** 2:
+        if not _is_int(radius2, 1, MAX_DISTANCE_CAP ** 2):
             raise ValueError(f"{who}: radius2 = {radius2!r}; an integer squared radius in 1..{MAX_DISTANCE_CAP ** 2} is expected")
         t = int(radius2)
         return t, math.isqrt(t - 1) + 1
@@ -1531,12 +1526,7 @@ def _d2_launch(entry, pred, labels, prep, d2_pred, d2_label, scalar, buf, name, 
     B, H, W = (int(v) for v in pred.shape)
     C = prep.num_classes
     with torch.cuda.device(pred.device):
-        largs = prep.launch_args(labels, B, H, W, pred.device)
-        if buf is None:
-            n_slots = B if slots is None else max(int(s) for s in slots) + 1
-            buf = torch.zeros(n_slots, *shape, dtype=torch.int64, device=pred.device)
-        _check_buffer(buf, name, shape, pred.device)
-        tab = _slot_args(slots, B, buf.shape[0])
+        largs, buf, tab = _slot_launch(prep, labels, B, H, W, pred.device, buf, name, shape, slots)
         lib.call(entry, pred.data_ptr(), largs[0], B, H, W, largs[1], largs[2], largs[3], C, largs[4], largs[5], tab, buf.shape[0], d2_pred.data_ptr(),
                  d2_label.data_ptr(), scalar, buf.data_ptr(), ops._stream())
     return buf
@@ -1549,7 +1539,7 @@ def boundary_counts_d2(pred, labels, prep, d2_pred, d2_label, t, counts=None, sl
     1 at [slot, 2 * near_label + near_pred, min(L, C), P].  d2_pred = boundary_distance(pred, cap, border, num_classes=C) and d2_label =
     boundary_distance(labels, cap, border, labels_prep=prep); t = floor(radius^2), an integer in 1..cap^2 (t = 2 is `boundary_counts` at radius 1, bit for
     bit; several radii are several of these launches over one pair of maps).  counts.sum(1) is `confusion(pred, labels, prep)`."""
-    if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 1 <= int(t) <= MAX_DISTANCE_CAP ** 2:
+    if not _is_int(t, 1, MAX_DISTANCE_CAP ** 2):
         raise ValueError(f"mmsa.evaluate: t = {t!r}; an integer squared radius in 1..{MAX_DISTANCE_CAP ** 2} is expected (floor(radius^2), at most cap^2 of the maps)")
     C = _check_euclidean_classes(prep.num_classes)
     return _d2_launch("mmsa_eval_boundary_d2", pred, labels, prep, d2_pred, d2_label, int(t), counts, "counts", (4, C + 1, C + 1), slots)
@@ -1609,7 +1599,7 @@ def boundary_f_of(hist, tolerance):
     float64 [...]: `boundary_f_curve_of` at that tolerance."""
     h = _displacement(hist)
     cap = h.shape[-1] - 2
-    if isinstance(tolerance, bool) or not isinstance(tolerance, (int, np.integer)) or not 1 <= int(tolerance) <= cap:
+    if not _is_int(tolerance, 1, cap):
         raise ValueError(f"mmsa.evaluate: tolerance = {tolerance!r}; an integer in 1..{cap} (the histogram's cap; tolerances count from 1) is expected")
     c = boundary_f_curve_of(h)
     return OrderedDict((k, v[..., int(tolerance) - 1]) for k, v in c.items() if k != "tolerance")
@@ -1671,10 +1661,13 @@ class EuclideanBoundaryEvaluator(BoundaryEvaluator):
         self._maps = {}         # (B, H, W, device, stream) -> (d2_pred, d2_label, scratch)
         self._init_buffer(device)
 
+    def _trailing_displacement(self):
+        return (2, self.prep.num_classes + 1, self.cap + 2)
+
     def _buffer(self, device):
         buf = super()._buffer(device)
         if self.with_displacement and self.displacement is None:
-            self.displacement = torch.zeros(self.n_slots, 2, self.prep.num_classes + 1, self.cap + 2, dtype=torch.int64, device=buf.device)
+            self.displacement = torch.zeros(self.n_slots, *self._trailing_displacement(), dtype=torch.int64, device=buf.device)
         return buf
 
     def _maps_for(self, B, H, W, device):
@@ -1694,16 +1687,17 @@ class EuclideanBoundaryEvaluator(BoundaryEvaluator):
         B, H, W = (int(v) for v in pred.shape)
         with torch.cuda.device(pred.device):
             self.prep.launch_args(labels, B, H, W, pred.device)      # the label side checked before the first launch
-            buf = self._buffer(pred.device)
-            d2p, d2l, scratch = self._maps_for(B, H, W, pred.device)
-            boundary_distance(pred, self.cap, self.border, num_classes=self.prep.num_classes, scratch=scratch, out=d2p)
-            boundary_distance(labels, self.cap, self.border, labels_prep=self.prep, size=(H, W), scratch=scratch, out=d2l)
-            use = self.slots_for(B, case, slots)
-            boundary_counts_d2(pred, labels, self.prep, d2p, d2l, self.radius2, buf, use)
-            if self.with_displacement:
-                boundary_displacement(pred, labels, self.prep, d2p, d2l, self.cap, self.displacement, use)
-        self._taken(B, case, slots)
-        return self
+            return self._add(pred, B, case, slots, self._launches, pred, labels, guard=False)      # this guard serves
+
+    def _launches(self, pred, labels, buf, use):
+        """The launches of one add(), in its device guard, into the slots `use` of both buffers."""
+        B, H, W = (int(v) for v in pred.shape)
+        d2p, d2l, scratch = self._maps_for(B, H, W, pred.device)
+        boundary_distance(pred, self.cap, self.border, num_classes=self.prep.num_classes, scratch=scratch, out=d2p)
+        boundary_distance(labels, self.cap, self.border, labels_prep=self.prep, size=(H, W), scratch=scratch, out=d2l)
+        boundary_counts_d2(pred, labels, self.prep, d2p, d2l, self.radius2, buf, use)
+        if self.with_displacement:
+            boundary_displacement(pred, labels, self.prep, d2p, d2l, self.cap, self.displacement, use)
 
     def reset(self):
         super().reset()
@@ -1714,14 +1708,10 @@ class EuclideanBoundaryEvaluator(BoundaryEvaluator):
         """The displacement histogram on the host: int64 numpy [n, 2, C + 1, cap + 2], n = images added so far / cases."""
         if not self.with_displacement:
             raise RuntimeError(f"mmsa.{self._who}: made with displacement=False: there is no displacement histogram (boundary F-score, Hausdorff percentiles)")
-        if self.displacement is None:
-            return np.zeros((0 if self.cases is None else self.n_slots, 2, self.prep.num_classes + 1, self.cap + 2), dtype=np.int64)
-        h = self.displacement.cpu().numpy()
-        return h[:self.used] if self.cases is None else h
+        return self._host("displacement", self._trailing_displacement())
 
     def _displacement_of(self, slot):
-        h = self.host_displacement()
-        return h.sum(0) if slot is None else h[self._slot_index(slot)]
+        return self._pick(self.host_displacement(), slot)
 
     def boundary_f(self, tolerance=None, slot=None):
         """`boundary_f_of` at `tolerance` (an integer in 1 .. cap, counted from 1; default: ceil(radius)), over every slot or
@@ -1743,7 +1733,7 @@ class EuclideanBoundaryEvaluator(BoundaryEvaluator):
         if self.with_displacement:
             with warnings.catch_warnings():
                 warnings.simplefilter("ignore", RuntimeWarning)
-                s["mBF"] = np.round(np.nanmean(self.boundary_f(slot=slot)["F"]) * 100, 2) / 100.0
+                s["mBF"] = _round_percent(np.nanmean(self.boundary_f(slot=slot)["F"]))
             s["HD95"] = self.distance_percentile(0.95, slot)["hd"]
         s["radius"], s["radius2"], s["metric"] = self.radius, self.radius2, self.metric
         return s

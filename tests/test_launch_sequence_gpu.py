@@ -219,3 +219,186 @@ def test_launches_of_a_plan(plan_calls, monkeypatch, case):
 
 def test_every_plan_case_has_a_list(plan_calls):
     assert sorted(plan_calls) == sorted(PLAN_EXPECTED)
+
+
+# ---- the same recorder on the count passes of mmsa.evaluate, at entry and at owner level: every entry that adds into an int64 [n_slots, ...] buffer, and the
+# add() of every owner of such a buffer.  The lists were written by reading mmsa/evaluate.py at the commit before the shared launch preamble and the shared
+# add(), and confirmed by running this file on that commit (an MI355X: every case passed there before the code was touched).  Five classes, two 24 x 40 maps,
+# the labels 12 x 20 and read through the resize tables; 4 bins, 3 temperatures, 3 rank planes, Chebyshev radius 2, Euclidean radius 2 at cap 4.
+D = "mmsa_boundary_distance_u8"
+EVAL_ENTRIES = {                                       # entry -> the library call it makes
+    "confusion": "mmsa_eval_confusion_u8",
+    "calibration": "mmsa_eval_calibration",
+    "selective": "mmsa_eval_selective",
+    "temperature_sweep": "mmsa_temperature_sweep_nchw",
+    "topk_counts": "mmsa_eval_topk_u8",
+    "boundary_counts": "mmsa_eval_boundary_u8",
+    "boundary_counts_d2": "mmsa_eval_boundary_d2",
+    "boundary_displacement": "mmsa_eval_boundary_displacement",
+}
+EVAL_EXPECTED = {
+    "confusion": ["torch.zeros", "mmsa_eval_confusion_u8"],
+    "confusion_buffer": ["mmsa_eval_confusion_u8"],
+    "calibration": ["torch.zeros", "mmsa_eval_calibration"],
+    "calibration_buffer": ["mmsa_eval_calibration"],
+    "selective": ["torch.zeros", "mmsa_eval_selective"],
+    "selective_buffer": ["mmsa_eval_selective"],
+    "temperature_sweep": ["torch.zeros", "mmsa_temperature_sweep_nchw"],
+    "temperature_sweep_buffer": ["mmsa_temperature_sweep_nchw"],
+    "topk_counts": ["torch.zeros", "mmsa_eval_topk_u8"],
+    "topk_counts_buffer": ["mmsa_eval_topk_u8"],
+    "boundary_counts": ["torch.zeros", "mmsa_eval_boundary_u8"],
+    "boundary_counts_buffer": ["mmsa_eval_boundary_u8"],
+    "boundary_counts_d2": ["torch.zeros", "mmsa_eval_boundary_d2"],
+    "boundary_counts_d2_buffer": ["mmsa_eval_boundary_d2"],
+    "boundary_displacement": ["torch.zeros", "mmsa_eval_boundary_displacement"],
+    "boundary_displacement_buffer": ["mmsa_eval_boundary_displacement"],
+    "boundary_distance": ["torch.empty", D],                                            # the map; the scratch plane of the stream exists
+    "boundary_distance_buffers": [D],
+}
+OWNER_EXPECTED = {                                     # owner -> what a warm add() records; the first add of an owner made without device= has "torch.zeros" in front
+    "Evaluator": ["mmsa_eval_confusion_u8"],
+    "Calibration": ["mmsa_eval_calibration"],
+    "SelectiveEvaluator": ["mmsa_eval_selective"],
+    "TemperatureSweep": ["mmsa_temperature_sweep_nchw"],
+    "TopKEvaluator": ["mmsa_eval_topk_u8"],
+    "BoundaryEvaluator": ["mmsa_eval_boundary_u8"],
+}
+EUCLIDEAN_EXPECTED = {
+    "first": 3 * ["torch.empty"] + [D, D, "mmsa_eval_boundary_d2", "mmsa_eval_boundary_displacement"],      # the distance maps and the scratch of a shape
+    "second": [D, D, "mmsa_eval_boundary_d2", "mmsa_eval_boundary_displacement"],
+    "first_no_device": 2 * ["torch.zeros"] + 3 * ["torch.empty"] + [D, D, "mmsa_eval_boundary_d2", "mmsa_eval_boundary_displacement"],
+    "first_no_displacement": 3 * ["torch.empty"] + [D, D, "mmsa_eval_boundary_d2"],
+    "first_no_device_no_displacement": ["torch.zeros"] + 3 * ["torch.empty"] + [D, D, "mmsa_eval_boundary_d2"],
+    "second_no_displacement": [D, D, "mmsa_eval_boundary_d2"],
+}
+
+
+@pytest.fixture(scope="module")
+def count_inputs():
+    """The maps of the count cases, with everything a first call uploads (the label LUT, the label tables, both code LUTs) and the scratch plane of the
+    distance launch on the device before anything is recorded: one warm call per entry."""
+    import mmsa.evaluate as E
+    g = torch.Generator().manual_seed(23)
+    C = 5
+    lp = E.LabelPrep(C, resize=dict(seg_scale=(40, 24), keep_ratio=False))
+    pred = torch.randint(0, C, (2, 24, 40), generator=g, dtype=torch.uint8).to(DEV)
+    lab = torch.randint(0, C + 1, (2, 12, 20), generator=g, dtype=torch.uint8)
+    lab[torch.rand(2, 12, 20, generator=g) < 0.1] = 255
+    lab = lab.to(DEV)
+    conf = torch.rand(2, 24, 40, generator=g).to(DEV)
+    logits = torch.randn(2, C, 24, 40, generator=g).to(DEV)
+    planes = torch.randint(0, C, (3, 2, 24, 40), generator=g, dtype=torch.uint8).to(DEV)
+    d2p = E.boundary_distance(pred, 4, num_classes=C)
+    d2l = E.boundary_distance(lab, 4, labels_prep=lp, size=(24, 40))
+    calls = dict(
+        confusion=lambda buf=None, slots=None: E.confusion(pred, lab, lp, counts=buf, slots=slots),
+        calibration=lambda buf=None, slots=None: E.calibration(pred, conf, lab, lp, bins=4, cal=buf, slots=slots),
+        selective=lambda buf=None, slots=None: E.selective(pred, conf, lab, lp, bins=4, counts=buf, slots=slots),
+        temperature_sweep=lambda buf=None, slots=None: E.temperature_sweep(logits, lab, lp, (0.5, 1, 2), bins=4, out=buf, slots=slots),
+        topk_counts=lambda buf=None, slots=None: E.topk_counts(planes, lab, lp, counts=buf, slots=slots),
+        boundary_counts=lambda buf=None, slots=None: E.boundary_counts(pred, lab, lp, 2, counts=buf, slots=slots),
+        boundary_counts_d2=lambda buf=None, slots=None: E.boundary_counts_d2(pred, lab, lp, d2p, d2l, 4, counts=buf, slots=slots),
+        boundary_displacement=lambda buf=None, slots=None: E.boundary_displacement(pred, lab, lp, d2p, d2l, 4, hist=buf, slots=slots),
+    )
+    for fn in calls.values():
+        fn()
+    owners = dict(
+        Evaluator=(lambda **kw: E.Evaluator(lp, **kw), (pred, lab)),
+        Calibration=(lambda **kw: E.Calibration(lp, bins=4, **kw), (pred, conf, lab)),
+        SelectiveEvaluator=(lambda **kw: E.SelectiveEvaluator(lp, bins=4, **kw), (pred, conf, lab)),
+        TemperatureSweep=(lambda **kw: E.TemperatureSweep(lp, (0.5, 1, 2), bins=4, **kw), (logits, lab)),
+        TopKEvaluator=(lambda **kw: E.TopKEvaluator(lp, 3, **kw), (planes, lab)),
+        BoundaryEvaluator=(lambda **kw: E.BoundaryEvaluator(lp, 2, **kw), (pred, lab)),
+        EuclideanBoundaryEvaluator=(lambda **kw: E.EuclideanBoundaryEvaluator(lp, 2, cap=4, **kw), (pred, lab)),
+    )
+    torch.cuda.synchronize()
+    return dict(E=E, C=C, lp=lp, pred=pred, lab=lab, calls=calls, owners=owners)
+
+
+@pytest.mark.parametrize("entry", sorted(EVAL_ENTRIES))
+def test_launches_of_a_count_entry(count_inputs, monkeypatch, entry):
+    """Without a buffer: the zeroed buffer, then the launch; with one: the launch alone, and a second launch into it doubles it."""
+    call, got = count_inputs["calls"][entry], {}
+    got[entry] = _recorded(monkeypatch, None, lambda: got.setdefault("one", call()))
+    buf = torch.zeros_like(got["one"])
+    got[entry + "_buffer"] = _recorded(monkeypatch, None, lambda: got.setdefault("same", call(buf)))
+    for key in (entry, entry + "_buffer"):
+        print(f"{key}: {got[key]}")
+        assert got[key] == EVAL_EXPECTED[key]
+    assert got["same"] is buf and torch.equal(buf, got["one"]) and int(buf.sum()) > 0
+    call(buf)
+    assert torch.equal(buf, 2 * got["one"])
+    both = call(torch.zeros_like(buf[:1]), [0, 0])                     # both images into slot 0
+    assert torch.equal(both[0], got["one"].sum(0))
+
+
+def test_launches_of_a_distance_map(count_inputs, monkeypatch):
+    E, pred = count_inputs["E"], count_inputs["pred"]
+    got, keep = {}, {}
+    got["boundary_distance"] = _recorded(monkeypatch, None, lambda: keep.setdefault("one", E.boundary_distance(pred, 4, num_classes=5)))
+    out, scratch = torch.empty_like(keep["one"]), torch.empty_like(keep["one"])
+    got["boundary_distance_buffers"] = _recorded(monkeypatch, None, lambda: E.boundary_distance(pred, 4, num_classes=5, out=out, scratch=scratch))
+    for key, names in got.items():
+        print(f"{key}: {names}")
+        assert names == EVAL_EXPECTED[key]
+    assert torch.equal(out, keep["one"])
+
+
+def test_every_count_case_has_a_list(count_inputs):
+    assert sorted(count_inputs["calls"]) == sorted(EVAL_ENTRIES)
+    assert sorted(EVAL_EXPECTED) == sorted(list(EVAL_ENTRIES) + [e + "_buffer" for e in EVAL_ENTRIES] + ["boundary_distance", "boundary_distance_buffers"])
+    assert all(EVAL_EXPECTED[e + "_buffer"] == [name] for e, name in EVAL_ENTRIES.items())
+    assert sorted(count_inputs["owners"]) == sorted(list(OWNER_EXPECTED) + ["EuclideanBoundaryEvaluator"])
+
+
+def _buffers(owner):
+    """The device buffers of an owner: `.bins` of a Calibration, `.counts` of the others, and `.displacement` where there is one."""
+    first = owner.bins if type(owner).__name__ == "Calibration" else owner.counts
+    return [b for b in (first, getattr(owner, "displacement", None)) if b is not None]
+
+
+def _owner_case(count_inputs, monkeypatch, name, warm, first_with_device, first_without, **kw):
+    """An owner's add() four ways: made with device= (the first and a second add, then two adds into named slots), and made without."""
+    make, args = count_inputs["owners"][name]
+    rec = lambda o, **k: _recorded(monkeypatch, None, lambda: o.add(*args, **k))
+    o = make(device=DEV, **kw)
+    got = [rec(o)]
+    assert o.used == 2
+    got.append(rec(o))
+    assert o.used == 4
+    print(f"{name} {kw} device=: {got}")
+    assert got == [first_with_device, warm]
+    per_image = [b.clone() for b in _buffers(o)]
+    for b in per_image:
+        assert int(b[:2].sum()) > 0 and torch.equal(b[2:4], b[:2]) and int(b[4:].sum()) == 0      # the second batch went to the next two slots
+    s = make(device=DEV, **kw)
+    s.add(*args)                                                                                   # the distance maps of the shape
+    s.reset()
+    assert rec(s, slots=[0, 0]) == warm and s.used == 0
+    one = [b.clone() for b in _buffers(s)]
+    assert rec(s, slots=[0, 0]) == warm and s.used == 0
+    for b, b1, p in zip(_buffers(s), one, per_image):
+        assert torch.equal(b, 2 * b1) and torch.equal(b1[0], p[:2].sum(0)) and int(b1[1:].sum()) == 0
+    n = make(**kw)
+    got = [rec(n), rec(n)]
+    print(f"{name} {kw} no device: {got}")
+    assert got == [first_without, warm] and n.used == 4
+    for b, p in zip(_buffers(n), per_image):
+        assert torch.equal(b, p)
+
+
+@pytest.mark.parametrize("name", sorted(OWNER_EXPECTED))
+def test_launches_of_an_owner(count_inputs, monkeypatch, name):
+    warm = OWNER_EXPECTED[name]
+    _owner_case(count_inputs, monkeypatch, name, warm, warm, ["torch.zeros"] + warm)
+
+
+@pytest.mark.parametrize("displacement", [True, False])
+def test_launches_of_the_euclidean_owner(count_inputs, monkeypatch, displacement):
+    x = EUCLIDEAN_EXPECTED
+    if displacement:
+        _owner_case(count_inputs, monkeypatch, "EuclideanBoundaryEvaluator", x["second"], x["first"], x["first_no_device"])
+    else:
+        _owner_case(count_inputs, monkeypatch, "EuclideanBoundaryEvaluator", x["second_no_displacement"], x["first_no_displacement"],
+                    x["first_no_device_no_displacement"], displacement=False)
