@@ -16,6 +16,27 @@
 #pragma clang fp contract(off)
 #include "slide_taps.h"   // WindowTable, the tap arithmetic and the two-stage pixel of the rescaled class map (shared with augment.hip)
 #include "softmax_px.h"   // the softmax of the confidence variants (shared with augment.hip)
+#include "slide_pixel.h"  // the pixel of the frame-size class-map kernels
+
+// The file by topic: what the variants of a class map write; the canvas path's kernels, each with its entry; the crop; the frame-size class maps (one pixel,
+// csrc/slide_pixel.h); the rescaled ones (one pixel, slide_resized_pixel); the host side of the one-pass entries.  Where a definition stands does not touch a
+// kernel's instruction stream: regrouping the file left every stream as it was (profiles/slide_pixel_template_isa.txt).
+
+// ---- confidence maps: the probability of the predicted class next to every class map, conf[b, y, x] = max_c P[b, c, y, x] with P the probabilities of
+// EncoderDecoder.inference (F.softmax(seg_logit, dim=1), ED:449,460), written by the launch that writes the map.  The arithmetic is csrc/softmax_px.h:
+// m = max_c x_c; s = e_0, s += e_c in class order, e_c = expf(x_c - m); conf = expf(m - m) / s -- P at the first maximum, which is the largest P.
+// ---- tempered confidence: softmax(x / T) in place of softmax(x) -- `it` = float32(1 / float64(T)) from the host, and every exponential is softmax_px_exp_t
+// (csrc/softmax_px.h: ONE more float32 product, exact at it == 1.0f, where the `_t` kernels are their siblings bit for bit).  The class map does not depend on T > 0.
+// ---- uncertainty maps: the top-2 margin or the entropy score (csrc/softmax_px.h: `kind` SCORE_MARGIN / SCORE_ENTROPY) in the confidence's place, float32
+// [B, Ho, Wo] in [0, 1], higher = more certain, 0 where the map is 255 -- so that csrc/conf_bin.h and everything behind it take it unchanged.  Both are formed
+// from the float32 probabilities p_c, the same operations in the canvas kernel (which reads p_c) and in the one-pass kernels (which form p_c = e_c / s of
+// softmax(x * it) themselves: `it` is always an argument, its product exact at 1.0f): bit for bit the same score.
+// ---- top-k maps: the first K classes of every pixel and their probabilities (csrc/softmax_px.h: TopkPx<S>, comparisons and moves on the float32 probabilities
+// p_c the confidence paths form), classes uint8 / probs float32 [K, B, Ho, Wo], rank-major: plane 0 of the classes IS the class map, plane 0 of the
+// probabilities IS the confidence map, and probs[0] - probs[1] is the top-2 margin, bit for bit.  The rank list lives in registers (S = 2 / 4 / 8 slots, the
+// smallest that holds K: the predicates of the unrolled insert are paid per class).
+
+// ---- the canvas path: one pass over a [B, C, H, W] canvas each, HBM-bound
 
 __global__ __launch_bounds__(256) void bilinear_accum_kernel(const float* __restrict__ src, int C, int hs, int ws, long sstrideB,
                                                              float* __restrict__ dst, int Hd, int Wd, int y0, int x0, int hc, int wc,
@@ -89,6 +110,118 @@ extern "C" int mmsa_argmax_nchw(const float* x, unsigned char* out, int B, int C
   return MMSA_OK;
 }
 
+// argmax_nchw_kernel that also writes the maximum: on the probabilities of the canvas paths (mmsa_softmax_flip_accum_nchw), the confidence map
+// max_c P[b, c, y, x] of ED:449,460 next to the class map, from one read of the canvas.
+__global__ __launch_bounds__(256) void argmax_max_nchw_kernel(const float* __restrict__ x, unsigned char* __restrict__ out, float* __restrict__ maxval, int C,
+                                                              long HW, long total) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;   // b * HW + p
+  if (i >= total) return;
+  const long b = i / HW, p = i - b * HW;
+  const float* xp = x + b * C * HW + p;
+  float best = xp[0];
+  int bi = 0;
+  for (int c = 1; c < C; ++c) {
+    const float v = xp[(long)c * HW];
+    if (v > best) { best = v; bi = c; }
+  }
+  out[i] = (unsigned char)bi;
+  maxval[i] = best;
+}
+
+extern "C" int mmsa_argmax_max_nchw(const float* x, unsigned char* out, float* maxval, int B, int C, long HW, hipStream_t stream) {
+  MMSA_CHECK_ARG(x && out && maxval && B > 0 && C > 0 && C <= 256 && HW > 0, "argmax_max_nchw: bad args (C <= 256 for the uint8 map)");
+  const long total = (long)B * HW;
+  hipLaunchKernelGGL(argmax_max_nchw_kernel, dim3(cdiv(total, 256)), dim3(256), 0, stream, x, out, maxval, C, HW, total);
+  MMSA_CHECK_LAUNCH("argmax_max_nchw");
+  return MMSA_OK;
+}
+
+// argmax_max_nchw_kernel with the score in the maximum's place: on a canvas of probabilities (one view's, or the mean over augmented views).  `bi` is the
+// first maximum of the probabilities; where the logits' argmax is a later class of the same probability, p[bi] and p2 are the same two values.
+__global__ __launch_bounds__(256) void argmax_score_nchw_kernel(const float* __restrict__ x, unsigned char* __restrict__ out, float* __restrict__ score, int C,
+                                                                long HW, long total, int kind, float ilc) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;   // b * HW + p
+  if (i >= total) return;
+  const long b = i / HW, p = i - b * HW;
+  const float* xp = x + b * C * HW + p;
+  float best = xp[0];
+  int bi = 0;
+  for (int c = 1; c < C; ++c) {
+    const float v = xp[(long)c * HW];
+    if (v > best) { best = v; bi = c; }
+  }
+  out[i] = (unsigned char)bi;
+  float sa = 0.f, spb = 0.f;
+  bool snone = true;
+  for (int c = 0; c < C; ++c) score_px_class(kind, bi, c, xp[(long)c * HW], sa, spb, snone);
+  score[i] = score_px_finish(kind, sa, spb, snone, ilc);
+}
+
+#define MMSA_CHECK_SCORE_KIND(name, kind) MMSA_CHECK_ARG((kind) == SCORE_MARGIN || (kind) == SCORE_ENTROPY, "%s: kind %d is neither 1 (top-2 margin) nor 2 (entropy score)", name, kind)
+
+extern "C" int mmsa_argmax_score_nchw(const float* prob, unsigned char* out, float* score, int B, int C, int H, int W, int kind, float inv_log_c,
+                                      hipStream_t stream) {
+  MMSA_CHECK_ARG(prob && out && score && B > 0 && C > 0 && C <= 256 && H > 0 && W > 0, "argmax_score_nchw: bad args (C <= 256 for the uint8 map)");
+  MMSA_CHECK_SCORE_KIND("argmax_score_nchw", kind);
+  MMSA_CHECK_ARG(inv_log_c >= 0.f && inv_log_c < INFINITY, "argmax_score_nchw: inv_log_c must be finite and not negative (1 / log C; 0 for one class)");
+  const long HW = (long)H * W, total = (long)B * HW;
+  hipLaunchKernelGGL(argmax_score_nchw_kernel, dim3(cdiv(total, 256)), dim3(256), 0, stream, prob, out, score, C, HW, total, kind, inv_log_c);
+  MMSA_CHECK_LAUNCH("argmax_score_nchw");
+  return MMSA_OK;
+}
+
+#define MMSA_CHECK_TOPK(name, K) MMSA_CHECK_ARG((K) >= 1 && (K) <= TOPK_MAX, "%s: K = %d; 1..%d ranks are supported (the rank list of a pixel is kept in registers)", name, K, TOPK_MAX)
+#define TOPK_DISPATCH(K, LAUNCH) \
+  do {                           \
+    if ((K) <= 2) LAUNCH(2);     \
+    else if ((K) <= 4) LAUNCH(4); \
+    else LAUNCH(8);              \
+  } while (0)
+
+// argmax_score_nchw_kernel with the rank list in the score's place: on a canvas of probabilities (one view's, or the mean over augmented views).  `first` NULL:
+// bi = the first maximum of the probabilities (the augmented path's map); else bi = first[i], the map of the one-view canvas path, which is the argmax of the
+// LOGITS (two logits can round to one probability, and the later one may be the map's).  A lane reads first[i] before it writes classes[i]: `first` may be plane 0.
+template <int S>
+__global__ __launch_bounds__(256) void argmax_topk_nchw_kernel(const float* __restrict__ x, const unsigned char* first, unsigned char* classes,
+                                                               float* __restrict__ probs, int C, long HW, long total, int K) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;   // b * HW + p
+  if (i >= total) return;
+  const long b = i / HW, p = i - b * HW;
+  const float* xp = x + b * C * HW + p;
+  int bi = 0;
+  if (first) {
+    bi = first[i];
+    if (bi >= C) {      // 255 = uncovered (any byte that is no class of the canvas is treated alike)
+      topk_px_store_none(classes, probs, total, i, K, 0);
+      return;
+    }
+  } else {
+    float best = xp[0];
+    for (int c = 1; c < C; ++c) {
+      const float v = xp[(long)c * HW];
+      if (v > best) { best = v; bi = c; }
+    }
+  }
+  TopkPx<S> tk;
+  topk_px_init(tk);
+  for (int c = 0; c < C; ++c) topk_px_class(tk, bi, c, xp[(long)c * HW]);
+  topk_px_store(tk, classes, probs, total, i, K, 0);
+}
+
+extern "C" int mmsa_argmax_topk_nchw(const float* prob, const unsigned char* first, unsigned char* classes, float* probs, int B, int C, int H, int W, int K,
+                                     hipStream_t stream) {
+  MMSA_CHECK_ARG(prob && classes && probs, "argmax_topk_nchw: prob, classes and probs are required");
+  MMSA_CHECK_ARG(C > 0 && C <= 255, "argmax_topk_nchw: %d classes; 1..255 are supported (255 is the byte of a rank without a class)", C);
+  MMSA_CHECK_TOPK("argmax_topk_nchw", K);
+  MMSA_CHECK_ARG(B > 0 && H > 0 && W > 0, "argmax_topk_nchw: bad args");
+  const long HW = (long)H * W, total = (long)B * HW;
+#define TOPK_LAUNCH(S) hipLaunchKernelGGL(argmax_topk_nchw_kernel<S>, dim3(cdiv(total, 256)), dim3(256), 0, stream, prob, first, classes, probs, C, HW, total, K)
+  TOPK_DISPATCH(K, TOPK_LAUNCH);
+#undef TOPK_LAUNCH
+  MMSA_CHECK_LAUNCH("argmax_topk_nchw");
+  return MMSA_OK;
+}
+
 // ---- crop extraction of slide inference (ED:205-212: crop_img = img[:, :, y1:y2, x1:x2]) as one launch for a batch of windows:
 // dst[k] = src[b_k, :, y0_k : y0_k + hc, x0_k : x0_k + wc].  The window table travels by value in the launch arguments.
 __global__ __launch_bounds__(256) void crop_batch_kernel(const float* __restrict__ src, int C, int H, int W, float* __restrict__ dst,
@@ -128,9 +261,7 @@ extern "C" int mmsa_crop_batch_nchw(const float* src, int B, int C, int H, int W
 // the whole-image `resize x4 + argmax` of ED:90-94,477.  Pixels no window covers make the call fail (ED:220 asserts the same).
 __global__ __launch_bounds__(256) void slide_argmax_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
                                                            int H, int W, int hc, int wc, float rh, float rw, WindowTable wt, int* __restrict__ uncovered) {
-#define SLIDE_Y blockIdx.y
-#define SLIDE_EXIT return
-#include "slide_pixel.inc"
+  slide_pixel<PX_MAP>(logits, C, hs, ws, out, nullptr, H, W, hc, wc, rh, rw, wt, uncovered, blockIdx.y);
 }
 
 // slide_argmax_kernel + the confusion counts of its class map in the same pass (csrc/evaluate.hip does the same from a stored map): the workgroup's
@@ -149,36 +280,86 @@ __global__ __launch_bounds__(256) void slide_argmax_eval_kernel(const float* __r
   unsigned* hist = eval_lds;
   const int row1 = min(H, ((int)blockIdx.y + 1) * SLIDE_EVAL_ROWS);
   for (int row = (int)blockIdx.y * SLIDE_EVAL_ROWS; row < row1; ++row) {
-#define SLIDE_EVAL 1
-#define SLIDE_Y row
-#define SLIDE_EXIT continue
-#include "slide_pixel.inc"
+    // the lanes with x >= W and the 255 pixels leave the pixel, not the kernel: the flush below has a barrier
+    slide_pixel<PX_MAP, false, false, 2, true>(logits, C, hs, ws, out, nullptr, H, W, hc, wc, rh, rw, wt, uncovered, row, nullptr, 1.f, 0, 0.f, 0, 0, hist, lut_s, &ev);
   }
   eval_hist_flush(eval_lds, ev.counts + (long)es.s[blockIdx.z] * nbins, nbins);
 }
 
-// (mmsa_slide_argmax: at the end of the file, with its siblings and the launcher they share)
-extern "C" int mmsa_slide_argmax_eval(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out /* or NULL */,
-                                      int B, int H, int W, int hc, int wc, int* uncovered, const unsigned char* label, int Hl, int Wl,
-                                      const unsigned char* lut, const int* ymap, const int* xmap, const int* slots /* HOST [B] */, int n_slots,
-                                      int64_t* counts, hipStream_t stream) {
-  MMSA_CHECK_ARG(logits && uncovered && hs > 0 && ws > 0 && hc > 0 && wc > 0 && B > 0 && H <= 65535 && B <= 65535, "slide_argmax_eval: bad args");
-  EvalSlots es;
-  int rc = eval_check("slide_argmax_eval", label, B, H, W, Hl, Wl, lut, C, ymap, xmap, slots, n_slots, counts, es);
-  if (rc) return rc;
-  WindowTable wt;
-  rc = fill_windows(wt, windows, n, B, H, W, hc, wc, "slide_argmax_eval");
-  if (rc) return rc;
-  const EvalLabel ev = {label, lut, ymap, xmap, (unsigned long long*)counts, Hl, Wl, C};
-  hipLaunchKernelGGL(slide_argmax_eval_kernel, dim3(cdiv(W, 256), cdiv(H, SLIDE_EVAL_ROWS), B), dim3(256), (size_t)(C + 1) * (C + 1) * 4 + 256, stream, logits, C, hs, ws, out,
-                     H, W, hc, wc, (float)hs / (float)hc, (float)ws / (float)wc, wt, uncovered, ev, es);
-  MMSA_CHECK_LAUNCH("slide_argmax_eval");
-  return MMSA_OK;
+// slide_argmax_kernel + the confidence map: conf[b, y, x] = max_c softmax(preds / count)[c], the probability of the class the map names (ED:449,460).  The
+// sum of the exponentials needs the maximum first, so the pixel's C values are needed twice; two forms (slide_pixel.h: LDS), chosen by measurement
+// (profiles/confidence.txt, profiles/slide_pixel_template.txt):
+//   slide_argmax_conf_lds_kernel : the first pass keeps them in a per-lane LDS column [c][lane], as aug_argmax_kernel does -- C * 256 floats of dynamic LDS,
+//                                  so C <= SLIDE_CONF_LDS_CLASSES = 64 (64 KiB); the faster form -- + 36 / + 88 us over the plain kernel where the other costs
+//                                  + 70 / + 248 us (two 1024 x 1024 maps / the six-window 1080 x 1920 frame, 25 classes; profiles/slide_pixel_template.txt) --
+//                                  and the one the entry takes wherever it fits;
+//   slide_argmax_conf_kernel     : a second pass recomputes them (the same operations on the same inputs, the same bits): no LDS, any C the map allows.
+// The recomputing form takes 118 registers, the LDS form 130 (profiles/slide_pixel_template_isa.txt).  Bit for bit max over C of
+// mmsa_softmax_flip_accum_nchw on the canvas path's logits, either way.
+#define SLIDE_CONF_LDS_CLASSES 64
+__global__ __launch_bounds__(256) void slide_argmax_conf_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
+                                                                float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, WindowTable wt,
+                                                                int* __restrict__ uncovered) {
+  slide_pixel<PX_CONF>(logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, wt, uncovered, blockIdx.y);
+}
+
+__global__ __launch_bounds__(256) void slide_argmax_conf_lds_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
+                                                                    float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, WindowTable wt,
+                                                                    int* __restrict__ uncovered) {
+  extern __shared__ float conf_lds[];      // the per-lane column [c][lane]
+  slide_pixel<PX_CONF, true>(logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, wt, uncovered, blockIdx.y, conf_lds + threadIdx.x);
+}
+
+// the two confidence kernels with the inverse temperature `it`
+__global__ __launch_bounds__(256) void slide_argmax_conf_t_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
+                                                                  float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, WindowTable wt,
+                                                                  int* __restrict__ uncovered, float it) {
+  slide_pixel<PX_CONF, false, true>(logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, wt, uncovered, blockIdx.y, nullptr, it);
+}
+
+__global__ __launch_bounds__(256) void slide_argmax_conf_lds_t_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
+                                                                      float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, WindowTable wt,
+                                                                      int* __restrict__ uncovered, float it) {
+  extern __shared__ float conf_lds[];      // the per-lane column [c][lane]
+  slide_pixel<PX_CONF, true, true>(logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, wt, uncovered, blockIdx.y, conf_lds + threadIdx.x, it);
+}
+
+// slide_argmax_kernel + the score map, in the two forms of the confidence (slide_pixel.h: PX_SCORE): the per-lane LDS column up to SLIDE_CONF_LDS_CLASSES
+// classes -- written with x_c by the class-map pass, overwritten with e_c by the sum pass, read once more for p_c = e_c / s -- and three recomputing passes
+// above that (65 .. 255 classes; slow, and allowed to be).
+__global__ __launch_bounds__(256) void slide_argmax_score_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
+                                                                 float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, WindowTable wt,
+                                                                 int* __restrict__ uncovered, int kind, float it, float ilc) {
+  slide_pixel<PX_SCORE, false, true>(logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, wt, uncovered, blockIdx.y, nullptr, it, kind, ilc);
+}
+
+__global__ __launch_bounds__(256) void slide_argmax_score_lds_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
+                                                                     float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, WindowTable wt,
+                                                                     int* __restrict__ uncovered, int kind, float it, float ilc) {
+  extern __shared__ float conf_lds[];      // the per-lane column [c][lane]
+  slide_pixel<PX_SCORE, true, true>(logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, wt, uncovered, blockIdx.y, conf_lds + threadIdx.x, it, kind, ilc);
+}
+
+// slide_argmax_kernel + the rank planes, in the two forms of the score (slide_pixel.h: PX_TOPK): the per-lane LDS column up to SLIDE_CONF_LDS_CLASSES
+// classes, three recomputing passes above that (65 .. 255 classes).  `out` / `conf` are the planes [K, B, H, W], `plane` = B * H * W.
+template <int S>
+__global__ __launch_bounds__(256) void slide_argmax_topk_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
+                                                                float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, WindowTable wt,
+                                                                int* __restrict__ uncovered, int K, long plane, float it) {
+  slide_pixel<PX_TOPK, false, true, S>(logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, wt, uncovered, blockIdx.y, nullptr, it, 0, 0.f, K, plane);
+}
+
+template <int S>
+__global__ __launch_bounds__(256) void slide_argmax_topk_lds_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
+                                                                    float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, WindowTable wt,
+                                                                    int* __restrict__ uncovered, int K, long plane, float it) {
+  extern __shared__ float conf_lds[];      // the per-lane column [c][lane]
+  slide_pixel<PX_TOPK, true, true, S>(logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, wt, uncovered, blockIdx.y, conf_lds + threadIdx.x, it, 0, 0.f, K, plane);
 }
 
 // ---- class map of a frame at a RESCALED size in one pass (ED:227-233, 314-325, 349-360, 393-414 + ED:449,477): what `rescale=True` adds to the
 // canvas above -- a second bilinear resize (align_corners=False) of the averaged logits to Hd x Wd, then the crop [:Hcut, :Wcut] -- before the argmax:
-//   canvas[c, y, x]  = (sum over covering windows, in window order, of bilinear(logits_k -> hc x wc)[c]) / count       (slide_pixel.inc)
+//   canvas[c, y, x]  = (sum over covering windows, in window order, of bilinear(logits_k -> hc x wc)[c]) / count       (slide_pixel.h)
 //   resized[c, Y, X] = bilinear_{align_corners=False}(canvas -> Hd x Wd)                                                (bilinear_accum_kernel, write mode)
 //   out[Y, X]        = first argmax_c resized[c, Y, X]
 // with neither the [B, C, H, W] canvas nor the [B, C, Hd, Wd] one in memory.  An output pixel reads a 2 x 2 block of canvas pixels (its four taps; on a
@@ -188,7 +369,7 @@ extern "C" int mmsa_slide_argmax_eval(const float* logits, int n, int C, int hs,
 // windows, gets 255 and is counted in `uncovered`.
 // The pixel (TwoStagePixel: set-up and value; why a tap keeps four windows in registers): csrc/slide_taps.h.
 // CONF: the probability of the predicted class also goes to `conf` float [B, Hcut, Wcut] (0 for a 255 pixel), by a second pass over the classes in the form
-// the first one took (slots or scanning), for the reason slide_pixel.inc gives: the same values again, now that their maximum `best` is known.
+// the first one took (slots or scanning), for the reason slide_pixel.h gives: the same values again, now that their maximum `best` is known.
 // TEMP (with CONF): the confidence of softmax(x / T) -- the exponentials are softmax_px_exp_t with the inverse temperature `it`; the map does not depend on it.
 // SCORE (without CONF / TEMP): an uncertainty score of csrc/softmax_px.h (`kind`, `ilc`) goes to `conf` in the confidence's place, from the probabilities of
 // softmax(x * it) -- a third pass over the classes in the recomputing form: the sum needs the maximum, the probabilities need the sum.
@@ -261,70 +442,6 @@ __global__ __launch_bounds__(256) void slide_argmax_resized_kernel(const float* 
   slide_resized_pixel<false>(logits, C, hs, ws, out, nullptr, H, W, hc, wc, rh, rw, Hcut, Wcut, rh2, rw2, wt, uncovered);
 }
 
-// (mmsa_slide_argmax_resized: at the end of the file, with its siblings and the launcher they share)
-
-// ---- confidence maps: the probability of the predicted class next to every class map, conf[b, y, x] = max_c P[b, c, y, x] with P the probabilities of
-// EncoderDecoder.inference (F.softmax(seg_logit, dim=1), ED:449,460), written by the launch that writes the map.  The arithmetic is csrc/softmax_px.h:
-// m = max_c x_c; s = e_0, s += e_c in class order, e_c = expf(x_c - m); conf = expf(m - m) / s -- P at the first maximum, which is the largest P.  The
-// kernels stand BELOW the ones they extend so that those keep their place in the file and with it their instruction streams, label for label
-// (profiles/confidence_isa.txt).
-
-// argmax_nchw_kernel that also writes the maximum: on the probabilities of the canvas paths (mmsa_softmax_flip_accum_nchw), the confidence map
-// max_c P[b, c, y, x] of ED:449,460 next to the class map, from one read of the canvas.
-__global__ __launch_bounds__(256) void argmax_max_nchw_kernel(const float* __restrict__ x, unsigned char* __restrict__ out, float* __restrict__ maxval, int C,
-                                                              long HW, long total) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;   // b * HW + p
-  if (i >= total) return;
-  const long b = i / HW, p = i - b * HW;
-  const float* xp = x + b * C * HW + p;
-  float best = xp[0];
-  int bi = 0;
-  for (int c = 1; c < C; ++c) {
-    const float v = xp[(long)c * HW];
-    if (v > best) { best = v; bi = c; }
-  }
-  out[i] = (unsigned char)bi;
-  maxval[i] = best;
-}
-
-extern "C" int mmsa_argmax_max_nchw(const float* x, unsigned char* out, float* maxval, int B, int C, long HW, hipStream_t stream) {
-  MMSA_CHECK_ARG(x && out && maxval && B > 0 && C > 0 && C <= 256 && HW > 0, "argmax_max_nchw: bad args (C <= 256 for the uint8 map)");
-  const long total = (long)B * HW;
-  hipLaunchKernelGGL(argmax_max_nchw_kernel, dim3(cdiv(total, 256)), dim3(256), 0, stream, x, out, maxval, C, HW, total);
-  MMSA_CHECK_LAUNCH("argmax_max_nchw");
-  return MMSA_OK;
-}
-
-// slide_argmax_kernel + the confidence map: conf[b, y, x] = max_c softmax(preds / count)[c], the probability of the class the map names (ED:449,460).  The
-// sum of the exponentials needs the maximum first, so the pixel's C values are needed twice; two forms (slide_pixel.inc), chosen by measurement
-// (profiles/confidence.txt):
-//   slide_argmax_conf_lds_kernel : the first pass keeps them in a per-lane LDS column [c][lane], as aug_argmax_kernel does -- C * 256 floats of dynamic LDS,
-//                                  so C <= SLIDE_CONF_LDS_CLASSES = 64 (64 KiB); the faster form -- within the spread of the plain kernel (+ 7 / - 15 us) where the other
-//                                  costs + 97 / + 330 us (two 1024 x 1024 maps / the six-window 1080 x 1920 frame, 25 classes) -- and the one the entry
-//                                  takes wherever it fits;
-//   slide_argmax_conf_kernel     : a second pass recomputes them (the same operations on the same inputs, the same bits): no LDS, any C the map allows.
-// Both take 160 registers.  Bit for bit max over C of mmsa_softmax_flip_accum_nchw on the canvas path's logits, either way.
-#define SLIDE_CONF_LDS_CLASSES 64
-__global__ __launch_bounds__(256) void slide_argmax_conf_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
-                                                                float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, WindowTable wt,
-                                                                int* __restrict__ uncovered) {
-#define SLIDE_CONF 1
-#define SLIDE_Y blockIdx.y
-#define SLIDE_EXIT return
-#include "slide_pixel.inc"
-}
-
-__global__ __launch_bounds__(256) void slide_argmax_conf_lds_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
-                                                                    float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, WindowTable wt,
-                                                                    int* __restrict__ uncovered) {
-  extern __shared__ float conf_lds[];
-  float* conf_col = conf_lds + threadIdx.x;      // private to the lane: no barrier
-#define SLIDE_CONF 2
-#define SLIDE_Y blockIdx.y
-#define SLIDE_EXIT return
-#include "slide_pixel.inc"
-}
-
 // slide_argmax_resized_kernel + the confidence map at the rescaled / cut size: conf = max_c softmax(resized)[c] (ED:449,460), slot form and scanning form.
 __global__ __launch_bounds__(256) void slide_argmax_resized_conf_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
                                                                         float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, int Hcut,
@@ -332,105 +449,38 @@ __global__ __launch_bounds__(256) void slide_argmax_resized_conf_kernel(const fl
   slide_resized_pixel<true>(logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, Hcut, Wcut, rh2, rw2, wt, uncovered);
 }
 
-// ---- tempered confidence: the three confidence kernels above with softmax(x / T) in place of softmax(x) -- `it` = float32(1 / float64(T)) from the host, and
-// every exponential is softmax_px_exp_t (csrc/softmax_px.h: ONE more float32 product, exact at it == 1.0f, where these kernels are their siblings bit for bit).
-// The class map does not depend on T > 0.  They stand here, behind the kernels that were there before them, for the reason given above argmax_max_nchw_kernel.
-__global__ __launch_bounds__(256) void slide_argmax_conf_t_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
-                                                                  float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, WindowTable wt,
-                                                                  int* __restrict__ uncovered, float it) {
-#define SLIDE_CONF 1
-#define SLIDE_TEMP 1
-#define SLIDE_Y blockIdx.y
-#define SLIDE_EXIT return
-#include "slide_pixel.inc"
-}
-
-__global__ __launch_bounds__(256) void slide_argmax_conf_lds_t_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
-                                                                      float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, WindowTable wt,
-                                                                      int* __restrict__ uncovered, float it) {
-  extern __shared__ float conf_lds[];
-  float* conf_col = conf_lds + threadIdx.x;      // private to the lane: no barrier
-#define SLIDE_CONF 2
-#define SLIDE_TEMP 1
-#define SLIDE_Y blockIdx.y
-#define SLIDE_EXIT return
-#include "slide_pixel.inc"
-}
-
+// ... tempered
 __global__ __launch_bounds__(256) void slide_argmax_resized_conf_t_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
                                                                           float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, int Hcut,
                                                                           int Wcut, float rh2, float rw2, WindowTable wt, int* __restrict__ uncovered, float it) {
   slide_resized_pixel<true, true>(logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, Hcut, Wcut, rh2, rw2, wt, uncovered, it);
 }
 
-// ---- uncertainty maps: the top-2 margin or the entropy score (csrc/softmax_px.h: `kind` SCORE_MARGIN / SCORE_ENTROPY) in the confidence's place, float32
-// [B, Ho, Wo] in [0, 1], higher = more certain, 0 where the map is 255 -- so that csrc/conf_bin.h and everything behind it take it unchanged.  Both are formed
-// from the float32 probabilities p_c, the same operations in the canvas kernel (which reads p_c) and in the one-pass kernels (which form p_c = e_c / s of
-// softmax(x * it) themselves: `it` is always an argument, its product exact at 1.0f): bit for bit the same score.  They stand here, behind every other kernel, for the
-// reason given above argmax_max_nchw_kernel (profiles/uncertainty_isa.txt).
-
-// argmax_max_nchw_kernel with the score in the maximum's place: on a canvas of probabilities (one view's, or the mean over augmented views).  `bi` is the
-// first maximum of the probabilities; where the logits' argmax is a later class of the same probability, p[bi] and p2 are the same two values.
-__global__ __launch_bounds__(256) void argmax_score_nchw_kernel(const float* __restrict__ x, unsigned char* __restrict__ out, float* __restrict__ score, int C,
-                                                                long HW, long total, int kind, float ilc) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;   // b * HW + p
-  if (i >= total) return;
-  const long b = i / HW, p = i - b * HW;
-  const float* xp = x + b * C * HW + p;
-  float best = xp[0];
-  int bi = 0;
-  for (int c = 1; c < C; ++c) {
-    const float v = xp[(long)c * HW];
-    if (v > best) { best = v; bi = c; }
-  }
-  out[i] = (unsigned char)bi;
-  float sa = 0.f, spb = 0.f;
-  bool snone = true;
-  for (int c = 0; c < C; ++c) score_px_class(kind, bi, c, xp[(long)c * HW], sa, spb, snone);
-  score[i] = score_px_finish(kind, sa, spb, snone, ilc);
-}
-
-#define MMSA_CHECK_SCORE_KIND(name, kind) MMSA_CHECK_ARG((kind) == SCORE_MARGIN || (kind) == SCORE_ENTROPY, "%s: kind %d is neither 1 (top-2 margin) nor 2 (entropy score)", name, kind)
-
-extern "C" int mmsa_argmax_score_nchw(const float* prob, unsigned char* out, float* score, int B, int C, int H, int W, int kind, float inv_log_c,
-                                      hipStream_t stream) {
-  MMSA_CHECK_ARG(prob && out && score && B > 0 && C > 0 && C <= 256 && H > 0 && W > 0, "argmax_score_nchw: bad args (C <= 256 for the uint8 map)");
-  MMSA_CHECK_SCORE_KIND("argmax_score_nchw", kind);
-  MMSA_CHECK_ARG(inv_log_c >= 0.f && inv_log_c < INFINITY, "argmax_score_nchw: inv_log_c must be finite and not negative (1 / log C; 0 for one class)");
-  const long HW = (long)H * W, total = (long)B * HW;
-  hipLaunchKernelGGL(argmax_score_nchw_kernel, dim3(cdiv(total, 256)), dim3(256), 0, stream, prob, out, score, C, HW, total, kind, inv_log_c);
-  MMSA_CHECK_LAUNCH("argmax_score_nchw");
-  return MMSA_OK;
-}
-
-// slide_argmax_kernel + the score map, in the two forms of the confidence (slide_pixel.inc SLIDE_SCORE): the per-lane LDS column up to SLIDE_CONF_LDS_CLASSES
-// classes -- written with x_c by the class-map pass, overwritten with e_c by the sum pass, read once more for p_c = e_c / s -- and three recomputing passes
-// above that (65 .. 255 classes; slow, and allowed to be).
-__global__ __launch_bounds__(256) void slide_argmax_score_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
-                                                                 float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, WindowTable wt,
-                                                                 int* __restrict__ uncovered, int kind, float it, float ilc) {
-#define SLIDE_SCORE 1
-#define SLIDE_Y blockIdx.y
-#define SLIDE_EXIT return
-#include "slide_pixel.inc"
-}
-
-__global__ __launch_bounds__(256) void slide_argmax_score_lds_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
-                                                                     float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, WindowTable wt,
-                                                                     int* __restrict__ uncovered, int kind, float it, float ilc) {
-  extern __shared__ float conf_lds[];
-  float* conf_col = conf_lds + threadIdx.x;      // private to the lane: no barrier
-#define SLIDE_SCORE 2
-#define SLIDE_Y blockIdx.y
-#define SLIDE_EXIT return
-#include "slide_pixel.inc"
-}
-
+// slide_argmax_resized_kernel + the score map: a third pass over the classes in the recomputing form
 __global__ __launch_bounds__(256) void slide_argmax_resized_score_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
                                                                          float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, int Hcut,
                                                                          int Wcut, float rh2, float rw2, WindowTable wt, int* __restrict__ uncovered, int kind,
                                                                          float it, float ilc) {
   slide_resized_pixel<false, false, true>(logits, C, hs, ws, out, conf, H, W, hc, wc, rh, rw, Hcut, Wcut, rh2, rw2, wt, uncovered, it, kind, ilc);
+}
+
+// ---- the host side of the fused evaluation entry
+extern "C" int mmsa_slide_argmax_eval(const float* logits, int n, int C, int hs, int ws, const int* windows /* HOST [n,3] */, unsigned char* out /* or NULL */,
+                                      int B, int H, int W, int hc, int wc, int* uncovered, const unsigned char* label, int Hl, int Wl,
+                                      const unsigned char* lut, const int* ymap, const int* xmap, const int* slots /* HOST [B] */, int n_slots,
+                                      int64_t* counts, hipStream_t stream) {
+  MMSA_CHECK_ARG(logits && uncovered && hs > 0 && ws > 0 && hc > 0 && wc > 0 && B > 0 && H <= 65535 && B <= 65535, "slide_argmax_eval: bad args");
+  EvalSlots es;
+  int rc = eval_check("slide_argmax_eval", label, B, H, W, Hl, Wl, lut, C, ymap, xmap, slots, n_slots, counts, es);
+  if (rc) return rc;
+  WindowTable wt;
+  rc = fill_windows(wt, windows, n, B, H, W, hc, wc, "slide_argmax_eval");
+  if (rc) return rc;
+  const EvalLabel ev = {label, lut, ymap, xmap, (unsigned long long*)counts, Hl, Wl, C};
+  hipLaunchKernelGGL(slide_argmax_eval_kernel, dim3(cdiv(W, 256), cdiv(H, SLIDE_EVAL_ROWS), B), dim3(256), (size_t)(C + 1) * (C + 1) * 4 + 256, stream, logits, C, hs, ws, out,
+                     H, W, hc, wc, (float)hs / (float)hc, (float)ws / (float)wc, wt, uncovered, ev, es);
+  MMSA_CHECK_LAUNCH("slide_argmax_eval");
+  return MMSA_OK;
 }
 
 // ---- the host side of the eight class-map entries mmsa_slide_argmax[_resized][_conf[_t] | _score]: one launcher per geometry, below every kernel it may launch.
@@ -551,87 +601,6 @@ extern "C" int mmsa_slide_argmax_resized_score(const float* logits, int n, int C
                                                hipStream_t stream) {
   return slide_argmax_resized_launch("slide_argmax_resized_score", logits, n, C, hs, ws, windows, out, score, B, H, W, hc, wc, Hd, Wd, Hcut, Wcut, uncovered, stream,
                                      &inv_temperature, &kind, inv_log_c);
-}
-
-// ---- top-k maps: the first K classes of every pixel and their probabilities (csrc/softmax_px.h: TopkPx<S>, comparisons and moves on the float32 probabilities
-// p_c the confidence paths form), classes uint8 / probs float32 [K, B, Ho, Wo], rank-major: plane 0 of the classes IS the class map, plane 0 of the
-// probabilities IS the confidence map, and probs[0] - probs[1] is the top-2 margin, bit for bit.  The rank list lives in registers (S = 2 / 4 / 8 slots, the
-// smallest that holds K: the predicates of the unrolled insert are paid per class).  They stand here, behind every other kernel and below the launchers of the
-// entries above, for the reason given above argmax_max_nchw_kernel (profiles/topk_isa.txt).
-#define MMSA_CHECK_TOPK(name, K) MMSA_CHECK_ARG((K) >= 1 && (K) <= TOPK_MAX, "%s: K = %d; 1..%d ranks are supported (the rank list of a pixel is kept in registers)", name, K, TOPK_MAX)
-#define TOPK_DISPATCH(K, LAUNCH) \
-  do {                           \
-    if ((K) <= 2) LAUNCH(2);     \
-    else if ((K) <= 4) LAUNCH(4); \
-    else LAUNCH(8);              \
-  } while (0)
-
-// argmax_score_nchw_kernel with the rank list in the score's place: on a canvas of probabilities (one view's, or the mean over augmented views).  `first` NULL:
-// bi = the first maximum of the probabilities (the augmented path's map); else bi = first[i], the map of the one-view canvas path, which is the argmax of the
-// LOGITS (two logits can round to one probability, and the later one may be the map's).  A lane reads first[i] before it writes classes[i]: `first` may be plane 0.
-template <int S>
-__global__ __launch_bounds__(256) void argmax_topk_nchw_kernel(const float* __restrict__ x, const unsigned char* first, unsigned char* classes,
-                                                               float* __restrict__ probs, int C, long HW, long total, int K) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;   // b * HW + p
-  if (i >= total) return;
-  const long b = i / HW, p = i - b * HW;
-  const float* xp = x + b * C * HW + p;
-  int bi = 0;
-  if (first) {
-    bi = first[i];
-    if (bi >= C) {      // 255 = uncovered (any byte that is no class of the canvas is treated alike)
-      topk_px_store_none(classes, probs, total, i, K, 0);
-      return;
-    }
-  } else {
-    float best = xp[0];
-    for (int c = 1; c < C; ++c) {
-      const float v = xp[(long)c * HW];
-      if (v > best) { best = v; bi = c; }
-    }
-  }
-  TopkPx<S> tk;
-  topk_px_init(tk);
-  for (int c = 0; c < C; ++c) topk_px_class(tk, bi, c, xp[(long)c * HW]);
-  topk_px_store(tk, classes, probs, total, i, K, 0);
-}
-
-extern "C" int mmsa_argmax_topk_nchw(const float* prob, const unsigned char* first, unsigned char* classes, float* probs, int B, int C, int H, int W, int K,
-                                     hipStream_t stream) {
-  MMSA_CHECK_ARG(prob && classes && probs, "argmax_topk_nchw: prob, classes and probs are required");
-  MMSA_CHECK_ARG(C > 0 && C <= 255, "argmax_topk_nchw: %d classes; 1..255 are supported (255 is the byte of a rank without a class)", C);
-  MMSA_CHECK_TOPK("argmax_topk_nchw", K);
-  MMSA_CHECK_ARG(B > 0 && H > 0 && W > 0, "argmax_topk_nchw: bad args");
-  const long HW = (long)H * W, total = (long)B * HW;
-#define TOPK_LAUNCH(S) hipLaunchKernelGGL(argmax_topk_nchw_kernel<S>, dim3(cdiv(total, 256)), dim3(256), 0, stream, prob, first, classes, probs, C, HW, total, K)
-  TOPK_DISPATCH(K, TOPK_LAUNCH);
-#undef TOPK_LAUNCH
-  MMSA_CHECK_LAUNCH("argmax_topk_nchw");
-  return MMSA_OK;
-}
-
-// slide_argmax_kernel + the rank planes, in the two forms of the score (slide_pixel.inc SLIDE_TOPK): the per-lane LDS column up to SLIDE_CONF_LDS_CLASSES
-// classes, three recomputing passes above that (65 .. 255 classes).  `out` / `conf` are the planes [K, B, H, W], `plane` = B * H * W.
-template <int S>
-__global__ __launch_bounds__(256) void slide_argmax_topk_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
-                                                                float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, WindowTable wt,
-                                                                int* __restrict__ uncovered, int K, long plane, float it) {
-#define SLIDE_TOPK 1
-#define SLIDE_Y blockIdx.y
-#define SLIDE_EXIT return
-#include "slide_pixel.inc"
-}
-
-template <int S>
-__global__ __launch_bounds__(256) void slide_argmax_topk_lds_kernel(const float* __restrict__ logits, int C, int hs, int ws, unsigned char* __restrict__ out,
-                                                                    float* __restrict__ conf, int H, int W, int hc, int wc, float rh, float rw, WindowTable wt,
-                                                                    int* __restrict__ uncovered, int K, long plane, float it) {
-  extern __shared__ float conf_lds[];
-  float* conf_col = conf_lds + threadIdx.x;      // private to the lane: no barrier
-#define SLIDE_TOPK 2
-#define SLIDE_Y blockIdx.y
-#define SLIDE_EXIT return
-#include "slide_pixel.inc"
 }
 
 // mmsa_slide_argmax_conf_t with the K planes in the place of out / conf: the same checks in the same order, K's behind the geometry's.

@@ -29,14 +29,14 @@ static inline int check_window(const char* name, int view, int k, int wb, int y0
   return MMSA_ERR_ARG;
 }
 
-// Registers: four taps with the eight slots of slide_pixel.inc would need 4 x 56 (the first form did: 372 registers, one wave per SIMD).  Here a tap
+// Registers: four taps with the eight slots of slide_pixel.h would need 4 x 56 (the first form did: 372 registers, one wave per SIMD).  Here a tap
 // keeps RESIZED_SLOTS = 4 windows, each packed to four registers (offset of the top-left logit, window index | "has a row below" << 8 | "has a column
 // to the right" << 9, the two weights); a pixel with a tap under 5 .. 8 windows (strides below half the crop) takes the scanning form instead, which walks
 // the window table again for every class and keeps nothing.  Same terms, same order, same bits either way.
 #define RESIZED_SLOTS 4
 struct TapSlots { int nk; int o[RESIZED_SLOTS], kf[RESIZED_SLOTS]; float lh[RESIZED_SLOTS], lw[RESIZED_SLOTS]; };
 
-// window k of image b over canvas pixel (ty, tx)?  -> its 4-tap coordinates in the window's logits, as slide_pixel.inc computes them
+// window k of image b over canvas pixel (ty, tx)?  -> its 4-tap coordinates in the window's logits, as slide_pixel.h computes them
 template <class WT>
 __device__ __forceinline__ bool tap_coords(const WT& wt, int k, int b, int ty, int tx, int hc, int wc, int hs, int ws, float rh, float rw,
                                            int& o, int& kf, float& lh, float& lw) {
@@ -54,7 +54,7 @@ __device__ __forceinline__ bool tap_coords(const WT& wt, int k, int b, int ty, i
   return true;
 }
 
-// one window's term of a canvas pixel: the interpolation of bilinear_accum_kernel / slide_pixel.inc
+// one window's term of a canvas pixel: the interpolation of bilinear_accum_kernel / slide_pixel.h
 __device__ __forceinline__ float tap_term(const float* __restrict__ logits, int C, int c, int hs, int ws, int o, int kf, float lh, float lw) {
   const int dh = (kf >> 8) & 1 ? ws : 0, dw = (kf >> 9) & 1;
   const float* sp = logits + ((long)(kf & 255) * C + c) * hs * ws + o;

@@ -9,7 +9,7 @@
 //
 // One lane per pixel, lanes along x: the reads of a class plane are coalesced.  A first pass over the classes gives the maximum m, the first argmax p and the
 // label's logit x_l; a second pass re-reads the pixel's logits (they are in the caches: a workgroup touches C runs of SWEEP_CHUNK floats) and forms the J
-// sums of exponentials in registers -- a constant-bound unrolled loop with predicates, as the slot arrays of slide_pixel.inc.  Then, temperature by
+// sums of exponentials in registers -- a constant-bound unrolled loop with predicates, as the slot arrays of slide_pixel.h.  Then, temperature by
 // temperature, the wave reduces bin by bin as calibrate.hip does (most pixels share a bin at every temperature) into uint64 LDS cells [J][K], which one
 // flush per workgroup adds to the result with 64-bit atomics.  Integer sums only, in LDS and in the int64 result: the same bytes whatever the order of arrival.
 #include "common.h"

@@ -1,4 +1,4 @@
-"""Float64 restatement of the class-map family (csrc/segment.hip, csrc/slide_pixel.inc, csrc/slide_taps.h, csrc/augment.hip), the per-element bound the
+"""Float64 restatement of the class-map family (csrc/segment.hip, csrc/slide_pixel.h, csrc/slide_taps.h, csrc/augment.hip), the per-element bound the
 geometry tests hold the device to (tests/test_class_map_geometry_gpu.py), the case table, and a float32 emulation of the kernels' formula with switchable
 mutations (tests/test_class_map_geometry_cpu.py keeps reference, bound and table honest) -- TEST INFRASTRUCTURE ONLY.
 
@@ -57,7 +57,7 @@ GEOS = {
     # ratios 5/12 and 7/20, overlap 1 / 2 / 4, every h/w swap
     "nonsq-5x7-12x20-20x33-b2": _geo(5, 7, 12, 20, 20, 33, 2, [(0, 0), (0, 13), (8, 0), (8, 13)], (8, 13),
                                      [(29, 47, 29, 47), (13, 21, 13, 21), (26, 24, 20, 17)]),
-    # overlap up to 8: all eight slots of slide_pixel.inc, the scanning form of the resized kernels
+    # overlap up to 8: all eight slots of slide_pixel.h, the scanning form of the resized kernels
     "ov8-5x7-12x20-18x35-b1": _geo(5, 7, 12, 20, 18, 35, 1, [(y, x) for y in (0, 6) for x in (0, 5, 10, 15)], (6, 5),
                                    [(25, 51, 25, 51), (11, 23, 11, 23), (27, 22, 21, 16)]),
     # W > 256: the second workgroup in x; ratios 1/3 and 7/27 (no map may exceed 300 a side, so no target is wider than the frame)
@@ -296,7 +296,7 @@ def emu_sums(lg, geo, mut=()):
 
 
 def emu_frame(lg, geo, target=None, mut=()):
-    """The emulated logits at the map's size, float32 [B, C, Ho, Wo]: tap_value / slide_pixel.inc, then two_stage_value."""
+    """The emulated logits at the map's size, float32 [B, C, Ho, Wo]: tap_value / slide_pixel.h, then two_stage_value."""
     acc, cnt = emu_sums(lg, geo, mut)
     if target is None:
         return acc / cnt[:, None]

@@ -658,11 +658,16 @@ def test_class_map_kernels_keep_their_registers_and_do_not_spill():
     for k, v in res.items():
         assert v["scratch_bytes"] == 0, f"{k}: {v['scratch_bytes']} scratch bytes"
     bounds = dict(slide_argmax=158, slide_argmax_eval=160, slide_argmax_conf=160, slide_argmax_conf_lds=160, slide_argmax_resized=216,
-                  slide_argmax_resized_conf=256, aug_argmax=226, aug_argmax_conf=228)
+                  slide_argmax_resized_conf=256, aug_argmax=226, aug_argmax_conf=228,
+                  # the other frame-size kernels: what they took while csrc/slide_pixel.inc built them (profiles/slide_pixel_template_isa.txt)
+                  slide_argmax_conf_t=160, slide_argmax_conf_lds_t=160, slide_argmax_score=164, slide_argmax_score_lds=160)
     for base, bound in bounds.items():
         hit = [k for k in res if re.match(r"_Z\d+%s_kernel[A-Z0-9]" % base, k)]
         assert len(hit) == 1, (base, hit)
         assert res[hit[0]]["vgprs"] <= bound, f"{base}_kernel: {res[hit[0]]['vgprs']} VGPRs, bound {bound}"
+    for base, bound in dict(slide_argmax_topk=166, slide_argmax_topk_lds=160).items():      # templates: the census names them base_kernel<S>
+        for S in (2, 4, 8):
+            assert res[f"{base}_kernel<{S}>"]["vgprs"] <= bound, f"{base}_kernel<{S}>: {res[f'{base}_kernel<{S}>']['vgprs']} VGPRs, bound {bound}"
 
 
 def test_kernel_gelu_coefficients_hold_their_error_bound():

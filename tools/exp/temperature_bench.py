@@ -6,7 +6,8 @@ process, every repetition timing each leg once (order rotated), `--inner` launch
   (e) mmsa_softmax_flip_accum_nchw      (f) mmsa_softmax_flip_accum_nchw_t      the canvas softmax
   (g) canvas softmax + mmsa_argmax_max_nchw + mmsa_eval_calibration: what one temperature costs without the sweep (the map's mmsa_argmax_nchw not counted)
   (h) the sweep at J = 1    (i) at J = 8    (j) at J = 16
-25 classes; two 1024 x 1024 maps (one window per image) and the 1080 x 1920 frame under six 1024 x 1024 windows; synthetic head-resolution logits
+25 classes (`--classes`: above 64 the frame-size kernels recompute, and the shape is two 1000 x 1000 maps); two 1024 x 1024 maps (one window per image)
+and the 1080 x 1920 frame under six 1024 x 1024 windows; synthetic head-resolution logits
 (randn * 6: the cost of these kernels does not depend on the values but for the sweep's bin rounds, so labels come in 32 x 32 patches with 5 % ignored and
 the logits are what they are).  Before anything is timed, (b), (d), (f) at T = 1 are checked against (a), (c), (e) bit for bit and (h) against (g)."""
 import argparse
@@ -34,6 +35,7 @@ def main():
     ap.add_argument("--inner", type=int, default=10)
     ap.add_argument("--bins", type=int, default=15)
     ap.add_argument("--temperature", type=float, default=2.5)
+    ap.add_argument("--classes", type=int, default=25, help="above 64 the frame-size legs (a), (b) take the recomputing form; two 1000 x 1000 maps then")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.reps < 30:
@@ -44,7 +46,7 @@ def main():
     import mmsa.inference as inf
     from mmsa.evaluate import LabelPrep, calibration, geometric_grid, temperature_sweep
     dev = torch.device("cuda", 0)
-    C, K, T = 25, a.bins, a.temperature
+    C, K, T = a.classes, a.bins, a.temperature
     lines = []
 
     def say(s=""):
@@ -56,6 +58,8 @@ def main():
     geos = (("2 x 1024 x 1024, one window per image", inf.MapPlan.whole(2, 1024, 1024), inf.MapPlan.whole(2, 512, 512, ori_shape=(1024, 1024))),
             ("1 x 1080 x 1920, six 1024 x 1024 windows", inf.MapPlan.slide(1, 1080, 1920, (1024, 1024), (768, 768)),
              inf.MapPlan.slide(1, 540, 960, (512, 512), (384, 384), ori_shape=(1080, 1920))))
+    if C > 64:      # 1000 rows: the canvas legs' resize launch takes classes x rows <= 65535
+        geos = (("2 x 1000 x 1000, one window per image", inf.MapPlan.whole(2, 1000, 1000), inf.MapPlan.whole(2, 500, 500, ori_shape=(1000, 1000))),)
     for name, plan, rplan in geos:
         g = torch.Generator().manual_seed(5)
         B, H, W = plan.B, plan.H, plan.W
