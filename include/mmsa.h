@@ -609,6 +609,34 @@ int mmsa_eval_boundary_displacement(const unsigned char* pred, const unsigned ch
                                     int C, const int* ymap, const int* xmap, const int* slots, int n_slots, const unsigned short* d2_pred,
                                     const unsigned short* d2_label, int cap, int64_t* hist, mmsa_stream_t stream);
 
+/* --- segment-level evaluation (csrc/components.hip): the connected components of code maps, and what is counted from two of them.
+ *   components_u8: the code map M(y, x) = lut[src[b, ymap[y], xmap[x]]] on the grid [H, W] is mmsa_boundary_distance_u8's (lut == NULL: the byte itself; ymap /
+ *     xmap both or neither, clamped into the source; without them Hs == H and Ws == W); the kernels compare BYTES: 255 and C are codes like any other.  Two
+ *     pixels of one image are connected iff they are 4- or 8-neighbours (connectivity = 4 or 8) and hold the same code; a component is a maximal connected set.
+ *     root int32 [B, H, W]: root[b, y, x] = the smallest linear index y * W + x of the pixel's component within its own image -- canonical, the same bytes
+ *     whatever the schedule.  B * H * W < 2^31, B <= 65535.  root is also the working plane of the (up to) three launches of the call -- a tile pass, a merge
+ *     pass over the tile borders, a flatten pass; no scratch.  No workgroup waits for another; every loop follows strictly falling indices or is bounded by
+ *     the tile's pixel count, and is capped by that size besides.
+ *   component_area: area int32 [B, H, W] (not root): the pixel count of the component at its root pixel, 0 elsewhere; the plane is zeroed, then added to (one
+ *     add per wave and distinct root).  root is a plane as components_u8 writes it; a value outside [0, H * W) is clamped, never followed outside the plane.
+ *   suppress_small_u8: out[p] = fill where area[root[p]] < min_area, pred[p] elsewhere; out may be pred.  min_area >= 1 (1: the identity), 0 <= fill <= 255.
+ *   eval_segments: pred, the label side (lut, ymap / xmap, slots: HOST int [B]) and the codes L (a class < C, C, or 255 = ignored), P = min(pred, C) are
+ *     mmsa_eval_confusion_u8's; root_pred / root_label are int32 [B, H, W] as components_u8 writes them for P and for L.  scratch int32 [4, B, H, W] is zeroed
+ *     here; every pixel whose own L is not 255 adds 1 at scratch[0][root_label[p]] and scratch[2][root_pred[p]], and where L < C and P == L also at
+ *     scratch[1][root_label[p]] and scratch[3][root_pred[p]]: area and hits of the label segments (side 0) and of the prediction segments (side 1), whose
+ *     area therefore excludes ignored pixels.  Then every root pixel with area > 0 and code c < C adds 1 at [slot, side, c, s, k] of counts int64
+ *     [n_slots, 2, C, 24, bins + 1], ADDED to: s = min(23, floor(log2 area)), k = floor(bins * hit / area) in 64-bit integers (k == bins iff the segment is
+ *     covered completely); 1 <= bins <= 64, 2 <= C <= 254, 1 <= B <= 64.
+ *   A limit broken or a null pointer: MMSA_ERR_ARG with a message, before any launch.  Integer sums: the same bytes whatever the order of arrival. --- */
+int mmsa_components_u8(const unsigned char* src, int B, int Hs, int Ws, const unsigned char* lut, const int* ymap, const int* xmap, int H, int W,
+                       int connectivity, int* root, mmsa_stream_t stream);
+int mmsa_component_area(const int* root, int B, int H, int W, int* area, mmsa_stream_t stream);
+int mmsa_suppress_small_u8(const unsigned char* pred, const int* root, const int* area, int B, int H, int W, int min_area, int fill, unsigned char* out,
+                           mmsa_stream_t stream);
+int mmsa_eval_segments(const unsigned char* pred, const unsigned char* label, int B, int H, int W, int Hl, int Wl, const unsigned char* lut, int C,
+                       const int* ymap, const int* xmap, const int* slots, int n_slots, const int* root_pred, const int* root_label, int bins, int* scratch,
+                       int64_t* counts, mmsa_stream_t stream);
+
 /* --- the picture of a prediction (segmentation/mmseg_custom/apis/test_bs.py:257-349, the `--show` / `--show-dir` output): `tensor2imgs` (test_bs.py:18-63) on
  *     planes 0..2 of the input tensor -> the crop `img[:h, :w]` (test_bs.py:275-276) -> `show_result` (tools/color_gt_according_palette.py:23-81:
  *     color_seg[seg == label] = color, channels reversed, img * (1 - opacity) + color_seg * opacity, .astype(uint8)), in one pass.

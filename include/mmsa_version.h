@@ -27,7 +27,10 @@
  *      and the blend of mmsa_render_u8).
  *      Still 114, for the same reason: new entries mmsa_boundary_distance_u8 / mmsa_eval_boundary_d2 / mmsa_eval_boundary_displacement (the exact squared
  *      Euclidean distance map of a code map, the boundary counts at a Euclidean radius from two such maps, and the displacement histogram of the two contours:
- *      boundary F-score and Hausdorff percentiles). */
+ *      boundary F-score and Hausdorff percentiles).
+ *      Still 114, for the same reason: new entries mmsa_components_u8 / mmsa_component_area / mmsa_suppress_small_u8 / mmsa_eval_segments (the connected
+ *      components of a code map as the smallest linear index of each, their areas, the class map without its small blobs, and the segment counts of a
+ *      prediction against the ground truth by class, size bucket and coverage bin: segment recall and precision). */
 #ifndef MMSA_VERSION_H
 #define MMSA_VERSION_H
 #define MMSA_ABI_VERSION 114

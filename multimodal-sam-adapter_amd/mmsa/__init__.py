@@ -23,6 +23,8 @@ from .evaluate import TopKEvaluator, topk_counts  # noqa: F401  (the rank of the
 from .evaluate import BoundaryEvaluator, boundary_counts, boundary_zone_sum_of, trimap_counts_of, boundary_iou_of  # noqa: F401  (confusion counts by nearness to a label / prediction boundary: trimap metrics and Boundary IoU)
 from .evaluate import (EuclideanBoundaryEvaluator, boundary_distance, boundary_counts_d2, boundary_displacement, boundary_f_of,  # noqa: F401  (exact distance
                        boundary_f_curve_of, boundary_distance_percentile_of)  # maps of the code maps: Euclidean bands up to 255 pixels, boundary F-score, Hausdorff percentiles)
+from .evaluate import (SegmentEvaluator, components, component_areas, suppress_small, segment_counts, segment_totals_of,  # noqa: F401  (connected components
+                       segment_rate_of, segment_f_of)  # of the code maps: segment recall and precision by class and size, and the map without its small blobs)
 from . import render  # noqa: F401  (the picture of a prediction on device: palette map over the frame, show_result)
 from .render import Renderer
 from .registry import BACKBONES, HEADS, build_backbone, build_head
@@ -51,4 +53,5 @@ __all__ = ["SegformerHead", "HEADS", "build_head", "register_head", "SAMAdapterb
            "probabilities", "aug_inference", "aug_class_map", "AugPlan", "argmax_max_map", "argmax_score_map", "TopK", "argmax_topk_map",
            "TopKEvaluator", "topk_counts", "BoundaryEvaluator", "boundary_counts", "boundary_zone_sum_of", "trimap_counts_of", "boundary_iou_of",
            "EuclideanBoundaryEvaluator", "boundary_distance", "boundary_counts_d2", "boundary_displacement", "boundary_f_of", "boundary_f_curve_of",
-           "boundary_distance_percentile_of"]
+           "boundary_distance_percentile_of", "SegmentEvaluator", "components", "component_areas", "suppress_small", "segment_counts", "segment_totals_of",
+           "segment_rate_of", "segment_f_of"]

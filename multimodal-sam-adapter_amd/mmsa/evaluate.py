@@ -45,7 +45,15 @@ radius is a threshold on two such maps (`boundary_counts_d2`, mmsa_eval_boundary
 are several pointwise launches over one pair of maps, and `boundary_displacement` (mmsa_eval_boundary_displacement) bins every contour pixel of one map by its
 distance to the other map's contour, int64 [2, C + 1, cap + 2] per slot -- from which `boundary_f_of` / `boundary_f_curve_of` form the boundary F-score at a
 tolerance (Csurka et al.; the DAVIS F measure) and `boundary_distance_percentile_of` the Hausdorff percentile HD95 in float64 on the host.
-`EuclideanBoundaryEvaluator` is a BoundaryEvaluator that owns both buffers."""
+`EuclideanBoundaryEvaluator` is a BoundaryEvaluator that owns both buffers.
+
+Segment-level evaluation asks what no pixel-weighted number answers: how many of the objects were found at all, by size, and how many of the painted blobs
+are real.  Its unit is the segment, a connected component of one code: `components` writes, per pixel, the smallest linear index of its component as int32
+(mmsa_components_u8, csrc/components.hip), read from a code map exactly as `boundary_distance` reads one.  `component_areas` and `suppress_small` (the class map
+without its blobs below an area) are pointwise passes on top, and `segment_counts` / `SegmentEvaluator` reduce (class map, label map, the two root maps) to int64
+[2, C, 24, bins + 1] per slot (mmsa_eval_segments): the label segments (side 0) and the prediction segments (side 1) by class, power-of-two size bucket and the
+share of the segment that is covered by a correct pixel -- from which `segment_rate_of` forms the segment recall and precision at a coverage threshold and
+`segment_f_of` their harmonic mean in float64 on the host."""
 import ctypes
 import math
 import warnings
@@ -1737,3 +1745,334 @@ class EuclideanBoundaryEvaluator(BoundaryEvaluator):
             s["HD95"] = self.distance_percentile(0.95, slot)["hd"]
         s["radius"], s["radius2"], s["metric"] = self.radius, self.radius2, self.metric
         return s
+
+
+# ---- segment-level evaluation: the connected components of the code maps, and what is counted from two of them (csrc/components.hip) ----
+# For a code map M (the label codes L or the prediction codes P = min(pred, C) of the boundary passes above: an ignored label, 255, and C are codes like any
+# other) two pixels of one image are connected iff they are 4- or 8-neighbours and hold the same code; a component -- a SEGMENT -- is a maximal connected set,
+# and root(p) is the smallest linear index y * W + x of p's component within its own image.  Over every pixel whose own L is not 255 a label segment (side 0)
+# and a prediction segment (side 1) collect their area and their hits (L < C and P == L): a prediction segment's area excludes ignored pixels, as every
+# evaluator here does.  A segment of class c < C with area > 0 is counted once, at the size bucket s = min(23, floor(log2 area)) and the coverage bin
+# k = floor(bins * hit / area): k == bins iff it is covered completely, and coverage >= j / bins iff k >= j.
+SIZE_BUCKETS = 24                  # csrc/components.hip COMP_SIZE_BUCKETS: bucket s holds the areas 2^s .. 2^(s + 1) - 1, the last one everything from 2^23
+MAX_SEGMENT_BINS = 64              # csrc/components.hip COMP_MAX_BINS
+DEFAULT_SEGMENT_BINS = 10
+_COMPONENT_SCRATCH = {}            # (device, stream) -> [root, area] int32 planes of suppress_small calls without root= / area=
+_SEGMENT_SCRATCH = {}              # (device, stream) -> the int32 planes of segment_counts calls without scratch=
+
+
+def check_connectivity(connectivity, who="mmsa.evaluate"):
+    if not _is_int(connectivity, 4, 8) or int(connectivity) not in (4, 8):
+        raise ValueError(f"{who}: connectivity = {connectivity!r}; 4 (edge neighbours) or 8 (edge and corner neighbours) is expected")
+    return int(connectivity)
+
+
+def check_segment_bins(bins, who="mmsa.evaluate"):
+    if not _is_int(bins, 1, MAX_SEGMENT_BINS):
+        raise ValueError(f"{who}: bins = {bins!r}; 1..{MAX_SEGMENT_BINS} coverage bins are supported")
+    return int(bins)
+
+
+def _check_int_plane(t, name, shape, device, what):
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous()
+            or (device is not None and t.device != device)):
+        raise RuntimeError(f"mmsa.evaluate: {name} must be a contiguous int32 {tuple(shape)} tensor{'' if device is None else f' on {device}'} ({what})")
+    return t
+
+
+def _cached_planes(cache, n, count, device, what):
+    """`count` int32 buffers of at least n elements each, cached per device and stream (the capture refusal of `_distance_scratch`)."""
+    key = (torch.device(device), ops._stream())
+    t = cache.get(key)
+    if t is None or t[0].numel() < n:
+        if _capturing(key[0]):
+            raise RuntimeError(f"mmsa.evaluate: {what} cannot be allocated during a graph capture: pass the buffers, or run one call of this size before "
+                               "capturing")
+        t = cache[key] = [torch.empty(n, dtype=torch.int32, device=key[0]) for _ in range(count)]
+    return t
+
+
+@torch.no_grad()
+def components(map, *, num_classes=None, labels_prep=None, size=None, connectivity=8, out=None):
+    """The connected components of a code map (up to three launches, mmsa_components_u8) -> int32 [B, H, W] on the device: root[b, y, x] = the smallest linear
+    index y * W + x of the pixel's component within its own image, so the output is canonical: the same bytes whatever the schedule.  Two pixels are connected
+    iff they are 4- or 8-neighbours (`connectivity`) and hold the same code.  The map is read exactly as `boundary_distance` reads it, one of the keywords:
+      num_classes=C     `map` is a stored uint8 class map [B, H, W]; the codes are P = min(map, C);
+      labels_prep=prep  `map` holds raw uint8 labels [B, Hl, Wl]; the codes are the label codes L of `prep` (a class, C = kept but out of range, 255 = ignored: a
+                        code like any other) on the grid `size=(H, W)` -- by default the size `prep` resizes an Hl x Wl label map to -- through the
+                        nearest-neighbour tables of the label side.
+    B * H * W < 2^31.  `out=` (int32 [B, H, W]) makes the call allocation-free: the launches work in it and need no scratch."""
+    connectivity = check_connectivity(connectivity)
+    if (labels_prep is None) == (num_classes is None):
+        raise ValueError("mmsa.evaluate: components takes num_classes= (a stored class map) or labels_prep= (raw labels), one of them")
+    src = _check_map(map, "map", torch.uint8, "a uint8 class map or raw uint8 labels", shape_only=True)
+    B, Hs, Ws = (int(v) for v in src.shape)
+    if labels_prep is None:
+        if size is not None and tuple(size) != (Hs, Ws):
+            raise RuntimeError(f"mmsa.evaluate: size={tuple(size)} for a stored {Hs} x {Ws} class map: only labels are resized (labels_prep=)")
+        H, W = Hs, Ws
+        code_lut(num_classes)      # the class count checked before the device is looked at
+    else:
+        H, W = labels_prep.resized(Hs, Ws) if size is None else (int(size[0]), int(size[1]))
+        if labels_prep.resized(Hs, Ws) != (H, W):
+            raise RuntimeError(f"mmsa.evaluate: size mismatch: the label maps are {Hs} x {Ws}, which the LabelPrep reads on a grid of "
+                               f"{labels_prep.resized(Hs, Ws)[0]} x {labels_prep.resized(Hs, Ws)[1]}, not {H} x {W}")
+    if B * H * W == 0:
+        raise RuntimeError(f"mmsa.evaluate: an empty map {tuple(src.shape)}")
+    if B * H * W >= 1 << 31:
+        raise RuntimeError(f"mmsa.evaluate: {B} x {H} x {W} pixels; components indexes a batch in 32 bits (B * H * W < 2^31)")
+    _check_map(src, "map", torch.uint8, "a uint8 class map or raw uint8 labels")
+    with torch.cuda.device(src.device):
+        if out is None:
+            out = torch.empty(B, H, W, dtype=torch.int32, device=src.device)
+        else:
+            _check_int_plane(out, "out", (B, H, W), src.device, "the root map")
+        lut = _code_lut_on(src.device, num_classes, labels_prep)
+        ymap, xmap = (None, None) if labels_prep is None else labels_prep.tables(Hs, Ws, H, W, src.device)
+        lib.call("mmsa_components_u8", src.data_ptr(), B, Hs, Ws, lut.data_ptr(), None if ymap is None else ymap.data_ptr(),
+                 None if xmap is None else xmap.data_ptr(), H, W, connectivity, out.data_ptr(), ops._stream())
+    return out
+
+
+def _check_root(root, name="root", like=None, shape_only=False):
+    return _check_map(root, name, torch.int32, "an int32 root map (mmsa.components)", like=like, shape_only=shape_only)
+
+
+@torch.no_grad()
+def component_areas(root, out=None):
+    """The pixel count of every component at its root pixel, 0 elsewhere (one memset and one launch, mmsa_component_area) -> int32 [B, H, W] on the device.
+    `root` is what `components` returns; a wave adds once per distinct root, so a component of half a frame costs no more than noise does."""
+    root = _check_root(root, shape_only=True)
+    if root.numel() == 0:
+        raise RuntimeError(f"mmsa.evaluate: an empty map {tuple(root.shape)}")
+    if out is not None:
+        _check_int_plane(out, "out", root.shape, None, "the area plane")
+    _check_root(root)
+    B, H, W = (int(v) for v in root.shape)
+    with torch.cuda.device(root.device):
+        if out is None:
+            out = torch.empty(B, H, W, dtype=torch.int32, device=root.device)
+        elif out.device != root.device or out.data_ptr() == root.data_ptr():
+            raise RuntimeError(f"mmsa.evaluate: out must live on {root.device}, and not be `root`")
+        lib.call("mmsa_component_area", root.data_ptr(), B, H, W, out.data_ptr(), ops._stream())
+    return out
+
+
+@torch.no_grad()
+def suppress_small(pred, min_area, *, num_classes, connectivity=8, fill=255, out=None, root=None, area=None):
+    """The class map without its small blobs -> uint8 [B, H, W]: a pixel whose component (of the codes min(pred, C), at `connectivity`) has fewer than `min_area`
+    pixels becomes `fill`, every other pixel is unchanged; min_area=1 is the identity.  The component launches, the area launch and one pointwise launch
+    (mmsa_suppress_small_u8).  `out=` may be `pred` itself (in place); `root=` / `area=` (int32 [B, H, W] each) take the caller's planes -- they hold the root
+    map and the areas afterwards -- so that a repeated call allocates nothing; without them buffers cached per device and stream are used."""
+    connectivity = check_connectivity(connectivity)
+    if not _is_int(min_area, 1, (1 << 31) - 1):
+        raise ValueError(f"mmsa.evaluate: min_area = {min_area!r}; an integer pixel count >= 1 is expected (1: nothing is removed)")
+    if not _is_int(fill, 0, 255):
+        raise ValueError(f"mmsa.evaluate: fill = {fill!r}; a byte 0..255 is expected")
+    code_lut(num_classes)
+    pred = _check_map(pred, "pred", torch.uint8, "a uint8 class map", shape_only=True)
+    if pred.numel() == 0:
+        raise RuntimeError(f"mmsa.evaluate: an empty map {tuple(pred.shape)}")
+    if out is not None:
+        _check_map(out, "out", torch.uint8, "a uint8 class map", like=pred, shape_only=True)
+    for name, t in (("root", root), ("area", area)):
+        if t is not None:
+            _check_int_plane(t, name, pred.shape, None, "a caller's plane of suppress_small")
+    _check_map(pred, "pred", torch.uint8, "a uint8 class map")
+    B, H, W = (int(v) for v in pred.shape)
+    n = B * H * W
+    with torch.cuda.device(pred.device):
+        if out is None:
+            out = torch.empty_like(pred)
+        else:
+            _check_map(out, "out", torch.uint8, "a uint8 class map", like=pred)
+        if root is None or area is None:
+            cached = _cached_planes(_COMPONENT_SCRATCH, n, 2, pred.device, "the root and area planes of suppress_small")
+            root = cached[0][:n].view(B, H, W) if root is None else root
+            area = cached[1][:n].view(B, H, W) if area is None else area
+        components(pred, num_classes=num_classes, connectivity=connectivity, out=root)
+        component_areas(root, out=area)
+        lib.call("mmsa_suppress_small_u8", pred.data_ptr(), root.data_ptr(), area.data_ptr(), B, H, W, int(min_area), int(fill), out.data_ptr(), ops._stream())
+    return out
+
+
+@torch.no_grad()
+def segment_counts(pred, labels, prep, root_pred, root_label, bins=DEFAULT_SEGMENT_BINS, counts=None, scratch=None, slots=None):
+    """ADD the segment counts of the uint8 class maps pred [B, H, W] against the raw labels into counts[slots[b]] (one memset and two launches,
+    mmsa_eval_segments) -> counts, int64 [n_slots, 2, C, 24, bins + 1] on the device.  root_pred = components(pred, num_classes=C) and root_label =
+    components(labels, labels_prep=prep, size=(H, W)), at one connectivity.  Every pixel whose own label code L is not 255 adds 1 to the area of its label
+    segment (side 0) and of its prediction segment (side 1), and, where L < C and min(pred, C) == L, to their hits; then every segment with area > 0 and class
+    c < C adds 1 at [slot, side, c, min(23, floor(log2 area)), floor(bins * hit / area)].  `scratch=` (an int32 tensor of at least 4 * B * H * W elements: the
+    four planes area0, hit0, area1, hit1 at the root pixels, zeroed by the call and readable afterwards) makes the call allocation-free; without it a buffer
+    cached per device and stream is used."""
+    bins = check_segment_bins(bins)
+    for only in (True, False):      # dtypes and shapes of all three first, then the devices
+        pred = _check_map(pred, "pred", torch.uint8, "a uint8 class map", shape_only=only)
+        root_pred = _check_root(root_pred, "root_pred", pred, only)
+        root_label = _check_root(root_label, "root_label", pred, only)
+    B, H, W = (int(v) for v in pred.shape)
+    C = prep.num_classes
+    n = 4 * B * H * W
+    with torch.cuda.device(pred.device):
+        if scratch is None:
+            scratch = _cached_planes(_SEGMENT_SCRATCH, n, 1, pred.device, "the scratch planes of segment_counts")[0]
+        elif (not isinstance(scratch, torch.Tensor) or scratch.dtype != torch.int32 or scratch.numel() < n or scratch.device != pred.device
+              or not scratch.is_contiguous()):
+            raise RuntimeError(f"mmsa.evaluate: scratch must be a contiguous int32 tensor of at least 4 * B * H * W = {n} elements on {pred.device}")
+        largs, counts, tab = _slot_launch(prep, labels, B, H, W, pred.device, counts, "counts", (2, C, SIZE_BUCKETS, bins + 1), slots)
+        lib.call("mmsa_eval_segments", pred.data_ptr(), largs[0], B, H, W, largs[1], largs[2], largs[3], C, largs[4], largs[5], tab, counts.shape[0],
+                 root_pred.data_ptr(), root_label.data_ptr(), bins, scratch.data_ptr(), counts.data_ptr(), ops._stream())
+    return counts
+
+
+def _segments(counts):
+    c = np.asarray(counts)
+    if c.ndim < 4 or c.shape[-4] != 2 or c.shape[-2] != SIZE_BUCKETS or c.shape[-1] < 2 or c.dtype.kind not in "iu":
+        raise ValueError(f"mmsa.evaluate: segment counts are an integer [..., 2, C, {SIZE_BUCKETS}, bins + 1] array, got {c.dtype} {c.shape}")
+    return c.astype(np.int64, copy=False)
+
+
+def _area_bucket(v, name, lo):
+    """An area limit -> its bucket edge: a power of two 2^s, lo <= s <= 23; anything else raises ValueError naming the nearest edges."""
+    if not _is_int(v, 1, 1 << 62):
+        raise ValueError(f"mmsa.evaluate: {name} = {v!r}; a pixel count (a power of two, the edge of a size bucket) is expected")
+    v = int(v)
+    s = v.bit_length() - 1
+    if v != 1 << s or not lo <= s <= SIZE_BUCKETS - 1:
+        below, above = max(lo, min(s, SIZE_BUCKETS - 1)), max(lo, min(s + 1, SIZE_BUCKETS - 1))
+        raise ValueError(f"mmsa.evaluate: {name} = {v} is not the edge of a size bucket: the counts keep floor(log2 area) only and cannot split a bucket; the "
+                         f"nearest edges are {1 << below} and {1 << above} (edges run from {1 << lo} to {1 << (SIZE_BUCKETS - 1)})")
+    return s
+
+
+def segment_totals_of(counts, min_area=1, max_area=None):
+    """Fold the size buckets of int64 [..., 2, C, 24, bins + 1] segment counts -> int64 [..., 2, C, bins + 1]: the segments with min_area <= area < max_area
+    (None: no upper limit).  Both limits must be powers of two, the edges of the buckets (at most 2^23, from where the last bucket holds everything)."""
+    c = _segments(counts)
+    s0 = _area_bucket(min_area, "min_area", 0)
+    s1 = SIZE_BUCKETS if max_area is None else _area_bucket(max_area, "max_area", 1)
+    if s1 <= s0:
+        raise ValueError(f"mmsa.evaluate: max_area = {max_area} must be above min_area = {min_area}")
+    return c[..., s0:s1, :].sum(-2)
+
+
+def _coverage_bin(threshold, bins):
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating, Fraction)) or not 0 <= threshold <= 1:
+        raise ValueError(f"mmsa.evaluate: threshold = {threshold!r}; a coverage in [0, 1] is expected")
+    k = round(float(threshold) * bins)
+    if abs(float(threshold) * bins - k) > 1e-9:
+        lo = math.floor(float(threshold) * bins)
+        raise ValueError(f"mmsa.evaluate: threshold {float(threshold)!r} is not a bin edge of {bins} coverage bins (threshold * bins must be an integer): the "
+                         f"counts cannot split bin {lo}; the nearest edges are {lo / bins!r} and {(lo + 1) / bins!r}")
+    return int(k)
+
+
+def segment_rate_of(counts, side, threshold=0.5, min_area=1, max_area=None):
+    """The share of the segments of one side whose coverage is at least `threshold`, per class -> float64 [..., C]; 0 / 0 is NaN (a class without segments in
+    that size range).  side 0: the label segments -- the segment RECALL, "was the object found"; side 1: the prediction segments -- the segment PRECISION, "is
+    the blob real".  threshold * bins must be an integer: coverage >= k / bins holds iff the stored bin is >= k, so the rate is exact."""
+    if isinstance(side, bool) or side not in (0, 1):
+        raise ValueError(f"mmsa.evaluate: side = {side!r}; 0 (label segments: recall) or 1 (prediction segments: precision) is expected")
+    t = segment_totals_of(counts, min_area, max_area)[..., int(side), :, :]
+    k = _coverage_bin(threshold, t.shape[-1] - 1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return t[..., k:].sum(-1).astype(np.float64) / t.sum(-1).astype(np.float64)
+
+
+def segment_f_of(counts, threshold=0.5, min_area=1, max_area=None):
+    """The harmonic mean of the segment precision and the segment recall per class -> float64 [..., C]; NaN where either is, and where both are 0."""
+    r = segment_rate_of(counts, 0, threshold, min_area, max_area)
+    p = segment_rate_of(counts, 1, threshold, min_area, max_area)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return 2 * p * r / (p + r)
+
+
+class SegmentEvaluator(_SlotOwner):
+    """Owns the segment counts of an evaluation run, as Evaluator owns the confusion counts: int64 [n_slots, 2, C, 24, bins + 1] on the device (`.counts`; side 0
+    the label segments, side 1 the prediction segments, by class, size bucket min(23, floor(log2 area)) and coverage bin floor(bins * hit / area)).  Slots and
+    cases as Evaluator's.  add() makes the two component launches (prediction and labels, at `connectivity`) and the count launch into buffers cached per shape
+    and stream: no host sync, and no allocation once the buffers of a shape exist.  Every class-map entry's `segments=` takes it.  Across ranks:
+    mmsa.dist.allreduce_counts(se.counts)."""
+    _who, _read, _one = "SegmentEvaluator", "host_counts()", "a SegmentEvaluator"
+
+    def __init__(self, prep, bins=DEFAULT_SEGMENT_BINS, connectivity=8, cases=None, images=MAX_IMAGES, device=None):
+        who = "mmsa.SegmentEvaluator"
+        self.prep = prep
+        self.n_bins = check_segment_bins(bins, who)
+        self.connectivity = check_connectivity(connectivity, who)
+        if not 2 <= prep.num_classes <= 254:
+            raise RuntimeError(f"{who}: {prep.num_classes} classes; a uint8 class map has 2..254")
+        self._init_slots(cases, images)
+        self._maps = {}         # (B, H, W, device, stream) -> (root_pred, root_label, scratch)
+        self._init_buffer(device)
+
+    def _trailing(self):
+        return (2, self.prep.num_classes, SIZE_BUCKETS, self.n_bins + 1)
+
+    def _maps_for(self, B, H, W, device):
+        key = (B, H, W, device, ops._stream())
+        m = self._maps.get(key)
+        if m is None:
+            if _capturing(device):
+                raise RuntimeError(f"mmsa.{self._who}: the root maps of a {B} x {H} x {W} batch cannot be allocated during a graph capture: run one add() of "
+                                   "this shape before capturing")
+            m = self._maps[key] = (torch.empty(B, H, W, dtype=torch.int32, device=device), torch.empty(B, H, W, dtype=torch.int32, device=device),
+                                   torch.empty(4, B, H, W, dtype=torch.int32, device=device))
+        return m
+
+    def add(self, pred, labels, case=None, slots=None):
+        """Count a batch of stored class maps: the components of both sides and the segment counts; no host sync, no allocation once the buffers for the
+        shape exist."""
+        pred = _check_pred(pred)
+        B, H, W = (int(v) for v in pred.shape)
+        with torch.cuda.device(pred.device):
+            self.prep.launch_args(labels, B, H, W, pred.device)      # the label side checked before the first launch
+            return self._add(pred, B, case, slots, self._launches, pred, labels, guard=False)      # this guard serves
+
+    def _launches(self, pred, labels, buf, use):
+        B, H, W = (int(v) for v in pred.shape)
+        root_pred, root_label, scratch = self._maps_for(B, H, W, pred.device)
+        components(pred, num_classes=self.prep.num_classes, connectivity=self.connectivity, out=root_pred)
+        components(labels, labels_prep=self.prep, size=(H, W), connectivity=self.connectivity, out=root_label)
+        segment_counts(pred, labels, self.prep, root_pred, root_label, self.n_bins, buf, scratch, use)
+
+    def host_counts(self):
+        """The counts on the host (the ONE device-to-host copy): int64 numpy [n, 2, C, 24, bins + 1], n = images added so far / cases."""
+        return self._host()
+
+    def _of(self, slot):
+        return self._pick(self.host_counts(), slot)
+
+    def recall(self, threshold=0.5, min_area=1, max_area=None, slot=None):
+        """The share of the LABEL segments covered to at least `threshold` by correct pixels, per class: float64 [C] (`segment_rate_of`, side 0)."""
+        return segment_rate_of(self._of(slot), 0, threshold, min_area, max_area)
+
+    def precision(self, threshold=0.5, min_area=1, max_area=None, slot=None):
+        """The share of the PREDICTION segments covered to at least `threshold` by correct pixels, per class: float64 [C] (side 1)."""
+        return segment_rate_of(self._of(slot), 1, threshold, min_area, max_area)
+
+    def f1(self, threshold=0.5, min_area=1, max_area=None, slot=None):
+        return segment_f_of(self._of(slot), threshold, min_area, max_area)
+
+    def by_size(self, threshold=0.5, slot=None):
+        """The rates per power-of-two size bucket -> OrderedDict: 'min_area' int64 [24] (2^s; the last bucket has no upper end), 'label_segments' /
+        'pred_segments' int64 [24, C], 'recall' / 'precision' float64 [24, C] (NaN where a class has no segment of that size)."""
+        c = self._of(slot)
+        k = _coverage_bin(threshold, self.n_bins)
+        total = np.moveaxis(c.sum(-1), -1, -2)                              # [2, 24, C]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rate = np.moveaxis(c[..., k:].sum(-1), -1, -2).astype(np.float64) / total.astype(np.float64)
+        return OrderedDict(min_area=1 << np.arange(SIZE_BUCKETS, dtype=np.int64), label_segments=total[0], pred_segments=total[1], recall=rate[0],
+                           precision=rate[1])
+
+    def summary(self, slot=None):
+        """The numbers of label and prediction segments (classes < C, area > 0) and mSR / mSP / mSF -- segment recall, precision and their harmonic mean at
+        coverage 0.5, nanmean over the classes that have segments, rounded to two places of a percent; at an odd `bins` the threshold is the next edge
+        above one half."""
+        c = self._of(slot)
+        thr = Fraction((self.n_bins + 1) // 2, self.n_bins)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)
+            return OrderedDict(label_segments=int(c[0].sum()), pred_segments=int(c[1].sum()),
+                               mSR=_round_percent(np.nanmean(segment_rate_of(c, 0, thr))), mSP=_round_percent(np.nanmean(segment_rate_of(c, 1, thr))),
+                               mSF=_round_percent(np.nanmean(segment_f_of(c, thr))), threshold=float(thr), connectivity=self.connectivity)

@@ -109,6 +109,10 @@ SIGNATURES = {
     "mmsa_boundary_distance_u8": [P, I, I, I, P, P, P, I, I, I, I, P, P, P],
     "mmsa_eval_boundary_d2": [P, P, I, I, I, I, I, P, I, P, P, P, I, P, P, I, P, P],
     "mmsa_eval_boundary_displacement": [P, P, I, I, I, I, I, P, I, P, P, P, I, P, P, I, P, P],
+    "mmsa_components_u8": [P, I, I, I, P, P, P, I, I, I, P, P],
+    "mmsa_component_area": [P, I, I, I, P, P],
+    "mmsa_suppress_small_u8": [P, P, P, I, I, I, I, I, P, P],
+    "mmsa_eval_segments": [P, P, I, I, I, I, I, P, I, P, P, P, I, P, P, I, P, P, P],
     "mmsa_slide_argmax_eval": [P, I, I, I, I, P, P, I, I, I, I, I, P, P, I, I, P, P, P, P, I, P, P],
     "mmsa_render_u8": [P, L, L, I, I, I, P, I, I, P, I, I, I, c_double, c_double, P, P],
     "mmsa_render_denorm_f32": [P, L, L, I, I, I, P, I, I, P, I, I, I, P, P, I, I, c_double, c_double, P, P],
