@@ -637,6 +637,29 @@ int mmsa_eval_segments(const unsigned char* pred, const unsigned char* label, in
                        const int* ymap, const int* xmap, const int* slots, int n_slots, const int* root_pred, const int* root_label, int bins, int* scratch,
                        int64_t* counts, mmsa_stream_t stream);
 
+/* --- panoptic quality (Kirillov et al., "Panoptic Segmentation", CVPR 2019): which prediction segment IS which label segment (csrc/pairs.hip).  Maps, codes,
+ *   connectivity and roots are components_u8's and eval_segments'.  A pixel takes part iff its own label code L is not 255; a HIT pixel has L < C and
+ *   P == L; inter(p, g) = the hit pixels with root_pred == p and root_label == g; area_g / area_p = planes 0 / 2 of eval_segments' scratch.
+ *   segment_pairs: ONE launch fills an open-addressing table with the intersections: keys int64 [capacity] (set to all-ones = empty by the entry), counts
+ *     int32 [capacity] (zeroed by the entry), capacity a power of two, 2 .. 2^30.  Every hit pixel of image b forms key = ((b * H * W + root_label) << 31) |
+ *     root_pred; counts[slot of key] = inter.  slot = (key * 0x9e3779b97f4a7c15 mod 2^64) >> (64 - log2 capacity), then linear probing over at most
+ *     min(128, capacity) slots; a key that finds none adds its pixels to *overflow (DEVICE int, zeroed by the CALLER, as `uncovered` of the class-map entries)
+ *     and is dropped.  Which key sits in which slot depends on the schedule; the multiset of (key, count) and -- while nothing is dropped -- the set of
+ *     occupied slots do not.  2 <= C <= 254, B * H * W < 2^31, B <= 65535.
+ *   eval_panoptic: the label side (lut, ymap / xmap, slots: HOST int [B]) is eval_segments'; planes = its scratch, as that entry left it; keys / counts as
+ *     segment_pairs left them.  match int32 [2, B, H, W] is set to -1 here.  Launch 1, a lane per slot: an occupied slot with 3 * inter > area_p + area_g
+ *     (IoU > 1/2, strict; at most one per segment) writes match[0][b][root_label] = root_pred and match[1][b][root_pred] = root_label and, where the label
+ *     code c at root_label is < C, adds 1 at [slot, c, s, 0] (TP) and floor(inter * 2^24 / (area_p + area_g - inter)) at [slot, c, s, 3] of pq_counts int64
+ *     [n_slots, C, 24, 4], ADDED to; s = min(23, floor(log2 area_g)).  Launch 2, a lane per pixel: a label root with area_g > 0, c < C and no match adds 1
+ *     at [slot, c, s, 2] (FN); a prediction root with area_p > 0, P < C and no match adds 1 at [slot, P, min(23, floor(log2 area_p)), 1] (FP).
+ *     2 <= C <= 254, 1 <= B <= 64, n_slots * C * 96 < 2^31. --- */
+int mmsa_segment_pairs(const unsigned char* pred, const unsigned char* label, int Hl, int Wl, const unsigned char* lut, int C, const int* ymap,
+                       const int* xmap, const int* root_pred, const int* root_label, int B, int H, int W, int64_t* keys, int* counts, long capacity,
+                       int* overflow, mmsa_stream_t stream);
+int mmsa_eval_panoptic(const unsigned char* pred, const unsigned char* label, int B, int H, int W, int Hl, int Wl, const unsigned char* lut, int C,
+                       const int* ymap, const int* xmap, const int* slots, int n_slots, const int* root_pred, const int* root_label, const int* planes,
+                       const int64_t* keys, const int* counts, long capacity, int* match, int64_t* pq_counts, mmsa_stream_t stream);
+
 /* --- the picture of a prediction (segmentation/mmseg_custom/apis/test_bs.py:257-349, the `--show` / `--show-dir` output): `tensor2imgs` (test_bs.py:18-63) on
  *     planes 0..2 of the input tensor -> the crop `img[:h, :w]` (test_bs.py:275-276) -> `show_result` (tools/color_gt_according_palette.py:23-81:
  *     color_seg[seg == label] = color, channels reversed, img * (1 - opacity) + color_seg * opacity, .astype(uint8)), in one pass.

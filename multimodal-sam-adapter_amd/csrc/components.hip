@@ -23,6 +23,7 @@
 // lowest pending lane's root is broadcast, a ballot counts its lanes, one lane adds their number: the form of csrc/cal_wave.h, at most 64 rounds).
 #include "common.h"
 #include "eval_hist.h"
+#include "comp_shared.h"
 
 #define COMP_TW 64
 #define COMP_TH 32
@@ -30,7 +31,6 @@
 #define COMP_PW (COMP_TW + 2)                 // the staged codes with their border
 #define COMP_PH (COMP_TH + 2)
 #define COMP_NONE 0xffffu                     // no pixel (outside the tile or the image): equal to no code
-#define COMP_SIZE_BUCKETS 24                  // s = min(23, floor(log2 area))
 #define COMP_MAX_BINS 64
 #define COMP_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
@@ -187,12 +187,6 @@ __global__ __launch_bounds__(256) void components_flatten_kernel(int H, int W, i
   img[i] = r;
 }
 
-static inline int comp_check_size(const char* name, int B, int H, int W) {
-  MMSA_CHECK_ARG(B > 0 && B <= 65535 && H > 0 && W > 0 && (long)B * H * W < (1l << 31),
-                 "%s: bad map size %d x %d x %d (B * H * W must be positive and below 2^31, B at most 65535)", name, B, H, W);
-  return MMSA_OK;
-}
-
 extern "C" int mmsa_components_u8(const unsigned char* src, int B, int Hs, int Ws, const unsigned char* lut, const int* ymap, const int* xmap, int H, int W,
                                   int connectivity, int* root, hipStream_t stream) {
   const char* name = "components_u8";
@@ -217,26 +211,7 @@ extern "C" int mmsa_components_u8(const unsigned char* src, int B, int Hs, int W
   return MMSA_OK;
 }
 
-// ---- the pointwise passes over root maps
-// dst[key] += the number of lanes that hold `key` (and dst2[key] += those of them with `flag`, where dst2 is given), ONE atomicAdd per (wave, key).  Called by
-// every lane of a wave together; `has` = false: a lane without a pixel.  At most 64 distinct keys in a wave: 64 rounds.
-__device__ __forceinline__ void comp_wave_add(int* dst, int* dst2, bool has, int key, bool flag) {
-  bool pending = has;
-  unsigned long long m = __ballot(pending);
-  for (int r = 0; r < 64 && m != 0ull; ++r) {
-    const int lead = __ffsll((long long)m) - 1;
-    const int lk = __builtin_amdgcn_readlane(key, lead);
-    const bool same = pending && key == lk;
-    const unsigned long long ms = __ballot(same), mf = __ballot(same && flag);
-    if ((int)(threadIdx.x & 63u) == lead) {
-      atomicAdd(&dst[lk], (int)__popcll(ms));
-      if (dst2 && mf) atomicAdd(&dst2[lk], (int)__popcll(mf));
-    }
-    pending = pending && !same;
-    m &= ~ms;
-  }
-}
-
+// ---- the pointwise passes over root maps (comp_wave_add, comp_label_code, seg_count_add and the size bucket: csrc/comp_shared.h, shared with csrc/pairs.hip)
 // grid (cdiv(H * W, 256), B): a wave lies inside one image
 __global__ __launch_bounds__(256) void component_area_kernel(const int* __restrict__ root, int H, int W, int* area) {
   const long HW = (long)H * W, i = (long)blockIdx.x * 256 + threadIdx.x, base = blockIdx.y * HW;
@@ -244,12 +219,6 @@ __global__ __launch_bounds__(256) void component_area_kernel(const int* __restri
   int r = has ? root[base + i] : 0;
   r = min(max(r, 0), (int)HW - 1);                                           // a root map from elsewhere cannot send the add outside the plane
   comp_wave_add(area + base, nullptr, has, r, false);
-}
-
-static inline int comp_zero(const char* name, void* p, size_t bytes, hipStream_t stream) {
-  const hipError_t e = hipMemsetAsync(p, 0, bytes, stream);
-  MMSA_CHECK_ARG(e == hipSuccess, "%s: zeroing the planes failed: %s", name, hipGetErrorString(e));
-  return MMSA_OK;
 }
 
 extern "C" int mmsa_component_area(const int* root, int B, int H, int W, int* area, hipStream_t stream) {
@@ -288,18 +257,6 @@ extern "C" int mmsa_suppress_small_u8(const unsigned char* pred, const int* root
   return MMSA_OK;
 }
 
-// pixel i of image b: its label code (a class < C, C, or MMSA_EVAL_IGNORE), read through the tables where there are any (csrc/distance.hip dist_label_code,
-// with the LUT in global memory: these passes keep no LDS)
-__device__ __forceinline__ int comp_label_code(const EvalLabel& ev, int b, int W, int i) {      // H * W < 2^31
-  long at = i;
-  if (ev.ymap) {
-    const int y = i / W, x = i - y * W;
-    at = (long)min(max(ev.ymap[y], 0), ev.Hl - 1) * ev.Wl + min(max(ev.xmap[x], 0), ev.Wl - 1);
-  }
-  const int l = ev.lut[ev.label[(long)b * ev.Hl * ev.Wl + at]];
-  return l == MMSA_EVAL_IGNORE ? l : min(l, ev.C);
-}
-
 struct SegMaps {
   const unsigned char* pred;        // [B, H, W]
   const int* root_pred;             // [B, H, W]
@@ -324,28 +281,10 @@ __global__ __launch_bounds__(256) void eval_segments_area_kernel(SegMaps m, Eval
   comp_wave_add(m.planes + 2 * plane + base, m.planes + 3 * plane + base, has, rp, hit);
 }
 
-// counts[bin] += 1 for every lane with bin >= 0: two rounds of the merge above first (a frame's root pixels of one class and size mostly share a cell), the
-// rest lane by lane.  Called by every lane of a wave together.
-__device__ __forceinline__ void seg_count_add(unsigned long long* counts, int bin) {
-  bool pending = bin >= 0;
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    const unsigned long long m = __ballot(pending);
-    if (m == 0ull) return;
-    const int lead = __ffsll((long long)m) - 1;
-    const int lb = __builtin_amdgcn_readlane(bin, lead);
-    const bool same = pending && bin == lb;
-    const unsigned long long ms = __ballot(same);
-    if ((int)(threadIdx.x & 63u) == lead) atomicAdd(&counts[lb], (unsigned long long)__popcll(ms));
-    pending = pending && !same;
-  }
-  if (pending) atomicAdd(&counts[bin], 1ull);
-}
-
 // the cell of a segment inside [C, 24, bins + 1] (at most 254 * 24 * 65 cells), or -1: area > 0, code c < C
 __device__ __forceinline__ int seg_cell(int c, int C, int area, int hit, int bins) {
   if (area <= 0 || c >= C) return -1;
-  const int s = min(COMP_SIZE_BUCKETS - 1, 31 - __clz(area));
+  const int s = comp_size_bucket(area);
   const int k = (int)((long)bins * hit / area);                              // hit <= area: k <= bins, k == bins iff hit == area
   return (c * COMP_SIZE_BUCKETS + s) * (bins + 1) + k;
 }

@@ -53,7 +53,13 @@ are real.  Its unit is the segment, a connected component of one code: `componen
 without its blobs below an area) are pointwise passes on top, and `segment_counts` / `SegmentEvaluator` reduce (class map, label map, the two root maps) to int64
 [2, C, 24, bins + 1] per slot (mmsa_eval_segments): the label segments (side 0) and the prediction segments (side 1) by class, power-of-two size bucket and the
 share of the segment that is covered by a correct pixel -- from which `segment_rate_of` forms the segment recall and precision at a coverage threshold and
-`segment_f_of` their harmonic mean in float64 on the host."""
+`segment_f_of` their harmonic mean in float64 on the host.
+
+Panoptic quality asks which prediction segment IS which label segment: `segment_pairs` fills a hash table on the device with the intersection of every (label
+segment, prediction segment) pair that shares a correct pixel (mmsa_segment_pairs, csrc/pairs.hip; `PairTable`, the compact pair list), `panoptic_counts` /
+`PanopticEvaluator` match the pairs by IoU > 1/2 -- unique, tested in integers -- and reduce them to int64 [C, 24, 4] per slot (mmsa_eval_panoptic): TP, FP, FN
+and the fixed-point IoU sum by class and size bucket, from which `panoptic_quality_of` forms PQ = SQ * RQ per class and `panoptic_summary_of` their means in
+float64 on the host."""
 import ctypes
 import math
 import warnings
@@ -2076,3 +2082,332 @@ class SegmentEvaluator(_SlotOwner):
             return OrderedDict(label_segments=int(c[0].sum()), pred_segments=int(c[1].sum()),
                                mSR=_round_percent(np.nanmean(segment_rate_of(c, 0, thr))), mSP=_round_percent(np.nanmean(segment_rate_of(c, 1, thr))),
                                mSF=_round_percent(np.nanmean(segment_f_of(c, thr))), threshold=float(thr), connectivity=self.connectivity)
+
+
+# ---- panoptic quality: which prediction segment IS which label segment (csrc/pairs.hip) ----
+# Segments, codes and roots are the section's above.  inter(p, g) = the hit pixels (L < C and P == L) with root_pred == p and root_label == g; p and g MATCH iff
+# 3 * inter > area_p + area_g -- IoU > 1/2, strict, in integers -- and a segment has at most one match.  Over the segments of class c < C with area > 0 a
+# matched pair is one TP (and adds floor(inter * 2^24 / union) to the IoU sum), an unmatched label segment one FN, an unmatched prediction segment one FP, at
+# the size bucket of area_g (TP, FN) or area_p (FP): int64 [C, 24, 4] per slot.
+PAIR_EMPTY = -1                    # an empty key of the pair table (all ones)
+PAIR_MAX_PROBES = 128              # csrc/pairs.hip PAIR_MAX_PROBES: the slots a key looks at before it is dropped into `overflow`
+PAIR_MAX_CAPACITY = 1 << 30        # csrc/pairs.hip PAIR_MAX_LOG2
+IOU_ONE = 1 << 24                  # the fixed-point unit of the IoU sum (Calibration's CONF_ONE)
+PQ_FIELDS = ("tp", "fp", "fn", "iou_sum")
+
+
+def check_pair_capacity(capacity, who="mmsa.evaluate"):
+    """The slots of a pair table: a power of two, 2 .. 2^30; anything else raises ValueError naming the neighbouring powers."""
+    if not _is_int(capacity, 1, 1 << 62):
+        raise ValueError(f"{who}: capacity = {capacity!r}; a number of table slots (a power of two, 2 .. 2^30) is expected")
+    v = int(capacity)
+    s = v.bit_length() - 1
+    if v != 1 << s or not 2 <= v <= PAIR_MAX_CAPACITY:
+        below, above = min(max(1 << s, 2), PAIR_MAX_CAPACITY), min(max(1 << (s + 1), 2), PAIR_MAX_CAPACITY)
+        raise ValueError(f"{who}: capacity = {v} is not a power of two in 2 .. 2^30 (the slot of a key is the top bits of its hash); the neighbouring powers "
+                         f"are {below} and {above}")
+    return v
+
+
+def default_pair_capacity(n):
+    """The default slots for maps of n = B * H * W pixels: the next power of two >= n / 2 (at least 2).  A table must hold every distinct (label segment,
+    prediction segment) pair that shares a hit pixel; maps of one-pixel segments that agree everywhere (n pairs) need capacity= spelled out."""
+    return max(2, 1 << max(0, (int(n) + 1) // 2 - 1).bit_length())
+
+
+class PairTable:
+    """The pair table of `segment_pairs` on the device: keys int64 [capacity] (-1: empty; else ((b * H * W + root_label) << 31) | root_pred), counts int32
+    [capacity] (the pair's hit pixels) and overflow int32 [1] (the hit pixels of keys that found no slot: the table was too small).  Which key sits in which
+    slot depends on the schedule; the multiset of (key, count) does not.  `shape` = (B, H, W) of the maps it was filled from."""
+
+    def __init__(self, keys, counts, overflow, shape=None):
+        self.keys, self.counts, self.overflow, self.shape = keys, counts, overflow, shape
+
+    @property
+    def capacity(self):
+        return int(self.keys.numel())
+
+    @classmethod
+    def empty(cls, capacity, device):
+        capacity = check_pair_capacity(capacity)
+        return cls(torch.empty(capacity, dtype=torch.int64, device=device), torch.empty(capacity, dtype=torch.int32, device=device),
+                   torch.zeros(1, dtype=torch.int32, device=device))
+
+    def _check(self, device):
+        k, c, o = self.keys, self.counts, self.overflow
+        ok = all(isinstance(t, torch.Tensor) and t.is_contiguous() and t.device == device for t in (k, c, o))
+        if not ok or k.dtype != torch.int64 or c.dtype != torch.int32 or o.dtype != torch.int32 or k.dim() != 1 or c.shape != k.shape or o.numel() != 1:
+            raise RuntimeError(f"mmsa.evaluate: a PairTable holds contiguous keys int64 [capacity], counts int32 [capacity] and overflow int32 [1] on {device}")
+        check_pair_capacity(k.numel())
+        return self
+
+    def host(self):
+        """The compact pair list -> int64 numpy arrays (image, root_label, root_pred, inter), sorted by (image, root_label, root_pred): two device-to-host
+        copies and the overflow word.  Raises RuntimeError where the table overflowed: the list would be short."""
+        lost = int(self.overflow.item())
+        if lost:
+            raise RuntimeError(f"mmsa.evaluate: the pair table of {self.capacity} slots overflowed ({lost} hit pixels were dropped): pass a larger capacity=")
+        if self.shape is None:
+            raise RuntimeError("mmsa.evaluate: a PairTable without its maps' shape= (B, H, W) cannot split a key into image and root")
+        keys, counts = self.keys.cpu().numpy(), self.counts.cpu().numpy()
+        used = keys != PAIR_EMPTY
+        keys, counts = keys[used], counts[used].astype(np.int64)
+        order = np.argsort(keys, kind="stable")
+        keys, counts = keys[order], counts[order]
+        HW = int(self.shape[1]) * int(self.shape[2])
+        g = keys >> 31
+        return g // HW, g % HW, keys & ((1 << 31) - 1), counts
+
+
+def _check_pair_maps(pred, root_pred, root_label):
+    for only in (True, False):      # dtypes and shapes of all three first, then the devices
+        pred = _check_map(pred, "pred", torch.uint8, "a uint8 class map", shape_only=only)
+        root_pred = _check_root(root_pred, "root_pred", pred, only)
+        root_label = _check_root(root_label, "root_label", pred, only)
+    if pred.numel() == 0:
+        raise RuntimeError(f"mmsa.evaluate: an empty map {tuple(pred.shape)}")
+    return pred, root_pred, root_label
+
+
+def _check_classes_u8(C, who="mmsa.evaluate"):
+    if not 2 <= C <= 254:
+        raise RuntimeError(f"{who}: {C} classes; a uint8 class map has 2..254")
+    return C
+
+
+@torch.no_grad()
+def segment_pairs(pred, labels, prep, root_pred, root_label, capacity=None, table=None):
+    """The intersections of the (label segment, prediction segment) pairs of the uint8 class maps pred [B, H, W] and the raw labels (two memsets and one
+    launch, mmsa_segment_pairs) -> PairTable on the device: the compact segment-pair list.  root_pred / root_label are `components`' of the two sides at one
+    connectivity.  Every pixel whose label code L is a class and equals P = min(pred, C) adds 1 to the pair (root_label, root_pred) of its image.
+    `capacity` (a power of two; default: the next one >= B * H * W / 2) sizes a new table whose overflow word starts at 0; `table=` (a PairTable of any
+    capacity) is emptied and filled instead, allocation-free, and its overflow word is ADDED to (zero it to start anew).  Nothing is read back: look at
+    `table.overflow`, or call `table.host()`, which raises where hit pixels were dropped."""
+    if capacity is not None:
+        capacity = check_pair_capacity(capacity)
+    pred, root_pred, root_label = _check_pair_maps(pred, root_pred, root_label)
+    B, H, W = (int(v) for v in pred.shape)
+    C = _check_classes_u8(prep.num_classes)
+    if B * H * W >= 1 << 31:
+        raise RuntimeError(f"mmsa.evaluate: {B} x {H} x {W} pixels; a pair key holds a batch index in 31 bits (B * H * W < 2^31)")
+    with torch.cuda.device(pred.device):
+        largs = prep.launch_args(labels, B, H, W, pred.device)
+        if table is None:
+            table = PairTable.empty(default_pair_capacity(B * H * W) if capacity is None else capacity, pred.device)
+        else:
+            if not isinstance(table, PairTable):
+                raise RuntimeError(f"mmsa.evaluate: table= takes an mmsa.evaluate.PairTable, got {type(table).__name__}")
+            table._check(pred.device)
+            if capacity is not None and capacity != table.capacity:
+                raise RuntimeError(f"mmsa.evaluate: capacity={capacity} with a table of {table.capacity} slots")
+        table.shape = (B, H, W)
+        lib.call("mmsa_segment_pairs", pred.data_ptr(), largs[0], largs[1], largs[2], largs[3], C, largs[4], largs[5], root_pred.data_ptr(),
+                 root_label.data_ptr(), B, H, W, table.keys.data_ptr(), table.counts.data_ptr(), table.capacity, table.overflow.data_ptr(), ops._stream())
+    return table
+
+
+@torch.no_grad()
+def panoptic_counts(pred, labels, prep, root_pred, root_label, planes, table, counts=None, match=None, slots=None):
+    """Match the pairs of `table` by IoU > 1/2 and ADD the TP / FP / FN counts and the IoU sum into counts[slots[b]] (one memset and two launches,
+    mmsa_eval_panoptic) -> counts, int64 [n_slots, C, 24, 4] on the device ([.., c, s, :] = TP, FP, FN, sum of floor(IoU * 2^24) of the TPs; s = the size
+    bucket of the label segment, of the prediction segment for an FP).  `planes` is the scratch `segment_counts` filled for the same maps (int32, at least
+    4 * B * H * W elements: area0, hit0, area1, hit1), `table` what `segment_pairs` returned for them.  `match=` (int32 [2, B, H, W]; a new tensor by default)
+    holds afterwards, at every label root, its prediction root and, at every prediction root, its label root; -1 elsewhere.  Nothing here looks at
+    `table.overflow`: a table that overflowed gives short intersections -- PanopticEvaluator refuses to report from one."""
+    pred, root_pred, root_label = _check_pair_maps(pred, root_pred, root_label)
+    B, H, W = (int(v) for v in pred.shape)
+    C = _check_classes_u8(prep.num_classes)
+    n = 4 * B * H * W
+    if (not isinstance(planes, torch.Tensor) or planes.dtype != torch.int32 or planes.numel() < n or planes.device != pred.device or not planes.is_contiguous()):
+        raise RuntimeError(f"mmsa.evaluate: planes must be a contiguous int32 tensor of at least 4 * B * H * W = {n} elements on {pred.device} (the scratch of "
+                           "segment_counts)")
+    if not isinstance(table, PairTable):
+        raise RuntimeError(f"mmsa.evaluate: table takes an mmsa.evaluate.PairTable, got {type(table).__name__}")
+    table._check(pred.device)
+    if match is not None:
+        _check_int_plane(match, "match", (2, B, H, W), pred.device, "the match planes")
+    with torch.cuda.device(pred.device):
+        if match is None:
+            match = torch.empty(2, B, H, W, dtype=torch.int32, device=pred.device)
+        largs, counts, tab = _slot_launch(prep, labels, B, H, W, pred.device, counts, "counts", (C, SIZE_BUCKETS, 4), slots)
+        lib.call("mmsa_eval_panoptic", pred.data_ptr(), largs[0], B, H, W, largs[1], largs[2], largs[3], C, largs[4], largs[5], tab, counts.shape[0],
+                 root_pred.data_ptr(), root_label.data_ptr(), planes.data_ptr(), table.keys.data_ptr(), table.counts.data_ptr(), table.capacity,
+                 match.data_ptr(), counts.data_ptr(), ops._stream())
+    return counts
+
+
+def _panoptic(counts):
+    c = np.asarray(counts)
+    if c.ndim < 3 or c.shape[-2] != SIZE_BUCKETS or c.shape[-1] != 4 or c.dtype.kind not in "iu":
+        raise ValueError(f"mmsa.evaluate: panoptic counts are an integer [..., C, {SIZE_BUCKETS}, 4] array (TP, FP, FN, IoU sum), got {c.dtype} {c.shape}")
+    return c.astype(np.int64, copy=False)
+
+
+def panoptic_quality_of(counts, min_area=1, max_area=None):
+    """int64 [..., C, 24, 4] panoptic counts -> OrderedDict per class: 'pq' = IoU sum / (TP + FP / 2 + FN / 2), 'sq' = IoU sum / TP, 'rq' = TP / (TP + FP / 2
+    + FN / 2), float64 [..., C], 0 / 0 is NaN (a class without segments; 'sq': without a TP), and 'tp', 'fp', 'fn' int64 [..., C] -- over the segments with
+    min_area <= area < max_area (powers of two, the bucket edges of `segment_totals_of`; the area is the label segment's, the prediction segment's for an
+    FP).  The IoU sum is the sum of floor(IoU * 2^24) / 2^24: 'sq' lies below the exact mean IoU by less than 2^-24, 'pq' below sq * rq's exact value by
+    less than 2^-24 as well."""
+    c = _panoptic(counts)
+    s0 = _area_bucket(min_area, "min_area", 0)
+    s1 = SIZE_BUCKETS if max_area is None else _area_bucket(max_area, "max_area", 1)
+    if s1 <= s0:
+        raise ValueError(f"mmsa.evaluate: max_area = {max_area} must be above min_area = {min_area}")
+    t = c[..., s0:s1, :].sum(-2)
+    tp, fp, fn = t[..., 0], t[..., 1], t[..., 2]
+    iou = t[..., 3].astype(np.float64) / IOU_ONE
+    den = tp + 0.5 * fp + 0.5 * fn
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return OrderedDict(pq=iou / den, sq=iou / tp.astype(np.float64), rq=tp / den, tp=tp, fp=fp, fn=fn)
+
+
+def panoptic_summary_of(counts, things=None):
+    """PQ / SQ / RQ of int64 [C, 24, 4] counts: the nanmean over the classes present (PQ, RQ: with a segment on either side; SQ: with a TP), rounded to two
+    places of a percent, and the totals 'tp', 'fp', 'fn'.  `things=` (class indices) restricts them: PQ_th / SQ_th / RQ_th over those classes and PQ_st /
+    SQ_st / RQ_st over the others are added."""
+    q = panoptic_quality_of(counts)
+    C = q["pq"].shape[-1]
+    if q["pq"].ndim != 1:
+        raise ValueError(f"mmsa.evaluate: a summary is formed from the counts of one slot [C, {SIZE_BUCKETS}, 4], got {np.asarray(counts).shape}")
+
+    def mean(v, keep):
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)
+            return _round_percent(np.nanmean(v[keep])) if keep.any() else float("nan")
+
+    every = np.ones(C, dtype=bool)
+    s = OrderedDict((k.upper(), mean(q[k], every)) for k in ("pq", "sq", "rq"))
+    if things is not None:
+        th = [things] if _is_int(things, 0, C - 1) else list(things)
+        if not th or any(not _is_int(t, 0, C - 1) for t in th) or len(set(int(t) for t in th)) != len(th):
+            raise ValueError(f"mmsa.evaluate: things = {things!r}; a list of distinct class indices in 0..{C - 1} is expected")
+        keep = np.zeros(C, dtype=bool)
+        keep[[int(t) for t in th]] = True
+        for tag, k in (("th", keep), ("st", ~keep)):
+            for name in ("pq", "sq", "rq"):
+                s[f"{name.upper()}_{tag}"] = mean(q[name], k)
+    s["tp"], s["fp"], s["fn"] = int(q["tp"].sum()), int(q["fp"].sum()), int(q["fn"].sum())
+    return s
+
+
+class PanopticEvaluator(_SlotOwner):
+    """Owns the panoptic counts of an evaluation run, as SegmentEvaluator owns the segment counts: int64 [n_slots, C, 24, 4] on the device (`.counts`: TP, FP, FN
+    and the fixed-point IoU sum by class and size bucket).  Slots and cases as Evaluator's.  add() makes, into buffers cached per shape and stream, the two
+    component calls, `segment_counts` (bins=1, into a private buffer: its scratch planes are the areas), `segment_pairs` and `panoptic_counts`: no host sync,
+    and no allocation once the buffers of a shape exist.  `capacity` (a power of two) sizes the pair table; None: the next power of two >= B * H * W / 2 of
+    every shape.  A table that was too small drops hit pixels into the device word that `overflow()` reads, and every host reduction raises RuntimeError
+    then: the counts are never silently short.  `things` = the class indices `summary()` reports PQ_th / PQ_st for.  Every class-map entry's `panoptic=` takes
+    it.  Across ranks: mmsa.dist.allreduce_counts(pe.counts)."""
+    _who, _read, _one = "PanopticEvaluator", "host_counts()", "a PanopticEvaluator"
+
+    def __init__(self, prep, connectivity=8, capacity=None, cases=None, things=None, images=MAX_IMAGES, device=None):
+        who = "mmsa.PanopticEvaluator"
+        self.prep = prep
+        self.connectivity = check_connectivity(connectivity, who)
+        self.capacity = None if capacity is None else check_pair_capacity(capacity, who)
+        _check_classes_u8(prep.num_classes, who)
+        self.things = None if things is None else list(things)
+        if self.things is not None:
+            panoptic_summary_of(np.zeros((prep.num_classes, SIZE_BUCKETS, 4), dtype=np.int64), self.things)      # refused here, not at the first summary
+        self._init_slots(cases, images)
+        self._maps = {}         # (B, H, W, device, stream) -> (root_pred, root_label, scratch, match, PairTable)
+        self._sides = None      # int64 [n_slots, 2, C, 24, 2]: what segment_counts adds at bins=1 (the segments of both sides by class and size)
+        self._overflow = None   # int32 [1]: the overflow word of every table of this evaluator
+        self._init_buffer(device)
+
+    def _trailing(self):
+        return (self.prep.num_classes, SIZE_BUCKETS, 4)
+
+    def _buffer(self, device):
+        buf = super()._buffer(device)              # refuses to allocate during a capture
+        if self._sides is None:                    # made with the counts: whoever has the one has the others
+            self._sides = torch.zeros(self.n_slots, 2, self.prep.num_classes, SIZE_BUCKETS, 2, dtype=torch.int64, device=device)
+            self._overflow = torch.zeros(1, dtype=torch.int32, device=device)
+        return buf
+
+    def _maps_for(self, B, H, W, device):
+        key = (B, H, W, device, ops._stream())
+        m = self._maps.get(key)
+        if m is None:
+            if _capturing(device):
+                raise RuntimeError(f"mmsa.{self._who}: the root maps of a {B} x {H} x {W} batch cannot be allocated during a graph capture: run one add() of "
+                                   "this shape before capturing")
+            capacity = default_pair_capacity(B * H * W) if self.capacity is None else self.capacity
+            table = PairTable(torch.empty(capacity, dtype=torch.int64, device=device), torch.empty(capacity, dtype=torch.int32, device=device), self._overflow,
+                              (B, H, W))
+            m = self._maps[key] = (torch.empty(B, H, W, dtype=torch.int32, device=device), torch.empty(B, H, W, dtype=torch.int32, device=device),
+                                   torch.empty(4, B, H, W, dtype=torch.int32, device=device), torch.empty(2, B, H, W, dtype=torch.int32, device=device), table)
+        return m
+
+    def add(self, pred, labels, case=None, slots=None):
+        """Count a batch of stored class maps: the components of both sides, their areas, the pair table, the matches and the counts; no host sync, no
+        allocation once the buffers for the shape exist."""
+        pred = _check_pred(pred)
+        B, H, W = (int(v) for v in pred.shape)
+        with torch.cuda.device(pred.device):
+            self.prep.launch_args(labels, B, H, W, pred.device)      # the label side checked before the first launch
+            return self._add(pred, B, case, slots, self._launches, pred, labels, guard=False)      # this guard serves
+
+    def _launches(self, pred, labels, buf, use):
+        B, H, W = (int(v) for v in pred.shape)
+        root_pred, root_label, scratch, match, table = self._maps_for(B, H, W, pred.device)
+        components(pred, num_classes=self.prep.num_classes, connectivity=self.connectivity, out=root_pred)
+        components(labels, labels_prep=self.prep, size=(H, W), connectivity=self.connectivity, out=root_label)
+        segment_counts(pred, labels, self.prep, root_pred, root_label, 1, self._sides, scratch, use)
+        segment_pairs(pred, labels, self.prep, root_pred, root_label, table=table)
+        panoptic_counts(pred, labels, self.prep, root_pred, root_label, scratch, table, buf, match, use)
+
+    def reset(self):
+        super().reset()
+        if self._sides is not None:
+            self._sides.zero_()
+            self._overflow.zero_()
+
+    def overflow(self):
+        """The hit pixels that found no slot in a pair table since the last reset() (one word from the device); 0: every count is complete."""
+        return 0 if self._overflow is None else int(self._overflow.item())
+
+    def host_counts(self):
+        """The counts on the host: int64 numpy [n, C, 24, 4], n = images added so far / cases.  RuntimeError where a pair table overflowed."""
+        lost = self.overflow()
+        if lost:
+            raise RuntimeError(f"mmsa.{self._who}: a pair table overflowed ({lost} hit pixels found no slot), so intersections are short and matches may be "
+                               f"missing: make the {self._who} with a larger capacity= (a power of two; "
+                               f"{'the default, half the pixels of a batch,' if self.capacity is None else self.capacity} was too small) and count again")
+        return self._host()
+
+    def _of(self, slot):
+        return self._pick(self.host_counts(), slot)
+
+    def quality(self, min_area=1, max_area=None, slot=None):
+        """`panoptic_quality_of` of one slot (index or case name) or of the sum over every slot."""
+        return panoptic_quality_of(self._of(slot), min_area, max_area)
+
+    def pq(self, min_area=1, max_area=None, slot=None):
+        """Panoptic quality per class: float64 [C], NaN for a class without segments."""
+        return self.quality(min_area, max_area, slot)["pq"]
+
+    def sq(self, min_area=1, max_area=None, slot=None):
+        """Segmentation quality per class, the mean IoU of the matched pairs: float64 [C], NaN without a TP."""
+        return self.quality(min_area, max_area, slot)["sq"]
+
+    def rq(self, min_area=1, max_area=None, slot=None):
+        """Recognition quality per class, the F1 of the matching: float64 [C]."""
+        return self.quality(min_area, max_area, slot)["rq"]
+
+    def by_size(self, slot=None):
+        """The counts and qualities per power-of-two size bucket -> OrderedDict: 'min_area' int64 [24], 'tp' / 'fp' / 'fn' int64 [24, C], 'pq' / 'sq' / 'rq'
+        float64 [24, C] (NaN where a class has no segment of that size)."""
+        c = np.moveaxis(self._of(slot), -2, -3)                              # [24, C, 4]
+        den = c[..., 0] + 0.5 * c[..., 1] + 0.5 * c[..., 2]
+        iou = c[..., 3].astype(np.float64) / IOU_ONE
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return OrderedDict(min_area=1 << np.arange(SIZE_BUCKETS, dtype=np.int64), tp=c[..., 0], fp=c[..., 1], fn=c[..., 2], pq=iou / den,
+                               sq=iou / c[..., 0].astype(np.float64), rq=c[..., 0] / den)
+
+    def summary(self, slot=None):
+        """PQ / SQ / RQ (`panoptic_summary_of`, with this evaluator's `things`), the totals, and the connectivity."""
+        s = panoptic_summary_of(self._of(slot), self.things)
+        s["connectivity"] = self.connectivity
+        return s
