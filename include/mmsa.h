@@ -660,6 +660,30 @@ int mmsa_eval_panoptic(const unsigned char* pred, const unsigned char* label, in
                        const int* ymap, const int* xmap, const int* slots, int n_slots, const int* root_pred, const int* root_label, const int* planes,
                        const int64_t* keys, const int* counts, long capacity, int* match, int64_t* pq_counts, mmsa_stream_t stream);
 
+/* --- the segment table (csrc/segtable.hip): the segments of a code map handed out -- dense ids, and one record per segment.  The code map (src, lut, ymap /
+ *   xmap, Hs x Ws on the grid H x W) and root int32 [B, H, W] are components_u8's, root as that entry wrote it for this code map.
+ *   segment_table: a component of image b is LISTED iff its area >= min_area and its code < void_from (the class count C: the classes only; 256: every code,
+ *     C and 255 included).  min_area == 1 needs no area; min_area > 1 reads `area` as mmsa_component_area wrote it for root.  The listed segments of an image
+ *     are numbered 0 .. n_b - 1 in ascending order of their root index (the raster order of their first pixel): canonical, the same bytes whatever the schedule.
+ *     count int32 [B] = n_b, also where it exceeds capacity.  ids int32 [B, H, W] = the number of the pixel's segment, -1 where it is not listed; it does not
+ *     depend on capacity.  records int64 [B, capacity, 10], zeroed here: row k < min(n_b, capacity) = ROOT, CLASS (the code), AREA, X0, Y0, X1, Y1 (the box,
+ *     inclusive), SUM_X, SUM_Y, SUM_Q; the rows of the segments from capacity on are dropped (count[b] > capacity shows it), every other row stays zero.
+ *     SUM_Q = the sum of floor(c * 2^24) over the segment's pixels, c = values float32 [B, H, W] clamped as in mmsa_eval_calibration (NaN, negatives, -0.0 ->
+ *     0; above 1, +inf -> 1); 0 with values == NULL.  scratch int32 [B * ceil(H * W / 2048)]: the block counts of the prefix sum.  root, ids and scratch are
+ *     three buffers.  Four launches -- flag counts per 2048 pixels, their prefix sums (one workgroup per image), ids and row heads at the root pixels, then a
+ *     lane per pixel that writes its id and adds itself to its row by 64-bit atomics: a wave reduces its lanes per distinct id in registers (8 rounds, then
+ *     lane by lane), the four waves of a workgroup merge their first id through LDS, and a wave issues one add, one min and one max instruction for all of
+ *     its rounds.  No workgroup waits for another; every loop is bounded by an index or a block count.  B * H * W < 2^31, B <= 65535, B * capacity < 2^31.
+ *   select_segments_u8: out[p] = fill where 0 <= ids[p] < capacity and keep[b][ids[p]] == 0, pred[p] elsewhere (ids -1 or >= capacity: unchanged); keep uint8
+ *     [B, capacity]; out may be pred.  0 <= fill <= 255.
+ *   A limit broken or a null pointer: MMSA_ERR_ARG with a message, before any launch.  Integer sums: the same bytes whatever the order of arrival. --- */
+int mmsa_segment_table(const unsigned char* src, int B, int Hs, int Ws, const unsigned char* lut, const int* ymap, const int* xmap, int H, int W,
+                       const int* root, const int* area, const float* values, int min_area, int void_from, int capacity, int* count, int* ids,
+                       int64_t* records, int* scratch, mmsa_stream_t stream);
+int mmsa_segment_table_block(void); /* the pixels per word of segment_table's scratch in THIS build (2048): scratch holds B * ceil(H * W / block) words */
+int mmsa_select_segments_u8(const unsigned char* pred, const int* ids, const unsigned char* keep, int B, int H, int W, int capacity, int fill,
+                            unsigned char* out, mmsa_stream_t stream);
+
 /* --- the picture of a prediction (segmentation/mmseg_custom/apis/test_bs.py:257-349, the `--show` / `--show-dir` output): `tensor2imgs` (test_bs.py:18-63) on
  *     planes 0..2 of the input tensor -> the crop `img[:h, :w]` (test_bs.py:275-276) -> `show_result` (tools/color_gt_according_palette.py:23-81:
  *     color_seg[seg == label] = color, channels reversed, img * (1 - opacity) + color_seg * opacity, .astype(uint8)), in one pass.

@@ -30,7 +30,10 @@
  *      boundary F-score and Hausdorff percentiles).
  *      Still 114, for the same reason: new entries mmsa_components_u8 / mmsa_component_area / mmsa_suppress_small_u8 / mmsa_eval_segments (the connected
  *      components of a code map as the smallest linear index of each, their areas, the class map without its small blobs, and the segment counts of a
- *      prediction against the ground truth by class, size bucket and coverage bin: segment recall and precision). */
+ *      prediction against the ground truth by class, size bucket and coverage bin: segment recall and precision).
+ *      Still 114, for the same reason: new entries mmsa_segment_table / mmsa_segment_table_block / mmsa_select_segments_u8 (the segments of a code map handed out: dense ids in raster
+ *      order of the first pixel by a device-wide prefix sum, one record per segment -- class, area, box, coordinate sums, fixed-point score sum -- and the
+ *      class map with chosen segments painted over). */
 #ifndef MMSA_VERSION_H
 #define MMSA_VERSION_H
 #define MMSA_ABI_VERSION 114

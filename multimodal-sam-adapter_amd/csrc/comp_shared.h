@@ -18,6 +18,22 @@ static inline int comp_zero(const char* name, void* p, size_t bytes, hipStream_t
   return MMSA_OK;
 }
 
+// the code map of a component launch and of csrc/segtable.hip: M(y, x) = lut[src[b, ymap[y], xmap[x]]]
+struct CompSrc {                    // the source of a component launch (csrc/distance.hip DistSrc)
+  const unsigned char* src;         // [B, Hs, Ws]
+  const unsigned char* lut;         // [256] or NULL (identity)
+  const int* ymap;                  // [H] / [W] source row / column, or both NULL (Hs == H, Ws == W)
+  const int* xmap;
+  int Hs, Ws, H, W;
+};
+
+__device__ __forceinline__ int comp_code(const CompSrc& s, int b, int y, int x) {      // 0 <= y < H, 0 <= x < W
+  const int ys = s.ymap ? min(max(s.ymap[y], 0), s.Hs - 1) : y;
+  const int xs = s.xmap ? min(max(s.xmap[x], 0), s.Ws - 1) : x;
+  const int v = s.src[((long)b * s.Hs + ys) * s.Ws + xs];
+  return s.lut ? (int)s.lut[v] : v;
+}
+
 // dst[key] += the number of lanes that hold `key` (and dst2[key] += those of them with `flag`, where dst2 is given), ONE atomicAdd per (wave, key).  Called by
 // every lane of a wave together; `has` = false: a lane without a pixel.  At most 64 distinct keys in a wave: 64 rounds.
 __device__ __forceinline__ void comp_wave_add(int* dst, int* dst2, bool has, int key, bool flag) {

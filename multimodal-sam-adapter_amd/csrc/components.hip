@@ -34,21 +34,6 @@
 #define COMP_MAX_BINS 64
 #define COMP_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
-struct CompSrc {                    // the source of a component launch (csrc/distance.hip DistSrc)
-  const unsigned char* src;         // [B, Hs, Ws]
-  const unsigned char* lut;         // [256] or NULL (identity)
-  const int* ymap;                  // [H] / [W] source row / column, or both NULL (Hs == H, Ws == W)
-  const int* xmap;
-  int Hs, Ws, H, W;
-};
-
-__device__ __forceinline__ int comp_code(const CompSrc& s, int b, int y, int x) {      // 0 <= y < H, 0 <= x < W
-  const int ys = s.ymap ? min(max(s.ymap[y], 0), s.Hs - 1) : y;
-  const int xs = s.xmap ? min(max(s.xmap[x], 0), s.Ws - 1) : x;
-  const int v = s.src[((long)b * s.Hs + ys) * s.Ws + xs];
-  return s.lut ? (int)s.lut[v] : v;
-}
-
 // grid.x = tiles_x * tiles_y * B, x fastest.  Lane t owns the local pixels t, t + 256, ...: a wave on one tile row.
 __global__ __launch_bounds__(256) void components_tile_kernel(CompSrc s, int tiles_x, int tiles_y, int conn8, int* __restrict__ parent) {
   __shared__ unsigned short code[COMP_PH * COMP_PW];

@@ -2411,3 +2411,265 @@ class PanopticEvaluator(_SlotOwner):
         s = panoptic_summary_of(self._of(slot), self.things)
         s["connectivity"] = self.connectivity
         return s
+
+
+# ---- the segment table: the segments of a code map handed out (csrc/segtable.hip) ----
+# Code map, connectivity and roots are `components`'.  A component of image b is LISTED iff its area >= min_area and its code is a class (< C); void=True also
+# lists the components of the other codes (C, and 255 on the label side).  The listed segments of an image are numbered 0 .. n_b - 1 in ascending order of
+# their root index -- the raster order of their first pixel -- so the numbering is canonical.  count[b] = n_b; ids[b, y, x] = the number of the pixel's segment
+# (-1: not listed); records[b, k] = ROOT, CLASS, AREA, X0, Y0, X1, Y1, SUM_X, SUM_Y, SUM_Q for k < min(n_b, capacity), zero rows behind them.
+SEGTAB_BLOCK = 2048                # csrc/segtable.hip SEGTAB_BLOCK: the pixels per workgroup of the prefix sum's count and id passes (one scratch word each)
+SEGTAB_SCAN_LANES = 256            # csrc/segtable.hip SEGTAB_SCAN_LANES: the block counts one trip of the scan pass takes
+SEGMENT_FIELDS = ("ROOT", "CLASS", "AREA", "X0", "Y0", "X1", "Y1", "SUM_X", "SUM_Y", "SUM_Q")
+ROOT, CLASS, AREA, X0, Y0, X1, Y1, SUM_X, SUM_Y, SUM_Q = range(10)
+SCORE_ONE = CONF_ONE               # the fixed-point unit of a record's score sum: SUM_Q = sum of floor(clamp(value) * 2^24)
+MIN_SEGMENT_CAPACITY = 1024
+SEGMENT_DTYPE = np.dtype([("image", np.int64), ("id", np.int64), ("root", np.int64), ("category", np.int64), ("area", np.int64), ("bbox", np.int64, (4,)),
+                          ("centroid", np.float64, (2,)), ("score", np.float64)])
+
+
+def default_segment_capacity(H, W):
+    """The default rows per image of a segment table: max(1024, H * W // 64)."""
+    return max(MIN_SEGMENT_CAPACITY, int(H) * int(W) // 64)
+
+
+def check_segment_capacity(capacity, who="mmsa.evaluate"):
+    if not _is_int(capacity, 1, (1 << 31) - 1):
+        raise ValueError(f"{who}: capacity = {capacity!r}; a positive number of rows per image is expected (None: max({MIN_SEGMENT_CAPACITY}, H * W // 64))")
+    return int(capacity)
+
+
+def score_threshold_q(t):
+    """floor(t * 2^24) of a score threshold t in [0, 1], exactly: the integer `keep(min_score=t)` tests SUM_Q >= q * AREA with."""
+    if isinstance(t, bool) or not isinstance(t, (int, float, np.integer, np.floating, Fraction)) or not 0 <= t <= 1:
+        raise ValueError(f"mmsa.evaluate: min_score = {t!r}; a score in [0, 1] is expected")
+    return int(Fraction(t) * SCORE_ONE // 1)
+
+
+def segment_records_of(records, count, scored=True, image=0):
+    """The host reading of raw records: integer [rows, 10] (one image's rows of `records`) and its `count` -> a numpy structured array of `count` segments with
+    'image', 'id', 'root', 'category' (the code), 'area', 'bbox' (COCO: x, y, width, height), 'centroid' (x, y) = (SUM_X / AREA, SUM_Y / AREA) and 'score' =
+    SUM_Q / (AREA * 2^24), float64 from those integers; 0 / 0 is NaN, and the score is NaN with scored=False (a table filled without `values`).  Raises
+    RuntimeError naming capacity= where count exceeds the rows: the list would be short."""
+    r = np.asarray(records)
+    if r.ndim != 2 or r.shape[1] != len(SEGMENT_FIELDS) or r.dtype.kind not in "iu":
+        raise ValueError(f"mmsa.evaluate: segment records are an integer [rows, {len(SEGMENT_FIELDS)}] array ({', '.join(SEGMENT_FIELDS)}), got {r.dtype} {r.shape}")
+    n = int(count)
+    if n < 0:
+        raise ValueError(f"mmsa.evaluate: count = {n}")
+    if n > r.shape[0]:
+        raise RuntimeError(f"mmsa.evaluate: image {image} has {n} listed segments and the table {r.shape[0]} rows: the records of the last {n - r.shape[0]} were "
+                           f"dropped; fill a table with a larger capacity= (capacity=H * W can never overflow)")
+    r = r[:n].astype(np.int64, copy=False)
+    out = np.zeros(n, dtype=SEGMENT_DTYPE)
+    out["image"], out["id"], out["root"], out["category"], out["area"] = image, np.arange(n), r[:, ROOT], r[:, CLASS], r[:, AREA]
+    out["bbox"] = np.stack([r[:, X0], r[:, Y0], r[:, X1] - r[:, X0] + 1, r[:, Y1] - r[:, Y0] + 1], 1)
+    area = r[:, AREA].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["centroid"] = np.stack([r[:, SUM_X] / area, r[:, SUM_Y] / area], 1)
+        out["score"] = r[:, SUM_Q] / (area * SCORE_ONE) if scored else np.nan
+    return out
+
+
+class SegmentTable:
+    """Owns the segment table of a batch of code maps on the device: `count` int32 [B], `records` int64 [B, capacity, 10], `ids` int32 [B, H, W], and the
+    scratch of the launches (the root map, the area plane where min_area > 1, the block counts of the prefix sum).  One of the keywords says how a map is read,
+    as `components` reads one: num_classes=C (a stored uint8 class map, codes min(map, C)) or labels_prep=prep (raw labels through the LUT and the
+    nearest-neighbour tables).  A component is listed iff its area >= min_area and its code is a class; void=True also lists the other codes.  `capacity` = the
+    rows per image (None: max(1024, H * W // 64) of every shape); the records of the segments beyond it are dropped, `count` keeps the true number and
+    `overflow()` / `host()` say so.  update() makes the launches into buffers cached per shape and stream: no host sync, and no allocation once the buffers of a
+    shape exist.  Every class-map entry's `segment_table=` takes one made with num_classes=."""
+
+    def __init__(self, num_classes=None, labels_prep=None, connectivity=8, min_area=1, void=False, capacity=None):
+        who = "mmsa.SegmentTable"
+        if (labels_prep is None) == (num_classes is None):
+            raise ValueError(f"{who}: takes num_classes= (stored class maps) or labels_prep= (raw labels), one of them")
+        if labels_prep is None:
+            code_lut(num_classes)
+        self.num_classes = int(num_classes) if labels_prep is None else int(labels_prep.num_classes)
+        self.labels_prep = labels_prep
+        self.connectivity = check_connectivity(connectivity, who)
+        if not _is_int(min_area, 1, (1 << 31) - 1):
+            raise ValueError(f"{who}: min_area = {min_area!r}; an integer pixel count >= 1 is expected (1: every component)")
+        self.min_area = int(min_area)
+        if not isinstance(void, (bool, np.bool_)):
+            raise ValueError(f"{who}: void = {void!r}; True (list the components of every code) or False (of the classes only) is expected")
+        self.void = bool(void)
+        self._capacity = None if capacity is None else check_segment_capacity(capacity, who)
+        self._maps = {}          # (B, H, W, device, stream) -> dict(count, records, ids, scratch, root, area)
+        self.count = self.records = self.ids = self.root = None
+        self.shape = None        # (B, H, W) of the last update
+        self.scored = False      # the last update had `values`
+
+    @property
+    def capacity(self):
+        """The rows per image: the constructor's, or the default of the last update's shape (None before the first)."""
+        return self._capacity if self._capacity is not None or self.shape is None else default_segment_capacity(self.shape[1], self.shape[2])
+
+    def _maps_for(self, B, H, W, device):
+        key = (B, H, W, device, ops._stream())
+        m = self._maps.get(key)
+        if m is None:
+            if _capturing(device):
+                raise RuntimeError(f"mmsa.SegmentTable: the buffers of a {B} x {H} x {W} batch cannot be allocated during a graph capture: run one update() of this "
+                                   "shape before capturing")
+            capacity = default_segment_capacity(H, W) if self._capacity is None else self._capacity
+            if lib.raw.mmsa_segment_table_block() != SEGTAB_BLOCK:      # a variant build (MMSA_LIB) with another block: the scratch would be sized wrong
+                raise RuntimeError(f"mmsa.SegmentTable: the library counts {lib.raw.mmsa_segment_table_block()} pixels per scratch word, mmsa.evaluate.SEGTAB_BLOCK "
+                                   f"is {SEGTAB_BLOCK}")
+            if B * capacity >= 1 << 31:
+                raise RuntimeError(f"mmsa.SegmentTable: {B} images of {capacity} rows; a row is indexed in 32 bits (B * capacity < 2^31)")
+            blocks = -(-H * W // SEGTAB_BLOCK)
+            m = self._maps[key] = dict(count=torch.zeros(B, dtype=torch.int32, device=device),
+                                       records=torch.zeros(B, capacity, len(SEGMENT_FIELDS), dtype=torch.int64, device=device),
+                                       ids=torch.empty(B, H, W, dtype=torch.int32, device=device), scratch=torch.empty(B * blocks, dtype=torch.int32, device=device),
+                                       root=torch.empty(B, H, W, dtype=torch.int32, device=device),
+                                       area=torch.empty(B, H, W, dtype=torch.int32, device=device) if self.min_area > 1 else None)
+        return m
+
+    @torch.no_grad()
+    def update(self, map, values=None, root=None):
+        """Fill the table from a batch of maps (the component launches unless `root=` brings the root map `components` made of this map at this connectivity,
+        the area launch where min_area > 1, one memset and four launches of mmsa_segment_table) -> self.  `values` (float32 [B, H, W] on the grid of the code
+        map: a confidence, margin or entropy map, or a probs[r] plane) fills SUM_Q; without it SUM_Q is 0 and every score NaN."""
+        src = _check_map(map, "map", torch.uint8, "a uint8 class map or raw uint8 labels", shape_only=True)
+        B, Hs, Ws = (int(v) for v in src.shape)
+        H, W = (Hs, Ws) if self.labels_prep is None else self.labels_prep.resized(Hs, Ws)
+        if B * H * W == 0:
+            raise RuntimeError(f"mmsa.evaluate: an empty map {tuple(src.shape)}")
+        if B * H * W >= 1 << 31:
+            raise RuntimeError(f"mmsa.evaluate: {B} x {H} x {W} pixels; a segment table indexes a batch in 32 bits (B * H * W < 2^31)")
+        grid = torch.Size((B, H, W))
+        if root is not None:
+            _check_int_plane(root, "root", grid, None, "the root map of mmsa.components")
+        if values is not None:
+            if not isinstance(values, torch.Tensor) or values.dtype != torch.float32 or tuple(values.shape) != tuple(grid) or not values.is_contiguous():
+                raise RuntimeError(f"mmsa.evaluate: values must be a contiguous float32 {tuple(grid)} tensor (a confidence, margin or entropy map, or a probs plane)")
+        _check_map(src, "map", torch.uint8, "a uint8 class map or raw uint8 labels")
+        for name, t in (("root", root), ("values", values)):
+            if t is not None and t.device != src.device:
+                raise RuntimeError(f"mmsa.evaluate: {name} is on {t.device}, the map on {src.device}")
+        with torch.cuda.device(src.device):
+            m = self._maps_for(B, H, W, src.device)
+            if root is None:
+                root = components(src, num_classes=None if self.labels_prep is not None else self.num_classes, labels_prep=self.labels_prep, size=(H, W),
+                                  connectivity=self.connectivity, out=m["root"])
+            if self.min_area > 1:
+                component_areas(root, out=m["area"])
+            lut = _code_lut_on(src.device, None if self.labels_prep is not None else self.num_classes, self.labels_prep)
+            ymap, xmap = (None, None) if self.labels_prep is None else self.labels_prep.tables(Hs, Ws, H, W, src.device)
+            capacity = m["records"].shape[1]
+            lib.call("mmsa_segment_table", src.data_ptr(), B, Hs, Ws, lut.data_ptr(), None if ymap is None else ymap.data_ptr(),
+                     None if xmap is None else xmap.data_ptr(), H, W, root.data_ptr(), None if m["area"] is None else m["area"].data_ptr(),
+                     None if values is None else values.data_ptr(), self.min_area, 256 if self.void else self.num_classes, capacity, m["count"].data_ptr(),
+                     m["ids"].data_ptr(), m["records"].data_ptr(), m["scratch"].data_ptr(), ops._stream())
+        self.count, self.records, self.ids, self.root = m["count"], m["records"], m["ids"], root
+        self.shape, self.scored = (B, H, W), values is not None
+        return self
+
+    def _filled(self):
+        if self.shape is None:
+            raise RuntimeError("mmsa.SegmentTable: nothing was filled yet: call update()")
+
+    def overflow(self):
+        """Whether an image of the last update has more listed segments than rows (the device words of `count`): its last records were dropped."""
+        self._filled()
+        return bool((self.count > self.records.shape[1]).any().item())
+
+    def host(self, b=None):
+        """The segments on the host (`segment_records_of`: two device-to-host copies) -> a numpy structured array with 'image', 'id', 'root', 'category',
+        'area', 'bbox', 'centroid' and 'score'; of image `b`, or of every image in turn.  RuntimeError naming capacity= where an image has more segments than
+        rows."""
+        self._filled()
+        B = self.shape[0]
+        if b is not None and not _is_int(b, 0, B - 1):
+            raise ValueError(f"mmsa.SegmentTable: b = {b!r}; an image index 0..{B - 1} (or None: every image) is expected")
+        count = self.count.cpu().numpy()
+        cap = int(self.records.shape[1])
+        for i in range(B):
+            if count[i] > cap:
+                raise RuntimeError(f"mmsa.SegmentTable: image {i} has {int(count[i])} listed segments and the table {cap} rows: the records of the last "
+                                   f"{int(count[i]) - cap} were dropped; make the SegmentTable with a larger capacity= (capacity=H * W can never overflow)")
+        records = self.records.cpu().numpy()
+        images = range(B) if b is None else [int(b)]
+        parts = [segment_records_of(records[i], count[i], self.scored, i) for i in images]
+        return parts[0] if len(parts) == 1 else np.concatenate(parts)
+
+    def segments_info(self, b):
+        """The `segments_info` list of the COCO panoptic format for image b: dicts with 'id' (the dense id + 1: the format's PNG is `ids + 1`, 0 = VOID),
+        'category_id', 'area', 'bbox' [x, y, width, height] and 'iscrowd' 0, and next to them 'centroid' [x, y] and 'score' (None without `values`)."""
+        return [dict(id=int(s["id"]) + 1, category_id=int(s["category"]), area=int(s["area"]), bbox=[int(v) for v in s["bbox"]], iscrowd=0,
+                     centroid=[float(v) for v in s["centroid"]], score=float(s["score"]) if self.scored else None) for s in self.host(int(b))]
+
+    @torch.no_grad()
+    def keep(self, min_area=None, max_area=None, min_score=None, classes=None):
+        """Which rows pass -> uint8 [B, capacity] on the device (1: keep), for `select_segments`: min_area <= AREA < max_area, mean score >= min_score -- tested
+        in integers, SUM_Q >= floor(min_score * 2^24) * AREA -- and CLASS among `classes`.  Torch operations on `records`: no host sync.  Empty rows are 0."""
+        self._filled()
+        r = self.records
+        area = r[..., AREA]
+        ok = area > 0
+        for name, v in (("min_area", min_area), ("max_area", max_area)):
+            if v is not None and not _is_int(v, 1, 1 << 62):
+                raise ValueError(f"mmsa.SegmentTable: {name} = {v!r}; a pixel count >= 1 is expected")
+        if min_area is not None:
+            ok = ok & (area >= int(min_area))
+        if max_area is not None:
+            ok = ok & (area < int(max_area))
+        if min_score is not None:
+            q = score_threshold_q(min_score)
+            if not self.scored:
+                raise RuntimeError("mmsa.SegmentTable: min_score= on a table filled without values=: there is no score to test")
+            ok = ok & (r[..., SUM_Q] >= area * q)
+        if classes is not None:
+            cs = [classes] if _is_int(classes, 0, 255) else list(classes)
+            if not cs or any(not _is_int(c, 0, 255) for c in cs):
+                raise ValueError(f"mmsa.SegmentTable: classes = {classes!r}; a list of codes 0..255 is expected")
+            among = torch.zeros_like(ok)
+            for c in sorted(set(int(c) for c in cs)):
+                among = among | (r[..., CLASS] == c)
+            ok = ok & among
+        return ok.to(torch.uint8)
+
+
+@torch.no_grad()
+def segment_table(map, *, num_classes=None, labels_prep=None, values=None, root=None, connectivity=8, min_area=1, void=False, capacity=None, table=None):
+    """The launches of SegmentTable.update alone -> the table: a new SegmentTable of these options, or `table=` (a SegmentTable, whose own options hold: an
+    option spelled out here must agree with it), filled from `map`."""
+    if table is None:
+        table = SegmentTable(num_classes=num_classes, labels_prep=labels_prep, connectivity=connectivity, min_area=min_area, void=void, capacity=capacity)
+    else:
+        if not isinstance(table, SegmentTable):
+            raise RuntimeError(f"mmsa.evaluate: table= takes an mmsa.evaluate.SegmentTable, got {type(table).__name__}")
+        for name, v, default, own in (("num_classes", num_classes, None, None if table.labels_prep is not None else table.num_classes),
+                                      ("labels_prep", labels_prep, None, table.labels_prep), ("connectivity", connectivity, 8, table.connectivity),
+                                      ("min_area", min_area, 1, table.min_area), ("void", void, False, table.void), ("capacity", capacity, None, table._capacity)):
+            if v is not default and v != default and v != own and v is not own:
+                raise RuntimeError(f"mmsa.evaluate: {name}={v!r} with a table made with {name}={own!r}")
+    return table.update(map, values=values, root=root)
+
+
+@torch.no_grad()
+def select_segments(pred, table, keep, fill=255, out=None):
+    """The class map with the segments that `keep` drops painted over (one pointwise launch, mmsa_select_segments_u8) -> uint8 [B, H, W]: `fill` where the
+    pixel's id is a row of the table and keep[b, id] == 0, `pred` elsewhere -- a pixel whose segment is not listed (id -1) or has no row (id >= capacity) is
+    unchanged.  `table` = a filled SegmentTable of this shape, `keep` = uint8 [B, capacity] on the device (`table.keep(...)`, or any mask made from
+    `table.records`); `out=` may be `pred` itself.  The instance-level sibling of `abstain`."""
+    if not isinstance(table, SegmentTable):
+        raise RuntimeError(f"mmsa.evaluate: table takes an mmsa.evaluate.SegmentTable, got {type(table).__name__}")
+    table._filled()
+    if not _is_int(fill, 0, 255):
+        raise ValueError(f"mmsa.evaluate: fill = {fill!r}; a byte 0..255 is expected")
+    pred = _check_map(pred, "pred", torch.uint8, "a uint8 class map", like=table.ids)
+    B, H, W = (int(v) for v in pred.shape)
+    capacity = int(table.records.shape[1])
+    if (not isinstance(keep, torch.Tensor) or keep.dtype != torch.uint8 or tuple(keep.shape) != (B, capacity) or not keep.is_contiguous()
+            or keep.device != pred.device):
+        raise RuntimeError(f"mmsa.evaluate: keep must be a contiguous uint8 {(B, capacity)} tensor on {pred.device} (one byte per row of the table)")
+    with torch.cuda.device(pred.device):
+        if out is None:
+            out = torch.empty_like(pred)
+        else:
+            _check_map(out, "out", torch.uint8, "a uint8 class map", like=pred)
+        lib.call("mmsa_select_segments_u8", pred.data_ptr(), table.ids.data_ptr(), keep.data_ptr(), B, H, W, capacity, int(fill), out.data_ptr(), ops._stream())
+    return out

@@ -414,6 +414,21 @@ def _check_panoptic_call(panoptic, labels, return_map, what):
                            "stores none (drop return_map=)")
 
 
+def _check_segment_table_call(segment_table, return_map, what):
+    """`segment_table=` of an entry: a SegmentTable made with num_classes=, filled from the STORED map -- so there must be one.  It needs no `labels=`."""
+    if segment_table is None:
+        return
+    from .evaluate import SegmentTable
+    if not isinstance(segment_table, SegmentTable):
+        raise RuntimeError(f"mmsa.{what}: segment_table= takes an mmsa.evaluate.SegmentTable, got {type(segment_table).__name__}")
+    if segment_table.labels_prep is not None:
+        raise RuntimeError(f"mmsa.{what}: segment_table= takes a SegmentTable made with num_classes= (the stored map is a class map), this one reads raw labels "
+                           "(labels_prep=)")
+    if not return_map:
+        raise RuntimeError(f"mmsa.{what}: segment_table= with return_map=False: the table is filled by further launches over the stored map, and return_map=False "
+                           "stores none (drop return_map=)")
+
+
 def _check_labels(labels, evaluator, *binned):
     """`labels=` feed an evaluator, a calibration, a selective evaluator or several of them; an evaluator needs them."""
     if (labels is None) != (evaluator is None) and not (labels is not None and any(b is not None for b in binned)):
@@ -430,6 +445,8 @@ class MapOptions:
     makes the TopK buffers; with `topk=None` neither step does anything it did not do before.
     `boundary=` (a BoundaryEvaluator) is per call: `with_call` refuses it without `labels=`, of another type, or with `return_map=False`; `count` launches it.
     `segments=` (a SegmentEvaluator) goes exactly the same way, and so does `panoptic=` (a PanopticEvaluator).
+    `segment_table=` (a SegmentTable made with num_classes=) is per call too and needs no `labels=`: `with_call` refuses another type, a table of raw labels and
+    `return_map=False`; `count_segments` fills it from the stored map, with the confidence or score map (`confidence=`) or probs[0] (`topk=`) as its values.
     What depends on the plan (`one_pass=` at frame size, `fused=` / `return_map=` at a rescaled size or without an evaluator) is refused by MapPlan.class_map."""
     conf: object = None          # the float32 [B, Ho, Wo] buffer the launch writes the confidence (or score) map into, or None; before `at`: the entry's `confidence=`
     it: object = None            # the float32 inverse temperature of the `_t` / `_score` launches (mmsa.evaluate.inv_temperature), or None
@@ -446,6 +463,7 @@ class MapOptions:
     topk_evaluator: object = None
     segments: object = None      # the mmsa.evaluate.SegmentEvaluator the stored map is counted into, or None
     panoptic: object = None      # the mmsa.evaluate.PanopticEvaluator the stored map is counted into, or None
+    segment_table: object = None # the mmsa.evaluate.SegmentTable filled from the stored map (and the confidence / score / probs[0] next to it), or None
     boundary: object = None      # the mmsa.evaluate.BoundaryEvaluator the stored map is counted into, or None
 
     @classmethod
@@ -460,15 +478,16 @@ class MapOptions:
         return cls(conf=confidence, it=it, kind=kind, one_pass=one_pass, topk=topk).with_call(what, **per_call)
 
     def with_call(self, what, labels=None, evaluator=None, case=None, calibration=None, selective=None, fused=None, return_map=True, topk_evaluator=None,
-                  segments=None, panoptic=None, boundary=None):
+                  segments=None, panoptic=None, segment_table=None, boundary=None):
         _check_topk_call(self.topk, topk_evaluator, labels, calibration, selective, fused, return_map, what)
         _check_boundary_call(boundary, labels, return_map, what)
         _check_segments_call(segments, labels, return_map, what)
         _check_panoptic_call(panoptic, labels, return_map, what)
+        _check_segment_table_call(segment_table, return_map, what)
         for kw, name, owner in (("calibration", "Calibration", calibration), ("selective", "SelectiveEvaluator", selective)):
             _check_binned(kw, name, owner, labels, self.conf, what, fused, return_map)
         return dataclasses.replace(self, labels=labels, evaluator=evaluator, case=case, calibration=calibration, selective=selective, fused=fused,
-                                   return_map=return_map, topk_evaluator=topk_evaluator, boundary=boundary, segments=segments, panoptic=panoptic)
+                                   return_map=return_map, topk_evaluator=topk_evaluator, boundary=boundary, segments=segments, panoptic=panoptic, segment_table=segment_table)
 
     def at(self, size, device, what, make=True):
         """`make=False`: a plan's `conf=` / `topk=`, which are the buffers themselves -- True / K make none there."""
@@ -514,6 +533,8 @@ class MapOptions:
             self.segments.add(out, self.labels, case=self.case)
         if self.panoptic is not None:
             self.panoptic.add(out, self.labels, case=self.case)
+        if self.segment_table is not None:      # needs no labels: the components of the stored map, then mmsa_segment_table
+            self.segment_table.update(out, values=self.topk.probs[0] if self.topk is not None else self.conf)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -621,7 +642,7 @@ class MapPlan:
                  ops._stream())
 
     def class_map(self, lg, out, unc, labels=None, evaluator=None, case=None, fused=None, return_map=True, one_pass=None, conf=None, calibration=None,
-                  selective=None, temperature=None, score="max", topk=None, topk_evaluator=None, segments=None, panoptic=None, boundary=None):
+                  selective=None, temperature=None, score="max", topk=None, topk_evaluator=None, segments=None, panoptic=None, segment_table=None, boundary=None):
         """The class-map launch of the three class-map calls, from the head-resolution logits lg [n, C, hs, ws] into out uint8 [B, Ho, Wo] and the
         uncovered-pixel word `unc`.  Without `labels`: mmsa_slide_argmax.  With `labels` (raw uint8 label maps [B, Hl, Wl]) and `evaluator`
         (mmsa.evaluate.Evaluator): the confusion counts of the map are ADDED to the evaluator's buffer as well -- by the same launch
@@ -660,7 +681,7 @@ class MapPlan:
         `panoptic=` (mmsa.evaluate.PanopticEvaluator; needs `labels=`, refused with `return_map=False`): the stored map's segments are matched with the label
         segments by IoU > 1/2 and TP / FP / FN and the IoU sum are ADDED to its counts (the launches of `segments=`, mmsa_segment_pairs, mmsa_eval_panoptic).  None: no launch."""
         o = MapOptions.of("inference", conf, temperature, score, one_pass, topk=topk, labels=labels, evaluator=evaluator, case=case, calibration=calibration,
-                          selective=selective, fused=fused, return_map=return_map, topk_evaluator=topk_evaluator, boundary=boundary, segments=segments, panoptic=panoptic)
+                          selective=selective, fused=fused, return_map=return_map, topk_evaluator=topk_evaluator, boundary=boundary, segments=segments, panoptic=panoptic, segment_table=segment_table)
         o = o.at((self.B, self.Ho, self.Wo), out.device if conf is not None or topk is not None else None, "inference", make=False)
         if o.topk is not None and (out.data_ptr() != o.topk.classes.data_ptr() or tuple(out.shape) != tuple(o.topk.classes.shape[1:]) or not out.is_contiguous()):
             raise RuntimeError("mmsa.inference: with topk= the map is plane 0 of the top-k classes: pass out=topk.classes[0]")
@@ -754,7 +775,7 @@ def _window_logits(backbone, head, cut, windows, max_batch):
 @torch.no_grad()
 def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preprocess=None, labels=None, evaluator=None, case=None, fused=None,
                     return_map=True, render=None, ori_shape=None, one_pass=None, confidence=False, calibration=None, selective=None, temperature=None,
-                    score="max", topk=None, topk_evaluator=None, segments=None, panoptic=None, boundary=None):
+                    score="max", topk=None, topk_evaluator=None, segments=None, panoptic=None, segment_table=None, boundary=None):
     """`simple_test` of a sliding-window frame (ED:191-234 + ED:449,477) -> uint8 class map [B, H, W], without the
     [B, classes, H, W] logits canvas: every window's logits stay at head resolution and ONE kernel (mmsa_slide_argmax) resizes,
     sums the overlapping windows in window order, divides by the count and takes the argmax -- the same additions in the same order
@@ -805,9 +826,13 @@ def slide_class_map(backbone, head, img, crop_size, stride, max_batch=8, preproc
     map's segments -- connected components of one class -- are counted by class, size and coverage into it on device (mmsa_components_u8 for each side,
     mmsa_eval_segments), over the same STORED map and under the same terms as `boundary=`: segment recall and precision next to mIoU.
     `panoptic=` (mmsa.evaluate.PanopticEvaluator; needs `labels=`, refused with `return_map=False`): the stored map's segments are matched with the label
-    segments by IoU > 1/2 and TP / FP / FN and the IoU sum are ADDED to its counts (the launches of `segments=`, mmsa_segment_pairs, mmsa_eval_panoptic)."""
+    segments by IoU > 1/2 and TP / FP / FN and the IoU sum are ADDED to its counts (the launches of `segments=`, mmsa_segment_pairs, mmsa_eval_panoptic).
+    `segment_table=` (mmsa.evaluate.SegmentTable made with num_classes=; needs no `labels=`, refused with `return_map=False`): the table is filled from the
+    stored map -- plane 0 with `topk=`, the rescaled or cut map with `ori_shape=` -- by SegmentTable.update (mmsa_components_u8, mmsa_segment_table), its
+    `values` the confidence or score map where `confidence=` was asked, probs[0] with `topk=`, nothing otherwise.  None: no launch.  Every class-map entry
+    (whole_class_map, class_map, aug_class_map, MapPlan.class_map, SlideRunner.run) takes it in the same way."""
     o = MapOptions.of("slide_class_map", confidence, temperature, score, one_pass, topk=topk, labels=labels, evaluator=evaluator, case=case,
-                      calibration=calibration, selective=selective, fused=fused, return_map=return_map, topk_evaluator=topk_evaluator, boundary=boundary, segments=segments, panoptic=panoptic)
+                      calibration=calibration, selective=selective, fused=fused, return_map=return_map, topk_evaluator=topk_evaluator, boundary=boundary, segments=segments, panoptic=panoptic, segment_table=segment_table)
     return _slide_class_map(o, backbone, head, img, crop_size, stride, max_batch, preprocess, render, ori_shape)
 
 
@@ -833,7 +858,7 @@ def _slide_class_map(o, backbone, head, img, crop_size, stride, max_batch=8, pre
 @torch.no_grad()
 def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator=None, case=None, fused=None, return_map=True, render=None,
                     ori_shape=None, dim=None, cut_dim=None, rescale=True, one_pass=None, confidence=False, calibration=None, selective=None, temperature=None,
-                    score="max", topk=None, topk_evaluator=None, segments=None, panoptic=None, boundary=None):
+                    score="max", topk=None, topk_evaluator=None, segments=None, panoptic=None, segment_table=None, boundary=None):
     """Whole-image `simple_test`: resize x4 (bilinear, align_corners=False) + argmax fused (ED:90-94,449,477) -> uint8 [B, H, W].
     `preprocess=` (mmsa.preprocess.Preprocess): img is the pair (rgb, aux) of raw frames, normalised (and padded) by one launch.
     `labels=` + `evaluator=` (+ `case=`): as in slide_class_map.
@@ -857,7 +882,7 @@ def whole_class_map(backbone, head, img, preprocess=None, labels=None, evaluator
     `boundary=`: as in slide_class_map (needs `labels=`), over the map stored at the size returned (rescaled, cut).
     `segments=` and `panoptic=`: as in slide_class_map too, over the same stored map."""
     o = MapOptions.of("whole_class_map", confidence, temperature, score, one_pass, topk=topk, labels=labels, evaluator=evaluator, case=case,
-                      calibration=calibration, selective=selective, fused=fused, return_map=return_map, topk_evaluator=topk_evaluator, boundary=boundary, segments=segments, panoptic=panoptic)
+                      calibration=calibration, selective=selective, fused=fused, return_map=return_map, topk_evaluator=topk_evaluator, boundary=boundary, segments=segments, panoptic=panoptic, segment_table=segment_table)
     return _whole_class_map(o, backbone, head, img, preprocess, render, ori_shape, dim, cut_dim, rescale)
 
 
@@ -952,7 +977,7 @@ def inference(backbone, head, img, test_cfg, rescale=True, preprocess=None, ori_
 @_on_device
 @torch.no_grad()
 def class_map(backbone, head, img, test_cfg, rescale=True, ori_shape=None, preprocess=None, labels=None, evaluator=None, case=None, render=None, one_pass=None,
-              confidence=False, calibration=None, selective=None, temperature=None, score="max", topk=None, topk_evaluator=None, segments=None, panoptic=None, boundary=None):
+              confidence=False, calibration=None, selective=None, temperature=None, score="max", topk=None, topk_evaluator=None, segments=None, panoptic=None, segment_table=None, boundary=None):
     """`simple_test` (ED:471-477) by mode: the dispatch of `inference` (ED:417-447) onto the class-map calls -> uint8 map, bit for bit
     argmax_map(inference(...)) of the same arguments, without a logits canvas: [B, H, W], or at the size `rescale` gives ('slide' / 'whole': `ori_shape`;
     'whole_dim': test_cfg['dim']; 'whole_dim_cut': the crop of the map at `dim`, or at the input size without `rescale`).  What `inference` refuses is
@@ -971,7 +996,7 @@ def class_map(backbone, head, img, test_cfg, rescale=True, ori_shape=None, prepr
     `panoptic=` (mmsa.evaluate.PanopticEvaluator; needs `labels=`): the panoptic counts of the stored map, likewise."""
     mode = test_cfg["mode"]
     o = MapOptions.of("class_map", confidence, temperature, score, one_pass, topk=topk, labels=labels, evaluator=evaluator, case=case, calibration=calibration,
-                      selective=selective, topk_evaluator=topk_evaluator, boundary=boundary, segments=segments, panoptic=panoptic)
+                      selective=selective, topk_evaluator=topk_evaluator, boundary=boundary, segments=segments, panoptic=panoptic, segment_table=segment_table)
     kw = dict(preprocess=preprocess, render=render)
     if mode == "slide":
         r = _slide_class_map(o, backbone, head, img, tuple(test_cfg["crop_size"]), tuple(test_cfg["stride"]), ori_shape=ori_shape if rescale else None, **kw)
@@ -1326,7 +1351,7 @@ def aug_inference(backbone, head, imgs, test_cfg, ori_shape=None, flips=None, pr
 @_on_views_device
 @torch.no_grad()
 def aug_class_map(backbone, head, imgs, test_cfg, ori_shape=None, flips=None, preprocess=None, max_batch=8, labels=None, evaluator=None, case=None,
-                  one_pass=None, confidence=False, calibration=None, selective=None, score="max", topk=None, topk_evaluator=None, segments=None, panoptic=None, boundary=None):
+                  one_pass=None, confidence=False, calibration=None, selective=None, score="max", topk=None, topk_evaluator=None, segments=None, panoptic=None, segment_table=None, boundary=None):
     """`aug_test` (ED:509-546) -> (uint8 class map [B, Ho, Wo], uncovered-pixel word), bit for bit argmax_map(aug_inference(...)) of the same arguments.
     Every view goes through backbone and head (`max_batch` windows per call, per view); then ONE launch (mmsa_aug_argmax) resizes every view's
     head-resolution logits as `class_map` would, takes the softmax, un-flips, averages over the views and takes the argmax, with no logits or probability
@@ -1350,7 +1375,7 @@ def aug_class_map(backbone, head, imgs, test_cfg, ori_shape=None, flips=None, pr
     `segments=` (mmsa.evaluate.SegmentEvaluator; needs `labels=`): the segment counts of the averaged map, over the stored map as well.
     `panoptic=` (mmsa.evaluate.PanopticEvaluator; needs `labels=`): the panoptic counts of the averaged map, likewise."""
     o = MapOptions.of("aug_class_map", confidence, None, score, one_pass, aug=True, topk=topk, labels=labels, evaluator=evaluator, case=case,
-                      calibration=calibration, selective=selective, topk_evaluator=topk_evaluator, boundary=boundary, segments=segments, panoptic=panoptic)
+                      calibration=calibration, selective=selective, topk_evaluator=topk_evaluator, boundary=boundary, segments=segments, panoptic=panoptic, segment_table=segment_table)
     imgs, flips, pre = AugPlan.views(imgs, flips, preprocess, "aug_class_map")
     frames = [_intake(img, p, "aug_class_map") for img, p in zip(imgs, pre)]
     plan = AugPlan.of(test_cfg, [f[:3] for f in frames], flips, ori_shape)
@@ -1462,7 +1487,7 @@ class SlideRunner:
 
     @torch.no_grad()
     def run(self, frame=None, labels=None, evaluator=None, case=None, fused=None, return_map=True, calibration=None, selective=None, topk_evaluator=None,
-            segments=None, panoptic=None, boundary=None):
+            segments=None, panoptic=None, segment_table=None, boundary=None):
         """Enqueue one frame on the current stream (asynchronous) -> FrameResult; `.outputs()` = (class map uint8 [B, H, W], uncovered-pixel flag) once the
         attention logit guard of this pass has been inspected.  The inspection costs one 4 * depth-byte copy per `check_every` frames and an event wait,
         no device sync; a frame that scored logits beyond the fp16 range raises mmsa.chains.AttentionRangeError from outputs() -- or from the next run(),
@@ -1482,7 +1507,7 @@ class SlideRunner:
         stored map are ADDED to it on device, under the same terms.
         `panoptic=` (mmsa.evaluate.PanopticEvaluator, made the same way; needs `labels=`; refused with return_map=False): the panoptic counts of the frame's
         stored map are ADDED to it on device, under the same terms."""
-        o = self.options.with_call("SlideRunner.run", labels, evaluator, case, calibration, selective, fused, return_map, topk_evaluator, segments=segments, boundary=boundary, panoptic=panoptic)
+        o = self.options.with_call("SlideRunner.run", labels, evaluator, case, calibration, selective, fused, return_map, topk_evaluator, segments=segments, boundary=boundary, panoptic=panoptic, segment_table=segment_table)
         o = o.at(self.out.shape, self.device, "SlideRunner.run")
         if frame is None:
             frame = self.frame

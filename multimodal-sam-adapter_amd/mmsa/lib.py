@@ -115,6 +115,9 @@ SIGNATURES = {
     "mmsa_eval_segments": [P, P, I, I, I, I, I, P, I, P, P, P, I, P, P, I, P, P, P],
     "mmsa_segment_pairs": [P, P, I, I, P, I, P, P, P, P, I, I, I, P, P, L, P, P],
     "mmsa_eval_panoptic": [P, P, I, I, I, I, I, P, I, P, P, P, I, P, P, P, P, P, L, P, P, P],
+    "mmsa_segment_table": [P, I, I, I, P, P, P, I, I, P, P, P, I, I, I, P, P, P, P, P],
+    "mmsa_segment_table_block": [],
+    "mmsa_select_segments_u8": [P, P, P, I, I, I, I, I, P, P],
     "mmsa_slide_argmax_eval": [P, I, I, I, I, P, P, I, I, I, I, I, P, P, I, I, P, P, P, P, I, P, P],
     "mmsa_render_u8": [P, L, L, I, I, I, P, I, I, P, I, I, I, c_double, c_double, P, P],
     "mmsa_render_denorm_f32": [P, L, L, I, I, I, P, I, I, P, I, I, I, P, P, I, I, c_double, c_double, P, P],
