@@ -684,6 +684,33 @@ int mmsa_segment_table_block(void); /* the pixels per word of segment_table's sc
 int mmsa_select_segments_u8(const unsigned char* pred, const int* ids, const unsigned char* keep, int B, int H, int W, int capacity, int fill,
                             unsigned char* out, mmsa_stream_t stream);
 
+/* --- run-length tables (csrc/runs.hip): the runs of a map, and the map of a table.  src [B, H, W] contiguous: uint8 (a class or code map) or int32 (the ids
+ *   of segment_table, -1 included; any value).  flat_b = the pixels of image b in row-major order (order 0) or column-major order (order 1: index x * H + y,
+ *   the order of COCO's mask RLE).  A HEAD is index 0 and every i > 0 with flat_b[i] != flat_b[i - 1]: runs continue across line ends; one value is ONE run.
+ *   run_lengths_u8 / _i32: count int32 [B] = the heads of image b, also where it exceeds capacity.  starts, values int32 [B, capacity]: row j <
+ *     min(count[b], capacity) = the flat index of the j-th head in ascending order, and flat_b there.  The rows from min(count[b], capacity) on are NOT
+ *     written: the caller's bytes stay.  Lengths are not stored: length[j] = (starts[j + 1], or H * W for the last) - starts[j].  Ascending starts and the
+ *     definition of a head make the table unique: the same bytes whatever the schedule.  scratch int32: one word per scan unit of run_lengths_block(0)
+ *     flat indices, B * ceil(H * W / 2048) words, and for order 1 the transposed map behind them: B * H * W more words for _i32, ceil(B * H * W / 4) for
+ *     _u8.  Three launches, reduce-then-scan: heads per unit, the exclusive prefix sums of the unit counts (one workgroup per image, run_lengths_block(3)
+ *     counts per trip), and the units again, writing their heads at their offsets.  Order 1 first transposes the map into scratch (one more launch, 64 x 64
+ *     tiles through padded LDS) and counts the rows of the copy: its flat index is the column-major index.  No workgroup waits for another; every loop is
+ *     bounded by an index or a unit count.  src, count, starts, values and scratch are separate buffers.
+ *   run_lengths_block(what): 0 = the pixels per scan unit (2048), 1 = the tile edge of the transpose (64), 2 = the lanes of the scan workgroup (256), 3 = the
+ *     unit counts per trip of the scan (1024) in THIS build; -1 otherwise.
+ *   run_decode_i32: the inverse, a lane per pixel: out int32 [B, H, W] = values[b, j] of the last row j < min(count[b], capacity) with starts[b, j] <= the
+ *     pixel's flat index (a binary search, 32 steps at the most), `fill` where the image has no row.  Of an overflowed table (count[b] > capacity) the last
+ *     kept run has no row behind it that ends it: its head pixel gets its value, and every pixel past that head gets `fill`.
+ *   B * H * W < 2^31, B <= 65535, 1 <= capacity, B * capacity < 2^31, order 0 or 1; a limit broken or a null pointer: MMSA_ERR_ARG with a message, before
+ *   any launch. --- */
+int mmsa_run_lengths_u8(const unsigned char* src, int B, int H, int W, int order, int capacity, int* count, int* starts, int* values, int* scratch,
+                        mmsa_stream_t stream);
+int mmsa_run_lengths_i32(const int* src, int B, int H, int W, int order, int capacity, int* count, int* starts, int* values, int* scratch,
+                         mmsa_stream_t stream);
+int mmsa_run_lengths_block(int what);
+int mmsa_run_decode_i32(const int* count, const int* starts, const int* values, int B, int H, int W, int order, int capacity, int fill, int* out,
+                        mmsa_stream_t stream);
+
 /* --- the picture of a prediction (segmentation/mmseg_custom/apis/test_bs.py:257-349, the `--show` / `--show-dir` output): `tensor2imgs` (test_bs.py:18-63) on
  *     planes 0..2 of the input tensor -> the crop `img[:h, :w]` (test_bs.py:275-276) -> `show_result` (tools/color_gt_according_palette.py:23-81:
  *     color_seg[seg == label] = color, channels reversed, img * (1 - opacity) + color_seg * opacity, .astype(uint8)), in one pass.

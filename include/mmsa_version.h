@@ -33,7 +33,10 @@
  *      prediction against the ground truth by class, size bucket and coverage bin: segment recall and precision).
  *      Still 114, for the same reason: new entries mmsa_segment_table / mmsa_segment_table_block / mmsa_select_segments_u8 (the segments of a code map handed out: dense ids in raster
  *      order of the first pixel by a device-wide prefix sum, one record per segment -- class, area, box, coordinate sums, fixed-point score sum -- and the
- *      class map with chosen segments painted over). */
+ *      class map with chosen segments painted over).
+ *      Still 114, for the same reason: new entries mmsa_run_lengths_u8 / mmsa_run_lengths_i32 / mmsa_run_lengths_block / mmsa_run_decode_i32 (the runs of a
+ *      class map or an ids map in row-major or column-major order -- starts and values in ascending order by a device-wide prefix sum over the run heads --
+ *      and the map of such a table). */
 #ifndef MMSA_VERSION_H
 #define MMSA_VERSION_H
 #define MMSA_ABI_VERSION 114

@@ -29,6 +29,8 @@ from .evaluate import (PanopticEvaluator, PairTable, segment_pairs, panoptic_cou
                        panoptic_summary_of)  # the pair table of two root maps, TP / FP / FN and the IoU sum by class and size, PQ / SQ / RQ)
 from .evaluate import SegmentTable, segment_table, select_segments, segment_records_of  # noqa: F401  (the segments handed out: dense ids, and one record
 #                                                            per segment -- class, area, box, centroid, mean score -- by a prefix sum over the root pixels)
+from .evaluate import (RunTable, run_lengths, run_decode, runs_of_value, coco_rle_of, rle_area_of, rle_bbox_of)  # noqa: F401  (run-length tables of a class
+#                                                            map or an ids map, row-major or column-major, and the uncompressed COCO RLE of one id or class)
 from . import render  # noqa: F401  (the picture of a prediction on device: palette map over the frame, show_result)
 from .render import Renderer
 from .registry import BACKBONES, HEADS, build_backbone, build_head
@@ -59,4 +61,5 @@ __all__ = ["SegformerHead", "HEADS", "build_head", "register_head", "SAMAdapterb
            "EuclideanBoundaryEvaluator", "boundary_distance", "boundary_counts_d2", "boundary_displacement", "boundary_f_of", "boundary_f_curve_of",
            "boundary_distance_percentile_of", "SegmentEvaluator", "components", "component_areas", "suppress_small", "segment_counts", "segment_totals_of",
            "segment_rate_of", "segment_f_of", "PanopticEvaluator", "PairTable", "segment_pairs", "panoptic_counts", "panoptic_quality_of",
-           "panoptic_summary_of", "SegmentTable", "segment_table", "select_segments", "segment_records_of"]
+           "panoptic_summary_of", "SegmentTable", "segment_table", "select_segments", "segment_records_of", "RunTable", "run_lengths",
+           "run_decode", "runs_of_value", "coco_rle_of", "rle_area_of", "rle_bbox_of"]

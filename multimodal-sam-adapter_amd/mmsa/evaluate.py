@@ -2478,10 +2478,15 @@ class SegmentTable:
     nearest-neighbour tables).  A component is listed iff its area >= min_area and its code is a class; void=True also lists the other codes.  `capacity` = the
     rows per image (None: max(1024, H * W // 64) of every shape); the records of the segments beyond it are dropped, `count` keeps the true number and
     `overflow()` / `host()` say so.  update() makes the launches into buffers cached per shape and stream: no host sync, and no allocation once the buffers of a
-    shape exist.  Every class-map entry's `segment_table=` takes one made with num_classes=."""
+    shape exist.  Every class-map entry's `segment_table=` takes one made with num_classes=.  runs="column" or "row": update() also fills `self.runs`, the
+    RunTable of `ids` in that order (the launches of `run_lengths` into buffers of the same cache, `run_capacity` rows per image; None: max(4096,
+    H * W // 8)), and with "column" `segments_info(b, masks=True)` carries every segment's COCO RLE.  runs=None: the launches are the ones above alone."""
 
-    def __init__(self, num_classes=None, labels_prep=None, connectivity=8, min_area=1, void=False, capacity=None):
+    def __init__(self, num_classes=None, labels_prep=None, connectivity=8, min_area=1, void=False, capacity=None, runs=None, run_capacity=None):
         who = "mmsa.SegmentTable"
+        self.run_order = None if runs is None else check_run_order(runs, who)
+        self._run_capacity = None if run_capacity is None else check_run_capacity(run_capacity, who)
+        self.runs = None         # the RunTable of `ids` of the last update (runs= given)
         if (labels_prep is None) == (num_classes is None):
             raise ValueError(f"{who}: takes num_classes= (stored class maps) or labels_prep= (raw labels), one of them")
         if labels_prep is None:
@@ -2524,7 +2529,9 @@ class SegmentTable:
                                        records=torch.zeros(B, capacity, len(SEGMENT_FIELDS), dtype=torch.int64, device=device),
                                        ids=torch.empty(B, H, W, dtype=torch.int32, device=device), scratch=torch.empty(B * blocks, dtype=torch.int32, device=device),
                                        root=torch.empty(B, H, W, dtype=torch.int32, device=device),
-                                       area=torch.empty(B, H, W, dtype=torch.int32, device=device) if self.min_area > 1 else None)
+                                       area=torch.empty(B, H, W, dtype=torch.int32, device=device) if self.min_area > 1 else None,
+                                       runs=None if self.run_order is None else RunTable.empty(
+                                           B, H, W, self.run_order, default_run_capacity(H, W) if self._run_capacity is None else self._run_capacity, device))
         return m
 
     @torch.no_grad()
@@ -2563,7 +2570,9 @@ class SegmentTable:
                      None if xmap is None else xmap.data_ptr(), H, W, root.data_ptr(), None if m["area"] is None else m["area"].data_ptr(),
                      None if values is None else values.data_ptr(), self.min_area, 256 if self.void else self.num_classes, capacity, m["count"].data_ptr(),
                      m["ids"].data_ptr(), m["records"].data_ptr(), m["scratch"].data_ptr(), ops._stream())
-        self.count, self.records, self.ids, self.root = m["count"], m["records"], m["ids"], root
+            if m["runs"] is not None:
+                run_lengths(m["ids"], table=m["runs"])
+        self.count, self.records, self.ids, self.root, self.runs = m["count"], m["records"], m["ids"], root, m["runs"]
         self.shape, self.scored = (B, H, W), values is not None
         return self
 
@@ -2595,11 +2604,25 @@ class SegmentTable:
         parts = [segment_records_of(records[i], count[i], self.scored, i) for i in images]
         return parts[0] if len(parts) == 1 else np.concatenate(parts)
 
-    def segments_info(self, b):
+    def segments_info(self, b, masks=False):
         """The `segments_info` list of the COCO panoptic format for image b: dicts with 'id' (the dense id + 1: the format's PNG is `ids + 1`, 0 = VOID),
-        'category_id', 'area', 'bbox' [x, y, width, height] and 'iscrowd' 0, and next to them 'centroid' [x, y] and 'score' (None without `values`)."""
-        return [dict(id=int(s["id"]) + 1, category_id=int(s["category"]), area=int(s["area"]), bbox=[int(v) for v in s["bbox"]], iscrowd=0,
+        'category_id', 'area', 'bbox' [x, y, width, height] and 'iscrowd' 0, and next to them 'centroid' [x, y] and 'score' (None without `values`).
+        masks=True adds 'segmentation', the segment's uncompressed COCO RLE (`coco_rle_of` on the runs of `ids`): a table made with runs="column" has them,
+        any other raises ValueError."""
+        if masks and self.run_order != "column":
+            raise ValueError(f"mmsa.SegmentTable: segments_info(masks=True) reads the column-major runs of ids: make the SegmentTable with runs='column' "
+                             f"(this one has runs={self.run_order!r})")
+        info = [dict(id=int(s["id"]) + 1, category_id=int(s["category"]), area=int(s["area"]), bbox=[int(v) for v in s["bbox"]], iscrowd=0,
                      centroid=[float(v) for v in s["centroid"]], score=float(s["score"]) if self.scored else None) for s in self.host(int(b))]
+        if masks and info:
+            H, W = self.shape[1:]
+            starts, lengths, values = self.runs.host(int(b))
+            by = np.argsort(values, kind="stable")                             # the runs grouped by id, ascending starts within one
+            lo, hi = (np.searchsorted(values[by], np.arange(len(info)), side) for side in ("left", "right"))
+            for k, d in enumerate(info):
+                at = by[lo[k]:hi[k]]
+                d["segmentation"] = {"size": [H, W], "counts": _rle_counts(starts[at], lengths[at], H * W)}
+        return info
 
     @torch.no_grad()
     def keep(self, min_area=None, max_area=None, min_score=None, classes=None):
@@ -2673,3 +2696,227 @@ def select_segments(pred, table, keep, fill=255, out=None):
             _check_map(out, "out", torch.uint8, "a uint8 class map", like=pred)
         lib.call("mmsa_select_segments_u8", pred.data_ptr(), table.ids.data_ptr(), keep.data_ptr(), B, H, W, capacity, int(fill), out.data_ptr(), ops._stream())
     return out
+
+
+# ---- run-length tables: the runs of a class map or an ids map, and the COCO RLE of one id (csrc/runs.hip) ----
+# Of image b of a map m [B, H, W], flat_b = m[b].ravel() (order "row") or m[b].T.ravel() (order "column": the order of COCO's mask RLE).  A HEAD is index 0 and
+# every i > 0 with flat_b[i] != flat_b[i - 1]: runs continue across line ends, and a map of one value is ONE run.  count[b] = the heads, also beyond capacity;
+# starts[b, j] / values[b, j] = the flat index of the j-th head in ascending order and flat_b there, for j < min(count[b], capacity); the rows behind them are
+# not written.  length[j] = (starts[j + 1] or H * W) - starts[j].
+RUNS_BLOCK = 2048                  # csrc/runs.hip RUNS_BLOCK: the flat indices per scan unit (one scratch word each)
+RUNS_TILE = 64                     # csrc/runs.hip RUNS_TILE: the tile edge of the transpose the column order starts with
+RUNS_SCAN_LANES = 256              # csrc/runs.hip RUNS_SCAN_LANES: the lanes of the scan workgroup
+RUNS_SCAN_TRIP = 1024              # the unit counts one trip of the scan pass takes (RUNS_SCAN_LANES * RUNS_SCAN_PER_LANE)
+RUN_ORDERS = ("row", "column")     # the library's order 0, 1
+MIN_RUN_CAPACITY = 4096
+
+
+def default_run_capacity(H, W):
+    """The default runs per image of a run table: max(4096, H * W // 8)."""
+    return max(MIN_RUN_CAPACITY, int(H) * int(W) // 8)
+
+
+def check_run_capacity(capacity, who="mmsa.evaluate"):
+    if not _is_int(capacity, 1, (1 << 31) - 1):
+        raise ValueError(f"{who}: capacity = {capacity!r}; a positive number of runs per image is expected (None: max({MIN_RUN_CAPACITY}, H * W // 8))")
+    return int(capacity)
+
+
+def check_run_order(order, who="mmsa.evaluate"):
+    if order not in RUN_ORDERS:
+        raise ValueError(f"{who}: order = {order!r}; 'row' (row-major runs) or 'column' (column-major runs: COCO's mask order) is expected")
+    return order
+
+
+def run_units(H, W):
+    """The scan units of one image, a scratch word each: ceil(H * W / RUNS_BLOCK)."""
+    return -(-int(H) * int(W) // RUNS_BLOCK)
+
+
+_run_constants_checked = False
+
+
+def run_scratch_words(B, H, W, order, itemsize=4):
+    """The int32 words of a launch's scratch: the unit counts of every image, and for "column" the transposed map (of `itemsize` bytes per pixel) behind them."""
+    global _run_constants_checked
+    if not _run_constants_checked:      # once per process: a variant build (MMSA_LIB) with other constants would get a scratch of the wrong size
+        for what, want in ((0, RUNS_BLOCK), (1, RUNS_TILE), (2, RUNS_SCAN_LANES), (3, RUNS_SCAN_TRIP)):
+            if lib.raw.mmsa_run_lengths_block(what) != want:
+                raise RuntimeError(f"mmsa.evaluate: the library's run-length constant {what} is {lib.raw.mmsa_run_lengths_block(what)}, mmsa.evaluate has {want}")
+        _run_constants_checked = True
+    return B * run_units(H, W) + (-(-B * int(H) * int(W) * itemsize // 4) if check_run_order(order) == "column" else 0)
+
+
+class RunTable:
+    """A run table on the device: `count` int32 [B] (the runs of every image, also beyond capacity), `starts` and `values` int32 [B, capacity] (the flat index
+    and the value of the first min(count, capacity) runs, in ascending order), the `order` ("row" or "column") the maps were flattened in, `shape` = (B, H, W) of
+    the maps, and `scratch` (int32, `run_scratch_words`: the launch's own -- the unit counts of the prefix sum and, for "column", the transposed map)."""
+
+    def __init__(self, count, starts, values, order, shape, capacity, scratch=None):
+        self.count, self.starts, self.values, self.scratch = count, starts, values, scratch
+        self.order = check_run_order(order, "mmsa.RunTable")
+        self.shape = None if shape is None else tuple(int(v) for v in shape)
+        self.capacity = check_run_capacity(capacity, "mmsa.RunTable")
+
+    @classmethod
+    def empty(cls, B, H, W, order, capacity, device):
+        """The buffers of a batch of B maps of H x W pixels, uint8 or int32: nothing a later run_lengths(..., table=) of this shape has to allocate."""
+        capacity = check_run_capacity(capacity, "mmsa.RunTable")
+        if B * capacity >= 1 << 31:
+            raise RuntimeError(f"mmsa.RunTable: {B} images of {capacity} runs; a row is indexed in 32 bits (B * capacity < 2^31)")
+        return cls(torch.zeros(B, dtype=torch.int32, device=device), torch.empty(B, capacity, dtype=torch.int32, device=device),
+                   torch.empty(B, capacity, dtype=torch.int32, device=device), order, (B, H, W), capacity,
+                   torch.empty(run_scratch_words(B, H, W, order), dtype=torch.int32, device=device))
+
+    def _check(self, B, device):
+        ok = all(isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.is_contiguous() and t.device == device for t in (self.count, self.starts, self.values))
+        if not ok or tuple(self.count.shape) != (B,) or tuple(self.starts.shape) != (B, self.capacity) or tuple(self.values.shape) != (B, self.capacity):
+            raise RuntimeError(f"mmsa.evaluate: a RunTable of {B} images holds contiguous int32 count [{B}], starts and values [{B}, {self.capacity}] on {device}")
+        return self
+
+    def overflow(self):
+        """Whether an image has more runs than rows (the device words of `count`): its last runs were dropped."""
+        return bool((self.count > self.capacity).any().item())
+
+    def host(self, b):
+        """The runs of image b on the host -> int64 numpy (starts, lengths, values).  RuntimeError naming capacity= where the image has more runs than rows."""
+        B, H, W = self.shape
+        if not _is_int(b, 0, B - 1):
+            raise ValueError(f"mmsa.RunTable: b = {b!r}; an image index 0..{B - 1} is expected")
+        n = int(self.count[int(b)].item())
+        if n > self.capacity:
+            raise RuntimeError(f"mmsa.RunTable: image {int(b)} has {n} runs and the table {self.capacity} rows: the last {n - self.capacity} were dropped; fill a "
+                               f"table with a larger capacity= (capacity=H * W can never overflow)")
+        starts = self.starts[int(b), :n].cpu().numpy().astype(np.int64)
+        values = self.values[int(b), :n].cpu().numpy().astype(np.int64)
+        return starts, np.diff(starts, append=H * W), values
+
+
+def _check_run_map(map):
+    if not isinstance(map, torch.Tensor) or map.dtype not in (torch.uint8, torch.int32):
+        raise RuntimeError(f"mmsa.evaluate: map must be a uint8 (class map) or int32 (ids) tensor, got {map.dtype if isinstance(map, torch.Tensor) else type(map).__name__}")
+    return _check_map(map, "map", map.dtype, "a uint8 or int32 map")
+
+
+@torch.no_grad()
+def run_lengths(map, order=None, capacity=None, table=None):
+    """The runs of a uint8 class map or an int32 ids map [B, H, W] (mmsa_run_lengths_u8 / _i32: three launches, and for "column" a transpose into the table's
+    scratch before them; no host sync) -> RunTable.  `order` = "column" (None: the default; COCO's mask order) or "row"; `capacity` = the rows per image (None: max(4096, H * W // 8); any positive number).  `table=` (a RunTable
+    of B images: its own order and capacity hold, and one spelled out here must agree) is filled instead: nothing is allocated where its scratch holds
+    `run_scratch_words` of this shape (RunTable.empty sizes it so), so the call can be captured.  Nothing is read back: look at `table.overflow()`, or call
+    `table.host(b)`, which raises where runs were dropped."""
+    if order is not None:
+        check_run_order(order)
+    if capacity is not None:
+        capacity = check_run_capacity(capacity)
+    if table is not None and not isinstance(table, RunTable):
+        raise RuntimeError(f"mmsa.evaluate: table= takes an mmsa.evaluate.RunTable, got {type(table).__name__}")
+    src = _check_run_map(map)
+    B, H, W = (int(v) for v in src.shape)
+    if B * H * W == 0:
+        raise RuntimeError(f"mmsa.evaluate: an empty map {tuple(src.shape)}")
+    if B * H * W >= 1 << 31:
+        raise RuntimeError(f"mmsa.evaluate: {B} x {H} x {W} pixels; a run table indexes a batch in 32 bits (B * H * W < 2^31)")
+    with torch.cuda.device(src.device):
+        if table is None:
+            table = RunTable.empty(B, H, W, order or "column", default_run_capacity(H, W) if capacity is None else capacity, src.device)
+        else:
+            table._check(B, src.device)
+            for name, v, own in (("order", order, table.order), ("capacity", capacity, table.capacity)):
+                if v is not None and v != own:
+                    raise RuntimeError(f"mmsa.evaluate: {name}={v!r} with a table made with {name}={own!r}")
+        words = run_scratch_words(B, H, W, table.order, src.element_size())
+        s = table.scratch
+        if not (isinstance(s, torch.Tensor) and s.dtype == torch.int32 and s.is_contiguous() and s.device == src.device and s.numel() >= words):
+            if _capturing(src.device):
+                raise RuntimeError(f"mmsa.evaluate: the scratch of a {B} x {H} x {W} run table cannot be allocated during a graph capture: make the table with "
+                                   "RunTable.empty of this shape, or run one call of this shape before capturing")
+            table.scratch = torch.empty(words, dtype=torch.int32, device=src.device)
+        table.shape = (B, H, W)
+        lib.call("mmsa_run_lengths_u8" if src.dtype == torch.uint8 else "mmsa_run_lengths_i32", src.data_ptr(), B, H, W, RUN_ORDERS.index(table.order),
+                 table.capacity, table.count.data_ptr(), table.starts.data_ptr(), table.values.data_ptr(), table.scratch.data_ptr(), ops._stream())
+    return table
+
+
+@torch.no_grad()
+def run_decode(table, fill=-1, out=None):
+    """The map of a run table (one launch, mmsa_run_decode_i32: a lane per pixel and a binary search over the starts) -> int32 [B, H, W]: the value of the run
+    the pixel lies in; `fill` where the image has no run.  Of an overflowed table the last kept run has no row behind it that ends it: its head pixel gets its
+    value and every pixel past that head `fill`."""
+    if not isinstance(table, RunTable):
+        raise RuntimeError(f"mmsa.evaluate: table takes an mmsa.evaluate.RunTable, got {type(table).__name__}")
+    if table.shape is None:
+        raise RuntimeError("mmsa.evaluate: a RunTable without its maps' shape= (B, H, W) cannot be decoded")
+    if not _is_int(fill, -(1 << 31), (1 << 31) - 1):
+        raise ValueError(f"mmsa.evaluate: fill = {fill!r}; an int32 value is expected")
+    B, H, W = table.shape
+    device = table.count.device
+    table._check(B, device)
+    with torch.cuda.device(device):
+        if out is None:
+            out = torch.empty(B, H, W, dtype=torch.int32, device=device)
+        else:
+            _check_int_plane(out, "out", (B, H, W), device, "the decoded map")
+        lib.call("mmsa_run_decode_i32", table.count.data_ptr(), table.starts.data_ptr(), table.values.data_ptr(), B, H, W, RUN_ORDERS.index(table.order),
+                 table.capacity, int(fill), out.data_ptr(), ops._stream())
+    return out
+
+
+def _runs3(starts, lengths, values):
+    s, l, v = (np.asarray(a) for a in (starts, lengths, values))
+    if any(a.ndim != 1 or a.dtype.kind not in "iu" for a in (s, l, v)) or not len(s) == len(l) == len(v):
+        raise ValueError("mmsa.evaluate: runs are three integer arrays of one length (starts, lengths, values): RunTable.host(b)")
+    return s.astype(np.int64), l.astype(np.int64), v.astype(np.int64)
+
+
+def runs_of_value(starts, lengths, values, v):
+    """The runs of one id or class among the runs of `RunTable.host(b)` -> (starts, lengths) of those with value v, in ascending order."""
+    s, l, vals = _runs3(starts, lengths, values)
+    at = vals == int(v)
+    return s[at], l[at]
+
+
+def _rle_counts(s, l, n):
+    """Ascending, non-adjacent runs (start, length) of the ones of a mask of n pixels -> COCO's counts: zeros first, no trailing zero-length entry."""
+    ends = s + l
+    counts = np.stack([s - np.concatenate([[0], ends[:-1]]), l], 1).ravel().tolist()
+    last = int(ends[-1]) if len(ends) else 0
+    return counts + [n - last] if last < n else counts
+
+
+def coco_rle_of(starts, lengths, values, v, H, W, order="column"):
+    """The uncompressed COCO RLE of the mask `map == v` from the runs of a COLUMN-order table (`RunTable.host(b)`) -> {"size": [H, W], "counts": [...]}: the
+    run lengths of the column-major mask, alternating and starting with the zeros (a leading 0 where the mask holds pixel 0), without a trailing zero-length
+    entry.  Two runs of v are never adjacent in a table (the second would be no head), so no count in the middle is 0.  `order` = the table's: "row" raises
+    ValueError."""
+    if check_run_order(order) != "column":
+        raise ValueError("mmsa.evaluate: COCO's RLE is the column-major mask: it takes the runs of a table made with order='column', this one is order='row'")
+    s, l, vals = _runs3(starts, lengths, values)
+    n = int(H) * int(W)
+    if len(s) == 0 or s[0] != 0 or s[-1] + l[-1] != n or (l <= 0).any():
+        raise ValueError(f"mmsa.evaluate: the runs do not cover the {H} x {W} = {n} pixels of the map from index 0")
+    at = vals == int(v)
+    return {"size": [int(H), int(W)], "counts": _rle_counts(s[at], l[at], n)}
+
+
+def rle_area_of(rle):
+    """The pixels of an uncompressed COCO RLE (pycocotools' `area`, in integers): the sum of the one-runs."""
+    return int(sum(rle["counts"][1::2]))
+
+
+def rle_bbox_of(rle):
+    """The box [x, y, width, height] of an uncompressed COCO RLE (pycocotools' `toBbox`, in integers); [0, 0, 0, 0] for an empty mask.  A one-run that
+    crosses a column end spans every row."""
+    H = int(rle["size"][0])
+    c = np.asarray(rle["counts"], dtype=np.int64)
+    ends = np.cumsum(c)
+    a, e = (ends - c)[1::2], ends[1::2] - 1            # the first and the last pixel of every one-run
+    keep = e >= a
+    a, e = a[keep], e[keep]
+    if len(a) == 0:
+        return [0, 0, 0, 0]
+    xa, xe = a // H, e // H
+    wraps = bool((xa != xe).any())
+    x0, x1 = int(xa.min()), int(xe.max())
+    y0, y1 = (0, H - 1) if wraps else (int((a % H).min()), int((e % H).max()))
+    return [x0, y0, x1 - x0 + 1, y1 - y0 + 1]

@@ -118,6 +118,10 @@ SIGNATURES = {
     "mmsa_segment_table": [P, I, I, I, P, P, P, I, I, P, P, P, I, I, I, P, P, P, P, P],
     "mmsa_segment_table_block": [],
     "mmsa_select_segments_u8": [P, P, P, I, I, I, I, I, P, P],
+    "mmsa_run_lengths_u8": [P, I, I, I, I, I, P, P, P, P, P],
+    "mmsa_run_lengths_i32": [P, I, I, I, I, I, P, P, P, P, P],
+    "mmsa_run_lengths_block": [I],
+    "mmsa_run_decode_i32": [P, P, P, I, I, I, I, I, I, P, P],
     "mmsa_slide_argmax_eval": [P, I, I, I, I, P, P, I, I, I, I, I, P, P, I, I, P, P, P, P, I, P, P],
     "mmsa_render_u8": [P, L, L, I, I, I, P, I, I, P, I, I, I, c_double, c_double, P, P],
     "mmsa_render_denorm_f32": [P, L, L, I, I, I, P, I, I, P, I, I, I, P, P, I, I, c_double, c_double, P, P],
