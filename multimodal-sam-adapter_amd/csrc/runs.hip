@@ -6,15 +6,11 @@
 // count[b] = the heads of image b, also where it exceeds capacity; starts[b, j] = the flat index of the j-th head in ascending order, values[b, j] = flat_b
 // there, for j < min(count[b], capacity); the rows behind them are NOT written.  Lengths are not stored: length[j] = (starts[j + 1] or H * W) - starts[j].
 //
-// The launches.  The prefix sum over the heads is reduce-then-scan, as in csrc/segtable.hip: no workgroup waits for another and no loop spins on a value
-// somebody else must write.  The heads are counted per SCAN UNIT of RUNS_BLOCK consecutive flat indices, a workgroup per unit.
-//   count pass   heads per unit -> scratch[b, unit].
-//   scan pass    ONE workgroup per image turns scratch[b, :] into its exclusive prefix sums: RUNS_SCAN_LANES lanes of RUNS_SCAN_PER_LANE consecutive counts
-//                per trip, with a carry; the loop is bounded by the unit count.
-//   write pass   the count pass again, now with the unit's offset: head j = offset + the heads before it in its unit; starts / values for j < capacity, and
-//                the last unit of an image writes count[b].
-// Row order: the pixels of a unit in (k, wave, lane) order as in segtable.hip.  A lane takes its predecessor from the lane below it; lane 0 of a wave reads
-//   it from memory -- the pixel before the unit's first included, across the line end.
+// The launches.  The heads are numbered by the stream compaction of csrc/compact.h (count, scan, rank: three launches); its blocks are the SCAN UNITS of
+// RUNS_BLOCK consecutive flat indices.  The rank launch is the write pass: starts / values of head j for j < capacity, and the last unit of an image writes
+// count[b].
+// Row order: a lane takes its predecessor from the lane below it; lane 0 of a wave reads it from memory -- the pixel before the unit's first included,
+//   across the line end.
 // Column order: the map is first transposed into the caller's scratch, behind the unit counts (a 64 x 64 tile per workgroup through padded LDS: row reads
 //   and row writes), and the row-order launches run on the copy: the flat index of the transposed map IS the column-major index.  A form that walked a
 //   staged tile with a lane per column, one (column, row tile) piece per scan unit, was built and timed first: on two 1024 x 1024 maps / the 1080 x 1920
@@ -23,63 +19,18 @@
 // Decode: a lane per pixel finds the last start <= its flat index by a binary search over min(count[b], capacity) starts, 32 steps at the most.
 #include "common.h"
 #include "comp_shared.h"    // comp_check_size
+#include "compact.h"
 
 #ifndef RUNS_BLOCK
 #define RUNS_BLOCK 2048                       // pixels per unit (and workgroup) of the row order; a multiple of 256
 #endif
 #define RUNS_TILE 64                          // rows and columns of a tile of the transpose: a wave is a row of it
-#define RUNS_SCAN_LANES 256                   // lanes of the scan workgroup
-#define RUNS_SCAN_PER_LANE 4                  // consecutive unit counts a lane takes per trip
 #define RUNS_PER_LANE (RUNS_BLOCK / 256)
 
-static_assert(RUNS_BLOCK % 256 == 0 && RUNS_PER_LANE >= 1 && RUNS_PER_LANE * 4 <= 64, "the (k, wave) counts of a block are scanned by one wave in one trip");
+COMPACT_CHECK_BLOCK(RUNS_BLOCK);
 static_assert(RUNS_TILE == 64, "a wave is one row of a tile");
 
-// an inclusive prefix sum over the 64 lanes of a wave
-__device__ __forceinline__ int runs_wave_scan(int v, int lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int up = __shfl_up(v, d);
-    if (lane >= d) v += up;
-  }
-  return v;
-}
-
-// grid B: scratch[b, :] (n words) -> its exclusive prefix sums, in place
-__global__ __launch_bounds__(RUNS_SCAN_LANES) void runs_scan_kernel(int n, int* scratch) {
-  __shared__ int ws[RUNS_SCAN_LANES / 64];
-  int* s = scratch + (long)blockIdx.x * n;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int carry = 0;
-  for (long c = 0; c < n; c += RUNS_SCAN_LANES * RUNS_SCAN_PER_LANE) {         // bounded by the unit count
-    const long j0 = c + (long)threadIdx.x * RUNS_SCAN_PER_LANE;
-    int v[RUNS_SCAN_PER_LANE], sum = 0;
-#pragma unroll
-    for (int k = 0; k < RUNS_SCAN_PER_LANE; ++k) {
-      v[k] = j0 + k < n ? s[j0 + k] : 0;
-      sum += v[k];
-    }
-    const int inc = runs_wave_scan(sum, lane);
-    if (lane == 63) ws[w] = inc;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int k = 0; k < RUNS_SCAN_LANES / 64; ++k) {
-      before += k < w ? ws[k] : 0;
-      total += ws[k];
-    }
-    int run = carry + before + inc - sum;
-#pragma unroll
-    for (int k = 0; k < RUNS_SCAN_PER_LANE; ++k) {
-      if (j0 + k < n) s[j0 + k] = run;
-      run += v[k];
-    }
-    carry += total;
-    __syncthreads();                                                           // ws is written again in the next trip
-  }
-}
-
-// ---- row order.  grid (cdiv(H * W, RUNS_BLOCK), B); lane t owns the pixels block * RUNS_BLOCK + k * 256 + t: pixel order is (k, wave, lane)
+// ---- row order.  grid (cdiv(H * W, RUNS_BLOCK), B)
 
 // pixel i of the image at `img` (every lane of the wave calls it together): whether it is a head, and its value
 template <typename T>
@@ -92,52 +43,31 @@ __device__ __forceinline__ bool runs_row_head(const T* __restrict__ img, long HW
 
 template <typename T>
 __global__ __launch_bounds__(256) void runs_row_count_kernel(const T* __restrict__ src, long HW, int nunit, int* __restrict__ scratch) {
-  __shared__ int ws[4];
   const T* img = src + blockIdx.y * HW;
-  const int lane = threadIdx.x & 63;
-  int n = 0;
-#pragma unroll
-  for (int k = 0; k < RUNS_PER_LANE; ++k) {
-    int v;
-    n += (int)__popcll(__ballot(runs_row_head(img, HW, (long)blockIdx.x * RUNS_BLOCK + k * 256 + threadIdx.x, lane, v)));      // the wave's heads, in every lane
-  }
-  if (lane == 0) ws[threadIdx.x >> 6] = n;
-  __syncthreads();
-  if (threadIdx.x == 0) scratch[(long)blockIdx.y * nunit + blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
+  int v;
+  compact_block_count<RUNS_PER_LANE>([&](int, long i) { return runs_row_head(img, HW, i, threadIdx.x & 63, v); }, nunit, scratch);
 }
 
 template <typename T>
 __global__ __launch_bounds__(256) void runs_row_write_kernel(const T* __restrict__ src, long HW, int nunit, const int* __restrict__ scratch, int capacity,
                                                              int* __restrict__ count, int* __restrict__ starts, int* __restrict__ values) {
-  __shared__ int cnt[RUNS_PER_LANE * 4 + 1];                                   // the heads per (k, wave), then their exclusive prefix sums and the total
   const T* img = src + blockIdx.y * HW;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, b = blockIdx.y;
-  int v[RUNS_PER_LANE], before[RUNS_PER_LANE];
+  const int lane = threadIdx.x & 63, b = blockIdx.y;
+  int v[RUNS_PER_LANE], rank[RUNS_PER_LANE], total;
   bool head[RUNS_PER_LANE];
 #pragma unroll
-  for (int k = 0; k < RUNS_PER_LANE; ++k) {
-    head[k] = runs_row_head(img, HW, (long)blockIdx.x * RUNS_BLOCK + k * 256 + threadIdx.x, lane, v[k]);
-    const unsigned long long ms = __ballot(head[k]);
-    before[k] = (int)__popcll(ms & ((1ull << lane) - 1ull));                   // the heads of this wave and k below this lane
-    if (lane == 0) cnt[k * 4 + w] = (int)__popcll(ms);
-  }
-  __syncthreads();
-  if (w == 0) {                                                                // RUNS_PER_LANE * 4 <= 64 entries: one trip of one wave
-    const int c = lane < RUNS_PER_LANE * 4 ? cnt[lane] : 0, inc = runs_wave_scan(c, lane);
-    if (lane < RUNS_PER_LANE * 4) cnt[lane] = inc - c;
-    if (lane == 63) cnt[RUNS_PER_LANE * 4] = inc;
-  }
-  __syncthreads();
+  for (int k = 0; k < RUNS_PER_LANE; ++k) head[k] = runs_row_head(img, HW, compact_index<RUNS_PER_LANE>(k), lane, v[k]);
+  compact_block_rank<RUNS_PER_LANE>(head, rank, total);
   const int off = scratch[(long)b * nunit + blockIdx.x];
 #pragma unroll
   for (int k = 0; k < RUNS_PER_LANE; ++k) {
-    const int j = off + cnt[k * 4 + w] + before[k];
+    const int j = off + rank[k];
     if (head[k] && j < capacity) {
-      starts[(long)b * capacity + j] = (int)((long)blockIdx.x * RUNS_BLOCK + k * 256 + threadIdx.x);
+      starts[(long)b * capacity + j] = (int)compact_index<RUNS_PER_LANE>(k);
       values[(long)b * capacity + j] = v[k];
     }
   }
-  if ((int)blockIdx.x == nunit - 1 && threadIdx.x == 0) count[b] = off + cnt[RUNS_PER_LANE * 4];
+  if ((int)blockIdx.x == nunit - 1 && threadIdx.x == 0) count[b] = off + total;
 }
 
 // ---- column order: the map transposed, then the row order.  grid (tiles across * tiles down, B), 256 lanes: lane (c = t & 63, q = t >> 6)
@@ -178,7 +108,7 @@ static int runs_launch(const char* name, const T* src, int B, int H, int W, int 
     src = flipped;
   }
   hipLaunchKernelGGL(runs_row_count_kernel<T>, dim3((unsigned)nunit, B), dim3(256), 0, stream, src, HW, nunit, scratch);
-  hipLaunchKernelGGL(runs_scan_kernel, dim3(B), dim3(RUNS_SCAN_LANES), 0, stream, nunit, scratch);
+  compact_scan(scratch, B, nunit, stream);
   hipLaunchKernelGGL(runs_row_write_kernel<T>, dim3((unsigned)nunit, B), dim3(256), 0, stream, src, HW, nunit, (const int*)scratch, capacity, count, starts,
                      values);
   MMSA_CHECK_LAUNCH(name);
@@ -199,7 +129,7 @@ extern "C" int mmsa_run_lengths_i32(const int* src, int B, int H, int W, int ord
 // the constants this library was built with, for the caller's scratch (mmsa/evaluate.py compares them with its own): 0 = the pixels per scan unit, 1 = the
 // tile edge of the column order's transpose, 2 = the lanes of the scan workgroup, 3 = the unit counts one trip of the scan takes; -1 otherwise
 extern "C" int mmsa_run_lengths_block(int what) {
-  return what == 0 ? RUNS_BLOCK : what == 1 ? RUNS_TILE : what == 2 ? RUNS_SCAN_LANES : what == 3 ? RUNS_SCAN_LANES * RUNS_SCAN_PER_LANE : -1;
+  return what == 0 ? RUNS_BLOCK : what == 1 ? RUNS_TILE : what == 2 ? COMPACT_SCAN_LANES : what == 3 ? COMPACT_SCAN_TRIP : -1;
 }
 
 // n = B * H * W pixels, a lane each

@@ -6,14 +6,10 @@
 // index -- the raster order of their first pixel -- so the numbering is canonical.  count[b] = n_b; ids[b, y, x] = the number of the pixel's segment, -1 where
 // it is not listed; records[b, k] = ROOT, CLASS, AREA, X0, Y0, X1, Y1, SUM_X, SUM_Y, SUM_Q for k < min(n_b, capacity), zero from there on.
 //
-// The launches.  No workgroup waits for another and no loop spins on a value somebody else must write: the prefix sum is reduce-then-scan, three launches.
-//   count pass   a WORKGROUP per SEGTAB_BLOCK pixels of one image: flag(i) = root[i] == i && listed; the flags of a block are counted by ballots and the
-//                number goes to scratch[b, block].
-//   scan pass    ONE workgroup per image turns scratch[b, :] into its exclusive prefix sums, SEGTAB_SCAN_LANES block counts per trip with a carry: the loop
-//                is bounded by the block count.
-//   id pass      the count pass again, now with the block's offset: a flagged pixel's id = offset + the flags before it in its block (the ballots of the
-//                block, in pixel order).  It writes ids at the root pixels (-1 at a root that is not listed), the row's ROOT, CLASS, X0 = X1 = x, Y0 = Y1 = y
-//                for id < capacity, and the last block of an image writes count[b].
+// The launches.  The listed roots are numbered by the stream compaction of csrc/compact.h (count, scan, rank: three launches, blocks of SEGTAB_BLOCK pixels)
+// with flag(i) = root[i] == i && listed.
+//   id pass      the rank launch: it writes ids at the root pixels (-1 at a root that is not listed), the row's ROOT, CLASS, X0 = X1 = x, Y0 = Y1 = y for
+//                id < capacity, and the last block of an image writes count[b].
 //   accumulate   a lane per pixel: id = ids[root] (the root clamped into the plane), written to ids[i]; for 0 <= id < capacity the row takes 1, x, y, q and the
 //                min / max of x and the max of y by 64-bit atomics.  A road of half a frame is ONE row: a wave first reduces its lanes per distinct id in
 //                registers (the form of comp_wave_add), SEGTAB_WAVE_ROUNDS = 8 rounds at the most; what is pending after them goes lane by lane.  A wave holds
@@ -30,6 +26,7 @@
 #include "common.h"
 #include "cal_wave.h"       // cal_wave_sum: a wave's sum by data-parallel-primitive moves
 #include "comp_shared.h"
+#include "compact.h"
 #include "conf_bin.h"
 
 #ifndef SEGTAB_BLOCK
@@ -44,7 +41,6 @@
 #ifndef SEGTAB_ACC_THREADS
 #define SEGTAB_ACC_THREADS 256                // lanes per workgroup of the accumulate pass
 #endif
-#define SEGTAB_SCAN_LANES 256                 // block counts per trip of the scan pass
 #define SEGTAB_PER_LANE (SEGTAB_BLOCK / 256)
 #define SEGTAB_FIELDS 10
 #define SEGTAB_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
@@ -52,7 +48,7 @@ enum { ST_ROOT, ST_CLASS, ST_AREA, ST_X0, ST_Y0, ST_X1, ST_Y1, ST_SUM_X, ST_SUM_
 
 static_assert(SEGTAB_WAVE_ROUNDS >= 1 && SEGTAB_WAVE_ROUNDS <= 8, "a round's terms take eight lanes of the wave");
 static_assert(ST_X1 == 5 && ST_Y1 == 6 && ST_SUM_Y == ST_SUM_X + 1 && ST_SUM_Q == ST_SUM_X + 2, "the lane -> field rule of the accumulate pass");
-static_assert(SEGTAB_BLOCK % 256 == 0 && SEGTAB_PER_LANE >= 1 && SEGTAB_PER_LANE <= 64, "a block is 1..64 pixels per lane of 256 lanes");
+COMPACT_CHECK_BLOCK(SEGTAB_BLOCK);
 
 struct SegTabMaps {
   CompSrc s;
@@ -74,89 +70,34 @@ __device__ __forceinline__ int segtab_flag(const SegTabMaps& m, int b, long base
   return m.area == nullptr || m.area[base + i] >= m.min_area ? 1 : -1;
 }
 
-// grid (cdiv(H * W, SEGTAB_BLOCK), B).  Lane t owns the pixels block * SEGTAB_BLOCK + k * 256 + t: pixel order is (k, wave, lane).
+// grid (cdiv(H * W, SEGTAB_BLOCK), B): the count launch of csrc/compact.h
 __global__ __launch_bounds__(256) void segtab_count_kernel(SegTabMaps m, int nblk, int* __restrict__ scratch) {
-  __shared__ int ws[4];
   const long HW = (long)m.s.H * m.s.W, base = blockIdx.y * HW;
-  int n = 0;
-#pragma unroll
-  for (int k = 0; k < SEGTAB_PER_LANE; ++k) {
-    const long i = (long)blockIdx.x * SEGTAB_BLOCK + k * 256 + threadIdx.x;
-    int code;
-    n += (int)__popcll(__ballot(i < HW && segtab_flag(m, blockIdx.y, base, (int)i, code) > 0));      // the wave's flags of this k, in every lane
-  }
-  if ((threadIdx.x & 63u) == 0) ws[threadIdx.x >> 6] = n;
-  __syncthreads();
-  if (threadIdx.x == 0) scratch[(long)blockIdx.y * nblk + blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
+  int code;
+  compact_block_count<SEGTAB_PER_LANE>([&](int, long i) { return i < HW && segtab_flag(m, blockIdx.y, base, (int)i, code) > 0; }, nblk, scratch);
 }
 
-// grid B: scratch[b, :] -> its exclusive prefix sums, in place
-__global__ __launch_bounds__(SEGTAB_SCAN_LANES) void segtab_scan_kernel(int nblk, int* scratch) {
-  __shared__ int ws[SEGTAB_SCAN_LANES / 64];
-  int* s = scratch + (long)blockIdx.x * nblk;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int carry = 0;
-  for (int c = 0; c < nblk; c += SEGTAB_SCAN_LANES) {                          // bounded by the block count
-    const int j = c + (int)threadIdx.x, v = j < nblk ? s[j] : 0;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int up = __shfl_up(inc, d);
-      if (lane >= d) inc += up;
-    }
-    if (lane == 63) ws[w] = inc;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int k = 0; k < SEGTAB_SCAN_LANES / 64; ++k) {
-      before += k < w ? ws[k] : 0;
-      total += ws[k];
-    }
-    if (j < nblk) s[j] = carry + before + inc - v;
-    carry += total;
-    __syncthreads();                                                           // ws is written again in the next trip
-  }
-}
-
-// grid (cdiv(H * W, SEGTAB_BLOCK), B): the count pass again, with the offsets of the scan pass
+// grid (cdiv(H * W, SEGTAB_BLOCK), B): the rank launch, with the offsets of the scan
 __global__ __launch_bounds__(256) void segtab_ids_kernel(SegTabMaps m, int nblk, const int* __restrict__ scratch, int capacity, int* __restrict__ count,
                                                          int* __restrict__ ids, long long* __restrict__ records) {
-  __shared__ int cnt[SEGTAB_PER_LANE * 4 + 1];                                 // the flags per (k, wave), then their exclusive prefix sums and the total
   const long HW = (long)m.s.H * m.s.W, base = blockIdx.y * HW;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, b = blockIdx.y, W = m.s.W;
-  int flag[SEGTAB_PER_LANE], code[SEGTAB_PER_LANE], before[SEGTAB_PER_LANE];
+  const int b = blockIdx.y, W = m.s.W;
+  int flag[SEGTAB_PER_LANE], code[SEGTAB_PER_LANE], rank[SEGTAB_PER_LANE], total;
+  bool listed[SEGTAB_PER_LANE];
 #pragma unroll
   for (int k = 0; k < SEGTAB_PER_LANE; ++k) {
-    const long i = (long)blockIdx.x * SEGTAB_BLOCK + k * 256 + threadIdx.x;
+    const long i = compact_index<SEGTAB_PER_LANE>(k);
     code[k] = 0;
     flag[k] = i < HW ? segtab_flag(m, b, base, (int)i, code[k]) : 0;
-    const unsigned long long ms = __ballot(flag[k] > 0);
-    before[k] = (int)__popcll(ms & ((1ull << lane) - 1ull));                   // the flagged lanes of this wave and k below this one
-    if (lane == 0) cnt[k * 4 + w] = (int)__popcll(ms);
+    listed[k] = flag[k] > 0;
   }
-  __syncthreads();
-  if (w == 0) {                                                                // SEGTAB_PER_LANE * 4 <= 256 entries: lane by lane in trips of 64, with a carry
-    int carry = 0;
-    for (int c = 0; c < SEGTAB_PER_LANE * 4; c += 64) {
-      const int j = c + lane, v = j < SEGTAB_PER_LANE * 4 ? cnt[j] : 0;
-      int inc = v;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const int up = __shfl_up(inc, d);
-        if (lane >= d) inc += up;
-      }
-      if (j < SEGTAB_PER_LANE * 4) cnt[j] = carry + inc - v;
-      carry += __builtin_amdgcn_readlane(inc, 63);
-    }
-    if (lane == 0) cnt[SEGTAB_PER_LANE * 4] = carry;
-  }
-  __syncthreads();
+  compact_block_rank<SEGTAB_PER_LANE>(listed, rank, total);
   const int off = scratch[(long)b * nblk + blockIdx.x];
 #pragma unroll
   for (int k = 0; k < SEGTAB_PER_LANE; ++k) {
     if (flag[k] == 0) continue;
-    const long i = (long)blockIdx.x * SEGTAB_BLOCK + k * 256 + threadIdx.x;
-    const int id = flag[k] > 0 ? off + cnt[k * 4 + w] + before[k] : -1;
+    const long i = compact_index<SEGTAB_PER_LANE>(k);
+    const int id = listed[k] ? off + rank[k] : -1;
     ids[base + i] = id;
     if (id >= 0 && id < capacity) {
       long long* row = records + ((long)b * capacity + id) * SEGTAB_FIELDS;
@@ -167,7 +108,7 @@ __global__ __launch_bounds__(256) void segtab_ids_kernel(SegTabMaps m, int nblk,
       row[ST_Y0] = row[ST_Y1] = y;
     }
   }
-  if ((int)blockIdx.x == nblk - 1 && threadIdx.x == 0) count[b] = off + cnt[SEGTAB_PER_LANE * 4];
+  if ((int)blockIdx.x == nblk - 1 && threadIdx.x == 0) count[b] = off + total;
 }
 
 // one (wave, id) or one lane: n pixels with these sums and extremes join the row
@@ -308,7 +249,7 @@ extern "C" int mmsa_segment_table(const unsigned char* src, int B, int Hs, int W
   const int nblk = cdiv(HW, (long)SEGTAB_BLOCK);
   const SegTabMaps m = {{src, lut, ymap, xmap, Hs, Ws, H, W}, root, min_area > 1 ? area : nullptr, min_area, void_from};
   hipLaunchKernelGGL(segtab_count_kernel, dim3((unsigned)nblk, B), dim3(256), 0, stream, m, nblk, scratch);
-  hipLaunchKernelGGL(segtab_scan_kernel, dim3(B), dim3(SEGTAB_SCAN_LANES), 0, stream, nblk, scratch);
+  compact_scan(scratch, B, nblk, stream);
   hipLaunchKernelGGL(segtab_ids_kernel, dim3((unsigned)nblk, B), dim3(256), 0, stream, m, nblk, (const int*)scratch, capacity, count, ids,
                      (long long*)records);
   hipLaunchKernelGGL(segtab_accumulate_kernel, dim3((unsigned)cdiv(HW, (long)SEGTAB_ACC_THREADS), B), dim3(SEGTAB_ACC_THREADS), 0, stream, root, values, H, W, capacity, ids,

@@ -2418,14 +2418,37 @@ class PanopticEvaluator(_SlotOwner):
 # lists the components of the other codes (C, and 255 on the label side).  The listed segments of an image are numbered 0 .. n_b - 1 in ascending order of
 # their root index -- the raster order of their first pixel -- so the numbering is canonical.  count[b] = n_b; ids[b, y, x] = the number of the pixel's segment
 # (-1: not listed); records[b, k] = ROOT, CLASS, AREA, X0, Y0, X1, Y1, SUM_X, SUM_Y, SUM_Q for k < min(n_b, capacity), zero rows behind them.
-SEGTAB_BLOCK = 2048                # csrc/segtable.hip SEGTAB_BLOCK: the pixels per workgroup of the prefix sum's count and id passes (one scratch word each)
-SEGTAB_SCAN_LANES = 256            # csrc/segtable.hip SEGTAB_SCAN_LANES: the block counts one trip of the scan pass takes
+SEGTAB_BLOCK = 2048                # csrc/segtable.hip SEGTAB_BLOCK: the pixels per block of the compaction (one scratch word each)
+SCAN_LANES = 256                   # csrc/compact.h COMPACT_SCAN_LANES: the lanes of the compaction's scan workgroup (segment table and run tables alike)
+SCAN_TRIP = 1024                   # csrc/compact.h COMPACT_SCAN_TRIP: the block counts one trip of the scan takes
 SEGMENT_FIELDS = ("ROOT", "CLASS", "AREA", "X0", "Y0", "X1", "Y1", "SUM_X", "SUM_Y", "SUM_Q")
 ROOT, CLASS, AREA, X0, Y0, X1, Y1, SUM_X, SUM_Y, SUM_Q = range(10)
 SCORE_ONE = CONF_ONE               # the fixed-point unit of a record's score sum: SUM_Q = sum of floor(clamp(value) * 2^24)
 MIN_SEGMENT_CAPACITY = 1024
 SEGMENT_DTYPE = np.dtype([("image", np.int64), ("id", np.int64), ("root", np.int64), ("category", np.int64), ("area", np.int64), ("bbox", np.int64, (4,)),
                           ("centroid", np.float64, (2,)), ("score", np.float64)])
+
+
+_library_checked = set()
+
+
+def _check_library(kind, **getters):
+    """Once per process and table kind: the named constants of this module are the loaded library's (a variant build, MMSA_LIB, would get a wrong scratch)."""
+    if kind not in _library_checked:
+        for name, get in getters.items():
+            if get() != globals()[name]:
+                raise RuntimeError(f"mmsa.evaluate: the library's {kind} constant {name} is {get()}, mmsa.evaluate.{name} is {globals()[name]}")
+        _library_checked.add(kind)
+
+
+def _check_rows(who, B, capacity, rows):
+    if B * capacity >= 1 << 31:
+        raise RuntimeError(f"{who}: {B} images of {capacity} {rows}; a row is indexed in 32 bits (B * capacity < 2^31)")
+
+
+def _overflow_error(who, image, n, rows, things, lost, remedy):
+    return RuntimeError(f"{who}: image {image} has {n} {things} and the table {rows} rows: {lost} {n - rows} were dropped; {remedy} with a larger capacity= "
+                        f"(capacity=H * W can never overflow)")
 
 
 def default_segment_capacity(H, W):
@@ -2458,8 +2481,7 @@ def segment_records_of(records, count, scored=True, image=0):
     if n < 0:
         raise ValueError(f"mmsa.evaluate: count = {n}")
     if n > r.shape[0]:
-        raise RuntimeError(f"mmsa.evaluate: image {image} has {n} listed segments and the table {r.shape[0]} rows: the records of the last {n - r.shape[0]} were "
-                           f"dropped; fill a table with a larger capacity= (capacity=H * W can never overflow)")
+        raise _overflow_error("mmsa.evaluate", image, n, r.shape[0], "listed segments", "the records of the last", "fill a table")
     r = r[:n].astype(np.int64, copy=False)
     out = np.zeros(n, dtype=SEGMENT_DTYPE)
     out["image"], out["id"], out["root"], out["category"], out["area"] = image, np.arange(n), r[:, ROOT], r[:, CLASS], r[:, AREA]
@@ -2519,11 +2541,8 @@ class SegmentTable:
                 raise RuntimeError(f"mmsa.SegmentTable: the buffers of a {B} x {H} x {W} batch cannot be allocated during a graph capture: run one update() of this "
                                    "shape before capturing")
             capacity = default_segment_capacity(H, W) if self._capacity is None else self._capacity
-            if lib.raw.mmsa_segment_table_block() != SEGTAB_BLOCK:      # a variant build (MMSA_LIB) with another block: the scratch would be sized wrong
-                raise RuntimeError(f"mmsa.SegmentTable: the library counts {lib.raw.mmsa_segment_table_block()} pixels per scratch word, mmsa.evaluate.SEGTAB_BLOCK "
-                                   f"is {SEGTAB_BLOCK}")
-            if B * capacity >= 1 << 31:
-                raise RuntimeError(f"mmsa.SegmentTable: {B} images of {capacity} rows; a row is indexed in 32 bits (B * capacity < 2^31)")
+            _check_library("segment table", SEGTAB_BLOCK=lib.raw.mmsa_segment_table_block)
+            _check_rows("mmsa.SegmentTable", B, capacity, "rows")
             blocks = -(-H * W // SEGTAB_BLOCK)
             m = self._maps[key] = dict(count=torch.zeros(B, dtype=torch.int32, device=device),
                                        records=torch.zeros(B, capacity, len(SEGMENT_FIELDS), dtype=torch.int64, device=device),
@@ -2597,8 +2616,7 @@ class SegmentTable:
         cap = int(self.records.shape[1])
         for i in range(B):
             if count[i] > cap:
-                raise RuntimeError(f"mmsa.SegmentTable: image {i} has {int(count[i])} listed segments and the table {cap} rows: the records of the last "
-                                   f"{int(count[i]) - cap} were dropped; make the SegmentTable with a larger capacity= (capacity=H * W can never overflow)")
+                raise _overflow_error("mmsa.SegmentTable", i, int(count[i]), cap, "listed segments", "the records of the last", "make the SegmentTable")
         records = self.records.cpu().numpy()
         images = range(B) if b is None else [int(b)]
         parts = [segment_records_of(records[i], count[i], self.scored, i) for i in images]
@@ -2705,8 +2723,6 @@ def select_segments(pred, table, keep, fill=255, out=None):
 # not written.  length[j] = (starts[j + 1] or H * W) - starts[j].
 RUNS_BLOCK = 2048                  # csrc/runs.hip RUNS_BLOCK: the flat indices per scan unit (one scratch word each)
 RUNS_TILE = 64                     # csrc/runs.hip RUNS_TILE: the tile edge of the transpose the column order starts with
-RUNS_SCAN_LANES = 256              # csrc/runs.hip RUNS_SCAN_LANES: the lanes of the scan workgroup
-RUNS_SCAN_TRIP = 1024              # the unit counts one trip of the scan pass takes (RUNS_SCAN_LANES * RUNS_SCAN_PER_LANE)
 RUN_ORDERS = ("row", "column")     # the library's order 0, 1
 MIN_RUN_CAPACITY = 4096
 
@@ -2733,17 +2749,11 @@ def run_units(H, W):
     return -(-int(H) * int(W) // RUNS_BLOCK)
 
 
-_run_constants_checked = False
-
-
 def run_scratch_words(B, H, W, order, itemsize=4):
     """The int32 words of a launch's scratch: the unit counts of every image, and for "column" the transposed map (of `itemsize` bytes per pixel) behind them."""
-    global _run_constants_checked
-    if not _run_constants_checked:      # once per process: a variant build (MMSA_LIB) with other constants would get a scratch of the wrong size
-        for what, want in ((0, RUNS_BLOCK), (1, RUNS_TILE), (2, RUNS_SCAN_LANES), (3, RUNS_SCAN_TRIP)):
-            if lib.raw.mmsa_run_lengths_block(what) != want:
-                raise RuntimeError(f"mmsa.evaluate: the library's run-length constant {what} is {lib.raw.mmsa_run_lengths_block(what)}, mmsa.evaluate has {want}")
-        _run_constants_checked = True
+    if "run-length" not in _library_checked:      # every run_lengths() call comes through here
+        block = lib.raw.mmsa_run_lengths_block
+        _check_library("run-length", RUNS_BLOCK=lambda: block(0), RUNS_TILE=lambda: block(1), SCAN_LANES=lambda: block(2), SCAN_TRIP=lambda: block(3))
     return B * run_units(H, W) + (-(-B * int(H) * int(W) * itemsize // 4) if check_run_order(order) == "column" else 0)
 
 
@@ -2762,8 +2772,7 @@ class RunTable:
     def empty(cls, B, H, W, order, capacity, device):
         """The buffers of a batch of B maps of H x W pixels, uint8 or int32: nothing a later run_lengths(..., table=) of this shape has to allocate."""
         capacity = check_run_capacity(capacity, "mmsa.RunTable")
-        if B * capacity >= 1 << 31:
-            raise RuntimeError(f"mmsa.RunTable: {B} images of {capacity} runs; a row is indexed in 32 bits (B * capacity < 2^31)")
+        _check_rows("mmsa.RunTable", B, capacity, "runs")
         return cls(torch.zeros(B, dtype=torch.int32, device=device), torch.empty(B, capacity, dtype=torch.int32, device=device),
                    torch.empty(B, capacity, dtype=torch.int32, device=device), order, (B, H, W), capacity,
                    torch.empty(run_scratch_words(B, H, W, order), dtype=torch.int32, device=device))
@@ -2785,8 +2794,7 @@ class RunTable:
             raise ValueError(f"mmsa.RunTable: b = {b!r}; an image index 0..{B - 1} is expected")
         n = int(self.count[int(b)].item())
         if n > self.capacity:
-            raise RuntimeError(f"mmsa.RunTable: image {int(b)} has {n} runs and the table {self.capacity} rows: the last {n - self.capacity} were dropped; fill a "
-                               f"table with a larger capacity= (capacity=H * W can never overflow)")
+            raise _overflow_error("mmsa.RunTable", int(b), n, self.capacity, "runs", "the last", "fill a table")
         starts = self.starts[int(b), :n].cpu().numpy().astype(np.int64)
         values = self.values[int(b), :n].cpu().numpy().astype(np.int64)
         return starts, np.diff(starts, append=H * W), values

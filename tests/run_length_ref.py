@@ -17,8 +17,8 @@ C = SR.C
 ORDERS = ("row", "column")
 BLOCK = 2048                       # mmsa.evaluate.RUNS_BLOCK (the flat indices per scan unit), held to it by tests/test_run_length_cpu.py
 TILE = 64                          # mmsa.evaluate.RUNS_TILE (the tile edge of the column order's transpose)
-SCAN_LANES = 256                   # mmsa.evaluate.RUNS_SCAN_LANES
-SCAN_TRIP = 1024                   # mmsa.evaluate.RUNS_SCAN_TRIP
+SCAN_LANES = 256                   # mmsa.evaluate.SCAN_LANES (the lanes of the compaction's scan workgroup)
+SCAN_TRIP = 1024                   # mmsa.evaluate.SCAN_TRIP (the unit counts one trip of the scan takes)
 
 
 def default_capacity(H, W):

@@ -142,7 +142,8 @@ def image_values(kind, H, W):
 
 SHAPES = [(1, 1), (1, 257), (257, 1), (31, 63), (67, 131), (130, 200)]
 BLOCK = 2048                       # mmsa.evaluate.SEGTAB_BLOCK, held to it by tests/test_segment_table_cpu.py
-LARGE = (600, 900)                 # 264 scan blocks of 2048 pixels: more than the 256 lanes of the scan workgroup
+LARGE = (600, 900)                 # 264 scan blocks of 2048 pixels: more than the 256 lanes of the scan workgroup (mmsa.evaluate.SCAN_LANES)
+LARGER = (1400, 1502)              # 1027 scan blocks: more than the 1024 counts of one trip of the scan (mmsa.evaluate.SCAN_TRIP), so the carry is used
 
 # every input of tests/test_segment_table_gpu.py: (kind, H, W, connectivity, min_area, void, capacity (None: the default), overflows).  The CPU file predicts
 # n_b of each against its capacity: exactly the cases marked so overflow.

@@ -178,7 +178,7 @@ def test_exports_and_constants():
     assert mmsa.lib.SIGNATURES["mmsa_run_lengths_u8"] == mmsa.lib.SIGNATURES["mmsa_run_lengths_i32"] and len(mmsa.lib.SIGNATURES["mmsa_run_lengths_u8"]) == 11
     assert len(mmsa.lib.SIGNATURES["mmsa_run_decode_i32"]) == 11 and mmsa.lib.version() == 114
     block = mmsa.lib.raw.mmsa_run_lengths_block
-    assert [block(k) for k in range(5)] == [E.RUNS_BLOCK, E.RUNS_TILE, E.RUNS_SCAN_LANES, E.RUNS_SCAN_TRIP, -1] == [RR.BLOCK, RR.TILE, RR.SCAN_LANES, RR.SCAN_TRIP, -1]
+    assert [block(k) for k in range(5)] == [E.RUNS_BLOCK, E.RUNS_TILE, E.SCAN_LANES, E.SCAN_TRIP, -1] == [RR.BLOCK, RR.TILE, RR.SCAN_LANES, RR.SCAN_TRIP, -1]
     assert E.default_run_capacity(31, 63) == 4096 == RR.default_capacity(31, 63) and E.default_run_capacity(1080, 1920) == 259200 == RR.default_capacity(1080, 1920)
     for H, W in RR.SHAPES + [RR.LARGE]:
         assert E.run_units(H, W) == RR.units(H, W) >= 1 and E.run_scratch_words(3, H, W, "row") == 3 * RR.units(H, W)

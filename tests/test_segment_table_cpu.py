@@ -140,7 +140,9 @@ def test_exports_and_entries():
     import mmsa.inference as inf
     for name in ("SegmentTable", "segment_table", "select_segments", "segment_records_of"):
         assert getattr(mmsa, name) is getattr(mmsa.evaluate, name) and name in mmsa.__all__
-    assert mmsa.evaluate.SEGTAB_BLOCK == SR.BLOCK and SR.LARGE[0] * SR.LARGE[1] > SR.BLOCK * mmsa.evaluate.SEGTAB_SCAN_LANES
+    assert mmsa.evaluate.SEGTAB_BLOCK == SR.BLOCK and SR.LARGE[0] * SR.LARGE[1] > SR.BLOCK * mmsa.evaluate.SCAN_LANES
+    assert SR.LARGER[0] * SR.LARGER[1] > SR.BLOCK * mmsa.evaluate.SCAN_TRIP and mmsa.evaluate.SCAN_TRIP > mmsa.evaluate.SCAN_LANES
+    assert [mmsa.lib.raw.mmsa_run_lengths_block(k) for k in (2, 3)] == [mmsa.evaluate.SCAN_LANES, mmsa.evaluate.SCAN_TRIP]      # the scan is the one of both tables
     for name in ("mmsa_segment_table", "mmsa_segment_table_block", "mmsa_select_segments_u8"):
         assert name in mmsa.lib.SIGNATURES and hasattr(mmsa.lib.raw, name)
     assert len(mmsa.lib.SIGNATURES["mmsa_segment_table"]) == 20 and len(mmsa.lib.SIGNATURES["mmsa_select_segments_u8"]) == 10 and mmsa.lib.raw.mmsa_segment_table_block() == SR.BLOCK and mmsa.lib.version() == 114

@@ -1,6 +1,6 @@
 """The segment table on the GPU (csrc/segtable.hip): count, ids and records against the numpy restatement of tests/segment_table_ref.py, byte for byte.
 Everything is integers: every comparison is equality.  The shapes are the smallest at which each mechanism can fail: one pixel, one row, one column, maps of
-one and of several scan blocks, the edges of a scan block, more scan blocks than the scan workgroup has lanes; one segment that takes every add, 64 segments
+one and of several scan blocks, the edges of a scan block, more scan blocks than the scan workgroup has lanes and than one trip of the scan takes; one segment that takes every add, 64 segments
 in a wave; the listing rules, the label side, the overflow; then the identities that tie the records to the passes that were there before, and the entries on
 the tiny model.  Every input is listed in segment_table_ref.CASES, where tests/test_segment_table_cpu.py predicts its number of segments."""
 import numpy as np
@@ -102,12 +102,9 @@ def test_the_edges_of_a_scan_block(d):
     _same(_fill([_case("noise", 1, W)], values, capacity=W), _want(["noise"], 1, W, values=values))
 
 
-def test_more_scan_blocks_than_the_scan_workgroup_has_lanes():
+def _large_map_equals_the_restatement_on_the_gpu_roots(H, W, n_want):
     """The roots come from mmsa.components and the restatement is applied to THOSE roots: the test judges the table, not the labelling a second time."""
     import mmsa
-    from mmsa.evaluate import SEGTAB_BLOCK, SEGTAB_SCAN_LANES
-    H, W = SR.LARGE
-    assert -(-H * W // SEGTAB_BLOCK) > SEGTAB_SCAN_LANES
     m = SR.image("noise", H, W)
     values = SR.image_values("plain", H, W)[None]
     d = _dev(m[None])
@@ -115,7 +112,26 @@ def test_more_scan_blocks_than_the_scan_workgroup_has_lanes():
     st = mmsa.segment_table(d, num_classes=C, values=_dev(values), root=root, capacity=H * W)
     assert st.root is root
     n, ids, rec = SR.table(m, _host(root)[0], values=values[0])
-    assert n == 457508 and _host(st.count).tolist() == [n] and np.array_equal(_host(st.ids)[0], ids) and np.array_equal(_host(st.records)[0], rec)
+    assert n == n_want and _host(st.count).tolist() == [n] and np.array_equal(_host(st.ids)[0], ids) and np.array_equal(_host(st.records)[0], rec)
+    return ids
+
+
+def test_more_scan_blocks_than_the_scan_workgroup_has_lanes():
+    from mmsa.evaluate import SEGTAB_BLOCK, SCAN_LANES
+    H, W = SR.LARGE
+    assert -(-H * W // SEGTAB_BLOCK) > SCAN_LANES
+    _large_map_equals_the_restatement_on_the_gpu_roots(H, W, 457508)
+
+
+def test_more_scan_blocks_than_one_trip_of_the_scan_takes():
+    """1027 blocks: the scan's second trip starts from the carry of the first, and the last block, behind it, writes the count."""
+    import mmsa
+    H, W = SR.LARGER
+    block = mmsa.lib.raw.mmsa_run_lengths_block                                # the scan of both tables: lanes and counts per trip from the library
+    blocks = -(-H * W // mmsa.lib.raw.mmsa_segment_table_block())
+    assert blocks > block(3) > block(2)
+    ids = _large_map_equals_the_restatement_on_the_gpu_roots(H, W, 1780301)
+    assert ids.ravel()[(blocks - 1) * SR.BLOCK:].max() > ids.ravel()[:block(3) * SR.BLOCK].max()      # listed roots in the last block, numbered past the first trip's
 
 
 def test_three_images_in_a_batch_then_a_batch_of_two():

@@ -70,7 +70,7 @@ def main():
         return (F.interpolate(coarse, size=(256, 256), mode="bilinear") + 0.05 * torch.randn(n, C, 256, 256, generator=g)).to(dev)
 
     say(f"device {torch.cuda.get_device_name(0)}; reps {a.reps}, {a.inner} calls per timing; times in microseconds per call; {C} classes; scan block "
-        f"{E.RUNS_BLOCK} pixels, transpose tile {E.RUNS_TILE} x {E.RUNS_TILE}, {E.RUNS_SCAN_TRIP} unit counts per scan trip" + (f"; {a.tag}" if a.tag else ""))
+        f"{E.RUNS_BLOCK} pixels, transpose tile {E.RUNS_TILE} x {E.RUNS_TILE}, {E.SCAN_TRIP} unit counts per scan trip" + (f"; {a.tag}" if a.tag else ""))
     g = torch.Generator().manual_seed(7)
     lp = LabelPrep(C)
     for name, plan in (("two 1024 x 1024 maps", inf.MapPlan.whole(2, 1024, 1024)),
