@@ -711,6 +711,20 @@ int mmsa_run_lengths_block(int what);
 int mmsa_run_decode_i32(const int* count, const int* starts, const int* values, int B, int H, int W, int order, int capacity, int fill, int* out,
                         mmsa_stream_t stream);
 
+/* --- nearest-label fill (csrc/fill.hip): the holes of a byte map take the value of the nearest kept pixel of their image.  src uint8 [B, H, W] contiguous;
+ *   role: DEVICE uint8 [256], the role of every byte: 0 = source (keeps its value and offers it to holes), 1 = hole (is to be filled), 2 = inert (keeps its
+ *   value and offers nothing; it blocks nothing: the fill is Euclidean, not geodesic).  none_byte: any byte whose role is 1 (the caller's to keep: the row pass
+ *   marks "no source within 255 columns" with it, which no source's value can be).  1 <= cap <= 255.
+ *     For a hole p = (py, px): among the source pixels q of the same image with d2 = (qy - py)^2 + (qx - px)^2 <= cap^2, the one with the smallest key
+ *     (d2, qy, qx), compared lexicographically -- nearest first, then topmost, then leftmost: out[p] = src[q].  No such q: out[p] = src[p].  Every pixel that
+ *     is not a hole: out[p] = src[p].  d2 (uint16 [B, H, W], or NULL: not written) = 0 at every pixel that is not a hole, the taken d2 (1..65025) at a filled
+ *     hole, 65535 at a hole that stays.  Images of a batch never see each other.  Integers only: the same bytes on every run.
+ *   out may be src (in place).  scratch: uint16 [B, H, W] of the caller's, written and read by the two launches of the call (a row pass and a column pass, as
+ *   mmsa_boundary_distance_u8's), never allocated here; scratch, d2 and the maps are separate buffers.  H * W < 2^31.  Every loop is bounded by the row
+ *   length, by cap or by the image height.  A limit broken or a null pointer: MMSA_ERR_ARG with a message, before any launch. --- */
+int mmsa_fill_nearest_u8(const unsigned char* src, int B, int H, int W, const unsigned char* role, int none_byte, int cap, unsigned short* scratch,
+                         unsigned char* out, unsigned short* d2, mmsa_stream_t stream);
+
 /* --- the picture of a prediction (segmentation/mmseg_custom/apis/test_bs.py:257-349, the `--show` / `--show-dir` output): `tensor2imgs` (test_bs.py:18-63) on
  *     planes 0..2 of the input tensor -> the crop `img[:h, :w]` (test_bs.py:275-276) -> `show_result` (tools/color_gt_according_palette.py:23-81:
  *     color_seg[seg == label] = color, channels reversed, img * (1 - opacity) + color_seg * opacity, .astype(uint8)), in one pass.

@@ -36,7 +36,9 @@
  *      class map with chosen segments painted over).
  *      Still 114, for the same reason: new entries mmsa_run_lengths_u8 / mmsa_run_lengths_i32 / mmsa_run_lengths_block / mmsa_run_decode_i32 (the runs of a
  *      class map or an ids map in row-major or column-major order -- starts and values in ascending order by a device-wide prefix sum over the run heads --
- *      and the map of such a table). */
+ *      and the map of such a table).
+ *      Still 114, for the same reason: new entry mmsa_fill_nearest_u8 (the holes of a byte map filled with the value of the nearest source pixel within a cap
+ *      of up to 255 pixels, ties to the topmost and then the leftmost, and the squared distance taken). */
 #ifndef MMSA_VERSION_H
 #define MMSA_VERSION_H
 #define MMSA_ABI_VERSION 114

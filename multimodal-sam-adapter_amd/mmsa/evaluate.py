@@ -59,7 +59,11 @@ Panoptic quality asks which prediction segment IS which label segment: `segment_
 segment, prediction segment) pair that shares a correct pixel (mmsa_segment_pairs, csrc/pairs.hip; `PairTable`, the compact pair list), `panoptic_counts` /
 `PanopticEvaluator` match the pairs by IoU > 1/2 -- unique, tested in integers -- and reduce them to int64 [C, 24, 4] per slot (mmsa_eval_panoptic): TP, FP, FN
 and the fixed-point IoU sum by class and size bucket, from which `panoptic_quality_of` forms PQ = SQ * RQ per class and `panoptic_summary_of` their means in
-float64 on the host."""
+float64 on the host.
+
+`suppress_small`, `select_segments` and `abstain` paint what they remove with one byte.  `fill_nearest` hands such a map back full: every hole takes the value
+of the nearest kept pixel of its image within a cap of up to 255 pixels, ties to the topmost and then the leftmost (mmsa_fill_nearest_u8, csrc/fill.hip: the
+two launches of `boundary_distance` with a value carried along); `suppress_small(…, nearest=cap)` and `select_segments(…, nearest=cap)` end with it."""
 import ctypes
 import math
 import warnings
@@ -762,7 +766,8 @@ def abstain(pred, conf, bins, min_bin=None, out=None, threshold=None):
     """The class map thresholded by confidence (one launch, mmsa_abstain_u8) -> uint8 [B, H, W]: pred where the confidence's bin (of `bins`, as in
     `selective` / `calibration`) is >= `min_bin`, 255 elsewhere.  0 <= min_bin <= bins: 0 copies, `bins` abstains everywhere.  `threshold=` in place
     of min_bin: a confidence in [0, 1] that is a bin edge (`threshold_bin`); any other is refused, since the per-bin counts cannot describe its map.
-    `out`: the uint8 tensor to write, pred's shape; it may be pred itself (in place); a new tensor by default."""
+    `out`: the uint8 tensor to write, pred's shape; it may be pred itself (in place); a new tensor by default.
+    `fill_nearest(out, hole=255)` then gives the abstained pixels the class of the nearest kept pixel."""
     pred = _check_pred(pred)
     conf = _check_confmap(conf, pred)
     K = _check_bins(bins)
@@ -1865,17 +1870,21 @@ def component_areas(root, out=None):
 
 
 @torch.no_grad()
-def suppress_small(pred, min_area, *, num_classes, connectivity=8, fill=255, out=None, root=None, area=None):
+def suppress_small(pred, min_area, *, num_classes, connectivity=8, fill=255, out=None, root=None, area=None, nearest=None):
     """The class map without its small blobs -> uint8 [B, H, W]: a pixel whose component (of the codes min(pred, C), at `connectivity`) has fewer than `min_area`
     pixels becomes `fill`, every other pixel is unchanged; min_area=1 is the identity.  The component launches, the area launch and one pointwise launch
     (mmsa_suppress_small_u8).  `out=` may be `pred` itself (in place); `root=` / `area=` (int32 [B, H, W] each) take the caller's planes -- they hold the root
-    map and the areas afterwards -- so that a repeated call allocates nothing; without them buffers cached per device and stream are used."""
+    map and the areas afterwards -- so that a repeated call allocates nothing; without them buffers cached per device and stream are used.
+    `nearest=cap` (None: the launches above alone): the removed blobs then take the class of what surrounds them, `fill_nearest(out, hole=fill, cap=nearest,
+    out=out)` -- two more launches.  EVERY pixel that holds `fill` is filled, also one that held it before the call: a caller who wants 255 kept as void
+    paints with another byte (fill=254).  `fill` must be no class: fill < num_classes with nearest= is a ValueError."""
     connectivity = check_connectivity(connectivity)
     if not _is_int(min_area, 1, (1 << 31) - 1):
         raise ValueError(f"mmsa.evaluate: min_area = {min_area!r}; an integer pixel count >= 1 is expected (1: nothing is removed)")
     if not _is_int(fill, 0, 255):
         raise ValueError(f"mmsa.evaluate: fill = {fill!r}; a byte 0..255 is expected")
     code_lut(num_classes)
+    nearest = _check_nearest(nearest, fill, num_classes, "mmsa.evaluate: suppress_small")
     pred = _check_map(pred, "pred", torch.uint8, "a uint8 class map", shape_only=True)
     if pred.numel() == 0:
         raise RuntimeError(f"mmsa.evaluate: an empty map {tuple(pred.shape)}")
@@ -1899,6 +1908,8 @@ def suppress_small(pred, min_area, *, num_classes, connectivity=8, fill=255, out
         components(pred, num_classes=num_classes, connectivity=connectivity, out=root)
         component_areas(root, out=area)
         lib.call("mmsa_suppress_small_u8", pred.data_ptr(), root.data_ptr(), area.data_ptr(), B, H, W, int(min_area), int(fill), out.data_ptr(), ops._stream())
+        if nearest is not None:
+            fill_nearest(out, hole=int(fill), cap=nearest, out=out)
     return out
 
 
@@ -2691,16 +2702,20 @@ def segment_table(map, *, num_classes=None, labels_prep=None, values=None, root=
 
 
 @torch.no_grad()
-def select_segments(pred, table, keep, fill=255, out=None):
+def select_segments(pred, table, keep, fill=255, out=None, nearest=None):
     """The class map with the segments that `keep` drops painted over (one pointwise launch, mmsa_select_segments_u8) -> uint8 [B, H, W]: `fill` where the
     pixel's id is a row of the table and keep[b, id] == 0, `pred` elsewhere -- a pixel whose segment is not listed (id -1) or has no row (id >= capacity) is
     unchanged.  `table` = a filled SegmentTable of this shape, `keep` = uint8 [B, capacity] on the device (`table.keep(...)`, or any mask made from
-    `table.records`); `out=` may be `pred` itself.  The instance-level sibling of `abstain`."""
+    `table.records`); `out=` may be `pred` itself.  The instance-level sibling of `abstain`.
+    `nearest=cap` (None: the launch above alone): the painted pixels then take the class of the nearest kept pixel within `cap` pixels,
+    `fill_nearest(out, hole=fill, cap=nearest, out=out)` -- two more launches.  EVERY pixel that holds `fill` is filled, also one that held it before the call:
+    a caller who wants 255 kept as void paints with another byte (fill=254).  `fill` must be no class of the table (ValueError)."""
     if not isinstance(table, SegmentTable):
         raise RuntimeError(f"mmsa.evaluate: table takes an mmsa.evaluate.SegmentTable, got {type(table).__name__}")
-    table._filled()
     if not _is_int(fill, 0, 255):
         raise ValueError(f"mmsa.evaluate: fill = {fill!r}; a byte 0..255 is expected")
+    nearest = _check_nearest(nearest, fill, table.num_classes, "mmsa.evaluate: select_segments")
+    table._filled()
     pred = _check_map(pred, "pred", torch.uint8, "a uint8 class map", like=table.ids)
     B, H, W = (int(v) for v in pred.shape)
     capacity = int(table.records.shape[1])
@@ -2713,7 +2728,108 @@ def select_segments(pred, table, keep, fill=255, out=None):
         else:
             _check_map(out, "out", torch.uint8, "a uint8 class map", like=pred)
         lib.call("mmsa_select_segments_u8", pred.data_ptr(), table.ids.data_ptr(), keep.data_ptr(), B, H, W, capacity, int(fill), out.data_ptr(), ops._stream())
+        if nearest is not None:
+            fill_nearest(out, hole=int(fill), cap=nearest, out=out)
     return out
+
+
+# ---- nearest-label fill: the holes of a map take the value of the nearest kept pixel (csrc/fill.hip) ----
+FILL_SOURCE, FILL_HOLE, FILL_INERT = 0, 1, 2      # the roles of csrc/fill.hip's table
+FILL_FAR = 65535                   # csrc/fill.hip FILL_FAR: the d2 of a hole that stays
+_FILL_ROLES = {}                   # (roles, device) -> the device role table of a fill launch
+
+
+def _fill_bytes(v, name):
+    """A byte or a list of bytes -> the sorted tuple of them."""
+    vs = (v,) if _is_int(v, 0, 255) else v
+    if isinstance(vs, (str, bytes)) or not hasattr(vs, "__iter__"):
+        raise ValueError(f"mmsa.evaluate: {name} = {v!r}; a byte 0..255 or a list of bytes is expected")
+    vs = tuple(vs)
+    if not all(_is_int(b, 0, 255) for b in vs):
+        raise ValueError(f"mmsa.evaluate: {name} = {v!r}; a byte 0..255 or a list of bytes is expected")
+    return tuple(sorted(set(int(b) for b in vs)))
+
+
+def fill_roles(hole=255, inert=()):
+    """The 256-byte role table of a fill launch, uint8 numpy [256]: 1 at the bytes of `hole` (to be filled), 2 at the bytes of `inert` (kept, offering nothing),
+    0 at every other byte (a source: kept, and offered to the holes).  `hole` and `inert` are a byte or a list of bytes, disjoint, `hole` not empty."""
+    holes, inerts = _fill_bytes(hole, "hole"), _fill_bytes(inert, "inert")
+    if not holes:
+        raise ValueError("mmsa.evaluate: hole is empty; at least one byte to fill is expected")
+    both = sorted(set(holes) & set(inerts))
+    if both:
+        raise ValueError(f"mmsa.evaluate: hole and inert share the bytes {both}; a byte is filled or kept")
+    roles = np.zeros(256, dtype=np.uint8)
+    roles[list(holes)] = FILL_HOLE
+    roles[list(inerts)] = FILL_INERT
+    return roles
+
+
+def _fill_roles_on(device, roles):
+    key = (roles.tobytes(), torch.device(device))
+    t = _FILL_ROLES.get(key)
+    if t is None:
+        if _capturing(key[1]):
+            raise RuntimeError("mmsa.evaluate: the role table of the fill launch is not on the device yet and cannot be uploaded during a graph capture: run one "
+                               "call before capturing")
+        t = _FILL_ROLES[key] = torch.from_numpy(roles).to(key[1])
+    return t
+
+
+@torch.no_grad()
+def fill_nearest(map, hole=255, inert=(), cap=32, out=None, d2=None, scratch=None):
+    """The map with its holes filled from the nearest kept pixel (two launches, mmsa_fill_nearest_u8) -> uint8 [B, H, W] on the device.  A pixel whose byte is
+    in `hole` takes the value of the nearest SOURCE pixel of its image within `cap` pixels (Euclidean, 1 <= cap <= 255), of equally near ones the topmost, then
+    the leftmost; a hole with no source that near stays.  Every byte in neither list is a source; the bytes of `inert` (e.g. the 255 of an ignored region when
+    the holes were painted with another byte) are kept and offer nothing -- they do not block either: the fill is Euclidean, not geodesic.  `hole` and `inert`
+    are a byte or a list of bytes, disjoint.  Integers only: the same bytes on every run.
+    `out=` (uint8, the map's shape) may be `map` itself (in place); `d2=` (uint16, the map's shape) receives 0 at every pixel that is no hole, the squared
+    distance taken (1..cap^2) at a filled hole and FILL_FAR (65535) at a hole that stays; `scratch=` (a uint16 tensor of at least B * H * W elements, the row
+    pass's plane, not `d2`) makes the call allocation-free -- without it the buffer of `boundary_distance`, cached per device and stream, is used."""
+    roles = fill_roles(hole, inert)
+    cap = check_distance_cap(cap)
+    src = _check_map(map, "map", torch.uint8, "a uint8 class map", shape_only=True)
+    B, H, W = (int(v) for v in src.shape)
+    if B * H * W == 0:
+        raise RuntimeError(f"mmsa.evaluate: an empty map {tuple(src.shape)}")
+    if out is not None:
+        _check_map(out, "out", torch.uint8, "a uint8 class map", like=src, shape_only=True)
+    if d2 is not None:
+        _check_map(d2, "d2", torch.uint16, "a uint16 distance map", like=src, shape_only=True)
+    if scratch is not None:
+        if not isinstance(scratch, torch.Tensor) or scratch.dtype != torch.uint16 or scratch.numel() < B * H * W or not scratch.is_contiguous():
+            raise RuntimeError(f"mmsa.evaluate: scratch must be a contiguous uint16 tensor of at least {B * H * W} elements")
+        if scratch is d2:
+            raise RuntimeError("mmsa.evaluate: scratch and d2 are two planes")
+    _check_map(src, "map", torch.uint8, "a uint8 class map")
+    with torch.cuda.device(src.device):
+        if out is None:
+            out = torch.empty_like(src)
+        else:
+            _check_map(out, "out", torch.uint8, "a uint8 class map", like=src)
+        if d2 is not None:
+            _check_map(d2, "d2", torch.uint16, "a uint16 distance map", like=src)
+        if scratch is None:
+            scratch = _distance_scratch(B * H * W, src.device)
+        elif scratch.device != src.device:
+            raise RuntimeError(f"mmsa.evaluate: scratch is on {scratch.device}, the map on {src.device}")
+        if d2 is not None and scratch.data_ptr() == d2.data_ptr():
+            raise RuntimeError("mmsa.evaluate: scratch and d2 are two planes")
+        role = _fill_roles_on(src.device, roles)
+        lib.call("mmsa_fill_nearest_u8", src.data_ptr(), B, H, W, role.data_ptr(), int(np.flatnonzero(roles == FILL_HOLE)[0]), cap, scratch.data_ptr(),
+                 out.data_ptr(), None if d2 is None else d2.data_ptr(), ops._stream())
+    return out
+
+
+def _check_nearest(nearest, fill, num_classes, who):
+    """The nearest= keyword of the calls that paint `fill`: None, or the cap of the fill that follows; the painted byte must be no class."""
+    if nearest is None:
+        return None
+    nearest = check_distance_cap(nearest, who)
+    if num_classes is not None and int(fill) < int(num_classes):
+        raise ValueError(f"{who}: fill = {fill} with nearest=: the byte is one of the {num_classes} classes, and a class byte would be a hole and a source at once; "
+                         f"paint with a byte from {num_classes} on")
+    return nearest
 
 
 # ---- run-length tables: the runs of a class map or an ids map, and the COCO RLE of one id (csrc/runs.hip; DESIGN.md section 2) ----
