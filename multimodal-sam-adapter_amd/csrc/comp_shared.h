@@ -1,5 +1,6 @@
 // What the passes over root maps share: csrc/components.hip (areas, suppression, segment counts) and csrc/pairs.hip (the pair table, panoptic matching).
 // Root maps are int32 [B, H, W] as mmsa_components_u8 writes them, B * H * W < 2^31; every pass clamps a root before it addresses anything with it.
+// These passes keep no LDS: they read a label code with label_code(ev, ev.lut, ...) of csrc/code_map.h, the LUT in global memory.
 #pragma once
 #include "common.h"
 #include "eval_hist.h"
@@ -16,22 +17,6 @@ static inline int comp_zero(const char* name, void* p, size_t bytes, hipStream_t
   const hipError_t e = hipMemsetAsync(p, 0, bytes, stream);
   MMSA_CHECK_ARG(e == hipSuccess, "%s: zeroing the planes failed: %s", name, hipGetErrorString(e));
   return MMSA_OK;
-}
-
-// the code map of a component launch and of csrc/segtable.hip: M(y, x) = lut[src[b, ymap[y], xmap[x]]]
-struct CompSrc {                    // the source of a component launch (csrc/distance.hip DistSrc)
-  const unsigned char* src;         // [B, Hs, Ws]
-  const unsigned char* lut;         // [256] or NULL (identity)
-  const int* ymap;                  // [H] / [W] source row / column, or both NULL (Hs == H, Ws == W)
-  const int* xmap;
-  int Hs, Ws, H, W;
-};
-
-__device__ __forceinline__ int comp_code(const CompSrc& s, int b, int y, int x) {      // 0 <= y < H, 0 <= x < W
-  const int ys = s.ymap ? min(max(s.ymap[y], 0), s.Hs - 1) : y;
-  const int xs = s.xmap ? min(max(s.xmap[x], 0), s.Ws - 1) : x;
-  const int v = s.src[((long)b * s.Hs + ys) * s.Ws + xs];
-  return s.lut ? (int)s.lut[v] : v;
 }
 
 // dst[key] += the number of lanes that hold `key` (and dst2[key] += those of them with `flag`, where dst2 is given), ONE atomicAdd per (wave, key).  Called by
@@ -51,18 +36,6 @@ __device__ __forceinline__ void comp_wave_add(int* dst, int* dst2, bool has, int
     pending = pending && !same;
     m &= ~ms;
   }
-}
-
-// pixel i of image b: its label code (a class < C, C, or MMSA_EVAL_IGNORE), read through the tables where there are any (csrc/distance.hip dist_label_code,
-// with the LUT in global memory: these passes keep no LDS)
-__device__ __forceinline__ int comp_label_code(const EvalLabel& ev, int b, int W, int i) {      // H * W < 2^31
-  long at = i;
-  if (ev.ymap) {
-    const int y = i / W, x = i - y * W;
-    at = (long)min(max(ev.ymap[y], 0), ev.Hl - 1) * ev.Wl + min(max(ev.xmap[x], 0), ev.Wl - 1);
-  }
-  const int l = ev.lut[ev.label[(long)b * ev.Hl * ev.Wl + at]];
-  return l == MMSA_EVAL_IGNORE ? l : min(l, ev.C);
 }
 
 // counts[bin] += 1 for every lane with bin >= 0: two rounds of the merge above first (a frame's root pixels of one class and size mostly share a cell), the

@@ -2,7 +2,7 @@
 // its small blobs (mmsa_suppress_small_u8) and the segment counts of a prediction against the ground truth (mmsa_eval_segments: how many label segments were
 // found, how many prediction segments are real, by class, by size and by the share of the segment that is covered).  Integers only: the same bytes run after run.
 //
-// The quantity.  For a code map M (one byte per pixel after the LUT and the nearest-neighbour tables, read as csrc/distance.hip reads it; the kernels compare
+// The quantity.  For a code map M (one byte per pixel after the LUT and the nearest-neighbour tables, read through csrc/code_map.h; the kernels compare
 // bytes and know nothing of classes) two pixels of one image are connected iff they are 4- or 8-neighbours and hold the same code; a component is a maximal
 // connected set, and root[b, y, x] = the smallest linear index y * W + x of the pixel's component, within its own image: canonical, whatever the schedule.
 //
@@ -23,6 +23,7 @@
 // lowest pending lane's root is broadcast, a ballot counts its lanes, one lane adds their number: the form of csrc/cal_wave.h, at most 64 rounds).
 #include "common.h"
 #include "eval_hist.h"
+#include "code_map.h"
 #include "comp_shared.h"
 
 #define COMP_TW 64
@@ -35,7 +36,7 @@
 #define COMP_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
 // grid.x = tiles_x * tiles_y * B, x fastest.  Lane t owns the local pixels t, t + 256, ...: a wave on one tile row.
-__global__ __launch_bounds__(256) void components_tile_kernel(CompSrc s, int tiles_x, int tiles_y, int conn8, int* __restrict__ parent) {
+__global__ __launch_bounds__(256) void components_tile_kernel(CodeSrc s, int tiles_x, int tiles_y, int conn8, int* __restrict__ parent) {
   __shared__ unsigned short code[COMP_PH * COMP_PW];
   __shared__ int lab[COMP_TILE];
   const long t = blockIdx.x;
@@ -48,7 +49,7 @@ __global__ __launch_bounds__(256) void components_tile_kernel(CompSrc s, int til
 #pragma unroll
   for (int k = 0; k < COMP_TILE / 256; ++k) {
     const int li = k * 256 + (int)threadIdx.x, ly = li / COMP_TW, lx = li % COMP_TW;
-    if (y0 + ly < H && x0 + lx < W) code[(ly + 1) * COMP_PW + lx + 1] = (unsigned short)comp_code(s, b, y0 + ly, x0 + lx);
+    if (y0 + ly < H && x0 + lx < W) code[(ly + 1) * COMP_PW + lx + 1] = (unsigned short)code_at(s, b, y0 + ly, x0 + lx);
     lab[li] = li;
   }
   __syncthreads();
@@ -131,7 +132,7 @@ __device__ __forceinline__ void comp_union(int* img, int a, int b, int cap) {
 
 // grid (cdiv(nv + nh, 256), B): nv = (tiles_x - 1) * H lanes on the first column behind a vertical tile border, nh = (tiles_y - 1) * W on the first row
 // behind a horizontal one.  A pair across a corner is seen from both sides, which does no harm.
-__global__ __launch_bounds__(256) void components_merge_kernel(CompSrc s, int tiles_x, int tiles_y, int conn8, int* parent) {
+__global__ __launch_bounds__(256) void components_merge_kernel(CodeSrc s, int tiles_x, int tiles_y, int conn8, int* parent) {
   const int H = s.H, W = s.W, b = blockIdx.y;
   const long nv = (long)(tiles_x - 1) * H, nh = (long)(tiles_y - 1) * W;
   long j = (long)blockIdx.x * 256 + threadIdx.x;
@@ -151,10 +152,10 @@ __global__ __launch_bounds__(256) void components_merge_kernel(CompSrc s, int ti
     ny[0] = ny[1] = ny[2] = y - 1;
     nx[0] = x, nx[1] = x - 1, nx[2] = x + 1;
   }
-  const int c = comp_code(s, b, y, x), n = conn8 ? 3 : 1;
+  const int c = code_at(s, b, y, x), n = conn8 ? 3 : 1;
   for (int k = 0; k < n; ++k) {
     if (ny[k] < 0 || ny[k] >= H || nx[k] < 0 || nx[k] >= W) continue;
-    if (comp_code(s, b, ny[k], nx[k]) == c) comp_union(img, y * W + x, ny[k] * W + nx[k], cap);
+    if (code_at(s, b, ny[k], nx[k]) == c) comp_union(img, y * W + x, ny[k] * W + nx[k], cap);
   }
 }
 
@@ -178,14 +179,12 @@ extern "C" int mmsa_components_u8(const unsigned char* src, int B, int Hs, int W
   MMSA_CHECK_ARG(src && root, "%s: src and root are required", name);
   int rc = comp_check_size(name, B, H, W);
   if (rc) return rc;
-  MMSA_CHECK_ARG(Hs > 0 && Ws > 0 && (long)Hs * Ws < (1l << 31), "%s: bad source size", name);
-  MMSA_CHECK_ARG((ymap != NULL) == (xmap != NULL), "%s: ymap and xmap come together", name);
-  MMSA_CHECK_ARG(ymap || (Hs == H && Ws == W), "%s: size mismatch: the source is %d x %d, the grid %d x %d, and no ymap / xmap tables were given", name, Hs,
-                 Ws, H, W);
+  rc = code_src_check(name, "bad source size", Hs, Ws, ymap, xmap, H, W);
+  if (rc) return rc;
   MMSA_CHECK_ARG(connectivity == 4 || connectivity == 8, "%s: connectivity = %d; 4 or 8 is expected", name, connectivity);
   const int tiles_x = cdiv(W, COMP_TW), tiles_y = cdiv(H, COMP_TH), conn8 = connectivity == 8;
   const long tiles = (long)tiles_x * tiles_y * B;                            // <= B * H * W < 2^31
-  const CompSrc s = {src, lut, ymap, xmap, Hs, Ws, H, W};
+  const CodeSrc s = {src, lut, ymap, xmap, Hs, Ws, H, W};
   hipLaunchKernelGGL(components_tile_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, s, tiles_x, tiles_y, conn8, root);
   if (tiles_x * tiles_y > 1) {
     const long pairs = (long)(tiles_x - 1) * H + (long)(tiles_y - 1) * W;
@@ -196,7 +195,7 @@ extern "C" int mmsa_components_u8(const unsigned char* src, int B, int Hs, int W
   return MMSA_OK;
 }
 
-// ---- the pointwise passes over root maps (comp_wave_add, comp_label_code, seg_count_add and the size bucket: csrc/comp_shared.h, shared with csrc/pairs.hip)
+// ---- the pointwise passes over root maps (comp_wave_add, seg_count_add and the size bucket: csrc/comp_shared.h, shared with csrc/pairs.hip)
 // grid (cdiv(H * W, 256), B): a wave lies inside one image
 __global__ __launch_bounds__(256) void component_area_kernel(const int* __restrict__ root, int H, int W, int* area) {
   const long HW = (long)H * W, i = (long)blockIdx.x * 256 + threadIdx.x, base = blockIdx.y * HW;
@@ -256,7 +255,7 @@ __global__ __launch_bounds__(256) void eval_segments_area_kernel(SegMaps m, Eval
   bool has = i < HW, hit = false;
   int rl = 0, rp = 0;
   if (has) {
-    const int l = comp_label_code(ev, blockIdx.y, m.W, (int)i);
+    const int l = label_code(ev, ev.lut, blockIdx.y, m.W, (int)i);
     has = l != MMSA_EVAL_IGNORE;
     hit = l < ev.C && min((int)m.pred[base + i], ev.C) == l;
     rl = min(max(m.root_label[base + i], 0), (int)HW - 1);
@@ -284,7 +283,7 @@ __global__ __launch_bounds__(256) void eval_segments_count_kernel(SegMaps m, Eva
   if (i < HW) {
     if (m.root_label[base + i] == (int)i) {
       const int a = m.planes[base + i];
-      if (a > 0) c0 = seg_cell(comp_label_code(ev, b, m.W, (int)i), C, a, m.planes[plane + base + i], bins);
+      if (a > 0) c0 = seg_cell(label_code(ev, ev.lut, b, m.W, (int)i), C, a, m.planes[plane + base + i], bins);
     }
     if (m.root_pred[base + i] == (int)i) {
       const int a = m.planes[2 * plane + base + i];

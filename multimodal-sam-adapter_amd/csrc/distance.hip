@@ -13,9 +13,8 @@
 // (a pixel of another code in row y' nearest to column px is either (px, y') itself or the end of the run of M(p) that holds (px, y')).
 //
 // Two launches, no dependence between workgroups inside either, every loop bounded by the row length, by cap or by the image height:
-//   row pass     a WORKGROUP per row of an image.  A lane owns ceil(W / 256) consecutive pixels: it finds the first and the last code change of its piece,
-//                the workgroup forms an exclusive prefix maximum / suffix minimum over the lanes (the last change before and the first change after every
-//                piece: a shuffle scan inside each wave, the four waves' ends through LDS), and the lane walks its piece again run by run and writes, per
+//   row pass     the row pass of csrc/row_scan.h with a code change as the marked index: a lane finds the first and the last change of its piece, row_scan
+//                gives it the last change before and the first change after the piece, and the lane walks its piece again run by run and writes, per
 //                pixel, the code and r - 1 saturated at 255 (r >= 256 can matter at no cap) as ONE uint16 into the scratch plane [B, H, W].
 //   column pass  a lane per pixel, a wave on 64 consecutive x: from the pixel's own row outward, dy = 1, 2, ... while dy <= cap and dy^2 < best, both rows at
 //                distance dy: one coalesced 128-byte read of the scratch plane per wave and row.  Pixels next to a contour stop after a step or two; a pixel
@@ -25,6 +24,8 @@
 // but not their position, which a pass that reads two more planes needs: these passes walk by themselves.)
 #include "common.h"
 #include "eval_hist.h"
+#include "code_map.h"
+#include "row_scan.h"
 
 #define DIST_FAR 65535
 #define DIST_MAX_CAP 255
@@ -41,40 +42,24 @@
 #define DIST_MAX_SIDE_CELLS ((DIST_LDS_BYTES - 256) / 4)
 static_assert(2 * 26 * 257 * 4 + 256 <= DIST_LDS_BYTES && 2 * 83 * 66 * 4 + 256 <= DIST_LDS_BYTES, "the required sizes of the displacement histogram");
 
-struct DistSrc {                    // the source of a distance launch
-  const unsigned char* src;         // [B, Hs, Ws]
-  const unsigned char* lut;         // [256] or NULL (identity)
-  const int* ymap;                  // [H] / [W] source row / column, or both NULL (Hs == H, Ws == W)
-  const int* xmap;
-  int Hs, Ws, H, W;
-};
-
-__device__ __forceinline__ int dist_code(const DistSrc& s, const unsigned char* __restrict__ row, int x) {
-  const int xs = s.xmap ? min(max(s.xmap[x], 0), s.Ws - 1) : x;
-  const int v = row[xs];
-  return s.lut ? (int)s.lut[v] : v;
-}
-
 // rows = B * H; the workgroup blockIdx.x owns one row
-__global__ __launch_bounds__(256) void distance_rows_kernel(DistSrc s, unsigned short* __restrict__ plane) {
+__global__ __launch_bounds__(256) void distance_rows_kernel(CodeSrc s, unsigned short* __restrict__ plane) {
   __shared__ int wave_last[4], wave_first[4];
   const long row = blockIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, W = s.W;
+  const int W = s.W;
   const int b = (int)(row / s.H), y = (int)(row - (long)b * s.H);
-  const int ys = s.ymap ? min(max(s.ymap[y], 0), s.Hs - 1) : y;
-  const unsigned char* __restrict__ srow = s.src + ((long)b * s.Hs + ys) * s.Ws;
+  const unsigned char* __restrict__ srow = code_row(s, b, y);
   unsigned short* __restrict__ prow = plane + row * W;
-  const int ch = (W + 255) >> 8;
-  const int x0 = min(W, (int)threadIdx.x * ch), x1 = min(W, x0 + ch);
-  const int NONE = 0x7fffffff;
+  int x0, x1, before, after;
+  row_piece(W, x0, x1);
 
   // 1. the first and the last change of this lane's piece; a change at x: code(x) != code(x - 1), x >= 1
-  int fc = NONE, lc = -1;
-  const int left = (x0 > 0 && x0 < x1) ? dist_code(s, srow, x0 - 1) : -1;
+  int fc = ROW_NONE, lc = -1;
+  const int left = (x0 > 0 && x0 < x1) ? code_at(s, srow, x0 - 1) : -1;
   {
     int prev = left;
     for (int x = x0; x < x1; ++x) {
-      const int c = dist_code(s, srow, x);
+      const int c = code_at(s, srow, x);
       if (prev >= 0 && c != prev) {
         fc = min(fc, x);
         lc = x;
@@ -82,44 +67,26 @@ __global__ __launch_bounds__(256) void distance_rows_kernel(DistSrc s, unsigned 
       prev = c;
     }
   }
-  // 2. the last change in front of the piece, the first change behind it: a scan inside the wave, the waves' own ends through LDS (every lane of the
-  //    workgroup is here: a row is a workgroup's)
-  int pm = lc, sm = fc;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int up = __shfl_up(pm, o, 64), dn = __shfl_down(sm, o, 64);
-    if (lane >= o) pm = max(pm, up);
-    if (lane + o < 64) sm = min(sm, dn);
-  }
-  if (lane == 63) wave_last[wave] = pm;                                      // the wave's last change
-  if (lane == 0) wave_first[wave] = sm;                                      // and its first
-  int before = __shfl_up(pm, 1, 64), after = __shfl_down(sm, 1, 64);
-  if (lane == 0) before = -1;
-  if (lane == 63) after = NONE;
-  __syncthreads();
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    if (w < wave) before = max(before, wave_last[w]);
-    if (w > wave) after = min(after, wave_first[w]);
-  }
+  // 2. the last change in front of the piece, the first change behind it (every lane of the workgroup is here: a row is a workgroup's)
+  row_scan(fc, lc, wave_last, wave_first, before, after);
   if (x0 >= x1) return;
 
   // 3. run by run: the run [a, x) of code `prev` starts behind the change `st` (-1: it reaches the row's left end) and ends at the change `en`
-  int a = x0, prev = dist_code(s, srow, x0);
+  int a = x0, prev = code_at(s, srow, x0);
   int st = (left >= 0 && left != prev) ? x0 : before;
   for (int x = x0 + 1; x <= x1; ++x) {
-    int c = -1, en = NONE;
+    int c = -1, en = ROW_NONE;
     if (x < x1) {
-      c = dist_code(s, srow, x);
+      c = code_at(s, srow, x);
       if (c == prev) continue;
       en = x;
     } else {
       en = after;
     }
     for (int q = a; q < x; ++q) {                                            // every pixel of the piece is written once
-      int r = NONE;
+      int r = ROW_NONE;
       if (st >= 0) r = q - st + 1;                                           // the pixel st - 1 holds another code
-      if (en != NONE) r = min(r, en - q);                                    // and so does the pixel en
+      if (en != ROW_NONE) r = min(r, en - q);                                    // and so does the pixel en
       const int rb = r > DIST_RUN_SAT ? DIST_RUN_SAT : r - 1;
       prow[q] = (unsigned short)(prev | (rb << 8));
     }
@@ -134,15 +101,11 @@ __device__ __forceinline__ int dist_run2(int v) {      // g^2 of a scratch word'
   return rb == DIST_RUN_SAT ? DIST_BIG : (rb + 1) * (rb + 1);
 }
 
-// grid.x = tiles of 64 columns x groups of 4 rows x B, x fastest; a wave per (row, 64 columns)
+// the grid of col_tile (csrc/row_scan.h)
 __global__ __launch_bounds__(256) void distance_cols_kernel(const unsigned short* __restrict__ plane, int H, int W, int tiles_x, int groups_y, int cap,
                                                             int border, unsigned short* __restrict__ d2) {
-  const long t = blockIdx.x;
-  const int tx = (int)(t % tiles_x);
-  const long rest = t / tiles_x;
-  const int gy = (int)(rest % groups_y), b = (int)(rest / groups_y);
-  const int x = tx * 64 + (threadIdx.x & 63), y = gy * 4 + (threadIdx.x >> 6);
-  if (x >= W || y >= H) return;
+  int b, y, x;
+  if (!col_tile(H, W, tiles_x, groups_y, b, y, x)) return;
   const unsigned short* __restrict__ col = plane + (long)b * H * W + x;
   const int own = col[(long)y * W], c = own & 255, limit = cap * cap;
   int best = min(limit + 1, dist_run2(own));
@@ -170,19 +133,17 @@ extern "C" int mmsa_boundary_distance_u8(const unsigned char* src, int B, int Hs
   const char* name = "boundary_distance_u8";
   MMSA_CHECK_ARG(src && scratch && d2, "%s: src, scratch and d2 are required", name);
   MMSA_CHECK_ARG(scratch != d2, "%s: scratch and d2 are two planes", name);
-  MMSA_CHECK_ARG(B > 0 && H > 0 && W > 0 && Hs > 0 && Ws > 0 && (long)H * W < (1l << 31) && (long)Hs * Ws < (1l << 31), "%s: bad map size", name);
-  MMSA_CHECK_ARG((ymap != NULL) == (xmap != NULL), "%s: ymap and xmap come together", name);
-  MMSA_CHECK_ARG(ymap || (Hs == H && Ws == W), "%s: size mismatch: the source is %d x %d, the grid %d x %d, and no ymap / xmap tables were given", name, Hs,
-                 Ws, H, W);
+  MMSA_CHECK_ARG(B > 0 && H > 0 && W > 0 && (long)H * W < (1l << 31), "%s: bad map size", name);
+  int rc = code_src_check(name, "bad map size", Hs, Ws, ymap, xmap, H, W);
+  if (rc) return rc;
   MMSA_CHECK_ARG(cap >= 1 && cap <= DIST_MAX_CAP, "%s: cap = %d; 1..%d are supported (cap^2 must fit the uint16 map below 65535)", name, cap, DIST_MAX_CAP);
   MMSA_CHECK_ARG(border == 0 || border == 1, "%s: border = %d; 0 (pixels outside the image do not exist) or 1 (the image border is a boundary)", name, border);
-  const long rows = (long)B * H;
-  const int tiles_x = cdiv(W, 64), groups_y = cdiv(H, 4);      // H, W < 2^31
-  const long blocks = (long)tiles_x * groups_y * B;
-  MMSA_CHECK_ARG(rows < (1l << 31) && blocks < (1l << 31), "%s: %d maps of %d x %d are more workgroups than a launch holds", name, B, H, W);
-  const DistSrc s = {src, lut, ymap, xmap, Hs, Ws, H, W};
-  hipLaunchKernelGGL(distance_rows_kernel, dim3((unsigned)rows), dim3(256), 0, stream, s, scratch);
-  hipLaunchKernelGGL(distance_cols_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, scratch, H, W, tiles_x, groups_y, cap, border, d2);
+  RowColGrid g;
+  rc = row_col_grid(name, B, H, W, g);
+  if (rc) return rc;
+  const CodeSrc s = {src, lut, ymap, xmap, Hs, Ws, H, W};
+  hipLaunchKernelGGL(distance_rows_kernel, dim3((unsigned)g.rows), dim3(256), 0, stream, s, scratch);
+  hipLaunchKernelGGL(distance_cols_kernel, dim3((unsigned)g.blocks), dim3(256), 0, stream, scratch, H, W, g.tiles_x, g.groups_y, cap, border, d2);
   MMSA_CHECK_LAUNCH("boundary_distance_u8");
   return MMSA_OK;
 }
@@ -194,17 +155,6 @@ struct DistMaps {
   const unsigned short* d2l;
   int H, W;
 };
-
-// pixel i of image b: its label code (a class < C, C, or MMSA_EVAL_IGNORE), read through the tables where there are any
-__device__ __forceinline__ int dist_label_code(const EvalLabel& ev, const unsigned char* lut_s, int b, int W, int i) {      // H * W < 2^31
-  long at = i;
-  if (ev.ymap) {
-    const int y = i / W, x = i - y * W;
-    at = (long)min(max(ev.ymap[y], 0), ev.Hl - 1) * ev.Wl + min(max(ev.xmap[x], 0), ev.Wl - 1);
-  }
-  const int l = lut_s[ev.label[(long)b * ev.Hl * ev.Wl + at]];
-  return l == MMSA_EVAL_IGNORE ? l : min(l, ev.C);
-}
 
 // grid (chunks of DIST_CHUNK pixels, B, zone groups): zone = 2 * (d2_label <= t) + (d2_pred <= t)
 __global__ __launch_bounds__(256) void eval_boundary_d2_kernel(DistMaps m, EvalLabel ev, EvalSlots es, int t, int zn) {
@@ -219,7 +169,7 @@ __global__ __launch_bounds__(256) void eval_boundary_d2_kernel(DistMaps m, EvalL
     const long i = start + k + threadIdx.x;
     int bin = -1;
     if (i < HW) {
-      const int l = dist_label_code(ev, lut_s, b, m.W, (int)i);
+      const int l = label_code(ev, lut_s, b, m.W, (int)i);
       if (l != MMSA_EVAL_IGNORE) {
         const int z = 2 * (int)((int)m.d2l[base + i] <= t) + (int)((int)m.d2p[base + i] <= t) - z0;
         if ((unsigned)z < (unsigned)zn) bin = z * nb + l * (C + 1) + min((int)m.pred[base + i], C);
@@ -283,7 +233,7 @@ __global__ __launch_bounds__(256) void eval_boundary_displacement_kernel(DistMap
     if (i >= HW) continue;
     const int dl = m.d2l[base + i], dp = m.d2p[base + i];
     if (dl > 2 && dp > 2) continue;                                          // most of a frame: on neither contour
-    const int l = dist_label_code(ev, lut_s, b, m.W, (int)i);
+    const int l = label_code(ev, lut_s, b, m.W, (int)i);
     if (l == MMSA_EVAL_IGNORE) continue;
     if (dl <= 2 && s0 == 0) atomicAdd(&hist[l * nk + dist_bin(dp, cap)], 1u);
     if (dp <= 2 && s0 + sn == 2) atomicAdd(&hist[(1 - s0) * ns + min((int)m.pred[base + i], C) * nk + dist_bin(dl, cap)], 1u);

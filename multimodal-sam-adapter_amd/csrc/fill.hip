@@ -10,19 +10,20 @@
 // The key is separable.  Within one row the nearest source to column px has the smallest |dx|, and of a left and a right source equally far the left one has
 // the smaller qx.  Across rows a candidate is the row's nearest source at its row distance g: keys (dy^2 + g^2, qy).
 //
-// Two launches in the shape of csrc/distance.hip, no dependence between workgroups inside either, every loop bounded by the row length, by cap or by the
+// Two launches in the frame of csrc/row_scan.h, no dependence between workgroups inside either, every loop bounded by the row length, by cap or by the
 // image height:
-//   row pass     a WORKGROUP per row of an image.  A lane owns ceil(W / 256) consecutive pixels: it finds the first and the last source of its piece, the
-//                workgroup forms an exclusive prefix maximum / suffix minimum over the lanes (the last source before and the first source after every piece:
-//                distance_rows_kernel's scan), and the lane walks its piece again and writes, per pixel, ONE uint16 into the scratch plane [B, H, W]: the
-//                value of the row's nearest source (left on ties) in the low byte, the distance g (0 at a source) in the high byte.  No source of the row
-//                within 255 columns: the low byte is `none_byte`, a hole byte, which is the value of no source.
+//   row pass     the row pass of csrc/row_scan.h with a source pixel as the marked index: a lane finds the first and the last source of its piece, row_scan
+//                gives it the last source before and the first source after the piece, and the lane walks its piece again and writes, per pixel, ONE
+//                uint16 into the scratch plane [B, H, W]: the value of the row's nearest source (left on ties) in the low byte, the distance g (0 at a
+//                source) in the high byte.  No source of the row within 255 columns: the low byte is `none_byte`, a hole byte, which is the value of no
+//                source.
 //   column pass  a lane per pixel, a wave on 64 consecutive x.  A lane whose own pixel is no hole copies it and leaves (a wave without holes: one read).  A
 //                hole lane walks dy = 0, 1, 2, ... over both rows at distance dy while dy <= min(cap, max(y, H - 1 - y)) and dy^2 <= best: one coalesced
 //                128-byte read of the scratch plane per wave and row.  The row above at the same d2 beats what was found (its qy is smaller: <=), the row
 //                below never does (<), and the loop still enters the dy whose dy^2 equals best, for the row above it.
 // out may be src: a lane of the column pass reads its own pixel of src and the scratch plane, nothing else.
 #include "common.h"
+#include "row_scan.h"
 
 #define FILL_FAR 65535
 #define FILL_MAX_CAP 255
@@ -36,61 +37,41 @@ __global__ __launch_bounds__(256) void fill_rows_kernel(const unsigned char* __r
   __shared__ unsigned char role_s[256];
   __shared__ int wave_last[4], wave_first[4];
   const long row = blockIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const unsigned char* __restrict__ srow = src + row * W;
   unsigned short* __restrict__ prow = plane + row * W;
-  const int ch = (W + 255) >> 8;
-  const int x0 = min(W, (int)threadIdx.x * ch), x1 = min(W, x0 + ch);
-  const int NONE = 0x7fffffff;
+  int x0, x1, before, after;
+  row_piece(W, x0, x1);
   role_s[threadIdx.x] = role[threadIdx.x];
   __syncthreads();
 
   // 1. the first and the last source of this lane's piece
-  int fs = NONE, ls = -1;
+  int fs = ROW_NONE, ls = -1;
   for (int x = x0; x < x1; ++x) {
     if (role_s[srow[x]] == FILL_ROLE_SOURCE) {
       fs = min(fs, x);
       ls = x;
     }
   }
-  // 2. the last source in front of the piece, the first source behind it: a scan inside the wave, the waves' own ends through LDS (every lane of the
-  //    workgroup is here: a row is a workgroup's)
-  int pm = ls, sm = fs;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int up = __shfl_up(pm, o, 64), dn = __shfl_down(sm, o, 64);
-    if (lane >= o) pm = max(pm, up);
-    if (lane + o < 64) sm = min(sm, dn);
-  }
-  if (lane == 63) wave_last[wave] = pm;                                      // the wave's last source
-  if (lane == 0) wave_first[wave] = sm;                                      // and its first
-  int before = __shfl_up(pm, 1, 64), after = __shfl_down(sm, 1, 64);
-  if (lane == 0) before = -1;
-  if (lane == 63) after = NONE;
-  __syncthreads();
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    if (w < wave) before = max(before, wave_last[w]);
-    if (w > wave) after = min(after, wave_first[w]);
-  }
+  // 2. the last source in front of the piece, the first source behind it (every lane of the workgroup is here: a row is a workgroup's)
+  row_scan(fs, ls, wave_last, wave_first, before, after);
   if (x0 >= x1) return;
 
-  // 3. stretch by stretch: the pixels [a, x) that are no sources lie between the source `st` (-1: none to the left) and the source `en` (NONE: none to the
+  // 3. stretch by stretch: the pixels [a, x) that are no sources lie between the source `st` (-1: none to the left) and the source `en` (ROW_NONE: none to the
   //    right); before and after are indices of this row, 0 <= before < x0 and x1 <= after < W where there are any
   const unsigned short none = (unsigned short)(none_byte | (255 << 8));
   int a = x0, st = before, stv = before >= 0 ? (int)srow[before] : 0;
   for (int x = x0; x <= x1; ++x) {
-    int en = NONE, env = 0;
+    int en = ROW_NONE, env = 0;
     if (x < x1) {
       env = srow[x];
       if (role_s[env] != FILL_ROLE_SOURCE) continue;
       en = x;
-    } else if (after != NONE) {
+    } else if (after != ROW_NONE) {
       en = after;
       env = srow[after];
     }
     for (int q = a; q < x; ++q) {                                            // every pixel of the piece is written once
-      const int dl = st >= 0 ? q - st : FILL_BIG, dr = en != NONE ? en - q : FILL_BIG;
+      const int dl = st >= 0 ? q - st : FILL_BIG, dr = en != ROW_NONE ? en - q : FILL_BIG;
       const int g = min(dl, dr), v = dl <= dr ? stv : env;                   // equally far: the left one
       prow[q] = g <= 255 ? (unsigned short)(v | (g << 8)) : none;
     }
@@ -101,18 +82,14 @@ __global__ __launch_bounds__(256) void fill_rows_kernel(const unsigned char* __r
   }
 }
 
-// grid.x = tiles of 64 columns x groups of 4 rows x B, x fastest; a wave per (row, 64 columns).  src and out may be one buffer: no __restrict__ on them.
+// the grid of col_tile (csrc/row_scan.h).  src and out may be one buffer: no __restrict__ on them.
 __global__ __launch_bounds__(256) void fill_cols_kernel(const unsigned char* src, const unsigned char* __restrict__ role,
                                                         const unsigned short* __restrict__ plane, int H, int W, int tiles_x, int groups_y, int none_byte, int cap,
                                                         unsigned char* out, unsigned short* __restrict__ d2) {
   __shared__ unsigned char role_s[256];
   role_s[threadIdx.x] = role[threadIdx.x];
-  const long t = blockIdx.x;
-  const int tx = (int)(t % tiles_x);
-  const long rest = t / tiles_x;
-  const int gy = (int)(rest % groups_y), b = (int)(rest / groups_y);
-  const int x = tx * 64 + (threadIdx.x & 63), y = gy * 4 + (threadIdx.x >> 6);
-  const bool inside = x < W && y < H;
+  int b, y, x;
+  const bool inside = col_tile(H, W, tiles_x, groups_y, b, y, x);
   const long at = ((long)b * H + (inside ? y : 0)) * W + (inside ? x : 0);
   const int own = src[at];                                                   // a pixel of the map for the lanes outside too: they write nothing
   __syncthreads();
@@ -163,12 +140,11 @@ extern "C" int mmsa_fill_nearest_u8(const unsigned char* src, int B, int H, int 
   MMSA_CHECK_ARG(B > 0 && H > 0 && W > 0 && (long)H * W < (1l << 31), "%s: bad map size", name);
   MMSA_CHECK_ARG(cap >= 1 && cap <= FILL_MAX_CAP, "%s: cap = %d; 1..%d are supported (cap^2 must fit the uint16 map below 65535)", name, cap, FILL_MAX_CAP);
   MMSA_CHECK_ARG(none_byte >= 0 && none_byte <= 255, "%s: none_byte = %d; a byte 0..255 whose role is 1 (a hole) is expected", name, none_byte);
-  const long rows = (long)B * H;
-  const int tiles_x = cdiv(W, 64), groups_y = cdiv(H, 4);      // H, W < 2^31
-  const long blocks = (long)tiles_x * groups_y * B;
-  MMSA_CHECK_ARG(rows < (1l << 31) && blocks < (1l << 31), "%s: %d maps of %d x %d are more workgroups than a launch holds", name, B, H, W);
-  hipLaunchKernelGGL(fill_rows_kernel, dim3((unsigned)rows), dim3(256), 0, stream, src, role, W, none_byte, scratch);
-  hipLaunchKernelGGL(fill_cols_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, src, role, scratch, H, W, tiles_x, groups_y, none_byte, cap, out, d2);
+  RowColGrid g;
+  const int rc = row_col_grid(name, B, H, W, g);
+  if (rc) return rc;
+  hipLaunchKernelGGL(fill_rows_kernel, dim3((unsigned)g.rows), dim3(256), 0, stream, src, role, W, none_byte, scratch);
+  hipLaunchKernelGGL(fill_cols_kernel, dim3((unsigned)g.blocks), dim3(256), 0, stream, src, role, scratch, H, W, g.tiles_x, g.groups_y, none_byte, cap, out, d2);
   MMSA_CHECK_LAUNCH("fill_nearest_u8");
   return MMSA_OK;
 }

@@ -24,6 +24,7 @@
 // dropped), and neither does the multiset of (key, count).
 #include "common.h"
 #include "eval_hist.h"
+#include "code_map.h"
 #include "comp_shared.h"
 
 #ifndef PAIR_MAX_PROBES
@@ -75,7 +76,7 @@ __global__ __launch_bounds__(256) void segment_pairs_kernel(PairMaps m, EvalLabe
   bool pending = false;
   unsigned long long key = 0ull;
   if (i < HW) {
-    const int l = comp_label_code(ev, blockIdx.y, m.W, (int)i);
+    const int l = label_code(ev, ev.lut, blockIdx.y, m.W, (int)i);
     pending = l < ev.C && min((int)m.pred[base + i], ev.C) == l;               // MMSA_EVAL_IGNORE = 255 > C: an ignored pixel is no hit
     const int rl = min(max(m.root_label[base + i], 0), (int)HW - 1);
     const int rp = min(max(m.root_pred[base + i], 0), (int)HW - 1);
@@ -162,7 +163,7 @@ __global__ __launch_bounds__(256) void panoptic_match_kernel(PanopticMaps m, Eva
       if (3 * inter > area_p + area_g && inter <= area_g && inter <= area_p) {
         m.match[g] = (int)rp;
         m.match[plane + (long)b * HW + rp] = rl;
-        const int c = comp_label_code(ev, b, m.W, rl);
+        const int c = label_code(ev, ev.lut, b, m.W, rl);
         if (c < ev.C) {
           bin = (es.s[b] * ev.C * COMP_SIZE_BUCKETS * 4) + pq_cell(c, (int)area_g);
           q = ((unsigned long long)inter << 24) / (unsigned long long)(area_p + area_g - inter);      // inter < 2^31: exact in 64 bits; union >= inter > 0
@@ -184,7 +185,7 @@ __global__ __launch_bounds__(256) void panoptic_count_kernel(PanopticMaps m, Eva
     if (m.root_label[base + i] == (int)i && m.match[base + i] < 0) {
       const int a = m.planes[base + i];
       if (a > 0) {
-        const int c = comp_label_code(ev, b, m.W, (int)i);
+        const int c = label_code(ev, ev.lut, b, m.W, (int)i);
         if (c < C) fn = pq_cell(c, a) + 2;
       }
     }

@@ -25,6 +25,7 @@
 // Y0 is the root's row: the root is the component's smallest linear index.  The rows are zeroed with hipMemsetAsync before the id pass.
 #include "common.h"
 #include "cal_wave.h"       // cal_wave_sum: a wave's sum by data-parallel-primitive moves
+#include "code_map.h"
 #include "comp_shared.h"
 #include "compact.h"
 #include "conf_bin.h"
@@ -51,7 +52,7 @@ static_assert(ST_X1 == 5 && ST_Y1 == 6 && ST_SUM_Y == ST_SUM_X + 1 && ST_SUM_Q =
 COMPACT_CHECK_BLOCK(SEGTAB_BLOCK);
 
 struct SegTabMaps {
-  CompSrc s;
+  CodeSrc s;
   const int* root;                  // [B, H, W]
   const int* area;                  // [B, H, W] as mmsa_component_area writes it, or NULL (min_area == 1)
   int min_area, void_from;
@@ -65,7 +66,7 @@ __device__ __forceinline__ unsigned segtab_q24(float v) { return (unsigned)(conf
 __device__ __forceinline__ int segtab_flag(const SegTabMaps& m, int b, long base, int i, int& code) {
   if (m.root[base + i] != i) return 0;
   const int y = i / m.s.W;
-  code = comp_code(m.s, b, y, i - y * m.s.W);
+  code = code_at(m.s, b, y, i - y * m.s.W);
   if (code >= m.void_from) return -1;
   return m.area == nullptr || m.area[base + i] >= m.min_area ? 1 : -1;
 }
@@ -231,10 +232,8 @@ extern "C" int mmsa_segment_table(const unsigned char* src, int B, int Hs, int W
   MMSA_CHECK_ARG(src && root && count && ids && records && scratch, "%s: src, root, count, ids, records and scratch are required", name);
   int rc = comp_check_size(name, B, H, W);
   if (rc) return rc;
-  MMSA_CHECK_ARG(Hs > 0 && Ws > 0 && (long)Hs * Ws < (1l << 31), "%s: bad source size", name);
-  MMSA_CHECK_ARG((ymap != NULL) == (xmap != NULL), "%s: ymap and xmap come together", name);
-  MMSA_CHECK_ARG(ymap || (Hs == H && Ws == W), "%s: size mismatch: the source is %d x %d, the grid %d x %d, and no ymap / xmap tables were given", name, Hs,
-                 Ws, H, W);
+  rc = code_src_check(name, "bad source size", Hs, Ws, ymap, xmap, H, W);
+  if (rc) return rc;
   MMSA_CHECK_ARG(root != ids && (const void*)root != (const void*)scratch && ids != scratch, "%s: root, ids and scratch are three buffers", name);
   MMSA_CHECK_ARG(min_area >= 1, "%s: min_area = %d; at least 1 (every component) is expected", name, min_area);
   MMSA_CHECK_ARG(min_area == 1 || area, "%s: min_area = %d needs the area plane of mmsa_component_area", name, min_area);

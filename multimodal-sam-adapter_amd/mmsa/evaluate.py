@@ -612,6 +612,23 @@ def _check_buffer(buf, name, shape, device):
     return buf
 
 
+def _check_out(out, dtype, shape, device):
+    """A caller's out= of an entry that writes a whole map: a contiguous tensor of this dtype and shape on `device`."""
+    if not isinstance(out, torch.Tensor) or out.dtype != dtype or tuple(out.shape) != tuple(shape) or out.device != device or not out.is_contiguous():
+        raise RuntimeError(f"mmsa.evaluate: out must be a contiguous {str(dtype).replace('torch.', '')} {tuple(shape)} tensor on {device}")
+    return out
+
+
+def _check_scratch(scratch, dtype, n, device=None, avoid=None, count=None):
+    """A caller's scratch=: a contiguous tensor of `dtype` with at least n elements (`count`: how the message spells n), on `device` where one is given (None:
+    the device is looked at later), and not the tensor `avoid`, the call's `out`."""
+    if (not isinstance(scratch, torch.Tensor) or scratch.dtype != dtype or scratch.numel() < n or not scratch.is_contiguous()
+            or (device is not None and scratch.device != device) or (avoid is not None and scratch.data_ptr() == avoid.data_ptr())):
+        raise RuntimeError(f"mmsa.evaluate: scratch must be a contiguous {str(dtype).replace('torch.', '')} tensor of at least {count or n} elements"
+                           f"{'' if device is None else f' on {device}'}{'' if avoid is None else ', and not `out`'}")
+    return scratch
+
+
 def _slot_launch(prep, labels, B, H, W, device, buf, name, shape, slots, default=True):
     """What every launch into an int64 [n_slots, *shape] buffer does before its `lib.call`, in the caller's device guard: the label side of a [B, H, W]
     map checked, the buffer `name` allocated where none is given (zeroed, max(slots) + 1 slots; `default=False`: an entry without that default) and
@@ -778,11 +795,7 @@ def abstain(pred, conf, bins, min_bin=None, out=None, threshold=None):
     if not _is_int(min_bin, 0, K):
         raise ValueError(f"mmsa.evaluate: min_bin = {min_bin!r}; 0..{K} for {K} bins ({K} abstains everywhere)")
     with torch.cuda.device(pred.device):
-        if out is None:
-            out = torch.empty_like(pred)
-        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != tuple(pred.shape) or out.device != pred.device
-              or not out.is_contiguous()):
-            raise RuntimeError(f"mmsa.evaluate: out must be a contiguous uint8 {tuple(pred.shape)} tensor on {pred.device}")
+        out = torch.empty_like(pred) if out is None else _check_out(out, torch.uint8, pred.shape, pred.device)
         if pred.numel():
             lib.call("mmsa_abstain_u8", pred.data_ptr(), conf.data_ptr(), pred.numel(), K, int(min_bin), out.data_ptr(), ops._stream())
     return out
@@ -1467,27 +1480,72 @@ def code_lut(num_classes=None, prep=None):
     return np.minimum(np.arange(256), C).astype(np.uint8)
 
 
-def _code_lut_on(device, num_classes=None, prep=None):
-    lut = code_lut(num_classes, prep)
-    key = (lut.tobytes(), torch.device(device))
-    t = _CODE_LUTS.get(key)
+def _table_on(cache, table, device, what):
+    """The 256-byte numpy `table` of a launch on `device`: uploaded once per (bytes, device) and kept in `cache`; an upload during a graph capture is refused."""
+    key = (table.tobytes(), torch.device(device))
+    t = cache.get(key)
     if t is None:
         if _capturing(key[1]):
-            raise RuntimeError("mmsa.evaluate: the code LUT of the distance launch is not on the device yet and cannot be uploaded during a graph capture: run "
-                               "one call before capturing")
-        t = _CODE_LUTS[key] = torch.from_numpy(lut).to(key[1])
+            raise RuntimeError(f"mmsa.evaluate: {what} is not on the device yet and cannot be uploaded during a graph capture: run one call before capturing")
+        t = cache[key] = torch.from_numpy(table).to(key[1])
     return t
 
 
-def _distance_scratch(n, device):
+def _cached_planes(cache, n, count, device, what, dtype=torch.int32, instead="the buffers"):
+    """`count` buffers of `dtype` with at least n elements each, kept in `cache` per device and stream; a new allocation during a graph capture is refused
+    (`instead`: what the caller can pass to need none)."""
     key = (torch.device(device), ops._stream())
-    t = _DISTANCE_SCRATCH.get(key)
-    if t is None or t.numel() < n:
+    t = cache.get(key)
+    if t is None or t[0].numel() < n:
         if _capturing(key[0]):
-            raise RuntimeError("mmsa.evaluate: the scratch plane of the distance launch cannot be allocated during a graph capture: pass scratch=, or run one "
-                               "call of this size before capturing")
-        t = _DISTANCE_SCRATCH[key] = torch.empty(n, dtype=torch.uint16, device=key[0])
+            raise RuntimeError(f"mmsa.evaluate: {what} cannot be allocated during a graph capture: pass {instead}, or run one call of this size before "
+                               "capturing")
+        t = cache[key] = [torch.empty(n, dtype=dtype, device=key[0]) for _ in range(count)]
     return t
+
+
+def _row_plane(n, device):
+    """The uint16 plane of the row pass of a distance or a fill launch without scratch=: one buffer for both."""
+    return _cached_planes(_DISTANCE_SCRATCH, n, 1, device, "the scratch plane of the distance launch", torch.uint16, "scratch=")[0]
+
+
+def _code_keywords(who, num_classes, labels_prep, maps="a stored class map"):
+    """num_classes= or labels_prep=, one of them: how an entry named by `who` reads its code map."""
+    if (labels_prep is None) == (num_classes is None):
+        raise ValueError(f"{who} takes num_classes= ({maps}) or labels_prep= (raw labels), one of them")
+
+
+def _code_map_grid(map, labels_prep, size=None, num_classes=None, index32=None):
+    """`map` = the uint8 tensor a code map is read from, [B, Hs, Ws] -> (map, (B, Hs, Ws, H, W)): a stored class map is its own grid, raw labels are read on the
+    grid `labels_prep` resizes them to (`size=` may spell that grid out, nothing else).  Type, dtype, shape and sizes only, so that a bad call is refused without
+    a device; the caller looks at the device next.  `num_classes`: a class count to check here too; `index32`: the name of an entry that indexes in 32 bits."""
+    src = _check_map(map, "map", torch.uint8, "a uint8 class map or raw uint8 labels", shape_only=True)
+    B, Hs, Ws = (int(v) for v in src.shape)
+    if labels_prep is None:
+        if size is not None and tuple(size) != (Hs, Ws):
+            raise RuntimeError(f"mmsa.evaluate: size={tuple(size)} for a stored {Hs} x {Ws} class map: only labels are resized (labels_prep=)")
+        H, W = Hs, Ws
+        if num_classes is not None:
+            code_lut(num_classes)
+    else:
+        H, W = labels_prep.resized(Hs, Ws) if size is None else (int(size[0]), int(size[1]))
+        if labels_prep.resized(Hs, Ws) != (H, W):
+            raise RuntimeError(f"mmsa.evaluate: size mismatch: the label maps are {Hs} x {Ws}, which the LabelPrep reads on a grid of "
+                               f"{labels_prep.resized(Hs, Ws)[0]} x {labels_prep.resized(Hs, Ws)[1]}, not {H} x {W}")
+    if B * H * W == 0:
+        raise RuntimeError(f"mmsa.evaluate: an empty map {tuple(src.shape)}")
+    if index32 is not None and B * H * W >= 1 << 31:
+        raise RuntimeError(f"mmsa.evaluate: {B} x {H} x {W} pixels; {index32} indexes a batch in 32 bits (B * H * W < 2^31)")
+    return src, (B, Hs, Ws, H, W)
+
+
+def _code_map_args(src, grid, num_classes, labels_prep):
+    """The leading arguments of a launch that reads a code map (src, B, Hs, Ws, lut, ymap, xmap, H, W), in the caller's device guard: the LUT and the
+    nearest-neighbour tables are cached on the device, and a first upload during a graph capture is refused."""
+    B, Hs, Ws, H, W = grid
+    lut = _table_on(_CODE_LUTS, code_lut(num_classes, labels_prep), src.device, "the code LUT of the distance launch")
+    ymap, xmap = (None, None) if labels_prep is None else labels_prep.tables(Hs, Ws, H, W, src.device)
+    return (src.data_ptr(), B, Hs, Ws, lut.data_ptr(), None if ymap is None else ymap.data_ptr(), None if xmap is None else xmap.data_ptr(), H, W)
 
 
 @torch.no_grad()
@@ -1502,37 +1560,15 @@ def boundary_distance(map, cap, border=False, *, labels_prep=None, num_classes=N
     `out=` (uint16 [B, H, W]) and `scratch=` (a uint16 tensor of at least B * H * W elements, the row pass's plane) make the call allocation-free; without
     scratch= a buffer cached per device and stream is used, which a repeated call does not allocate again."""
     cap = check_distance_cap(cap)
-    if (labels_prep is None) == (num_classes is None):
-        raise ValueError("mmsa.evaluate: boundary_distance takes num_classes= (a stored class map) or labels_prep= (raw labels), one of them")
-    src = _check_map(map, "map", torch.uint8, "a uint8 class map or raw uint8 labels", shape_only=True)
-    B, Hs, Ws = (int(v) for v in src.shape)
-    if labels_prep is None:
-        if size is not None and tuple(size) != (Hs, Ws):
-            raise RuntimeError(f"mmsa.evaluate: size={tuple(size)} for a stored {Hs} x {Ws} class map: only labels are resized (labels_prep=)")
-        H, W = Hs, Ws
-    else:
-        H, W = labels_prep.resized(Hs, Ws) if size is None else (int(size[0]), int(size[1]))
-        if labels_prep.resized(Hs, Ws) != (H, W):
-            raise RuntimeError(f"mmsa.evaluate: size mismatch: the label maps are {Hs} x {Ws}, which the LabelPrep reads on a grid of "
-                               f"{labels_prep.resized(Hs, Ws)[0]} x {labels_prep.resized(Hs, Ws)[1]}, not {H} x {W}")
-    if B * H * W == 0:
-        raise RuntimeError(f"mmsa.evaluate: an empty map {tuple(src.shape)}")
+    _code_keywords("mmsa.evaluate: boundary_distance", num_classes, labels_prep)
+    src, grid = _code_map_grid(map, labels_prep, size)
+    B, H, W = grid[0], grid[3], grid[4]
     _check_map(src, "map", torch.uint8, "a uint8 class map or raw uint8 labels")
     with torch.cuda.device(src.device):
-        if out is None:
-            out = torch.empty(B, H, W, dtype=torch.uint16, device=src.device)
-        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint16 or tuple(out.shape) != (B, H, W) or out.device != src.device
-              or not out.is_contiguous()):
-            raise RuntimeError(f"mmsa.evaluate: out must be a contiguous uint16 {(B, H, W)} tensor on {src.device}")
-        if scratch is None:
-            scratch = _distance_scratch(B * H * W, src.device)
-        elif (not isinstance(scratch, torch.Tensor) or scratch.dtype != torch.uint16 or scratch.numel() < B * H * W or scratch.device != src.device
-              or not scratch.is_contiguous() or scratch.data_ptr() == out.data_ptr()):
-            raise RuntimeError(f"mmsa.evaluate: scratch must be a contiguous uint16 tensor of at least {B * H * W} elements on {src.device}, and not `out`")
-        lut = _code_lut_on(src.device, num_classes, labels_prep)
-        ymap, xmap = (None, None) if labels_prep is None else labels_prep.tables(Hs, Ws, H, W, src.device)
-        lib.call("mmsa_boundary_distance_u8", src.data_ptr(), B, Hs, Ws, lut.data_ptr(), None if ymap is None else ymap.data_ptr(),
-                 None if xmap is None else xmap.data_ptr(), H, W, cap, 1 if border else 0, scratch.data_ptr(), out.data_ptr(), ops._stream())
+        out = torch.empty(B, H, W, dtype=torch.uint16, device=src.device) if out is None else _check_out(out, torch.uint16, (B, H, W), src.device)
+        scratch = _row_plane(B * H * W, src.device) if scratch is None else _check_scratch(scratch, torch.uint16, B * H * W, src.device, avoid=out)
+        lib.call("mmsa_boundary_distance_u8", *_code_map_args(src, grid, num_classes, labels_prep), cap, 1 if border else 0, scratch.data_ptr(),
+                 out.data_ptr(), ops._stream())
     return out
 
 
@@ -1791,18 +1827,6 @@ def _check_int_plane(t, name, shape, device, what):
     return t
 
 
-def _cached_planes(cache, n, count, device, what):
-    """`count` int32 buffers of at least n elements each, cached per device and stream (the capture refusal of `_distance_scratch`)."""
-    key = (torch.device(device), ops._stream())
-    t = cache.get(key)
-    if t is None or t[0].numel() < n:
-        if _capturing(key[0]):
-            raise RuntimeError(f"mmsa.evaluate: {what} cannot be allocated during a graph capture: pass the buffers, or run one call of this size before "
-                               "capturing")
-        t = cache[key] = [torch.empty(n, dtype=torch.int32, device=key[0]) for _ in range(count)]
-    return t
-
-
 @torch.no_grad()
 def components(map, *, num_classes=None, labels_prep=None, size=None, connectivity=8, out=None):
     """The connected components of a code map (up to three launches, mmsa_components_u8) -> int32 [B, H, W] on the device: root[b, y, x] = the smallest linear
@@ -1814,34 +1838,16 @@ def components(map, *, num_classes=None, labels_prep=None, size=None, connectivi
                         nearest-neighbour tables of the label side.
     B * H * W < 2^31.  `out=` (int32 [B, H, W]) makes the call allocation-free: the launches work in it and need no scratch."""
     connectivity = check_connectivity(connectivity)
-    if (labels_prep is None) == (num_classes is None):
-        raise ValueError("mmsa.evaluate: components takes num_classes= (a stored class map) or labels_prep= (raw labels), one of them")
-    src = _check_map(map, "map", torch.uint8, "a uint8 class map or raw uint8 labels", shape_only=True)
-    B, Hs, Ws = (int(v) for v in src.shape)
-    if labels_prep is None:
-        if size is not None and tuple(size) != (Hs, Ws):
-            raise RuntimeError(f"mmsa.evaluate: size={tuple(size)} for a stored {Hs} x {Ws} class map: only labels are resized (labels_prep=)")
-        H, W = Hs, Ws
-        code_lut(num_classes)      # the class count checked before the device is looked at
-    else:
-        H, W = labels_prep.resized(Hs, Ws) if size is None else (int(size[0]), int(size[1]))
-        if labels_prep.resized(Hs, Ws) != (H, W):
-            raise RuntimeError(f"mmsa.evaluate: size mismatch: the label maps are {Hs} x {Ws}, which the LabelPrep reads on a grid of "
-                               f"{labels_prep.resized(Hs, Ws)[0]} x {labels_prep.resized(Hs, Ws)[1]}, not {H} x {W}")
-    if B * H * W == 0:
-        raise RuntimeError(f"mmsa.evaluate: an empty map {tuple(src.shape)}")
-    if B * H * W >= 1 << 31:
-        raise RuntimeError(f"mmsa.evaluate: {B} x {H} x {W} pixels; components indexes a batch in 32 bits (B * H * W < 2^31)")
+    _code_keywords("mmsa.evaluate: components", num_classes, labels_prep)
+    src, grid = _code_map_grid(map, labels_prep, size, num_classes, index32="components")      # the class count too: before the device is looked at
+    B, H, W = grid[0], grid[3], grid[4]
     _check_map(src, "map", torch.uint8, "a uint8 class map or raw uint8 labels")
     with torch.cuda.device(src.device):
         if out is None:
             out = torch.empty(B, H, W, dtype=torch.int32, device=src.device)
         else:
             _check_int_plane(out, "out", (B, H, W), src.device, "the root map")
-        lut = _code_lut_on(src.device, num_classes, labels_prep)
-        ymap, xmap = (None, None) if labels_prep is None else labels_prep.tables(Hs, Ws, H, W, src.device)
-        lib.call("mmsa_components_u8", src.data_ptr(), B, Hs, Ws, lut.data_ptr(), None if ymap is None else ymap.data_ptr(),
-                 None if xmap is None else xmap.data_ptr(), H, W, connectivity, out.data_ptr(), ops._stream())
+        lib.call("mmsa_components_u8", *_code_map_args(src, grid, num_classes, labels_prep), connectivity, out.data_ptr(), ops._stream())
     return out
 
 
@@ -1933,9 +1939,8 @@ def segment_counts(pred, labels, prep, root_pred, root_label, bins=DEFAULT_SEGME
     with torch.cuda.device(pred.device):
         if scratch is None:
             scratch = _cached_planes(_SEGMENT_SCRATCH, n, 1, pred.device, "the scratch planes of segment_counts")[0]
-        elif (not isinstance(scratch, torch.Tensor) or scratch.dtype != torch.int32 or scratch.numel() < n or scratch.device != pred.device
-              or not scratch.is_contiguous()):
-            raise RuntimeError(f"mmsa.evaluate: scratch must be a contiguous int32 tensor of at least 4 * B * H * W = {n} elements on {pred.device}")
+        else:
+            _check_scratch(scratch, torch.int32, n, pred.device, count=f"4 * B * H * W = {n}")
         largs, counts, tab = _slot_launch(prep, labels, B, H, W, pred.device, counts, "counts", (2, C, SIZE_BUCKETS, bins + 1), slots)
         lib.call("mmsa_eval_segments", pred.data_ptr(), largs[0], B, H, W, largs[1], largs[2], largs[3], C, largs[4], largs[5], tab, counts.shape[0],
                  root_pred.data_ptr(), root_label.data_ptr(), bins, scratch.data_ptr(), counts.data_ptr(), ops._stream())
@@ -2520,8 +2525,7 @@ class SegmentTable:
         self.run_order = None if runs is None else check_run_order(runs, who)
         self._run_capacity = None if run_capacity is None else check_run_capacity(run_capacity, who)
         self.runs = None         # the RunTable of `ids` of the last update (runs= given)
-        if (labels_prep is None) == (num_classes is None):
-            raise ValueError(f"{who}: takes num_classes= (stored class maps) or labels_prep= (raw labels), one of them")
+        _code_keywords(f"{who}:", num_classes, labels_prep, "stored class maps")
         if labels_prep is None:
             code_lut(num_classes)
         self.num_classes = int(num_classes) if labels_prep is None else int(labels_prep.num_classes)
@@ -2569,19 +2573,14 @@ class SegmentTable:
         """Fill the table from a batch of maps (the component launches unless `root=` brings the root map `components` made of this map at this connectivity,
         the area launch where min_area > 1, one memset and four launches of mmsa_segment_table) -> self.  `values` (float32 [B, H, W] on the grid of the code
         map: a confidence, margin or entropy map, or a probs[r] plane) fills SUM_Q; without it SUM_Q is 0 and every score NaN."""
-        src = _check_map(map, "map", torch.uint8, "a uint8 class map or raw uint8 labels", shape_only=True)
-        B, Hs, Ws = (int(v) for v in src.shape)
-        H, W = (Hs, Ws) if self.labels_prep is None else self.labels_prep.resized(Hs, Ws)
-        if B * H * W == 0:
-            raise RuntimeError(f"mmsa.evaluate: an empty map {tuple(src.shape)}")
-        if B * H * W >= 1 << 31:
-            raise RuntimeError(f"mmsa.evaluate: {B} x {H} x {W} pixels; a segment table indexes a batch in 32 bits (B * H * W < 2^31)")
-        grid = torch.Size((B, H, W))
+        num_classes = None if self.labels_prep is not None else self.num_classes
+        src, grid = _code_map_grid(map, self.labels_prep, index32="a segment table")
+        B, H, W = grid[0], grid[3], grid[4]
         if root is not None:
-            _check_int_plane(root, "root", grid, None, "the root map of mmsa.components")
+            _check_int_plane(root, "root", (B, H, W), None, "the root map of mmsa.components")
         if values is not None:
-            if not isinstance(values, torch.Tensor) or values.dtype != torch.float32 or tuple(values.shape) != tuple(grid) or not values.is_contiguous():
-                raise RuntimeError(f"mmsa.evaluate: values must be a contiguous float32 {tuple(grid)} tensor (a confidence, margin or entropy map, or a probs plane)")
+            if not isinstance(values, torch.Tensor) or values.dtype != torch.float32 or tuple(values.shape) != (B, H, W) or not values.is_contiguous():
+                raise RuntimeError(f"mmsa.evaluate: values must be a contiguous float32 {(B, H, W)} tensor (a confidence, margin or entropy map, or a probs plane)")
         _check_map(src, "map", torch.uint8, "a uint8 class map or raw uint8 labels")
         for name, t in (("root", root), ("values", values)):
             if t is not None and t.device != src.device:
@@ -2589,17 +2588,14 @@ class SegmentTable:
         with torch.cuda.device(src.device):
             m = self._maps_for(B, H, W, src.device)
             if root is None:
-                root = components(src, num_classes=None if self.labels_prep is not None else self.num_classes, labels_prep=self.labels_prep, size=(H, W),
-                                  connectivity=self.connectivity, out=m["root"])
+                root = components(src, num_classes=num_classes, labels_prep=self.labels_prep, size=(H, W), connectivity=self.connectivity, out=m["root"])
             if self.min_area > 1:
                 component_areas(root, out=m["area"])
-            lut = _code_lut_on(src.device, None if self.labels_prep is not None else self.num_classes, self.labels_prep)
-            ymap, xmap = (None, None) if self.labels_prep is None else self.labels_prep.tables(Hs, Ws, H, W, src.device)
             capacity = m["records"].shape[1]
-            lib.call("mmsa_segment_table", src.data_ptr(), B, Hs, Ws, lut.data_ptr(), None if ymap is None else ymap.data_ptr(),
-                     None if xmap is None else xmap.data_ptr(), H, W, root.data_ptr(), None if m["area"] is None else m["area"].data_ptr(),
-                     None if values is None else values.data_ptr(), self.min_area, 256 if self.void else self.num_classes, capacity, m["count"].data_ptr(),
-                     m["ids"].data_ptr(), m["records"].data_ptr(), m["scratch"].data_ptr(), ops._stream())
+            lib.call("mmsa_segment_table", *_code_map_args(src, grid, num_classes, self.labels_prep), root.data_ptr(),
+                     None if m["area"] is None else m["area"].data_ptr(), None if values is None else values.data_ptr(), self.min_area,
+                     256 if self.void else self.num_classes, capacity, m["count"].data_ptr(), m["ids"].data_ptr(), m["records"].data_ptr(),
+                     m["scratch"].data_ptr(), ops._stream())
             if m["runs"] is not None:
                 run_lengths(m["ids"], table=m["runs"])
         self.count, self.records, self.ids, self.root, self.runs = m["count"], m["records"], m["ids"], root, m["runs"]
@@ -2765,17 +2761,6 @@ def fill_roles(hole=255, inert=()):
     return roles
 
 
-def _fill_roles_on(device, roles):
-    key = (roles.tobytes(), torch.device(device))
-    t = _FILL_ROLES.get(key)
-    if t is None:
-        if _capturing(key[1]):
-            raise RuntimeError("mmsa.evaluate: the role table of the fill launch is not on the device yet and cannot be uploaded during a graph capture: run one "
-                               "call before capturing")
-        t = _FILL_ROLES[key] = torch.from_numpy(roles).to(key[1])
-    return t
-
-
 @torch.no_grad()
 def fill_nearest(map, hole=255, inert=(), cap=32, out=None, d2=None, scratch=None):
     """The map with its holes filled from the nearest kept pixel (two launches, mmsa_fill_nearest_u8) -> uint8 [B, H, W] on the device.  A pixel whose byte is
@@ -2797,8 +2782,7 @@ def fill_nearest(map, hole=255, inert=(), cap=32, out=None, d2=None, scratch=Non
     if d2 is not None:
         _check_map(d2, "d2", torch.uint16, "a uint16 distance map", like=src, shape_only=True)
     if scratch is not None:
-        if not isinstance(scratch, torch.Tensor) or scratch.dtype != torch.uint16 or scratch.numel() < B * H * W or not scratch.is_contiguous():
-            raise RuntimeError(f"mmsa.evaluate: scratch must be a contiguous uint16 tensor of at least {B * H * W} elements")
+        _check_scratch(scratch, torch.uint16, B * H * W)
         if scratch is d2:
             raise RuntimeError("mmsa.evaluate: scratch and d2 are two planes")
     _check_map(src, "map", torch.uint8, "a uint8 class map")
@@ -2810,12 +2794,12 @@ def fill_nearest(map, hole=255, inert=(), cap=32, out=None, d2=None, scratch=Non
         if d2 is not None:
             _check_map(d2, "d2", torch.uint16, "a uint16 distance map", like=src)
         if scratch is None:
-            scratch = _distance_scratch(B * H * W, src.device)
+            scratch = _row_plane(B * H * W, src.device)
         elif scratch.device != src.device:
             raise RuntimeError(f"mmsa.evaluate: scratch is on {scratch.device}, the map on {src.device}")
         if d2 is not None and scratch.data_ptr() == d2.data_ptr():
             raise RuntimeError("mmsa.evaluate: scratch and d2 are two planes")
-        role = _fill_roles_on(src.device, roles)
+        role = _table_on(_FILL_ROLES, roles, src.device, "the role table of the fill launch")
         lib.call("mmsa_fill_nearest_u8", src.data_ptr(), B, H, W, role.data_ptr(), int(np.flatnonzero(roles == FILL_HOLE)[0]), cap, scratch.data_ptr(),
                  out.data_ptr(), None if d2 is None else d2.data_ptr(), ops._stream())
     return out

@@ -82,6 +82,17 @@ def test_rows_on_both_sides_of_one_pixel_per_lane(H, W):
         _check(_codes(H, W), cap)
 
 
+@pytest.mark.parametrize("W,x", [(256, 255), (512, 1), (512, 511)])
+def test_a_row_with_one_change_at_an_end_of_the_scan(W, x):
+    """The scan over the lanes of a row (csrc/row_scan.h) with ONE marked index in the whole row, every other row without any: the change in the last piece of
+    the last wave (one pixel per lane at 256 columns, two at 512) and in the first piece of the first wave (a change is at x >= 1: two pixels per lane)."""
+    code = np.zeros((2, 5, W), dtype=np.uint8)
+    code[0, 2, x:] = 9                                                # the only change of image 0: at x of row 2
+    code[1, 4, :x] = 9                                                # and of image 1: at x of row 4
+    for cap in (3, 255):
+        _check(code, cap, (W, x))
+
+
 def test_a_cap_larger_than_the_image():
     _check(_codes(9, 70), 255)
     _check(_codes(9, 70), 100)

@@ -50,6 +50,15 @@ def test_every_case_equals_the_restatement(name):
     _run(FR.maps_of(name), FR.CASE[name].cap, name, want=FR.want_of(name))
 
 
+@pytest.mark.parametrize("W,x", [(256, 0), (256, 255), (512, 0), (512, 511)])
+def test_a_row_with_one_source_at_an_end_of_the_scan(W, x):
+    """The scan over the lanes of a row (csrc/row_scan.h) with ONE marked index in the whole row, every other row without any: the source in the first piece
+    of the first wave and in the last piece of the last wave (one pixel per lane at 256 columns, two at 512); image 1 has it at the other end."""
+    maps = np.stack([FR.one_source(5, W, 2, x), FR.one_source(5, W, 0, W - 1 - x, value=3)])
+    for cap in (3, 255):
+        _run(maps, cap, (W, x, cap))
+
+
 def test_no_hole_copies_and_all_holes_stay():
     for H, W in ((1, 1), (5, 70), (67, 131)):
         out, d2 = _run(FR.maps_of(f"stack {H}x{W} cap 255"), 255, (H, W), want=FR.want_of(f"stack {H}x{W} cap 255"))
