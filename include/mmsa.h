@@ -725,6 +725,23 @@ int mmsa_run_decode_i32(const int* count, const int* starts, const int* values, 
 int mmsa_fill_nearest_u8(const unsigned char* src, int B, int H, int W, const unsigned char* role, int none_byte, int cap, unsigned short* scratch,
                          unsigned char* out, unsigned short* d2, mmsa_stream_t stream);
 
+/* --- majority (mode) filter (csrc/majority.hip): every target pixel of a byte map takes the most frequent voter value of its (2 r + 1) x (2 r + 1) window.
+ *   src uint8 [B, H, W] contiguous; role: DEVICE uint8 [256], the role of every byte: 0 = voter (votes with its value and may be rewritten), 1 = hole (votes
+ *   nothing and is to be rewritten), 2 = inert (votes nothing, is never rewritten and blocks nothing).  1 <= radius r <= 32; all, half: 0 or 1.
+ *     Votes.  The window of a pixel p of image b is the set of pixels q of the SAME image with |qy - py| <= r and |qx - px| <= r, clipped at the image border:
+ *     there is no padding, a window at a corner simply holds fewer pixels.  n_v(p) = the number of voter pixels of value v in the window, T(p) = sum_v n_v(p),
+ *     n_best(p) = max_v n_v(p).
+ *     Winner.  w(p) = p's own value if p is a voter and n_own(p) = n_best(p) -- a tie never changes a pixel that is among the tied; otherwise the smallest v
+ *     with n_v(p) = n_best(p).
+ *     Targets.  Every hole pixel; with all = 1 every voter pixel as well; never an inert pixel.
+ *     Result.  out[p] = w(p) iff p is a target AND T(p) > 0 AND (half = 0 OR 2 n_best(p) > T(p), strict); otherwise out[p] = src[p].
+ *     support (uint16 [B, H, W], or NULL: not written) = n_best(p) at every target pixel, whether or not the half rule let it change, 0 at every other pixel;
+ *     the largest value is 65^2 = 4225.  Images of a batch never see each other.  Integers only: the same bytes on every run.
+ *   out must not be src (a stencil cannot run in place), and support is a separate buffer from both.  H * W < 2^31.  ONE launch; every loop is bounded by the
+ *   tile, by the radius or by 256 values.  A limit broken or a null pointer: MMSA_ERR_ARG with a message, before any launch. --- */
+int mmsa_majority_filter_u8(const unsigned char* src, int B, int H, int W, const unsigned char* role, int radius, int all, int half,
+                            unsigned char* out, unsigned short* support, mmsa_stream_t stream);
+
 /* --- the picture of a prediction (segmentation/mmseg_custom/apis/test_bs.py:257-349, the `--show` / `--show-dir` output): `tensor2imgs` (test_bs.py:18-63) on
  *     planes 0..2 of the input tensor -> the crop `img[:h, :w]` (test_bs.py:275-276) -> `show_result` (tools/color_gt_according_palette.py:23-81:
  *     color_seg[seg == label] = color, channels reversed, img * (1 - opacity) + color_seg * opacity, .astype(uint8)), in one pass.

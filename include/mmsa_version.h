@@ -38,7 +38,9 @@
  *      class map or an ids map in row-major or column-major order -- starts and values in ascending order by a device-wide prefix sum over the run heads --
  *      and the map of such a table).
  *      Still 114, for the same reason: new entry mmsa_fill_nearest_u8 (the holes of a byte map filled with the value of the nearest source pixel within a cap
- *      of up to 255 pixels, ties to the topmost and then the leftmost, and the squared distance taken). */
+ *      of up to 255 pixels, ties to the topmost and then the leftmost, and the squared distance taken).
+ *      Still 114, for the same reason: new entry mmsa_majority_filter_u8 (the majority filter of a byte map: every target pixel takes the most frequent voter
+ *      value of its (2 r + 1) x (2 r + 1) window, ties kept by the own value or else resolved to the smallest, and the count that won). */
 #ifndef MMSA_VERSION_H
 #define MMSA_VERSION_H
 #define MMSA_ABI_VERSION 114

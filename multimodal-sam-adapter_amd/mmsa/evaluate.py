@@ -63,7 +63,11 @@ float64 on the host.
 
 `suppress_small`, `select_segments` and `abstain` paint what they remove with one byte.  `fill_nearest` hands such a map back full: every hole takes the value
 of the nearest kept pixel of its image within a cap of up to 255 pixels, ties to the topmost and then the leftmost (mmsa_fill_nearest_u8, csrc/fill.hip: the
-two launches of `boundary_distance` with a value carried along); `suppress_small(…, nearest=cap)` and `select_segments(…, nearest=cap)` end with it."""
+two launches of `boundary_distance` with a value carried along); `suppress_small(…, nearest=cap)` and `select_segments(…, nearest=cap)` end with it.
+
+`majority_filter` is the mode filter of a class map: every target pixel takes the most frequent voter value of its (2 r + 1)^2 window, r <= 32, a tie kept by
+the own value or else resolved to the smallest (mmsa_majority_filter_u8, csrc/majority.hip: one launch, per value present in a tile the rows as ballot masks,
+popcounts and a sliding column sum).  It removes salt-and-pepper pixels, straightens contours and, with `where="holes"`, fills holes by vote."""
 import ctypes
 import math
 import warnings
@@ -2814,6 +2818,96 @@ def _check_nearest(nearest, fill, num_classes, who):
         raise ValueError(f"{who}: fill = {fill} with nearest=: the byte is one of the {num_classes} classes, and a class byte would be a hole and a source at once; "
                          f"paint with a byte from {num_classes} on")
     return nearest
+
+
+# ---- majority filter: every target pixel takes the most frequent class of its window (csrc/majority.hip) ----
+MAJORITY_VOTER, MAJORITY_HOLE, MAJORITY_INERT = 0, 1, 2      # the roles of csrc/majority.hip's table
+MAX_MAJORITY_RADIUS = 32           # csrc/majority.hip MAJ_MAX_RADIUS: a staged row of 64 + 2 r columns is two 64-bit masks
+MAJORITY_WHERE = ("holes", "all")  # the library's all = 0, 1
+_MAJORITY_ROLES = {}               # (roles, device) -> the device role table of a majority launch
+
+
+def check_majority_radius(radius, who="mmsa.evaluate"):
+    if not _is_int(radius, 1, MAX_MAJORITY_RADIUS):
+        raise ValueError(f"{who}: radius = {radius!r}; an int in 1..{MAX_MAJORITY_RADIUS} is expected (the window is (2 r + 1) x (2 r + 1) pixels)")
+    return int(radius)
+
+
+def majority_roles(num_classes=None, hole=(), inert=None):
+    """The 256-byte role table of a majority launch, uint8 numpy [256]: 1 at the bytes of `hole` (vote nothing, are rewritten), 2 at the bytes of `inert` (vote
+    nothing, are kept), 0 at the voters.  With `num_classes=C` the voters are the bytes < C, and every byte >= C that is no hole is inert (the 255 of an
+    uncovered or ignored pixel stays and votes nothing); without it every byte in neither list votes.  `hole` and `inert` are a byte or a list of bytes,
+    disjoint, and no hole byte is a class."""
+    holes, inerts = _fill_bytes(hole, "hole"), _fill_bytes(() if inert is None else inert, "inert")
+    both = sorted(set(holes) & set(inerts))
+    if both:
+        raise ValueError(f"mmsa.evaluate: hole and inert share the bytes {both}; a byte is rewritten or kept")
+    roles = np.zeros(256, dtype=np.uint8)
+    if num_classes is not None:
+        if not _is_int(num_classes, 1, 256):
+            raise ValueError(f"mmsa.evaluate: num_classes = {num_classes!r}; a uint8 class map has 1..256 classes")
+        low = [b for b in holes if b < int(num_classes)]
+        if low:
+            raise ValueError(f"mmsa.evaluate: hole holds the bytes {low}, which are among the {int(num_classes)} classes; a class byte votes, a hole byte "
+                             f"does not: paint holes with a byte from {int(num_classes)} on")
+        roles[int(num_classes):] = MAJORITY_INERT
+    roles[list(holes)] = MAJORITY_HOLE
+    roles[list(inerts)] = MAJORITY_INERT
+    return roles
+
+
+@torch.no_grad()
+def majority_filter(map, radius=1, *, num_classes=None, hole=(), inert=None, where="all", half=False, out=None, support=None):
+    """The majority (mode) filter of a class map (one launch, mmsa_majority_filter_u8) -> uint8 [B, H, W] on the device.  Every TARGET pixel takes the most
+    frequent VOTER value of its (2 radius + 1)^2 window, 1 <= radius <= 32; the window is clipped at the image border (no padding), and images of a batch never
+    see each other.  A tie never changes a pixel whose own value is among the tied; otherwise the smallest of the tied values wins.  Integers only: the same
+    bytes on every run.
+    Roles: with `num_classes=C` the bytes < C vote, and every byte >= C that is not in `hole` is inert -- it votes nothing and is never rewritten, so the 255
+    of an uncovered or ignored pixel stays; without `num_classes` every byte in neither list votes, as in `fill_nearest`.  The bytes of `hole` vote nothing and
+    are rewritten (a hole whose window holds no voter stays); `inert=` adds bytes that are kept.  `where="all"` rewrites voters and holes, `where="holes"` the
+    holes alone (the other natural fill: by the vote of everything near, where `fill_nearest` takes the single nearest pixel).  `half=True`: a pixel changes only
+    where one value holds MORE than half of the votes of its window.
+        smooth = mmsa.majority_filter(pred, 2, num_classes=C)                                   # 5 x 5 mode filter; 255 stays void
+        stable = mmsa.majority_filter(pred, 1, num_classes=C, half=True)                        # only where one class holds more than half of the votes
+        closed = mmsa.majority_filter(mmsa.suppress_small(pred, 64, num_classes=C, fill=254), 3,
+                                      num_classes=C, hole=254, where="holes")                   # specks take the vote of what surrounds them
+    `out=` (uint8, the map's shape, NOT the map: a stencil cannot run in place); `support=` (uint16, the map's shape) receives the winning count n_best at
+    every target pixel, whether or not `half` let it change, and 0 elsewhere.  The role table is uploaded once per (roles, device); with `out=` (and
+    `support=`) a later call allocates nothing and can be captured in a graph."""
+    radius = check_majority_radius(radius)
+    roles = majority_roles(num_classes, hole, inert)
+    if where not in MAJORITY_WHERE:
+        raise ValueError(f"mmsa.evaluate: where = {where!r}; \"all\" (voters and holes are rewritten) or \"holes\" is expected")
+    if where == "holes" and not (roles == MAJORITY_HOLE).any():
+        raise ValueError("mmsa.evaluate: where = \"holes\" and hole is empty; at least one byte to rewrite is expected")
+    if not isinstance(half, (bool, np.bool_)):
+        raise ValueError(f"mmsa.evaluate: half = {half!r}; True or False is expected")
+    src = _check_map(map, "map", torch.uint8, "a uint8 class map", shape_only=True)
+    B, H, W = (int(v) for v in src.shape)
+    if B * H * W == 0:
+        raise RuntimeError(f"mmsa.evaluate: an empty map {tuple(src.shape)}")
+    if out is not None:
+        _check_map(out, "out", torch.uint8, "a uint8 class map", like=src, shape_only=True)
+        if out is map:
+            raise RuntimeError("mmsa.evaluate: out is the map; a stencil cannot run in place")
+    if support is not None:
+        _check_map(support, "support", torch.uint16, "a uint16 count map", like=src, shape_only=True)
+    _check_map(src, "map", torch.uint8, "a uint8 class map")
+    with torch.cuda.device(src.device):
+        if out is None:
+            out = torch.empty_like(src)
+        else:
+            _check_map(out, "out", torch.uint8, "a uint8 class map", like=src)
+            if out.data_ptr() == src.data_ptr():
+                raise RuntimeError("mmsa.evaluate: out is the map; a stencil cannot run in place")
+        if support is not None:
+            _check_map(support, "support", torch.uint16, "a uint16 count map", like=src)
+            if support.data_ptr() in (src.data_ptr(), out.data_ptr()):
+                raise RuntimeError("mmsa.evaluate: support aliases a map; it is a plane of its own")
+        role = _table_on(_MAJORITY_ROLES, roles, src.device, "the role table of the majority launch")
+        lib.call("mmsa_majority_filter_u8", src.data_ptr(), B, H, W, role.data_ptr(), radius, MAJORITY_WHERE.index(where), int(bool(half)), out.data_ptr(),
+                 None if support is None else support.data_ptr(), ops._stream())
+    return out
 
 
 # ---- run-length tables: the runs of a class map or an ids map, and the COCO RLE of one id (csrc/runs.hip; DESIGN.md section 2) ----
