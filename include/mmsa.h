@@ -742,6 +742,29 @@ int mmsa_fill_nearest_u8(const unsigned char* src, int B, int H, int W, const un
 int mmsa_majority_filter_u8(const unsigned char* src, int B, int H, int W, const unsigned char* role, int radius, int all, int half,
                             unsigned char* out, unsigned short* support, mmsa_stream_t stream);
 
+/* --- guided vote filter (csrc/vote.hip): the joint-bilateral weighted mode filter of a byte map.  Every voter of the (2 r + 1) x (2 r + 1) window of a pixel
+ *   votes for its value with a weight that falls with the difference of its guide pixel from the centre's and rises with its own confidence.
+ *   src, role, all, half: as mmsa_majority_filter_u8 (roles 0 = voter, 1 = hole, 2 = inert; the window is clipped at the image border, there is no padding;
+ *   targets are every hole and, with all = 1, every voter, never an inert pixel).  1 <= radius r <= 16.
+ *   guide: uint8 [B, Hg, Wg, G] contiguous, G = 1 or 3, Hg >= H, Wg >= W, of which the top-left H x W is used (a padded raw frame needs no copy), with
+ *     range_lut: DEVICE uint16 [255 G + 1], every entry in 0 .. 4096; or both NULL (G, Hg, Wg are not looked at then).  weight: float32 [B, H, W], or NULL.
+ *     Votes.  d(p, q) = sum_c |g_p[c] - g_q[c]|, the L1 distance of two guide pixels, 0 .. 255 G.  wq(q) = min(255, (int)(clamp(weight[q]) * 256.0f)) with
+ *     the clamp of the calibration bins (NaN, negatives and -0.0 -> 0, above 1 -> 1): NaN, negatives and anything below 1 / 256 vote nothing; wq = 1 without
+ *     weight.  S_v(p) = sum of range_lut[d(p, q)] * wq(q) over the voter pixels q of value v in the window (range_lut = 1 without a guide),
+ *     T(p) = sum_v S_v(p), S_best(p) = max_v S_v(p).  A tap adds at most 4096 * 255 < 2^20 and a window holds at most 33^2 = 1089 < 2^11 taps, so
+ *     T <= 1 137 438 720 < 2^31: the uint32 sums are exact.
+ *     Winner.  w(p) = p's own value if p is a voter and S_own(p) = S_best(p); otherwise the smallest v with S_v(p) = S_best(p).
+ *     Result.  out[p] = w(p) iff p is a target AND T(p) > 0 AND (half = 0 OR 2 S_best(p) > T(p), strict); otherwise out[p] = src[p].  T = 0 can happen with
+ *     voters in the window: zeros in the table, zero weights.
+ *     support (uint32 [B, H, W], or NULL: not written) = S_best(p) at every target pixel, 0 at every other pixel.
+ *     With neither guide nor weight, or with a table of ones, out and support are mmsa_majority_filter_u8's.  Images of a batch never see each other.
+ *     Integers only: the same bytes on every run.
+ *   out must not be src, and out and support are separate buffers from every input.  H * W < 2^31.  ONE launch; every loop is bounded by the tile, by the
+ *   radius or by 256 values.  A limit broken or a null pointer: MMSA_ERR_ARG with a message, before any launch. --- */
+int mmsa_vote_filter_u8(const unsigned char* src, int B, int H, int W, const unsigned char* role, int radius, int all, int half,
+                        const unsigned char* guide, int Hg, int Wg, int G, const unsigned short* range_lut, const float* weight,
+                        unsigned char* out, unsigned* support, mmsa_stream_t stream);
+
 /* --- the picture of a prediction (segmentation/mmseg_custom/apis/test_bs.py:257-349, the `--show` / `--show-dir` output): `tensor2imgs` (test_bs.py:18-63) on
  *     planes 0..2 of the input tensor -> the crop `img[:h, :w]` (test_bs.py:275-276) -> `show_result` (tools/color_gt_according_palette.py:23-81:
  *     color_seg[seg == label] = color, channels reversed, img * (1 - opacity) + color_seg * opacity, .astype(uint8)), in one pass.

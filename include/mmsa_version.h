@@ -40,7 +40,9 @@
  *      Still 114, for the same reason: new entry mmsa_fill_nearest_u8 (the holes of a byte map filled with the value of the nearest source pixel within a cap
  *      of up to 255 pixels, ties to the topmost and then the leftmost, and the squared distance taken).
  *      Still 114, for the same reason: new entry mmsa_majority_filter_u8 (the majority filter of a byte map: every target pixel takes the most frequent voter
- *      value of its (2 r + 1) x (2 r + 1) window, ties kept by the own value or else resolved to the smallest, and the count that won). */
+ *      value of its (2 r + 1) x (2 r + 1) window, ties kept by the own value or else resolved to the smallest, and the count that won).
+ *      Still 114, for the same reason: new entry mmsa_vote_filter_u8 (the guided vote filter of a byte map: the majority filter with every vote weighted by a
+ *      range table of the guide frame's L1 difference and by the voter's quantised confidence, and the sum that won). */
 #ifndef MMSA_VERSION_H
 #define MMSA_VERSION_H
 #define MMSA_ABI_VERSION 114

@@ -33,6 +33,7 @@ from .evaluate import (RunTable, run_lengths, run_decode, runs_of_value, coco_rl
 #                                                            map or an ids map, row-major or column-major, and the uncompressed COCO RLE of one id or class)
 from .evaluate import fill_nearest  # noqa: F401  (the holes of a class map filled from the nearest kept pixel: what suppress_small / select_segments / abstain removed)
 from .evaluate import majority_filter  # noqa: F401  (the majority filter of a class map: every target pixel takes the most frequent class of its window)
+from .evaluate import vote_filter  # noqa: F401  (the guided vote filter: the majority filter with votes weighted by a guide frame and by the confidence)
 from . import render  # noqa: F401  (the picture of a prediction on device: palette map over the frame, show_result)
 from .render import Renderer
 from .registry import BACKBONES, HEADS, build_backbone, build_head
@@ -64,4 +65,4 @@ __all__ = ["SegformerHead", "HEADS", "build_head", "register_head", "SAMAdapterb
            "boundary_distance_percentile_of", "SegmentEvaluator", "components", "component_areas", "suppress_small", "segment_counts", "segment_totals_of",
            "segment_rate_of", "segment_f_of", "PanopticEvaluator", "PairTable", "segment_pairs", "panoptic_counts", "panoptic_quality_of",
            "panoptic_summary_of", "SegmentTable", "segment_table", "select_segments", "segment_records_of", "RunTable", "run_lengths",
-           "run_decode", "runs_of_value", "coco_rle_of", "rle_area_of", "rle_bbox_of", "fill_nearest", "majority_filter"]
+           "run_decode", "runs_of_value", "coco_rle_of", "rle_area_of", "rle_bbox_of", "fill_nearest", "majority_filter", "vote_filter"]

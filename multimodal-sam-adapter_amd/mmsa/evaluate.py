@@ -67,7 +67,11 @@ two launches of `boundary_distance` with a value carried along); `suppress_small
 
 `majority_filter` is the mode filter of a class map: every target pixel takes the most frequent voter value of its (2 r + 1)^2 window, r <= 32, a tie kept by
 the own value or else resolved to the smallest (mmsa_majority_filter_u8, csrc/majority.hip: one launch, per value present in a tile the rows as ballot masks,
-popcounts and a sliding column sum).  It removes salt-and-pepper pixels, straightens contours and, with `where="holes"`, fills holes by vote."""
+popcounts and a sliding column sum).  It removes salt-and-pepper pixels, straightens contours and, with `where="holes"`, fills holes by vote.
+
+`vote_filter` is the same filter with weighted votes, r <= 16: a voter's vote falls with the L1 difference of its pixel of a guide frame (raw uint8, 1 or 3
+channels) from the centre's, through a range table (`vote_range_table`, or one of the caller's), and rises with its quantised confidence; the largest integer
+sum wins (mmsa_vote_filter_u8, csrc/vote.hip: one launch, a per-lane column of sums in LDS over dense value slots).  Contours snap to the guide's edges."""
 import ctypes
 import math
 import warnings
@@ -2907,6 +2911,128 @@ def majority_filter(map, radius=1, *, num_classes=None, hole=(), inert=None, whe
         role = _table_on(_MAJORITY_ROLES, roles, src.device, "the role table of the majority launch")
         lib.call("mmsa_majority_filter_u8", src.data_ptr(), B, H, W, role.data_ptr(), radius, MAJORITY_WHERE.index(where), int(bool(half)), out.data_ptr(),
                  None if support is None else support.data_ptr(), ops._stream())
+    return out
+
+
+# ---- guided vote filter: the majority filter with every vote weighted by the guide frame and by the voter's confidence (csrc/vote.hip) ----
+MAX_VOTE_RADIUS = 16               # csrc/vote.hip VOTE_MAX_RADIUS: a lane walks every tap of the window
+MAX_RANGE_WEIGHT = 4096            # the largest entry of a range table: 4096 * 255 per tap, 33^2 taps, stays below 2^31
+_VOTE_TABLES = {}                  # (bytes, device) -> the device role table or range table of a vote launch
+
+
+def vote_range_table(sigma, channels=3):
+    """The Gaussian range table of `vote_filter`, uint16 numpy [255 * channels + 1]: entry d = floor(256 * exp(-d^2 / (2 sigma^2)) + 0.5), formed in float64
+    on the host; d is the L1 distance of two guide pixels.  Entry 0 is 256, and the table never rises."""
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float, np.integer, np.floating)) or not (float(sigma) > 0 and math.isfinite(float(sigma))):
+        raise ValueError(f"mmsa.evaluate: sigma = {sigma!r}; a finite float > 0 is expected (in units of the guide's L1 difference)")
+    if not _is_int(channels, 1, 3) or int(channels) == 2:
+        raise ValueError(f"mmsa.evaluate: channels = {channels!r}; a guide has 1 or 3 channels")
+    d = np.arange(255 * int(channels) + 1, dtype=np.float64)
+    return np.floor(256.0 * np.exp(-(d * d) / (2.0 * float(sigma) * float(sigma))) + 0.5).astype(np.uint16)
+
+
+def _check_range_weights(table, channels):
+    """range_weights= -> uint16 numpy [255 * channels + 1] with every entry in 0 .. 4096."""
+    try:
+        t = np.asarray(table.cpu() if isinstance(table, torch.Tensor) else table)
+    except Exception:
+        t = None
+    n = 255 * channels + 1
+    if t is None or t.dtype == object or t.dtype.kind not in "iuf" or t.ndim != 1:
+        raise ValueError(f"mmsa.evaluate: range_weights must be a one-dimensional array of {n} integers in 0..{MAX_RANGE_WEIGHT}")
+    if t.shape[0] != n:
+        raise ValueError(f"mmsa.evaluate: range_weights has {t.shape[0]} entries; a guide of {channels} channel{'s' if channels > 1 else ''} has L1 differences "
+                         f"0..{n - 1}, so {n} are expected")
+    if t.dtype.kind == "f" and not (np.isfinite(t).all() and (t == np.floor(t)).all()):
+        raise ValueError("mmsa.evaluate: range_weights holds values that are not integers")
+    if (t < 0).any() or (t > MAX_RANGE_WEIGHT).any():
+        raise ValueError(f"mmsa.evaluate: range_weights holds values outside 0..{MAX_RANGE_WEIGHT} (a tap's vote must stay below 2^20)")
+    return np.ascontiguousarray(t.astype(np.uint16))
+
+
+@torch.no_grad()
+def vote_filter(map, radius=2, *, guide=None, sigma=None, range_weights=None, weights=None, num_classes=None, hole=(), inert=None, where="all", half=False,
+                out=None, support=None):
+    """The guided vote filter of a class map (one launch, mmsa_vote_filter_u8) -> uint8 [B, H, W] on the device: the joint-bilateral weighted mode filter.
+    Roles (`num_classes`, `hole`, `inert`), the clipped (2 radius + 1)^2 window, `where`, `half` and the tie rule are `majority_filter`'s, 1 <= radius <= 16;
+    every voter q of the window of p votes for its value with lut[d(p, q)] * wq(q), and the value with the largest SUM wins.
+    `guide`: the raw uint8 frame, [B, Hg, Wg, 3], [B, Hg, Wg, 1] or [B, Hg, Wg], Hg >= H, Wg >= W (the top-left H x W is used: a padded frame needs no copy);
+    d is the L1 difference of two guide pixels, and lut comes from `sigma=` (`vote_range_table`: 256 exp(-d^2 / (2 sigma^2)), rounded) or from
+    `range_weights=` (255 G + 1 integers in 0..4096) -- exactly one of them with a guide, neither without.  `weights`: float32 [B, H, W], a confidence, margin
+    or probability map; wq = min(255, int(clamp(w, 0, 1) * 256)), so NaN, negatives and anything below 1 / 256 vote nothing.  Integers only: the same bytes on
+    every run.  With neither `guide` nor `weights` the result is `majority_filter`'s.
+        snapped = mmsa.vote_filter(pred, 8, guide=rgb, sigma=8, num_classes=C)                               # contours move to the RGB frame's edges
+        crossed = mmsa.vote_filter(pred, 4, guide=aux, sigma=6, weights=conf, num_classes=C)                 # guided by the aux frame, confident pixels count more
+        closed = mmsa.vote_filter(mmsa.suppress_small(pred, 64, num_classes=C, fill=254), 3, guide=rgb, sigma=8,
+                                  num_classes=C, hole=254, where="holes")                                    # specks take the weighted vote around them
+    `out=` (uint8, the map's shape, NOT the map); `support=` (uint32, the map's shape) receives the winning sum S_best at every target pixel and 0 elsewhere.
+    A pixel whose window holds no vote (zero weights, zeros in the table) stays.  The role and range tables are uploaded once per (content, device); with
+    `out=` (and `support=`) a later call allocates nothing and can be captured in a graph."""
+    if not _is_int(radius, 1, MAX_VOTE_RADIUS):
+        raise ValueError(f"mmsa.evaluate: radius = {radius!r}; an int in 1..{MAX_VOTE_RADIUS} is expected (the window is (2 r + 1) x (2 r + 1) pixels)")
+    radius = int(radius)
+    roles = majority_roles(num_classes, hole, inert)
+    if where not in MAJORITY_WHERE:
+        raise ValueError(f"mmsa.evaluate: where = {where!r}; \"all\" (voters and holes are rewritten) or \"holes\" is expected")
+    if where == "holes" and not (roles == MAJORITY_HOLE).any():
+        raise ValueError("mmsa.evaluate: where = \"holes\" and hole is empty; at least one byte to rewrite is expected")
+    if not isinstance(half, (bool, np.bool_)):
+        raise ValueError(f"mmsa.evaluate: half = {half!r}; True or False is expected")
+    src = _check_map(map, "map", torch.uint8, "a uint8 class map", shape_only=True)
+    B, H, W = (int(v) for v in src.shape)
+    if B * H * W == 0:
+        raise RuntimeError(f"mmsa.evaluate: an empty map {tuple(src.shape)}")
+    G, Hg, Wg, table = 0, 0, 0, None
+    if guide is None:
+        if sigma is not None or range_weights is not None:
+            raise ValueError("mmsa.evaluate: sigma= and range_weights= weigh the differences of a guide; without guide= neither is taken")
+    else:
+        if (sigma is None) == (range_weights is None):
+            raise ValueError("mmsa.evaluate: a guide takes sigma= (the Gaussian table) or range_weights= (a table of your own), exactly one of them")
+        if not isinstance(guide, torch.Tensor):
+            raise RuntimeError(f"mmsa.evaluate: guide must be a tensor, got {type(guide).__name__}")
+        if guide.dtype != torch.uint8:
+            raise RuntimeError(f"mmsa.evaluate: guide is {guide.dtype}; the raw uint8 frame is expected")
+        if guide.dim() not in (3, 4) or not guide.is_contiguous() or (guide.dim() == 4 and int(guide.shape[3]) not in (1, 3)):
+            raise RuntimeError(f"mmsa.evaluate: guide must be a contiguous [B, Hg, Wg, 3], [B, Hg, Wg, 1] or [B, Hg, Wg] tensor, got {tuple(guide.shape)}")
+        G, Hg, Wg = (int(guide.shape[3]) if guide.dim() == 4 else 1), int(guide.shape[1]), int(guide.shape[2])
+        if int(guide.shape[0]) != B or Hg < H or Wg < W:
+            raise RuntimeError(f"mmsa.evaluate: guide has shape {tuple(guide.shape)}, the map is [B, H, W] = {tuple(src.shape)}; as many frames of at least that "
+                               "size are expected (the map is the frame's top-left corner)")
+        table = vote_range_table(sigma, G) if sigma is not None else _check_range_weights(range_weights, G)
+    if weights is not None:
+        _check_map(weights, "weights", torch.float32, "a float32 confidence map", like=src, shape_only=True)
+    if out is not None:
+        _check_map(out, "out", torch.uint8, "a uint8 class map", like=src, shape_only=True)
+        if out is map:
+            raise RuntimeError("mmsa.evaluate: out is the map; a stencil cannot run in place")
+    if support is not None:
+        _check_map(support, "support", torch.uint32, "a uint32 sum map", like=src, shape_only=True)
+    _check_map(src, "map", torch.uint8, "a uint8 class map")
+    with torch.cuda.device(src.device):
+        if guide is not None:
+            if not guide.is_cuda or guide.device != src.device:
+                raise RuntimeError(f"mmsa.evaluate: guide is on {guide.device}, the map on {src.device}")
+        if weights is not None:
+            _check_map(weights, "weights", torch.float32, "a float32 confidence map", like=src)
+        if out is None:
+            out = torch.empty_like(src)
+        else:
+            _check_map(out, "out", torch.uint8, "a uint8 class map", like=src)
+            if out.data_ptr() == src.data_ptr():
+                raise RuntimeError("mmsa.evaluate: out is the map; a stencil cannot run in place")
+        if support is not None:
+            _check_map(support, "support", torch.uint32, "a uint32 sum map", like=src)
+            if support.data_ptr() in (src.data_ptr(), out.data_ptr()):
+                raise RuntimeError("mmsa.evaluate: support aliases a map; it is a plane of its own")
+        inputs = [t.data_ptr() for t in (guide, weights) if t is not None]
+        if out.data_ptr() in inputs or (support is not None and support.data_ptr() in inputs):
+            raise RuntimeError("mmsa.evaluate: out or support aliases the guide or the weights; they are planes of their own")
+        role = _table_on(_VOTE_TABLES, roles, src.device, "the role table of the vote launch")
+        lut = None if table is None else _table_on(_VOTE_TABLES, table, src.device, "the range table of the vote launch")
+        lib.call("mmsa_vote_filter_u8", src.data_ptr(), B, H, W, role.data_ptr(), radius, MAJORITY_WHERE.index(where), int(bool(half)),
+                 None if guide is None else guide.data_ptr(), Hg, Wg, G, None if lut is None else lut.data_ptr(),
+                 None if weights is None else weights.data_ptr(), out.data_ptr(), None if support is None else support.data_ptr(), ops._stream())
     return out
 
 

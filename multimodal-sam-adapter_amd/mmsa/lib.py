@@ -124,6 +124,7 @@ SIGNATURES = {
     "mmsa_run_decode_i32": [P, P, P, I, I, I, I, I, I, P, P],
     "mmsa_fill_nearest_u8": [P, I, I, I, P, I, I, P, P, P, P],
     "mmsa_majority_filter_u8": [P, I, I, I, P, I, I, I, P, P, P],
+    "mmsa_vote_filter_u8": [P, I, I, I, P, I, I, I, P, I, I, I, P, P, P, P, P],
     "mmsa_slide_argmax_eval": [P, I, I, I, I, P, P, I, I, I, I, I, P, P, I, I, P, P, P, P, I, P, P],
     "mmsa_render_u8": [P, L, L, I, I, I, P, I, I, P, I, I, I, c_double, c_double, P, P],
     "mmsa_render_denorm_f32": [P, L, L, I, I, I, P, I, I, P, I, I, I, P, P, I, I, c_double, c_double, P, P],
