@@ -684,6 +684,39 @@ int mmsa_segment_table_block(void); /* the pixels per word of segment_table's sc
 int mmsa_select_segments_u8(const unsigned char* pred, const int* ids, const unsigned char* keep, int B, int H, int W, int capacity, int fill,
                             unsigned char* out, mmsa_stream_t stream);
 
+/* --- segments tracked across frames (csrc/track.hip): persistent ids by IoU match.  Image b of one call follows image b of the call before (B parallel
+ *   streams).  ids int32 [B, H, W], count int32 [B] and records int64 [B, rows, 10] are segment_table's of the CURRENT frame, rows = its capacity R.  A segment
+ *   of either frame takes part iff its id is in [0, R); ids -1 and ids >= R take part nowhere.  inter(k, j) = the pixels with ids_cur == k and ids_prev == j;
+ *   k CONTINUES j iff 3 * inter > AREA_k + AREA_j (IoU > 1/2, strict, in 64 bits) and, with same_class = 1, CLASS_k == CLASS_j: at most one j per k and one k
+ *   per j pass (two j of one k would need inter1 + inter2 > AREA_k; the class test only removes candidates), so matches never conflict.
+ *   track_pairs: TWO launches.  The first, a lane per slot, empties the table: keys int64 [capacity] to all-ones = empty, counts int32 [capacity] to 0;
+ *     capacity a power of two, 2 .. 2^30.  (A launch where segment_pairs has two memsets: a captured sequence with the memsets was seen to replay wrongly,
+ *     cause not known -- csrc/track.hip, track_empty_kernel.)  The second, a lane per pixel, fills the table as segment_pairs does (the same device code,
+ *     csrc/pair_table.h).  Every pixel of
+ *     image b whose two ids take part forms key = ((b * rows + id_cur) << 31) | id_prev; counts[slot of key] = inter.  The slot, the probing over at most
+ *     min(128, capacity) slots and *overflow (DEVICE int, zeroed by the CALLER, added to by the pixels of the keys that found no slot) are segment_pairs'.
+ *     Which key sits in which slot depends on the schedule; the multiset of (key, count) and -- while nothing is dropped -- the set of occupied slots do not.
+ *     B * H * W < 2^31, B <= 65535, 1 <= rows, B * rows < 2^31.
+ *   track_update: keys / counts as track_pairs left them for (ids_cur, prev_ids).  The previous frame lives in the caller's buffers at FIXED addresses:
+ *     prev_ids int32 [B, H, W], prev_rows int32 [B, rows, 4] = CLASS, AREA, TRACK, AGE and prev_count int32 [B]; prev_count[b] = 0 (and prev_ids -1) is an
+ *     image without a previous frame: everything is born, nothing ends.  state int32 [B, rows, 4] = TRACK, AGE, PREV, INTER: row k < min(count[b], rows) of
+ *     a segment that continues j = TRACK of j, AGE of j + 1, j, inter(k, j); of any other = next_track[b] + (the non-continuing rows k' < k), 1, -1, 0 -- new
+ *     ids in ascending k, the raster order of the first pixel: canonical, the same bytes whatever the schedule.  Every row from min(count[b], rows) on is
+ *     (-1, 0, -1, 0).  succ int32 [B, rows]: at a previous row the current row that continues it, -1 elsewhere; prev_area int32 [B, rows]: at a continued
+ *     row AREA of its predecessor, 0 elsewhere.  stats int32 [B, 3] = continued, born, ended (the previous rows below min(prev_count[b], rows) that nothing
+ *     continues) of this frame; the same three are ADDED to totals int64 [B, 3]; next_track int32 [B] grows by `born`.  tracks int32 [B, H, W] or NULL:
+ *     TRACK of the pixel's row, -1 where its id takes part nowhere.  Then prev_ids = ids_cur, prev_rows = (CLASS, AREA, TRACK, AGE) of every row and
+ *     prev_count = count.  Four launches -- a lane per row (the rows to "unmatched"), a lane per table slot (the test; conflict-free by uniqueness), ONE
+ *     workgroup per image (a scan of the flags "not continued" in trips of track_trip() = 1024 rows with a carry, bounded by rows), a lane per pixel / row
+ *     (the carry-over).  No workgroup waits for another.  state and prev_rows 16-byte aligned; ids_cur, prev_ids and tracks are three buffers; limits as above.
+ *   A limit broken or a null pointer: MMSA_ERR_ARG with a message, before any launch. --- */
+int mmsa_track_pairs(const int* ids_cur, const int* ids_prev, int B, int H, int W, int rows, int64_t* keys, int* counts, long capacity, int* overflow,
+                     mmsa_stream_t stream);
+int mmsa_track_update(const int64_t* keys, const int* counts, long capacity, const int* ids_cur, const int* count, const int64_t* records, int B, int H, int W,
+                      int rows, int same_class, int* prev_ids, int* prev_rows, int* prev_count, int* succ, int* prev_area, int* state, int* stats,
+                      int64_t* totals, int* next_track, int* tracks, mmsa_stream_t stream);
+int mmsa_track_trip(void); /* the rows one trip of track_update's scan takes in THIS build (1024) */
+
 /* --- run-length tables (csrc/runs.hip): the runs of a map, and the map of a table.  src [B, H, W] contiguous: uint8 (a class or code map) or int32 (the ids
  *   of segment_table, -1 included; any value).  flat_b = the pixels of image b in row-major order (order 0) or column-major order (order 1: index x * H + y,
  *   the order of COCO's mask RLE).  A HEAD is index 0 and every i > 0 with flat_b[i] != flat_b[i - 1]: runs continue across line ends; one value is ONE run.

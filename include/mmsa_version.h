@@ -42,7 +42,10 @@
  *      Still 114, for the same reason: new entry mmsa_majority_filter_u8 (the majority filter of a byte map: every target pixel takes the most frequent voter
  *      value of its (2 r + 1) x (2 r + 1) window, ties kept by the own value or else resolved to the smallest, and the count that won).
  *      Still 114, for the same reason: new entry mmsa_vote_filter_u8 (the guided vote filter of a byte map: the majority filter with every vote weighted by a
- *      range table of the guide frame's L1 difference and by the voter's quantised confidence, and the sum that won). */
+ *      range table of the guide frame's L1 difference and by the voter's quantised confidence, and the sum that won).
+ *      Still 114, for the same reason: new entries mmsa_track_pairs / mmsa_track_update / mmsa_track_trip (the segments of a stream tracked across frames:
+ *      the intersections of current and previous segments in the pair table of segment_pairs, and the association by IoU > 1/2 that hands every segment a
+ *      persistent track id, its age and its predecessor, with new ids in raster order of the first pixel). */
 #ifndef MMSA_VERSION_H
 #define MMSA_VERSION_H
 #define MMSA_ABI_VERSION 114

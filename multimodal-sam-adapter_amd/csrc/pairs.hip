@@ -6,43 +6,21 @@
 // has L < C and min(pred, C) == L, and inter(p, g) = the hit pixels with root_pred == p and root_label == g.  p and g MATCH iff 3 * inter > area_p + area_g
 // (IoU > 1/2, strict, in integers); a segment has at most one match (two matches of one p would need inter1 + inter2 > area_p).
 //
-// The pair table.  keys int64 [capacity] (all-ones: empty), counts int32 [capacity], capacity a power of two.  Every hit pixel forms
+// The pair table (csrc/pair_table.h: the table, the in-wave reduction, the insert and its probe bound -- shared with csrc/track.hip).  Every hit pixel forms
 //   key = ((b * HW + root_label) << 31) | root_pred          (< 2^62: B * H * W < 2^31)
-// A wave first reduces its lanes per distinct key in registers (the form of comp_wave_add, the key's halves through readlane), PAIR_WAVE_ROUNDS = 8 rounds
-// at the most; what is pending after them goes lane by lane.  (Measured, profiles/panoptic.txt: a wave of a class map holds one to a few pairs, and 8 rounds
+// PAIR_WAVE_ROUNDS = 8 rounds of the in-wave reduction.  (Measured, profiles/panoptic.txt: a wave of a class map holds one to a few pairs, and 8 rounds
 // equal 64 there -- 34 us for two 1024 x 1024 maps -- while 2 rounds leave whole edges to contend for one slot, 128 - 156 us; on a noise map, where a wave
-// holds 64 keys and no round retires more than one lane, 8 rounds take 209 - 214 us against 226 - 232 us for 64.)  Every lane that then holds a (key, n) inserts it: slot = the top log2(capacity) bits of key * 2^64 /
-// phi, then linear probing.  ONE atomicCAS(empty -> key) per slot, and its return value alone decides: empty or the same key -- atomicAdd(counts[slot], n),
-// done; another key -- the next slot.  Keys are written once and never change, so no lane ever waits for a value another lane must write, and the loop is
-// bounded by PAIR_MAX_PROBES = 128 slots (and by the capacity): a key that finds no slot adds its n to *overflow and is dropped -- the caller must look.
-// The longest walk of a key in the measured tables is 2 slots for a class map (load 0.004), 7 for noise against noise (load 0.08) and 3 at load 0.42
-// (profiles/panoptic.txt), so a bound of 32 and one of 128 take the same time there; 128 keeps a margin for the loads near 1 that a small capacity= gives, and
-// only ends the walk through a table that is too small after 128 CAS instead of `capacity`.
+// holds 64 keys and no round retires more than one lane, 8 rounds take 209 - 214 us against 226 - 232 us for 64.)
+// PAIR_MAX_PROBES = 128.  The longest walk of a key in the measured tables is 2 slots for a class map (load 0.004), 7 for noise against noise (load 0.08)
+// and 3 at load 0.42 (profiles/panoptic.txt), so a bound of 32 and one of 128 take the same time there; 128 keeps a margin for the loads near 1 that a small
+// capacity= gives, and only ends the walk through a table that is too small after 128 CAS instead of `capacity`.
 // The atomics are device-scope (HIP's default for atomicCAS / atomicAdd on global memory: performed at L2 / memory, coherent across XCDs); the table is
 // READ by a later launch only.
-// Which key sits in which slot depends on the order of arrival; the SET of occupied slots of a linear-probing table does not (as long as nothing is
-// dropped), and neither does the multiset of (key, count).
 #include "common.h"
 #include "eval_hist.h"
 #include "code_map.h"
 #include "comp_shared.h"
-
-#ifndef PAIR_MAX_PROBES
-#define PAIR_MAX_PROBES 128                   // slots a key looks at before it is dropped into *overflow
-#endif
-#ifndef PAIR_WAVE_ROUNDS
-#define PAIR_WAVE_ROUNDS 8                    // rounds of the in-wave reduction (64: one inserting lane per distinct key, whatever the wave holds)
-#endif
-#define PAIR_EMPTY 0xffffffffffffffffull
-#define PAIR_HASH_MUL 0x9e3779b97f4a7c15ull   // 2^64 / phi, odd
-#define PAIR_MAX_LOG2 30                      // capacity <= 2^30 slots
-
-struct PairTable {
-  unsigned long long* keys;         // [capacity]
-  int* counts;                      // [capacity]
-  int* overflow;                    // [1]
-  int log2cap;                      // 1 .. 30
-};
+#include "pair_table.h"
 
 struct PairMaps {
   const unsigned char* pred;        // [B, H, W]
@@ -50,25 +28,6 @@ struct PairMaps {
   const int* root_label;
   int H, W, B;
 };
-
-__device__ __forceinline__ unsigned pair_slot(unsigned long long key, int log2cap) {      // < 2^log2cap
-  return (unsigned)((key * PAIR_HASH_MUL) >> (64 - log2cap));
-}
-
-__device__ __forceinline__ void pair_insert(const PairTable& t, unsigned long long key, int n) {
-  const unsigned mask = (1u << t.log2cap) - 1u;
-  const int probes = (int)min((unsigned)PAIR_MAX_PROBES, mask + 1u);
-  unsigned at = pair_slot(key, t.log2cap) & mask;
-  for (int p = 0; p < probes; ++p) {
-    const unsigned long long old = atomicCAS(&t.keys[at], PAIR_EMPTY, key);
-    if (old == PAIR_EMPTY || old == key) {
-      atomicAdd(&t.counts[at], n);
-      return;
-    }
-    at = (at + 1u) & mask;
-  }
-  atomicAdd(t.overflow, n);
-}
 
 // grid (cdiv(H * W, 256), B): a wave lies inside one image
 __global__ __launch_bounds__(256) void segment_pairs_kernel(PairMaps m, EvalLabel ev, PairTable t) {
@@ -82,29 +41,8 @@ __global__ __launch_bounds__(256) void segment_pairs_kernel(PairMaps m, EvalLabe
     const int rp = min(max(m.root_pred[base + i], 0), (int)HW - 1);
     key = ((unsigned long long)(base + rl) << 31) | (unsigned long long)rp;
   }
-  const unsigned lo = (unsigned)key, hi = (unsigned)(key >> 32);
-  int n = 0;
-  unsigned long long live = __ballot(pending);
-  for (int r = 0; r < PAIR_WAVE_ROUNDS && live != 0ull; ++r) {
-    const int lead = __ffsll((long long)live) - 1;
-    const unsigned llo = __builtin_amdgcn_readlane(lo, lead), lhi = __builtin_amdgcn_readlane(hi, lead);
-    const bool same = pending && lo == llo && hi == lhi;
-    const unsigned long long ms = __ballot(same);
-    if ((int)(threadIdx.x & 63u) == lead) n = (int)__popcll(ms);
-    pending = pending && !same;
-    live &= ~ms;
-  }
-  if (pending) n = 1;                                                          // beyond the rounds: lane by lane
+  const int n = pair_wave_reduce(pending, key);
   if (n > 0) pair_insert(t, key, n);
-}
-
-static inline int pair_check_table(const char* name, const void* keys, const void* counts, long capacity, int* log2cap) {
-  MMSA_CHECK_ARG(keys && counts, "%s: keys and counts are required", name);
-  int lg = 0;
-  while (lg < PAIR_MAX_LOG2 && (1l << lg) < capacity) ++lg;
-  MMSA_CHECK_ARG(capacity >= 2 && (1l << lg) == capacity, "%s: capacity = %ld; a power of two, 2 .. 2^%d slots, is expected", name, capacity, PAIR_MAX_LOG2);
-  *log2cap = lg;
-  return MMSA_OK;
 }
 
 extern "C" int mmsa_segment_pairs(const unsigned char* pred, const unsigned char* label, int Hl, int Wl, const unsigned char* lut, int C, const int* ymap,

@@ -29,6 +29,8 @@ from .evaluate import (PanopticEvaluator, PairTable, segment_pairs, panoptic_cou
                        panoptic_summary_of)  # the pair table of two root maps, TP / FP / FN and the IoU sum by class and size, PQ / SQ / RQ)
 from .evaluate import SegmentTable, segment_table, select_segments, segment_records_of  # noqa: F401  (the segments handed out: dense ids, and one record
 #                                                            per segment -- class, area, box, centroid, mean score -- by a prefix sum over the root pixels)
+from .evaluate import SegmentTracker, track_pairs, track_records_of, track_summary_of  # noqa: F401  (the segments of a stream followed across frames:
+#                                                            persistent track ids by IoU > 1/2 against the previous frame, new ids in raster order)
 from .evaluate import (RunTable, run_lengths, run_decode, runs_of_value, coco_rle_of, rle_area_of, rle_bbox_of)  # noqa: F401  (run-length tables of a class
 #                                                            map or an ids map, row-major or column-major, and the uncompressed COCO RLE of one id or class)
 from .evaluate import fill_nearest  # noqa: F401  (the holes of a class map filled from the nearest kept pixel: what suppress_small / select_segments / abstain removed)
@@ -65,4 +67,5 @@ __all__ = ["SegformerHead", "HEADS", "build_head", "register_head", "SAMAdapterb
            "boundary_distance_percentile_of", "SegmentEvaluator", "components", "component_areas", "suppress_small", "segment_counts", "segment_totals_of",
            "segment_rate_of", "segment_f_of", "PanopticEvaluator", "PairTable", "segment_pairs", "panoptic_counts", "panoptic_quality_of",
            "panoptic_summary_of", "SegmentTable", "segment_table", "select_segments", "segment_records_of", "RunTable", "run_lengths",
-           "run_decode", "runs_of_value", "coco_rle_of", "rle_area_of", "rle_bbox_of", "fill_nearest", "majority_filter", "vote_filter"]
+           "run_decode", "runs_of_value", "coco_rle_of", "rle_area_of", "rle_bbox_of", "fill_nearest", "majority_filter", "vote_filter", "SegmentTracker",
+           "track_pairs", "track_records_of", "track_summary_of"]

@@ -71,7 +71,11 @@ popcounts and a sliding column sum).  It removes salt-and-pepper pixels, straigh
 
 `vote_filter` is the same filter with weighted votes, r <= 16: a voter's vote falls with the L1 difference of its pixel of a guide frame (raw uint8, 1 or 3
 channels) from the centre's, through a range table (`vote_range_table`, or one of the caller's), and rises with its quantised confidence; the largest integer
-sum wins (mmsa_vote_filter_u8, csrc/vote.hip: one launch, a per-lane column of sums in LDS over dense value slots).  Contours snap to the guide's edges."""
+sum wins (mmsa_vote_filter_u8, csrc/vote.hip: one launch, a per-lane column of sums in LDS over dense value slots).  Contours snap to the guide's edges.
+
+`SegmentTracker` follows the segments of a `SegmentTable` along a stream: `track_pairs` fills the pair table with the intersection of every (current segment,
+previous segment) pair (mmsa_track_pairs, csrc/track.hip), and `update()` matches them by IoU > 1/2 and hands every segment a persistent track id, its age
+and its predecessor (mmsa_track_update): int32 [B, capacity, 4] per frame, new ids in raster order of the first pixel, no host sync."""
 import ctypes
 import math
 import warnings
@@ -2735,6 +2739,251 @@ def select_segments(pred, table, keep, fill=255, out=None, nearest=None):
         if nearest is not None:
             fill_nearest(out, hole=int(fill), cap=nearest, out=out)
     return out
+
+
+# ---- segments tracked across frames: persistent ids by IoU match (csrc/track.hip) ----
+TRACK_FIELDS = ("TRACK", "AGE", "PREV", "INTER")
+TRACK, AGE, PREV, INTER = range(4)
+TRACK_STATS = ("continued", "born", "ended")
+TRACK_TRIP = 1024                  # csrc/track.hip TRACK_TRIP: the rows one trip of the assign scan takes
+TRACK_DTYPE = np.dtype(SEGMENT_DTYPE.descr + [("track", np.int64), ("age", np.int64), ("prev", np.int64), ("iou", np.float64)])
+
+
+def _check_ids(t, name, like=None):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 3 or not t.is_contiguous() or t.numel() == 0:
+        raise RuntimeError(f"mmsa.evaluate: {name} must be a contiguous int32 [B, H, W] tensor (the ids of a SegmentTable)")
+    if like is not None and (t.shape != like.shape or t.device != like.device):
+        raise RuntimeError(f"mmsa.evaluate: {name} is {tuple(t.shape)} on {t.device}, ids_cur {tuple(like.shape)} on {like.device}")
+    return t
+
+
+@torch.no_grad()
+def track_pairs(ids_cur, ids_prev, rows, capacity=None, table=None):
+    """The intersections of the (current segment, previous segment) pairs of two ids maps, int32 [B, H, W] each (two launches: the table emptied, then a lane
+    per pixel; mmsa_track_pairs) -> PairTable on the device.  Every pixel whose two ids lie in [0, rows) adds 1 to the pair of its image: key = ((b * rows + id_cur)
+    << 31) | id_prev.  `capacity` / `table=` as in `segment_pairs`: a new table of the default capacity (the next power of two >= B * H * W / 2) whose
+    overflow word starts at 0, or the caller's, emptied and filled, its overflow word ADDED to.  The table's shape is (B, 1, rows): `host()` then gives
+    (image, current id, previous id, inter), sorted."""
+    if capacity is not None:
+        capacity = check_pair_capacity(capacity)
+    ids_cur = _check_ids(ids_cur, "ids_cur")
+    ids_prev = _check_ids(ids_prev, "ids_prev", ids_cur)
+    B, H, W = (int(v) for v in ids_cur.shape)
+    if not _is_int(rows, 1, (1 << 31) - 1):
+        raise ValueError(f"mmsa.evaluate: rows = {rows!r}; the rows per image of the segment table (>= 1) are expected")
+    _check_rows("mmsa.evaluate", B, int(rows), "rows")
+    with torch.cuda.device(ids_cur.device):
+        if table is None:
+            table = PairTable.empty(default_pair_capacity(B * H * W) if capacity is None else capacity, ids_cur.device)
+        else:
+            if not isinstance(table, PairTable):
+                raise RuntimeError(f"mmsa.evaluate: table= takes an mmsa.evaluate.PairTable, got {type(table).__name__}")
+            table._check(ids_cur.device)
+            if capacity is not None and capacity != table.capacity:
+                raise RuntimeError(f"mmsa.evaluate: capacity={capacity} with a table of {table.capacity} slots")
+        table.shape = (B, 1, int(rows))
+        lib.call("mmsa_track_pairs", ids_cur.data_ptr(), ids_prev.data_ptr(), B, H, W, int(rows), table.keys.data_ptr(), table.counts.data_ptr(), table.capacity,
+                 table.overflow.data_ptr(), ops._stream())
+    return table
+
+
+def _track_state(state, rows=None):
+    s = np.asarray(state)
+    if s.ndim < 2 or s.shape[-1] != len(TRACK_FIELDS) or s.dtype.kind not in "iu" or (rows is not None and s.shape[-2] != rows):
+        raise ValueError(f"mmsa.evaluate: a tracker's state is an integer [..., rows, {len(TRACK_FIELDS)}] array ({', '.join(TRACK_FIELDS)}), got {s.dtype} {s.shape}")
+    return s.astype(np.int64, copy=False)
+
+
+def track_records_of(records, count, state, prev_area, scored=True, image=0):
+    """The host reading of one image's rows: `segment_records_of(records, count)` with 'track', 'age', 'prev' (the predecessor's id in the previous frame, -1
+    at birth) and 'iou' = INTER / (AREA + the predecessor's AREA - INTER) in float64 from those integers, NaN at birth.  state integer [rows, 4], prev_area
+    integer [rows] as the tracker holds them for this image."""
+    out_seg = segment_records_of(records, count, scored, image)
+    s = _track_state(state, np.asarray(records).shape[0])
+    pa = np.asarray(prev_area)
+    if pa.shape != s.shape[:1] or pa.dtype.kind not in "iu":
+        raise ValueError(f"mmsa.evaluate: prev_area is an integer [{s.shape[0]}] array (one previous area per row), got {pa.dtype} {pa.shape}")
+    n = len(out_seg)
+    s, pa = s[:n], pa[:n].astype(np.int64)
+    out = np.zeros(n, dtype=TRACK_DTYPE)
+    for name in SEGMENT_DTYPE.names:
+        out[name] = out_seg[name]
+    out["track"], out["age"], out["prev"] = s[:, TRACK], s[:, AGE], s[:, PREV]
+    union = (out["area"] + pa - s[:, INTER]).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["iou"] = np.where(s[:, PREV] >= 0, s[:, INTER] / union, np.nan)
+    return out
+
+
+def track_summary_of(state, totals):
+    """state integer [B, rows, 4] and totals integer [B, 3] -> dict(alive = the rows with a track, born / continued / ended = the totals over the images,
+    mean_age = the mean AGE of the rows alive in float64, NaN without one)."""
+    s = _track_state(state)
+    t = np.asarray(totals)
+    if t.shape[-1:] != (len(TRACK_STATS),) or t.dtype.kind not in "iu":
+        raise ValueError(f"mmsa.evaluate: a tracker's totals are an integer [..., 3] array ({', '.join(TRACK_STATS)}), got {t.dtype} {t.shape}")
+    t = t.astype(np.int64).reshape(-1, len(TRACK_STATS)).sum(0)
+    live = s[..., TRACK] >= 0
+    alive = int(live.sum())
+    return dict(alive=alive, continued=int(t[0]), born=int(t[1]), ended=int(t[2]), mean_age=float(s[..., AGE][live].sum()) / alive if alive else float("nan"))
+
+
+class SegmentTracker:
+    """Follows the segments of one SegmentTable along a stream: image b of one `table.update()` follows image b of the one before.  `update()`, called after
+    `table.update(...)`, matches the table's segments with those of the previous frame -- k continues j iff 3 * inter > AREA_k + AREA_j (IoU > 1/2, strict)
+    and, with same_class=True, their classes agree; at most one partner on either side -- and fills `state` int32 [B, capacity, 4] = TRACK, AGE, PREV, INTER
+    per row: the predecessor's track id and AGE + 1, or a NEW id `next_track[b]` + (the non-continuing rows before it) with AGE 1, PREV -1, INTER 0; the rows
+    from min(count, capacity) on are (-1, 0, -1, 0).  `stats` int32 [B, 3] = continued, born, ended of the frame, ADDED to `totals` int64 [B, 3]
+    (`mmsa.dist.allreduce_counts(tracker.totals)` sums them over ranks); `next_track` int32 [B]; tracks=True: `tracks` int32 [B, H, W], the track id of
+    every pixel's segment, -1 elsewhere (an int32 map as `ids`: `run_lengths` takes it).  A segment whose id is beyond the table's rows takes part nowhere.
+    The buffers are sized by the table's shape and capacity at the first update() and kept: a later update() allocates nothing and syncs nothing, and the
+    previous frame lives at fixed addresses, so a captured table.update + tracker.update advances one frame per replay.  `pair_capacity` = the slots of the
+    pair table (a power of two; None: `default_pair_capacity(B * H * W)`); the pixels of pairs that found no slot are ADDED to its overflow word, which
+    `reset()` zeroes -- a tracker that overflowed once has lost matches, and `host` / `segments_info` / `summary` refuse to report from it.
+    The device tensors speak of the table as the last tracker.update() saw it: read them before the table is filled again."""
+
+    def __init__(self, table, same_class=True, pair_capacity=None, tracks=False):
+        who = "mmsa.SegmentTracker"
+        if not isinstance(table, SegmentTable):
+            raise RuntimeError(f"{who}: table takes an mmsa.evaluate.SegmentTable, got {type(table).__name__}")
+        for name, v in (("same_class", same_class), ("tracks", tracks)):
+            if not isinstance(v, (bool, np.bool_)):
+                raise ValueError(f"{who}: {name} = {v!r}; True or False is expected")
+        self.table, self.same_class, self.with_tracks = table, bool(same_class), bool(tracks)
+        self.pair_capacity = None if pair_capacity is None else check_pair_capacity(pair_capacity, who)
+        self.shape = self.rows = None        # (B, H, W) and the rows per image the buffers were made for
+        self.pairs = self.state = self.stats = self.totals = self.next_track = self.tracks = None
+        self.prev_ids = self.prev_rows = self.prev_count = self.succ = self.prev_area = None
+
+    def _make(self):
+        t = self.table
+        B, H, W = t.shape
+        rows, device = int(t.records.shape[1]), t.ids.device
+        if _capturing(device):
+            raise RuntimeError("mmsa.SegmentTracker: the buffers cannot be allocated during a graph capture: run one update() before capturing")
+        _check_library("segment tracker", TRACK_TRIP=lib.raw.mmsa_track_trip)
+        i32 = dict(dtype=torch.int32, device=device)
+        self.pairs = PairTable.empty(default_pair_capacity(B * H * W) if self.pair_capacity is None else self.pair_capacity, device)
+        self.pairs.shape = (B, 1, rows)
+        self.state = torch.tensor([-1, 0, -1, 0], **i32).repeat(B, rows, 1)
+        self.stats, self.totals = torch.zeros(B, 3, **i32), torch.zeros(B, 3, dtype=torch.int64, device=device)
+        self.next_track, self.prev_count = torch.zeros(B, **i32), torch.zeros(B, **i32)
+        self.prev_ids, self.prev_rows = torch.full((B, H, W), -1, **i32), torch.zeros(B, rows, 4, **i32)
+        self.succ, self.prev_area = torch.full((B, rows), -1, **i32), torch.zeros(B, rows, **i32)
+        self.tracks = torch.full((B, H, W), -1, **i32) if self.with_tracks else None
+        self.shape, self.rows = (B, H, W), rows
+
+    @torch.no_grad()
+    def update(self):
+        """Associate the table's current frame with the previous one (six launches: mmsa_track_pairs, mmsa_track_update) -> self."""
+        t = self.table
+        t._filled()
+        with torch.cuda.device(t.ids.device):
+            if self.shape is None:
+                self._make()
+            if t.shape != self.shape or int(t.records.shape[1]) != self.rows or t.ids.device != self.state.device:
+                raise RuntimeError(f"mmsa.SegmentTracker: the table holds a {t.shape} batch of {int(t.records.shape[1])} rows on {t.ids.device}, the tracker follows "
+                                   f"{self.shape} of {self.rows} rows on {self.state.device}: a stream keeps its shape (make another tracker for another one)")
+            B, H, W = self.shape
+            p = self.pairs
+            lib.call("mmsa_track_pairs", t.ids.data_ptr(), self.prev_ids.data_ptr(), B, H, W, self.rows, p.keys.data_ptr(), p.counts.data_ptr(), p.capacity,
+                     p.overflow.data_ptr(), ops._stream())
+            lib.call("mmsa_track_update", p.keys.data_ptr(), p.counts.data_ptr(), p.capacity, t.ids.data_ptr(), t.count.data_ptr(), t.records.data_ptr(), B, H, W,
+                     self.rows, int(self.same_class), self.prev_ids.data_ptr(), self.prev_rows.data_ptr(), self.prev_count.data_ptr(), self.succ.data_ptr(),
+                     self.prev_area.data_ptr(), self.state.data_ptr(), self.stats.data_ptr(), self.totals.data_ptr(), self.next_track.data_ptr(),
+                     None if self.tracks is None else self.tracks.data_ptr(), ops._stream())
+        return self
+
+    @torch.no_grad()
+    def reset(self, b=None):
+        """Forget the previous frame of image b, or of every image (None): its next frame is a first frame -- everything is born, nothing ends -- and its
+        track ids start at 0 again.  `totals` stay.  reset() of every image also zeroes the pair table's overflow word.  No host sync."""
+        if self.shape is None:
+            return self
+        B = self.shape[0]
+        if b is not None and not _is_int(b, 0, B - 1):
+            raise ValueError(f"mmsa.SegmentTracker: b = {b!r}; an image index 0..{B - 1} (or None: every image) is expected")
+        at = slice(None) if b is None else slice(int(b), int(b) + 1)
+        self.prev_ids[at].fill_(-1)
+        self.prev_count[at].zero_()
+        self.next_track[at].zero_()
+        if b is None:
+            self.pairs.overflow.zero_()
+        return self
+
+    def _ready(self):
+        if self.shape is None:
+            raise RuntimeError("mmsa.SegmentTracker: nothing was tracked yet: call update()")
+
+    def overflow(self):
+        """The pixels of (current, previous) pairs that found no slot of the pair table since the last reset() (one device word; a host sync): 0, or the
+        matches of some frame are incomplete."""
+        self._ready()
+        return int(self.pairs.overflow.item())
+
+    def _complete(self):
+        """-> count [B] on the host, after both overflow checks."""
+        lost = self.overflow()
+        if lost:
+            raise RuntimeError(f"mmsa.SegmentTracker: the pair table of {self.pairs.capacity} slots overflowed ({lost} pixels of (current, previous) pairs were "
+                               "dropped, so matches are missing): make the SegmentTracker with a larger pair_capacity= and reset()")
+        count = self.table.count.cpu().numpy()
+        for i in range(self.shape[0]):
+            if count[i] > self.rows:
+                raise _overflow_error("mmsa.SegmentTracker", i, int(count[i]), self.rows, "listed segments", "the records of the last", "make the SegmentTable")
+        return count
+
+    def host(self, b=None):
+        """The tracked segments on the host (`track_records_of`) -> a numpy structured array with the fields of `SegmentTable.host` and 'track', 'age',
+        'prev', 'iou'; of image `b`, or of every image in turn.  RuntimeError naming pair_capacity= where the pair table overflowed, naming the table's
+        capacity= where an image has more segments than rows."""
+        self._ready()
+        B = self.shape[0]
+        if b is not None and not _is_int(b, 0, B - 1):
+            raise ValueError(f"mmsa.SegmentTracker: b = {b!r}; an image index 0..{B - 1} (or None: every image) is expected")
+        count = self._complete()
+        records, state, prev_area = self.table.records.cpu().numpy(), self.state.cpu().numpy(), self.prev_area.cpu().numpy()
+        parts = [track_records_of(records[i], count[i], state[i], prev_area[i], self.table.scored, i) for i in (range(B) if b is None else [int(b)])]
+        return parts[0] if len(parts) == 1 else np.concatenate(parts)
+
+    def segments_info(self, b, masks=False):
+        """`SegmentTable.segments_info(b, masks)` with 'track_id' and 'age' added to every dict."""
+        rows = self.host(int(b))
+        info = self.table.segments_info(int(b), masks=masks)
+        for d, s in zip(info, rows):
+            d["track_id"], d["age"] = int(s["track"]), int(s["age"])
+        return info
+
+    @torch.no_grad()
+    def keep(self, min_age=None, max_age=None, tracks=None):
+        """Which rows pass -> uint8 [B, capacity] on the device (1: keep), the format of `SegmentTable.keep`: min_age <= AGE < max_age and TRACK among
+        `tracks` (a list of track ids).  Torch operations on `state`: no host sync.  Rows without a track are 0.  `table.keep(...) & tracker.keep(min_age=3)`
+        through `select_segments` drops what has not persisted for three frames."""
+        self._ready()
+        age, track = self.state[..., AGE], self.state[..., TRACK]
+        ok = track >= 0
+        for name, v in (("min_age", min_age), ("max_age", max_age)):
+            if v is not None and not _is_int(v, 1, (1 << 31) - 1):
+                raise ValueError(f"mmsa.SegmentTracker: {name} = {v!r}; a number of frames >= 1 is expected")
+        if min_age is not None:
+            ok = ok & (age >= int(min_age))
+        if max_age is not None:
+            ok = ok & (age < int(max_age))
+        if tracks is not None:
+            ts = [tracks] if _is_int(tracks, 0, (1 << 31) - 1) else list(tracks)
+            if not ts or any(not _is_int(v, 0, (1 << 31) - 1) for v in ts):
+                raise ValueError(f"mmsa.SegmentTracker: tracks = {tracks!r}; a list of track ids >= 0 is expected")
+            among = torch.zeros_like(ok)
+            for v in sorted(set(int(v) for v in ts)):
+                among = among | (track == v)
+            ok = ok & among
+        return ok.to(torch.uint8)
+
+    def summary(self):
+        """`track_summary_of` of the device tensors: tracks alive in the last frame, born / continued / ended over all frames and images, mean age."""
+        self._ready()
+        self._complete()
+        return track_summary_of(self.state.cpu().numpy(), self.totals.cpu().numpy())
 
 
 # ---- nearest-label fill: the holes of a map take the value of the nearest kept pixel (csrc/fill.hip; DESIGN.md section 4) ----

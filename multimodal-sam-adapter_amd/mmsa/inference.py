@@ -429,6 +429,19 @@ def _check_segment_table_call(segment_table, return_map, what):
                            "stores none (drop return_map=)")
 
 
+def _check_tracker_call(tracker, segment_table, what):
+    """`tracker=` of SlideRunner.run: a SegmentTracker, together with `segment_table=` -- the tracker's own table, which the frame fills first."""
+    if tracker is None:
+        return
+    from .evaluate import SegmentTracker
+    if not isinstance(tracker, SegmentTracker):
+        raise RuntimeError(f"mmsa.{what}: tracker= takes an mmsa.evaluate.SegmentTracker, got {type(tracker).__name__}")
+    if segment_table is None:
+        raise RuntimeError(f"mmsa.{what}: tracker= needs segment_table= (the tracker's own SegmentTable: the frame fills it, then the tracker follows it)")
+    if tracker.table is not segment_table:
+        raise RuntimeError(f"mmsa.{what}: tracker= is bound to another SegmentTable than segment_table= (pass tracker.table)")
+
+
 def _check_labels(labels, evaluator, *binned):
     """`labels=` feed an evaluator, a calibration, a selective evaluator or several of them; an evaluator needs them."""
     if (labels is None) != (evaluator is None) and not (labels is not None and any(b is not None for b in binned)):
@@ -464,6 +477,7 @@ class MapOptions:
     segments: object = None      # the mmsa.evaluate.SegmentEvaluator the stored map is counted into, or None
     panoptic: object = None      # the mmsa.evaluate.PanopticEvaluator the stored map is counted into, or None
     segment_table: object = None # the mmsa.evaluate.SegmentTable filled from the stored map (and the confidence / score / probs[0] next to it), or None
+    tracker: object = None       # the mmsa.evaluate.SegmentTracker of `segment_table` (SlideRunner.run alone: a stream has frames), or None
     boundary: object = None      # the mmsa.evaluate.BoundaryEvaluator the stored map is counted into, or None
 
     @classmethod
@@ -478,16 +492,18 @@ class MapOptions:
         return cls(conf=confidence, it=it, kind=kind, one_pass=one_pass, topk=topk).with_call(what, **per_call)
 
     def with_call(self, what, labels=None, evaluator=None, case=None, calibration=None, selective=None, fused=None, return_map=True, topk_evaluator=None,
-                  segments=None, panoptic=None, segment_table=None, boundary=None):
+                  segments=None, panoptic=None, segment_table=None, tracker=None, boundary=None):
         _check_topk_call(self.topk, topk_evaluator, labels, calibration, selective, fused, return_map, what)
         _check_boundary_call(boundary, labels, return_map, what)
         _check_segments_call(segments, labels, return_map, what)
         _check_panoptic_call(panoptic, labels, return_map, what)
         _check_segment_table_call(segment_table, return_map, what)
+        _check_tracker_call(tracker, segment_table, what)
         for kw, name, owner in (("calibration", "Calibration", calibration), ("selective", "SelectiveEvaluator", selective)):
             _check_binned(kw, name, owner, labels, self.conf, what, fused, return_map)
         return dataclasses.replace(self, labels=labels, evaluator=evaluator, case=case, calibration=calibration, selective=selective, fused=fused,
-                                   return_map=return_map, topk_evaluator=topk_evaluator, boundary=boundary, segments=segments, panoptic=panoptic, segment_table=segment_table)
+                                   return_map=return_map, topk_evaluator=topk_evaluator, boundary=boundary, segments=segments, panoptic=panoptic, segment_table=segment_table,
+                                   tracker=tracker)
 
     def at(self, size, device, what, make=True):
         """`make=False`: a plan's `conf=` / `topk=`, which are the buffers themselves -- True / K make none there."""
@@ -535,6 +551,8 @@ class MapOptions:
             self.panoptic.add(out, self.labels, case=self.case)
         if self.segment_table is not None:      # needs no labels: the components of the stored map, then mmsa_segment_table
             self.segment_table.update(out, values=self.topk.probs[0] if self.topk is not None else self.conf)
+        if self.tracker is not None:            # behind its table: the frame's segments against the previous frame's (mmsa_track_pairs, mmsa_track_update)
+            self.tracker.update()
 
 
 @dataclasses.dataclass(frozen=True)
@@ -1487,7 +1505,7 @@ class SlideRunner:
 
     @torch.no_grad()
     def run(self, frame=None, labels=None, evaluator=None, case=None, fused=None, return_map=True, calibration=None, selective=None, topk_evaluator=None,
-            segments=None, panoptic=None, segment_table=None, boundary=None):
+            segments=None, panoptic=None, segment_table=None, tracker=None, boundary=None):
         """Enqueue one frame on the current stream (asynchronous) -> FrameResult; `.outputs()` = (class map uint8 [B, H, W], uncovered-pixel flag) once the
         attention logit guard of this pass has been inspected.  The inspection costs one 4 * depth-byte copy per `check_every` frames and an event wait,
         no device sync; a frame that scored logits beyond the fp16 range raises mmsa.chains.AttentionRangeError from outputs() -- or from the next run(),
@@ -1506,8 +1524,13 @@ class SlideRunner:
         `segments=` (mmsa.evaluate.SegmentEvaluator, made the same way; needs `labels=`; refused with return_map=False): the segment counts of the frame's
         stored map are ADDED to it on device, under the same terms.
         `panoptic=` (mmsa.evaluate.PanopticEvaluator, made the same way; needs `labels=`; refused with return_map=False): the panoptic counts of the frame's
-        stored map are ADDED to it on device, under the same terms."""
-        o = self.options.with_call("SlideRunner.run", labels, evaluator, case, calibration, selective, fused, return_map, topk_evaluator, segments=segments, boundary=boundary, panoptic=panoptic, segment_table=segment_table)
+        stored map are ADDED to it on device, under the same terms.
+        `tracker=` (mmsa.evaluate.SegmentTracker; only together with `segment_table=`, which must be the tracker's own table): `tracker.update()` runs behind
+        the table's update, so consecutive run() calls are the frames of the tracker's stream; a frame that has to be run again has been tracked -- reset
+        the tracker or accept the repeated frame (every segment continues itself).  None: exactly the launches made without it.  The single-frame class-map
+        entries do not take it."""
+        o = self.options.with_call("SlideRunner.run", labels, evaluator, case, calibration, selective, fused, return_map, topk_evaluator, segments=segments, boundary=boundary, panoptic=panoptic, segment_table=segment_table,
+                                   tracker=tracker)
         o = o.at(self.out.shape, self.device, "SlideRunner.run")
         if frame is None:
             frame = self.frame

@@ -118,6 +118,9 @@ SIGNATURES = {
     "mmsa_segment_table": [P, I, I, I, P, P, P, I, I, P, P, P, I, I, I, P, P, P, P, P],
     "mmsa_segment_table_block": [],
     "mmsa_select_segments_u8": [P, P, P, I, I, I, I, I, P, P],
+    "mmsa_track_pairs": [P, P, I, I, I, I, P, P, L, P, P],
+    "mmsa_track_update": [P, P, L, P, P, P, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P],
+    "mmsa_track_trip": [],
     "mmsa_run_lengths_u8": [P, I, I, I, I, I, P, P, P, P, P],
     "mmsa_run_lengths_i32": [P, I, I, I, I, I, P, P, P, P, P],
     "mmsa_run_lengths_block": [I],
